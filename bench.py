@@ -3,7 +3,8 @@
 
 One "step" = one pass of the hot path (Discretizer.discretize + get_constraint_terms + solve_OPT of
 the reference, one SCP iteration) over every satellite of the batch, inputs resident in HBM.
-Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".
+Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement".  A plain run measures the headline only (set-up, warm-up,
+the timed steps, the line); --full adds the secondary measurements, --dump-outputs DIR writes the last step's results.
 
 `python bench.py --gpus N` starts N ranks itself (torch.distributed.run, one process per GPU, before this process has
 touched a GPU); under an outer launcher (WORLD_SIZE set) it is one of the ranks."""
@@ -27,7 +28,7 @@ WORKLOADS = {            # BASELINE.json configs: name -> (satellites per GPU, n
     "S4096_K100_scp2": (4096, 100, 2), # configs[3]: 2 SCP iterations with nonlinear re-rollout (control.py:166,183-227)
     "S8192_K30": (8192, 30, 1),        # configs[4] per GPU (65,536 over 8)
 }
-DEFAULT_SINGLE = "S4096_K30"      # the same per-GPU work at every N (weak scaling); configs[4]'s 8192 per GPU rides along as `also` when N > 1
+DEFAULT_SINGLE = "S4096_K30"      # the same per-GPU work at every N (weak scaling); configs[4]'s 8192 per GPU rides along as `also` when N > 1 (--full)
 F64_VALU_PEAK_TFLOPS = 78.6     # MI355X fp64 vector peak
 FLOP_PER_NODE_ITER = 18e3       # factorisation 8.7k + 8-channel sweeps 7k + node-parallel phases 2.4k
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md chip table
@@ -165,6 +166,29 @@ def measure(runner, steps, warmup, world):
         elapsed = float(tt.item())
     solve_ms = float(np.mean([a.elapsed_time(b) for a, b in runner.solve_events]))
     return elapsed, solve_ms
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(runner, status, iters, kkt, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step (the last SCP iteration's solve: X, U,
+    nu, tf, status with the discretisation's folded in as in solver_stats, iterations, KKT residual) as float64 .npy files,
+    one per array (with N > 1 every rank writes its own block, <name>.rank<r>.npy).  Above 64 MB in all, a fixed seeded
+    sample of satellites is written instead, and its indices as satellite_index.npy."""
+    arrays = {"X": runner.d_X.cpu().numpy(), "U": runner.d_U.cpu().numpy(), "NU": runner.d_NU.cpu().numpy(),
+              "tf": runner.d_tfo.cpu().numpy(), "status": status, "iters": iters, "kkt": kkt}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    S = runner.S
+    per_satellite = sum(a.nbytes for a in arrays.values()) / S
+    if per_satellite * S > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(S, int(DUMP_LIMIT_BYTES // (per_satellite + 8)), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["satellite_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v)
 
 
 def _committed_counters(fname, workload, kernel):
@@ -386,11 +410,17 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
-                    help=f"default: {DEFAULT_SINGLE} per GPU at every N (with N > 1 also S8192_K30 per GPU, reported under `also`)")
+                    help=f"default: {DEFAULT_SINGLE} per GPU at every N (with N > 1 and --full also S8192_K30 per GPU, reported under `also`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra S64_K30 measurement of the default run")
+    ap.add_argument("--no-also", action="store_true", help="skip the extra workloads, host-pointer and closed-loop measurements of a --full run")
     ap.add_argument("--cpu-sample", type=int, default=256, help="satellites solved by the CPU oracle")
     ap.add_argument("--solve-flags", type=int, default=0, help="mpcx_solve_opts.flags of the measured solves (64: the time-parallel kernel; profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: the host-pointer entry (value_pcie), the index launch "
+                         "order, the other BASELINE workloads, the closed loop, the CPU oracle baseline and the trajectory error against it "
+                         "(with N > 1: configs[4]'s 8192 satellites per GPU); --no-also / --no-cpu-baseline trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -422,8 +452,10 @@ def main():
     stats = torch.tensor([float(((status == 0) | (status == 7)).sum()), float(S)], dtype=torch.float64,
                          device="cpu" if (world > 1 and dist.get_backend() == "gloo") else "cuda")
     if world > 1: dist.all_reduce(stats)
+    if args.dump_outputs:
+        dump_outputs(run, status, iters, kkt, args.dump_outputs, rank, world)
     also_multi = None
-    if world > 1 and not args.no_also and workload == DEFAULT_SINGLE:
+    if args.full and world > 1 and not args.no_also and workload == DEFAULT_SINGLE:
         # BASELINE configs[4] (65 536 satellites over 8 GPUs = 8192 per GPU) by every rank in the same run, timed the same way
         # (barriers, slowest rank); the headline keeps the per-GPU work of the N = 1 line so that the N = 1, 2, 4, 8 values are
         # one weak-scaling curve
@@ -459,8 +491,8 @@ def main():
             out["scp_iterations_per_s"] = value * n_scp
         h = run.host
         # device results of the timed steps (first SCP iteration's inputs are the host arrays only when n_scp == 1)
-        dev_res = (run.d_X.cpu().numpy(), run.d_U.cpu().numpy(), run.d_tfo.cpu().numpy(), status) if n_scp == 1 else None
-        if world == 1 and not args.no_also:
+        dev_res = (run.d_X.cpu().numpy(), run.d_U.cpu().numpy(), run.d_tfo.cpu().numpy(), status) if args.full and n_scp == 1 else None
+        if args.full and world == 1 and not args.no_also:
             out["host_pointer_entry"] = host_pointer_rate(h, S if n_scp == 1 else S / n_scp, local_rank)
             # SURVEY 8(d)'s metric with H2D of the inputs and D2H of the results inside the timed region, ordinary numpy
             # arrays in and out (what the drop-in Optimizer passes): beside `value`, never instead of it
@@ -472,7 +504,7 @@ def main():
             run.opts.flags = 0
             out["index_launch_order"] = {"value": S * max(2, args.steps // 2) / ei, "ms_per_step": ei / max(2, args.steps // 2) * 1e3,
                                          "solve_kernel_ms": si}
-        if world == 1 and not args.no_also and workload == DEFAULT_SINGLE:
+        if args.full and world == 1 and not args.no_also and workload == DEFAULT_SINGLE:
             del run
             torch.cuda.empty_cache()
             out["also"] = {
@@ -490,7 +522,7 @@ def main():
             out["closed_loop"]["S64_time_parallel"] = closed_loop(64, local_rank, time_parallel=True)
             out["also"]["api_devices8"] = api_devices8_overhead(local_rank)
         if also_multi: out["also"] = also_multi
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], err = cpu_baseline(h["xbar"], h["ubar"], h["tfbar"], h["consts"], h["r_des"], args.cpu_sample, dev_res)
             if err: out["trajectory_error_vs_cpu_oracle"] = err
         print(json.dumps(with_summary(out)), flush=True)

@@ -298,7 +298,7 @@ def test_bench_two_ranks_launched_as_child_processes():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -309,6 +309,28 @@ def test_bench_two_ranks_launched_as_child_processes():
     assert a4["satellites_total"] == 16384 and a4["converged"] == a4["of"] and a4["value"] > 0
     assert out["scaling"] == "weak" and out["solver"]["converged"] == out["solver"]["of"] == 8192
     assert out["value"] > 0 and abs(out["value"] - 8192 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"]
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) measures the headline only and, with --dump-outputs, writes the last timed step's
+    results: the solver's arrays for every satellite of the workload, float64, every problem solved."""
+    import json
+    import subprocess
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "S64_K30", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert abs(out["value"] - 64 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+    assert not {"also", "closed_loop", "cpu_baseline", "host_pointer_entry", "value_pcie"} & set(out)
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in ("X", "U", "NU", "tf", "status", "iters", "kkt")}
+    assert all(v.dtype == np.float64 for v in d.values())
+    assert d["X"].shape == (64, 7, 30) and d["U"].shape == (64, 3, 30) and d["NU"].shape == (64, 7, 30) and d["tf"].shape == (64,)
+    assert np.isin(d["status"], (0, 7)).all() and (d["kkt"] <= 1e-8).all() and (d["iters"] > 0).all() and (d["tf"] > 0).all()
+    assert np.linalg.norm(d["U"], axis=1).max() <= 5 + 1e-6 and not os.path.exists(tmp_path / "satellite_index.npy")
 
 
 @pytest.mark.parametrize("K,tf,r_des", [(30, 1.0, 1.5), (30, 2.0, 1.2), (60, 2.0, 1.5), (30, 1.0, 1.05)])

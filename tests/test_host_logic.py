@@ -339,3 +339,39 @@ def test_bench_line_carries_its_summary_ahead_of_the_lists():
     # the CPU quota of the process's cgroup: a number of CPUs or None, never an exception
     q = bench.cpu_quota()
     assert q is None or q > 0
+
+
+def test_bench_dump_outputs_layout_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 .npy per result array of the last step; above the size limit the same fixed
+    seeded sample of satellites from every array (and its indices), below it everything; with N > 1 a file per rank."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import bench
+
+    class Host:                                            # stands in for a device tensor: .cpu().numpy()
+        def __init__(self, a): self.a = a
+        def cpu(self): return self
+        def numpy(self): return self.a
+
+    S, K = 96, 30
+    rng = np.random.default_rng(1)
+    r = type("R", (), {})()
+    r.S = S
+    r.d_X, r.d_U, r.d_NU = (Host(rng.standard_normal((S, n, K))) for n in (7, 3, 7))
+    r.d_tfo = Host(rng.random(S))
+    status, iters, kkt = np.zeros(S, np.int32), np.arange(S, dtype=np.int32), rng.random(S)
+    bench.dump_outputs(r, status, iters, kkt, str(tmp_path / "all"), 0, 1)
+    d = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in ("X", "U", "NU", "tf", "status", "iters", "kkt")}
+    assert all(v.dtype == np.float64 for v in d.values()) and not (tmp_path / "all" / "satellite_index.npy").exists()
+    assert np.array_equal(d["X"], r.d_X.a) and np.array_equal(d["NU"], r.d_NU.a) and np.array_equal(d["iters"], iters)
+    per_sat = 8 * (17 * K + 4)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40 * per_sat)
+    for rep in ("a", "b"):
+        bench.dump_outputs(r, status, iters, kkt, str(tmp_path / rep), 1, 2)
+    idx = np.load(tmp_path / "a" / "satellite_index.rank1.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "satellite_index.rank1.npy"))      # the same sample every run
+    assert 0 < len(idx) < 40 and np.all(np.diff(idx) > 0) and idx.max() < S
+    total = sum(os.path.getsize(p) - 128 for p in (tmp_path / "a").iterdir())             # (.npy header: 128 bytes)
+    assert total <= 40 * per_sat
+    i = idx.astype(int)
+    assert np.array_equal(np.load(tmp_path / "a" / "U.rank1.npy"), r.d_U.a[i]) and np.array_equal(np.load(tmp_path / "a" / "iters.rank1.npy"), iters[i])
