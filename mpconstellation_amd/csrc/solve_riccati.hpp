@@ -627,17 +627,24 @@ __device__ __forceinline__ bool riccati_factor(const Sat &s, SatData &sd, Scratc
 }
 #endif
 #else
+template <bool B> struct BoolC { static constexpr bool value = B; };     // a compile-time flag passed to a generic lambda
+// A value the compiler may not look through (an empty asm that "changes" the register): a lane-dependent choice of a store's
+// address stays a select.  Without it the compiler splits the fused sweep's two stores (channel slot or sink) into exec-mask
+// regions of their own -- saveexec / restore pairs and branches in every node of the factorisation loop.
+template <typename T> __device__ __forceinline__ T opaque(T v) { asm("" : "+v"(v)); return v; }
+
 // Backward Riccati sweep: factorisation (DESIGN.md "Solver algorithm").  Returns false on breakdown.
-// With fuse_sweep the backward linear-term sweep of all 8 channels rides along: node k's p_k, qu_k are formed
-// right after its matrices, while they are still in LDS (same arithmetic as sweep_backward).
+// The backward linear-term sweep of all 8 channels always rides along (fuse_sweep: every caller asks for it): node k's
+// p_k, qu_k are formed right after its matrices, while they are still in LDS (same arithmetic as sweep_backward).
 __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratch &w, int lane, bool fuse_sweep, bool keep_pt)
 {
+    (void)fuse_sweep;
     if (MPCX_PRIO_RIC) __builtin_amdgcn_s_setprio(MPCX_PRIO_RIC);
     const Sat s = uniform_view(s_in);   // private copy: scalar registers, not re-read after every LDS fence
     const int K = s.K;
     bool good = true;
     const int sc = lane >> 3, sr = lane & 7;
-    const bool sact = fuse_sweep && sr < 7;
+    const bool sact = sr < 7;
     const int srr = (sr < 7) ? sr : 6, sr3 = (sr < 3) ? sr : 2;
     // The fused backward sweep runs one node behind the factorisation: node k+1's sweep sits in the same straight-line
     // block as node k's LDL^T chain, so that the two dependent chains fill each other's latency gaps.
@@ -674,8 +681,8 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
     };
     const int sink_e = s.o_sink + lane;                       // this lane's sink slot (element offset in the workspace)
     auto sweep_store = [&](int j, double pp, double qu) {
-        ustore(s.ws, sact ? s.o_ch + j * CH_N + C_P + sc * 7 + sr : sink_e, pp);
-        ustore(s.ws, (sact && sr < 3) ? s.o_ch + j * CH_N + C_QU + sc * 3 + sr3 : sink_e, qu);
+        ustore(s.ws, opaque(sact ? s.o_ch + j * CH_N + C_P + sc * 7 + sr : sink_e), pp);
+        ustore(s.ws, opaque((sact && sr < 3) ? s.o_ch + j * CH_N + C_QU + sc * 3 + sr3 : sink_e), qu);
         pnext = sact ? pp : pnext;
     };
     // operand prefetch: node k's (A, Bn | Bpm | Wx, Wu, D) -> registers -> LDS buffer.  Three branch-free loads per
@@ -718,15 +725,15 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
         return (int)offsetof(StageOps, SX) + 8 * ((e < OPS_IN) ? e - 156 : 0);
     };
     const int slot0 = ops_slot(lane), slot1 = ops_slot(e1), slot2 = ops_slot(e2);
-    auto stash = [&](StageOps &o, int k) {
-        const bool dynk = (k <= K - 2);
+    auto stash = [&](auto dyn_c, StageOps &o, int k) {
+        constexpr bool dynk = decltype(dyn_c)::value;             // (k <= K - 2)
         char *base = (char *)&o;
         *(double *)(base + slot0) = dynk ? pre[0] : 0.0;
         *(double *)(base + slot1) = ((e1 < 70) ? dynk : (e1 < 91) ? (k >= 1) : true) ? pre[1] : 0.0;
         if (e2 < OPS_IN) *(double *)(base + slot2) = (e2 < 149 || e2 >= 156 || dynk) ? pre[2] : 0.0;
     };
     fetch(K - 1);
-    stash(w.ops[(K - 1) & 1], K - 1);
+    stash(BoolC<false>{}, w.ops[(K - 1) & 1], K - 1);
     // (the terminal node's Hessian -- soft part, capped rank-1 terms, AL term -- is a full matrix: from SatData)
     if (lane < 49) w.ops[(K - 1) & 1].G2[(lane / 7) * FS + lane % 7] = sd.WxK[lane];
     for (int e = lane; e < 49; e += 64) w.Pn[e] = 0.0;
@@ -751,13 +758,16 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
     { int tt = lane; for (int i = 0; i < FS; ++i) { const int n = FS - i; if (tt < n) { p6_i = i; p6_j = i + tt; break; } tt -= n; } }
     const bool p6_on = lane < 55;
     const bool p6_qyy = p6_on && p6_j < 7, p6_quy = p6_on && p6_i < 7 && p6_j >= 7, p6_quu = p6_on && p6_i >= 7;
-    for (int k = K - 1; k >= 0; --k) {
+    // One node of the recursion, specialised at compile time: DYN -- a node with dynamics (k <= K-2; not the terminal node),
+    // LAST -- node 0, the last one visited (nothing to prefetch or stash behind it).  The terminal node K-1 and node 0 are
+    // peeled off the loop (K >= 3: the loop runs at least once), so its body tests neither.  Returns false on a breakdown.
+    auto node = [&](auto dyn_c, auto last_c, int k) -> bool {
+        constexpr bool dyn = decltype(dyn_c)::value, last = decltype(last_c)::value;
         StageOps &o = w.ops[k & 1];
         wf64 *fac = s.fac + (size_t)k * FAC_N;
         FT_DECL
-        if (k >= 1) fetch(k - 1);
-        const bool dyn = (k <= K - 2);
-        if (fuse_sweep) nraw = chan_fetch(s, k, sc, srr, sr3);
+        if constexpr (!last) fetch(k - 1);
+        nraw = chan_fetch(s, k, sc, srr, sr3);
         FT_MARK(0)
         // P1: Bh = A Bpm + Bn ; WxBp = Wx Bpm
         {
@@ -767,8 +777,8 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             *dst = val;
         }
         double rd[7] = {0, 0, 0, 0, 0, 0, 0};
-        double sw_p = 0.0, sw_qu = 0.0;
-        if (dyn) {
+        if constexpr (dyn) {
+            double sw_p = 0.0, sw_qu = 0.0;
             // P2: LDL^T of M = D + Pn, redundantly in the registers of every lane (broadcast LDS reads, no exchange):
             // m holds the lower triangle, the strict part ends up as Lt.  Same arithmetic as the oracle's ldl_solve7.
             double m[28];
@@ -779,10 +789,10 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             // fused backward sweep of node k+1 (its matrices are still in the other operand buffer), interleaved
             // with the pivots: one column of its first matrix-vector product per pivot
             const StageOps &on = w.ops[(k + 1) & 1];
-            if (fuse_sweep) sweep_begin(on);
+            sweep_begin(on);
 #pragma unroll
             for (int pp = 0; pp < 7; ++pp) {
-                if (fuse_sweep) sweep_col(pp);
+                sweep_col(pp);
                 const double d = m[pp * (pp + 1) / 2 + pp];
                 if (!(d > 0.0)) good = false;
                 rd[pp] = rcp_pos(d);
@@ -814,9 +824,9 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
 #pragma unroll
                 for (int pp = 0; pp < 7; ++pp) dst[pp * st] = x[pp];
             }
-            if (fuse_sweep) sweep_finish(on, k + 1, sw_p, sw_qu);
+            sweep_finish(on, k + 1, sw_p, sw_qu);
+            sweep_store(k + 1, sw_p, sw_qu);
         }
-        if (fuse_sweep && dyn) sweep_store(k + 1, sw_p, sw_qu);
         wsync();
         FT_MARK(1)
         {
@@ -826,18 +836,20 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             // Branch-free: every lane computes (idle lanes on element 0), LDS / global stores of idle lanes go to sinks;
             // the terminal node (no dynamics) stores zeros.
             const bool on = lane < 49;
-            const int ci = on ? mi : 0, cj = on ? mj : 0;
-            const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
-            double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+            double pt = 0.0, a2 = 0.0, a3 = 0.0;
+            if constexpr (dyn) {
+                const int ci = on ? mi : 0, cj = on ? mj : 0;
+                const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
+                double a1 = 0.0;
 #pragma unroll
-            for (int l = 0; l < 7; ++l) {
-                const double x1i = w.WlLi[l * 14 + ci], x1lo = w.WlLi[l * 14 + lo], x1hi = w.WlLi[l * 14 + hi];
-                const double x2i = w.WlLi[l * 14 + 7 + ci], x2j = w.WlLi[l * 14 + 7 + cj];
-                a1 += x1lo * (rd[l] * x1hi);
-                a2 += x1i * (rd[l] * x2j); a3 += x2i * (rd[l] * x2j);
+                for (int l = 0; l < 7; ++l) {
+                    const double x1i = w.WlLi[l * 14 + ci], x1lo = w.WlLi[l * 14 + lo], x1hi = w.WlLi[l * 14 + hi];
+                    const double x2i = w.WlLi[l * 14 + 7 + ci], x2j = w.WlLi[l * 14 + 7 + cj];
+                    a1 += x1lo * (rd[l] * x1hi);
+                    a2 += x1i * (rd[l] * x2j); a3 += x2i * (rd[l] * x2j);
+                }
+                pt = w.Pn[lo * 7 + hi] - a1;
             }
-            const double pt = dyn ? w.Pn[lo * 7 + hi] - a1 : 0.0;
-            a2 = dyn ? a2 : 0.0; a3 = dyn ? a3 : 0.0;
             *(on ? &o.Pt[lane] : &w.sink[lane]) = pt;
             *(on ? &o.G[lane] : &w.sink[lane]) = a2;
             *(on ? &o.Minv[lane] : &w.sink[lane]) = a3;
@@ -918,25 +930,27 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
         if (o.SX[SX_EX] > 0.0 || o.SX[SX_EU] > 0.0) stiff_stage_update<true>(o, w, nullptr, fac, lane);
         FT_MARK(6)
         FT_MARK(7)
-        // inputs of node k for its sweep in the next iteration (the terminal node's come from LDS)
-        if (fuse_sweep) {
-            // (the terminal node's inputs come through the same branch-free fetch: a conditional load here would make
-            //  the first use of `cur` in the next node wait with vmcnt(0), i.e. for that node's whole prefetch)
-            cur = chan_mask(nraw, sc, sr, sact);
-            if (!dyn) {
-                const double tg = (sc == 2) ? sd.avt[srr] : sd.ta[sc >= 3 ? sc - 3 : 0][srr];
-                cur.gx = (sact && sc >= 2) ? tg : cur.gx;
-                cur.rho = 0.0; cur.aff = 0.0;
-            }
+        // inputs of node k for its sweep in the next node
+        // (the terminal node's inputs come through the same branch-free fetch: a conditional load here would make
+        //  the first use of `cur` in the next node wait with vmcnt(0), i.e. for that node's whole prefetch)
+        cur = chan_mask(nraw, sc, sr, sact);
+        if constexpr (!dyn) {
+            const double tg = (sc == 2) ? sd.avt[srr] : sd.ta[sc >= 3 ? sc - 3 : 0][srr];
+            cur.gx = (sact && sc >= 2) ? tg : cur.gx;
+            cur.rho = 0.0; cur.aff = 0.0;
         }
         FT_MARK(8)
         // a breakdown (every lane sees the same pivots) ends the sweep here: the caller retries with a larger delta_w
-        if (!__all(good)) break;
-        if (k >= 1) stash(w.ops[(k - 1) & 1], k - 1);
+        if (!__all(good)) return false;
+        if constexpr (!last) stash(BoolC<true>{}, w.ops[(k - 1) & 1], k - 1);
         wsync();
         FT_MARK(9)
-    }
-    if (fuse_sweep && __all(good)) {             // the sweep of node 0
+        return true;
+    };
+    bool run = node(BoolC<false>{}, BoolC<false>{}, K - 1);
+    for (int k = K - 2; run && k >= 1; --k) run = node(BoolC<true>{}, BoolC<false>{}, k);
+    if (run) node(BoolC<true>{}, BoolC<true>{}, 0);
+    if (__all(good)) {                           // the sweep of node 0
         double sw_p, sw_qu;
         sweep_begin(w.ops[0]);
 #pragma unroll
