@@ -56,7 +56,10 @@ extern "C" {
                                * resident; not a numerical failure: X, U, NU hold the last iterate, kkt = -1; solve again
                                * without the flag or with the device to itself */
 
-/* dynamics flags (reference include_drag / include_J2 keyword arguments) */
+/* dynamics flags (reference include_drag / include_J2 keyword arguments).  On the discretize / mpc_step entry points
+ * MPCX_FLAG_DRAG is the reference's Discretizer(include_drag=True) (linearize_discretize.py:162-173) with the simulator's
+ * atmosphere -- the fixed density 9.983e-13 kg/m^3 over the constants' RHO, drho = 0, C_D = 2.5: the drag partials in A
+ * (velocity block, mass column), and drag in Sigma and xi. */
 #define MPCX_FLAG_DRAG 1
 #define MPCX_FLAG_J2 2
 /* discretize entry points only: Discretizer.use_uniform_steps (linearize_discretize.py:27-30, 50-53) with
@@ -68,6 +71,11 @@ extern "C" {
  * `method`) -- scipy's Bogacki-Shampine 3(2) pair instead of the default 'RK45', same step-size controller, same tolerances.
  * The implicit methods scipy also offers (Radau, BDF, LSODA) and DOP853 are not implemented. */
 #define MPCX_FLAG_RK23 8
+/* mpcx_mpc_update_batch's disc_flags only: the planning rollouts -- the tangential reference rollout and the re-rollouts under
+ * the optimised sequence -- use the dynamics of the discretisation, disc_flags & (MPCX_FLAG_DRAG | MPCX_FLAG_J2), so that the
+ * planner predicts what that model flies.  Without it they use neither (flags 0), as the reference's run_nonlinear does
+ * (control.py:237-240).  The discretize entry points ignore the bit. */
+#define MPCX_FLAG_PLAN_ROLLOUTS 16
 
 /* normalised constants per satellite: reference constants.py:11-20 field order */
 enum { MPCX_C_MU = 0, MPCX_C_R_E, MPCX_C_J2, MPCX_C_G0, MPCX_C_ISP, MPCX_C_S, MPCX_C_R0,
@@ -388,6 +396,8 @@ int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *
  * Results: the last iteration's plan X [S][7][K], U [S][3][K], NU [S][7][K] (rows of length K, Ks_out[s] columns in use, zeros
  * behind them), tf_out [S] = tf_u, Ks_out [S]; status, iters [n_scp][S]: every iteration's solver outcome; kkt [S]: the last
  * iteration's; prop_status [S]: the first failure among the rollouts (MPCX_ST_*).
+ * disc_flags: the discretisation's flags (MPCX_FLAG_DRAG, MPCX_FLAG_J2, ...); with MPCX_FLAG_PLAN_ROLLOUTS the rollouts of the
+ * plan use its MPCX_FLAG_DRAG | MPCX_FLAG_J2 as well.
  * Segment flight (y_sim != NULL): from y0 over sim_tf under the truth model sim_flags (MPCX_FLAG_DRAG | MPCX_FLAG_J2) with
  * SequenceController(u_opt, tf_u, tf_sim = sim_interval) (end_tau = tf_u / sim_interval, control.py:102,217),
  * y_sim [S][7][sim_n_eval] = sol.y at linspace(0, 1, sim_n_eval), sim_status [S].

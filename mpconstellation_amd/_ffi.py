@@ -17,7 +17,7 @@ STATUS_TEXT = {
     8: "constraint set empty (start node outside its radius bounds, terminal window outside r_max, empty window or tf range)",
     10: "time-parallel solve: a workgroup of the satellite did not answer within the wait limit (device shared with another long kernel?)",
 }
-FLAG_DRAG, FLAG_J2, FLAG_UNIFORM_STEPS, FLAG_RK23 = 1, 2, 4, 8
+FLAG_DRAG, FLAG_J2, FLAG_UNIFORM_STEPS, FLAG_RK23, FLAG_PLAN_ROLLOUTS = 1, 2, 4, 8, 16
 CTRL_ZERO, CTRL_CONSTANT, CTRL_TANGENTIAL, CTRL_SEQUENCE = 0, 1, 2, 3
 NCONST = 8
 STAGE_DOUBLES = 105

@@ -25,7 +25,7 @@ from .simulator import propagate_batch
 class ConstellationMPC:
     def __init__(self, sats, base_res=100, tf_horizon=1, tf_interval=1, r_des=1.5, scp_iterations=2, sim_base_res=100,
                  include_drag=True, include_J2=True, device=0, strict=False, scales=None, verbose=False, devices=None,
-                 time_parallel=False):
+                 time_parallel=False, plan_drag=False, plan_J2=False):
         self.sats = list(sats)
         # every satellite in its own "designer units" (so that each sees MU = 4 pi^2) unless the caller brings the scales
         self.scales = list(scales) if scales is not None else [SatelliteScale(sat=s) for s in self.sats]
@@ -35,7 +35,12 @@ class ConstellationMPC:
         self.horizon, self.interval = tf_horizon, tf_interval
         self.r_des = np.broadcast_to(np.asarray(r_des, dtype=np.float64), (len(self.sats),)).copy()
         self.scp_iterations = scp_iterations
-        self.include_drag, self.include_J2 = include_drag, include_J2
+        self.include_drag, self.include_J2 = include_drag, include_J2          # the truth model the segments are flown with
+        # the planning model: drag / J2 in every linearisation and every planning rollout (include/mpcx.h,
+        # MPCX_FLAG_PLAN_ROLLOUTS), so that the plan predicts what a truth model with them flies.  Default: the reference's
+        # planner, which has neither (control.py:187, 237-240)
+        self.plan_drag, self.plan_J2 = bool(plan_drag), bool(plan_J2)
+        self._plan_model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, rollout_model=self.plan_drag or self.plan_J2)
         self.device = device
         # devices=[0, 1, ..., 7]: the constellation is dealt out in contiguous blocks to these devices, one host thread and one
         # context per device, no exchange between them (sharding.sharded_call) -- the reference loops over
@@ -135,7 +140,7 @@ class ConstellationMPC:
             else:
                 res = self._timed("update", mpc_update_batch, y0, float(self.horizon), self.consts, self.r_des, self.base_res,
                                   n_scp=self.scp_iterations, options=opts, device=self.device, fly=fly, devices=self.devices,
-                                  flags=flags)
+                                  flags=flags, **self._plan_model)
                 self._check(res.prop_status)
                 self.last_status = res.status; self.last_iters = res.iters
                 flown = (res.y_sim, res.sim_status) if fly is not None else None
@@ -167,7 +172,7 @@ class ConstellationMPC:
         res = None
         for it in range(self.scp_iterations):
             res = self._timed("update", scp_iteration_batch, y0, tf_u, self.consts, self.r_des, law, K, options=opts,
-                              Ks=Ks, Kus=Kus, device=self.device, flags=flags)
+                              Ks=Ks, Kus=Kus, device=self.device, flags=flags, **self._plan_model)
             self._check(res.prop_status)
             self.last_status[it] = res.status; self.last_iters[it] = res.iters
             for j in range(S):

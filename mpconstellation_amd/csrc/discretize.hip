@@ -7,7 +7,7 @@
 // The 56-component ODE state [Phi (7x7) ; x (7)] is held column-wise: lane c < 7 owns column c
 // of Phi, lane 7 owns x.  Every column obeys the same linear ODE d(col)/dtau = A(x,u) col, so
 // the 8 lanes run the same instruction stream; the only cross-lane traffic per RHS evaluation
-// is the broadcast of (r, m) from lane 7 (4 x two v_mov_b64_dpp, mpcx_device.hpp) and the 3-step butterfly
+// is the broadcast of (r, m) -- (r, v, m) in the drag forms -- from lane 7 (4 x two v_mov_b64_dpp, mpcx_device.hpp) and the 3-step butterfly
 // of the RMS error norm (DPP as well: no LDS round trip in the step loop).  All groups of a wave take their own adaptive RK45 step sequence
 // (scipy's controller, reproduced decision for decision); the loop is wave-uniform and a
 // group that has reached its end point idles under predicate.  At every accepted node each
@@ -109,7 +109,7 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
     const double gs = -(tf * (im * im));
 #pragma unroll
     for (int i = 0; i < 3; ++i) { L.gmt[i] = gs * u[i]; L.acc[i] = c1 * r[i] + u[i] * im + j2a[i]; }
-    if (flags & MPCX_FLAG_DRAG) {                            // simulator.py:150-153 (the Python Discretizer never sets it)
+    if (flags & MPCX_FLAG_DRAG) {                            // simulator.py:150-153
         const double vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
         const double coef = -0.5 * kCd * c.s * im * (kRho500 / c.rho) * vn;
 #pragma unroll
@@ -122,18 +122,49 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
     L.im = im;
 }
 
+// The drag partials of the linearisation (DRAG forms of the kernel): A_func's include_drag branch (linearize_discretize.py:162-169)
+// with the simulator's atmosphere -- the density ratio kRho500 / rho is fixed, drho = 0, so Dr a_D = 0.  With
+// kd = -C_D S (rho / rho_500) / (2 m):  Dm a_D = -kd |v| v / m goes into L.gmt (the mass column), and the velocity block
+// Dv a_D = kd (|v| I + v v^T / |v|) is applied to a column c in its rank-one form by drag_dv, never formed as a 3x3.
+struct DragLin {
+    double kvt, kwt;     // tf kd |v|, tf kd / |v|
+};
+__device__ __forceinline__ DragLin drag_lin(const double (&v)[3], const SatConst &c, double tf, Lin &L)
+{
+    const double vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    const double ivn = rsq_nr(vv), vn = vv * ivn;
+    const double kdt = tf * (-0.5 * kCd * c.s * L.im * (kRho500 / c.rho));
+    const double gm = -(kdt * vn) * L.im;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) L.gmt[i] += gm * v[i];
+    return {kdt * vn, kdt * ivn};
+}
+// tf Dv a_D c = tf kd (|v| c + v (v . c) / |v|)
+__device__ __forceinline__ void drag_dv(const DragLin &d, const double (&v)[3], double c0, double c1, double c2, double (&out)[3])
+{
+    const double w = d.kwt * (v[0] * c0 + v[1] * c1 + v[2] * c2);
+    out[0] = d.kvt * c0 + w * v[0];
+    out[1] = d.kvt * c1 + w * v[1];
+    out[2] = d.kvt * c2 + w * v[2];
+}
+
 // One evaluation of dPhi (linearize_discretize.py:262-290) for this lane's column.
+template <bool DRAG>
 __device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], double ts,
                                          double (&out)[7], int &err)
 {
     double u[3];
     foh3_cached(ts, p.us, p.Ku, p.ldu, p.foh, u, err);
     const double r[3] = {bcast8<7>(ys[0]), bcast8<7>(ys[1]), bcast8<7>(ys[2])};
-    const double v[3] = {ys[3], ys[4], ys[5]};               // drag acts in the x column only: lane 7's own velocity
+    // drag acts in the x column only: lane 7's own velocity -- except in the DRAG forms, whose Phi columns need the reference
+    // velocity for the drag partials: broadcast from lane 7 like r and m
+    const double v[3] = {DRAG ? bcast8<7>(ys[3]) : ys[3], DRAG ? bcast8<7>(ys[4]) : ys[4], DRAG ? bcast8<7>(ys[5]) : ys[5]};
     const double m = bcast8<7>(ys[6]);
     const double tf = p.tf;
     Lin L;
     lin_eval(r, v, m, u, p.cst, p.flags, tf, p.inv_ve, L);
+    double dv[3] = {0.0, 0.0, 0.0};
+    if constexpr (DRAG) drag_dv(drag_lin(v, p.cst, tf, L), v, ys[3], ys[4], ys[5], dv);
     const bool isx = (p.c == 7);
     if (isx && m <= 0.0) err = MPCX_ST_MASS;
 #pragma unroll
@@ -143,6 +174,7 @@ __device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], doubl
         a += L.Gt[i][1] * ys[1];
         a += L.Gt[i][2] * ys[2];
         a += L.gmt[i] * ys[6];
+        if constexpr (DRAG) a += dv[i];
         out[3 + i] = isx ? tf * L.acc[i] : a;                // x column: tf * f(x, u)
     }
     out[6] = isx ? tf * L.mdot : 0.0;
@@ -198,6 +230,7 @@ __device__ __forceinline__ bool lu_solve_cols(double (&col)[6], double (&b)[6])
 
 // Quadrature integrand column of this lane at an accepted node (linearize_discretize.py:60-75):
 // g = Phi(t)^-1 [B lam-, B lam+, Sigma, xi][:, c]
+template <bool DRAG>
 __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
                                                double t, double tau_k, double tau_kp1,
                                                double (&g)[7], int &err)
@@ -215,6 +248,8 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
     const double r[3] = {x[0], x[1], x[2]}, v[3] = {x[3], x[4], x[5]};
     Lin L;
     lin_eval(r, v, x[6], u, p.cst, p.flags, tf, p.inv_ve, L);
+    double dv[3] = {0.0, 0.0, 0.0};                         // DRAG: xi's A x gains the velocity block and (in L.gmt) the mass column
+    if constexpr (DRAG) drag_dv(drag_lin(v, p.cst, tf, L), v, v[0], v[1], v[2], dv);
 
     // B column (B_func :186-215), Sigma (:239-254), xi (:218-236)
     const int j = (c < 3) ? c : c - 3;
@@ -233,6 +268,7 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
         ax += L.Gt[i][1] * x[1];
         ax += L.Gt[i][2] * x[2];
         ax += L.gmt[i] * x[6];
+        if constexpr (DRAG) ax += dv[i];
         xi[3 + i] = -(ax + (tf * L.im) * u[i]);
         bu6 += nou ? 0.0 : (b6s * u[i]) * u[i];
     }
@@ -264,7 +300,9 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
 // at the last of them; a separate instantiation, the default path is untouched.
 // METHOD: 45 -- scipy's 'RK45', the reference's default (linearize_discretize.py:105) -- or 23: 'RK23' (ivp_solver goes to
 // solve_ivp's `method`, :40): the same controller around the Bogacki-Shampine tableau, separate instantiations.
-template <int LAYOUT, bool UNIFORM, int METHOD = 45>
+// DRAG: MPCX_FLAG_DRAG -- the reference's Discretizer(include_drag=True) with the simulator's atmosphere: the drag partials
+// in Phi's Jacobian and in xi (drag_lin / drag_dv); separate instantiations, the drag-free ones are untouched.
+template <int LAYOUT, bool UNIFORM, int METHOD = 45, bool DRAG = false>
 #ifndef MPCX_DISC_WAVES
 #define MPCX_DISC_WAVES 1      // waves per SIMD the register allocation is bounded for (360 registers at 1)
 #endif
@@ -316,7 +354,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
 #pragma unroll
     for (int i = 0; i < 7; ++i) y[i] = (c < 7) ? ((i == c) ? 1.0 : 0.0) : xs[(size_t)i * a.K + k];
     double t = tau_k;
-    rhs_eval(p, y, t, f, err);
+    rhs_eval<DRAG>(p, y, t, f, err);
 
     // ---- scipy select_initial_step (common.py:68-134), direction +1, order 4 ----
     double h_abs;
@@ -336,7 +374,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         double y1[7], f1[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i) y1[i] = y[i] + h0 * f[i];
-        rhs_eval(p, y1, t + h0, f1, err);
+        rhs_eval<DRAG>(p, y1, t + h0, f1, err);
         double s2 = 0.0;
 #pragma unroll
         for (int i = 0; i < 7; ++i) { const double d = (f1[i] - f[i]) / scale[i]; s2 += d * d; }
@@ -352,7 +390,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
     double acc[7], gprev[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) acc[i] = 0.0;
-    node_integrand(p, y, t, tau_k, tau_kp1, gprev, err);
+    node_integrand<DRAG>(p, y, t, tau_k, tau_kp1, gprev, err);
 
     // uniform mode: index of the next evaluation point, time of the previous one, the interpolated state at it
     const double ustep = UNIFORM ? (tau_kp1 - tau_k) / (double)(n_uni - 1) : 0.0;   // np.linspace(tau_k, tau_kp1, n)
@@ -389,13 +427,13 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             // last stage in both methods (first-same-as-last: it becomes f of the next step)
 #pragma unroll
             for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK23_A10) * h;
-            rhs_eval(p, yt, t + RK23_C[1] * h, K1, err);
+            rhs_eval<DRAG>(p, yt, t + RK23_C[1] * h, K1, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * 0.0 + K1[i] * RK23_A21) * h;
-            rhs_eval(p, yt, t + RK23_C[2] * h, K2, err);
+            rhs_eval<DRAG>(p, yt, t + RK23_C[2] * h, K2, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) yn[i] = y[i] + h * (f[i] * RK23_B[0] + K1[i] * RK23_B[1] + K2[i] * RK23_B[2]);
-            rhs_eval(p, yn, t + h, K6, err);
+            rhs_eval<DRAG>(p, yn, t + h, K6, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 K3[i] = 0.0; K4[i] = 0.0; K5[i] = 0.0;
@@ -407,29 +445,29 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         } else {
 #pragma unroll
         for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK_A[1][0]) * h;
-        rhs_eval(p, yt, t + RK_C[1] * h, K1, err);
+        rhs_eval<DRAG>(p, yt, t + RK_C[1] * h, K1, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK_A[2][0] + K1[i] * RK_A[2][1]) * h;
-        rhs_eval(p, yt, t + RK_C[2] * h, K2, err);
+        rhs_eval<DRAG>(p, yt, t + RK_C[2] * h, K2, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[3][0] + K1[i] * RK_A[3][1] + K2[i] * RK_A[3][2]) * h;
-        rhs_eval(p, yt, t + RK_C[3] * h, K3, err);
+        rhs_eval<DRAG>(p, yt, t + RK_C[3] * h, K3, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[4][0] + K1[i] * RK_A[4][1] + K2[i] * RK_A[4][2] +
                             K3[i] * RK_A[4][3]) * h;
-        rhs_eval(p, yt, t + RK_C[4] * h, K4, err);
+        rhs_eval<DRAG>(p, yt, t + RK_C[4] * h, K4, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[5][0] + K1[i] * RK_A[5][1] + K2[i] * RK_A[5][2] +
                             K3[i] * RK_A[5][3] + K4[i] * RK_A[5][4]) * h;
-        rhs_eval(p, yt, t + RK_C[5] * h, K5, err);
+        rhs_eval<DRAG>(p, yt, t + RK_C[5] * h, K5, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yn[i] = y[i] + h * (f[i] * RK_B[0] + K1[i] * RK_B[1] + K2[i] * RK_B[2] +
                                 K3[i] * RK_B[3] + K4[i] * RK_B[4] + K5[i] * RK_B[5]);
-        rhs_eval(p, yn, t + h, K6, err);
+        rhs_eval<DRAG>(p, yn, t + h, K6, err);
 
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
@@ -506,7 +544,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                                                             : Q[i][0] * p1 + Q[i][1] * p2 + Q[i][2] * p3 + Q[i][3] * p4;
                         yd[i] = has ? h * accq + yold[i] : y[i];
                     }
-                    node_integrand(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
+                    node_integrand<DRAG>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
                     if (has) {
                         const double d = te - te_prev;
 #pragma unroll
@@ -523,7 +561,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         // node quadrature (wave-uniform call; only accepting groups commit)
         if (!UNIFORM && __any(accept)) {
             double g[7];
-            node_integrand(p, y, t, tau_k, tau_kp1, g, err);
+            node_integrand<DRAG>(p, y, t, tau_k, tau_kp1, g, err);
             if (accept) {
                 const double d = h;          // ts[i+1] - ts[i]
 #pragma unroll
@@ -610,8 +648,13 @@ static int launch_discretize(mpcx_ctx *ctx, int layout, DiscArgs a, hipStream_t 
     const bool uni = (a.flags & MPCX_FLAG_UNIFORM_STEPS) != 0;
     if (uni && (a.flags >> 8) < 2) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: uniform steps need MPCX_UNIFORM_STEPS(n), n >= 2");
     const bool rk23 = (a.flags & MPCX_FLAG_RK23) != 0;
+    const bool drag = (a.flags & MPCX_FLAG_DRAG) != 0;
     if (!uni) a.flags &= (MPCX_FLAG_DRAG | MPCX_FLAG_J2);
-#define MPCX_DISC_LAUNCH(L, U, M) hipLaunchKernelGGL((discretize_kernel<L, U, M>), dim3(blocks), dim3(64), 0, st, a)
+#define MPCX_DISC_LAUNCH(L, U, M)                                                                            \
+    do {                                                                                                     \
+        if (drag) hipLaunchKernelGGL((discretize_kernel<L, U, M, true>), dim3(blocks), dim3(64), 0, st, a);  \
+        else hipLaunchKernelGGL((discretize_kernel<L, U, M, false>), dim3(blocks), dim3(64), 0, st, a);      \
+    } while (0)
     if (layout == LAYOUT_STAGE) {
         if (rk23) { if (uni) MPCX_DISC_LAUNCH(LAYOUT_STAGE, true, 23); else MPCX_DISC_LAUNCH(LAYOUT_STAGE, false, 23); }
         else if (uni) MPCX_DISC_LAUNCH(LAYOUT_STAGE, true, 45);

@@ -446,6 +446,9 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
         MPCX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));                   // the uploads are behind this point of the first stream
         MPCX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
     }
+    // the planning rollouts' dynamics: the discretisation's with MPCX_FLAG_PLAN_ROLLOUTS, the reference's drag- and J2-free
+    // run_nonlinear (control.py:237-240) without
+    const int roll_flags = (disc_flags & MPCX_FLAG_PLAN_ROLLOUTS) ? (disc_flags & (MPCX_FLAG_DRAG | MPCX_FLAG_J2)) : 0;
     const double *tf_fin = dtf0;
     const int32_t *Ks_fin = nullptr;
     const double *Uplan = dU[(n_scp - 1) & 1];
@@ -468,10 +471,10 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
             // control.py:178-180 / :217-227: rollout under the tangential reference law, then under the sequence just optimised,
             // played over its own horizon (end_tau = 1) and sampled at int(base_res * tf_u) nodes; u_bar = extract_uk (:188)
             if (it == 0)
-                rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, n, K, nullptr, dy0 + o1 * 7, tf_cur, dc + o1 * MPCX_NCONST, 0, MPCX_CTRL_TANGENTIAL,
+                rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, n, K, nullptr, dy0 + o1 * 7, tf_cur, dc + o1 * MPCX_NCONST, roll_flags, MPCX_CTRL_TANGENTIAL,
                                                             dmag + o1, 0, nullptr, nullptr, prop_max_step, dx + o7, du + o3, dps2 + o1, dpn + o1, st);
             else
-                rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, n, K, Ks, dy0 + o1 * 7, tf_cur, dc + o1 * MPCX_NCONST, 0, MPCX_CTRL_SEQUENCE,
+                rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, n, K, Ks, dy0 + o1 * 7, tf_cur, dc + o1 * MPCX_NCONST, roll_flags, MPCX_CTRL_SEQUENCE,
                                                             dU[(it - 1) & 1] + o3, K, it >= 2 ? dKn[(it - 1) & 1] + o1 : nullptr, done + o1,
                                                             prop_max_step, dx + o7, du + o3, dps2 + o1, dpn + o1, st);
             if (rc) break;

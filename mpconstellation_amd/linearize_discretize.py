@@ -78,9 +78,10 @@ class Discretizer:
         return A[0], Bp[0], Bn[0], Sig[0], xi[0]
 
     def device_flags(self):
-        """the integration settings as flags of the discretize / fused-step entry points (include/mpcx.h): use_uniform_steps
-        with integrator_steps (linearize_discretize.py:27-30: t_eval = linspace(.., integrator_steps)), ivp_solver (:40)"""
-        flags = 0
+        """the linearisation's settings as flags of the discretize / fused-step entry points (include/mpcx.h): include_drag
+        (:162-173, with the simulator's atmosphere), use_uniform_steps with integrator_steps (linearize_discretize.py:27-30:
+        t_eval = linspace(.., integrator_steps)), ivp_solver (:40)"""
+        flags = _ffi.FLAG_DRAG if self.include_drag else 0
         if self.use_uniform_steps:
             flags |= _ffi.FLAG_UNIFORM_STEPS | (int(self.integrator_steps) << 8)
         if self.ivp_solver == 'RK23':
@@ -88,9 +89,11 @@ class Discretizer:
         return flags
 
     def _check_modes(self):
-        if self.include_drag:
-            # the reference's drag branch cannot run either (Constants has no CD, rho_func is None)
-            raise NotImplementedError("drag in the linearisation is not supported")
+        if self.include_drag and (self.rho_func is not None or self.drho_func is not None):
+            # the drag branch (:162-173) runs on the device with the simulator's atmosphere (fixed density, drho = 0,
+            # simulator.py:112) -- rho_func / drho_func None; a Python density model cannot run there
+            raise NotImplementedError("drag in the linearisation: only the simulator's fixed-density atmosphere "
+                                      "(rho_func=None, drho_func=None) is implemented on the device")
         if self.ivp_solver not in ('RK45', 'RK23'):
             raise NotImplementedError("ivp_solver: 'RK45' (the reference's default) and 'RK23' are implemented on the device; "
                                       "scipy's DOP853 and its implicit methods (Radau, BDF, LSODA) are not")

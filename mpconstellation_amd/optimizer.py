@@ -59,6 +59,24 @@ def _solver_flags(solver, linear_vt, fixed_tf=None, shared_tf=False):
     return solver
 
 
+def _model_flags(include_drag, include_J2):
+    return (_ffi.FLAG_DRAG if include_drag else 0) | (_ffi.FLAG_J2 if include_J2 else 0)
+
+
+def scp_flags(include_drag=False, include_J2=False, rollout_model=False):
+    """(prop_flags, disc_flags) of an SCP iteration (mpcx_scp_iteration_batch_ragged) that plans with the given model: the
+    linearisation with drag / J2, and -- rollout_model=True -- the rollout too.  The reference's planner has neither
+    (control.py:187, 237-240): all defaults."""
+    model = _model_flags(include_drag, include_J2)
+    return (model if rollout_model else 0), model
+
+
+def update_flags(include_drag=False, include_J2=False, rollout_model=False):
+    """disc_flags of an update (mpcx_mpc_update_batch) that plans with the given model: rollout_model=True adds
+    MPCX_FLAG_PLAN_ROLLOUTS, which gives its planning rollouts the discretisation's drag / J2."""
+    return _model_flags(include_drag, include_J2) | (_ffi.FLAG_PLAN_ROLLOUTS if rollout_model else 0)
+
+
 _pinned_results = {}
 
 
@@ -88,9 +106,11 @@ def _tf_io(S, fixed_tf):
 
 def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False, max_step=1e-2, device=0, slot=0,
                    linear_vt=False, fixed_tf=None, pinned_results=False, uniform_steps=0, regularised=False, Ks=None, shared_tf=False,
-                   devices=None, rk23=False, out=None, **solver):
+                   devices=None, rk23=False, out=None, include_drag=False, **solver):
     """S independent satellite-MPC-steps (discretize + solve) on the device.
     xbar (S,7,K), ubar (S,3,K), tf (S,), consts (S,8), r_des (S,) -> SolveResult with batched arrays.
+    include_drag / include_J2: the linearisation of Discretizer(include_drag=..., include_J2=...), drag with the simulator's
+    atmosphere (include/mpcx.h, MPCX_FLAG_DRAG).
     Ks (S,) int: a ragged batch -- satellite s has Ks[s] <= K nodes in the first columns of its rows (what the reference's
     second SCP iteration poses: int(base_res * tf_u) nodes per satellite, control.py:227); result columns past a
     satellite's count are zero.
@@ -111,7 +131,8 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         X, U, NU, kkt, status, iters = _result_arrays(S, K, tuple(int(d) for d in devices) if pinned_results else int(devices[0]), pinned_results)
         tfo = np.empty(S); reg = np.zeros((S, 2), dtype=np.int32) if regularised else None
         fn = lambda x, u, t, c, r, k, device, slot, out: mpc_step_batch(x, u, t, c, r, options, include_J2, max_step, device, slot, linear_vt,
-                                                                        None, False, uniform_steps, regularised, k, False, None, rk23, out, **solver)
+                                                                        None, False, uniform_steps, regularised, k, False, None, rk23, out,
+                                                                        include_drag, **solver)
         sharded_call(fn, devices, [xbar, _ffi.as_f64(ubar), bc(tf), _ffi.as_f64(consts), bc(r_des), Ksb],
                      dict(X=X, U=U, NU=NU, kkt=kkt, status=status, iters=iters, tf=tfo, regularised=reg))
         return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg)
@@ -137,7 +158,7 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         tfo, held = oa.get("tf", (S,)), None
     lib = _ffi.load(); ctx = _ffi.context(device, slot)
     import ctypes as C
-    dflags = _ffi.FLAG_J2 if include_J2 else 0
+    dflags = _model_flags(include_drag, include_J2)
     if uniform_steps:                         # Discretizer.use_uniform_steps with integrator_steps = uniform_steps
         dflags |= _ffi.FLAG_UNIFORM_STEPS | (int(uniform_steps) << 8)
     if rk23:                                  # Discretizer.ivp_solver = 'RK23'
@@ -162,13 +183,16 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
 
 
 def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Kus=None, include_J2=False, max_step=1e-2,
-                        prop_max_step=1e-3, device=0, slot=0, linear_vt=False, return_reference=False, **solver):
+                        prop_max_step=1e-3, device=0, slot=0, linear_vt=False, return_reference=False, include_drag=False,
+                        rollout_model=False, **solver):
     """One SCP iteration of OptimalController.update (control.py:183-227) for S satellites in ONE library call
     (mpcx_scp_iteration_batch_ragged): the nonlinear rollout from y0 (S,7) over tf (S,) under `law` = (kind, vec, Ku, end_tau)
     (simulator.propagate_batch's law tuple) sampled at K nodes -- Ks[s] of them in a ragged batch --, its controller's thrust
     at those nodes (extract_uk), the discretisation about them and the solve.  The reference trajectory stays on the device
     unless return_reference=True (then the result carries .xbar (S,7,K) and .ubar (S,3,K)).  Returns a SolveResult with the
-    extra attribute prop_status (S,)."""
+    extra attribute prop_status (S,).
+    Planning model (scp_flags): include_drag / include_J2 in the linearisation; rollout_model=True flies the rollout with them
+    too (the reference's rollout has neither)."""
     solver = _solver_flags(solver, linear_vt, None, False)
     y0 = _ffi.as_f64(y0); S = y0.shape[0]; K = int(K)
     tf = _ffi.as_f64(np.broadcast_to(np.asarray(tf, dtype=np.float64), (S,)))
@@ -191,12 +215,13 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     tfo = np.empty(S); pst = np.zeros(S, dtype=np.int32)
     xb = np.empty((S, 7, K)) if return_reference else None
     ub = np.empty((S, 3, K)) if return_reference else None
+    prop_flags, disc_flags = scp_flags(include_drag, include_J2, rollout_model)
     lib = _ffi.load(); ctx = _ffi.context(device, slot)
     import ctypes as C
     rc = lib.mpcx_scp_iteration_batch_ragged(ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(y0), _ffi.dptr(tf),
-                                             _ffi.dptr(consts), _ffi.dptr(r_des), 0, kind, vec_p, int(Ku),
+                                             _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags, kind, vec_p, int(Ku),
                                              None if Kus is None else _ffi.iptr(Kus), et_p, float(prop_max_step),
-                                             _ffi.FLAG_J2 if include_J2 else 0, float(max_step), C.byref(opts),
+                                             disc_flags, float(max_step), C.byref(opts),
                                              None if xb is None else _ffi.dptr(xb), None if ub is None else _ffi.dptr(ub),
                                              _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status),
                                              _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst))
@@ -212,7 +237,8 @@ class UpdateResult(SolveResult):
 
 
 def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None, ref_thrust=0.5, include_J2=False, max_step=1e-2,
-                     prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, out=None, **solver):
+                     prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, out=None, include_drag=False,
+                     rollout_model=False, **solver):
     """OptimalController.update (control.py:170-235) for S satellites in ONE library call (mpcx_mpc_update_batch): the tangential
     reference rollout over `horizon` sampled at K = int(base_res * horizon) nodes, n_scp x (extract_uk, discretise, solve) with
     the nonlinear re-rollout under the optimised sequence -- sampled at int(base_res * tf_u) nodes per satellite -- between
@@ -220,6 +246,8 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     fly = (tf, interval, n_eval, include_drag, include_J2[, max_step]): also Simulator.run_segment's flight (simulator.py:58-65)
     of the plan over tf under the truth model, SequenceController(u_opt, tf_u, tf_sim = interval), from the same start states;
     the result then carries y_sim (S,7,n_eval) and sim_status.
+    Planning model (update_flags): include_drag / include_J2 in every linearisation; rollout_model=True flies the planning
+    rollouts with them too (MPCX_FLAG_PLAN_ROLLOUTS).  The defaults are the reference's planner, which has neither.
     devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (see mpc_step_batch)."""
     if devices is not None and len(devices) > 1:
         from .sharding import sharded_call
@@ -228,7 +256,8 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
         hz = bc(horizon); K = int(base_res * float(hz[0]))
         res = _update_result(S, K, n_scp, int(devices[0]), fly)          # ONE result set; every block fills its satellites' part
         fn = lambda y, h, c, r, device, slot, out: mpc_update_batch(y, h, c, r, base_res, n_scp, options, ref_thrust, include_J2, max_step,
-                                                                    prop_max_step, device, slot, linear_vt, fly, None, out, **solver)
+                                                                    prop_max_step, device, slot, linear_vt, fly, None, out, include_drag,
+                                                                    rollout_model, **solver)
         sharded_call(fn, devices, [y0, hz, _ffi.as_f64(consts), bc(r_des)],
                      dict(X=res.X, U=res.U, NU=res.NU, kkt=res.kkt, tf=res.tf, Ks=res.Ks, prop_status=res.prop_status,
                           status=(res.status, 1), iters=(res.iters, 1), y_sim=res.y_sim, sim_status=res.sim_status))
@@ -266,7 +295,8 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     lib = _ffi.load(); ctx = _ffi.context(device, slot)
     import ctypes as C
     rc = lib.mpcx_mpc_update_batch(ctx, S, K, int(n_scp), float(base_res), _ffi.dptr(y0), _ffi.dptr(horizon), _ffi.dptr(consts),
-                                   _ffi.dptr(r_des), float(ref_thrust), float(prop_max_step), _ffi.FLAG_J2 if include_J2 else 0,
+                                   _ffi.dptr(r_des), float(ref_thrust), float(prop_max_step),
+                                   update_flags(include_drag, include_J2, rollout_model),
                                    float(max_step), C.byref(opts), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo),
                                    _ffi.iptr(Ks), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst), sim[0], sim[1],
                                    sim[2], sim[3], sim[4], None if y_sim is None else _ffi.dptr(y_sim), None if sst is None else _ffi.iptr(sst))
@@ -540,7 +570,7 @@ class Optimizer:
                                                           options, device=getattr(self.d, "device", 0), **solver)
         else:
             self.result = mpc_step_batch(xbar, ubar, self.tf, consts, options['r_des'], options,
-                                         include_J2=self.d.include_J2, max_step=self.d.ivp_max_step,
+                                         include_J2=self.d.include_J2, include_drag=self.d.include_drag, max_step=self.d.ivp_max_step,
                                          device=getattr(self.d, "device", 0),
                                          uniform_steps=int(self.d.integrator_steps) if self.d.use_uniform_steps else 0,
                                          rk23=(self.d.ivp_solver == 'RK23'), **solver)
