@@ -223,7 +223,9 @@ typedef struct {
 #define MPCX_SOLVE_TP_SELFTEST_DEAD (1 << 30)
 
 void mpcx_default_solve_opts(mpcx_solve_opts *o);
-/* Workspace of the _dev solves / fused steps.  The plain queries are device-independent upper bounds (one slot per
+/* Workspace of the _dev solves / fused steps.  It need not be initialised: a call's results do not depend on what the
+ * workspace holds on entry -- any bit pattern, another call's leftovers (tests/test_stale_memory_gpu.py) -- and its contents
+ * after the call are unspecified.  The plain queries are device-independent upper bounds (one slot per
  * satellite); the _ctx queries return what a launch on the context's device touches -- one slot per persistent workgroup,
  * min(S, workgroups resident at once: 2048 on MI355X), 0.44 GB instead of 1.8 GB at S = 8192, K = 30 -- and are enough. */
 size_t mpcx_solve_workspace_bytes(int S, int K);
@@ -323,9 +325,13 @@ int mpcx_propagate_batch_dev(mpcx_ctx *ctx, int S, int n_eval, const double *y0,
  * simulator.py:38), a different count for every satellite of a constellation: the next discretize / solve then has K_s
  * nodes for satellite s.  The *_ragged entry points take one launch of satellites with different counts: arrays keep the
  * rectangular shapes of the plain entry points with K (n_eval, Ku) the ROW LENGTH, and satellite s uses the first Ks[s]
- * (n_evals[s], Kus[s]) columns of its rows; np.linspace(0, 1, Ks[s]) is its node grid.  Result columns past a satellite's
- * count come back zero (stage records past its last interval are unspecified).  A count outside the accepted range gives
- * that satellite MPCX_ST_BADK and leaves the others alone.  A NULL count array means "all K": the plain entry points are
+ * (n_evals[s], Kus[s]) columns of its rows; np.linspace(0, 1, Ks[s]) is its node grid.  Input columns past a satellite's
+ * count are never read: they may hold anything.  Result columns past a satellite's count come back zero (stage records past
+ * its last interval are unspecified).  In the _dev variants: the solves and fused steps write those zeros themselves, into
+ * every row of X, U and NU -- except for a satellite that comes back MPCX_ST_BADK or MPCX_ST_INFEASIBLE, whose reference rows
+ * are handed back whole, the columns past its count as they came in; mpcx_resample_sequence_dev writes them too; the
+ * propagate _dev variants leave the columns of y_out / u_out past n_evals[s] untouched (the host variants clear them).
+ * A count outside the accepted range gives that satellite MPCX_ST_BADK and leaves the others alone.  A NULL count array means "all K": the plain entry points are
  * these with NULL.  Count arrays are int32; device pointers in the _dev variants.
  */
 int mpcx_discretize_stages_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, int Ku, const int32_t *Kus,

@@ -1068,6 +1068,10 @@ __device__ __noinline__ void combine_channels(const Sat &s_in, SatData &sd, doub
         for (int q = 0; q < NQ; ++q) {
             const int e = lane + 64 * q;
             const int i = e >> 5, kl = e & 31, k = k0 + kl;
+            // (invariant: d[I_NU] / d[I_LAM] of the terminal node are NEVER written -- they hold whatever the workspace held -- and a trial
+            //  with a != 0 carries that into the candidate iterate's terminal nu / lam: every reader of those 14 entries, of the direction
+            //  or of an iterate, must stay masked by `dyn` / `valid` (eval_residual, finish_direction, newton_blocks, the result
+            //  write-out); tests/test_stale_memory_gpu.py holds this with NaN, Inf and 1e300 in their place)
             const bool act = kl < nk && !(k == K - 1 && i >= T_NU);
             const int off = (i < T_U) ? I_X + i : (i < T_NU ? I_U + (i - T_U) : (i < T_LAM ? I_NU + (i - T_NU) : I_LAM + (i - T_LAM)));
             const int dst = off * KP + (kl < nk ? k : k0);

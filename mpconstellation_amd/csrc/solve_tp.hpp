@@ -586,6 +586,7 @@ __device__ __noinline__ void tp_combine(const Sat &s_in, SatData &sd, TpData &tp
         for (int q = 0; q < NQ; ++q) {
             const int e = lane + 64 * wave + 128 * q;
             const int i = e >> 5, kl = e & 31, k = k0 + kl;
+            // (the terminal node's d[I_NU] / d[I_LAM] are never written: the invariant stated at combine_channels, solve_phases.hpp)
             const bool act = kl < nk && !(k == K - 1 && i >= T_NU);
             const int off = (i < T_U) ? I_X + i : (i < T_NU ? I_U + (i - T_U) : (i < T_LAM ? I_NU + (i - T_NU) : I_LAM + (i - T_LAM)));
             const int dst = off * KP + (kl < nk ? k : k0);

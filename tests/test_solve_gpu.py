@@ -32,6 +32,21 @@ def load(golden_dir, name):
     return d, d["x"], d["u"], float(d["tf"]), d["const"]
 
 
+def solution_tolerance(ref, iters, n_dev, first_dev):
+    """The tolerance at which a device solution (iters iterations, n_dev of them regularised, the first at first_dev) is held to
+    the oracle's `ref`, and the bound on the difference of their iteration counts.
+    Same data, same algorithm: the same iteration path.  Two things are decided by rounding and may part the paths
+    near their end: whether the last iterate already meets E_0 <= tol (one iteration more or less), and -- on a path
+    that runs through factorisation breakdowns (indefinite reduced Hessian far from the solution, regularised by
+    delta_w) -- whether a pivot of a nearly singular matrix comes out at +1e-17 or -1e-17.  Both sides still end at
+    the same KKT point: the solutions are compared at rounding level when the paths coincide, at the solver
+    tolerance otherwise."""
+    clean = ref["n_regularised"] == 0 and n_dev == 0
+    same_path = (clean or (n_dev == ref["n_regularised"] and first_dev == ref["first_regularised"])) and iters == ref["iters"]
+    assert abs(int(iters) - ref["iters"]) <= (1 if clean else 10)
+    return 5 * TOL if same_path else TOL_SOL
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_solve_vs_oracle(golden_dir, name):
     from mpconstellation_amd import solve_batch
@@ -46,17 +61,8 @@ def test_solve_vs_oracle(golden_dir, name):
     # the device reports its own regularised iterations (mpcx_solve_regularised): a rounding flip of a breakdown decision
     # shows as a different count / first index, a path divergence without any regularisation on either side would not
     n_dev, first_dev = int(res.n_regularised[0]), int(res.first_regularised[0])
-    clean = ref["n_regularised"] == 0 and n_dev == 0
     firsts = ([ref["first_regularised"]] if ref["n_regularised"] > 0 else []) + ([first_dev] if n_dev > 0 else [])
-    # Same data, same algorithm: the same iteration path.  Two things are decided by rounding and may part the paths
-    # near their end: whether the last iterate already meets E_0 <= tol (one iteration more or less), and -- on a path
-    # that runs through factorisation breakdowns (indefinite reduced Hessian far from the solution, regularised by
-    # delta_w) -- whether a pivot of a nearly singular matrix comes out at +1e-17 or -1e-17.  Both sides still end at
-    # the same KKT point: the solutions are compared at rounding level when the paths coincide, at the solver
-    # tolerance otherwise ...
-    same_path = (clean or (n_dev == ref["n_regularised"] and first_dev == ref["first_regularised"])) and res.iters[0] == ref["iters"]
-    assert abs(int(res.iters[0]) - ref["iters"]) <= (1 if clean else 10)
-    tol = 5 * TOL if same_path else TOL_SOL
+    tol = solution_tolerance(ref, res.iters[0], n_dev, first_dev)
     assert np.abs(res.X[0] - ref["X"]).max() < tol
     assert np.abs(res.U[0] - ref["U"]).max() < tol
     assert np.abs(res.NU[0] - ref["NU"]).max() < tol
