@@ -85,8 +85,8 @@ class HostCopier {
 struct StagePool {
     struct Chunk { char *p; size_t cap; };
     std::vector<Chunk> chunks;
-    size_t cur, off;          // chunk in use and bump offset inside it
-    bool pinned;
+    size_t cur = 0, off = 0;  // chunk in use and bump offset inside it
+    bool pinned = false;
 };
 
 inline void *pool_take(StagePool &pl, size_t bytes)
@@ -115,38 +115,60 @@ inline void pool_free(StagePool &pl)
     pl.chunks.clear(); pl.cur = pl.off = 0;
 }
 
+// Grow-only device buffer of a context: a request it already holds costs nothing -- no free / allocation, hence no implicit
+// device synchronisation, when ConstellationMPC alternates group sizes on one context.  Growing discards the contents; a
+// growth that fails leaves the buffer empty (p null, cap 0) and the next request tries again.
+template <typename T> struct DeviceBuf {
+    T *p = nullptr;
+    size_t cap = 0;           // elements
+    hipError_t reserve(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&p, n * sizeof(T));
+        if (e == hipSuccess) cap = n; else p = nullptr;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Launch order of the solver's workgroups for ONE sequence of solves: the iteration counts of the sequence's last solves
+// (library-owned copies), the prediction made of them and the satellites sorted by it, longest first.  What is recorded
+// is valid only for a following solve of the same batch size.  (The members that enqueue kernels: solve_api.hip.)
+struct LaunchOrder {
+    DeviceBuf<int32_t> pred, hist, order;        // pred: the prediction the order is sorted by; hist: the last solves' counts
+    int S = 0, valid = 0;                        // batch size of the recorded solves and how many of them there are (wrapped: record())
+    hipError_t grow(int batch);                  // room for a batch; another batch size than the last forgets the record
+    const int32_t *sorted(hipStream_t st);       // the order to launch with (sorted on st), or null: nothing recorded
+    void record(const int32_t *iters, hipStream_t st);       // this solve's iteration counts, read on st
+    void invalidate() { valid = 0; }
+    void release() { pred.release(); hist.release(); order.release(); S = valid = 0; }
+};
+
 struct mpcx_ctx {
-    int device;
-    hipStream_t stream;       // stream used by the host-pointer entry points
-    bool own_stream;          // created by the library (mpcx_create / MPCX_STREAM_PRIVATE), not handed in by mpcx_set_stream
-    char err[512];
-    // grow-only device workspace reused by the solver / fused step (never freed between calls)
-    void *ws;
-    size_t ws_bytes;
-    // launch order of the solver's workgroups: the previous solve's iteration counts (library-owned copy) sorted
-    // longest first; valid only for a following solve of the same batch size
-    int32_t *prev_iters, *order, *pred_hist;     // prev_iters: the prediction the order is sorted by; pred_hist: the last solves' counts
-    int order_S, order_valid, order_cap;
-    // the same state for the SECOND half of a split update (mpcx_mpc_update_batch runs the two halves of a large batch as two
-    // chains on two streams: each half is its own sequence of solves of its own batch size)
-    struct OrderState { int32_t *prev_iters, *order, *pred_hist; int order_S, order_valid, order_cap; } ord2;
-    int cur_lane;             // 0: the state above; 1: ord2 (set around the second half's solves only)
+    int device = 0;
+    hipStream_t stream = nullptr;      // stream used by the host-pointer entry points
+    bool own_stream = false;           // created by the library (mpcx_create / MPCX_STREAM_PRIVATE), not handed in by mpcx_set_stream
+    char err[512] = "";
+    DeviceBuf<char> ws;                // workspace of the solver / fused step of the host-pointer entry points (ctx_workspace)
+    // launch-order state of the context's solves, and of the SECOND half of a split update (mpcx_mpc_update_batch runs the two
+    // halves of a large batch as two chains on two streams: each half is its own sequence of solves of its own batch size)
+    LaunchOrder ord[2];
     // regularisation counts of the last solve ([S][2] int32, include/mpcx.h: mpcx_solve_regularised)
-    int32_t *nreg;
-    int nreg_cap, nreg_S;
-    int nreg_first, nreg_total;        // split update: this solve's satellites start at nreg_first of a record of nreg_total
-    hipStream_t stream2;               // the second half's stream and the events that fork / join it (created on first use)
-    hipEvent_t ev_fork, ev_join, ev_stagger;
-    int32_t *counter;         // ring of work-queue counters of the solver's persistent workgroups (one per launch in flight)
-    unsigned launch_seq;      // solves launched so far: selects the counter
-    int n_slots;              // single-wave workgroups of solve_kernel the device holds at once (compute units x 8)
-    double *red;              // shared-tf launches: reduction slots + arrival counter + abort flag
-    int red_cap, coop_max;    // coop_max: workgroups of solve_shared_kernel resident at once (0: not asked yet, -1: unsupported)
-    int tp_max;               // satellites the time-parallel kernel holds at once (0: not asked yet, -1: query failed)
-    int trace_on;             // mpcx_trace_enable: every host-pointer call records where its time went (last_trace), without the env switch
-    double last_trace[MPCX_TRACE_N];   // the last traced call's record (include/mpcx.h: MPCX_TR_*)
+    DeviceBuf<int32_t> nreg;
+    int nreg_S = 0;                    // satellites in that record
+    hipStream_t stream2 = nullptr;     // the second half's stream and the events that fork / join it (created on first use)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_stagger = nullptr;
+    int32_t *counter = nullptr;        // ring of work-queue counters of the solver's persistent workgroups (one per launch in flight)
+    unsigned launch_seq = 0;           // solves launched so far: selects the counter
+    int n_slots = 0;                   // single-wave workgroups of solve_kernel the device holds at once (compute units x 8)
+    DeviceBuf<double> red;             // shared-tf launches: reduction slots, then arrival counter + abort flag in the last two elements
+    int coop_max = 0;                  // workgroups of solve_shared_kernel resident at once (0: not asked yet, -1: unsupported)
+    int tp_max = 0;                    // satellites the time-parallel kernel holds at once (0: not asked yet, -1: query failed)
+    int trace_on = 0;                  // mpcx_trace_enable: every host-pointer call records where its time went (last_trace), without the env switch
+    double last_trace[MPCX_TRACE_N] = {};      // the last traced call's record (include/mpcx.h: MPCX_TR_*)
     StagePool pool_dev, pool_host;     // staging of the host-pointer entry points
-    HostCopier *copier;                // worker threads of the pageable <-> page-locked copies (created on first use)
+    HostCopier *copier = nullptr;      // worker threads of the pageable <-> page-locked copies (created on first use)
     std::vector<hipEvent_t> events;    // one per download of a host-pointer call: its copy-out starts when ITS transfer is done
 };
 
@@ -179,12 +201,8 @@ inline int ctx_fail(mpcx_ctx *ctx, int code, const char *msg)
 // Device workspace of at least `bytes` (grow-only).  Returns nullptr on failure.
 inline void *ctx_workspace(mpcx_ctx *ctx, size_t bytes)
 {
-    if (bytes <= ctx->ws_bytes) return ctx->ws;
-    if (ctx->ws) { (void)hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) { ctx_fail(ctx, MPCX_E_NOMEM, "workspace allocation failed"); return nullptr; }
-    ctx->ws = p; ctx->ws_bytes = bytes;
-    return p;
+    if (ctx->ws.reserve(bytes) != hipSuccess) { ctx_fail(ctx, MPCX_E_NOMEM, "workspace allocation failed"); return nullptr; }
+    return ctx->ws.p;
 }
 
 // Diagnostic of the host-pointer path (MPCX_HOST_TRACE=<ms> in the environment): a call that takes longer than <ms>

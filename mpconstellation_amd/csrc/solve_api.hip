@@ -1,13 +1,14 @@
 // solve_api.hip -- the C entry points of the batched solve, the fused MPC step, one SCP iteration and the whole
-// OptimalController.update (include/mpcx.h): argument checks, staging of host buffers, launch order bookkeeping.  The kernels
-// they launch are in solve.hip / solve2w.hip, reached through the launchers of solve_launch.hpp.
+// OptimalController.update (include/mpcx.h): argument checks, the choice of the kernel, staging of host buffers, launch order
+// bookkeeping.  The kernels they launch are in solve.hip / solve2w.hip / solve_lds.hip / solve_tp.hip, reached through the
+// launchers of solve_launch.hpp.
 #include <vector>
 #include "mpcx_host.hpp"
 #include "solve_launch.hpp"
 
-
 using namespace mpcx;
 
+// ---- which kernel a batch takes: the limits, the choice (choose_kernel) ---------------------------------------------------
 #ifndef MPCX_TWO_WAVE_MAX
 #define MPCX_TWO_WAVE_MAX 1024      // two waves per satellite pay up to one satellite per SIMD (profiles/r03/batch_size_sweep.txt)
 #endif
@@ -20,6 +21,63 @@ constexpr int kTimeParallelMax = 128;
 constexpr int kTimeParallelMinK = 24;
 constexpr int kCounterRing = 64;    // work-queue counters per context: solves in flight at once on different streams
 
+enum class Kernel { Shared, TimeParallel, Lds, TwoWave, OneWave };
+
+static bool time_parallel_shape(int S, int K) { return S <= kTimeParallelMax && K >= kTimeParallelMinK; }
+
+// small batches -- at most one satellite per SIMD -- go to the two-wave build (solve2w.hip): a second wave per satellite shares
+// the factorisation; results are bit for bit the one-wave kernel's (-ffp-contract=on, build.py;
+// tests/test_full_size_gpu.py::test_two_wave_small_batch_kernel).  MPCX_SOLVE_ONE_WAVE keeps the one-wave kernel.
+static Kernel wave_kernel(int S, int flags) { return S <= kTwoWaveMax && !(flags & MPCX_SOLVE_ONE_WAVE) ? Kernel::TwoWave : Kernel::OneWave; }
+
+// Launches nothing.  (TimeParallel with ctx->tp_max < 0: the occupancy query failed, which the solve reports.  Lds: the launcher
+// still declines a horizon whose working set does not fit, and the batch takes its wave_kernel.)
+static Kernel choose_kernel(mpcx_ctx *ctx, int S, int K, int flags)
+{
+    if (flags & MPCX_SOLVE_SHARED_TF) return Kernel::Shared;
+    if ((flags & MPCX_SOLVE_TIME_PARALLEL) && time_parallel_shape(S, K)) {
+        if (ctx->tp_max == 0) { const int per_cu = mpcxtp_blocks_per_cu(); ctx->tp_max = per_cu > 0 ? per_cu * (ctx->n_slots / 8) / TP_MAXSEG : -1; }
+        // (a device that cannot hold the batch's workgroups at once -- fewer compute units, another partition mode -- solves it with
+        //  the default kernels, as it does a batch above kTimeParallelMax: the flag asks for speed, never for an error)
+        if (ctx->tp_max < 0 || ((S + 7) / 8) * 8 <= ctx->tp_max) return Kernel::TimeParallel;
+    }
+    // at most one satellite per compute unit: the LDS-resident build (solve_lds.hip), if the horizon's working set fits
+    if (S <= ctx->n_slots / 8 && !(flags & (MPCX_SOLVE_ONE_WAVE | MPCX_SOLVE_NO_LDS))) return Kernel::Lds;
+    return wave_kernel(S, flags);
+}
+
+// ---- LaunchOrder (mpcx_host.hpp) -----------------------------------------------------------------------------------------
+hipError_t LaunchOrder::grow(int batch)
+{
+    if (S == batch) return hipSuccess;           // (S != 0: the arrays hold a batch of S)
+    S = valid = 0;
+    hipError_t e = pred.reserve(batch);
+    if (e == hipSuccess) e = hist.reserve((size_t)kPredHist * batch);
+    if (e == hipSuccess) e = order.reserve(batch);
+    if (e == hipSuccess) S = batch;
+    return e;
+}
+
+const int32_t *LaunchOrder::sorted(hipStream_t st)
+{
+    if (valid) mpcx_launch::launch_order(S, pred.p, order.p, st);
+    return valid ? order.p : nullptr;
+}
+
+void LaunchOrder::record(const int32_t *iters, hipStream_t st)
+{
+    // (valid counts the solves of this batch size recorded so far)
+    const int slot = valid % kPredHist, n_valid = valid + 1 < kPredHist ? valid + 1 : kPredHist;
+    mpcx_launch::update_prediction(S, iters, hist.p, pred.p, slot, n_valid, st);
+    valid += 1;
+    if (valid >= 2 * kPredHist) valid -= kPredHist;     // (keeps slot and n_valid as they are)
+}
+
+// A solve's place in a sequence of solves: whose launch-order state it continues, and where its satellites' regularisation
+// counts go -- from satellite `first` on in a record of `total` satellites.  A solve on its own: {&ctx->ord[0], 0, S}; the
+// halves of a split update (mpcx_mpc_update_batch) share one record and have a LaunchOrder each.
+struct SolvePlace { LaunchOrder *ord; int first, total; };
+
 static SolveOpts to_dev_opts(const mpcx_solve_opts *o)
 {
     SolveOpts d;
@@ -31,8 +89,6 @@ static SolveOpts to_dev_opts(const mpcx_solve_opts *o)
     d.tp_selftest = (o->flags & MPCX_SOLVE_TP_SELFTEST_DEAD) ? 1 : 0;
     return d;
 }
-
-
 
 extern "C" int mpcx_constraint_terms_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
                                          const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT,
@@ -66,19 +122,19 @@ extern "C" int mpcx_constraint_terms(mpcx_ctx *ctx, int S, int K, const double *
 extern "C" int mpcx_solve_regularised_dev(mpcx_ctx *ctx, int S, int32_t *out, void *stream)
 {
     if (!ctx || !out) return MPCX_E_BADARG;
-    if (S < 1 || S != ctx->nreg_S || !ctx->nreg) return ctx_fail(ctx, MPCX_E_BADARG, "solve_regularised: S must be the batch size of the last solve on this context");
+    if (S < 1 || S != ctx->nreg_S || !ctx->nreg.p) return ctx_fail(ctx, MPCX_E_BADARG, "solve_regularised: S must be the batch size of the last solve on this context");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    MPCX_HIP(ctx, hipMemcpyAsync(out, ctx->nreg, (size_t)S * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    MPCX_HIP(ctx, hipMemcpyAsync(out, ctx->nreg.p, (size_t)S * 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MPCX_OK;
 }
 
 extern "C" int mpcx_solve_regularised(mpcx_ctx *ctx, int S, int32_t *out)
 {
     if (!ctx || !out) return MPCX_E_BADARG;
-    if (S < 1 || S != ctx->nreg_S || !ctx->nreg) return ctx_fail(ctx, MPCX_E_BADARG, "solve_regularised: S must be the batch size of the last solve on this context");
+    if (S < 1 || S != ctx->nreg_S || !ctx->nreg.p) return ctx_fail(ctx, MPCX_E_BADARG, "solve_regularised: S must be the batch size of the last solve on this context");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     // (the host-pointer solves ran on the context's stream and have completed; a _dev solve is ordered by its stream)
-    MPCX_HIP(ctx, hipMemcpy(out, ctx->nreg, (size_t)S * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    MPCX_HIP(ctx, hipMemcpy(out, ctx->nreg.p, (size_t)S * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MPCX_OK;
 }
 
@@ -101,68 +157,22 @@ extern "C" size_t mpcx_solve_workspace_bytes(int S, int K)
 extern "C" size_t mpcx_solve_workspace_bytes_ctx(const mpcx_ctx *ctx, int S, int K)
 {
     const int slots = (ctx && S > ctx->n_slots) ? ctx->n_slots : S;
-    const int slots_tp = (S <= kTimeParallelMax && K >= kTimeParallelMinK) ? S : 0;
+    const int slots_tp = time_parallel_shape(S, K) ? S : 0;
     const size_t a = (size_t)slots * ws_doubles(K), b = (size_t)slots_tp * ws_doubles_tp(K);
     return (a > b ? a : b) * sizeof(double);
 }
 
-extern "C" int mpcx_solve_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
-                                           const double *ubar, const double *tf, const double *consts,
-                                           const double *r_des, const mpcx_solve_opts *opts, double *X, double *U,
-                                           double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
-                                           void *workspace, void *stream)
+static int solve_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
+                        const double *ubar, const double *tf, const double *consts, const double *r_des, const mpcx_solve_opts *opts,
+                        double *X, double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                        void *workspace, hipStream_t st)
 {
-    if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "solve: need S>=1, K>=3 and options");
     if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "solve: workspace of mpcx_solve_workspace_bytes(S,K) required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    SolveArgs a;
-    a.S = S; a.K = K; a.Ks = Ks; a.stage = stage; a.xbar = xbar; a.ubar = ubar; a.tfbar = tf; a.consts = consts; a.r_des = r_des;
-    a.o = to_dev_opts(opts);
-    a.X = X; a.U = U; a.NU = NU; a.tf_out = tf_out; a.kkt = kkt; a.status = status; a.iters = iters;
-    a.ws = (double *)workspace; a.ws_stride = ws_doubles(K);
-    // per-satellite regularisation counts of this solve (library-owned, grow-only; read back by mpcx_solve_regularised)
-    // (a split update -- two halves of one batch solved on two streams -- has sized the record for the whole batch beforehand and
-    //  names this half's place in it: nreg_first / nreg_total)
-    const int nreg_need = ctx->nreg_total > 0 ? ctx->nreg_total : S;
-    if (ctx->nreg_cap < nreg_need) {
-        if (ctx->nreg) (void)hipFree(ctx->nreg);
-        ctx->nreg = nullptr; ctx->nreg_cap = 0;
-        MPCX_HIP(ctx, hipMalloc((void **)&ctx->nreg, (size_t)nreg_need * 2 * sizeof(int32_t)));
-        ctx->nreg_cap = nreg_need;
-    }
-    a.nreg = ctx->nreg + (ctx->nreg_total > 0 ? 2 * (size_t)ctx->nreg_first : 0); ctx->nreg_S = nreg_need;
-    // longest-first launch order from the previous solve's iteration counts (include/mpcx.h, MPCX_SOLVE_INDEX_ORDER)
-    // (a batch the device holds at once has no order to choose: every satellite starts at time 0)
-    const bool adaptive = !(opts->flags & MPCX_SOLVE_INDEX_ORDER) && S > ctx->n_slots;
-    a.order = nullptr;
-    // the launch-order state of this sequence of solves: the context's, or -- second half of a split update -- its twin
-    int32_t *&o_prev = ctx->cur_lane ? ctx->ord2.prev_iters : ctx->prev_iters, *&o_order = ctx->cur_lane ? ctx->ord2.order : ctx->order;
-    int32_t *&o_hist = ctx->cur_lane ? ctx->ord2.pred_hist : ctx->pred_hist;
-    int &o_S = ctx->cur_lane ? ctx->ord2.order_S : ctx->order_S, &o_valid = ctx->cur_lane ? ctx->ord2.order_valid : ctx->order_valid;
-    int &o_cap = ctx->cur_lane ? ctx->ord2.order_cap : ctx->order_cap;
-    if (adaptive) {
-        // grow-only buffers (a smaller batch reuses them: no free / allocation, hence no implicit device synchronisation,
-        // when ConstellationMPC alternates group sizes on one context); the stored counts are valid only for a following
-        // solve of the same batch size
-        if (o_cap < S) {
-            if (o_prev) (void)hipFree(o_prev);
-            if (o_hist) (void)hipFree(o_hist);
-            o_hist = nullptr;
-            if (o_order) (void)hipFree(o_order);
-            o_prev = o_order = nullptr; o_cap = 0; o_S = 0; o_valid = 0;
-            MPCX_HIP(ctx, hipMalloc((void **)&o_prev, (size_t)S * sizeof(int32_t)));
-            MPCX_HIP(ctx, hipMalloc((void **)&o_hist, (size_t)kPredHist * S * sizeof(int32_t)));
-            MPCX_HIP(ctx, hipMalloc((void **)&o_order, (size_t)S * sizeof(int32_t)));
-            o_cap = S;
-        }
-        if (o_S != S) { o_S = S; o_valid = 0; }
-        if (o_valid) {
-            mpcx_launch::launch_order(S, o_prev, o_order, (hipStream_t)stream);
-            a.order = o_order;
-        }
-    }
-    if (opts->flags & MPCX_SOLVE_SHARED_TF) {
+    // everything that can reject the call, before anything of the context changes or is enqueued
+    Kernel kern = choose_kernel(ctx, S, K, opts->flags);
+    if (kern == Kernel::Shared) {
         // one final time for the whole batch: a cooperative launch, one workgroup per satellite, all of them resident
         if (Ks) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF needs the same node count for every satellite (no ragged batch)");
         if (opts->flags & MPCX_SOLVE_FIXED_TF) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF and MPCX_SOLVE_FIXED_TF exclude each other");
@@ -174,68 +184,78 @@ extern "C" int mpcx_solve_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const in
         }
         if (ctx->coop_max < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: the device does not support cooperative launches (MPCX_SOLVE_SHARED_TF)");
         if (S > ctx->coop_max) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF takes at most as many satellites as the device holds workgroups at once");
-        if (ctx->red_cap < S) {
-            if (ctx->red) (void)hipFree(ctx->red);
-            ctx->red = nullptr; ctx->red_cap = 0;
-            MPCX_HIP(ctx, hipMalloc((void **)&ctx->red, ((size_t)2 * S * GR_N + 2) * sizeof(double)));
-            ctx->red_cap = S;
-        }
-        a.red = ctx->red;
-        a.arrive = (int32_t *)(ctx->red + (size_t)2 * ctx->red_cap * GR_N);
-        a.abort_flag = a.arrive + 1;
-        a.counter = nullptr; a.order = nullptr;
-        MPCX_HIP(ctx, hipMemsetAsync(a.arrive, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
-        MPCX_HIP(ctx, mpcx_launch::solve_shared(a, (hipStream_t)stream));
-        o_valid = 0;
-        return MPCX_OK;
     }
-    // the launch's own work-queue counter: one of a ring, so that two solves of one context enqueued on different streams
-    // do not share (and reset) one queue -- each queue position must go to exactly one workgroup of ITS launch
-    if (!ctx->counter) MPCX_HIP(ctx, hipMalloc((void **)&ctx->counter, kCounterRing * sizeof(int32_t)));
-    a.counter = ctx->counter + (ctx->launch_seq++ % kCounterRing);
-    MPCX_HIP(ctx, hipMemsetAsync(a.counter, 0, sizeof(int32_t), (hipStream_t)stream));
-    // (the workspace is the caller's: slot b of THIS call's buffer)
+    if (kern == Kernel::TimeParallel && ctx->tp_max < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: occupancy query of the time-parallel kernel failed");
+    SolveArgs a;
+    a.S = S; a.K = K; a.Ks = Ks; a.stage = stage; a.xbar = xbar; a.ubar = ubar; a.tfbar = tf; a.consts = consts; a.r_des = r_des;
+    a.o = to_dev_opts(opts);
+    a.X = X; a.U = U; a.NU = NU; a.tf_out = tf_out; a.kkt = kkt; a.status = status; a.iters = iters;
+    a.ws = (double *)workspace; a.ws_stride = ws_doubles(K);         // (the workspace is the caller's: slot b of THIS call's buffer)
+    // per-satellite regularisation counts of this solve (library-owned; read back by mpcx_solve_regularised)
+    MPCX_HIP(ctx, ctx->nreg.reserve((size_t)at.total * 2));
+    a.nreg = ctx->nreg.p + 2 * (size_t)at.first; ctx->nreg_S = at.total;
+    // longest-first launch order from the previous solves' iteration counts (include/mpcx.h, MPCX_SOLVE_INDEX_ORDER)
+    // (a batch the device holds at once has no order to choose: every satellite starts at time 0)
+    const bool adaptive = !(opts->flags & MPCX_SOLVE_INDEX_ORDER) && S > ctx->n_slots;
+    a.order = nullptr;
+    if (adaptive) {
+        MPCX_HIP(ctx, at.ord->grow(S));
+        a.order = at.ord->sorted(st);
+    }
     const int slots = S < ctx->n_slots ? S : ctx->n_slots;
-    // small batches -- at most one satellite per SIMD -- go to the two-wave build (solve2w.hip): a second wave per
-    // satellite shares the factorisation; results are bit for bit the one-wave kernel's (-ffp-contract=on, build.py;
-    // tests/test_full_size_gpu.py::test_two_wave_small_batch_kernel).  MPCX_SOLVE_ONE_WAVE keeps the one-wave kernel.
-    // at most one satellite per compute unit: the LDS-resident build (solve_lds.hip), if the horizon's working set fits
-    int lds = 1;
-    bool tp = (opts->flags & MPCX_SOLVE_TIME_PARALLEL) && S <= kTimeParallelMax && K >= kTimeParallelMinK;
-    if (tp) {
-        if (ctx->tp_max == 0) { const int per_cu = mpcxtp_blocks_per_cu(); ctx->tp_max = per_cu > 0 ? per_cu * (ctx->n_slots / 8) / TP_MAXSEG : -1; }
-        if (ctx->tp_max < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: occupancy query of the time-parallel kernel failed");
-        // (a device that cannot hold the batch's workgroups at once -- fewer compute units, another partition mode -- solves it with
-        //  the default kernels, as it does a batch above kTimeParallelMax: the flag asks for speed, never for an error)
-        if (((S + 7) / 8) * 8 > ctx->tp_max) tp = false;
+    if (kern == Kernel::Shared) { a.counter = nullptr; a.order = nullptr; }     // (every workgroup has its satellite: no queue, no order)
+    else {
+        // the launch's own work-queue counter: one of a ring, so that two solves of one context enqueued on different streams
+        // do not share (and reset) one queue -- each queue position must go to exactly one workgroup of ITS launch
+        if (!ctx->counter) MPCX_HIP(ctx, hipMalloc((void **)&ctx->counter, kCounterRing * sizeof(int32_t)));
+        a.counter = ctx->counter + (ctx->launch_seq++ % kCounterRing);
+        MPCX_HIP(ctx, hipMemsetAsync(a.counter, 0, sizeof(int32_t), st));
     }
-    if (tp) {
-        // the time-parallel kernel: four workgroups per satellite, each on its own compute unit while the batch is that small,
-        // all resident (they wait for each other); its own slot size, one slot per satellite; the satellites' mailboxes zeroed
+    switch (kern) {
+    case Kernel::Shared:
+        // reduction slots of the S workgroups, then the arrival counter and the abort flag
+        MPCX_HIP(ctx, ctx->red.reserve((size_t)2 * S * GR_N + 2));
+        a.red = ctx->red.p; a.arrive = (int32_t *)(a.red + ctx->red.cap - 2); a.abort_flag = a.arrive + 1;
+        MPCX_HIP(ctx, hipMemsetAsync(a.arrive, 0, 2 * sizeof(int32_t), st));
+        MPCX_HIP(ctx, mpcx_launch::solve_shared(a, st));
+        at.ord->invalidate();
+        return MPCX_OK;
+    case Kernel::TimeParallel:
+        // four workgroups per satellite, each on its own compute unit while the batch is that small, all resident (they wait
+        // for each other); its own slot size, one slot per satellite; the satellites' mailboxes zeroed
         a.ws_stride = ws_doubles_tp(K);
-        MPCX_HIP(ctx, hipMemset2DAsync((double *)workspace + tp_mail_offset(K), a.ws_stride * sizeof(double), 0, TP_MAIL_N * sizeof(double), (size_t)S, (hipStream_t)stream));
-        if (mpcxtp_launch(&a, sizeof a, S, (hipStream_t)stream) != 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: time-parallel launch failed");
-        lds = 0;
-    } else
-    if (S <= ctx->n_slots / 8 && !(opts->flags & (MPCX_SOLVE_ONE_WAVE | MPCX_SOLVE_NO_LDS))) {
-        lds = mpcxl_launch(&a, sizeof a, slots, (hipStream_t)stream);
-        if (lds < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: LDS-resident launch failed");
+        MPCX_HIP(ctx, hipMemset2DAsync((double *)workspace + tp_mail_offset(K), a.ws_stride * sizeof(double), 0, TP_MAIL_N * sizeof(double), (size_t)S, st));
+        if (mpcxtp_launch(&a, sizeof a, S, st) != 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: time-parallel launch failed");
+        break;
+    case Kernel::Lds: {
+        const int fit = mpcxl_launch(&a, sizeof a, slots, st);
+        if (fit < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: LDS-resident launch failed");
+        if (fit == 0) break;
+        kern = wave_kernel(S, opts->flags);                          // (1: the working set does not fit, nothing was launched)
+    }   [[fallthrough]];
+    case Kernel::TwoWave:
+    case Kernel::OneWave:
+        if (kern == Kernel::OneWave) mpcx_launch::solve(a, slots, st);
+        else if (mpcx2w_launch(&a, sizeof a, slots, st) != 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: two-wave launch failed");
+        break;
     }
-    if (lds == 0) {
-    } else if (S <= kTwoWaveMax && !(opts->flags & MPCX_SOLVE_ONE_WAVE)) {
-        if (mpcx2w_launch(&a, sizeof a, slots, (hipStream_t)stream) != 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: two-wave launch failed");
-    } else
-        mpcx_launch::solve(a, slots, (hipStream_t)stream);
     MPCX_HIP(ctx, hipGetLastError());
     if (adaptive) {
-        // (order_valid counts the solves of this batch size recorded so far)
-        const int slot = o_valid % kPredHist, n_valid = o_valid + 1 < kPredHist ? o_valid + 1 : kPredHist;
-        mpcx_launch::update_prediction(S, iters, o_hist, o_prev, slot, n_valid, (hipStream_t)stream);
+        at.ord->record(iters, st);
         MPCX_HIP(ctx, hipGetLastError());
-        o_valid += 1;
-        if (o_valid >= 2 * kPredHist) o_valid -= kPredHist;     // (keeps slot and n_valid as they are)
     }
     return MPCX_OK;
+}
+
+extern "C" int mpcx_solve_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
+                                           const double *ubar, const double *tf, const double *consts,
+                                           const double *r_des, const mpcx_solve_opts *opts, double *X, double *U,
+                                           double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                                           void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return solve_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, X, U, NU, tf_out, status, iters,
+                        kkt, workspace, (hipStream_t)stream);
 }
 
 extern "C" int mpcx_solve_batch_dev(mpcx_ctx *ctx, int S, int K, const double *stage, const double *xbar,
@@ -248,6 +268,32 @@ extern "C" int mpcx_solve_batch_dev(mpcx_ctx *ctx, int S, int K, const double *s
                                        iters, kkt, workspace, stream);
 }
 
+// the fused step's workspace = [stage records | int32 discretize status | solver workspace]: where the parts begin, in doubles
+struct StepLayout {
+    size_t status_at, solver_at;
+    StepLayout(int S, int K) : status_at((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES), solver_at(status_at + ((size_t)S + 1) / 2 + 1) {}
+    size_t header_bytes() const { return solver_at * sizeof(double); }
+};
+
+static int mpc_step_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                           const double *tf, const double *consts, const double *r_des, int flags, double max_step,
+                           const mpcx_solve_opts *opts, double *X, double *U, double *NU, double *tf_out, int32_t *status,
+                           int32_t *iters, double *kkt, void *workspace, hipStream_t st)
+{
+    if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_step: workspace of mpcx_mpc_step_workspace_bytes(S,K) required");
+    const StepLayout lay(S, K);
+    double *stage = (double *)workspace, *sws = stage + lay.solver_at;
+    int32_t *dstat = (int32_t *)(stage + lay.status_at);
+    // (a ragged batch's thrust tables have as many columns as the satellite has nodes)
+    int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, xbar, ubar, tf, consts, flags, max_step, stage, dstat, st);
+    if (rc) return rc;
+    rc = solve_ragged(ctx, at, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, X, U, NU, tf_out, status, iters, kkt, sws, st);
+    if (rc) return rc;
+    mpcx_launch::merge_status(S, dstat, status, st);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
 extern "C" int mpcx_mpc_step_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
                                               const double *tf, const double *consts, const double *r_des, int flags,
                                               double max_step, const mpcx_solve_opts *opts, double *X, double *U,
@@ -255,21 +301,8 @@ extern "C" int mpcx_mpc_step_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const
                                               void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_step: workspace of mpcx_mpc_step_workspace_bytes(S,K) required");
-    // workspace = [stage records | int32 discretize status | solver workspace]
-    double *stage = (double *)workspace;
-    const size_t nstage = (size_t)S * (K - 1) * MPCX_STAGE_DOUBLES;
-    int32_t *dstat = (int32_t *)(stage + nstage);
-    double *sws = stage + nstage + ((size_t)S + 1) / 2 + 1;
-    // (a ragged batch's thrust tables have as many columns as the satellite has nodes)
-    int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, xbar, ubar, tf, consts, flags, max_step, stage, dstat, stream);
-    if (rc) return rc;
-    rc = mpcx_solve_batch_ragged_dev(ctx, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, X, U, NU, tf_out, status, iters,
-                                     kkt, sws, stream);
-    if (rc) return rc;
-    mpcx_launch::merge_status(S, dstat, status, (hipStream_t)stream);
-    MPCX_HIP(ctx, hipGetLastError());
-    return MPCX_OK;
+    return mpc_step_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, xbar, ubar, tf, consts, r_des, flags, max_step, opts, X, U, NU, tf_out,
+                           status, iters, kkt, workspace, (hipStream_t)stream);
 }
 
 extern "C" int mpcx_mpc_step_batch_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *ubar,
@@ -284,15 +317,32 @@ extern "C" int mpcx_mpc_step_batch_dev(mpcx_ctx *ctx, int S, int K, const double
 
 extern "C" size_t mpcx_mpc_step_workspace_bytes(int S, int K)
 {
-    return ((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES + ((size_t)S + 1) / 2 + 1) * sizeof(double) +
-           mpcx_solve_workspace_bytes(S, K);
+    return StepLayout(S, K).header_bytes() + mpcx_solve_workspace_bytes(S, K);
 }
 
 extern "C" size_t mpcx_mpc_step_workspace_bytes_ctx(const mpcx_ctx *ctx, int S, int K)
 {
-    return ((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES + ((size_t)S + 1) / 2 + 1) * sizeof(double) +
-           mpcx_solve_workspace_bytes_ctx(ctx, S, K);
+    return StepLayout(S, K).header_bytes() + mpcx_solve_workspace_bytes_ctx(ctx, S, K);
 }
+
+// The device result set of a solve for the host-pointer entry points.
+struct SolveResults {
+    const size_t S, n7, n3;
+    double *X, *U, *NU, *tf_out, *kkt;
+    int32_t *status, *iters;
+    // tf_fixed: the caller's tf_out of a MPCX_SOLVE_FIXED_TF solve, where it is an input too (include/mpcx.h); null otherwise
+    SolveResults(DeviceArena &ar, int S_, int K, const double *tf_fixed) : S(S_), n7(S * 7 * K), n3(S * 3 * K)
+    {
+        X = ar.alloc<double>(n7); U = ar.alloc<double>(n3); NU = ar.alloc<double>(n7);
+        tf_out = tf_fixed ? ar.upload(tf_fixed, S) : ar.alloc<double>(S); kkt = ar.alloc<double>(S);
+        status = ar.alloc<int32_t>(S); iters = ar.alloc<int32_t>(S);
+    }
+    void download(DeviceArena &ar, double *hX, double *hU, double *hNU, double *htf, int32_t *hstatus, int32_t *hiters, double *hkkt) const
+    {
+        ar.download(hX, X, n7); ar.download(hU, U, n3); ar.download(hNU, NU, n7);
+        ar.download(htf, tf_out, S); ar.download(hstatus, status, S); ar.download(hiters, iters, S); ar.download(hkkt, kkt, S);
+    }
+};
 
 extern "C" int mpcx_mpc_step_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
                                           const double *tf, const double *consts, const double *r_des, int flags,
@@ -308,16 +358,12 @@ extern "C" int mpcx_mpc_step_batch_ragged(mpcx_ctx *ctx, int S, int K, const int
     double *dx = ar.upload(xbar, (size_t)S * 7 * K), *du = ar.upload(ubar, (size_t)S * 3 * K);
     double *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr;
-    double *dX = ar.alloc<double>((size_t)S * 7 * K), *dU = ar.alloc<double>((size_t)S * 3 * K);
-    const bool fixed_tf = (opts->flags & MPCX_SOLVE_FIXED_TF) != 0;          // tf_out is an input too (include/mpcx.h)
-    double *dNU = ar.alloc<double>((size_t)S * 7 * K), *dtfo = fixed_tf ? ar.upload(tf_out, S) : ar.alloc<double>(S), *dk = ar.alloc<double>(S);
-    int32_t *dst = ar.alloc<int32_t>(S), *dit = ar.alloc<int32_t>(S);
+    SolveResults r(ar, S, K, (opts->flags & MPCX_SOLVE_FIXED_TF) ? tf_out : nullptr);
     if (ar.failed()) return ar.code();
-    int rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, flags, max_step, opts, dX, dU, dNU, dtfo, dst,
-                                            dit, dk, ws, ctx->stream);
+    int rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, flags, max_step, opts, r.X, r.U, r.NU, r.tf_out, r.status,
+                                            r.iters, r.kkt, ws, ctx->stream);
     if (rc) return rc;
-    ar.download(X, dX, (size_t)S * 7 * K); ar.download(U, dU, (size_t)S * 3 * K); ar.download(NU, dNU, (size_t)S * 7 * K);
-    ar.download(tf_out, dtfo, S); ar.download(status, dst, S); ar.download(iters, dit, S); ar.download(kkt, dk, S);
+    r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     return ar.finish();
 }
 
@@ -357,9 +403,8 @@ extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, cons
     double *de = (ctrl_kind == MPCX_CTRL_SEQUENCE && end_tau) ? ar.upload(end_tau, S) : nullptr;
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr, *dKus = Kus ? ar.upload(Kus, S) : nullptr;
     double *dx = ar.alloc<double>((size_t)S * 7 * K), *du = ar.alloc<double>((size_t)S * 3 * K);
-    double *dX = ar.alloc<double>((size_t)S * 7 * K), *dU = ar.alloc<double>((size_t)S * 3 * K), *dNU = ar.alloc<double>((size_t)S * 7 * K);
-    double *dtfo = ar.alloc<double>(S), *dk = ar.alloc<double>(S);
-    int32_t *dst = ar.alloc<int32_t>(S), *dit = ar.alloc<int32_t>(S), *dps = ar.alloc<int32_t>(S), *dpn = ar.alloc<int32_t>(S);
+    SolveResults r(ar, S, K, nullptr);
+    int32_t *dps = ar.alloc<int32_t>(S), *dpn = ar.alloc<int32_t>(S);
     if (ar.failed()) return ar.code();
     if (Ks) {                                                                                        // the unused columns
         MPCX_HIP(ctx, hipMemsetAsync(dx, 0, (size_t)S * 7 * K * sizeof(double), ctx->stream));
@@ -368,17 +413,30 @@ extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, cons
     int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, K, dKs, dy0, dtf, dc, prop_flags, ctrl_kind, dv, Ku, dKus, de, prop_max_step,
                                                     dx, du, dps, dpn, ctx->stream);
     if (rc) return rc;
-    rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, disc_flags, disc_max_step, opts, dX, dU, dNU, dtfo, dst,
-                                        dit, dk, ws, ctx->stream);
+    rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, disc_flags, disc_max_step, opts, r.X, r.U, r.NU, r.tf_out,
+                                        r.status, r.iters, r.kkt, ws, ctx->stream);
     if (rc) return rc;
     if (xbar_out) ar.download(xbar_out, dx, (size_t)S * 7 * K);
     if (ubar_out) ar.download(ubar_out, du, (size_t)S * 3 * K);
-    ar.download(X, dX, (size_t)S * 7 * K); ar.download(U, dU, (size_t)S * 3 * K); ar.download(NU, dNU, (size_t)S * 7 * K);
-    ar.download(tf_out, dtfo, S); ar.download(status, dst, S); ar.download(iters, dit, S); ar.download(kkt, dk, S);
+    r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     ar.download(prop_status, dps, S);
     return ar.finish();
 }
 
+// MPCX_UPDATE_SPLIT=1 / 2 (default 0): the batch as TWO chains -- the two halves of the satellites, each rollout -> discretise ->
+// solve -> ... -> flight on its own stream (satellites are independent: every satellite gets the bits the one-chain call
+// gives it, tests/test_mpc_loop_gpu.py::test_split_update_two_chains_equal_one), so that one half's rollouts (a sequential
+// chain of ~1000 RK steps on a quarter of the SIMDs whatever S: 13.5 of 79.5 ms of kernels per two segments at 4096
+// satellites) run under the other half's solve; =2 also delays the second chain's start until the first has reached its
+// first solve.  Round-4 verdict item 5; built, measured (profiles/r05/update_split.txt) and NOT the default: the kernels do
+// overlap, and the closed loop is exactly as fast -- 45.0 against 45.1 ms per segment at 4096 satellites, 80.9 / 79.7 at
+// 8192, 28.1 / 33.1 at 2048 -- because two launches of 2048 satellites fill the 2048 wave slots in index order, which gives
+// back what the longest-first order of ONE launch of 4096 had gained (9.5 against 10.3 ms per solve).
+static int update_split_mode()
+{
+    const char *e = getenv("MPCX_UPDATE_SPLIT");                    // (read per call: a test switches it inside one process)
+    return e ? atoi(e) : 0;
+}
 
 // OptimalController.update (control.py:170-235) for S satellites as ONE call, everything between the first input and the
 // last result resident in HBM (include/mpcx.h).
@@ -397,17 +455,7 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
     if (y_sim && (sim_n_eval < 1 || !(sim_tf > 0.0) || !(sim_interval > 0.0) || !sim_status))
         return ctx_fail(ctx, MPCX_E_BADARG, "mpc_update: segment flight needs sim_tf>0, sim_interval>0, sim_n_eval>=1, sim_status");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    // MPCX_UPDATE_SPLIT=1 / 2 (default 0): the batch as TWO chains -- the two halves of the satellites, each rollout -> discretise ->
-    // solve -> ... -> flight on its own stream (satellites are independent: every satellite gets the bits the one-chain call
-    // gives it, tests/test_mpc_loop_gpu.py::test_split_update_two_chains_equal_one), so that one half's rollouts (a sequential
-    // chain of ~1000 RK steps on a quarter of the SIMDs whatever S: 13.5 of 79.5 ms of kernels per two segments at 4096
-    // satellites) run under the other half's solve; =2 also delays the second chain's start until the first has reached its
-    // first solve.  Round-4 verdict item 5; built, measured (profiles/r05/update_split.txt) and NOT the default: the kernels do
-    // overlap, and the closed loop is exactly as fast -- 45.0 against 45.1 ms per segment at 4096 satellites, 80.9 / 79.7 at
-    // 8192, 28.1 / 33.1 at 2048 -- because two launches of 2048 satellites fill the 2048 wave slots in index order, which gives
-    // back what the longest-first order of ONE launch of 4096 had gained (9.5 against 10.3 ms per solve).
-    const char *split_env = getenv("MPCX_UPDATE_SPLIT");            // (read per call: a test switches it inside one process)
-    const int split_mode = split_env ? atoi(split_env) : 0;
+    const int split_mode = update_split_mode();
     const bool split = split_mode > 0 && S >= 2 * kTwoWaveMax && !(opts->flags & MPCX_SOLVE_TIME_PARALLEL);
     const int cnt[2] = {split ? (S + 1) / 2 : S, split ? S / 2 : 0}, fst[2] = {0, cnt[0]};
     size_t ws_bytes[2] = {mpcx_mpc_step_workspace_bytes_ctx(ctx, cnt[0], K), split ? mpcx_mpc_step_workspace_bytes_ctx(ctx, cnt[1], K) : 0};
@@ -435,25 +483,19 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
     double *dys = y_sim ? ar.alloc<double>((size_t)S * 7 * sim_n_eval) : nullptr;
     int32_t *dss = y_sim ? ar.alloc<int32_t>(S) : nullptr;
     if (ar.failed()) return ar.code();
-    if (split) {
-        // (the regularisation record is sized for the whole batch BEFORE anything is enqueued: no allocation under a running half)
-        if (ctx->nreg_cap < S) {
-            if (ctx->nreg) (void)hipFree(ctx->nreg);
-            ctx->nreg = nullptr; ctx->nreg_cap = 0;
-            MPCX_HIP(ctx, hipMalloc((void **)&ctx->nreg, (size_t)S * 2 * sizeof(int32_t)));
-            ctx->nreg_cap = S;
-        }
-        MPCX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));                   // the uploads are behind this point of the first stream
-        MPCX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    }
+    // (a split update's regularisation record is sized for the whole batch BEFORE anything is enqueued: no allocation under a running half)
+    if (split) MPCX_HIP(ctx, ctx->nreg.reserve((size_t)S * 2));
     // the planning rollouts' dynamics: the discretisation's with MPCX_FLAG_PLAN_ROLLOUTS, the reference's drag- and J2-free
     // run_nonlinear (control.py:237-240) without
     const int roll_flags = (disc_flags & MPCX_FLAG_PLAN_ROLLOUTS) ? (disc_flags & (MPCX_FLAG_DRAG | MPCX_FLAG_J2)) : 0;
     const double *tf_fin = dtf0;
     const int32_t *Ks_fin = nullptr;
     const double *Uplan = dU[(n_scp - 1) & 1];
-    // one half's chain: satellites f .. f + n - 1 on stream st, with its own workspace and (second half) launch-order state
-    auto chain = [&](int f, int n, hipStream_t st, void *ws, int lane) -> int {
+    // one half's chain: satellites f .. f + n - 1 on stream st, with its own workspace and launch-order state
+    auto chain = [&](int lane) -> int {
+        const int f = fst[lane], n = cnt[lane];
+        const hipStream_t st = lane ? ctx->stream2 : ctx->stream;
+        void *ws = wsb + (lane ? ws_bytes[0] : 0);
         const size_t o1 = (size_t)f, o7 = (size_t)f * 7 * K, o3 = (size_t)f * 3 * K;
         mpcx_launch::fill_f64(n, ref_thrust, dmag + o1, st);
         mpcx_launch::fill_f64(n, 1.0, done + o1, st);
@@ -461,7 +503,7 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
         const double *tf_cur = dtf0 + o1;
         const int32_t *Ks = nullptr;            // node counts of the current iteration (nullptr: K for everybody)
         int rc = MPCX_OK;
-        ctx->cur_lane = lane; ctx->nreg_first = f; ctx->nreg_total = split ? S : 0;
+        const SolvePlace at = {&ctx->ord[lane], f, split ? S : n};
         for (int it = 0; it < n_scp && rc == MPCX_OK; ++it) {
             double *Uw = dU[it & 1] + o3, *tfw = dtfu[it & 1] + o1;
             if (Ks) {                                                                         // ragged rows: the unused columns
@@ -480,7 +522,7 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
             if (rc) break;
             mpcx_launch::merge_status(n, dps2 + o1, dps + o1, st);                          // (any rollout's failure is the update's)
             if (split && lane == 0 && it == 0 && split_mode == 2) MPCX_HIP(ctx, hipEventRecord(ctx->ev_stagger, st));
-            rc = mpcx_mpc_step_batch_ragged_dev(ctx, n, K, Ks, dx + o7, du + o3, tf_cur, dc + o1 * MPCX_NCONST, drd + o1, disc_flags, disc_max_step,
+            rc = mpc_step_ragged(ctx, at, n, K, Ks, dx + o7, du + o3, tf_cur, dc + o1 * MPCX_NCONST, drd + o1, disc_flags, disc_max_step,
                                                 opts, dX + o7, Uw, dNU + o7, tfw, dst + (size_t)it * S + o1, dit + (size_t)it * S + o1, dk + o1, ws, st);
             if (rc) break;
             tf_cur = tfw;
@@ -490,10 +532,9 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
                 Ks = kn;
             }
         }
-        ctx->cur_lane = 0; ctx->nreg_first = 0; ctx->nreg_total = 0;
         if (rc) return rc;
         MPCX_HIP(ctx, hipGetLastError());
-        if (f == 0) { tf_fin = tf_cur; Ks_fin = Ks; }                                       // (the whole-batch arrays the downloads read)
+        if (lane == 0) { tf_fin = tf_cur; Ks_fin = Ks; }                                      // (the whole-batch arrays the downloads read)
         if (y_sim) {
             // Simulator.run_segment (simulator.py:58-65): fly sim_tf under the truth model with SequenceController(u_opt, tf_u,
             // tf_sim = sim_interval): end_tau = tf_u / sim_interval (control.py:102), the plan's table with its own column count
@@ -507,15 +548,18 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
         }
         return MPCX_OK;
     };
-    int rc = MPCX_OK;
-    rc = chain(fst[0], cnt[0], ctx->stream, wsb, 0);
-    ctx->cur_lane = 0; ctx->nreg_first = 0; ctx->nreg_total = 0;          // (also when the chain left early on an error)
-    if (rc == MPCX_OK && split) {
+    // everything between the fork and the join: whatever fails in here still passes through the join
+    auto chains = [&]() -> int {
+        if (!split) return chain(0);
+        MPCX_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));                   // the uploads are behind this point of the first stream
+        MPCX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+        const int rc = chain(0);
+        if (rc) return rc;
         // (mode 2: the second chain starts when the first has reached its first solve -- its rollout and discretisation then run UNDER it)
         if (split_mode == 2) MPCX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_stagger, 0));
-        rc = chain(fst[1], cnt[1], ctx->stream2, wsb + ws_bytes[0], 1);
-        ctx->cur_lane = 0; ctx->nreg_first = 0; ctx->nreg_total = 0;
-    }
+        return chain(1);
+    };
+    const int rc = chains();
     if (split) {
         // join: the downloads on the first stream follow everything of the second (also on an error path: nothing of this call
         // is left running on the second stream when the arena's buffers are handed to the next call)
@@ -523,11 +567,9 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
         (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
     }
     if (rc) return rc;
-    const double *tf_cur = tf_fin;
-    const int32_t *Ks = Ks_fin;
-    ar.download(X, dX, n7); ar.download(U, (const double *)Uplan, n3); ar.download(NU, dNU, n7);
-    ar.download(tf_out, tf_cur, S);
-    if (Ks) ar.download(Ks_out, Ks, S);
+    ar.download(X, dX, n7); ar.download(U, Uplan, n3); ar.download(NU, dNU, n7);
+    ar.download(tf_out, tf_fin, S);
+    if (Ks_fin) ar.download(Ks_out, Ks_fin, S);
     else for (int i = 0; i < S; ++i) Ks_out[i] = K;                                      // (a single iteration: K nodes for everybody)
     ar.download(status, dst, (size_t)n_scp * S); ar.download(iters, dit, (size_t)n_scp * S); ar.download(kkt, dk, S);
     ar.download(prop_status, dps, S);
@@ -564,16 +606,11 @@ extern "C" int mpcx_solve_batch(mpcx_ctx *ctx, int S, int K, const double *A, co
     double *dst_ = ar.upload(st.data(), st.size());
     double *dx = ar.upload(xbar, (size_t)S * 7 * K), *du = ar.upload(ubar, (size_t)S * 3 * K);
     double *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
-    double *dX = ar.alloc<double>((size_t)S * 7 * K), *dU = ar.alloc<double>((size_t)S * 3 * K);
-    const bool fixed_tf = (opts->flags & MPCX_SOLVE_FIXED_TF) != 0;          // tf_out is an input too (include/mpcx.h)
-    double *dNU = ar.alloc<double>((size_t)S * 7 * K), *dtfo = fixed_tf ? ar.upload(tf_out, S) : ar.alloc<double>(S), *dk = ar.alloc<double>(S);
-    int32_t *dstat = ar.alloc<int32_t>(S), *dit = ar.alloc<int32_t>(S);
+    SolveResults r(ar, S, K, (opts->flags & MPCX_SOLVE_FIXED_TF) ? tf_out : nullptr);
     if (ar.failed()) return ar.code();
-    int rc = mpcx_solve_batch_dev(ctx, S, K, dst_, dx, du, dtf, dc, drd, opts, dX, dU, dNU, dtfo, dstat, dit, dk, ws,
+    int rc = mpcx_solve_batch_dev(ctx, S, K, dst_, dx, du, dtf, dc, drd, opts, r.X, r.U, r.NU, r.tf_out, r.status, r.iters, r.kkt, ws,
                                   ctx->stream);
     if (rc) return rc;
-    ar.download(X, dX, (size_t)S * 7 * K); ar.download(U, dU, (size_t)S * 3 * K); ar.download(NU, dNU, (size_t)S * 7 * K);
-    ar.download(tf_out, dtfo, S); ar.download(status, dstat, S); ar.download(iters, dit, S); ar.download(kkt, dk, S);
+    r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     return ar.finish();
 }
-

@@ -373,3 +373,43 @@ def test_split_update_two_chains_equal_one():
         for f in ("X", "U", "NU", "tf", "status", "iters", "kkt", "Ks", "prop_status", "y_sim", "sim_status"):
             assert np.array_equal(getattr(one, f), getattr(two, f)), (mode, f)
         assert np.array_equal(reg, res["0"][1]), mode
+
+
+def test_split_update_adaptive_launch_order_in_both_chains():
+    """The sibling above has halves of 1025 and 1024 satellites: at or below the device's slot count, so neither chain keeps a
+    launch order.  Here S = 2 n_slots + 2 -- the smallest batch whose two halves EACH exceed the slot count -- and every mode runs
+    the update twice on one context: the second call's solves launch longest first, in the order predicted from the first call's
+    iteration counts, in both chains (each chain with its own launch-order state).  A launch order moves satellites between
+    workgroups, never changes a satellite's bits: both calls of both split modes equal the one-chain call, field by field, and
+    so does the regularisation record of the two halves."""
+    import os
+    import dev_solve as D
+    from mpconstellation_amd import mpc_update_batch, ConstellationMPC, _ffi
+    from mpconstellation_amd.constellation import constellation_states, normalize_batch
+    S = 2 * D.n_slots() + 2
+    y0, consts = normalize_batch(constellation_states(S))
+    kw = dict(n_scp=2, options=ConstellationMPC.OPTIONS(2.0), fly=(1.0, 1.0, 25, True, True))
+    fields = ("X", "U", "NU", "tf", "status", "iters", "kkt", "Ks", "prop_status", "y_sim", "sim_status")
+    lib = _ffi.load()
+    res = {}
+    old = os.environ.get("MPCX_UPDATE_SPLIT")
+    try:
+        for mode in ("0", "1", "2"):
+            os.environ["MPCX_UPDATE_SPLIT"] = mode
+            slot = 20 + int(mode)                                       # a fresh context per mode: no launch-order state inherited
+            ctx = _ffi.context(0, slot)
+            for call in (0, 1):
+                r = mpc_update_batch(y0, 2.0, consts, 1.5, 30, slot=slot, **kw)
+                reg = np.zeros((S, 2), dtype=np.int32)
+                _ffi.check(lib.mpcx_solve_regularised(ctx, S, _ffi.iptr(reg)), ctx, "mpcx_solve_regularised")
+                res[mode, call] = (r, reg)
+    finally:
+        if old is None: os.environ.pop("MPCX_UPDATE_SPLIT", None)
+        else: os.environ["MPCX_UPDATE_SPLIT"] = old
+    one, reg_one = res["0", 0]
+    assert np.isin(one.status, (0, 7)).mean() >= 0.99 and (one.prop_status == 0).all() and (one.sim_status == 0).all()
+    assert len(set(one.Ks.tolist())) > 1
+    for key, (two, reg) in res.items():
+        for f in fields:
+            assert np.array_equal(getattr(one, f), getattr(two, f)), (key, f)
+        assert np.array_equal(reg, reg_one), key

@@ -89,7 +89,7 @@ def other_problem(kernel, S=S_SMALL):
 
 
 def assert_kernel(kernel, S, K, flags):
-    """the call takes the intended kernel: the dispatcher's own conditions (solve_api.hip), by batch size, row length, flags"""
+    """the call takes the intended kernel: the dispatcher's own conditions (solve_api.hip: choose_kernel), by batch size, row length, flags"""
     tp = bool(flags & TIME_PARALLEL) and S <= 128 and K >= 24
     if kernel == "shared":
         assert flags & SHARED_TF
