@@ -15,7 +15,9 @@
  *    pointers, stage through HBM and return when the results are in the caller's buffers;
  *  - the library never keeps a caller pointer after a call returns (host variants) or after
  *    the enqueued work has completed (device variants);
- *  - there is no CPU fallback: without a HIP device mpcx_create fails with MPCX_E_NODEVICE.
+ *  - there is no CPU fallback: without a HIP device mpcx_create fails with MPCX_E_NODEVICE;
+ *  - the solver's problem options are one mpcx_solve_opts per call or, in the *_sat entry points, one row per satellite of a
+ *    table popts [S][MPCX_NPOPT] (MPCX_PO_*): a constellation with different limits per satellite is still one launch.
  */
 #ifndef MPCX_H
 #define MPCX_H
@@ -223,6 +225,21 @@ typedef struct {
 #define MPCX_SOLVE_TP_SELFTEST_DEAD (1 << 30)
 
 void mpcx_default_solve_opts(mpcx_solve_opts *o);
+
+/* Per-satellite problem options.  The eleven PROBLEM options of mpcx_solve_opts -- its first eleven doubles, in this order --
+ * as a table popts [S][MPCX_NPOPT], row s for satellite s (satellite index: whatever order the launch takes the satellites in,
+ * whichever half of a split update holds them).  A constellation whose satellites each live in their own units
+ * (SatelliteScale per satellite) states a physical keep-out radius, maximum thrust or dry mass as a different normalised number
+ * for every satellite; one call with a table replaces one call per distinct option set, and satellite s gets bit for bit what a
+ * call with row s as its scalar options gives it.  The *_sat entry points below take the table directly after `opts`; the
+ * solver controls (tol, acceptable_tol, max_iter, acceptable_iter, n_refine) and the flags stay those of `opts` for the whole
+ * launch, and the table replaces all eleven problem options of `opts`.  A NULL table is the entry point without _sat: every
+ * one of those is its _sat form with NULL.  Host-pointer variants take a host table, _dev variants a device table.
+ * MPCX_SOLVE_SHARED_TF with a table is MPCX_E_BADARG (one tf cannot have per-satellite tf_max); MPCX_SOLVE_FIXED_TF is allowed.
+ * A row whose constraint set is empty (r_min > r_max, tf_max <= 0, a terminal window outside r_max) gives that satellite alone
+ * MPCX_ST_INFEASIBLE. */
+enum { MPCX_PO_MIN_MASS = 0, MPCX_PO_U_MAX, MPCX_PO_R_MIN, MPCX_PO_R_MAX, MPCX_PO_EPS_R, MPCX_PO_EPS_VR, MPCX_PO_EPS_VN,
+       MPCX_PO_EPS_VT, MPCX_PO_TF_MAX, MPCX_PO_W_NU, MPCX_PO_W_TR, MPCX_NPOPT };
 /* Workspace of the _dev solves / fused steps.  It need not be initialised: a call's results do not depend on what the
  * workspace holds on entry -- any bit pattern, another call's leftovers (tests/test_stale_memory_gpu.py) -- and its contents
  * after the call are unspecified.  The plain queries are device-independent upper bounds (one slot per
@@ -254,6 +271,12 @@ int mpcx_solve_batch_dev(mpcx_ctx *ctx, int S, int K, const double *stage, const
                          const double *r_des, const mpcx_solve_opts *opts, double *X, double *U,
                          double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
                          void *workspace, void *stream);
+/* ... with per-satellite problem options popts [S][MPCX_NPOPT] (MPCX_PO_*; NULL: the calls above) */
+int mpcx_solve_batch_sat(mpcx_ctx *ctx, int S, int K, const double *A, const double *Bp, const double *Bn,
+                         const double *Sigma, const double *xi, const double *xbar, const double *ubar,
+                         const double *tf, const double *consts, const double *r_des,
+                         const mpcx_solve_opts *opts, const double *popts, double *X, double *U, double *NU, double *tf_out,
+                         int32_t *status, int32_t *iters, double *kkt);
 
 /* Per-satellite regularisation record of the LAST solve (or fused step) on this context, out [S][2] int32: the number of
  * interior-point iterations whose Newton system needed a Hessian regularisation delta_w > 0 (ipopt's inertia correction:
@@ -283,6 +306,13 @@ int mpcx_constraint_terms(mpcx_ctx *ctx, int S, int K, const double *xbar, const
 int mpcx_constraint_terms_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
                               const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT,
                               double *scalars, void *stream);
+/* ... every satellite's terms under its own row of popts [S][MPCX_NPOPT] (NULL: the calls above) */
+int mpcx_constraint_terms_sat(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                              const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *aT, double *bT,
+                              double *scalars);
+int mpcx_constraint_terms_sat_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                                  const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *aT, double *bT,
+                                  double *scalars, void *stream);
 
 /*
  * One satellite-MPC-step = Optimizer.solve_OPT as the reference runs it (optimizer.py:243-251 calls
@@ -353,6 +383,21 @@ int mpcx_mpc_step_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *K
                                    double max_step, const mpcx_solve_opts *opts, double *X, double *U,
                                    double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
                                    void *workspace, void *stream);
+/* the ragged solve and fused step with per-satellite problem options popts [S][MPCX_NPOPT] (MPCX_PO_*; NULL: the calls above) */
+int mpcx_solve_batch_ragged_sat_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
+                                    const double *ubar, const double *tf, const double *consts,
+                                    const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *X, double *U,
+                                    double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                                    void *workspace, void *stream);
+int mpcx_mpc_step_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                                   const double *tf, const double *consts, const double *r_des, int flags,
+                                   double max_step, const mpcx_solve_opts *opts, const double *popts, double *X, double *U,
+                                   double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt);
+int mpcx_mpc_step_batch_ragged_sat_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                                       const double *tf, const double *consts, const double *r_des, int flags,
+                                       double max_step, const mpcx_solve_opts *opts, const double *popts, double *X, double *U,
+                                       double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                                       void *workspace, void *stream);
 /* Simulator.get_trajectory_ODE with t_eval = linspace(0, 1, n_evals[s]) per satellite (simulator.py:38,185-187) and, for
  * MPCX_CTRL_SEQUENCE, thrust tables of Kus[s] columns */
 int mpcx_propagate_batch_ragged(mpcx_ctx *ctx, int S, int n_eval, const int32_t *n_evals, const double *y0,
@@ -391,6 +436,13 @@ int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *
                                     double prop_max_step, int disc_flags, double disc_max_step, const mpcx_solve_opts *opts,
                                     double *xbar_out, double *ubar_out, double *X, double *U, double *NU, double *tf_out,
                                     int32_t *status, int32_t *iters, double *kkt, int32_t *prop_status);
+/* ... with per-satellite problem options popts [S][MPCX_NPOPT] (MPCX_PO_*; NULL: the call above) */
+int mpcx_scp_iteration_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *y0, const double *tf,
+                                        const double *consts, const double *r_des, int prop_flags, int ctrl_kind,
+                                        const double *ctrl_vec, int Ku, const int32_t *Kus, const double *end_tau,
+                                        double prop_max_step, int disc_flags, double disc_max_step, const mpcx_solve_opts *opts,
+                                        const double *popts, double *xbar_out, double *ubar_out, double *X, double *U, double *NU,
+                                        double *tf_out, int32_t *status, int32_t *iters, double *kkt, int32_t *prop_status);
 /*
  * OptimalController.update (control.py:170-235) for S satellites in ONE call -- and, optionally, the segment flight of
  * Simulator.run_segment (simulator.py:58-65) that follows it -- with everything between the first input and the last result
@@ -418,6 +470,14 @@ int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, double base_re
                           int32_t *Ks_out, int32_t *status, int32_t *iters, double *kkt, int32_t *prop_status, double sim_tf,
                           double sim_interval, int sim_n_eval, int sim_flags, double sim_max_step, double *y_sim,
                           int32_t *sim_status);
+/* ... with per-satellite problem options popts [S][MPCX_NPOPT] (MPCX_PO_*; NULL: the call above): every SCP iteration of the
+ * update solves satellite s under row s, in either chain of a split update */
+int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp, double base_res, const double *y0, const double *tf0,
+                              const double *consts, const double *r_des, double ref_thrust, double prop_max_step, int disc_flags,
+                              double disc_max_step, const mpcx_solve_opts *opts, const double *popts, double *X, double *U,
+                              double *NU, double *tf_out, int32_t *Ks_out, int32_t *status, int32_t *iters, double *kkt,
+                              int32_t *prop_status, double sim_tf, double sim_interval, int sim_n_eval, int sim_flags,
+                              double sim_max_step, double *y_sim, int32_t *sim_status);
 /*
  * Replaces Discretizer.extract_uk (linearize_discretize.py:393-411) for a SequenceController played over its own horizon
  * (control.py:217-221, tf_sim = tf_u: end_tau = 1): the first-order hold (control.py:104-126) of table u [S][3][Ku]

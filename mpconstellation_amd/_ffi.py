@@ -103,6 +103,21 @@ _SIGS = {
                                         C.c_double, _po, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _ip, C.c_double, C.c_double, C.c_int, C.c_int,
                                         C.c_double, _dp, _ip]),
     "mpcx_resample_sequence_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    # per-satellite problem options: the table popts [S][NPOPT] directly after the options
+    "mpcx_constraint_terms_sat": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _po, _dp, _dp, _dp, _dp]),
+    "mpcx_constraint_terms_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _po, _vp, _vp, _vp, _vp, _vp]),
+    "mpcx_solve_batch_sat": (C.c_int, [_vp, C.c_int, C.c_int] + [_dp] * 10 + [_po, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
+    "mpcx_solve_batch_ragged_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 6 + [_po, _vp] + [_vp] * 7 + [_vp, _vp]),
+    "mpcx_mpc_step_batch_ragged_sat": (C.c_int, [_vp, C.c_int, C.c_int, _ip] + [_dp] * 5 + [C.c_int, C.c_double, _po, _dp, _dp, _dp, _dp,
+                                                                                         _dp, _ip, _ip, _dp]),
+    "mpcx_mpc_step_batch_ragged_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 5 + [C.c_int, C.c_double, _po, _vp] + [_vp] * 7
+                                           + [_vp, _vp]),
+    "mpcx_scp_iteration_batch_ragged_sat": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp,
+                                                      C.c_double, C.c_int, C.c_double, _po, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
+                                                      _ip]),
+    "mpcx_mpc_update_batch_sat": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int,
+                                            C.c_double, _po, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _ip, C.c_double, C.c_double, C.c_int,
+                                            C.c_int, C.c_double, _dp, _ip]),
 }
 
 
@@ -274,13 +289,85 @@ def check_solver_keywords(solver):
         raise TypeError(f"unknown solver option(s) {bad}; known: {list(SOLVER_KEYWORDS)}")
 
 
+# per-satellite problem options (include/mpcx.h, MPCX_PO_*): the columns of the table, = mpcx_solve_opts' first eleven doubles
+PO_MIN_MASS, PO_U_MAX, PO_R_MIN, PO_R_MAX, PO_EPS_R, PO_EPS_VR, PO_EPS_VN, PO_EPS_VT, PO_TF_MAX, PO_W_NU, PO_W_TR, NPOPT = range(12)
+PO_FIELDS = ("min_mass", "u_max", "r_min", "r_max", "eps_r", "eps_vr", "eps_vn", "eps_vt", "tf_max", "w_nu", "w_tr")
+_PO_SCALAR_KEYS = ("min_mass", "eps_r", "eps_vr", "eps_vn", "eps_vt", "tf_max", "w_nu", "w_tr")
+_PO_DEFAULTS = (0.1, 5.0, 0.99, 5.0, 0.01, 1e-5, 1e-5, 1e-5, 5.0, 1000.0, 0.002)        # mpcx_default_solve_opts (optimizer.py:178-188)
+
+
+def per_satellite_keys(options):
+    """the problem options of `options` that are given per satellite: (S,) arrays, or (S, 2) for u_lim / r_lim"""
+    out = []
+    for k, v in (options or {}).items():
+        if k in _PO_SCALAR_KEYS and np.ndim(v) >= 1:
+            out.append(k)
+        elif k in ("u_lim", "r_lim") and np.ndim(v) >= 2:
+            out.append(k)
+    return out
+
+
+def make_popts(options, S):
+    """The per-satellite option table of a call for S satellites (include/mpcx.h, popts [S][MPCX_NPOPT]): None when every
+    problem option of `options` is a scalar (the call is then the one without a table, with its bits), otherwise a
+    C-contiguous (S, 11) float64 array, scalars and defaults broadcast.  min_mass, eps_r, eps_vr, eps_vn, eps_vt, tf_max, w_nu,
+    w_tr: a scalar or shape (S,); u_lim, r_lim: (2,) or (S, 2).  Any other shape raises ValueError."""
+    options = options or {}
+    if not per_satellite_keys(options):
+        return None
+    S = int(S)
+    tab = np.empty((S, NPOPT), dtype=np.float64)
+    tab[:] = _PO_DEFAULTS
+
+    def column(key, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim == 0:
+            return v
+        if v.shape != (S,):
+            raise ValueError(f"options[{key!r}]: expected a scalar or shape ({S},), got {v.shape}")
+        return v
+    for key in _PO_SCALAR_KEYS:
+        if key in options:
+            tab[:, PO_FIELDS.index(key)] = column(key, options[key])
+    for key, cols in (("u_lim", (None, PO_U_MAX)), ("r_lim", (PO_R_MIN, PO_R_MAX))):
+        if key in options:
+            v = np.asarray(options[key], dtype=np.float64)
+            if v.shape not in ((2,), (S, 2)):
+                raise ValueError(f"options[{key!r}]: expected shape (2,) or ({S}, 2), got {v.shape}")
+            for j, c in enumerate(cols):
+                if c is not None:
+                    tab[:, c] = v[..., j]
+    return np.ascontiguousarray(tab)
+
+
+def popts_ptr(popts):
+    return None if popts is None else dptr(popts)
+
+
+def scalar_options(options):
+    """`options` with every per-satellite entry replaced by its first satellite's value: the scalar mpcx_solve_opts that goes
+    with a table (which overrides all eleven problem options for every satellite)"""
+    out = dict(options or {})
+    for k in per_satellite_keys(out):
+        out[k] = np.asarray(out[k], dtype=np.float64)[0].tolist()
+    return out
+
+
+def refuse_per_satellite(options, who):
+    keys = per_satellite_keys(options)
+    if keys:
+        raise ValueError(f"{who}: per-satellite options {sorted(keys)} are not possible here (one final time for all satellites "
+                         "cannot have per-satellite limits); pass scalars")
+
+
 # reference option keys (optimizer.py:178-188) -> mpcx_solve_opts
 def make_solve_opts(options=None, **solver):
     """options: dict with the reference's keys (min_mass, u_lim, r_lim, eps_r, eps_vr, eps_vn, tf_max, w_nu, w_tr;
-    r_des is passed per satellite); solver: tol, acceptable_tol, max_iter, acceptable_iter, n_refine."""
+    r_des is passed per satellite); solver: tol, acceptable_tol, max_iter, acceptable_iter, n_refine.  Per-satellite entries
+    (make_popts) go into the table of the call; the struct then carries the first satellite's values."""
     o = SolveOpts()
     load().mpcx_default_solve_opts(C.byref(o))
-    options = options or {}
+    options = scalar_options(options)
     if "min_mass" in options: o.min_mass = options["min_mass"]
     if "u_lim" in options: o.u_max = options["u_lim"][1]
     if "r_lim" in options: o.r_min, o.r_max = options["r_lim"][0], options["r_lim"][1]

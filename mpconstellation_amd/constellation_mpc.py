@@ -22,11 +22,37 @@ from .satellite_scale import SatelliteScale
 from .simulator import propagate_batch
 
 
+def normalised_limits(scales, r_min=None, r_max=None, u_max=None, min_mass=None):
+    """Physical limits -- radii in metres, thrust in newtons, mass in kilograms; scalars or one value per satellite -- as the
+    options dict of a constellation whose satellites each live in their own units (SatelliteScale.units: length = the start radius,
+    mass = the start mass, force derived from those): r_lim (S, 2), u_lim (S, 2) and min_mass (S,) in EACH satellite's units,
+    ready for ConstellationMPC(options=...) and the batched calls of optimizer.py.  A common keep-out radius, engine or dry mass is
+    then a different normalised number for every satellite.  Limits not given keep the defaults (optimizer.DEFAULT_OPTIONS)."""
+    from .optimizer import DEFAULT_OPTIONS
+    S = len(scales)
+    unit = lambda name: np.array([sc.units[name] for sc in scales], dtype=np.float64)
+    per_sat = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float64), (S,))
+    out = {}
+    if r_min is not None or r_max is not None:
+        lo = np.full(S, float(DEFAULT_OPTIONS["r_lim"][0])) if r_min is None else per_sat(r_min) / unit("length")
+        hi = np.full(S, float(DEFAULT_OPTIONS["r_lim"][1])) if r_max is None else per_sat(r_max) / unit("length")
+        out["r_lim"] = np.column_stack([lo, hi])
+    if u_max is not None:
+        out["u_lim"] = np.column_stack([np.full(S, float(DEFAULT_OPTIONS["u_lim"][0])), per_sat(u_max) / unit("force")])
+    if min_mass is not None:
+        out["min_mass"] = per_sat(min_mass) / unit("mass")
+    return out
+
+
 class ConstellationMPC:
     def __init__(self, sats, base_res=100, tf_horizon=1, tf_interval=1, r_des=1.5, scp_iterations=2, sim_base_res=100,
                  include_drag=True, include_J2=True, device=0, strict=False, scales=None, verbose=False, devices=None,
-                 time_parallel=False, plan_drag=False, plan_J2=False):
+                 time_parallel=False, plan_drag=False, plan_J2=False, options=None):
         self.sats = list(sats)
+        # problem options on top of OPTIONS(horizon): the reference's keys, scalars or one value per satellite ((S,), (S, 2) for
+        # u_lim / r_lim: _ffi.make_popts; normalised_limits above turns physical limits into them).  The user's values win.
+        self.options = dict(options) if options else {}
+        _ffi.make_popts(self.options, len(self.sats))      # (a wrong length is reported here, not at the first update)
         # every satellite in its own "designer units" (so that each sees MU = 4 pi^2) unless the caller brings the scales
         self.scales = list(scales) if scales is not None else [SatelliteScale(sat=s) for s in self.sats]
         self.verbose = verbose                # control.py:208-209's prints, per satellite
@@ -132,7 +158,7 @@ class ConstellationMPC:
         S = len(self.sats)
         y0 = self._y0() if y0 is None else y0
         K = int(self.base_res * self.horizon)
-        opts = self.OPTIONS(self.horizon)
+        opts = {**self.OPTIONS(self.horizon), **self.options}
         for flags in ((self.solver_flags, 0) if self.solver_flags & _ffi.SOLVE_TIME_PARALLEL else (self.solver_flags,)):
             if self.verbose:
                 res = self._update_by_iterations(y0, K, opts, flags)

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64, MPCX_SOLVE_WAVES) MPCX_NO_TAIL void solve_share
 // (build_terminal: Optimizer.get_constraint_terms, optimizer.py:80-170, as consumed by the rules :398-403, 406-446,
 // 471-489, 351-352) and the relaxed scalar bounds.  Same device function, same lane, same LDS struct as in the solve.
 __global__ __launch_bounds__(64) void constraint_terms_kernel(int S, int K, const double *xbar, const double *consts, const double *r_des,
-                                                              SolveOpts o, double *aT, double *bT, double *scal)
+                                                              SolveOpts o, const double *popts, double *aT, double *bT, double *scal)
 {
     __shared__ SatData sd;
     const int sat = blockIdx.x, lane = threadIdx.x;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(64) void constraint_terms_kernel(int S, int K, cons
         double xK[7], x0[3];
         for (int i = 0; i < 7; ++i) xK[i] = xbar[(size_t)sat * 7 * K + (size_t)i * K + K - 1];
         for (int i = 0; i < 3; ++i) x0[i] = xbar[(size_t)sat * 7 * K + (size_t)i * K];
-        build_terminal(xK, consts[(size_t)sat * MPCX_NCONST + MPCX_C_MU], r_des[sat], o, sd);
+        build_terminal_sat(xK, consts[(size_t)sat * MPCX_NCONST + MPCX_C_MU], r_des[sat], o, popts, sat, sd);
         sd.infeas = structural_violation(x0, K, sd);
     }
     __syncthreads();
@@ -186,10 +186,10 @@ void update_prediction(int S, const int32_t *iters, int32_t *hist, int32_t *pred
 
 void merge_status(int S, const int32_t *dstat, int32_t *status, hipStream_t st) { merge_status_kernel_launch(S, dstat, status, st); }
 
-void constraint_terms(int S, int K, const double *xbar, const double *consts, const double *r_des, const SolveOpts &o, double *aT,
-                      double *bT, double *scal, hipStream_t st)
+void constraint_terms(int S, int K, const double *xbar, const double *consts, const double *r_des, const SolveOpts &o, const double *popts,
+                      double *aT, double *bT, double *scal, hipStream_t st)
 {
-    hipLaunchKernelGGL(constraint_terms_kernel, dim3(S), dim3(64), 0, st, S, K, xbar, consts, r_des, o, aT, bT, scal);
+    hipLaunchKernelGGL(constraint_terms_kernel, dim3(S), dim3(64), 0, st, S, K, xbar, consts, r_des, o, popts, aT, bT, scal);
 }
 
 void node_count(int S, double base_res, const double *tf, int32_t *Kn, hipStream_t st)

@@ -90,33 +90,48 @@ static SolveOpts to_dev_opts(const mpcx_solve_opts *o)
     return d;
 }
 
-extern "C" int mpcx_constraint_terms_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
-                                         const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT,
-                                         double *scalars, void *stream)
+extern "C" int mpcx_constraint_terms_sat_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                                             const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *aT,
+                                             double *bT, double *scalars, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 2 || !opts || !xbar || !consts || !r_des || !aT || !bT || !scalars)
         return ctx_fail(ctx, MPCX_E_BADARG, "constraint_terms: need S>=1, K>=2, options and all arrays");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    mpcx_launch::constraint_terms(S, K, xbar, consts, r_des, to_dev_opts(opts), aT, bT, scalars, (hipStream_t)stream);
+    mpcx_launch::constraint_terms(S, K, xbar, consts, r_des, to_dev_opts(opts), popts, aT, bT, scalars, (hipStream_t)stream);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
 }
 
-extern "C" int mpcx_constraint_terms(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
-                                     const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT, double *scalars)
+extern "C" int mpcx_constraint_terms_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                                         const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT,
+                                         double *scalars, void *stream)
+{
+    return mpcx_constraint_terms_sat_dev(ctx, S, K, xbar, consts, r_des, opts, nullptr, aT, bT, scalars, stream);
+}
+
+extern "C" int mpcx_constraint_terms_sat(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                                         const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *aT,
+                                         double *bT, double *scalars)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 2 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "constraint_terms: need S>=1, K>=2 and options");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     double *dx = ar.upload(xbar, (size_t)S * 7 * K), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
+    double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;
     double *da = ar.alloc<double>((size_t)S * 56), *db = ar.alloc<double>((size_t)S * 8), *ds = ar.alloc<double>((size_t)S * MPCX_NTERM_SCALARS);
     if (ar.failed()) return ar.code();
-    int rc = mpcx_constraint_terms_dev(ctx, S, K, dx, dc, drd, opts, da, db, ds, ctx->stream);
+    int rc = mpcx_constraint_terms_sat_dev(ctx, S, K, dx, dc, drd, opts, dpo, da, db, ds, ctx->stream);
     if (rc) return rc;
     ar.download(aT, da, (size_t)S * 56); ar.download(bT, db, (size_t)S * 8); ar.download(scalars, ds, (size_t)S * MPCX_NTERM_SCALARS);
     return ar.finish();
+}
+
+extern "C" int mpcx_constraint_terms(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *consts,
+                                     const double *r_des, const mpcx_solve_opts *opts, double *aT, double *bT, double *scalars)
+{
+    return mpcx_constraint_terms_sat(ctx, S, K, xbar, consts, r_des, opts, nullptr, aT, bT, scalars);
 }
 
 extern "C" int mpcx_solve_regularised_dev(mpcx_ctx *ctx, int S, int32_t *out, void *stream)
@@ -164,8 +179,8 @@ extern "C" size_t mpcx_solve_workspace_bytes_ctx(const mpcx_ctx *ctx, int S, int
 
 static int solve_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
                         const double *ubar, const double *tf, const double *consts, const double *r_des, const mpcx_solve_opts *opts,
-                        double *X, double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
-                        void *workspace, hipStream_t st)
+                        const double *popts, double *X, double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters,
+                        double *kkt, void *workspace, hipStream_t st)
 {
     if (S < 1 || K < 3 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "solve: need S>=1, K>=3 and options");
     if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "solve: workspace of mpcx_solve_workspace_bytes(S,K) required");
@@ -174,6 +189,7 @@ static int solve_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const
     Kernel kern = choose_kernel(ctx, S, K, opts->flags);
     if (kern == Kernel::Shared) {
         // one final time for the whole batch: a cooperative launch, one workgroup per satellite, all of them resident
+        if (popts) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF takes no per-satellite options (one tf cannot have per-satellite tf_max)");
         if (Ks) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF needs the same node count for every satellite (no ragged batch)");
         if (opts->flags & MPCX_SOLVE_FIXED_TF) return ctx_fail(ctx, MPCX_E_BADARG, "solve: MPCX_SOLVE_SHARED_TF and MPCX_SOLVE_FIXED_TF exclude each other");
         if (ctx->coop_max == 0) {
@@ -188,7 +204,7 @@ static int solve_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const
     if (kern == Kernel::TimeParallel && ctx->tp_max < 0) return ctx_fail(ctx, MPCX_E_HIP, "solve: occupancy query of the time-parallel kernel failed");
     SolveArgs a;
     a.S = S; a.K = K; a.Ks = Ks; a.stage = stage; a.xbar = xbar; a.ubar = ubar; a.tfbar = tf; a.consts = consts; a.r_des = r_des;
-    a.o = to_dev_opts(opts);
+    a.o = to_dev_opts(opts); a.popts = popts;
     a.X = X; a.U = U; a.NU = NU; a.tf_out = tf_out; a.kkt = kkt; a.status = status; a.iters = iters;
     a.ws = (double *)workspace; a.ws_stride = ws_doubles(K);         // (the workspace is the caller's: slot b of THIS call's buffer)
     // per-satellite regularisation counts of this solve (library-owned; read back by mpcx_solve_regularised)
@@ -247,15 +263,25 @@ static int solve_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const
     return MPCX_OK;
 }
 
+extern "C" int mpcx_solve_batch_ragged_sat_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
+                                               const double *ubar, const double *tf, const double *consts,
+                                               const double *r_des, const mpcx_solve_opts *opts, const double *popts, double *X,
+                                               double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                                               void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return solve_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, popts, X, U, NU, tf_out, status,
+                        iters, kkt, workspace, (hipStream_t)stream);
+}
+
 extern "C" int mpcx_solve_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const double *xbar,
                                            const double *ubar, const double *tf, const double *consts,
                                            const double *r_des, const mpcx_solve_opts *opts, double *X, double *U,
                                            double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
                                            void *workspace, void *stream)
 {
-    if (!ctx) return MPCX_E_BADARG;
-    return solve_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, X, U, NU, tf_out, status, iters,
-                        kkt, workspace, (hipStream_t)stream);
+    return mpcx_solve_batch_ragged_sat_dev(ctx, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, nullptr, X, U, NU, tf_out, status,
+                                           iters, kkt, workspace, stream);
 }
 
 extern "C" int mpcx_solve_batch_dev(mpcx_ctx *ctx, int S, int K, const double *stage, const double *xbar,
@@ -277,8 +303,8 @@ struct StepLayout {
 
 static int mpc_step_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
                            const double *tf, const double *consts, const double *r_des, int flags, double max_step,
-                           const mpcx_solve_opts *opts, double *X, double *U, double *NU, double *tf_out, int32_t *status,
-                           int32_t *iters, double *kkt, void *workspace, hipStream_t st)
+                           const mpcx_solve_opts *opts, const double *popts, double *X, double *U, double *NU, double *tf_out,
+                           int32_t *status, int32_t *iters, double *kkt, void *workspace, hipStream_t st)
 {
     if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_step: workspace of mpcx_mpc_step_workspace_bytes(S,K) required");
     const StepLayout lay(S, K);
@@ -287,11 +313,22 @@ static int mpc_step_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, co
     // (a ragged batch's thrust tables have as many columns as the satellite has nodes)
     int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, xbar, ubar, tf, consts, flags, max_step, stage, dstat, st);
     if (rc) return rc;
-    rc = solve_ragged(ctx, at, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, X, U, NU, tf_out, status, iters, kkt, sws, st);
+    rc = solve_ragged(ctx, at, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, popts, X, U, NU, tf_out, status, iters, kkt, sws, st);
     if (rc) return rc;
     mpcx_launch::merge_status(S, dstat, status, st);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
+}
+
+extern "C" int mpcx_mpc_step_batch_ragged_sat_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                                                  const double *tf, const double *consts, const double *r_des, int flags,
+                                                  double max_step, const mpcx_solve_opts *opts, const double *popts, double *X,
+                                                  double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters,
+                                                  double *kkt, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return mpc_step_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, xbar, ubar, tf, consts, r_des, flags, max_step, opts, popts, X, U, NU,
+                           tf_out, status, iters, kkt, workspace, (hipStream_t)stream);
 }
 
 extern "C" int mpcx_mpc_step_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
@@ -300,9 +337,8 @@ extern "C" int mpcx_mpc_step_batch_ragged_dev(mpcx_ctx *ctx, int S, int K, const
                                               double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
                                               void *workspace, void *stream)
 {
-    if (!ctx) return MPCX_E_BADARG;
-    return mpc_step_ragged(ctx, {&ctx->ord[0], 0, S}, S, K, Ks, xbar, ubar, tf, consts, r_des, flags, max_step, opts, X, U, NU, tf_out,
-                           status, iters, kkt, workspace, (hipStream_t)stream);
+    return mpcx_mpc_step_batch_ragged_sat_dev(ctx, S, K, Ks, xbar, ubar, tf, consts, r_des, flags, max_step, opts, nullptr, X, U, NU,
+                                              tf_out, status, iters, kkt, workspace, stream);
 }
 
 extern "C" int mpcx_mpc_step_batch_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *ubar,
@@ -344,10 +380,10 @@ struct SolveResults {
     }
 };
 
-extern "C" int mpcx_mpc_step_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
-                                          const double *tf, const double *consts, const double *r_des, int flags,
-                                          double max_step, const mpcx_solve_opts *opts, double *X, double *U, double *NU,
-                                          double *tf_out, int32_t *status, int32_t *iters, double *kkt)
+extern "C" int mpcx_mpc_step_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                                              const double *tf, const double *consts, const double *r_des, int flags,
+                                              double max_step, const mpcx_solve_opts *opts, const double *popts, double *X,
+                                              double *U, double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_step: need S>=1, K>=3 and options");
@@ -358,13 +394,23 @@ extern "C" int mpcx_mpc_step_batch_ragged(mpcx_ctx *ctx, int S, int K, const int
     double *dx = ar.upload(xbar, (size_t)S * 7 * K), *du = ar.upload(ubar, (size_t)S * 3 * K);
     double *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr;
+    double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;
     SolveResults r(ar, S, K, (opts->flags & MPCX_SOLVE_FIXED_TF) ? tf_out : nullptr);
     if (ar.failed()) return ar.code();
-    int rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, flags, max_step, opts, r.X, r.U, r.NU, r.tf_out, r.status,
-                                            r.iters, r.kkt, ws, ctx->stream);
+    int rc = mpcx_mpc_step_batch_ragged_sat_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, flags, max_step, opts, dpo, r.X, r.U, r.NU, r.tf_out,
+                                                r.status, r.iters, r.kkt, ws, ctx->stream);
     if (rc) return rc;
     r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     return ar.finish();
+}
+
+extern "C" int mpcx_mpc_step_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *xbar, const double *ubar,
+                                          const double *tf, const double *consts, const double *r_des, int flags,
+                                          double max_step, const mpcx_solve_opts *opts, double *X, double *U, double *NU,
+                                          double *tf_out, int32_t *status, int32_t *iters, double *kkt)
+{
+    return mpcx_mpc_step_batch_ragged_sat(ctx, S, K, Ks, xbar, ubar, tf, consts, r_des, flags, max_step, opts, nullptr, X, U, NU, tf_out,
+                                          status, iters, kkt);
 }
 
 extern "C" int mpcx_mpc_step_batch(mpcx_ctx *ctx, int S, int K, const double *xbar, const double *ubar,
@@ -379,13 +425,13 @@ extern "C" int mpcx_mpc_step_batch(mpcx_ctx *ctx, int S, int K, const double *xb
 // One SCP iteration of OptimalController.update (control.py:183-227) for S satellites, host buffers in and out: the nonlinear
 // rollout under the given thrust law sampled at the satellite's nodes (its thrust at those nodes = extract_uk), the
 // linearisation / discretisation about it and the solve -- x_bar and u_bar never leave the device.
-extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *y0, const double *tf,
-                                               const double *consts, const double *r_des, int prop_flags, int ctrl_kind,
-                                               const double *ctrl_vec, int Ku, const int32_t *Kus, const double *end_tau,
-                                               double prop_max_step, int disc_flags, double disc_max_step,
-                                               const mpcx_solve_opts *opts, double *xbar_out, double *ubar_out, double *X, double *U,
-                                               double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
-                                               int32_t *prop_status)
+extern "C" int mpcx_scp_iteration_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *y0, const double *tf,
+                                                   const double *consts, const double *r_des, int prop_flags, int ctrl_kind,
+                                                   const double *ctrl_vec, int Ku, const int32_t *Kus, const double *end_tau,
+                                                   double prop_max_step, int disc_flags, double disc_max_step,
+                                                   const mpcx_solve_opts *opts, const double *popts, double *xbar_out,
+                                                   double *ubar_out, double *X, double *U, double *NU, double *tf_out,
+                                                   int32_t *status, int32_t *iters, double *kkt, int32_t *prop_status)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts || !prop_status) return ctx_fail(ctx, MPCX_E_BADARG, "scp_iteration: need S>=1, K>=3, options and prop_status");
@@ -402,6 +448,7 @@ extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, cons
     double *dv = (nv && ctrl_vec) ? ar.upload(ctrl_vec, nv) : nullptr;
     double *de = (ctrl_kind == MPCX_CTRL_SEQUENCE && end_tau) ? ar.upload(end_tau, S) : nullptr;
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr, *dKus = Kus ? ar.upload(Kus, S) : nullptr;
+    double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;
     double *dx = ar.alloc<double>((size_t)S * 7 * K), *du = ar.alloc<double>((size_t)S * 3 * K);
     SolveResults r(ar, S, K, nullptr);
     int32_t *dps = ar.alloc<int32_t>(S), *dpn = ar.alloc<int32_t>(S);
@@ -413,14 +460,27 @@ extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, cons
     int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, K, dKs, dy0, dtf, dc, prop_flags, ctrl_kind, dv, Ku, dKus, de, prop_max_step,
                                                     dx, du, dps, dpn, ctx->stream);
     if (rc) return rc;
-    rc = mpcx_mpc_step_batch_ragged_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, disc_flags, disc_max_step, opts, r.X, r.U, r.NU, r.tf_out,
-                                        r.status, r.iters, r.kkt, ws, ctx->stream);
+    rc = mpcx_mpc_step_batch_ragged_sat_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, disc_flags, disc_max_step, opts, dpo, r.X, r.U, r.NU,
+                                            r.tf_out, r.status, r.iters, r.kkt, ws, ctx->stream);
     if (rc) return rc;
     if (xbar_out) ar.download(xbar_out, dx, (size_t)S * 7 * K);
     if (ubar_out) ar.download(ubar_out, du, (size_t)S * 3 * K);
     r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     ar.download(prop_status, dps, S);
     return ar.finish();
+}
+
+extern "C" int mpcx_scp_iteration_batch_ragged(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *y0, const double *tf,
+                                               const double *consts, const double *r_des, int prop_flags, int ctrl_kind,
+                                               const double *ctrl_vec, int Ku, const int32_t *Kus, const double *end_tau,
+                                               double prop_max_step, int disc_flags, double disc_max_step,
+                                               const mpcx_solve_opts *opts, double *xbar_out, double *ubar_out, double *X, double *U,
+                                               double *NU, double *tf_out, int32_t *status, int32_t *iters, double *kkt,
+                                               int32_t *prop_status)
+{
+    return mpcx_scp_iteration_batch_ragged_sat(ctx, S, K, Ks, y0, tf, consts, r_des, prop_flags, ctrl_kind, ctrl_vec, Ku, Kus, end_tau,
+                                               prop_max_step, disc_flags, disc_max_step, opts, nullptr, xbar_out, ubar_out, X, U, NU, tf_out,
+                                               status, iters, kkt, prop_status);
 }
 
 // MPCX_UPDATE_SPLIT=1 / 2 (default 0): the batch as TWO chains -- the two halves of the satellites, each rollout -> discretise ->
@@ -440,12 +500,12 @@ static int update_split_mode()
 
 // OptimalController.update (control.py:170-235) for S satellites as ONE call, everything between the first input and the
 // last result resident in HBM (include/mpcx.h).
-extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, double base_res, const double *y0, const double *tf0,
-                                     const double *consts, const double *r_des, double ref_thrust, double prop_max_step,
-                                     int disc_flags, double disc_max_step, const mpcx_solve_opts *opts, double *X, double *U,
-                                     double *NU, double *tf_out, int32_t *Ks_out, int32_t *status, int32_t *iters, double *kkt,
-                                     int32_t *prop_status, double sim_tf, double sim_interval, int sim_n_eval, int sim_flags,
-                                     double sim_max_step, double *y_sim, int32_t *sim_status)
+extern "C" int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp, double base_res, const double *y0, const double *tf0,
+                                         const double *consts, const double *r_des, double ref_thrust, double prop_max_step,
+                                         int disc_flags, double disc_max_step, const mpcx_solve_opts *opts, const double *popts,
+                                         double *X, double *U, double *NU, double *tf_out, int32_t *Ks_out, int32_t *status,
+                                         int32_t *iters, double *kkt, int32_t *prop_status, double sim_tf, double sim_interval,
+                                         int sim_n_eval, int sim_flags, double sim_max_step, double *y_sim, int32_t *sim_status)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || n_scp < 1 || !opts || !y0 || !tf0 || !consts || !r_des || !X || !U || !NU || !tf_out || !Ks_out || !status ||
@@ -471,6 +531,7 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
     }
     DeviceArena ar(ctx);
     double *dy0 = ar.upload(y0, (size_t)S * 7), *dtf0 = ar.upload(tf0, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
+    double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;             // (row s: satellite s of the WHOLE batch)
     const size_t n7 = (size_t)S * 7 * K, n3 = (size_t)S * 3 * K;
     double *dx = ar.alloc<double>(n7), *du = ar.alloc<double>(n3);                      // reference trajectory / thrust of the iteration
     double *dX = ar.alloc<double>(n7), *dNU = ar.alloc<double>(n7);
@@ -523,7 +584,7 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
             mpcx_launch::merge_status(n, dps2 + o1, dps + o1, st);                          // (any rollout's failure is the update's)
             if (split && lane == 0 && it == 0 && split_mode == 2) MPCX_HIP(ctx, hipEventRecord(ctx->ev_stagger, st));
             rc = mpc_step_ragged(ctx, at, n, K, Ks, dx + o7, du + o3, tf_cur, dc + o1 * MPCX_NCONST, drd + o1, disc_flags, disc_max_step,
-                                                opts, dX + o7, Uw, dNU + o7, tfw, dst + (size_t)it * S + o1, dit + (size_t)it * S + o1, dk + o1, ws, st);
+                                                opts, dpo ? dpo + o1 * MPCX_NPOPT : nullptr, dX + o7, Uw, dNU + o7, tfw, dst + (size_t)it * S + o1, dit + (size_t)it * S + o1, dk + o1, ws, st);
             if (rc) break;
             tf_cur = tfw;
             if (it + 1 < n_scp) {
@@ -577,11 +638,23 @@ extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, dou
     return ar.finish();
 }
 
-extern "C" int mpcx_solve_batch(mpcx_ctx *ctx, int S, int K, const double *A, const double *Bp, const double *Bn,
-                                const double *Sigma, const double *xi, const double *xbar, const double *ubar,
-                                const double *tf, const double *consts, const double *r_des,
-                                const mpcx_solve_opts *opts, double *X, double *U, double *NU, double *tf_out,
-                                int32_t *status, int32_t *iters, double *kkt)
+extern "C" int mpcx_mpc_update_batch(mpcx_ctx *ctx, int S, int K, int n_scp, double base_res, const double *y0, const double *tf0,
+                                     const double *consts, const double *r_des, double ref_thrust, double prop_max_step,
+                                     int disc_flags, double disc_max_step, const mpcx_solve_opts *opts, double *X, double *U,
+                                     double *NU, double *tf_out, int32_t *Ks_out, int32_t *status, int32_t *iters, double *kkt,
+                                     int32_t *prop_status, double sim_tf, double sim_interval, int sim_n_eval, int sim_flags,
+                                     double sim_max_step, double *y_sim, int32_t *sim_status)
+{
+    return mpcx_mpc_update_batch_sat(ctx, S, K, n_scp, base_res, y0, tf0, consts, r_des, ref_thrust, prop_max_step, disc_flags,
+                                     disc_max_step, opts, nullptr, X, U, NU, tf_out, Ks_out, status, iters, kkt, prop_status, sim_tf,
+                                     sim_interval, sim_n_eval, sim_flags, sim_max_step, y_sim, sim_status);
+}
+
+extern "C" int mpcx_solve_batch_sat(mpcx_ctx *ctx, int S, int K, const double *A, const double *Bp, const double *Bn,
+                                    const double *Sigma, const double *xi, const double *xbar, const double *ubar,
+                                    const double *tf, const double *consts, const double *r_des,
+                                    const mpcx_solve_opts *opts, const double *popts, double *X, double *U, double *NU,
+                                    double *tf_out, int32_t *status, int32_t *iters, double *kkt)
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "solve: need S>=1, K>=3 and options");
@@ -606,11 +679,22 @@ extern "C" int mpcx_solve_batch(mpcx_ctx *ctx, int S, int K, const double *A, co
     double *dst_ = ar.upload(st.data(), st.size());
     double *dx = ar.upload(xbar, (size_t)S * 7 * K), *du = ar.upload(ubar, (size_t)S * 3 * K);
     double *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
+    double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;
     SolveResults r(ar, S, K, (opts->flags & MPCX_SOLVE_FIXED_TF) ? tf_out : nullptr);
     if (ar.failed()) return ar.code();
-    int rc = mpcx_solve_batch_dev(ctx, S, K, dst_, dx, du, dtf, dc, drd, opts, r.X, r.U, r.NU, r.tf_out, r.status, r.iters, r.kkt, ws,
-                                  ctx->stream);
+    int rc = mpcx_solve_batch_ragged_sat_dev(ctx, S, K, nullptr, dst_, dx, du, dtf, dc, drd, opts, dpo, r.X, r.U, r.NU, r.tf_out, r.status,
+                                             r.iters, r.kkt, ws, ctx->stream);
     if (rc) return rc;
     r.download(ar, X, U, NU, tf_out, status, iters, kkt);
     return ar.finish();
+}
+
+extern "C" int mpcx_solve_batch(mpcx_ctx *ctx, int S, int K, const double *A, const double *Bp, const double *Bn,
+                                const double *Sigma, const double *xi, const double *xbar, const double *ubar,
+                                const double *tf, const double *consts, const double *r_des,
+                                const mpcx_solve_opts *opts, double *X, double *U, double *NU, double *tf_out,
+                                int32_t *status, int32_t *iters, double *kkt)
+{
+    return mpcx_solve_batch_sat(ctx, S, K, A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, opts, nullptr, X, U, NU, tf_out, status,
+                                iters, kkt);
 }

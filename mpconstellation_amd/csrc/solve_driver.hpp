@@ -164,7 +164,8 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
     if (lane == 0) {
         double xK[7];
         for (int i = 0; i < 7; ++i) xK[i] = s.xbar[(size_t)i * Kmax + K - 1];
-        build_terminal(xK, a.consts[(size_t)sat * MPCX_NCONST + MPCX_C_MU], a.r_des[sat], o, sd);
+        // (the satellite's own problem options: its row of a.popts, which a shared-tf launch does not have -- SolveArgs)
+        build_terminal_sat(xK, a.consts[(size_t)sat * MPCX_NCONST + MPCX_C_MU], a.r_des[sat], o, SHARED ? nullptr : a.popts, sat, sd);
         sd.tfbar = a.tfbar[sat];
         double x0[3];
         for (int i = 0; i < 3; ++i) x0[i] = s.xbar[(size_t)i * Kmax];
@@ -253,7 +254,7 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
             clean = false;
         // ... and the reference ends within kCleanRadius half-widths of the terminal radius window
         const double xr[3] = {s.xbar[K - 1], s.xbar[(size_t)Kmax + K - 1], s.xbar[(size_t)2 * Kmax + K - 1]};
-        if (!(fabs(sqrt(xr[0] * xr[0] + xr[1] * xr[1] + xr[2] * xr[2]) - a.r_des[sat]) <= kCleanRadius * o.eps_r)) clean = false;
+        if (!(fabs(sqrt(xr[0] * xr[0] + xr[1] * xr[1] + xr[2] * xr[2]) - a.r_des[sat]) <= kCleanRadius * sd.eps_r)) clean = false;
     }
 #ifdef MPCX_NO_CLEAN_START      // measurement builds only (profiles/tools): every start treated as it was before round 3
     clean = false;

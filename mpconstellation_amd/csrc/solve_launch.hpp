@@ -12,8 +12,8 @@ hipError_t solve_shared_blocks_per_cu(int *per_cu);
 void launch_order(int S, const int32_t *prev_iters, int32_t *order, hipStream_t st);
 void update_prediction(int S, const int32_t *iters, int32_t *hist, int32_t *pred, int slot, int n_valid, hipStream_t st);
 void merge_status(int S, const int32_t *dstat, int32_t *status, hipStream_t st);
-void constraint_terms(int S, int K, const double *xbar, const double *consts, const double *r_des, const mpcx::SolveOpts &o, double *aT,
-                      double *bT, double *scal, hipStream_t st);
+void constraint_terms(int S, int K, const double *xbar, const double *consts, const double *r_des, const mpcx::SolveOpts &o,
+                      const double *popts, double *aT, double *bT, double *scal, hipStream_t st);
 void node_count(int S, double base_res, const double *tf, int32_t *Kn, hipStream_t st);
 void fill_f64(int n, double v, double *out, hipStream_t st);
 void divide_f64(int n, const double *a, double d, double *out, hipStream_t st);

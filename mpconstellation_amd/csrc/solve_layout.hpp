@@ -66,8 +66,13 @@ struct SolveArgs {
     double *X, *U, *NU, *tf_out, *kkt;
     int32_t *status, *iters;
     const int32_t *order;     // workgroup b solves satellite order[b]; nullptr = index order
-    // shared-tf launches (solve_shared_kernel): per-block reduction slots [2][S][GR_N], arrival counter, abort flag
-    double *red;
+    // shared-tf launches (solve_shared_kernel): per-block reduction slots [2][S][GR_N], arrival counter, abort flag.
+    // Every other launch: per-satellite problem options popts [S][MPCX_NPOPT] (include/mpcx.h, MPCX_PO_*), indexed by SATELLITE --
+    // not by workgroup, slot or position in the launch order; nullptr: the eleven problem options of `o` for everybody.
+    // (One slot for both: a shared-tf launch takes no table -- solve_api.hip rejects it -- and no other kernel reduces across
+    //  workgroups; a ninth pointer grew the kernels' private copy of this struct, 16 bytes of scratch per lane in three of them:
+    //  profiles/per_satellite_options.txt.)
+    union { double *red; const double *popts; };
     int32_t *arrive, *abort_flag;
     int32_t *counter;         // work queue of the persistent workgroups: next position of the launch order (zeroed per launch)
     int32_t *nreg;            // [S][2]: iterations whose direction needed delta_w > 0, and the first of them (-1: none)

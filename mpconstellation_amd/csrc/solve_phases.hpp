@@ -55,6 +55,7 @@ struct SatData {
         int n_acc, status, it_count, n_reg, first_reg, mono, refined_prev, n_small, iter, have_dir, have_trial, clean, ls;
     } dv;
     double infeas;           // > 0: the constraint set is empty whatever the dynamics (structural_violation)
+    double eps_r;            // the satellite's own eps_r (build_terminal_sat): the clean-start test reads it
     int flag;
 #ifdef MPCX_PHASE_TIMING
     unsigned long long fpt[16];   // diagnostic build only: cycle sums of the recursion's inner phases
@@ -243,6 +244,24 @@ __device__ __noinline__ void build_terminal(const double *xK, double mu_grav, do
     sd.b_tf[0] = relax(0.0); sd.b_tf[1] = relax(o.tf_max);
     sd.vt_des = sqrt(mu_grav / r_des);
     sd.w_tr = o.w_tr; sd.w_nu = o.w_nu;
+}
+
+// build_terminal for satellite `sat` of a launch with per-satellite problem options: a local copy of the launch's options --
+// solver controls and flags as they are -- takes the eleven problem options from the satellite's row of the table (SolveArgs::popts,
+// [S][MPCX_NPOPT] in the order of mpcx_solve_opts' first eleven doubles, indexed by SATELLITE), and build_terminal gets the copy.
+// popts == nullptr: the launch's options for everybody.  Out of line, like build_terminal: the copy lives in this function's frame,
+// not in the driver's.
+__device__ __noinline__ void build_terminal_sat(const double *xK, double mu_grav, double r_des, const SolveOpts &o, const double *popts, int sat, SatData &sd)
+{
+    SolveOpts os = o;
+    if (popts) {
+        const double *row = popts + (size_t)sat * MPCX_NPOPT;
+        os.min_mass = row[MPCX_PO_MIN_MASS]; os.u_max = row[MPCX_PO_U_MAX]; os.r_min = row[MPCX_PO_R_MIN]; os.r_max = row[MPCX_PO_R_MAX];
+        os.eps_r = row[MPCX_PO_EPS_R]; os.eps_vr = row[MPCX_PO_EPS_VR]; os.eps_vn = row[MPCX_PO_EPS_VN]; os.eps_vt = row[MPCX_PO_EPS_VT];
+        os.tf_max = row[MPCX_PO_TF_MAX]; os.w_nu = row[MPCX_PO_W_NU]; os.w_tr = row[MPCX_PO_W_TR];
+    }
+    build_terminal(xK, mu_grav, r_des, os, sd);
+    sd.eps_r = os.eps_r;
 }
 
 // > 0 when the constraint set is empty whatever the dynamics.  The virtual control makes every x_1..x_K reachable, so

@@ -29,17 +29,23 @@ def _regularised(lib, ctx, S, out=None):
 
 def constraint_terms_batch(xbar, consts, r_des, options=None, device=0, linear_vt=False):
     """What the device builds from Optimizer.get_constraint_terms (optimizer.py:80-170) before its first iteration
-    (include/mpcx.h, mpcx_constraint_terms): aT (S,8,7), bT (S,8), scalars (S,8)."""
+    (include/mpcx.h, mpcx_constraint_terms): aT (S,8,7), bT (S,8), scalars (S,8).
+    options may hold per-satellite values (_ffi.make_popts): every satellite's terms are then built under its own row."""
     xbar = _ffi.as_f64(xbar)
     S, _, K = xbar.shape
     consts = _ffi.as_f64(consts)
     r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
     opts = _ffi.make_solve_opts(options, **_solver_flags({}, linear_vt))
+    popts = _ffi.make_popts(options, S)
     aT = np.empty((S, 8, 7)); bT = np.empty((S, 8)); sc = np.empty((S, _ffi.NTERM_SCALARS))
     lib = _ffi.load(); ctx = _ffi.context(device)
     import ctypes as C
-    rc = lib.mpcx_constraint_terms(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
-                                   _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc))
+    if popts is None:
+        rc = lib.mpcx_constraint_terms(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
+                                       _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc))
+    else:
+        rc = lib.mpcx_constraint_terms_sat(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
+                                           _ffi.dptr(popts), _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc))
     _ffi.check(rc, ctx, "mpcx_constraint_terms")
     return aT, bT, sc
 
@@ -106,7 +112,7 @@ def _tf_io(S, fixed_tf):
 
 def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False, max_step=1e-2, device=0, slot=0,
                    linear_vt=False, fixed_tf=None, pinned_results=False, uniform_steps=0, regularised=False, Ks=None, shared_tf=False,
-                   devices=None, rk23=False, out=None, include_drag=False, **solver):
+                   devices=None, rk23=False, out=None, include_drag=False, popts=None, **solver):
     """S independent satellite-MPC-steps (discretize + solve) on the device.
     xbar (S,7,K), ubar (S,3,K), tf (S,), consts (S,8), r_des (S,) -> SolveResult with batched arrays.
     include_drag / include_J2: the linearisation of Discretizer(include_drag=..., include_J2=...), drag with the simulator's
@@ -120,7 +126,12 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
     host thread and context per device, no exchange between them), every block writing its results in place into its slice of
     ONE result set for the constellation (page-locked with pinned_results=True: then every device's DMA lands in the caller's
     arrays directly); satellites are independent units, so every satellite gets bit for bit what a single-device call gives it.
-    out: (internal) views of such a result set for this call's satellites -- X, U, NU, tf, status, iters, kkt[, regularised]."""
+    out: (internal) views of such a result set for this call's satellites -- X, U, NU, tf, status, iters, kkt[, regularised].
+    options may hold per-satellite values -- (S,) arrays, (S, 2) for u_lim / r_lim (_ffi.make_popts): satellite s is then posed
+    with row s of the table and gets bit for bit what a call with that row as scalar options gives it; not with shared_tf.
+    popts: (internal) a block's rows of such a table, cut by sharded_call like r_des."""
+    if shared_tf:
+        _ffi.refuse_per_satellite(options, "mpc_step_batch(shared_tf=True)")
     if devices is not None and len(devices) > 1:
         if shared_tf or fixed_tf is not None:
             raise ValueError("devices=[...]: independent per-satellite problems only (no shared / fixed tf)")
@@ -130,10 +141,10 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         Ksb = None if Ks is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
         X, U, NU, kkt, status, iters = _result_arrays(S, K, tuple(int(d) for d in devices) if pinned_results else int(devices[0]), pinned_results)
         tfo = np.empty(S); reg = np.zeros((S, 2), dtype=np.int32) if regularised else None
-        fn = lambda x, u, t, c, r, k, device, slot, out: mpc_step_batch(x, u, t, c, r, options, include_J2, max_step, device, slot, linear_vt,
-                                                                        None, False, uniform_steps, regularised, k, False, None, rk23, out,
-                                                                        include_drag, **solver)
-        sharded_call(fn, devices, [xbar, _ffi.as_f64(ubar), bc(tf), _ffi.as_f64(consts), bc(r_des), Ksb],
+        fn = lambda x, u, t, c, r, k, po, device, slot, out: mpc_step_batch(x, u, t, c, r, _ffi.scalar_options(options), include_J2, max_step,
+                                                                            device, slot, linear_vt, None, False, uniform_steps, regularised,
+                                                                            k, False, None, rk23, out, include_drag, po, **solver)
+        sharded_call(fn, devices, [xbar, _ffi.as_f64(ubar), bc(tf), _ffi.as_f64(consts), bc(r_des), Ksb, _ffi.make_popts(options, S)],
                      dict(X=X, U=U, NU=NU, kkt=kkt, status=status, iters=iters, tf=tfo, regularised=reg))
         return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg)
     if devices is not None and len(devices) == 1:
@@ -147,6 +158,7 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
     r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
     consts = _ffi.as_f64(consts)
     opts = _ffi.make_solve_opts(options, **solver)
+    popts = _block_popts(popts, options, S)
     if out is None:
         X, U, NU, kkt, status, iters = _result_arrays(S, K, device, pinned_results and slot == 0)
         tfo, held = _tf_io(S, fixed_tf)
@@ -163,7 +175,13 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         dflags |= _ffi.FLAG_UNIFORM_STEPS | (int(uniform_steps) << 8)
     if rk23:                                  # Discretizer.ivp_solver = 'RK23'
         dflags |= _ffi.FLAG_RK23
-    if Ks is None:
+    if popts is not None:
+        Ks = None if Ks is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
+        rc = lib.mpcx_mpc_step_batch_ragged_sat(ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(xbar), _ffi.dptr(ubar),
+                                                _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), dflags, float(max_step),
+                                                C.byref(opts), _ffi.dptr(popts), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU),
+                                                _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt))
+    elif Ks is None:
         rc = lib.mpcx_mpc_step_batch(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts),
                                      _ffi.dptr(r_des), dflags, float(max_step), C.byref(opts),
                                      _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status),
@@ -180,6 +198,17 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         oa.finish()
     return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg) if held is None else \
         SolveResult(X, U, NU, held, status, iters, kkt, tfo, reg)
+
+
+def _block_popts(popts, options, S):
+    """the option table of a call for S satellites: the rows handed in (a block of a multi-device call) or the table of
+    `options` (None: scalar options only)"""
+    if popts is None:
+        return _ffi.make_popts(options, S)
+    popts = _ffi.as_f64(popts)
+    if popts.shape != (S, _ffi.NPOPT):
+        raise ValueError(f"popts: expected ({S}, {_ffi.NPOPT}), got {popts.shape}")
+    return popts
 
 
 def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Kus=None, include_J2=False, max_step=1e-2,
@@ -211,6 +240,7 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     if Ks is not None: Ks = np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
     if Kus is not None: Kus = np.ascontiguousarray(np.broadcast_to(np.asarray(Kus), (S,)), dtype=np.int32)
     opts = _ffi.make_solve_opts(options, **solver)
+    popts = _ffi.make_popts(options, S)          # (per-satellite options: every satellite solved under its own row)
     X, U, NU, kkt, status, iters = _result_arrays(S, K, device, False)
     tfo = np.empty(S); pst = np.zeros(S, dtype=np.int32)
     xb = np.empty((S, 7, K)) if return_reference else None
@@ -218,13 +248,15 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     prop_flags, disc_flags = scp_flags(include_drag, include_J2, rollout_model)
     lib = _ffi.load(); ctx = _ffi.context(device, slot)
     import ctypes as C
-    rc = lib.mpcx_scp_iteration_batch_ragged(ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(y0), _ffi.dptr(tf),
-                                             _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags, kind, vec_p, int(Ku),
-                                             None if Kus is None else _ffi.iptr(Kus), et_p, float(prop_max_step),
-                                             disc_flags, float(max_step), C.byref(opts),
-                                             None if xb is None else _ffi.dptr(xb), None if ub is None else _ffi.dptr(ub),
-                                             _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status),
-                                             _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst))
+    head = (ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(y0), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags,
+            kind, vec_p, int(Ku), None if Kus is None else _ffi.iptr(Kus), et_p, float(prop_max_step), disc_flags, float(max_step),
+            C.byref(opts))
+    tail = (None if xb is None else _ffi.dptr(xb), None if ub is None else _ffi.dptr(ub), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU),
+            _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst))
+    if popts is None:
+        rc = lib.mpcx_scp_iteration_batch_ragged(*head, *tail)
+    else:
+        rc = lib.mpcx_scp_iteration_batch_ragged_sat(*head, _ffi.dptr(popts), *tail)
     _ffi.check(rc, ctx, "mpcx_scp_iteration_batch_ragged")
     res = SolveResult(X, U, NU, tfo, status, iters, kkt)
     res.prop_status = pst; res.xbar = xb; res.ubar = ub
@@ -238,7 +270,7 @@ class UpdateResult(SolveResult):
 
 def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None, ref_thrust=0.5, include_J2=False, max_step=1e-2,
                      prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, out=None, include_drag=False,
-                     rollout_model=False, **solver):
+                     rollout_model=False, popts=None, **solver):
     """OptimalController.update (control.py:170-235) for S satellites in ONE library call (mpcx_mpc_update_batch): the tangential
     reference rollout over `horizon` sampled at K = int(base_res * horizon) nodes, n_scp x (extract_uk, discretise, solve) with
     the nonlinear re-rollout under the optimised sequence -- sampled at int(base_res * tf_u) nodes per satellite -- between
@@ -248,17 +280,19 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     the result then carries y_sim (S,7,n_eval) and sim_status.
     Planning model (update_flags): include_drag / include_J2 in every linearisation; rollout_model=True flies the planning
     rollouts with them too (MPCX_FLAG_PLAN_ROLLOUTS).  The defaults are the reference's planner, which has neither.
-    devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (see mpc_step_batch)."""
+    devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (see mpc_step_batch).
+    options may hold per-satellite values (_ffi.make_popts): every SCP iteration solves satellite s under row s of the table.
+    popts: (internal) a block's rows of that table."""
     if devices is not None and len(devices) > 1:
         from .sharding import sharded_call
         y0 = _ffi.as_f64(y0); S = y0.shape[0]
         bc = lambda a: _ffi.as_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (S,)))
         hz = bc(horizon); K = int(base_res * float(hz[0]))
         res = _update_result(S, K, n_scp, int(devices[0]), fly)          # ONE result set; every block fills its satellites' part
-        fn = lambda y, h, c, r, device, slot, out: mpc_update_batch(y, h, c, r, base_res, n_scp, options, ref_thrust, include_J2, max_step,
-                                                                    prop_max_step, device, slot, linear_vt, fly, None, out, include_drag,
-                                                                    rollout_model, **solver)
-        sharded_call(fn, devices, [y0, hz, _ffi.as_f64(consts), bc(r_des)],
+        fn = lambda y, h, c, r, po, device, slot, out: mpc_update_batch(y, h, c, r, base_res, n_scp, _ffi.scalar_options(options), ref_thrust,
+                                                                        include_J2, max_step, prop_max_step, device, slot, linear_vt, fly,
+                                                                        None, out, include_drag, rollout_model, po, **solver)
+        sharded_call(fn, devices, [y0, hz, _ffi.as_f64(consts), bc(r_des), _ffi.make_popts(options, S)],
                      dict(X=res.X, U=res.U, NU=res.NU, kkt=res.kkt, tf=res.tf, Ks=res.Ks, prop_status=res.prop_status,
                           status=(res.status, 1), iters=(res.iters, 1), y_sim=res.y_sim, sim_status=res.sim_status))
         return res
@@ -273,6 +307,7 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
     consts = _ffi.as_f64(consts)
     opts = _ffi.make_solve_opts(options, **solver)
+    popts = _block_popts(popts, options, S)
     sim = (0.0, 0.0, 0, 0, 1e-3)
     if fly is not None:
         tf_sim, interval, n_eval, drag, j2 = fly[:5]
@@ -294,12 +329,15 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
         res.Ks = Ks; res.prop_status = pst; res.y_sim = y_sim; res.sim_status = sst
     lib = _ffi.load(); ctx = _ffi.context(device, slot)
     import ctypes as C
-    rc = lib.mpcx_mpc_update_batch(ctx, S, K, int(n_scp), float(base_res), _ffi.dptr(y0), _ffi.dptr(horizon), _ffi.dptr(consts),
-                                   _ffi.dptr(r_des), float(ref_thrust), float(prop_max_step),
-                                   update_flags(include_drag, include_J2, rollout_model),
-                                   float(max_step), C.byref(opts), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo),
-                                   _ffi.iptr(Ks), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst), sim[0], sim[1],
-                                   sim[2], sim[3], sim[4], None if y_sim is None else _ffi.dptr(y_sim), None if sst is None else _ffi.iptr(sst))
+    head = (ctx, S, K, int(n_scp), float(base_res), _ffi.dptr(y0), _ffi.dptr(horizon), _ffi.dptr(consts), _ffi.dptr(r_des), float(ref_thrust),
+            float(prop_max_step), update_flags(include_drag, include_J2, rollout_model), float(max_step), C.byref(opts))
+    tail = (_ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(Ks), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt),
+            _ffi.iptr(pst), sim[0], sim[1], sim[2], sim[3], sim[4], None if y_sim is None else _ffi.dptr(y_sim),
+            None if sst is None else _ffi.iptr(sst))
+    if popts is None:
+        rc = lib.mpcx_mpc_update_batch(*head, *tail)
+    else:
+        rc = lib.mpcx_mpc_update_batch_sat(*head, _ffi.dptr(popts), *tail)
     _ffi.check(rc, ctx, "mpcx_mpc_update_batch")
     if out is not None:
         oa.finish()
@@ -318,7 +356,10 @@ def _update_result(S, K, n_scp, device, fly):
 
 def solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options=None, device=0, linear_vt=False, fixed_tf=None,
                 regularised=False, shared_tf=False, **solver):
-    """Solve only (dynamics already discretised, reference-shaped arrays with a leading satellite axis)."""
+    """Solve only (dynamics already discretised, reference-shaped arrays with a leading satellite axis).  options may hold
+    per-satellite values (_ffi.make_popts); not with shared_tf."""
+    if shared_tf:
+        _ffi.refuse_per_satellite(options, "solve_batch(shared_tf=True)")
     solver = _solver_flags(solver, linear_vt, fixed_tf, shared_tf)
     xbar = _ffi.as_f64(xbar); ubar = _ffi.as_f64(ubar)
     S, _, K = xbar.shape
@@ -327,15 +368,19 @@ def solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options=Non
     r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
     consts = _ffi.as_f64(consts)
     opts = _ffi.make_solve_opts(options, **solver)
+    popts = _ffi.make_popts(options, S)
     X = np.empty((S, 7, K)); U = np.empty((S, 3, K)); NU = np.empty((S, 7, K)); kkt = np.empty(S)
     tfo, held = _tf_io(S, fixed_tf)
     status = np.zeros(S, dtype=np.int32); iters = np.zeros(S, dtype=np.int32)
     lib = _ffi.load(); ctx = _ffi.context(device)
     import ctypes as C
-    rc = lib.mpcx_solve_batch(ctx, S, K, *[_ffi.dptr(a) for a in arrs], _ffi.dptr(xbar), _ffi.dptr(ubar),
-                              _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts), _ffi.dptr(X),
-                              _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters),
-                              _ffi.dptr(kkt))
+    head = (ctx, S, K, *[_ffi.dptr(a) for a in arrs], _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des),
+            C.byref(opts))
+    tail = (_ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt))
+    if popts is None:
+        rc = lib.mpcx_solve_batch(*head, *tail)
+    else:
+        rc = lib.mpcx_solve_batch_sat(*head, _ffi.dptr(popts), *tail)
     _ffi.check(rc, ctx, "mpcx_solve_batch")
     reg = _regularised(lib, ctx, S) if regularised else None
     return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg) if held is None else \
@@ -416,6 +461,7 @@ def solve_shared_tf(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options
     result is returned with the status set and the search marked not converged; one that stops at max_iter is used as it
     is and recorded in the search's message -- the reference never raises from solve_OPT (optimizer.py:603 ignores
     ipopt's status)."""
+    _ffi.refuse_per_satellite(options, "solve_shared_tf")
     opts = {**DEFAULT_OPTIONS, **(options or {})}
     S = np.asarray(xbar).shape[0]
     if monolithic:
@@ -556,6 +602,8 @@ class Optimizer:
         """Transcribe-and-solve replacement (optimizer.py:219-613).  Extra keyword arguments are solver
         controls (tol, acceptable_tol, max_iter, acceptable_iter, n_refine)."""
         options = self.init_options(input_options)
+        if self._N > 1:      # (the reference's Optimizer poses ONE problem with one option set for its satellites, optimizer.py:178-188)
+            _ffi.refuse_per_satellite(options, "Optimizer.solve_OPT with several satellites")
         if getattr(self.f, "__name__", "") != "satellite_dynamics":
             raise NotImplementedError("only Simulator.satellite_dynamics is implemented on the device")
         self.d._check_modes()
