@@ -103,22 +103,21 @@ _SIGS = {
                                         C.c_double, _po, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _ip, C.c_double, C.c_double, C.c_int, C.c_int,
                                         C.c_double, _dp, _ip]),
     "mpcx_resample_sequence_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
-    # per-satellite problem options: the table popts [S][NPOPT] directly after the options
-    "mpcx_constraint_terms_sat": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _po, _dp, _dp, _dp, _dp]),
-    "mpcx_constraint_terms_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _po, _vp, _vp, _vp, _vp, _vp]),
-    "mpcx_solve_batch_sat": (C.c_int, [_vp, C.c_int, C.c_int] + [_dp] * 10 + [_po, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp]),
-    "mpcx_solve_batch_ragged_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 6 + [_po, _vp] + [_vp] * 7 + [_vp, _vp]),
-    "mpcx_mpc_step_batch_ragged_sat": (C.c_int, [_vp, C.c_int, C.c_int, _ip] + [_dp] * 5 + [C.c_int, C.c_double, _po, _dp, _dp, _dp, _dp,
-                                                                                         _dp, _ip, _ip, _dp]),
-    "mpcx_mpc_step_batch_ragged_sat_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp] + [_vp] * 5 + [C.c_int, C.c_double, _po, _vp] + [_vp] * 7
-                                           + [_vp, _vp]),
-    "mpcx_scp_iteration_batch_ragged_sat": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp,
-                                                      C.c_double, C.c_int, C.c_double, _po, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp,
-                                                      _ip]),
-    "mpcx_mpc_update_batch_sat": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int,
-                                            C.c_double, _po, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _ip, C.c_double, C.c_double, C.c_int,
-                                            C.c_int, C.c_double, _dp, _ip]),
 }
+
+
+def _sat_twin(name):
+    """(name, signature) of an entry point's per-satellite twin (include/mpcx.h): `_sat` in the name, the option table
+    popts [S][NPOPT] directly after the options pointer"""
+    res, args = _SIGS[name]
+    dev = name.endswith("_dev")
+    i = args.index(_po) + 1
+    return (name[:-4] + "_sat_dev" if dev else name + "_sat"), (res, args[:i] + [_vp if dev else _dp] + args[i:])
+
+
+_SIGS.update([_sat_twin(n) for n in ("mpcx_constraint_terms", "mpcx_constraint_terms_dev", "mpcx_solve_batch", "mpcx_solve_batch_ragged_dev",
+                                     "mpcx_mpc_step_batch_ragged", "mpcx_mpc_step_batch_ragged_dev", "mpcx_scp_iteration_batch_ragged",
+                                     "mpcx_mpc_update_batch")])
 
 
 def exported_symbols():
@@ -278,6 +277,67 @@ def iptr(a):
     return a.ctypes.data_as(_ip)
 
 
+def dptr_opt(a):
+    """pointer, or NULL for None"""
+    return None if a is None else dptr(a)
+
+
+def iptr_opt(a):
+    return None if a is None else iptr(a)
+
+
+def per_sat(a, S):
+    """a scalar or (S,) values as the contiguous float64 (S,) array the entry points take"""
+    return as_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (S,)))
+
+
+def counts(a, S):
+    """optional per-satellite counts (Ks, Kus, n_eval): None stays None (NULL), anything else becomes (S,) int32"""
+    return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a), (S,)), dtype=np.int32)
+
+
+def thrust_law(law, S):
+    """law = (kind, vec, Ku, end_tau) with per-satellite or broadcastable parameters -> (kind, vec, Ku, end_tau) as the
+    propagating entry points take them: vec (S,3) CONSTANT, (S,) TANGENTIAL, (S,3,Ku) SEQUENCE, None otherwise; end_tau (S,)
+    for SEQUENCE and None otherwise"""
+    kind, vec, Ku, end_tau = law
+    if kind == CTRL_CONSTANT:
+        vec = as_f64(np.broadcast_to(np.asarray(vec, dtype=np.float64).reshape(-1, 3), (S, 3)))
+    elif kind == CTRL_TANGENTIAL:
+        vec = per_sat(np.asarray(vec, dtype=np.float64).reshape(-1), S)
+    elif kind == CTRL_SEQUENCE:
+        vec = np.asarray(vec, dtype=np.float64)
+        vec = as_f64(np.broadcast_to(vec if vec.ndim == 3 else vec[None], (S, 3, Ku)))
+    else:
+        vec = None
+    return kind, vec, int(Ku), per_sat(end_tau, S) if kind == CTRL_SEQUENCE else None
+
+
+def model_flags(include_drag, include_J2):
+    return (FLAG_DRAG if include_drag else 0) | (FLAG_J2 if include_J2 else 0)
+
+
+def discretize_flags(include_drag, include_J2, uniform_steps=0, rk23=False):
+    """flags of the discretize / fused-step entry points (include/mpcx.h): the model, Discretizer.use_uniform_steps with
+    integrator_steps = uniform_steps (0: adaptive steps), ivp_solver = 'RK23'"""
+    flags = model_flags(include_drag, include_J2)
+    if uniform_steps:
+        flags |= FLAG_UNIFORM_STEPS | (int(uniform_steps) << 8)
+    if rk23:
+        flags |= FLAG_RK23
+    return flags
+
+
+def call(name, *args, popts=None):
+    """Call entry point `name` with args (the context first) and raise MpcxError unless it returns 0.  popts: a per-satellite
+    option table -- the call is then the entry point's `_sat` twin, the table's pointer directly after the options pointer.
+    The function is looked up on the library at call time (callers may wrap an entry point, e.g. to time it)."""
+    if popts is not None:
+        i = _SIGS[name][1].index(_po) + 1
+        name, args = name + "_sat", (*args[:i], dptr(popts), *args[i:])
+    check(getattr(load(), name)(*args), args[0], name)
+
+
 SOLVER_KEYWORDS = ("tol", "acceptable_tol", "max_iter", "acceptable_iter", "n_refine", "flags")
 SOLVE_INDEX_ORDER, SOLVE_LINEAR_VT, SOLVE_FIXED_TF, SOLVE_SHARED_TF, SOLVE_ONE_WAVE, SOLVE_NO_LDS, SOLVE_TIME_PARALLEL = 1, 2, 4, 8, 16, 32, 64      # mpcx_solve_opts.flags (include/mpcx.h)
 SOLVE_TP_SELFTEST_DEAD = 1 << 30
@@ -338,10 +398,6 @@ def make_popts(options, S):
                 if c is not None:
                     tab[:, c] = v[..., j]
     return np.ascontiguousarray(tab)
-
-
-def popts_ptr(popts):
-    return None if popts is None else dptr(popts)
 
 
 def scalar_options(options):

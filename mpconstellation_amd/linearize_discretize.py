@@ -49,10 +49,8 @@ class Discretizer:
         status = np.zeros(S, dtype=np.int32)
         lib = _ffi.load()
         ctx = _ffi.context(self.device)
-        flags = _ffi.FLAG_J2 if self.include_J2 else 0
-        flags |= self.device_flags()
         rc = lib.mpcx_discretize_batch(ctx, S, K, Ku, _ffi.dptr(x), _ffi.dptr(u), _ffi.dptr(tf),
-                                       _ffi.dptr(consts), flags, float(self.ivp_max_step),
+                                       _ffi.dptr(consts), self.device_flags(self.include_J2), float(self.ivp_max_step),
                                        _ffi.dptr(A), _ffi.dptr(Bp), _ffi.dptr(Bn), _ffi.dptr(Sig),
                                        _ffi.dptr(xi), _ffi.iptr(status))
         _ffi.check(rc, ctx, "mpcx_discretize_batch")
@@ -77,16 +75,12 @@ class Discretizer:
             raise RuntimeError(_ffi.STATUS_TEXT.get(int(status[0]), "discretize failed"))
         return A[0], Bp[0], Bn[0], Sig[0], xi[0]
 
-    def device_flags(self):
+    def device_flags(self, include_J2=False):
         """the linearisation's settings as flags of the discretize / fused-step entry points (include/mpcx.h): include_drag
         (:162-173, with the simulator's atmosphere), use_uniform_steps with integrator_steps (linearize_discretize.py:27-30:
-        t_eval = linspace(.., integrator_steps)), ivp_solver (:40)"""
-        flags = _ffi.FLAG_DRAG if self.include_drag else 0
-        if self.use_uniform_steps:
-            flags |= _ffi.FLAG_UNIFORM_STEPS | (int(self.integrator_steps) << 8)
-        if self.ivp_solver == 'RK23':
-            flags |= _ffi.FLAG_RK23
-        return flags
+        t_eval = linspace(.., integrator_steps)), ivp_solver (:40); include_J2: with MPCX_FLAG_J2"""
+        return _ffi.discretize_flags(self.include_drag, include_J2, int(self.integrator_steps) if self.use_uniform_steps else 0,
+                                     self.ivp_solver == 'RK23')
 
     def _check_modes(self):
         if self.include_drag and (self.rho_func is not None or self.drho_func is not None):

@@ -1,6 +1,8 @@
 """Optimizer: drop-in for the reference class of the same name (reference optimizer.py:12-613).
 solve_OPT runs discretize -> constraint terms -> interior-point solve on the MI355X through libmpcx.so
 (mpcx_mpc_step_batch); there is no pyomo model and no ipopt subprocess, and no host fallback."""
+import ctypes as C
+
 import numpy as np
 
 from . import _ffi
@@ -20,13 +22,6 @@ class SolveResult:
         self.first_regularised = None if regularised is None else regularised[:, 1]
 
 
-def _regularised(lib, ctx, S, out=None):
-    """mpcx_solve_regularised of the solve that just returned on this context"""
-    out = np.zeros((S, 2), dtype=np.int32) if out is None else out
-    _ffi.check(lib.mpcx_solve_regularised(ctx, S, _ffi.iptr(out)), ctx, "mpcx_solve_regularised")
-    return out
-
-
 def constraint_terms_batch(xbar, consts, r_des, options=None, device=0, linear_vt=False):
     """What the device builds from Optimizer.get_constraint_terms (optimizer.py:80-170) before its first iteration
     (include/mpcx.h, mpcx_constraint_terms): aT (S,8,7), bT (S,8), scalars (S,8).
@@ -34,19 +29,11 @@ def constraint_terms_batch(xbar, consts, r_des, options=None, device=0, linear_v
     xbar = _ffi.as_f64(xbar)
     S, _, K = xbar.shape
     consts = _ffi.as_f64(consts)
-    r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
+    r_des = _ffi.per_sat(r_des, S)
     opts = _ffi.make_solve_opts(options, **_solver_flags({}, linear_vt))
-    popts = _ffi.make_popts(options, S)
     aT = np.empty((S, 8, 7)); bT = np.empty((S, 8)); sc = np.empty((S, _ffi.NTERM_SCALARS))
-    lib = _ffi.load(); ctx = _ffi.context(device)
-    import ctypes as C
-    if popts is None:
-        rc = lib.mpcx_constraint_terms(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
-                                       _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc))
-    else:
-        rc = lib.mpcx_constraint_terms_sat(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
-                                           _ffi.dptr(popts), _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc))
-    _ffi.check(rc, ctx, "mpcx_constraint_terms")
+    _ffi.call("mpcx_constraint_terms", _ffi.context(device), S, K, _ffi.dptr(xbar), _ffi.dptr(consts), _ffi.dptr(r_des), C.byref(opts),
+              _ffi.dptr(aT), _ffi.dptr(bT), _ffi.dptr(sc), popts=_ffi.make_popts(options, S))
     return aT, bT, sc
 
 
@@ -65,22 +52,22 @@ def _solver_flags(solver, linear_vt, fixed_tf=None, shared_tf=False):
     return solver
 
 
-def _model_flags(include_drag, include_J2):
-    return (_ffi.FLAG_DRAG if include_drag else 0) | (_ffi.FLAG_J2 if include_J2 else 0)
-
-
 def scp_flags(include_drag=False, include_J2=False, rollout_model=False):
     """(prop_flags, disc_flags) of an SCP iteration (mpcx_scp_iteration_batch_ragged) that plans with the given model: the
     linearisation with drag / J2, and -- rollout_model=True -- the rollout too.  The reference's planner has neither
     (control.py:187, 237-240): all defaults."""
-    model = _model_flags(include_drag, include_J2)
+    model = _ffi.model_flags(include_drag, include_J2)
     return (model if rollout_model else 0), model
 
 
 def update_flags(include_drag=False, include_J2=False, rollout_model=False):
     """disc_flags of an update (mpcx_mpc_update_batch) that plans with the given model: rollout_model=True adds
     MPCX_FLAG_PLAN_ROLLOUTS, which gives its planning rollouts the discretisation's drag / J2."""
-    return _model_flags(include_drag, include_J2) | (_ffi.FLAG_PLAN_ROLLOUTS if rollout_model else 0)
+    return _ffi.model_flags(include_drag, include_J2) | (_ffi.FLAG_PLAN_ROLLOUTS if rollout_model else 0)
+
+
+def _many(devices):
+    return devices is not None and len(devices) > 1
 
 
 _pinned_results = {}
@@ -106,13 +93,18 @@ def _tf_io(S, fixed_tf):
     """tf_out buffer: plain output, or (fixed-tf mode) the values to hold on entry and g_s on exit"""
     if fixed_tf is None:
         return np.empty(S), None
-    held = _ffi.as_f64(np.broadcast_to(np.asarray(fixed_tf, dtype=np.float64), (S,))).copy()
+    held = _ffi.per_sat(fixed_tf, S).copy()
     return held.copy(), held
+
+
+def _solve_result(X, U, NU, tfo, held, status, iters, kkt, reg):
+    return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg) if held is None else \
+        SolveResult(X, U, NU, held, status, iters, kkt, tfo, reg)
 
 
 def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False, max_step=1e-2, device=0, slot=0,
                    linear_vt=False, fixed_tf=None, pinned_results=False, uniform_steps=0, regularised=False, Ks=None, shared_tf=False,
-                   devices=None, rk23=False, out=None, include_drag=False, popts=None, **solver):
+                   devices=None, rk23=False, include_drag=False, **solver):
     """S independent satellite-MPC-steps (discretize + solve) on the device.
     xbar (S,7,K), ubar (S,3,K), tf (S,), consts (S,8), r_des (S,) -> SolveResult with batched arrays.
     include_drag / include_J2: the linearisation of Discretizer(include_drag=..., include_J2=...), drag with the simulator's
@@ -126,89 +118,50 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
     host thread and context per device, no exchange between them), every block writing its results in place into its slice of
     ONE result set for the constellation (page-locked with pinned_results=True: then every device's DMA lands in the caller's
     arrays directly); satellites are independent units, so every satellite gets bit for bit what a single-device call gives it.
-    out: (internal) views of such a result set for this call's satellites -- X, U, NU, tf, status, iters, kkt[, regularised].
     options may hold per-satellite values -- (S,) arrays, (S, 2) for u_lim / r_lim (_ffi.make_popts): satellite s is then posed
-    with row s of the table and gets bit for bit what a call with that row as scalar options gives it; not with shared_tf.
-    popts: (internal) a block's rows of such a table, cut by sharded_call like r_des."""
+    with row s of the table and gets bit for bit what a call with that row as scalar options gives it; not with shared_tf."""
     if shared_tf:
         _ffi.refuse_per_satellite(options, "mpc_step_batch(shared_tf=True)")
-    if devices is not None and len(devices) > 1:
-        if shared_tf or fixed_tf is not None:
-            raise ValueError("devices=[...]: independent per-satellite problems only (no shared / fixed tf)")
-        from .sharding import sharded_call
-        xbar = _ffi.as_f64(xbar); S, _, K = xbar.shape
-        bc = lambda a: _ffi.as_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (S,)))
-        Ksb = None if Ks is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
-        X, U, NU, kkt, status, iters = _result_arrays(S, K, tuple(int(d) for d in devices) if pinned_results else int(devices[0]), pinned_results)
-        tfo = np.empty(S); reg = np.zeros((S, 2), dtype=np.int32) if regularised else None
-        fn = lambda x, u, t, c, r, k, po, device, slot, out: mpc_step_batch(x, u, t, c, r, _ffi.scalar_options(options), include_J2, max_step,
-                                                                            device, slot, linear_vt, None, False, uniform_steps, regularised,
-                                                                            k, False, None, rk23, out, include_drag, po, **solver)
-        sharded_call(fn, devices, [xbar, _ffi.as_f64(ubar), bc(tf), _ffi.as_f64(consts), bc(r_des), Ksb, _ffi.make_popts(options, S)],
-                     dict(X=X, U=U, NU=NU, kkt=kkt, status=status, iters=iters, tf=tfo, regularised=reg))
-        return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg)
+    many = _many(devices)
+    if many and (shared_tf or fixed_tf is not None):
+        raise ValueError("devices=[...]: independent per-satellite problems only (no shared / fixed tf)")
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
-    solver = _solver_flags(solver, linear_vt, fixed_tf, shared_tf)
     xbar = _ffi.as_f64(xbar); ubar = _ffi.as_f64(ubar)
     S, _, K = xbar.shape
     if xbar.shape[1] != 7 or ubar.shape != (S, 3, K):
         raise ValueError("expected xbar (S,7,K) and ubar (S,3,K)")
-    tf = _ffi.as_f64(np.broadcast_to(np.asarray(tf, dtype=np.float64), (S,)))
-    r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
-    consts = _ffi.as_f64(consts)
-    opts = _ffi.make_solve_opts(options, **solver)
-    popts = _block_popts(popts, options, S)
-    if out is None:
-        X, U, NU, kkt, status, iters = _result_arrays(S, K, device, pinned_results and slot == 0)
-        tfo, held = _tf_io(S, fixed_tf)
-    else:                                                  # (a block of a multi-device call: its slice of the constellation's arrays)
-        from .sharding import OutArrays
-        oa = OutArrays(out)
-        X, U, NU = oa.get("X", (S, 7, K)), oa.get("U", (S, 3, K)), oa.get("NU", (S, 7, K))
-        kkt, status, iters = oa.get("kkt", (S,)), oa.get("status", (S,), np.int32), oa.get("iters", (S,), np.int32)
-        tfo, held = oa.get("tf", (S,)), None
-    lib = _ffi.load(); ctx = _ffi.context(device, slot)
-    import ctypes as C
-    dflags = _model_flags(include_drag, include_J2)
-    if uniform_steps:                         # Discretizer.use_uniform_steps with integrator_steps = uniform_steps
-        dflags |= _ffi.FLAG_UNIFORM_STEPS | (int(uniform_steps) << 8)
-    if rk23:                                  # Discretizer.ivp_solver = 'RK23'
-        dflags |= _ffi.FLAG_RK23
-    if popts is not None:
-        Ks = None if Ks is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
-        rc = lib.mpcx_mpc_step_batch_ragged_sat(ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(xbar), _ffi.dptr(ubar),
-                                                _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), dflags, float(max_step),
-                                                C.byref(opts), _ffi.dptr(popts), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU),
-                                                _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt))
-    elif Ks is None:
-        rc = lib.mpcx_mpc_step_batch(ctx, S, K, _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts),
-                                     _ffi.dptr(r_des), dflags, float(max_step), C.byref(opts),
-                                     _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status),
-                                     _ffi.iptr(iters), _ffi.dptr(kkt))
+    batched = [xbar, ubar, _ffi.per_sat(tf, S), _ffi.as_f64(consts), _ffi.per_sat(r_des, S), _ffi.counts(Ks, S), _ffi.make_popts(options, S)]
+    how = dict(opts=_ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt, fixed_tf, shared_tf)),
+               dflags=_ffi.discretize_flags(include_drag, include_J2, uniform_steps, rk23), max_step=float(max_step))
+    if many:                                               # ONE result set; every block fills its satellites' part
+        X, U, NU, kkt, status, iters = _result_arrays(S, K, tuple(int(d) for d in devices) if pinned_results else int(devices[0]), pinned_results)
     else:
-        Ks = np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
-        rc = lib.mpcx_mpc_step_batch_ragged(ctx, S, K, _ffi.iptr(Ks), _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf),
-                                            _ffi.dptr(consts), _ffi.dptr(r_des), dflags, float(max_step), C.byref(opts),
-                                            _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status),
-                                            _ffi.iptr(iters), _ffi.dptr(kkt))
-    _ffi.check(rc, ctx, "mpcx_mpc_step_batch")
-    reg = _regularised(lib, ctx, S, None if out is None else out.get("regularised")) if regularised else None
-    if out is not None:
-        oa.finish()
-    return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg) if held is None else \
-        SolveResult(X, U, NU, held, status, iters, kkt, tfo, reg)
+        X, U, NU, kkt, status, iters = _result_arrays(S, K, device, pinned_results and slot == 0)
+    tfo, held = _tf_io(S, fixed_tf)
+    reg = np.zeros((S, 2), dtype=np.int32) if regularised else None
+    out = dict(X=X, U=U, NU=NU, kkt=kkt, status=status, iters=iters, tf=tfo, regularised=reg)
+    if many:
+        from .sharding import sharded_call
+        sharded_call(_step_call, devices, batched, out, **how)
+    else:
+        _step_call(*batched, device=device, slot=slot, out=out, **how)
+    return _solve_result(X, U, NU, tfo, held, status, iters, kkt, reg)
 
 
-def _block_popts(popts, options, S):
-    """the option table of a call for S satellites: the rows handed in (a block of a multi-device call) or the table of
-    `options` (None: scalar options only)"""
-    if popts is None:
-        return _ffi.make_popts(options, S)
-    popts = _ffi.as_f64(popts)
-    if popts.shape != (S, _ffi.NPOPT):
-        raise ValueError(f"popts: expected ({S}, {_ffi.NPOPT}), got {popts.shape}")
-    return popts
+def _step_call(xbar, ubar, tf, consts, r_des, Ks, popts, *, device, slot, out, opts, dflags, max_step):
+    """One step call on context (device, slot): the normalised inputs of the context's satellites (a whole batch, or a block of
+    a multi-device call) and `out`, their part of the result set -- X, U, NU, tf, status, iters, kkt, and regularised (S,2)
+    where mpcx_solve_regularised of the solve is wanted."""
+    S, _, K = xbar.shape
+    ctx = _ffi.context(device, slot)
+    ragged = Ks is not None or popts is not None           # (the table comes with the ragged entry point only; its Ks may be NULL)
+    _ffi.call("mpcx_mpc_step_batch_ragged" if ragged else "mpcx_mpc_step_batch", ctx, S, K, *([_ffi.iptr_opt(Ks)] if ragged else []),
+              _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), dflags, max_step, C.byref(opts),
+              _ffi.dptr(out["X"]), _ffi.dptr(out["U"]), _ffi.dptr(out["NU"]), _ffi.dptr(out["tf"]), _ffi.iptr(out["status"]),
+              _ffi.iptr(out["iters"]), _ffi.dptr(out["kkt"]), popts=popts)
+    if out.get("regularised") is not None:
+        _ffi.call("mpcx_solve_regularised", ctx, S, _ffi.iptr(out["regularised"]))
 
 
 def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Kus=None, include_J2=False, max_step=1e-2,
@@ -222,42 +175,22 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     extra attribute prop_status (S,).
     Planning model (scp_flags): include_drag / include_J2 in the linearisation; rollout_model=True flies the rollout with them
     too (the reference's rollout has neither)."""
-    solver = _solver_flags(solver, linear_vt, None, False)
     y0 = _ffi.as_f64(y0); S = y0.shape[0]; K = int(K)
-    tf = _ffi.as_f64(np.broadcast_to(np.asarray(tf, dtype=np.float64), (S,)))
-    r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
+    tf = _ffi.per_sat(tf, S); r_des = _ffi.per_sat(r_des, S)
     consts = _ffi.as_f64(consts)
-    kind, vec, Ku, end_tau = law
-    vec_p = None; et_p = None
-    if kind == _ffi.CTRL_CONSTANT:
-        vec = _ffi.as_f64(np.broadcast_to(np.asarray(vec, dtype=np.float64).reshape(-1, 3), (S, 3))); vec_p = _ffi.dptr(vec)
-    elif kind == _ffi.CTRL_TANGENTIAL:
-        vec = _ffi.as_f64(np.broadcast_to(np.asarray(vec, dtype=np.float64).reshape(-1), (S,))); vec_p = _ffi.dptr(vec)
-    elif kind == _ffi.CTRL_SEQUENCE:
-        vec = np.asarray(vec, dtype=np.float64)
-        vec = _ffi.as_f64(np.broadcast_to(vec if vec.ndim == 3 else vec[None], (S, 3, Ku))); vec_p = _ffi.dptr(vec)
-        end_tau = _ffi.as_f64(np.broadcast_to(np.asarray(end_tau, dtype=np.float64), (S,))); et_p = _ffi.dptr(end_tau)
-    if Ks is not None: Ks = np.ascontiguousarray(np.broadcast_to(np.asarray(Ks), (S,)), dtype=np.int32)
-    if Kus is not None: Kus = np.ascontiguousarray(np.broadcast_to(np.asarray(Kus), (S,)), dtype=np.int32)
-    opts = _ffi.make_solve_opts(options, **solver)
-    popts = _ffi.make_popts(options, S)          # (per-satellite options: every satellite solved under its own row)
+    kind, vec, Ku, end_tau = _ffi.thrust_law(law, S)
+    Ks = _ffi.counts(Ks, S); Kus = _ffi.counts(Kus, S)
+    opts = _ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt))
     X, U, NU, kkt, status, iters = _result_arrays(S, K, device, False)
     tfo = np.empty(S); pst = np.zeros(S, dtype=np.int32)
     xb = np.empty((S, 7, K)) if return_reference else None
     ub = np.empty((S, 3, K)) if return_reference else None
     prop_flags, disc_flags = scp_flags(include_drag, include_J2, rollout_model)
-    lib = _ffi.load(); ctx = _ffi.context(device, slot)
-    import ctypes as C
-    head = (ctx, S, K, None if Ks is None else _ffi.iptr(Ks), _ffi.dptr(y0), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags,
-            kind, vec_p, int(Ku), None if Kus is None else _ffi.iptr(Kus), et_p, float(prop_max_step), disc_flags, float(max_step),
-            C.byref(opts))
-    tail = (None if xb is None else _ffi.dptr(xb), None if ub is None else _ffi.dptr(ub), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU),
-            _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst))
-    if popts is None:
-        rc = lib.mpcx_scp_iteration_batch_ragged(*head, *tail)
-    else:
-        rc = lib.mpcx_scp_iteration_batch_ragged_sat(*head, _ffi.dptr(popts), *tail)
-    _ffi.check(rc, ctx, "mpcx_scp_iteration_batch_ragged")
+    _ffi.call("mpcx_scp_iteration_batch_ragged", _ffi.context(device, slot), S, K, _ffi.iptr_opt(Ks), _ffi.dptr(y0), _ffi.dptr(tf),
+              _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags, kind, _ffi.dptr_opt(vec), Ku, _ffi.iptr_opt(Kus), _ffi.dptr_opt(end_tau),
+              float(prop_max_step), disc_flags, float(max_step), C.byref(opts), _ffi.dptr_opt(xb), _ffi.dptr_opt(ub), _ffi.dptr(X),
+              _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst),
+              popts=_ffi.make_popts(options, S))          # (per-satellite options: every satellite solved under its own row)
     res = SolveResult(X, U, NU, tfo, status, iters, kkt)
     res.prop_status = pst; res.xbar = xb; res.ubar = ub
     return res
@@ -269,8 +202,8 @@ class UpdateResult(SolveResult):
 
 
 def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None, ref_thrust=0.5, include_J2=False, max_step=1e-2,
-                     prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, out=None, include_drag=False,
-                     rollout_model=False, popts=None, **solver):
+                     prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, include_drag=False,
+                     rollout_model=False, **solver):
     """OptimalController.update (control.py:170-235) for S satellites in ONE library call (mpcx_mpc_update_batch): the tangential
     reference rollout over `horizon` sampled at K = int(base_res * horizon) nodes, n_scp x (extract_uk, discretise, solve) with
     the nonlinear re-rollout under the optimised sequence -- sampled at int(base_res * tf_u) nodes per satellite -- between
@@ -281,72 +214,55 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     Planning model (update_flags): include_drag / include_J2 in every linearisation; rollout_model=True flies the planning
     rollouts with them too (MPCX_FLAG_PLAN_ROLLOUTS).  The defaults are the reference's planner, which has neither.
     devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (see mpc_step_batch).
-    options may hold per-satellite values (_ffi.make_popts): every SCP iteration solves satellite s under row s of the table.
-    popts: (internal) a block's rows of that table."""
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        y0 = _ffi.as_f64(y0); S = y0.shape[0]
-        bc = lambda a: _ffi.as_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (S,)))
-        hz = bc(horizon); K = int(base_res * float(hz[0]))
-        res = _update_result(S, K, n_scp, int(devices[0]), fly)          # ONE result set; every block fills its satellites' part
-        fn = lambda y, h, c, r, po, device, slot, out: mpc_update_batch(y, h, c, r, base_res, n_scp, _ffi.scalar_options(options), ref_thrust,
-                                                                        include_J2, max_step, prop_max_step, device, slot, linear_vt, fly,
-                                                                        None, out, include_drag, rollout_model, po, **solver)
-        sharded_call(fn, devices, [y0, hz, _ffi.as_f64(consts), bc(r_des), _ffi.make_popts(options, S)],
-                     dict(X=res.X, U=res.U, NU=res.NU, kkt=res.kkt, tf=res.tf, Ks=res.Ks, prop_status=res.prop_status,
-                          status=(res.status, 1), iters=(res.iters, 1), y_sim=res.y_sim, sim_status=res.sim_status))
-        return res
+    options may hold per-satellite values (_ffi.make_popts): every SCP iteration solves satellite s under row s of the table."""
+    many = _many(devices)
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
-    solver = _solver_flags(solver, linear_vt, None, False)
     y0 = _ffi.as_f64(y0); S = y0.shape[0]
-    horizon = _ffi.as_f64(np.broadcast_to(np.asarray(horizon, dtype=np.float64), (S,)))
+    horizon = _ffi.per_sat(horizon, S)
     K = int(base_res * float(horizon[0]))
     if not (horizon == horizon[0]).all():
         raise ValueError("mpc_update_batch: one horizon for the whole batch (the row length K = int(base_res * horizon))")
-    r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
-    consts = _ffi.as_f64(consts)
-    opts = _ffi.make_solve_opts(options, **solver)
-    popts = _block_popts(popts, options, S)
     sim = (0.0, 0.0, 0, 0, 1e-3)
     if fly is not None:
         tf_sim, interval, n_eval, drag, j2 = fly[:5]
-        sim = (float(tf_sim), float(interval), int(n_eval), (_ffi.FLAG_DRAG if drag else 0) | (_ffi.FLAG_J2 if j2 else 0),
-               float(fly[5]) if len(fly) > 5 else 1e-3)
-    if out is None:
-        res = _update_result(S, K, n_scp, device, fly)
-        X, U, NU, kkt, status, iters, tfo, Ks, pst, y_sim, sst = (res.X, res.U, res.NU, res.kkt, res.status, res.iters, res.tf, res.Ks,
-                                                                  res.prop_status, res.y_sim, res.sim_status)
-    else:                                                  # (a block of a multi-device call: its slice of the constellation's arrays)
-        from .sharding import OutArrays
-        oa = OutArrays(out)
-        X, U, NU, kkt = oa.get("X", (S, 7, K)), oa.get("U", (S, 3, K)), oa.get("NU", (S, 7, K)), oa.get("kkt", (S,))
-        status, iters = oa.get("status", (n_scp, S), np.int32), oa.get("iters", (n_scp, S), np.int32)
-        tfo, Ks, pst = oa.get("tf", (S,)), oa.get("Ks", (S,), np.int32), oa.get("prop_status", (S,), np.int32)
-        y_sim = oa.get("y_sim", (S, 7, sim[2])) if fly is not None else None
-        sst = oa.get("sim_status", (S,), np.int32) if fly is not None else None
-        res = UpdateResult(X, U, NU, tfo, status, iters, kkt)
-        res.Ks = Ks; res.prop_status = pst; res.y_sim = y_sim; res.sim_status = sst
-    lib = _ffi.load(); ctx = _ffi.context(device, slot)
-    import ctypes as C
-    head = (ctx, S, K, int(n_scp), float(base_res), _ffi.dptr(y0), _ffi.dptr(horizon), _ffi.dptr(consts), _ffi.dptr(r_des), float(ref_thrust),
-            float(prop_max_step), update_flags(include_drag, include_J2, rollout_model), float(max_step), C.byref(opts))
-    tail = (_ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(Ks), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt),
-            _ffi.iptr(pst), sim[0], sim[1], sim[2], sim[3], sim[4], None if y_sim is None else _ffi.dptr(y_sim),
-            None if sst is None else _ffi.iptr(sst))
-    if popts is None:
-        rc = lib.mpcx_mpc_update_batch(*head, *tail)
+        sim = (float(tf_sim), float(interval), int(n_eval), _ffi.model_flags(drag, j2), float(fly[5]) if len(fly) > 5 else 1e-3)
+    batched = [y0, horizon, _ffi.as_f64(consts), _ffi.per_sat(r_des, S), _ffi.make_popts(options, S)]
+    how = dict(K=K, n_scp=int(n_scp), base_res=float(base_res), ref_thrust=float(ref_thrust), prop_max_step=float(prop_max_step),
+               flags=update_flags(include_drag, include_J2, rollout_model), max_step=float(max_step),
+               opts=_ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt)), sim=sim)
+    res = _update_result(S, K, n_scp, fly)                 # ONE result set; with several devices every block fills its satellites' part
+    out = dict(X=res.X, U=res.U, NU=res.NU, kkt=res.kkt, tf=res.tf, Ks=res.Ks, prop_status=res.prop_status, status=res.status,
+               iters=res.iters, y_sim=res.y_sim, sim_status=res.sim_status)
+    if many:
+        from .sharding import sharded_call
+        out.update(status=(res.status, 1), iters=(res.iters, 1))          # (n_scp, S): the satellite axis is the second
+        sharded_call(_update_call, devices, batched, out, **how)
     else:
-        rc = lib.mpcx_mpc_update_batch_sat(*head, _ffi.dptr(popts), *tail)
-    _ffi.check(rc, ctx, "mpcx_mpc_update_batch")
-    if out is not None:
-        oa.finish()
+        _update_call(*batched, device=device, slot=slot, out=out, **how)
     return res
 
 
-def _update_result(S, K, n_scp, device, fly):
+def _update_call(y0, horizon, consts, r_des, popts, *, device, slot, out, K, n_scp, base_res, ref_thrust, prop_max_step, flags, max_step,
+                 opts, sim):
+    """One update call on context (device, slot): the normalised inputs of the context's satellites and `out`, their part of
+    the result set (_update_result's arrays by name).  A block's columns of the (n_scp, S) records are not contiguous: the
+    library fills a temporary that OutArrays copies over."""
+    from .sharding import OutArrays
+    S = y0.shape[0]
+    oa = OutArrays(out)
+    status, iters = oa.get("status", (n_scp, S), np.int32), oa.get("iters", (n_scp, S), np.int32)
+    _ffi.call("mpcx_mpc_update_batch", _ffi.context(device, slot), S, K, n_scp, base_res, _ffi.dptr(y0), _ffi.dptr(horizon),
+              _ffi.dptr(consts), _ffi.dptr(r_des), ref_thrust, prop_max_step, flags, max_step, C.byref(opts), _ffi.dptr(out["X"]),
+              _ffi.dptr(out["U"]), _ffi.dptr(out["NU"]), _ffi.dptr(out["tf"]), _ffi.iptr(out["Ks"]), _ffi.iptr(status), _ffi.iptr(iters),
+              _ffi.dptr(out["kkt"]), _ffi.iptr(out["prop_status"]), *sim, _ffi.dptr_opt(out.get("y_sim")),
+              _ffi.iptr_opt(out.get("sim_status")), popts=popts)
+    oa.finish()
+
+
+def _update_result(S, K, n_scp, fly):
     """the result set of an update of S satellites (large arrays from the recycling pool: _ffi.result_pool)"""
-    X, U, NU, kkt, _, _ = _result_arrays(S, K, device, False)
+    X, U, NU, kkt, _, _ = _result_arrays(S, K, 0, False)
     res = UpdateResult(X, U, NU, np.empty(S), np.zeros((n_scp, S), dtype=np.int32), np.zeros((n_scp, S), dtype=np.int32), kkt)
     res.Ks = np.zeros(S, dtype=np.int32); res.prop_status = np.zeros(S, dtype=np.int32)
     res.y_sim = _ffi.result_pool.take((S, 7, int(fly[2]))) if fly is not None else None
@@ -360,31 +276,22 @@ def solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options=Non
     per-satellite values (_ffi.make_popts); not with shared_tf."""
     if shared_tf:
         _ffi.refuse_per_satellite(options, "solve_batch(shared_tf=True)")
-    solver = _solver_flags(solver, linear_vt, fixed_tf, shared_tf)
-    xbar = _ffi.as_f64(xbar); ubar = _ffi.as_f64(ubar)
+    xbar = _ffi.as_f64(xbar)
     S, _, K = xbar.shape
-    arrs = [_ffi.as_f64(a) for a in (A, Bp, Bn, Sigma, xi)]
-    tf = _ffi.as_f64(np.broadcast_to(np.asarray(tf, dtype=np.float64), (S,)))
-    r_des = _ffi.as_f64(np.broadcast_to(np.asarray(r_des, dtype=np.float64), (S,)))
-    consts = _ffi.as_f64(consts)
-    opts = _ffi.make_solve_opts(options, **solver)
-    popts = _ffi.make_popts(options, S)
+    inputs = [_ffi.as_f64(a) for a in (A, Bp, Bn, Sigma, xi)] + [xbar, _ffi.as_f64(ubar), _ffi.per_sat(tf, S), _ffi.as_f64(consts),
+                                                                 _ffi.per_sat(r_des, S)]
+    opts = _ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt, fixed_tf, shared_tf))
     X = np.empty((S, 7, K)); U = np.empty((S, 3, K)); NU = np.empty((S, 7, K)); kkt = np.empty(S)
     tfo, held = _tf_io(S, fixed_tf)
     status = np.zeros(S, dtype=np.int32); iters = np.zeros(S, dtype=np.int32)
-    lib = _ffi.load(); ctx = _ffi.context(device)
-    import ctypes as C
-    head = (ctx, S, K, *[_ffi.dptr(a) for a in arrs], _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des),
-            C.byref(opts))
-    tail = (_ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt))
-    if popts is None:
-        rc = lib.mpcx_solve_batch(*head, *tail)
-    else:
-        rc = lib.mpcx_solve_batch_sat(*head, _ffi.dptr(popts), *tail)
-    _ffi.check(rc, ctx, "mpcx_solve_batch")
-    reg = _regularised(lib, ctx, S) if regularised else None
-    return SolveResult(X, U, NU, tfo, status, iters, kkt, regularised=reg) if held is None else \
-        SolveResult(X, U, NU, held, status, iters, kkt, tfo, reg)
+    ctx = _ffi.context(device)
+    _ffi.call("mpcx_solve_batch", ctx, S, K, *[_ffi.dptr(a) for a in inputs], C.byref(opts), _ffi.dptr(X), _ffi.dptr(U), _ffi.dptr(NU),
+              _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), popts=_ffi.make_popts(options, S))
+    reg = None
+    if regularised:
+        reg = np.zeros((S, 2), dtype=np.int32)
+        _ffi.call("mpcx_solve_regularised", ctx, S, _ffi.iptr(reg))
+    return _solve_result(X, U, NU, tfo, held, status, iters, kkt, reg)
 
 
 class SharedTfSearch(list):
@@ -465,7 +372,8 @@ def solve_shared_tf(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options
     opts = {**DEFAULT_OPTIONS, **(options or {})}
     S = np.asarray(xbar).shape[0]
     if monolithic:
-        r = solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options, device, linear_vt, shared_tf=True, **solver)
+        r = solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options=options, device=device, linear_vt=linear_vt,
+                        shared_tf=True, **solver)
         ev = SharedTfSearch()
         ev.converged = bool(np.isin(r.status, (0, 7)).all())
         ev.message = "monolithic device solve" + ("" if ev.converged else f": status {sorted(set(int(c) for c in r.status))}")
@@ -476,7 +384,7 @@ def solve_shared_tf(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options
     notes = []
 
     def inner(t):
-        return solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options, device, linear_vt,
+        return solve_batch(A, Bp, Bn, Sigma, xi, xbar, ubar, tf, consts, r_des, options=options, device=device, linear_vt=linear_vt,
                            fixed_tf=np.full(S, float(t)), **solver)
 
     def G(t):
@@ -617,7 +525,7 @@ class Optimizer:
             self.result, self.tf_search = solve_shared_tf(A, Bp, Bn, Sig, xi, xbar, ubar, self.tf, consts, options['r_des'],
                                                           options, device=getattr(self.d, "device", 0), **solver)
         else:
-            self.result = mpc_step_batch(xbar, ubar, self.tf, consts, options['r_des'], options,
+            self.result = mpc_step_batch(xbar, ubar, self.tf, consts, options['r_des'], options=options,
                                          include_J2=self.d.include_J2, include_drag=self.d.include_drag, max_step=self.d.ivp_max_step,
                                          device=getattr(self.d, "device", 0),
                                          uniform_steps=int(self.d.integrator_steps) if self.d.use_uniform_steps else 0,

@@ -20,7 +20,7 @@ class OdeResult:
 
 
 def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=False, max_step=1e-3, device=0, slot=0,
-                    Kus=None, thrust=False, devices=None, out=None, row_len=None):
+                    Kus=None, thrust=False, devices=None):
     """y0 (S,7) normalised, tf (S,), consts (S,8); law = (kind, vec, Ku, end_tau) with per-satellite or
     broadcastable parameters.  Returns y (S,7,n_eval), status (S,), nsteps (S,) -- and, with thrust=True, u (S,3,n_eval) as a
     fourth value: the law evaluated at the output points, Discretizer.extract_uk of the rollout's own controller
@@ -29,75 +29,36 @@ def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=
     max(n_eval) columns, zero past a satellite's count -- and Kus (S,) gives the columns in use of each satellite's
     thrust table (law SEQUENCE, table rows of length Ku).
     devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (sharding.sharded_call), every block
-    writing in place into its slice of one result set (out / row_len: internal -- a block's views of that set, and the set's
-    row length, which a ragged block uses instead of its own longest satellite's)."""
+    writing in place into its slice of one result set, whose row length -- the constellation's longest satellite -- is every
+    block's."""
     y0 = _ffi.as_f64(y0); S = y0.shape[0]
+    kind, vec, Ku, end_tau = _ffi.thrust_law(law, S)
+    n_evals = _ffi.counts(n_eval, S) if np.ndim(n_eval) > 0 else None
+    n_eval = int(n_eval) if n_evals is None else int(n_evals.max())
+    batched = [y0, _ffi.per_sat(tf, S), _ffi.as_f64(consts), vec, end_tau, n_evals, _ffi.counts(Kus, S)]
+    how = dict(n_eval=n_eval, flags=_ffi.model_flags(include_drag, include_J2), kind=kind, Ku=Ku, max_step=float(max_step))
+    out = dict(y=_ffi.result_pool.take((S, 7, n_eval)), status=np.zeros(S, dtype=np.int32), nsteps=np.zeros(S, dtype=np.int32),
+               u=_ffi.result_pool.take((S, 3, n_eval)) if thrust else None)
     if devices is not None and len(devices) > 1:
         from .sharding import sharded_call
-        kind, vec, Ku, end_tau = law
-        bc = lambda a, shape: None if a is None else _ffi.as_f64(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
-        if kind == _ffi.CTRL_CONSTANT: vec = bc(np.asarray(vec, dtype=np.float64).reshape(-1, 3), (S, 3))
-        elif kind == _ffi.CTRL_TANGENTIAL: vec = bc(np.asarray(vec, dtype=np.float64).reshape(-1), (S,))
-        elif kind == _ffi.CTRL_SEQUENCE:
-            vec = np.asarray(vec, dtype=np.float64); vec = bc(vec if vec.ndim == 3 else vec[None], (S, 3, Ku)); end_tau = bc(end_tau, (S,))
-        else: vec = None
-        if kind != _ffi.CTRL_SEQUENCE: end_tau = None
-        ne = np.ascontiguousarray(np.broadcast_to(np.asarray(n_eval), (S,)), dtype=np.int32) if np.ndim(n_eval) > 0 else None
-        ku = None if Kus is None else np.ascontiguousarray(np.broadcast_to(np.asarray(Kus), (S,)), dtype=np.int32)
-        nmax = int(ne.max()) if ne is not None else int(n_eval)
-        y = _ffi.result_pool.take((S, 7, nmax)); status = np.zeros(S, dtype=np.int32); nsteps = np.zeros(S, dtype=np.int32)
-        u = _ffi.result_pool.take((S, 3, nmax)) if thrust else None
-
-        def fn(y0b, t, c, v, e, n, k, device, slot, out):
-            propagate_batch(y0b, t, c, (kind, v, Ku, e), n_eval if n is None else n, include_drag, include_J2, max_step, device, slot, k, thrust,
-                            None, out, nmax)
-        sharded_call(fn, devices, [y0, bc(tf, (S,)), _ffi.as_f64(consts), vec, end_tau, ne, ku], dict(y=y, status=status, nsteps=nsteps, u=u))
-        return (y, status, nsteps, u) if thrust else (y, status, nsteps)
-    if devices is not None and len(devices) == 1:
-        device = int(devices[0])
-    n_evals = None
-    if np.ndim(n_eval) > 0:
-        n_evals = np.ascontiguousarray(np.broadcast_to(np.asarray(n_eval), (S,)), dtype=np.int32)
-        n_eval = int(n_evals.max()) if row_len is None else int(row_len)
-    if Kus is not None:
-        Kus = np.ascontiguousarray(np.broadcast_to(np.asarray(Kus), (S,)), dtype=np.int32)
-    tf = _ffi.as_f64(np.broadcast_to(np.asarray(tf, dtype=np.float64), (S,)))
-    consts = _ffi.as_f64(consts)
-    kind, vec, Ku, end_tau = law
-    vec_p = None; et_p = None
-    if kind == _ffi.CTRL_CONSTANT:
-        vec = _ffi.as_f64(np.broadcast_to(np.asarray(vec, dtype=np.float64).reshape(-1, 3), (S, 3))); vec_p = _ffi.dptr(vec)
-    elif kind == _ffi.CTRL_TANGENTIAL:
-        vec = _ffi.as_f64(np.broadcast_to(np.asarray(vec, dtype=np.float64).reshape(-1), (S,))); vec_p = _ffi.dptr(vec)
-    elif kind == _ffi.CTRL_SEQUENCE:
-        vec = np.asarray(vec, dtype=np.float64)
-        vec = _ffi.as_f64(np.broadcast_to(vec if vec.ndim == 3 else vec[None], (S, 3, Ku))); vec_p = _ffi.dptr(vec)
-        end_tau = _ffi.as_f64(np.broadcast_to(np.asarray(end_tau, dtype=np.float64), (S,))); et_p = _ffi.dptr(end_tau)
-    from .sharding import OutArrays
-    oa = OutArrays(out)
-    y = oa.get("y", (S, 7, n_eval)); status = oa.get("status", (S,), np.int32, lambda: np.zeros(S, dtype=np.int32))
-    nsteps = oa.get("nsteps", (S,), np.int32, lambda: np.zeros(S, dtype=np.int32))
-    flags = (_ffi.FLAG_DRAG if include_drag else 0) | (_ffi.FLAG_J2 if include_J2 else 0)
-    lib = _ffi.load(); ctx = _ffi.context(device, slot)
-    if thrust:
-        u = oa.get("u", (S, 3, n_eval))
-        rc = lib.mpcx_propagate_thrust_batch_ragged(ctx, S, int(n_eval), None if n_evals is None else _ffi.iptr(n_evals), _ffi.dptr(y0),
-                                                    _ffi.dptr(tf), _ffi.dptr(consts), flags, kind, vec_p, int(Ku),
-                                                    None if Kus is None else _ffi.iptr(Kus), et_p, float(max_step), _ffi.dptr(y),
-                                                    _ffi.dptr(u), _ffi.iptr(status), _ffi.iptr(nsteps))
-        _ffi.check(rc, ctx, "mpcx_propagate_thrust_batch_ragged")
-        return y, status, nsteps, u
-    if n_evals is None and Kus is None:
-        rc = lib.mpcx_propagate_batch(ctx, S, int(n_eval), _ffi.dptr(y0), _ffi.dptr(tf), _ffi.dptr(consts), flags, kind,
-                                      vec_p, int(Ku), et_p, float(max_step), _ffi.dptr(y), _ffi.iptr(status),
-                                      _ffi.iptr(nsteps))
+        sharded_call(_propagate_call, devices, batched, out, **how)
     else:
-        rc = lib.mpcx_propagate_batch_ragged(ctx, S, int(n_eval), None if n_evals is None else _ffi.iptr(n_evals), _ffi.dptr(y0),
-                                             _ffi.dptr(tf), _ffi.dptr(consts), flags, kind, vec_p, int(Ku),
-                                             None if Kus is None else _ffi.iptr(Kus), et_p, float(max_step), _ffi.dptr(y),
-                                             _ffi.iptr(status), _ffi.iptr(nsteps))
-    _ffi.check(rc, ctx, "mpcx_propagate_batch")
-    return y, status, nsteps
+        if devices is not None and len(devices) == 1:
+            device = int(devices[0])
+        _propagate_call(*batched, device=device, slot=slot, out=out, **how)
+    return (out["y"], out["status"], out["nsteps"], out["u"]) if thrust else (out["y"], out["status"], out["nsteps"])
+
+
+def _propagate_call(y0, tf, consts, vec, end_tau, n_evals, Kus, *, device, slot, out, n_eval, flags, kind, Ku, max_step):
+    """One rollout call on context (device, slot): the normalised inputs of the context's satellites and `out`, their part of
+    the result set -- y, status, nsteps, and u where the thrust at the output points is wanted."""
+    u = out.get("u")
+    ragged = u is not None or n_evals is not None or Kus is not None
+    name = "mpcx_propagate_thrust_batch_ragged" if u is not None else "mpcx_propagate_batch_ragged" if ragged else "mpcx_propagate_batch"
+    only_ragged = lambda p: [p] if ragged else []          # (the per-satellite counts: arguments of the ragged entry points only)
+    _ffi.call(name, _ffi.context(device, slot), y0.shape[0], n_eval, *only_ragged(_ffi.iptr_opt(n_evals)), _ffi.dptr(y0), _ffi.dptr(tf),
+              _ffi.dptr(consts), flags, kind, _ffi.dptr_opt(vec), Ku, *only_ragged(_ffi.iptr_opt(Kus)), _ffi.dptr_opt(end_tau), max_step,
+              _ffi.dptr(out["y"]), *([] if u is None else [_ffi.dptr(u)]), _ffi.iptr(out["status"]), _ffi.iptr(out["nsteps"]))
 
 
 class Simulator:
@@ -121,8 +82,8 @@ class Simulator:
         const = self.scale.get_normalized_constants().as_vector()
         y0 = np.stack([self.scale.normalize_state(s.get_state_vector()) for s in sats])
         law = self._device_law()
-        y, status, nsteps = propagate_batch(y0, tf, np.tile(const, (len(sats), 1)), law, self.eval_points,
-                                            self.include_drag, self.include_J2, 0.001, self.device, devices=self.devices)
+        y, status, nsteps = propagate_batch(y0, tf, np.tile(const, (len(sats), 1)), law, self.eval_points, include_drag=self.include_drag,
+                                            include_J2=self.include_J2, max_step=0.001, device=self.device, devices=self.devices)
         if (status == 1).any():
             raise Exception("ERROR: INVALID SATELLITE MASS")           # simulator.py:135-136
         if (status != 0).any():
