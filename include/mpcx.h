@@ -61,7 +61,8 @@ extern "C" {
 /* dynamics flags (reference include_drag / include_J2 keyword arguments).  On the discretize / mpc_step entry points
  * MPCX_FLAG_DRAG is the reference's Discretizer(include_drag=True) (linearize_discretize.py:162-173) with the simulator's
  * atmosphere -- the fixed density 9.983e-13 kg/m^3 over the constants' RHO, drho = 0, C_D = 2.5: the drag partials in A
- * (velocity block, mass column), and drag in Sigma and xi. */
+ * (velocity block, mass column), and drag in Sigma and xi.  MPCX_FLAG_ATMO (below) replaces that atmosphere by an
+ * altitude-dependent one. */
 #define MPCX_FLAG_DRAG 1
 #define MPCX_FLAG_J2 2
 /* discretize entry points only: Discretizer.use_uniform_steps (linearize_discretize.py:27-30, 50-53) with
@@ -78,6 +79,14 @@ extern "C" {
  * planner predicts what that model flies.  Without it they use neither (flags 0), as the reference's run_nonlinear does
  * (control.py:237-240).  The discretize entry points ignore the bit. */
 #define MPCX_FLAG_PLAN_ROLLOUTS 16
+/* With MPCX_FLAG_DRAG, wherever that flag is honoured -- the propagate, discretize / stage, fused-step, scp_iteration (both flag
+ * words) and mpc_update (disc_flags, passed on to the planning rollouts by MPCX_FLAG_PLAN_ROLLOUTS, and sim_flags) entry points:
+ * the drag uses the context's altitude-dependent atmosphere (mpcx_set_atmosphere below) instead of the fixed density.  The
+ * density at a stage's own altitude enters every right-hand side, Sigma and xi, and the linearisation gains the position block
+ * Dr a_D = -C_D S / (2 m) |v| v (drho r_hat^T) (linearize_discretize.py:164-166: the reference's rho_func / drho_func).  The bit
+ * without MPCX_FLAG_DRAG, or on a context with no atmosphere set, is MPCX_E_BADARG before anything is enqueued.  Without the
+ * bit every call takes the kernels it takes on a context that never had an atmosphere. */
+#define MPCX_FLAG_ATMO 32
 
 /* normalised constants per satellite: reference constants.py:11-20 field order */
 enum { MPCX_C_MU = 0, MPCX_C_R_E, MPCX_C_J2, MPCX_C_G0, MPCX_C_ISP, MPCX_C_S, MPCX_C_R0,
@@ -102,6 +111,19 @@ int mpcx_synchronize(mpcx_ctx *ctx, void *stream);
  * for the device's default stream, MPCX_STREAM_PRIVATE for a new private stream.  The old stream is drained first. */
 #define MPCX_STREAM_PRIVATE ((void *)(intptr_t)-1)
 int mpcx_set_stream(mpcx_ctx *ctx, void *stream);
+/* The atmosphere of the world this context simulates, for the calls that carry MPCX_FLAG_ATMO: one closed form with four
+ * coefficients atmo[MPCX_NATMO] = {c0, c1, c2, h_floor} in physical units,
+ *   alt = |r R0| - R_EARTH  (metres; the altitude of Simulator.get_atmo_density, simulator.py:109, R_EARTH = 6.371e6)
+ *   h = max(alt, h_floor),   rho(h) = exp(c0 + c1 ln h + c2 h)  kg/m^3,   d rho / d h = rho (c1 / h + c2) above the floor, 0 on it.
+ * The Harris-Priester power fit a h^-b the reference keeps commented out (simulator.py:110: a = 8e26, b = 6.828) is
+ * c0 = ln a, c1 = -b, c2 = 0; the exponential atmosphere rho_ref exp(-(h - h_ref) / H) is c0 = ln rho_ref + h_ref / H, c1 = 0,
+ * c2 = -1 / H.  h_floor > 0 keeps the logarithm defined wherever a trial stage of an integrator lands.  The drag acceleration
+ * uses rho / consts[s][MPCX_C_RHO] and the linearisation drho = (d rho / d h) consts[s][MPCX_C_R0] / consts[s][MPCX_C_RHO]:
+ * the model is launch-wide, each satellite's units enter through its constants.  The coefficients are copied into the context
+ * here and into the kernel arguments at every launch (no kernel reads the context; a later change does not reach work already
+ * enqueued).  atmo = NULL clears them.  Non-finite coefficients or h_floor <= 0: MPCX_E_BADARG, the context keeps what it had. */
+enum { MPCX_ATMO_C0 = 0, MPCX_ATMO_C1, MPCX_ATMO_C2, MPCX_ATMO_HFLOOR, MPCX_NATMO };
+int mpcx_set_atmosphere(mpcx_ctx *ctx, const double *atmo);
 /* Where a host-pointer call's time went, as data (the reference has no counterpart: its solve is a subprocess whose time
  * optimizer.py:603 does not look at).  mpcx_trace_enable(ctx, 1): every following host-pointer call on the context records, at
  * the price of four events and one polled marker per call,
@@ -338,7 +360,7 @@ int mpcx_mpc_step_batch_dev(mpcx_ctx *ctx, int S, int K, const double *xbar, con
 /*
  * Replaces Simulator.get_trajectory_ODE (simulator.py:164-189) for S satellites: scipy
  * solve_ivp(RK45, rtol 1e-3, atol 1e-6, max_step, t_eval=linspace(0,1,n_eval)) of
- * Simulator.satellite_dynamics (simulator.py:116-161, flags = MPCX_FLAG_DRAG|MPCX_FLAG_J2) under a
+ * Simulator.satellite_dynamics (simulator.py:116-161, flags = MPCX_FLAG_DRAG|MPCX_FLAG_J2[|MPCX_FLAG_ATMO]) under a
  * thrust law u(y, tau).  y0 [S][7] normalised states, y_out [S][7][n_eval] (= sol.y per satellite).
  */
 int mpcx_propagate_batch(mpcx_ctx *ctx, int S, int n_eval, const double *y0, const double *tf,
@@ -455,8 +477,8 @@ int mpcx_scp_iteration_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const int32
  * behind them), tf_out [S] = tf_u, Ks_out [S]; status, iters [n_scp][S]: every iteration's solver outcome; kkt [S]: the last
  * iteration's; prop_status [S]: the first failure among the rollouts (MPCX_ST_*).
  * disc_flags: the discretisation's flags (MPCX_FLAG_DRAG, MPCX_FLAG_J2, ...); with MPCX_FLAG_PLAN_ROLLOUTS the rollouts of the
- * plan use its MPCX_FLAG_DRAG | MPCX_FLAG_J2 as well.
- * Segment flight (y_sim != NULL): from y0 over sim_tf under the truth model sim_flags (MPCX_FLAG_DRAG | MPCX_FLAG_J2) with
+ * plan use its MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO as well.
+ * Segment flight (y_sim != NULL): from y0 over sim_tf under the truth model sim_flags (MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO) with
  * SequenceController(u_opt, tf_u, tf_sim = sim_interval) (end_tau = tf_u / sim_interval, control.py:102,217),
  * y_sim [S][7][sim_n_eval] = sol.y at linspace(0, 1, sim_n_eval), sim_status [S].
  * Environment (measurement switch, read per call): MPCX_UPDATE_SPLIT=1 runs a batch of 2048 or more satellites as two chains --

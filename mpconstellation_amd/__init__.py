@@ -10,7 +10,8 @@ from .control import (Controller, ConstantThrustController, ConstantTangentialTh
                       SequenceController, OptimalController)
 from .simulator import Simulator, propagate_batch
 from .constellation_mpc import ConstellationMPC
+from .atmosphere import Atmosphere
 
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
-           "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC"]
+           "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC", "Atmosphere"]

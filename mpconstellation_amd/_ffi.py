@@ -17,7 +17,8 @@ STATUS_TEXT = {
     8: "constraint set empty (start node outside its radius bounds, terminal window outside r_max, empty window or tf range)",
     10: "time-parallel solve: a workgroup of the satellite did not answer within the wait limit (device shared with another long kernel?)",
 }
-FLAG_DRAG, FLAG_J2, FLAG_UNIFORM_STEPS, FLAG_RK23, FLAG_PLAN_ROLLOUTS = 1, 2, 4, 8, 16
+FLAG_DRAG, FLAG_J2, FLAG_UNIFORM_STEPS, FLAG_RK23, FLAG_PLAN_ROLLOUTS, FLAG_ATMO = 1, 2, 4, 8, 16, 32
+NATMO = 4
 CTRL_ZERO, CTRL_CONSTANT, CTRL_TANGENTIAL, CTRL_SEQUENCE = 0, 1, 2, 3
 NCONST = 8
 STAGE_DOUBLES = 105
@@ -52,6 +53,7 @@ _SIGS = {
     "mpcx_last_error": (C.c_char_p, [_vp]),
     "mpcx_synchronize": (C.c_int, [_vp, _vp]),
     "mpcx_set_stream": (C.c_int, [_vp, _vp]),
+    "mpcx_set_atmosphere": (C.c_int, [_vp, _dp]),
     "mpcx_trace_enable": (C.c_int, [_vp, C.c_int]),
     "mpcx_last_call_trace": (C.c_int, [_vp, _dp, C.c_int]),
     "mpcx_host_alloc": (_vp, [_vp, C.c_size_t]),
@@ -166,6 +168,27 @@ def set_stream(stream, device=0, slot=0):
     For processes that also drive the device through another stream: include/mpcx.h, mpcx_set_stream."""
     lib = load(); ctx = context(device, slot)
     check(lib.mpcx_set_stream(ctx, stream if isinstance(stream, C.c_void_p) else C.c_void_p(stream or 0)), ctx, "mpcx_set_stream")
+
+
+def set_atmosphere(ctx, atmosphere):
+    """mpcx_set_atmosphere: give context `ctx` the atmosphere that its calls with FLAG_ATMO use -- an Atmosphere
+    (mpconstellation_amd.atmosphere), anything with coefficients(), or the four numbers (c0, c1, c2, h_floor); None clears it."""
+    if atmosphere is None:
+        check(load().mpcx_set_atmosphere(ctx, None), ctx, "mpcx_set_atmosphere")
+        return
+    coef = as_f64(atmosphere.coefficients() if hasattr(atmosphere, "coefficients") else atmosphere)
+    if coef.shape != (NATMO,):
+        raise ValueError(f"atmosphere: expected {NATMO} coefficients (c0, c1, c2, h_floor), got shape {coef.shape}")
+    check(load().mpcx_set_atmosphere(ctx, dptr(coef)), ctx, "mpcx_set_atmosphere")
+
+
+def atmosphere_context(device=0, slot=0, atmosphere=None):
+    """context(device, slot), given `atmosphere` first when there is one: what a wrapper whose flags carry FLAG_ATMO calls on.
+    A call without an atmosphere leaves the context's alone (its flags do not carry the bit, so it is not read)."""
+    ctx = context(device, slot)
+    if atmosphere is not None:
+        set_atmosphere(ctx, atmosphere)
+    return ctx
 
 
 TRACE_FIELDS = ("wall_ms", "first_marker_ms", "host_stage_ms", "host_wait_ms", "host_copyout_ms", "dev_span_ms", "dev_kernels_ms", "valid")
@@ -313,14 +336,15 @@ def thrust_law(law, S):
     return kind, vec, int(Ku), per_sat(end_tau, S) if kind == CTRL_SEQUENCE else None
 
 
-def model_flags(include_drag, include_J2):
-    return (FLAG_DRAG if include_drag else 0) | (FLAG_J2 if include_J2 else 0)
+def model_flags(include_drag, include_J2, atmosphere=None):
+    """the dynamics flags; atmosphere (not None): FLAG_ATMO beside the drag -- without drag there is nothing for it to act on"""
+    return (FLAG_DRAG if include_drag else 0) | (FLAG_J2 if include_J2 else 0) | (FLAG_ATMO if include_drag and atmosphere is not None else 0)
 
 
-def discretize_flags(include_drag, include_J2, uniform_steps=0, rk23=False):
+def discretize_flags(include_drag, include_J2, uniform_steps=0, rk23=False, atmosphere=None):
     """flags of the discretize / fused-step entry points (include/mpcx.h): the model, Discretizer.use_uniform_steps with
     integrator_steps = uniform_steps (0: adaptive steps), ivp_solver = 'RK23'"""
-    flags = model_flags(include_drag, include_J2)
+    flags = model_flags(include_drag, include_J2, atmosphere)
     if uniform_steps:
         flags |= FLAG_UNIFORM_STEPS | (int(uniform_steps) << 8)
     if rk23:

@@ -47,7 +47,7 @@ def normalised_limits(scales, r_min=None, r_max=None, u_max=None, min_mass=None)
 class ConstellationMPC:
     def __init__(self, sats, base_res=100, tf_horizon=1, tf_interval=1, r_des=1.5, scp_iterations=2, sim_base_res=100,
                  include_drag=True, include_J2=True, device=0, strict=False, scales=None, verbose=False, devices=None,
-                 time_parallel=False, plan_drag=False, plan_J2=False, options=None):
+                 time_parallel=False, plan_drag=False, plan_J2=False, options=None, atmosphere=None):
         self.sats = list(sats)
         # problem options on top of OPTIONS(horizon): the reference's keys, scalars or one value per satellite ((S,), (S, 2) for
         # u_lim / r_lim: _ffi.make_popts; normalised_limits above turns physical limits into them).  The user's values win.
@@ -66,7 +66,11 @@ class ConstellationMPC:
         # MPCX_FLAG_PLAN_ROLLOUTS), so that the plan predicts what a truth model with them flies.  Default: the reference's
         # planner, which has neither (control.py:187, 237-240)
         self.plan_drag, self.plan_J2 = bool(plan_drag), bool(plan_J2)
-        self._plan_model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, rollout_model=self.plan_drag or self.plan_J2)
+        # atmosphere (an Atmosphere): the altitude-dependent density (include/mpcx.h, MPCX_FLAG_ATMO) -- for the flown segments when
+        # include_drag, for the plan when plan_drag; None: the reference's fixed density on both sides
+        self.atmosphere = atmosphere
+        self._plan_model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, rollout_model=self.plan_drag or self.plan_J2,
+                                atmosphere=atmosphere)
         self.device = device
         # devices=[0, 1, ..., 7]: the constellation is dealt out in contiguous blocks to these devices, one host thread and one
         # context per device, no exchange between them (sharding.sharded_call) -- the reference loops over
@@ -223,7 +227,8 @@ class ConstellationMPC:
             U = self._plan[1]
             y, st, _ = self._timed("truth_propagation", propagate_batch, y0, tf, self.consts,
                                    (_ffi.CTRL_SEQUENCE, U, U.shape[2], self.plan_tf / self.interval), n_eval,
-                                   self.include_drag, self.include_J2, 0.001, self.device, Kus=self.plan_K, devices=self.devices)
+                                   self.include_drag, self.include_J2, 0.001, self.device, Kus=self.plan_K, devices=self.devices,
+                                   atmosphere=self.atmosphere)
         else:
             y, st = flown
         self._check(st)

@@ -113,7 +113,8 @@ class OptimalController(Controller):
     opt_trajectory, sequence_controller."""
 
     def __init__(self, sats=[], objective=None, base_res=100, tf_horizon=1, tf_interval=1, plot_inter=True,
-                 opt_verbose=True, r_des=1.5, strict=False, device=0, time_parallel=None, plan_drag=False, plan_J2=False):
+                 opt_verbose=True, r_des=1.5, strict=False, device=0, time_parallel=None, plan_drag=False, plan_J2=False,
+                 atmosphere=None):
         super().__init__(sats)
         from .satellite_scale import SatelliteScale
         self.u = np.zeros((3, 1))
@@ -143,13 +144,14 @@ class OptimalController(Controller):
         # The planning model (ConstellationMPC's plan_drag / plan_J2): drag / J2 in the linearisations and the planning rollouts.
         # Default: the reference's planner, which has neither (:187, run_nonlinear below).
         self.plan_drag, self.plan_J2 = plan_drag, plan_J2
+        self.atmosphere = atmosphere      # an Atmosphere: the plan's drag (plan_drag) with the altitude-dependent density
 
     def update(self):
         from .constellation_mpc import ConstellationMPC
         mpc = ConstellationMPC([self.sat], base_res=self.base_res, tf_horizon=self.horizon, tf_interval=self.interval,
                                r_des=self.r_des, scp_iterations=self.SCPn_iterations, device=self.device, strict=self.strict,
                                scales=[self.scale], verbose=self.opt_verbose, time_parallel=self.time_parallel,
-                               plan_drag=self.plan_drag, plan_J2=self.plan_J2)
+                               plan_drag=self.plan_drag, plan_J2=self.plan_J2, atmosphere=self.atmosphere)
         mpc.update()
         self.last_status = [int(c) for c in mpc.last_status[:, 0]]
         self.opt_trajectory = mpc.plan_x[0]

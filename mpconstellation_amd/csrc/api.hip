@@ -1,4 +1,5 @@
 // api.hip -- context management of libmpcx.so (see include/mpcx.h).
+#include <cmath>
 #include "mpcx_host.hpp"
 
 static char g_create_err[512] = "";
@@ -73,6 +74,18 @@ extern "C" int mpcx_set_stream(mpcx_ctx *ctx, void *stream)
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     ctx->stream = fresh;
     ctx->own_stream = (stream == MPCX_STREAM_PRIVATE);
+    return MPCX_OK;
+}
+
+extern "C" int mpcx_set_atmosphere(mpcx_ctx *ctx, const double *atmo)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    if (!atmo) { ctx->atmo_set = false; return MPCX_OK; }
+    for (int i = 0; i < MPCX_NATMO; ++i)
+        if (!std::isfinite(atmo[i])) return ctx_fail(ctx, MPCX_E_BADARG, "set_atmosphere: coefficients must be finite");
+    if (!(atmo[MPCX_ATMO_HFLOOR] > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "set_atmosphere: h_floor must be > 0 (it keeps ln h defined)");
+    for (int i = 0; i < MPCX_NATMO; ++i) ctx->atmo[i] = atmo[i];
+    ctx->atmo_set = true;
     return MPCX_OK;
 }
 

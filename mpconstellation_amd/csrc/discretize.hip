@@ -32,6 +32,7 @@ struct DiscArgs {
     double *stage;                       // LAYOUT_STAGE
     double *A, *Bp, *Bn, *Sigma, *xi;    // LAYOUT_REF
     int32_t *status;
+    double atmo[MPCX_NATMO];             // MPCX_FLAG_ATMO: the context's atmosphere, copied at launch (last: the other members keep their places)
 };
 
 __device__ __forceinline__ double group_sum(double v)
@@ -45,6 +46,7 @@ struct RhsCtx {
     double tf, inv_ve;   // inv_ve = 1 / (g0 Isp)
     SatConst cst;
     FohCache foh;        // the thrust table's interval in use (see foh3_cached)
+    double atm[MPCX_NATMO];      // ATMO forms: the atmosphere's coefficients (launch constants)
 };
 
 // 1/d and 1/sqrt(d) for d > 0 well inside the normal range: hardware seed + two Newton steps (half an ulp, measured:
@@ -70,11 +72,13 @@ __device__ __forceinline__ double rsq_nr(double d)
 // here everything is arranged around one reciprocal each of |r|, m and |u| (round 3).  Results move by rounding only (a few
 // ulp per evaluation, 1e-13 on A_k, B_k against the reference's arrays; the accepted RK45 nodes are the same).
 struct Lin {
-    double Gt[3][3], gmt[3], acc[3], mdot, im, iun, un;
+    double Gt[3][3], gmt[3], acc[3], mdot, im, iun, un, irn;
 };
 
+// ATMO: the drag acceleration with dens_atmo = rho(h) / c.rho (atmo_density) in place of the fixed density.
+template <bool ATMO>
 __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)[3], double m, const double (&u)[3],
-                                         const SatConst &c, int flags, double tf, double inv_ve, Lin &L)
+                                         const SatConst &c, int flags, double tf, double inv_ve, double dens_atmo, Lin &L)
 {
     const double rx = r[0], ry = r[1], rz = r[2];
     const double r2 = rx * rx + ry * ry + rz * rz;
@@ -111,7 +115,9 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
     for (int i = 0; i < 3; ++i) { L.gmt[i] = gs * u[i]; L.acc[i] = c1 * r[i] + u[i] * im + j2a[i]; }
     if (flags & MPCX_FLAG_DRAG) {                            // simulator.py:150-153
         const double vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        const double coef = -0.5 * kCd * c.s * im * (kRho500 / c.rho) * vn;
+        double dens;
+        if constexpr (ATMO) dens = dens_atmo; else dens = kRho500 / c.rho;
+        const double coef = -0.5 * kCd * c.s * im * dens * vn;
 #pragma unroll
         for (int i = 0; i < 3; ++i) L.acc[i] += coef * v[i];
     }
@@ -120,36 +126,50 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
     L.un = uu * L.iun;
     L.mdot = -L.un * inv_ve;
     L.im = im;
+    L.irn = irn;
 }
 
 // The drag partials of the linearisation (DRAG forms of the kernel): A_func's include_drag branch (linearize_discretize.py:162-169)
 // with the simulator's atmosphere -- the density ratio kRho500 / rho is fixed, drho = 0, so Dr a_D = 0.  With
 // kd = -C_D S (rho / rho_500) / (2 m):  Dm a_D = -kd |v| v / m goes into L.gmt (the mass column), and the velocity block
 // Dv a_D = kd (|v| I + v v^T / |v|) is applied to a column c in its rank-one form by drag_dv, never formed as a 3x3.
+// ATMO forms (MPCX_FLAG_ATMO): rho = rho(h) and drho = d(rho / rho_norm) / d|r| from atmo_density, and the position block
+// Dr a_D = -C_D S / (2 m) |v| v (drho r_hat^T) (:166) joins the velocity block in the same rank-one form: both are a multiple of v.
 struct DragLin {
     double kvt, kwt;     // tf kd |v|, tf kd / |v|
+    double krt;          // ATMO: -tf C_D S / (2 m) |v| drho / |r|
 };
-__device__ __forceinline__ DragLin drag_lin(const double (&v)[3], const SatConst &c, double tf, Lin &L)
+template <bool ATMO>
+__device__ __forceinline__ DragLin drag_lin(const double (&v)[3], const SatConst &c, double tf, double dens_atmo, double drho, Lin &L)
 {
     const double vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
     const double ivn = rsq_nr(vv), vn = vv * ivn;
-    const double kdt = tf * (-0.5 * kCd * c.s * L.im * (kRho500 / c.rho));
+    double kdt, krt = 0.0;
+    if constexpr (ATMO) {
+        const double k0 = tf * (-0.5 * kCd * c.s * L.im);
+        kdt = k0 * dens_atmo;
+        krt = ((k0 * vn) * drho) * L.irn;
+    } else kdt = tf * (-0.5 * kCd * c.s * L.im * (kRho500 / c.rho));
     const double gm = -(kdt * vn) * L.im;
 #pragma unroll
     for (int i = 0; i < 3; ++i) L.gmt[i] += gm * v[i];
-    return {kdt * vn, kdt * ivn};
+    return {kdt * vn, kdt * ivn, krt};
 }
-// tf Dv a_D c = tf kd (|v| c + v (v . c) / |v|)
-__device__ __forceinline__ void drag_dv(const DragLin &d, const double (&v)[3], double c0, double c1, double c2, double (&out)[3])
+// tf Dv a_D c = tf kd (|v| c + v (v . c) / |v|) for a column's velocity part c; ATMO: plus tf Dr a_D c_r = krt (r . c_r) v for its
+// position part
+template <bool ATMO>
+__device__ __forceinline__ void drag_dv(const DragLin &d, const double (&v)[3], const double (&r)[3], double cr0, double cr1, double cr2,
+                                        double c0, double c1, double c2, double (&out)[3])
 {
-    const double w = d.kwt * (v[0] * c0 + v[1] * c1 + v[2] * c2);
+    double w = d.kwt * (v[0] * c0 + v[1] * c1 + v[2] * c2);
+    if constexpr (ATMO) w += d.krt * (r[0] * cr0 + r[1] * cr1 + r[2] * cr2);
     out[0] = d.kvt * c0 + w * v[0];
     out[1] = d.kvt * c1 + w * v[1];
     out[2] = d.kvt * c2 + w * v[2];
 }
 
 // One evaluation of dPhi (linearize_discretize.py:262-290) for this lane's column.
-template <bool DRAG>
+template <bool DRAG, bool ATMO>
 __device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], double ts,
                                          double (&out)[7], int &err)
 {
@@ -161,10 +181,12 @@ __device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], doubl
     const double v[3] = {DRAG ? bcast8<7>(ys[3]) : ys[3], DRAG ? bcast8<7>(ys[4]) : ys[4], DRAG ? bcast8<7>(ys[5]) : ys[5]};
     const double m = bcast8<7>(ys[6]);
     const double tf = p.tf;
+    double dens = 0.0, drho = 0.0;
+    if constexpr (ATMO) dens = atmo_density(r, p.cst, p.atm, &drho);
     Lin L;
-    lin_eval(r, v, m, u, p.cst, p.flags, tf, p.inv_ve, L);
+    lin_eval<ATMO>(r, v, m, u, p.cst, p.flags, tf, p.inv_ve, dens, L);
     double dv[3] = {0.0, 0.0, 0.0};
-    if constexpr (DRAG) drag_dv(drag_lin(v, p.cst, tf, L), v, ys[3], ys[4], ys[5], dv);
+    if constexpr (DRAG) drag_dv<ATMO>(drag_lin<ATMO>(v, p.cst, tf, dens, drho, L), v, r, ys[0], ys[1], ys[2], ys[3], ys[4], ys[5], dv);
     const bool isx = (p.c == 7);
     if (isx && m <= 0.0) err = MPCX_ST_MASS;
 #pragma unroll
@@ -230,7 +252,7 @@ __device__ __forceinline__ bool lu_solve_cols(double (&col)[6], double (&b)[6])
 
 // Quadrature integrand column of this lane at an accepted node (linearize_discretize.py:60-75):
 // g = Phi(t)^-1 [B lam-, B lam+, Sigma, xi][:, c]
-template <bool DRAG>
+template <bool DRAG, bool ATMO>
 __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
                                                double t, double tau_k, double tau_kp1,
                                                double (&g)[7], int &err)
@@ -246,10 +268,12 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
     const double tf = p.tf;
 
     const double r[3] = {x[0], x[1], x[2]}, v[3] = {x[3], x[4], x[5]};
+    double dens = 0.0, drho = 0.0;
+    if constexpr (ATMO) dens = atmo_density(r, p.cst, p.atm, &drho);
     Lin L;
-    lin_eval(r, v, x[6], u, p.cst, p.flags, tf, p.inv_ve, L);
-    double dv[3] = {0.0, 0.0, 0.0};                         // DRAG: xi's A x gains the velocity block and (in L.gmt) the mass column
-    if constexpr (DRAG) drag_dv(drag_lin(v, p.cst, tf, L), v, v[0], v[1], v[2], dv);
+    lin_eval<ATMO>(r, v, x[6], u, p.cst, p.flags, tf, p.inv_ve, dens, L);
+    double dv[3] = {0.0, 0.0, 0.0};                         // DRAG: xi's A x gains the velocity block and (in L.gmt) the mass column; ATMO: the position block too
+    if constexpr (DRAG) drag_dv<ATMO>(drag_lin<ATMO>(v, p.cst, tf, dens, drho, L), v, r, r[0], r[1], r[2], v[0], v[1], v[2], dv);
 
     // B column (B_func :186-215), Sigma (:239-254), xi (:218-236)
     const int j = (c < 3) ? c : c - 3;
@@ -302,12 +326,15 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
 // solve_ivp's `method`, :40): the same controller around the Bogacki-Shampine tableau, separate instantiations.
 // DRAG: MPCX_FLAG_DRAG -- the reference's Discretizer(include_drag=True) with the simulator's atmosphere: the drag partials
 // in Phi's Jacobian and in xi (drag_lin / drag_dv); separate instantiations, the drag-free ones are untouched.
-template <int LAYOUT, bool UNIFORM, int METHOD = 45, bool DRAG = false>
+// ATMO: MPCX_FLAG_ATMO on top of DRAG -- the altitude-dependent density (atmo_density) in every right-hand side, Sigma and xi, and
+// the position block Dr a_D in the Jacobian; a third set of instantiations, the other two are untouched.
+template <int LAYOUT, bool UNIFORM, int METHOD = 45, bool DRAG = false, bool ATMO = false>
 #ifndef MPCX_DISC_WAVES
 #define MPCX_DISC_WAVES 1      // waves per SIMD the register allocation is bounded for (360 registers at 1)
 #endif
 __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArgs a)
 {
+    static_assert(DRAG || !ATMO, "the atmosphere is a property of the drag");
     __shared__ double lds[8 * kRec];
     const int lane = threadIdx.x;
     const int grp = lane >> 3, c = lane & 7;
@@ -339,6 +366,10 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
     p.tf = a.tf[s];
     p.cst.load(a.consts + (size_t)s * MPCX_NCONST);
     p.inv_ve = 1.0 / (p.cst.g0 * p.cst.isp);
+    if constexpr (ATMO) {
+#pragma unroll
+        for (int i = 0; i < MPCX_NATMO; ++i) p.atm[i] = a.atmo[i];
+    }
     const double *xs = a.xbar + (size_t)s * 7 * a.K;
 
     // np.linspace(0, 1, K)[k], [k+1]
@@ -354,7 +385,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
 #pragma unroll
     for (int i = 0; i < 7; ++i) y[i] = (c < 7) ? ((i == c) ? 1.0 : 0.0) : xs[(size_t)i * a.K + k];
     double t = tau_k;
-    rhs_eval<DRAG>(p, y, t, f, err);
+    rhs_eval<DRAG, ATMO>(p, y, t, f, err);
 
     // ---- scipy select_initial_step (common.py:68-134), direction +1, order 4 ----
     double h_abs;
@@ -374,7 +405,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         double y1[7], f1[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i) y1[i] = y[i] + h0 * f[i];
-        rhs_eval<DRAG>(p, y1, t + h0, f1, err);
+        rhs_eval<DRAG, ATMO>(p, y1, t + h0, f1, err);
         double s2 = 0.0;
 #pragma unroll
         for (int i = 0; i < 7; ++i) { const double d = (f1[i] - f[i]) / scale[i]; s2 += d * d; }
@@ -390,7 +421,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
     double acc[7], gprev[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) acc[i] = 0.0;
-    node_integrand<DRAG>(p, y, t, tau_k, tau_kp1, gprev, err);
+    node_integrand<DRAG, ATMO>(p, y, t, tau_k, tau_kp1, gprev, err);
 
     // uniform mode: index of the next evaluation point, time of the previous one, the interpolated state at it
     const double ustep = UNIFORM ? (tau_kp1 - tau_k) / (double)(n_uni - 1) : 0.0;   // np.linspace(tau_k, tau_kp1, n)
@@ -427,13 +458,13 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             // last stage in both methods (first-same-as-last: it becomes f of the next step)
 #pragma unroll
             for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK23_A10) * h;
-            rhs_eval<DRAG>(p, yt, t + RK23_C[1] * h, K1, err);
+            rhs_eval<DRAG, ATMO>(p, yt, t + RK23_C[1] * h, K1, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * 0.0 + K1[i] * RK23_A21) * h;
-            rhs_eval<DRAG>(p, yt, t + RK23_C[2] * h, K2, err);
+            rhs_eval<DRAG, ATMO>(p, yt, t + RK23_C[2] * h, K2, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) yn[i] = y[i] + h * (f[i] * RK23_B[0] + K1[i] * RK23_B[1] + K2[i] * RK23_B[2]);
-            rhs_eval<DRAG>(p, yn, t + h, K6, err);
+            rhs_eval<DRAG, ATMO>(p, yn, t + h, K6, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 K3[i] = 0.0; K4[i] = 0.0; K5[i] = 0.0;
@@ -445,29 +476,29 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         } else {
 #pragma unroll
         for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK_A[1][0]) * h;
-        rhs_eval<DRAG>(p, yt, t + RK_C[1] * h, K1, err);
+        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[1] * h, K1, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i) yt[i] = y[i] + (f[i] * RK_A[2][0] + K1[i] * RK_A[2][1]) * h;
-        rhs_eval<DRAG>(p, yt, t + RK_C[2] * h, K2, err);
+        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[2] * h, K2, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[3][0] + K1[i] * RK_A[3][1] + K2[i] * RK_A[3][2]) * h;
-        rhs_eval<DRAG>(p, yt, t + RK_C[3] * h, K3, err);
+        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[3] * h, K3, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[4][0] + K1[i] * RK_A[4][1] + K2[i] * RK_A[4][2] +
                             K3[i] * RK_A[4][3]) * h;
-        rhs_eval<DRAG>(p, yt, t + RK_C[4] * h, K4, err);
+        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[4] * h, K4, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[5][0] + K1[i] * RK_A[5][1] + K2[i] * RK_A[5][2] +
                             K3[i] * RK_A[5][3] + K4[i] * RK_A[5][4]) * h;
-        rhs_eval<DRAG>(p, yt, t + RK_C[5] * h, K5, err);
+        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[5] * h, K5, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yn[i] = y[i] + h * (f[i] * RK_B[0] + K1[i] * RK_B[1] + K2[i] * RK_B[2] +
                                 K3[i] * RK_B[3] + K4[i] * RK_B[4] + K5[i] * RK_B[5]);
-        rhs_eval<DRAG>(p, yn, t + h, K6, err);
+        rhs_eval<DRAG, ATMO>(p, yn, t + h, K6, err);
 
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
@@ -544,7 +575,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                                                             : Q[i][0] * p1 + Q[i][1] * p2 + Q[i][2] * p3 + Q[i][3] * p4;
                         yd[i] = has ? h * accq + yold[i] : y[i];
                     }
-                    node_integrand<DRAG>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
+                    node_integrand<DRAG, ATMO>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
                     if (has) {
                         const double d = te - te_prev;
 #pragma unroll
@@ -561,7 +592,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         // node quadrature (wave-uniform call; only accepting groups commit)
         if (!UNIFORM && __any(accept)) {
             double g[7];
-            node_integrand<DRAG>(p, y, t, tau_k, tau_kp1, g, err);
+            node_integrand<DRAG, ATMO>(p, y, t, tau_k, tau_kp1, g, err);
             if (accept) {
                 const double d = h;          // ts[i+1] - ts[i]
 #pragma unroll
@@ -641,6 +672,7 @@ static int launch_discretize(mpcx_ctx *ctx, int layout, DiscArgs a, hipStream_t 
 {
     if (a.S < 1 || a.K < 2 || a.Ku < 2) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: need S>=1, K>=2, Ku>=2");
     if (!(a.max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: max_step must be > 0");
+    if (int rc = ctx_atmosphere(ctx, a.flags, a.atmo, "discretize")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     MPCX_HIP(ctx, hipMemsetAsync(a.status, 0, sizeof(int32_t) * a.S, st));
     const long total = (long)a.S * (a.K - 1);
@@ -648,11 +680,12 @@ static int launch_discretize(mpcx_ctx *ctx, int layout, DiscArgs a, hipStream_t 
     const bool uni = (a.flags & MPCX_FLAG_UNIFORM_STEPS) != 0;
     if (uni && (a.flags >> 8) < 2) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: uniform steps need MPCX_UNIFORM_STEPS(n), n >= 2");
     const bool rk23 = (a.flags & MPCX_FLAG_RK23) != 0;
-    const bool drag = (a.flags & MPCX_FLAG_DRAG) != 0;
+    const bool drag = (a.flags & MPCX_FLAG_DRAG) != 0, atmo = (a.flags & MPCX_FLAG_ATMO) != 0;
     if (!uni) a.flags &= (MPCX_FLAG_DRAG | MPCX_FLAG_J2);
 #define MPCX_DISC_LAUNCH(L, U, M)                                                                            \
     do {                                                                                                     \
-        if (drag) hipLaunchKernelGGL((discretize_kernel<L, U, M, true>), dim3(blocks), dim3(64), 0, st, a);  \
+        if (atmo) hipLaunchKernelGGL((discretize_kernel<L, U, M, true, true>), dim3(blocks), dim3(64), 0, st, a); \
+        else if (drag) hipLaunchKernelGGL((discretize_kernel<L, U, M, true>), dim3(blocks), dim3(64), 0, st, a);  \
         else hipLaunchKernelGGL((discretize_kernel<L, U, M, false>), dim3(blocks), dim3(64), 0, st, a);      \
     } while (0)
     if (layout == LAYOUT_STAGE) {
@@ -676,7 +709,7 @@ extern "C" int mpcx_discretize_batch_dev(mpcx_ctx *ctx, int S, int K, int Ku, co
                                          void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    DiscArgs a{S, K, Ku, flags, nullptr, nullptr, max_step, xbar, ubar, tf, consts, nullptr, A, Bp, Bn, Sigma, xi, status};
+    DiscArgs a{S, K, Ku, flags, nullptr, nullptr, max_step, xbar, ubar, tf, consts, nullptr, A, Bp, Bn, Sigma, xi, status, {}};
     return launch_discretize(ctx, LAYOUT_REF, a, (hipStream_t)stream);
 }
 
@@ -686,7 +719,7 @@ extern "C" int mpcx_discretize_stages_ragged_dev(mpcx_ctx *ctx, int S, int K, co
                                                  int32_t *status, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    DiscArgs a{S, K, Ku, flags, Ks, Kus, max_step, xbar, ubar, tf, consts, stage, nullptr, nullptr, nullptr, nullptr, nullptr, status};
+    DiscArgs a{S, K, Ku, flags, Ks, Kus, max_step, xbar, ubar, tf, consts, stage, nullptr, nullptr, nullptr, nullptr, nullptr, status, {}};
     return launch_discretize(ctx, LAYOUT_STAGE, a, (hipStream_t)stream);
 }
 
@@ -705,6 +738,7 @@ extern "C" int mpcx_discretize_batch(mpcx_ctx *ctx, int S, int K, int Ku, const 
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 2 || Ku < 2) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: need S>=1, K>=2, Ku>=2");
+    if (int rc = ctx_check_atmosphere(ctx, flags, "discretize")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)S * (K - 1);
     DeviceArena ar(ctx);

@@ -10,6 +10,7 @@ namespace mpcx {
 constexpr double kCd = 2.5;             // constants.py:7
 constexpr double kRho500 = 9.983E-13;   // simulator.py:112
 constexpr double kEps = 2.220446049250313e-16;
+constexpr double kREarth = 6.371E6;     // constants.py:3 (metres)
 
 // Dormand-Prince 5(4) tableau as used by scipy's RK45 (scipy/integrate/_ivp/rk.py:377-404)
 __device__ constexpr double RK_C[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
@@ -174,10 +175,33 @@ struct SatConst {
     }
 };
 
+// The altitude-dependent atmosphere (MPCX_FLAG_ATMO, include/mpcx.h: atm = {c0, c1, c2, h_floor}, physical units):
+//   h = max(|r R0| - R_EARTH, h_floor) metres (the altitude of simulator.py:109),  rho(h) = exp(c0 + c1 ln h + c2 h) kg/m^3.
+// d2 = |r R0|^2, the sum of the squared components r_i R0 (the rollout's lanes hold one component each and bring the quad's
+// sum).  Returns rho / c.rho, what the drag acceleration multiplies where the fixed model has kRho500 / c.rho; with drho given,
+// also d(rho / c.rho) / d|r| = rho (c1 / h + c2) R0 / c.rho above the floor and 0 on it -- the reference's drho_func
+// (linearize_discretize.py:165-166).  A trial stage that lands below the floor (or at a NaN) is evaluated on the floor.
+__device__ __forceinline__ double atmo_density(double d2, const SatConst &c, const double (&atm)[MPCX_NATMO], double *drho = nullptr)
+{
+    const double alt = sqrt(d2) - kREarth;
+    const bool above = alt > atm[MPCX_ATMO_HFLOOR];
+    const double h = above ? alt : atm[MPCX_ATMO_HFLOOR];
+    const double rho = exp(atm[MPCX_ATMO_C0] + atm[MPCX_ATMO_C1] * log(h) + atm[MPCX_ATMO_C2] * h) / c.rho;
+    if (drho) *drho = above ? rho * (atm[MPCX_ATMO_C1] / h + atm[MPCX_ATMO_C2]) * c.r0 : 0.0;
+    return rho;
+}
+__device__ __forceinline__ double atmo_density(const double (&r)[3], const SatConst &c, const double (&atm)[MPCX_NATMO], double *drho = nullptr)
+{
+    const double p[3] = {r[0] * c.r0, r[1] * c.r0, r[2] * c.r0};
+    return atmo_density(p[0] * p[0] + p[1] * p[1] + p[2] * p[2], c, atm, drho);
+}
+
 // Simulator.satellite_dynamics (simulator.py:116-161) for a given thrust u; result NOT yet
 // multiplied by tf (the caller scales, so Sigma_func's tf=1 evaluation reuses it).
+// (atm: the atmosphere's coefficients, read with MPCX_FLAG_ATMO only)
 __device__ __forceinline__ void dynamics_unscaled(const double (&y)[7], const double (&u)[3],
-                                                  const SatConst &c, int flags, double (&yd)[7])
+                                                  const SatConst &c, int flags, double (&yd)[7],
+                                                  const double (*atm)[MPCX_NATMO] = nullptr)
 {
     const double r2 = y[0] * y[0] + y[1] * y[1] + y[2] * y[2];
     const double rn = sqrt(r2);
@@ -191,7 +215,9 @@ __device__ __forceinline__ void dynamics_unscaled(const double (&y)[7], const do
     }
     if (flags & MPCX_FLAG_DRAG) {
         const double vn = sqrt(y[3] * y[3] + y[4] * y[4] + y[5] * y[5]);
-        const double coef = -0.5 * kCd * c.s * (1.0 / m) * (kRho500 / c.rho) * vn;
+        const double r3v[3] = {y[0], y[1], y[2]};
+        const double dens = ((flags & MPCX_FLAG_ATMO) && atm) ? atmo_density(r3v, c, *atm) : (kRho500 / c.rho);
+        const double coef = -0.5 * kCd * c.s * (1.0 / m) * dens * vn;
 #pragma unroll
         for (int i = 0; i < 3; ++i) yd[3 + i] += coef * y[3 + i];
     }

@@ -150,6 +150,8 @@ struct mpcx_ctx {
     hipStream_t stream = nullptr;      // stream used by the host-pointer entry points
     bool own_stream = false;           // created by the library (mpcx_create / MPCX_STREAM_PRIVATE), not handed in by mpcx_set_stream
     char err[512] = "";
+    double atmo[MPCX_NATMO] = {};      // mpcx_set_atmosphere: the coefficients the launchers copy into the kernel arguments of MPCX_FLAG_ATMO calls
+    bool atmo_set = false;
     DeviceBuf<char> ws;                // workspace of the solver / fused step of the host-pointer entry points (ctx_workspace)
     // launch-order state of the context's solves, and of the SECOND half of a split update (mpcx_mpc_update_batch runs the two
     // halves of a large batch as two chains on two streams: each half is its own sequence of solves of its own batch size)
@@ -186,6 +188,29 @@ inline int ctx_fail(mpcx_ctx *ctx, int code, const char *msg)
 {
     if (ctx) snprintf(ctx->err, sizeof ctx->err, "%s", msg);
     return code;
+}
+
+// MPCX_FLAG_ATMO of a call's flag word: refused (a message, nothing enqueued) without MPCX_FLAG_DRAG or without an atmosphere on
+// the context; otherwise the context's coefficients go into `out`, the launch's own copy.  Without the bit `out` is left alone.
+inline int ctx_atmosphere(mpcx_ctx *ctx, int flags, double (&out)[MPCX_NATMO], const char *who)
+{
+    if (!(flags & MPCX_FLAG_ATMO)) return MPCX_OK;
+    char msg[160];
+    if (!(flags & MPCX_FLAG_DRAG)) {
+        snprintf(msg, sizeof msg, "%s: MPCX_FLAG_ATMO needs MPCX_FLAG_DRAG (the atmosphere is the drag's)", who);
+        return ctx_fail(ctx, MPCX_E_BADARG, msg);
+    }
+    if (!ctx->atmo_set) {
+        snprintf(msg, sizeof msg, "%s: MPCX_FLAG_ATMO without an atmosphere on the context (mpcx_set_atmosphere)", who);
+        return ctx_fail(ctx, MPCX_E_BADARG, msg);
+    }
+    for (int i = 0; i < MPCX_NATMO; ++i) out[i] = ctx->atmo[i];
+    return MPCX_OK;
+}
+inline int ctx_check_atmosphere(mpcx_ctx *ctx, int flags, const char *who)
+{
+    double unused[MPCX_NATMO];
+    return ctx_atmosphere(ctx, flags, unused, who);
 }
 
 #define MPCX_HIP(ctx, call)                                                                   \

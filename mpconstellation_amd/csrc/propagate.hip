@@ -23,6 +23,7 @@ struct PropArgs {
     double *y_out;            // [S][7][n_eval]
     double *u_out;            // [S][3][n_eval] or nullptr: the thrust law at the output points (Discretizer.extract_uk)
     int32_t *status, *nsteps;
+    double atmo[MPCX_NATMO];  // MPCX_FLAG_ATMO: the context's atmosphere, copied at launch (last: the other members keep their places)
 };
 
 // Four lanes per satellite (a quad): lane c < 3 owns position and velocity component c, every lane carries the mass; lane 3
@@ -106,7 +107,7 @@ __device__ __forceinline__ double foh_cached(double tau, Ctrl &c, int &err)
 // by rounding only (rollouts agree with the reference's to 1e-12, the accepted step sequence is the same -- max_step
 // clips every step).  inv_gi = 1 / (g0 Isp).
 template <int KIND, int FLAGS>
-__device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, double inv_gi, double tf, double tau, int comp, bool on,
+__device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, const double (&atm)[MPCX_NATMO], double inv_gi, double tf, double tau, int comp, bool on,
                                          double r, double v, double m, double &dr, double &dv, double &dm, int &err)
 {
     constexpr int flags = FLAGS;
@@ -144,7 +145,10 @@ __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, double in
     dv = kg * r + u * im;
     if (flags & MPCX_FLAG_DRAG) {                            // simulator.py:150-153
         const double vn = sqrt(quad_sum(v * v));
-        const double coef = -0.5 * kCd * cst.s * im * (kRho500 / cst.rho) * vn;
+        double dens;                                         // rho / cst.rho: the fixed density, or the atmosphere's at this altitude
+        if constexpr ((flags & MPCX_FLAG_ATMO) != 0) { const double p = r * cst.r0; dens = atmo_density(quad_sum(p * p), cst, atm); }
+        else dens = kRho500 / cst.rho;
+        const double coef = -0.5 * kCd * cst.s * im * dens * vn;
         dv += coef * v;
     }
     if (flags & MPCX_FLAG_J2) {                              // simulator.py:154-158
@@ -158,7 +162,8 @@ __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, double in
 }
 
 // One instantiation per thrust law and truth-model flag set (both are launch constants): the right-hand side appears
-// eight times in the step and every variant it does not need would sit in each copy.
+// eight times in the step and every variant it does not need would sit in each copy.  FLAGS: MPCX_FLAG_DRAG | MPCX_FLAG_J2, and
+// MPCX_FLAG_ATMO with drag -- the density at the stage's own altitude (atmo_density) in place of the fixed one.
 template <int KIND, int FLAGS>
 __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
 {
@@ -194,7 +199,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
     double yr = on ? a.y0[(size_t)sat * 7 + comp] : 0.0, yv = on ? a.y0[(size_t)sat * 7 + 3 + comp] : 0.0, ym = a.y0[(size_t)sat * 7 + 6];
     double fr, fv, fm;
     double t = 0.0;
-    prop_rhs<KIND, FLAGS>(c, cst, inv_gi, tf, t, comp, on, yr, yv, ym, fr, fv, fm, err);
+    prop_rhs<KIND, FLAGS>(c, cst, a.atmo, inv_gi, tf, t, comp, on, yr, yv, ym, fr, fv, fm, err);
     // select_initial_step (scipy common.py:68-134)
     double h_abs;
     {
@@ -203,7 +208,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
         double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
         h0 = fmin(h0, 1.0);
         double f1r, f1v, f1m;
-        prop_rhs<KIND, FLAGS>(c, cst, inv_gi, tf, t + h0, comp, on, yr + h0 * fr, yv + h0 * fv, ym + h0 * fm, f1r, f1v, f1m, err);
+        prop_rhs<KIND, FLAGS>(c, cst, a.atmo, inv_gi, tf, t + h0, comp, on, yr + h0 * fr, yv + h0 * fv, ym + h0 * fm, f1r, f1v, f1m, err);
         const double d2 = rms7((f1r - fr) / scr, (f1v - fv) / scv, (f1m - fm) / scm) / h0;
         const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 0.2);
         h_abs = fmin(fmin(100.0 * h0, h1), fmin(1.0, a.max_step));
@@ -229,7 +234,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
         // the six stages, each of this lane's three components with the arithmetic of the one-lane form
         double Kr[6], Kv[6], Km[6];
 #define MPCX_STAGE(S, EXPR_R, EXPR_V, EXPR_M)                                                                            \
-        prop_rhs<KIND, FLAGS>(c, cst, inv_gi, tf, t + RK_C[S] * h, comp, on, yr + (EXPR_R) * h, yv + (EXPR_V) * h, ym + (EXPR_M) * h, \
+        prop_rhs<KIND, FLAGS>(c, cst, a.atmo, inv_gi, tf, t + RK_C[S] * h, comp, on, yr + (EXPR_R) * h, yv + (EXPR_V) * h, ym + (EXPR_M) * h, \
                               Kr[S - 1], Kv[S - 1], Km[S - 1], err);
         MPCX_STAGE(1, fr * RK_A[1][0], fv * RK_A[1][0], fm * RK_A[1][0])
         MPCX_STAGE(2, fr * RK_A[2][0] + Kr[0] * RK_A[2][1], fv * RK_A[2][0] + Kv[0] * RK_A[2][1], fm * RK_A[2][0] + Km[0] * RK_A[2][1])
@@ -245,7 +250,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
         const double ynr = yr + h * (fr * RK_B[0] + Kr[0] * RK_B[1] + Kr[1] * RK_B[2] + Kr[2] * RK_B[3] + Kr[3] * RK_B[4] + Kr[4] * RK_B[5]);
         const double ynv = yv + h * (fv * RK_B[0] + Kv[0] * RK_B[1] + Kv[1] * RK_B[2] + Kv[2] * RK_B[3] + Kv[3] * RK_B[4] + Kv[4] * RK_B[5]);
         const double ynm = ym + h * (fm * RK_B[0] + Km[0] * RK_B[1] + Km[1] * RK_B[2] + Km[2] * RK_B[3] + Km[3] * RK_B[4] + Km[4] * RK_B[5]);
-        prop_rhs<KIND, FLAGS>(c, cst, inv_gi, tf, t + h, comp, on, ynr, ynv, ynm, Kr[5], Kv[5], Km[5], err);
+        prop_rhs<KIND, FLAGS>(c, cst, a.atmo, inv_gi, tf, t + h, comp, on, ynr, ynv, ynm, Kr[5], Kv[5], Km[5], err);
         const double ehr = (fr * RK_E[0] + Kr[0] * RK_E[1] + Kr[1] * RK_E[2] + Kr[2] * RK_E[3] + Kr[3] * RK_E[4] + Kr[4] * RK_E[5] + Kr[5] * RK_E[6]) * h;
         const double ehv = (fv * RK_E[0] + Kv[0] * RK_E[1] + Kv[1] * RK_E[2] + Kv[2] * RK_E[3] + Kv[3] * RK_E[4] + Kv[4] * RK_E[5] + Kv[5] * RK_E[6]) * h;
         const double ehm = (fm * RK_E[0] + Km[0] * RK_E[1] + Km[1] * RK_E[2] + Km[2] * RK_E[3] + Km[3] * RK_E[4] + Km[4] * RK_E[5] + Km[5] * RK_E[6]) * h;
@@ -374,17 +379,20 @@ extern "C" int mpcx_propagate_thrust_batch_ragged_dev(mpcx_ctx *ctx, int S, int 
     if (ctrl_kind < MPCX_CTRL_ZERO || ctrl_kind > MPCX_CTRL_SEQUENCE) return ctx_fail(ctx, MPCX_E_BADARG, "propagate: unknown thrust law");
     if (ctrl_kind == MPCX_CTRL_SEQUENCE && (Ku < 2 || !end_tau || !ctrl_vec)) return ctx_fail(ctx, MPCX_E_BADARG, "propagate: sequence needs Ku>=2, table and end_tau");
     if ((ctrl_kind == MPCX_CTRL_CONSTANT || ctrl_kind == MPCX_CTRL_TANGENTIAL) && !ctrl_vec) return ctx_fail(ctx, MPCX_E_BADARG, "propagate: thrust parameters missing");
+    PropArgs a{S, n_eval, flags, ctrl_kind, Ku, n_evals, Kus, max_step, y0, tf, consts, ctrl_vec, end_tau, y_out, u_out, status, nsteps, {}};
+    if (int rc = ctx_atmosphere(ctx, flags, a.atmo, "propagate")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    PropArgs a{S, n_eval, flags, ctrl_kind, Ku, n_evals, Kus, max_step, y0, tf, consts, ctrl_vec, end_tau, y_out, u_out, status, nsteps};
     const dim3 grid((S + 15) / 16), block(64);            // 16 satellites (quads) per wave
     hipStream_t st = (hipStream_t)stream;
 #define MPCX_PROP_LAUNCH(KIND, FLAGS) hipLaunchKernelGGL((propagate_kernel<KIND, FLAGS>), grid, block, 0, st, a)
 #define MPCX_PROP_FLAGS(KIND)                                                                                         \
-    switch (flags & 3) {                                                                                              \
+    switch (flags & (3 | MPCX_FLAG_ATMO)) {                                                                           \
     case 0: MPCX_PROP_LAUNCH(KIND, 0); break;                                                                         \
     case 1: MPCX_PROP_LAUNCH(KIND, 1); break;                                                                         \
     case 2: MPCX_PROP_LAUNCH(KIND, 2); break;                                                                         \
-    default: MPCX_PROP_LAUNCH(KIND, 3); break;                                                                        \
+    case 3: MPCX_PROP_LAUNCH(KIND, 3); break;                                                                         \
+    case MPCX_FLAG_ATMO | 1: MPCX_PROP_LAUNCH(KIND, MPCX_FLAG_ATMO | 1); break;                                       \
+    default: MPCX_PROP_LAUNCH(KIND, MPCX_FLAG_ATMO | 3); break;          /* (the bit without drag: refused above) */  \
     }
     switch (ctrl_kind) {
     case MPCX_CTRL_ZERO: MPCX_PROP_FLAGS(MPCX_CTRL_ZERO); break;
@@ -423,6 +431,7 @@ extern "C" int mpcx_propagate_thrust_batch_ragged(mpcx_ctx *ctx, int S, int n_ev
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || n_eval < 1) return ctx_fail(ctx, MPCX_E_BADARG, "propagate: need S>=1, n_eval>=1");
+    if (int rc = ctx_check_atmosphere(ctx, flags, "propagate")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     double *dy0 = ar.upload(y0, (size_t)S * 7), *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST);

@@ -387,6 +387,7 @@ extern "C" int mpcx_mpc_step_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, const
 {
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_step: need S>=1, K>=3 and options");
+    if (int rc = ctx_check_atmosphere(ctx, flags, "mpc_step")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     void *ws = ctx_workspace(ctx, mpcx_mpc_step_workspace_bytes_ctx(ctx, S, K));
     if (!ws) return MPCX_E_NOMEM;
@@ -436,6 +437,8 @@ extern "C" int mpcx_scp_iteration_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, 
     if (!ctx) return MPCX_E_BADARG;
     if (S < 1 || K < 3 || !opts || !prop_status) return ctx_fail(ctx, MPCX_E_BADARG, "scp_iteration: need S>=1, K>=3, options and prop_status");
     if (opts->flags & (MPCX_SOLVE_FIXED_TF | MPCX_SOLVE_SHARED_TF)) return ctx_fail(ctx, MPCX_E_BADARG, "scp_iteration: free per-satellite tf only");
+    if (int rc = ctx_check_atmosphere(ctx, prop_flags, "scp_iteration (prop_flags)")) return rc;
+    if (int rc = ctx_check_atmosphere(ctx, disc_flags, "scp_iteration (disc_flags)")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     void *ws = ctx_workspace(ctx, mpcx_mpc_step_workspace_bytes_ctx(ctx, S, K));
     if (!ws) return MPCX_E_NOMEM;
@@ -514,6 +517,8 @@ extern "C" int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp,
     if (opts->flags & (MPCX_SOLVE_FIXED_TF | MPCX_SOLVE_SHARED_TF)) return ctx_fail(ctx, MPCX_E_BADARG, "mpc_update: free per-satellite tf only");
     if (y_sim && (sim_n_eval < 1 || !(sim_tf > 0.0) || !(sim_interval > 0.0) || !sim_status))
         return ctx_fail(ctx, MPCX_E_BADARG, "mpc_update: segment flight needs sim_tf>0, sim_interval>0, sim_n_eval>=1, sim_status");
+    if (int rc = ctx_check_atmosphere(ctx, disc_flags, "mpc_update (disc_flags)")) return rc;
+    if (y_sim) if (int rc = ctx_check_atmosphere(ctx, sim_flags, "mpc_update (sim_flags)")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     const int split_mode = update_split_mode();
     const bool split = split_mode > 0 && S >= 2 * kTwoWaveMax && !(opts->flags & MPCX_SOLVE_TIME_PARALLEL);
@@ -548,7 +553,7 @@ extern "C" int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp,
     if (split) MPCX_HIP(ctx, ctx->nreg.reserve((size_t)S * 2));
     // the planning rollouts' dynamics: the discretisation's with MPCX_FLAG_PLAN_ROLLOUTS, the reference's drag- and J2-free
     // run_nonlinear (control.py:237-240) without
-    const int roll_flags = (disc_flags & MPCX_FLAG_PLAN_ROLLOUTS) ? (disc_flags & (MPCX_FLAG_DRAG | MPCX_FLAG_J2)) : 0;
+    const int roll_flags = (disc_flags & MPCX_FLAG_PLAN_ROLLOUTS) ? (disc_flags & (MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO)) : 0;
     const double *tf_fin = dtf0;
     const int32_t *Ks_fin = nullptr;
     const double *Uplan = dU[(n_scp - 1) & 1];

@@ -14,7 +14,7 @@ def _is_native_dynamics(f):
 
 class Discretizer:
     def __init__(self, const, rho_func=None, drho_func=None, include_drag=False, include_J2=False,
-                 use_scipy_ZOH=False, device=0):
+                 use_scipy_ZOH=False, device=0, atmosphere=None):
         self.const = const
         self.include_drag = include_drag
         self.include_J2 = include_J2
@@ -25,6 +25,9 @@ class Discretizer:
         self.use_scipy_ZOH = use_scipy_ZOH
         self.rho_func = rho_func
         self.drho_func = drho_func
+        # atmosphere (an Atmosphere): with include_drag, the linearisation with the altitude-dependent density -- what the reference
+        # takes as rho_func / drho_func (:164-166), in the one closed form the device evaluates (include/mpcx.h, MPCX_FLAG_ATMO)
+        self.atmosphere = atmosphere
         # ODE / quadrature settings, same names and defaults as the reference (:104-109)
         self.ivp_max_step = 1e-2
         self.ivp_solver = 'RK45'
@@ -48,7 +51,7 @@ class Discretizer:
         Sig = np.empty((S, 7, K - 1)); xi = np.empty((S, 7, K - 1))
         status = np.zeros(S, dtype=np.int32)
         lib = _ffi.load()
-        ctx = _ffi.context(self.device)
+        ctx = _ffi.atmosphere_context(self.device, 0, self.atmosphere if self.include_drag else None)
         rc = lib.mpcx_discretize_batch(ctx, S, K, Ku, _ffi.dptr(x), _ffi.dptr(u), _ffi.dptr(tf),
                                        _ffi.dptr(consts), self.device_flags(self.include_J2), float(self.ivp_max_step),
                                        _ffi.dptr(A), _ffi.dptr(Bp), _ffi.dptr(Bn), _ffi.dptr(Sig),
@@ -77,17 +80,18 @@ class Discretizer:
 
     def device_flags(self, include_J2=False):
         """the linearisation's settings as flags of the discretize / fused-step entry points (include/mpcx.h): include_drag
-        (:162-173, with the simulator's atmosphere), use_uniform_steps with integrator_steps (linearize_discretize.py:27-30:
+        (:162-173, with the simulator's atmosphere or, given one, self.atmosphere), use_uniform_steps with integrator_steps (linearize_discretize.py:27-30:
         t_eval = linspace(.., integrator_steps)), ivp_solver (:40); include_J2: with MPCX_FLAG_J2"""
         return _ffi.discretize_flags(self.include_drag, include_J2, int(self.integrator_steps) if self.use_uniform_steps else 0,
-                                     self.ivp_solver == 'RK23')
+                                     self.ivp_solver == 'RK23', self.atmosphere)
 
     def _check_modes(self):
         if self.include_drag and (self.rho_func is not None or self.drho_func is not None):
             # the drag branch (:162-173) runs on the device with the simulator's atmosphere (fixed density, drho = 0,
-            # simulator.py:112) -- rho_func / drho_func None; a Python density model cannot run there
-            raise NotImplementedError("drag in the linearisation: only the simulator's fixed-density atmosphere "
-                                      "(rho_func=None, drho_func=None) is implemented on the device")
+            # simulator.py:112) or with the closed-form model of atmosphere=; a Python density callable cannot run there
+            raise NotImplementedError("drag in the linearisation: a Python rho_func / drho_func cannot run on the device; pass "
+                                      "atmosphere=Atmosphere.power_law(...) / Atmosphere.exponential(...) for an altitude-dependent "
+                                      "density, or rho_func=None, drho_func=None for the simulator's fixed one")
         if self.ivp_solver not in ('RK45', 'RK23'):
             raise NotImplementedError("ivp_solver: 'RK45' (the reference's default) and 'RK23' are implemented on the device; "
                                       "scipy's DOP853 and its implicit methods (Radau, BDF, LSODA) are not")

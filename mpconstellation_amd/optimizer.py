@@ -52,18 +52,18 @@ def _solver_flags(solver, linear_vt, fixed_tf=None, shared_tf=False):
     return solver
 
 
-def scp_flags(include_drag=False, include_J2=False, rollout_model=False):
+def scp_flags(include_drag=False, include_J2=False, rollout_model=False, atmosphere=None):
     """(prop_flags, disc_flags) of an SCP iteration (mpcx_scp_iteration_batch_ragged) that plans with the given model: the
     linearisation with drag / J2, and -- rollout_model=True -- the rollout too.  The reference's planner has neither
     (control.py:187, 237-240): all defaults."""
-    model = _ffi.model_flags(include_drag, include_J2)
+    model = _ffi.model_flags(include_drag, include_J2, atmosphere)
     return (model if rollout_model else 0), model
 
 
-def update_flags(include_drag=False, include_J2=False, rollout_model=False):
+def update_flags(include_drag=False, include_J2=False, rollout_model=False, atmosphere=None):
     """disc_flags of an update (mpcx_mpc_update_batch) that plans with the given model: rollout_model=True adds
     MPCX_FLAG_PLAN_ROLLOUTS, which gives its planning rollouts the discretisation's drag / J2."""
-    return _ffi.model_flags(include_drag, include_J2) | (_ffi.FLAG_PLAN_ROLLOUTS if rollout_model else 0)
+    return _ffi.model_flags(include_drag, include_J2, atmosphere) | (_ffi.FLAG_PLAN_ROLLOUTS if rollout_model else 0)
 
 
 def _many(devices):
@@ -104,11 +104,11 @@ def _solve_result(X, U, NU, tfo, held, status, iters, kkt, reg):
 
 def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False, max_step=1e-2, device=0, slot=0,
                    linear_vt=False, fixed_tf=None, pinned_results=False, uniform_steps=0, regularised=False, Ks=None, shared_tf=False,
-                   devices=None, rk23=False, include_drag=False, **solver):
+                   devices=None, rk23=False, include_drag=False, atmosphere=None, **solver):
     """S independent satellite-MPC-steps (discretize + solve) on the device.
     xbar (S,7,K), ubar (S,3,K), tf (S,), consts (S,8), r_des (S,) -> SolveResult with batched arrays.
     include_drag / include_J2: the linearisation of Discretizer(include_drag=..., include_J2=...), drag with the simulator's
-    atmosphere (include/mpcx.h, MPCX_FLAG_DRAG).
+    atmosphere (include/mpcx.h, MPCX_FLAG_DRAG) or, with atmosphere= (an Atmosphere), the altitude-dependent one (MPCX_FLAG_ATMO).
     Ks (S,) int: a ragged batch -- satellite s has Ks[s] <= K nodes in the first columns of its rows (what the reference's
     second SCP iteration poses: int(base_res * tf_u) nodes per satellite, control.py:227); result columns past a
     satellite's count are zero.
@@ -133,7 +133,8 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
         raise ValueError("expected xbar (S,7,K) and ubar (S,3,K)")
     batched = [xbar, ubar, _ffi.per_sat(tf, S), _ffi.as_f64(consts), _ffi.per_sat(r_des, S), _ffi.counts(Ks, S), _ffi.make_popts(options, S)]
     how = dict(opts=_ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt, fixed_tf, shared_tf)),
-               dflags=_ffi.discretize_flags(include_drag, include_J2, uniform_steps, rk23), max_step=float(max_step))
+               dflags=_ffi.discretize_flags(include_drag, include_J2, uniform_steps, rk23, atmosphere), max_step=float(max_step),
+               atmosphere=atmosphere if include_drag else None)
     if many:                                               # ONE result set; every block fills its satellites' part
         X, U, NU, kkt, status, iters = _result_arrays(S, K, tuple(int(d) for d in devices) if pinned_results else int(devices[0]), pinned_results)
     else:
@@ -149,12 +150,12 @@ def mpc_step_batch(xbar, ubar, tf, consts, r_des, options=None, include_J2=False
     return _solve_result(X, U, NU, tfo, held, status, iters, kkt, reg)
 
 
-def _step_call(xbar, ubar, tf, consts, r_des, Ks, popts, *, device, slot, out, opts, dflags, max_step):
+def _step_call(xbar, ubar, tf, consts, r_des, Ks, popts, *, device, slot, out, opts, dflags, max_step, atmosphere=None):
     """One step call on context (device, slot): the normalised inputs of the context's satellites (a whole batch, or a block of
     a multi-device call) and `out`, their part of the result set -- X, U, NU, tf, status, iters, kkt, and regularised (S,2)
     where mpcx_solve_regularised of the solve is wanted."""
     S, _, K = xbar.shape
-    ctx = _ffi.context(device, slot)
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere)
     ragged = Ks is not None or popts is not None           # (the table comes with the ragged entry point only; its Ks may be NULL)
     _ffi.call("mpcx_mpc_step_batch_ragged" if ragged else "mpcx_mpc_step_batch", ctx, S, K, *([_ffi.iptr_opt(Ks)] if ragged else []),
               _ffi.dptr(xbar), _ffi.dptr(ubar), _ffi.dptr(tf), _ffi.dptr(consts), _ffi.dptr(r_des), dflags, max_step, C.byref(opts),
@@ -166,7 +167,7 @@ def _step_call(xbar, ubar, tf, consts, r_des, Ks, popts, *, device, slot, out, o
 
 def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Kus=None, include_J2=False, max_step=1e-2,
                         prop_max_step=1e-3, device=0, slot=0, linear_vt=False, return_reference=False, include_drag=False,
-                        rollout_model=False, **solver):
+                        rollout_model=False, atmosphere=None, **solver):
     """One SCP iteration of OptimalController.update (control.py:183-227) for S satellites in ONE library call
     (mpcx_scp_iteration_batch_ragged): the nonlinear rollout from y0 (S,7) over tf (S,) under `law` = (kind, vec, Ku, end_tau)
     (simulator.propagate_batch's law tuple) sampled at K nodes -- Ks[s] of them in a ragged batch --, its controller's thrust
@@ -174,7 +175,7 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     unless return_reference=True (then the result carries .xbar (S,7,K) and .ubar (S,3,K)).  Returns a SolveResult with the
     extra attribute prop_status (S,).
     Planning model (scp_flags): include_drag / include_J2 in the linearisation; rollout_model=True flies the rollout with them
-    too (the reference's rollout has neither)."""
+    too (the reference's rollout has neither); atmosphere (an Atmosphere): the drag of both with the altitude-dependent density."""
     y0 = _ffi.as_f64(y0); S = y0.shape[0]; K = int(K)
     tf = _ffi.per_sat(tf, S); r_des = _ffi.per_sat(r_des, S)
     consts = _ffi.as_f64(consts)
@@ -185,8 +186,8 @@ def scp_iteration_batch(y0, tf, consts, r_des, law, K, options=None, Ks=None, Ku
     tfo = np.empty(S); pst = np.zeros(S, dtype=np.int32)
     xb = np.empty((S, 7, K)) if return_reference else None
     ub = np.empty((S, 3, K)) if return_reference else None
-    prop_flags, disc_flags = scp_flags(include_drag, include_J2, rollout_model)
-    _ffi.call("mpcx_scp_iteration_batch_ragged", _ffi.context(device, slot), S, K, _ffi.iptr_opt(Ks), _ffi.dptr(y0), _ffi.dptr(tf),
+    prop_flags, disc_flags = scp_flags(include_drag, include_J2, rollout_model, atmosphere)
+    _ffi.call("mpcx_scp_iteration_batch_ragged", _ffi.atmosphere_context(device, slot, atmosphere if include_drag else None), S, K, _ffi.iptr_opt(Ks), _ffi.dptr(y0), _ffi.dptr(tf),
               _ffi.dptr(consts), _ffi.dptr(r_des), prop_flags, kind, _ffi.dptr_opt(vec), Ku, _ffi.iptr_opt(Kus), _ffi.dptr_opt(end_tau),
               float(prop_max_step), disc_flags, float(max_step), C.byref(opts), _ffi.dptr_opt(xb), _ffi.dptr_opt(ub), _ffi.dptr(X),
               _ffi.dptr(U), _ffi.dptr(NU), _ffi.dptr(tfo), _ffi.iptr(status), _ffi.iptr(iters), _ffi.dptr(kkt), _ffi.iptr(pst),
@@ -203,7 +204,7 @@ class UpdateResult(SolveResult):
 
 def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None, ref_thrust=0.5, include_J2=False, max_step=1e-2,
                      prop_max_step=1e-3, device=0, slot=0, linear_vt=False, fly=None, devices=None, include_drag=False,
-                     rollout_model=False, **solver):
+                     rollout_model=False, atmosphere=None, **solver):
     """OptimalController.update (control.py:170-235) for S satellites in ONE library call (mpcx_mpc_update_batch): the tangential
     reference rollout over `horizon` sampled at K = int(base_res * horizon) nodes, n_scp x (extract_uk, discretise, solve) with
     the nonlinear re-rollout under the optimised sequence -- sampled at int(base_res * tf_u) nodes per satellite -- between
@@ -214,7 +215,9 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     Planning model (update_flags): include_drag / include_J2 in every linearisation; rollout_model=True flies the planning
     rollouts with them too (MPCX_FLAG_PLAN_ROLLOUTS).  The defaults are the reference's planner, which has neither.
     devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (see mpc_step_batch).
-    options may hold per-satellite values (_ffi.make_popts): every SCP iteration solves satellite s under row s of the table."""
+    options may hold per-satellite values (_ffi.make_popts): every SCP iteration solves satellite s under row s of the table.
+    atmosphere (an Atmosphere): the altitude-dependent density for both sides -- the plan where include_drag, the flight where
+    fly's include_drag."""
     many = _many(devices)
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
@@ -226,11 +229,13 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
     sim = (0.0, 0.0, 0, 0, 1e-3)
     if fly is not None:
         tf_sim, interval, n_eval, drag, j2 = fly[:5]
-        sim = (float(tf_sim), float(interval), int(n_eval), _ffi.model_flags(drag, j2), float(fly[5]) if len(fly) > 5 else 1e-3)
+        sim = (float(tf_sim), float(interval), int(n_eval), _ffi.model_flags(drag, j2, atmosphere), float(fly[5]) if len(fly) > 5 else 1e-3)
     batched = [y0, horizon, _ffi.as_f64(consts), _ffi.per_sat(r_des, S), _ffi.make_popts(options, S)]
     how = dict(K=K, n_scp=int(n_scp), base_res=float(base_res), ref_thrust=float(ref_thrust), prop_max_step=float(prop_max_step),
-               flags=update_flags(include_drag, include_J2, rollout_model), max_step=float(max_step),
+               flags=update_flags(include_drag, include_J2, rollout_model, atmosphere), max_step=float(max_step),
                opts=_ffi.make_solve_opts(options, **_solver_flags(solver, linear_vt)), sim=sim)
+    if (how["flags"] | sim[3]) & _ffi.FLAG_ATMO:
+        how["atmosphere"] = atmosphere
     res = _update_result(S, K, n_scp, fly)                 # ONE result set; with several devices every block fills its satellites' part
     out = dict(X=res.X, U=res.U, NU=res.NU, kkt=res.kkt, tf=res.tf, Ks=res.Ks, prop_status=res.prop_status, status=res.status,
                iters=res.iters, y_sim=res.y_sim, sim_status=res.sim_status)
@@ -244,7 +249,7 @@ def mpc_update_batch(y0, horizon, consts, r_des, base_res, n_scp=2, options=None
 
 
 def _update_call(y0, horizon, consts, r_des, popts, *, device, slot, out, K, n_scp, base_res, ref_thrust, prop_max_step, flags, max_step,
-                 opts, sim):
+                 opts, sim, atmosphere=None):
     """One update call on context (device, slot): the normalised inputs of the context's satellites and `out`, their part of
     the result set (_update_result's arrays by name).  A block's columns of the (n_scp, S) records are not contiguous: the
     library fills a temporary that OutArrays copies over."""
@@ -252,7 +257,7 @@ def _update_call(y0, horizon, consts, r_des, popts, *, device, slot, out, K, n_s
     S = y0.shape[0]
     oa = OutArrays(out)
     status, iters = oa.get("status", (n_scp, S), np.int32), oa.get("iters", (n_scp, S), np.int32)
-    _ffi.call("mpcx_mpc_update_batch", _ffi.context(device, slot), S, K, n_scp, base_res, _ffi.dptr(y0), _ffi.dptr(horizon),
+    _ffi.call("mpcx_mpc_update_batch", _ffi.atmosphere_context(device, slot, atmosphere), S, K, n_scp, base_res, _ffi.dptr(y0), _ffi.dptr(horizon),
               _ffi.dptr(consts), _ffi.dptr(r_des), ref_thrust, prop_max_step, flags, max_step, C.byref(opts), _ffi.dptr(out["X"]),
               _ffi.dptr(out["U"]), _ffi.dptr(out["NU"]), _ffi.dptr(out["tf"]), _ffi.iptr(out["Ks"]), _ffi.iptr(status), _ffi.iptr(iters),
               _ffi.dptr(out["kkt"]), _ffi.iptr(out["prop_status"]), *sim, _ffi.dptr_opt(out.get("y_sim")),
@@ -529,7 +534,7 @@ class Optimizer:
                                          include_J2=self.d.include_J2, include_drag=self.d.include_drag, max_step=self.d.ivp_max_step,
                                          device=getattr(self.d, "device", 0),
                                          uniform_steps=int(self.d.integrator_steps) if self.d.use_uniform_steps else 0,
-                                         rk23=(self.d.ivp_solver == 'RK23'), **solver)
+                                         rk23=(self.d.ivp_solver == 'RK23'), atmosphere=getattr(self.d, "atmosphere", None), **solver)
         self.status = self.result.status
         if self.shared_tf and self._N > 1 and not self.tf_search.converged:
             import warnings

@@ -20,7 +20,7 @@ class OdeResult:
 
 
 def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=False, max_step=1e-3, device=0, slot=0,
-                    Kus=None, thrust=False, devices=None):
+                    Kus=None, thrust=False, devices=None, atmosphere=None):
     """y0 (S,7) normalised, tf (S,), consts (S,8); law = (kind, vec, Ku, end_tau) with per-satellite or
     broadcastable parameters.  Returns y (S,7,n_eval), status (S,), nsteps (S,) -- and, with thrust=True, u (S,3,n_eval) as a
     fourth value: the law evaluated at the output points, Discretizer.extract_uk of the rollout's own controller
@@ -30,13 +30,16 @@ def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=
     thrust table (law SEQUENCE, table rows of length Ku).
     devices=[d0, d1, ...]: contiguous blocks of satellites on several devices at once (sharding.sharded_call), every block
     writing in place into its slice of one result set, whose row length -- the constellation's longest satellite -- is every
-    block's."""
+    block's.
+    atmosphere (an Atmosphere): with include_drag, the drag meets the altitude-dependent density instead of the fixed one
+    (include/mpcx.h, MPCX_FLAG_ATMO); every context the call runs on is given the model first."""
     y0 = _ffi.as_f64(y0); S = y0.shape[0]
     kind, vec, Ku, end_tau = _ffi.thrust_law(law, S)
     n_evals = _ffi.counts(n_eval, S) if np.ndim(n_eval) > 0 else None
     n_eval = int(n_eval) if n_evals is None else int(n_evals.max())
     batched = [y0, _ffi.per_sat(tf, S), _ffi.as_f64(consts), vec, end_tau, n_evals, _ffi.counts(Kus, S)]
-    how = dict(n_eval=n_eval, flags=_ffi.model_flags(include_drag, include_J2), kind=kind, Ku=Ku, max_step=float(max_step))
+    how = dict(n_eval=n_eval, flags=_ffi.model_flags(include_drag, include_J2, atmosphere), kind=kind, Ku=Ku, max_step=float(max_step),
+               atmosphere=atmosphere if include_drag else None)
     out = dict(y=_ffi.result_pool.take((S, 7, n_eval)), status=np.zeros(S, dtype=np.int32), nsteps=np.zeros(S, dtype=np.int32),
                u=_ffi.result_pool.take((S, 3, n_eval)) if thrust else None)
     if devices is not None and len(devices) > 1:
@@ -49,21 +52,21 @@ def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=
     return (out["y"], out["status"], out["nsteps"], out["u"]) if thrust else (out["y"], out["status"], out["nsteps"])
 
 
-def _propagate_call(y0, tf, consts, vec, end_tau, n_evals, Kus, *, device, slot, out, n_eval, flags, kind, Ku, max_step):
+def _propagate_call(y0, tf, consts, vec, end_tau, n_evals, Kus, *, device, slot, out, n_eval, flags, kind, Ku, max_step, atmosphere=None):
     """One rollout call on context (device, slot): the normalised inputs of the context's satellites and `out`, their part of
     the result set -- y, status, nsteps, and u where the thrust at the output points is wanted."""
     u = out.get("u")
     ragged = u is not None or n_evals is not None or Kus is not None
     name = "mpcx_propagate_thrust_batch_ragged" if u is not None else "mpcx_propagate_batch_ragged" if ragged else "mpcx_propagate_batch"
     only_ragged = lambda p: [p] if ragged else []          # (the per-satellite counts: arguments of the ragged entry points only)
-    _ffi.call(name, _ffi.context(device, slot), y0.shape[0], n_eval, *only_ragged(_ffi.iptr_opt(n_evals)), _ffi.dptr(y0), _ffi.dptr(tf),
+    _ffi.call(name, _ffi.atmosphere_context(device, slot, atmosphere), y0.shape[0], n_eval, *only_ragged(_ffi.iptr_opt(n_evals)), _ffi.dptr(y0), _ffi.dptr(tf),
               _ffi.dptr(consts), flags, kind, _ffi.dptr_opt(vec), Ku, *only_ragged(_ffi.iptr_opt(Kus)), _ffi.dptr_opt(end_tau), max_step,
               _ffi.dptr(out["y"]), *([] if u is None else [_ffi.dptr(u)]), _ffi.iptr(out["status"]), _ffi.iptr(out["nsteps"]))
 
 
 class Simulator:
     def __init__(self, sats=[], controller=Controller(), scale=SatelliteScale(), base_res=100, include_drag=True,
-                 include_J2=True, verbose=False, device=0, devices=None):
+                 include_J2=True, verbose=False, device=0, devices=None, atmosphere=None):
         self.sim_data = {}
         self.sim_time = {}
         self.sats = sats
@@ -75,6 +78,7 @@ class Simulator:
         self.scale = scale
         self.verbose = verbose
         self.device = device
+        self.atmosphere = atmosphere  # an Atmosphere: the truth model's drag with the altitude-dependent density (None: the reference's fixed one)
         self.devices = devices        # several devices: the satellites are dealt out in contiguous blocks (sharding.sharded_call)
 
     # ---- batched rollout of all satellites (one kernel) ----
@@ -83,7 +87,8 @@ class Simulator:
         y0 = np.stack([self.scale.normalize_state(s.get_state_vector()) for s in sats])
         law = self._device_law()
         y, status, nsteps = propagate_batch(y0, tf, np.tile(const, (len(sats), 1)), law, self.eval_points, include_drag=self.include_drag,
-                                            include_J2=self.include_J2, max_step=0.001, device=self.device, devices=self.devices)
+                                            include_J2=self.include_J2, max_step=0.001, device=self.device, devices=self.devices,
+                                            atmosphere=self.atmosphere)
         if (status == 1).any():
             raise Exception("ERROR: INVALID SATELLITE MASS")           # simulator.py:135-136
         if (status != 0).any():
