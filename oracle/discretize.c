@@ -15,6 +15,7 @@ typedef struct {
     double tf;
     const double *cst;
     int flags;
+    const double *atm; /* the atmosphere of ORACLE_FLAG_ATMO, or NULL */
     int foh_err;
 } dphi_ctx;
 
@@ -25,14 +26,14 @@ static int dphi(double tau, const double *y, double *ydot, void *vctx)
     double u[3], A[49];
     if (oracle_u_foh(tau, c->u, c->Ku, u)) { c->foh_err = 1; u[0] = u[1] = u[2] = 0.0; }
     const double *Phi = y, *x = y + 49;
-    oracle_A_func(x, u, c->tf, c->cst, c->flags, A);                    /* :282 */
+    oracle_A_func_atm(x, u, c->tf, c->cst, c->flags, c->atm, A);                    /* :282 */
     for (int i = 0; i < 7; ++i)                                          /* :284 */
         for (int j = 0; j < 7; ++j) {
             double acc = 0.0;
             for (int l = 0; l < 7; ++l) acc += A[i * 7 + l] * Phi[l * 7 + j];
             ydot[i * 7 + j] = acc;
         }
-    return oracle_dynamics(x, u, c->tf, c->cst, c->flags, ydot + 49);    /* :287 */
+    return oracle_dynamics_atm(x, u, c->tf, c->cst, c->flags, c->atm, ydot + 49);    /* :287 */
 }
 
 /* 7x7 inverse by LU with partial pivoting (np.linalg.inv -> LAPACK gesv), :69 */
@@ -68,7 +69,7 @@ static void linspace01(int K, int j, double *out) /* np.linspace(0, 1, K)[j] */
 
 /* get_matrices for one interval k: linearize_discretize.py:8-82 */
 static int get_matrices(int K, int Ku, const double *x, const double *u, double tf,
-                        const double *cst, int flags, double max_step, int n_uniform, int k, double *A_k,
+                        const double *cst, int flags, const double *atm, double max_step, int n_uniform, int k, double *A_k,
                         double *B_kp, double *B_kn, double *Sigma_k, double *xi_k, int32_t *n_nodes,
                         int32_t *n_fev, double *dump_t, double *dump_y, int dump_cap)
 {
@@ -78,7 +79,7 @@ static int get_matrices(int K, int Ku, const double *x, const double *u, double 
     double y0[56];
     memset(y0, 0, sizeof y0);
     for (int i = 0; i < 7; ++i) { y0[i * 7 + i] = 1.0; y0[49 + i] = x[i * K + k]; }   /* :31-34 */
-    dphi_ctx ctx = {u, Ku, tf, cst, flags, 0};
+    dphi_ctx ctx = {u, Ku, tf, cst, flags, atm, 0};
     rk45 s;
     /* :37-41; method = options['ivp_solver'] (:40): flag bit 8 = 'RK23', otherwise the default 'RK45' (:105) */
     rk_init_method(&s, (flags & 8) ? 23 : 45, 56, dphi, &ctx, tau_k, y0, tau_kp1, max_step, 1e-3, 1e-6);
@@ -131,8 +132,8 @@ static int get_matrices(int K, int Ku, const double *x, const double *u, double 
         double ut[3], B[21], Sig[7], xiv[7], Pinv[49];
         if (oracle_u_foh(t, u, Ku, ut)) status = 3;
         oracle_B_func(xs, ut, tf, cst, B);                                              /* :65 */
-        oracle_dynamics(xs, ut, 1.0, cst, flags, Sig);                                  /* :66, Sigma_func :252-253 */
-        oracle_xi_func(xs, ut, tf, cst, flags, xiv);                                    /* :67 */
+        oracle_dynamics_atm(xs, ut, 1.0, cst, flags, atm, Sig);                                 /* :66, Sigma_func :252-253 */
+        oracle_xi_func_atm(xs, ut, tf, cst, flags, atm, xiv);                                   /* :67 */
         if (inv7(Phi, Pinv)) status = 4;                                                /* :69 */
         for (int r = 0; r < 7; ++r) {
             for (int c = 0; c < 3; ++c) {
@@ -193,11 +194,21 @@ int oracle_discretize_mode(int K, int Ku, const double *x, const double *u, doub
                            double *xi, int32_t *node_counts, int32_t *node_nfev, double *node_t,
                            double *node_y, int node_cap)
 {
+    return oracle_discretize_mode_atm(K, Ku, x, u, tf, cst, flags, 0, max_step, n_uniform, A, Bp, Bn, Sigma, xi, node_counts,
+                                      node_nfev, node_t, node_y, node_cap);
+}
+
+/* atm: the atmosphere {c0, c1, c2, h_floor} that ORACLE_FLAG_DRAG | ORACLE_FLAG_ATMO meets; NULL: the fixed density */
+int oracle_discretize_mode_atm(int K, int Ku, const double *x, const double *u, double tf, const double *cst,
+                               int flags, const double *atm, double max_step, int n_uniform, double *A, double *Bp, double *Bn,
+                               double *Sigma, double *xi, int32_t *node_counts, int32_t *node_nfev, double *node_t,
+                               double *node_y, int node_cap)
+{
     int status = 0, used = 0;
     for (int k = 0; k < K - 1; ++k) {
         double S7[7], X7[7];
         int32_t nn = 0, nf = 0;
-        int r = get_matrices(K, Ku, x, u, tf, cst, flags, max_step, n_uniform, k, A + k * 49, Bp + k * 21,
+        int r = get_matrices(K, Ku, x, u, tf, cst, flags, atm, max_step, n_uniform, k, A + k * 49, Bp + k * 21,
                              Bn + k * 21, S7, X7, &nn, &nf, node_t ? node_t + used : 0,
                              node_y ? node_y + used * 56 : 0, node_cap - used);
         if (r && !status) status = r;

@@ -10,6 +10,7 @@
 
 #define C_D_CONST 2.5          /* constants.py:7 */
 #define RHO_500KM 9.983E-13    /* simulator.py:112 (fixed density) */
+#define R_EARTH_M 6.371E6      /* constants.py:3, the altitude of simulator.py:109 */
 
 static double norm3(const double a[3]) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 
@@ -20,9 +21,37 @@ static void cross3(const double a[3], const double b[3], double c[3])
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+/* The density the drag meets, over const.RHO, and its derivative with respect to the normalised radius: what the reference's
+ * Discretizer takes as rho_func / drho_func (linearize_discretize.py:164-165) and its simulator as get_atmo_density / const.RHO
+ * (simulator.py:152).  atm = {c0, c1, c2, h_floor} with ORACLE_FLAG_ATMO: the closed form the fixtures were made with,
+ *   alt = |r R0| - R_EARTH (simulator.py:109),  h = alt above h_floor, h_floor below or on it,
+ *   rho = exp(c0 + c1 ln h + c2 h),  drho = rho (c1 / h + c2) R0 above the floor and 0 below or on it;
+ * otherwise the fixed density of simulator.py:112 and drho = 0.  ORACLE_FLAG_NO_DRHO: the model's rho with drho_func = 0, the
+ * linearisation without its position block Dr a_D (what the tests remove to show that an input is sensitive to it). */
+static double density_ratio(const double r[3], const double *cst, int flags, const double *atm, double *drho)
+{
+    if (!((flags & ORACLE_FLAG_ATMO) && atm)) {
+        if (drho) *drho = 0.0;
+        return RHO_500KM / cst[OC_RHO];
+    }
+    double p[3] = {r[0] * cst[OC_R0], r[1] * cst[OC_R0], r[2] * cst[OC_R0]};
+    double alt = norm3(p) - R_EARTH_M;
+    int above = alt > atm[3];
+    double h = above ? alt : atm[3];
+    double rho = exp(atm[0] + atm[1] * log(h) + atm[2] * h);
+    if (drho) *drho = (above && !(flags & ORACLE_FLAG_NO_DRHO)) ? rho * (atm[1] / h + atm[2]) * cst[OC_R0] / cst[OC_RHO] : 0.0;
+    return rho / cst[OC_RHO];
+}
+
 /* simulator.py:116-161.  The thrust u = u_func(y, tau) is evaluated by the caller. */
 int oracle_dynamics(const double y[7], const double u[3], double tf, const double *cst,
                     int flags, double ydot[7])
+{
+    return oracle_dynamics_atm(y, u, tf, cst, flags, 0, ydot);
+}
+
+int oracle_dynamics_atm(const double y[7], const double u[3], double tf, const double *cst,
+                        int flags, const double *atm, double ydot[7])
 {
     const double *r = y, *v = y + 3;
     double m = y[6];
@@ -35,7 +64,7 @@ int oracle_dynamics(const double y[7], const double u[3], double tf, const doubl
         yd[3 + i] = k_g * r[i] + u[i] / m;                 /* :145-149 */
     }
     if (flags & ORACLE_FLAG_DRAG) {                        /* :150-153 */
-        double coef = -1.0 / 2.0 * C_D_CONST * cst[OC_S] * (1.0 / m) * (RHO_500KM / cst[OC_RHO])
+        double coef = -1.0 / 2.0 * C_D_CONST * cst[OC_S] * (1.0 / m) * density_ratio(r, cst, flags, atm, 0)
                       * norm3(v);
         for (int i = 0; i < 3; ++i) yd[3 + i] += coef * v[i];
     }
@@ -51,10 +80,17 @@ int oracle_dynamics(const double y[7], const double u[3], double tf, const doubl
     return bad;
 }
 
-/* linearize_discretize.py:119-183 (include_drag branch :162-169 is dead in the reference:
- * Constants has no CD and rho_func defaults to None, so it is out of scope). */
+/* linearize_discretize.py:119-183.  The include_drag branch (:162-169) runs in the reference once the Discretizer is given
+ * const.CD = C_D and rho_func / drho_func (tests/golden/make_drag_golden.py, make_atmo_golden.py): ORACLE_FLAG_DRAG, with
+ * the density of density_ratio(). */
 void oracle_A_func(const double x[7], const double u[3], double tf, const double *cst,
                    int flags, double A[49])
+{
+    oracle_A_func_atm(x, u, tf, cst, flags, 0, A);
+}
+
+void oracle_A_func_atm(const double x[7], const double u[3], double tf, const double *cst,
+                       int flags, const double *atm, double A[49])
 {
     double D[49];
     memset(D, 0, sizeof D);
@@ -86,7 +122,23 @@ void oracle_A_func(const double x[7], const double u[3], double tf, const double
                 D[(3 + i) * 7 + j] += t1 + t2 + t3;
             }
     }
-    for (int i = 0; i < 3; ++i) D[(3 + i) * 7 + 6] = -u[i] / (m * m);   /* :175 */
+    double Dm_aD[3] = {0.0, 0.0, 0.0};
+    if (flags & ORACLE_FLAG_DRAG) {                        /* :162-169 */
+        const double *v = x + 3;
+        double v_norm = norm3(v);
+        double drho, rho = density_ratio(r, cst, flags, atm, &drho);                     /* :164-165 */
+        double kr = -C_D_CONST * cst[OC_S] / (2.0 * m);
+        double kv = (-rho * C_D_CONST * cst[OC_S]) / (2.0 * m);
+        double km = (rho * C_D_CONST * cst[OC_S]) / (2.0 * (m * m));
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) {
+                D[(3 + i) * 7 + j] += (kr * v_norm * v[i]) * (drho * r[j] / r_norm);     /* :166 */
+                D[(3 + i) * 7 + 3 + j] = kv * ((i == j ? v_norm : 0.0) + (1.0 / v_norm) * (v[i] * v[j]));   /* :167-168 */
+            }
+            Dm_aD[i] = km * v_norm * v[i];                                               /* :169 */
+        }
+    }
+    for (int i = 0; i < 3; ++i) D[(3 + i) * 7 + 6] = Dm_aD[i] + -u[i] / (m * m);         /* :175, :178 */
     for (int i = 0; i < 49; ++i) A[i] = tf * D[i];                       /* :182 */
 }
 
@@ -109,8 +161,14 @@ void oracle_B_func(const double x[7], const double u[3], double tf, const double
 void oracle_xi_func(const double x[7], const double u[3], double tf, const double *cst, int flags,
                     double xi[7])
 {
+    oracle_xi_func_atm(x, u, tf, cst, flags, 0, xi);
+}
+
+void oracle_xi_func_atm(const double x[7], const double u[3], double tf, const double *cst, int flags,
+                        const double *atm, double xi[7])
+{
     double A[49], B[21];
-    oracle_A_func(x, u, tf, cst, flags, A);
+    oracle_A_func_atm(x, u, tf, cst, flags, atm, A);
     oracle_B_func(x, u, tf, cst, B);
     for (int i = 0; i < 7; ++i) {
         double ax = 0.0, bu = 0.0;

@@ -24,7 +24,14 @@ extern "C" {
 /* Normalised constants, same field order as reference constants.py:11-20. */
 enum { OC_MU = 0, OC_R_E, OC_J2, OC_G0, OC_ISP, OC_S, OC_R0, OC_RHO, OC_NCONST };
 
-enum { ORACLE_FLAG_DRAG = 1, ORACLE_FLAG_J2 = 2 };
+/* ORACLE_FLAG_DRAG: simulator.py:150-153 and the include_drag branch of A_func (linearize_discretize.py:162-169), hence of
+ * xi_func and of the Phi right-hand side of oracle_discretize*.  ORACLE_FLAG_ATMO (with DRAG, in the *_atm entry points): the
+ * density is the model atm = {c0, c1, c2, h_floor} in the convention of mpconstellation_amd.Atmosphere.reference_funcs,
+ *   rho_func(r) = rho(alt) / RHO,  drho_func(r) = rho'(alt) R0 / RHO,  alt = |r R0| - R_EARTH,
+ *   rho(h) = exp(c0 + c1 ln h + c2 h) above h_floor; the floor's density and a zero slope below or on it.
+ * Without the bit, or with atm = NULL: the fixed density rho = 9.983e-13 / RHO (simulator.py:112), drho = 0.
+ * ORACLE_FLAG_NO_DRHO: drho_func = 0 beside the model's rho_func -- for sensitivity checks, no mode of the reference's callers. */
+enum { ORACLE_FLAG_DRAG = 1, ORACLE_FLAG_J2 = 2, ORACLE_FLAG_ATMO = 32, ORACLE_FLAG_NO_DRHO = 64 };
 
 /* Thrust laws u(y, tau): reference control.py */
 enum {
@@ -45,14 +52,20 @@ typedef struct {
 /* D1  simulator.py:116-161 ; returns 0, or 1 if mass <= 0 (reference raises) */
 int oracle_dynamics(const double y[7], const double u[3], double tf, const double *cst,
                     int flags, double ydot[7]);
-/* D2  linearize_discretize.py:119-183 (drag branch out of scope: cannot run in the reference) */
+int oracle_dynamics_atm(const double y[7], const double u[3], double tf, const double *cst,
+                        int flags, const double *atm, double ydot[7]);
+/* D2  linearize_discretize.py:119-183, the drag branch :162-169 with CD = 2.5 included */
 void oracle_A_func(const double x[7], const double u[3], double tf, const double *cst,
                    int flags, double A[49]);
+void oracle_A_func_atm(const double x[7], const double u[3], double tf, const double *cst,
+                       int flags, const double *atm, double A[49]);
 /* D3  linearize_discretize.py:186-215 */
 void oracle_B_func(const double x[7], const double u[3], double tf, const double *cst, double B[21]);
 /* D4  linearize_discretize.py:218-236 */
 void oracle_xi_func(const double x[7], const double u[3], double tf, const double *cst, int flags,
                     double xi[7]);
+void oracle_xi_func_atm(const double x[7], const double u[3], double tf, const double *cst, int flags,
+                        const double *atm, double xi[7]);
 /* D6  linearize_discretize.py:294-315 ; returns 0 or -1 on the reference's IndexError */
 int oracle_u_foh(double tau, const double *u, int Ku, double out[3]);
 
@@ -68,12 +81,19 @@ int oracle_discretize_mode(int K, int Ku, const double *x, const double *u, doub
                            int flags, double max_step, int n_uniform, double *A, double *Bp, double *Bn, double *Sigma,
                            double *xi, int32_t *node_counts, int32_t *node_nfev, double *node_t,
                            double *node_y, int node_cap);
+int oracle_discretize_mode_atm(int K, int Ku, const double *x, const double *u, double tf, const double *cst,
+                               int flags, const double *atm, double max_step, int n_uniform, double *A, double *Bp, double *Bn,
+                               double *Sigma, double *xi, int32_t *node_counts, int32_t *node_nfev, double *node_t,
+                               double *node_y, int node_cap);
 
 /* simulator.py:164-189: solve_ivp(RK45, max_step, t_eval=linspace(0,1,n_eval)) with dense output.
  * y_out (7, n_eval) row-major as sol.y.  Returns 0, 1 = mass<=0, 2 = step too small. */
 int oracle_propagate(const double y0[7], double tf, const double *cst, int flags,
                      const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
                      int32_t *nsteps);
+int oracle_propagate_atm(const double y0[7], double tf, const double *cst, int flags, const double *atm,
+                         const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
+                         int32_t *nsteps);
 /* linearize_discretize.py:393-411 */
 void oracle_extract_uk(int K, const double *x, const double *t, const oracle_ctrl *ctrl, double *u);
 

@@ -16,6 +16,7 @@ typedef struct {
     double tf;
     const double *cst;
     int flags;
+    const double *atm;
     int err;
 } prop_ctx;
 
@@ -24,14 +25,22 @@ static int prop_rhs(double tau, const double *y, double *ydot, void *vctx)
     prop_ctx *c = (prop_ctx *)vctx;
     double u[3];
     if (oracle_ctrl_eval(c->ctrl, y, tau, u)) c->err = 3;                /* simulator.py:147 */
-    return oracle_dynamics(y, u, c->tf, c->cst, c->flags, ydot);
+    return oracle_dynamics_atm(y, u, c->tf, c->cst, c->flags, c->atm, ydot);
 }
 
 int oracle_propagate(const double y0[7], double tf, const double *cst, int flags,
                      const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
                      int32_t *nsteps)
 {
-    prop_ctx ctx = {ctrl, tf, cst, flags, 0};
+    return oracle_propagate_atm(y0, tf, cst, flags, 0, ctrl, n_eval, max_step, y_out, nsteps);
+}
+
+/* atm: the atmosphere get_atmo_density returns with ORACLE_FLAG_DRAG | ORACLE_FLAG_ATMO; NULL: the fixed density */
+int oracle_propagate_atm(const double y0[7], double tf, const double *cst, int flags, const double *atm,
+                         const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
+                         int32_t *nsteps)
+{
+    prop_ctx ctx = {ctrl, tf, cst, flags, atm, 0};
     rk45 s;
     rk45_init(&s, 7, prop_rhs, &ctx, 0.0, y0, 1.0, max_step, 1e-3, 1e-6);
     int ei = 0, status = 0;

@@ -150,6 +150,13 @@ def discretize_stages(x, u, tf, consts, Ks=None, Kus=None, flags=0, max_step=1e-
     return stage, st.cpu().numpy()
 
 
+def unpack_stage(stage, s, K):
+    """the K - 1 stage records [A | Bn | Bp | Sigma | xi] of satellite s as the arrays of the reference layout"""
+    rec = stage[s, :K - 1].cpu().numpy()
+    return dict(A=rec[:, 0:49].reshape(K - 1, 7, 7), Bn=rec[:, 49:70].reshape(K - 1, 7, 3), Bp=rec[:, 70:91].reshape(K - 1, 7, 3),
+                Sigma=np.ascontiguousarray(rec[:, 91:98].T), xi=np.ascontiguousarray(rec[:, 98:105].T))
+
+
 def solve_dev(stage, x, u, tf, consts, r_des, opts, Ks=None, ws=None, out=None):
     """mpcx_solve_batch_ragged_dev in the caller's workspace tensor `ws` -> (results dict of numpy arrays, ws, out)"""
     torch, _ffi, lib, ctx, d = _env()

@@ -13,6 +13,8 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 LIB_PATH = os.path.join(ORACLE_DIR, "liboracle.so")
 
 FLAG_DRAG, FLAG_J2, FLAG_RK23 = 1, 2, 8      # (FLAG_RK23: Discretizer.ivp_solver = 'RK23' in oracle_discretize*)
+FLAG_ATMO = 32                               # with FLAG_DRAG: the density model of the atmosphere= keyword (set by it)
+FLAG_NO_DRHO = 64                            # the model's density with drho_func = 0 (sensitivity checks)
 CTRL_ZERO, CTRL_CONSTANT, CTRL_TANGENTIAL, CTRL_SEQUENCE = 0, 1, 2, 3
 CT_NTERMS = 32
 CT_SLICES = {
@@ -67,6 +69,17 @@ def lib():
         _lib.oracle_extract_uk.argtypes = [C.c_int, _dp, _dp, C.POINTER(OracleCtrl), _dp]
         _lib.oracle_constraint_terms.argtypes = [C.c_int, _dp, _dp, C.c_double, _dp, _dp, _dp]
         _lib.oracle_scale.argtypes = [_dp, _dp, _dp]
+        _lib.oracle_dynamics_atm.restype = C.c_int
+        _lib.oracle_discretize_mode_atm.restype = C.c_int
+        _lib.oracle_propagate_atm.restype = C.c_int
+        _lib.oracle_dynamics_atm.argtypes = [_dp, _dp, C.c_double, _dp, C.c_int, _dp, _dp]
+        _lib.oracle_A_func_atm.argtypes = [_dp, _dp, C.c_double, _dp, C.c_int, _dp, _dp]
+        _lib.oracle_xi_func_atm.argtypes = [_dp, _dp, C.c_double, _dp, C.c_int, _dp, _dp]
+        _lib.oracle_discretize_mode_atm.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int, _dp,
+                                                    C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp,
+                                                    C.c_int]
+        _lib.oracle_propagate_atm.argtypes = [_dp, C.c_double, _dp, C.c_int, _dp, C.POINTER(OracleCtrl),
+                                              C.c_int, C.c_double, _dp, _ip]
     return _lib
 
 
@@ -78,17 +91,30 @@ def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def dynamics(y, u, tf, cst, flags=0):
+def _atm(atmosphere, flags):
+    """atmosphere= of the wrappers below: an Atmosphere (anything with coefficients()) or its four numbers (c0, c1, c2,
+    h_floor) -> (flags with FLAG_ATMO, the coefficient array to keep alive, its pointer); None: the fixed density (NULL)"""
+    if atmosphere is None:
+        return flags, None, None
+    coef = _c(atmosphere.coefficients() if hasattr(atmosphere, "coefficients") else atmosphere)
+    if coef.shape != (4,):
+        raise ValueError(f"atmosphere: expected (c0, c1, c2, h_floor), got shape {coef.shape}")
+    return flags | FLAG_ATMO, coef, _p(coef)
+
+
+def dynamics(y, u, tf, cst, flags=0, atmosphere=None):
     y, u, cst = _c(y), _c(u), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
     out = np.zeros(7)
-    rc = lib().oracle_dynamics(_p(y), _p(u), tf, _p(cst), flags, _p(out))
+    rc = lib().oracle_dynamics_atm(_p(y), _p(u), tf, _p(cst), flags, atm, _p(out))
     return out, rc
 
 
-def A_func(x, u, tf, cst, flags=0):
+def A_func(x, u, tf, cst, flags=0, atmosphere=None):
     x, u, cst = _c(x), _c(u), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
     out = np.zeros((7, 7))
-    lib().oracle_A_func(_p(x), _p(u), tf, _p(cst), flags, _p(out))
+    lib().oracle_A_func_atm(_p(x), _p(u), tf, _p(cst), flags, atm, _p(out))
     return out
 
 
@@ -99,10 +125,11 @@ def B_func(x, u, tf, cst):
     return out
 
 
-def xi_func(x, u, tf, cst, flags=0):
+def xi_func(x, u, tf, cst, flags=0, atmosphere=None):
     x, u, cst = _c(x), _c(u), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
     out = np.zeros(7)
-    lib().oracle_xi_func(_p(x), _p(u), tf, _p(cst), flags, _p(out))
+    lib().oracle_xi_func_atm(_p(x), _p(u), tf, _p(cst), flags, atm, _p(out))
     return out
 
 
@@ -113,16 +140,18 @@ def u_foh(tau, u):
     return out, rc
 
 
-def discretize(x, u, tf, cst, flags=0, max_step=1e-2, dump_nodes=False, uniform_steps=0):
-    """uniform_steps = integrator_steps of Discretizer.use_uniform_steps (0: the default adaptive quadrature nodes)"""
+def discretize(x, u, tf, cst, flags=0, max_step=1e-2, dump_nodes=False, uniform_steps=0, atmosphere=None):
+    """uniform_steps = integrator_steps of Discretizer.use_uniform_steps (0: the default adaptive quadrature nodes);
+    atmosphere: with FLAG_DRAG, the density model in place of the fixed density"""
     x, u, cst = _c(x), _c(u), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
     K, Ku = x.shape[1], u.shape[1]
     A = np.zeros((K - 1, 7, 7)); Bp = np.zeros((K - 1, 7, 3)); Bn = np.zeros((K - 1, 7, 3))
     Sig = np.zeros((7, K - 1)); xi = np.zeros((7, K - 1))
     cnt = np.zeros(K - 1, dtype=np.int32); nfev = np.zeros(K - 1, dtype=np.int32)
     cap = max(64, int(uniform_steps) + 1) * (K - 1) if dump_nodes else 0
     nt = np.zeros(max(cap, 1)); ny = np.zeros((max(cap, 1), 56))
-    rc = lib().oracle_discretize_mode(K, Ku, _p(x), _p(u), float(tf), _p(cst), flags, max_step, int(uniform_steps), _p(A),
+    rc = lib().oracle_discretize_mode_atm(K, Ku, _p(x), _p(u), float(tf), _p(cst), flags, atm, max_step, int(uniform_steps), _p(A),
                                  _p(Bp), _p(Bn), _p(Sig), _p(xi), cnt.ctypes.data_as(_ip),
                                  nfev.ctypes.data_as(_ip), _p(nt) if dump_nodes else None,
                                  _p(ny) if dump_nodes else None, cap)
@@ -147,11 +176,12 @@ def make_ctrl(kind, thrust=(0.0, 0.0, 0.0), useq=None, end_tau=1.0):
     return c
 
 
-def propagate(y0, tf, cst, ctrl, n_eval, flags=0, max_step=1e-3):
+def propagate(y0, tf, cst, ctrl, n_eval, flags=0, max_step=1e-3, atmosphere=None):
     y0, cst = _c(y0), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
     out = np.zeros((7, n_eval))
     ns = np.zeros(1, dtype=np.int32)
-    rc = lib().oracle_propagate(_p(y0), float(tf), _p(cst), flags, C.byref(ctrl), n_eval, max_step,
+    rc = lib().oracle_propagate_atm(_p(y0), float(tf), _p(cst), flags, atm, C.byref(ctrl), n_eval, max_step,
                                 _p(out), ns.ctypes.data_as(_ip))
     return out, rc, int(ns[0])
 

@@ -170,17 +170,12 @@ def test_uniform_table_equals_null(golden_dir, flags):
         assert not np.array_equal(null["X"], sat_dev(P, _ffi.make_solve_opts(P["sets"][2]), None, step=True, stage=stage)["X"])
 
 
-def unpack_stage(stage, s, K):
-    rec = stage[s, :K - 1].cpu().numpy()
-    return dict(A=rec[:, 0:49].reshape(K - 1, 7, 7), Bn=rec[:, 49:70].reshape(K - 1, 7, 3), Bp=rec[:, 70:91].reshape(K - 1, 7, 3),
-                Sigma=np.ascontiguousarray(rec[:, 91:98].T), xi=np.ascontiguousarray(rec[:, 98:105].T))
-
-
 def test_table_launch_against_the_oracle(golden_dir):
     """every satellite of the table launch against the oracle solved under that satellite's own options, on the device's own
     stage records: the rule of tests/test_solve_gpu.py -- rounding level where the iteration paths coincide (neither side
     regularised, or both alike), the solver tolerance otherwise"""
     from test_solve_gpu import oracle_solve, solution_tolerance
+    from dev_solve import unpack_stage
     P, rows, structs, table, scalar = table_and_scalar_runs(golden_dir, RAGGED, 0, False)
     _, stage = stages(golden_dir, RAGGED)
     for s in range(P["S"]):

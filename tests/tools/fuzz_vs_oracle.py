@@ -1,6 +1,8 @@
 """checking helper (GPU box): random satellites, horizons and option sets, device (mpc_step_batch through the C ABI) against the
 CPU oracle: status, iteration count, regularised iterations, |dX|, |dtf|.  The oracle is the checker here as in tests/.
-usage: python tests/tools/fuzz_vs_oracle.py [n_problems] [seed]      (lives under tests/: it uses oracle/ as the checker)"""
+usage: python tests/tools/fuzz_vs_oracle.py [n_problems] [seed] [model] [atmosphere]      (lives under tests/: it uses oracle/ as the checker)
+model: letters of "dj" -- d: drag in the linearisation (S x 1e4 on every other problem), j: J2; "-": neither (the default).
+atmosphere (with d): "power", "exp" or "general" (tests/drag_cases.py); the density model on both sides instead of the fixed density."""
 import os, sys, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -9,6 +11,14 @@ import multiprocessing as mp
 from mpconstellation_amd import _ffi
 if os.environ.get("MPCX_LIB"): _ffi.LIB_PATH = os.path.abspath(os.environ["MPCX_LIB"])       # e.g. a -DMPCX_ITER_LOG build
 ONLY = int(os.environ["FUZZ_ONLY"]) if os.environ.get("FUZZ_ONLY") else None                 # one problem, with both iteration logs
+MODEL = sys.argv[3] if len(sys.argv) > 3 else "-"
+DRAG, J2 = "d" in MODEL, "j" in MODEL
+ATMO = sys.argv[4] if len(sys.argv) > 4 and DRAG else None
+
+
+def atmosphere():
+    import drag_cases
+    return drag_cases.models()[ATMO] if ATMO else None
 
 
 def make(args):
@@ -26,7 +36,8 @@ def make(args):
 def oracle(job):
     import oracle_lib as O, nlp_ipm as N
     x, u, cst, tf, opts = job
-    P = N.MpcProblem(x, u, tf, cst[0], O.discretize(x, u, tf, cst), O.constraint_terms(x, u, cst[0]), opts)
+    flags = (O.FLAG_DRAG if DRAG else 0) | (O.FLAG_J2 if J2 else 0)
+    P = N.MpcProblem(x, u, tf, cst[0], O.discretize(x, u, tf, cst, flags, atmosphere=atmosphere()), O.constraint_terms(x, u, cst[0]), opts)
     r = N.solve(P, verbose=ONLY is not None)
     return r["status"], r["iters"], r["n_regularised"], r["X"], r["tf"], bool(r["iterate"].clean) if r["iterate"] is not None else False
 
@@ -44,7 +55,8 @@ if __name__ == "__main__":
     with mp.Pool(min(16, os.cpu_count())) as pool:
         data = pool.map(make, specs)
         jobs = []
-        for (x, u, cst), (idx, K, tf, thrust) in zip(data, specs):
+        for i, ((x, u, cst), (idx, K, tf, thrust)) in enumerate(zip(data, specs)):
+            if DRAG and i % 2: cst[5] *= 1e4                                                 # MPCX_C_S
             rK = float(np.linalg.norm(x[:3, -1]))
             o = {"r_des": rK * float(rng.choice([1.0, 1.0, 1.0, 1.002, 0.99, 1.1]))}
             if rng.random() < 0.3: o["eps_r"] = float(rng.choice([1e-6, 1e-3, 0.05]))
@@ -58,7 +70,8 @@ if __name__ == "__main__":
     bad = 0; n_clean = 0
     for j, (job, r) in enumerate(zip(jobs, ref)):
         x, u, cst, tf, o = job
-        res = mpc_step_batch(x[None], u[None], [tf], cst[None], [o["r_des"]], options={k: v for k, v in o.items() if k != "r_des"}, regularised=True)
+        res = mpc_step_batch(x[None], u[None], [tf], cst[None], [o["r_des"]], options={k: v for k, v in o.items() if k != "r_des"}, regularised=True,
+                             include_drag=DRAG, include_J2=J2, atmosphere=atmosphere())
         st, it, nr = int(res.status[0]), int(res.iters[0]), int(res.n_regularised[0])
         if ONLY is not None and os.environ.get("MPCX_LIB"):      # iteration log of a -DMPCX_ITER_LOG build (it overwrites X and U)
             lg = res.X[0].ravel(); lu = res.U[0].ravel()
