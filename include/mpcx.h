@@ -509,6 +509,59 @@ int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp, double bas
 int mpcx_resample_sequence_dev(mpcx_ctx *ctx, int S, int Ku, const int32_t *Kus, const double *u, int n,
                                const int32_t *ns, double *u_out, int32_t *status, void *stream);
 
+/*
+ * Conjunction screening: the constellation on one clock, and the closest approach of every pair on it.  The reference flies
+ * and plans every satellite in its own units and on its own clock and never looks at two satellites at once (simulator.py:68,87
+ * leaves "scale the tfs so satellites orbit for the same time?" open).
+ *
+ * mpcx_ephemeris_batch: trajectories as the library returns them -- Y [S][7][n] normalised states (rows of length n, ns[s] nodes
+ * in use; ns = NULL: all n; the ragged convention above) -- resampled at M >= 2 common instants linspace(T0, T1, M) (seconds; the
+ * last instant is exactly T1) in physical units:
+ *   units [S][2]   each satellite's length unit (m) and time unit (s); its speed unit is their quotient
+ *   span  [S][2]   physical times (s) of the satellite's first and last node; the nodes are uniform in between
+ *   eph   [S][6][M]   position (m) and velocity (m/s): cubic Hermite in physical time on the node positions and velocities (the
+ *                     state carries the velocity, so the interpolant is C1; error h_n^4 / 384 max |p''''| for node spacing h_n)
+ * An instant outside [span[s][0], span[s][1]] gives NaN in all six rows.  status [S]: ns[s] outside 2..n or span[s][1] <=
+ * span[s][0] gives all NaN and MPCX_ST_BADK.  M < 2, S < 1, n < 1, T1 <= T0: MPCX_E_BADARG, nothing enqueued.
+ *
+ * mpcx_conjunction_screen: for the rows i = row0 .. row0 + nrows - 1 (a block of rows per device: every device is given the whole
+ * eph; row0 = 0, nrows = S for all) against every column j != i, over every grid interval [t_m, t_m+1] (h = (T1 - T0) / (M - 1)),
+ * skipping an interval where either satellite has a NaN among the six values of either end.  With lo = min(i, j), hi = max(i, j),
+ * d = p_hi - p_lo and w = v_hi - v_lo at the two ends (so both orderings of a pair get the same bits):
+ *   chord  D = d1 - d0,  s* = clamp(-d0 . D / |D|^2, 0, 1)  (0 when |D|^2 is zero or not finite);
+ *   if 0 < s* < 1: three Newton steps on g(s) = d(s) . d'(s), d(s) the cubic Hermite of (d0, h w0, d1, h w1), g' = |d'|^2 + d . d'',
+ *   a step skipped where g' <= 0, s clamped to [0, 1] after every step;
+ *   the interval's distance is min(|d0|, |d1|, |d(s)|), its time that of the smallest (t_m, t_m+1, t_m + s h; of equal ones the
+ *   first in this order).  Distances are compared as their squares.
+ * Per row: dmin [nrows] (m), partner [nrows] (-1: none), tca [nrows] (s) -- the smallest distance, of equal ones the smaller j,
+ * then the earlier interval; a row with no valid interval against anybody gets +inf, -1, NaN.
+ * threshold > 0: every pair i < j (i among the rows) whose minimum over all intervals is <= threshold is appended to
+ * pairs [max_pairs][4] = (i, j, distance, time), in no particular order; *n_pairs is the number of such pairs even when it
+ * exceeds max_pairs (the list then holds some max_pairs of them).  threshold <= 0: no list, *n_pairs = 0 (n_pairs may be NULL).
+ * M < 2, S < 1, T1 <= T0, max_pairs < 0, rows outside 0 .. S-1: MPCX_E_BADARG, nothing enqueued.
+ * The host variant takes eph in host memory; the _dev variant takes device pointers throughout (n_pairs too) and a workspace of
+ * mpcx_conjunction_workspace_bytes(S, M) bytes (the instant-major copy of eph and the partial minima; contents unspecified on
+ * entry and exit).  Results do not depend on the block of rows a row is computed in.
+ *
+ * mpcx_conjunction_screen_traj: both steps in one call, from trajectories (host pointers) to results; eph stays in HBM.
+ * status [S] (may be NULL): the ephemeris'.  Same bits as the two calls.
+ */
+int mpcx_ephemeris_batch(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
+                         const double *span, int M, double T0, double T1, double *eph, int32_t *status);
+int mpcx_ephemeris_batch_dev(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
+                             const double *span, int M, double T0, double T1, double *eph, int32_t *status, void *stream);
+size_t mpcx_conjunction_workspace_bytes(int S, int M);
+int mpcx_conjunction_screen(mpcx_ctx *ctx, int S, int M, const double *eph, double T0, double T1, int row0, int nrows,
+                            double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs,
+                            int64_t *n_pairs);
+int mpcx_conjunction_screen_dev(mpcx_ctx *ctx, int S, int M, const double *eph, double T0, double T1, int row0, int nrows,
+                                double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs,
+                                int64_t *n_pairs, void *workspace, void *stream);
+int mpcx_conjunction_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
+                                 const double *span, int M, double T0, double T1, int row0, int nrows, double threshold,
+                                 int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs, int64_t *n_pairs,
+                                 int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

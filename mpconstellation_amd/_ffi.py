@@ -26,6 +26,7 @@ NTERM_SCALARS = 8
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 _vp = C.c_void_p
 
 
@@ -105,6 +106,16 @@ _SIGS = {
                                         C.c_double, _po, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _ip, C.c_double, C.c_double, C.c_int, C.c_int,
                                         C.c_double, _dp, _ip]),
     "mpcx_resample_sequence_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    # conjunction screening (the constellation on one clock, all-pairs closest approach)
+    "mpcx_ephemeris_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, _dp, _ip]),
+    "mpcx_ephemeris_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mpcx_conjunction_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mpcx_conjunction_screen": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
+                                          _dp, _ip, _dp, _dp, _lp]),
+    "mpcx_conjunction_screen_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mpcx_conjunction_screen_traj": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                               C.c_double, C.c_int, _dp, _ip, _dp, _dp, _lp, _ip]),
 }
 
 

@@ -1,0 +1,163 @@
+"""Conjunction screening: the constellation on one clock, and the closest approach of every pair of satellites on it.
+
+Everything else in the package works on one satellite in its own units (SatelliteScale: length = its start radius, time = its
+own orbital period), so node k of two trajectories is two different instants in two different lengths, and nothing looks at two
+satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip):
+
+  common_clock   resamples trajectories at M common instants in metres and m/s (cubic Hermite on the node positions and velocities);
+  screen         the closest approach of every ordered pair over every grid interval -- per satellite the nearest other one, how
+                 near and when, and with a threshold the list of pairs that come closer than it.
+
+The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
+import numpy as np
+
+from . import _ffi
+
+DEFAULT_MAX_PAIRS = 65536
+
+
+class ConjunctionResult:
+    """dmin (S,) metres, partner (S,) int32 (-1: none), tca (S,) seconds: each satellite's closest approach to any other one.
+    pairs (n, 4) float64 rows (i, j, distance, time) with i < j, sorted by (i, j): the pairs at or below the threshold -- at most
+    max_pairs of them; n_pairs_total is how many there are.  status (S,) int32 or None: the ephemeris' MPCX_ST_* per satellite
+    when the screen started from trajectories."""
+
+    def __init__(self, dmin, partner, tca, pairs, n_pairs_total, status=None):
+        self.dmin, self.partner, self.tca, self.pairs, self.n_pairs_total, self.status = dmin, partner, tca, pairs, int(n_pairs_total), status
+
+    def __repr__(self):
+        return f"ConjunctionResult(S={len(self.dmin)}, pairs={len(self.pairs)} of {self.n_pairs_total})"
+
+
+def sort_pairs(pairs):
+    """rows (i, j, d, t) sorted by (i, j)"""
+    pairs = np.asarray(pairs, dtype=np.float64).reshape(-1, 4)
+    return pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+
+
+def _check_grid(M, T0, T1):
+    if int(M) != M or M < 2:
+        raise ValueError(f"M: need an integer >= 2 common instants, got {M}")
+    if not (np.isfinite(T0) and np.isfinite(T1) and T1 > T0):
+        raise ValueError(f"need finite T0 < T1, got [{T0}, {T1}]")
+    return int(M), float(T0), float(T1)
+
+
+def _check_trajectories(Y, units, span, ns):
+    Y = _ffi.as_f64(Y)
+    if Y.ndim != 3 or Y.shape[1] != 7 or Y.shape[0] < 1 or Y.shape[2] < 1:
+        raise ValueError(f"Y: expected (S, 7, n) normalised trajectories, got {Y.shape}")
+    S = Y.shape[0]
+    units, span = _ffi.as_f64(units), _ffi.as_f64(span)
+    if units.shape != (S, 2):
+        raise ValueError(f"units: expected ({S}, 2) = (length unit in m, time unit in s) per satellite, got {units.shape}")
+    if span.shape != (S, 2):
+        raise ValueError(f"span: expected ({S}, 2) = physical times of the first and last node per satellite, got {span.shape}")
+    if ns is not None and np.shape(ns) != (S,):
+        raise ValueError(f"ns: expected ({S},) node counts, got {np.shape(ns)}")
+    return Y, units, span, _ffi.counts(ns, S)
+
+
+def common_clock(Y, units, span, M, T0, T1, ns=None, device=0, return_status=False):
+    """Y (S, 7, n) normalised trajectories (ns (S,): nodes in use per satellite, None: all n), units (S, 2) each satellite's length
+    unit (m) and time unit (s), span (S, 2) the physical times (s) of its first and last node (uniform in between) -> eph (S, 6, M):
+    position (m) and velocity (m/s) at linspace(T0, T1, M).  Instants outside a satellite's span are NaN; a satellite with fewer than
+    two nodes or an empty span is NaN throughout (status MPCX_ST_BADK = 9; return_status=True returns (eph, status))."""
+    M, T0, T1 = _check_grid(M, T0, T1)
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, n = Y.shape
+    eph = _ffi.result_pool.take((S, 6, M))
+    status = np.zeros(S, dtype=np.int32)
+    _ffi.call("mpcx_ephemeris_batch", _ffi.context(device), S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), M, T0, T1,
+              _ffi.dptr(eph), _ffi.iptr(status))
+    return (eph, status) if return_status else eph
+
+
+def screen(eph=None, T0=None, T1=None, threshold=None, max_pairs=DEFAULT_MAX_PAIRS, device=0, devices=None, *, Y=None, units=None,
+           span=None, ns=None, M=None):
+    """The closest approach of every pair on the common grid linspace(T0, T1, M).  Either eph (S, 6, M) from common_clock, or the
+    trajectories Y, units, span [, ns] and M (the fused call: the ephemeris never leaves the device).  threshold (metres; None or
+    <= 0: no list) and max_pairs: ConjunctionResult.pairs.  devices=[d0, d1, ...]: contiguous blocks of ROWS on several devices
+    (sharding.sharded_call); every device holds the whole ephemeris, results are written in place, the bits are those of one device."""
+    if (eph is None) == (Y is None):
+        raise ValueError("screen: give either eph or the trajectories Y, units, span, M")
+    if T0 is None or T1 is None:
+        raise ValueError("screen: T0 and T1 (the common grid's first and last instant, seconds) are required")
+    if int(max_pairs) != max_pairs or max_pairs < 0:
+        raise ValueError(f"max_pairs: need an integer >= 0, got {max_pairs}")
+    thr = 0.0 if threshold is None else float(threshold)
+    if not thr == thr:
+        raise ValueError("threshold is NaN")
+    if eph is not None:
+        eph = _ffi.as_f64(eph)
+        if eph.ndim != 3 or eph.shape[1] != 6 or eph.shape[0] < 1:
+            raise ValueError(f"eph: expected (S, 6, M), got {eph.shape}")
+        if M is not None and int(M) != eph.shape[2]:
+            raise ValueError(f"M = {M} but eph has {eph.shape[2]} instants")
+        S, M = eph.shape[0], eph.shape[2]
+        src = (eph,)
+    else:
+        if M is None:
+            raise ValueError("screen: M (the number of common instants) is required with trajectories")
+        src = _check_trajectories(Y, units, span, ns)
+        S = src[0].shape[0]
+    M, T0, T1 = _check_grid(M, T0, T1)
+    out = dict(dmin=np.empty(S), partner=np.empty(S, dtype=np.int32), tca=np.empty(S))
+    how = dict(src=src, S=S, M=M, T0=T0, T1=T1, thr=thr, max_pairs=int(max_pairs) if thr > 0.0 else 0)
+    rows = np.arange(S)
+    if devices is not None and len(devices) > 1:
+        from .sharding import sharded_call
+        parts = sharded_call(_screen_call, devices, [rows], out, **how)
+    else:
+        if devices is not None and len(devices) == 1:
+            device = int(devices[0])
+        parts = [_screen_call(rows, device=device, slot=0, out=out, **how)]
+    pairs = sort_pairs(np.concatenate([p for p, _, _ in parts]))[:int(max_pairs)]
+    status = parts[0][2]
+    return ConjunctionResult(out["dmin"], out["partner"], out["tca"], pairs, sum(n for _, n, _ in parts), status)
+
+
+def _screen_call(rows, *, device, slot, out, src, S, M, T0, T1, thr, max_pairs):
+    """One block of rows on context (device, slot): dmin, partner, tca into `out` (the block's views); returns the block's pairs
+    (those whose smaller index is one of its rows), how many there are, and the ephemeris status (fused call) or None."""
+    row0, nrows = int(rows[0]), len(rows)
+    pairs = np.zeros((max_pairs, 4))
+    n_pairs = np.zeros(1, dtype=np.int64)
+    tail = (T0, T1, row0, nrows, thr, max_pairs, _ffi.dptr(out["dmin"]), _ffi.iptr(out["partner"]), _ffi.dptr(out["tca"]), _ffi.dptr(pairs),
+            n_pairs.ctypes.data_as(_ffi._lp))
+    ctx = _ffi.context(device, slot)
+    status = None
+    if len(src) == 1:
+        _ffi.call("mpcx_conjunction_screen", ctx, S, M, _ffi.dptr(src[0]), *tail)
+    else:
+        Y, units, span, ns = src
+        status = np.zeros(S, dtype=np.int32)
+        _ffi.call("mpcx_conjunction_screen_traj", ctx, S, Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), M,
+                  *tail, _ffi.iptr(status))
+    n = int(n_pairs[0])
+    return pairs[:min(n, max_pairs)], n, status
+
+
+def combine(results):
+    """Several screens of the same satellites over consecutive time windows (the flown segments) as one: per row the smallest
+    distance, of equal ones the smaller partner, then the earlier window; per pair its smallest distance, the earlier window on a
+    tie.  n_pairs_total counts the pairs of the union of the lists (exact when no window's list was cut off at max_pairs)."""
+    results = list(results)
+    if not results:
+        raise ValueError("combine: nothing to combine")
+    dmin, partner, tca = results[0].dmin.copy(), results[0].partner.copy(), results[0].tca.copy()
+    for r in results[1:]:
+        none = partner < 0
+        jr = np.where(r.partner < 0, np.iinfo(np.int32).max, r.partner)
+        jb = np.where(none, np.iinfo(np.int32).max, partner)
+        better = (r.partner >= 0) & (none | (r.dmin < dmin) | ((r.dmin == dmin) & (jr < jb)))
+        dmin[better], partner[better], tca[better] = r.dmin[better], r.partner[better], r.tca[better]
+    best = {}
+    for r in results:
+        for i, j, d, t in r.pairs:
+            key = (int(i), int(j))
+            if key not in best or d < best[key][0]:
+                best[key] = (d, t)
+    pairs = sort_pairs([(i, j, d, t) for (i, j), (d, t) in best.items()])
+    total = max([len(pairs)] + [r.n_pairs_total for r in results])
+    return ConjunctionResult(dmin, partner, tca, pairs, total)

@@ -89,6 +89,7 @@ class ConstellationMPC:
         # (satellite_scale.py:46-100: r / r0, v / v0, m / m0 and back)
         self._f = np.array([[sc._r0, sc._v0, sc._m0] for sc in self.scales]).reshape(len(self.sats), 3)
         self._seg_y, self._seg_t, self._sim_cache = [], [], None       # flown segments (S,7,n) / (n,), and the dict view of them
+        self._seg_tf = []                 # every flown segment's length in each satellite's own time unit (screen: its physical span)
         self.last_status = None           # (scp_iterations, S): every solve's MPCX_ST_* code of the last update
         self.last_iters = None            # ... and its interior-point iteration count
         self.plan_tf, self.plan_K = None, None
@@ -239,11 +240,53 @@ class ConstellationMPC:
             sat.update_state_vector(end[i])
         if self._seg_t:
             t = t + self._seg_t[-1][-1] * tf + 0.0000001                  # simulator.py:69-76
-        self._seg_y.append(y); self._seg_t.append(t); self._sim_cache = None
+        self._seg_y.append(y); self._seg_t.append(t); self._seg_tf.append(float(tf)); self._sim_cache = None
 
     def run_segments(self, tf=1, num_segments=1):
         for _ in range(num_segments):
             self.run_segment(tf=tf / float(num_segments))
+
+    # ---- conjunction screening: all satellites on one clock (conjunction.py) ----
+    def _screen_windows(self, what="flown", samples_per_node=4, T0=None, T1=None):
+        """What `screen` hands to conjunction.screen, one dict per window -- Y, ns, units, span, M, T0, T1: every satellite's
+        units are its scale's length and time unit; a flown segment q spans (sum of the earlier segments' tf, that sum + its own
+        tf) times the satellite's time unit, a plan (0, plan_tf) times it with plan_K nodes in use.  [T0, T1], unless given, is the
+        intersection of the satellites' spans; the grid has samples_per_node intervals per node interval of the longest row."""
+        if int(samples_per_node) != samples_per_node or samples_per_node < 1:
+            raise ValueError(f"samples_per_node: need an integer >= 1, got {samples_per_node}")
+        units = np.array([[sc.units["length"], sc.units["time"]] for sc in self.scales], dtype=np.float64)
+        if what == "flown":
+            if not self._seg_y:
+                raise ValueError("screen(what='flown'): no segment has been flown yet (run_segment)")
+            t_end = np.cumsum(self._seg_tf)
+            rows = [(y, None, np.outer(units[:, 1], [t1 - tf, t1])) for y, tf, t1 in zip(self._seg_y, self._seg_tf, t_end)]
+        elif what == "plan":
+            if self._plan is None:
+                raise ValueError("screen(what='plan'): there is no plan yet (update)")
+            rows = [(self._plan[0], np.asarray(self.plan_K, dtype=np.int32),
+                     np.column_stack([np.zeros(len(self.sats)), np.asarray(self.plan_tf) * units[:, 1]]))]
+        else:
+            raise ValueError(f"screen: what = {what!r}, expected 'flown' or 'plan'")
+        out = []
+        for Y, ns, span in rows:
+            t0 = float(span[:, 0].max()) if T0 is None else float(T0)
+            t1 = float(span[:, 1].min()) if T1 is None else float(T1)
+            if not t1 > t0:
+                raise ValueError(f"screen: the satellites' spans have no common interval ([{t0}, {t1}] s)")
+            n = Y.shape[2] if ns is None else int(ns.max())
+            out.append(dict(Y=Y, ns=ns, units=units, span=span, M=int(samples_per_node) * (max(n, 2) - 1) + 1, T0=t0, T1=t1))
+        return out
+
+    def screen(self, threshold_m, samples_per_node=4, what="flown", T0=None, T1=None, max_pairs=None):
+        """Closest approaches inside the constellation (conjunction.screen; distances in metres, times in seconds since the start
+        of the first flown segment, or of the plan): what='flown' screens every flown segment on its own common grid and combines
+        them (conjunction.combine); what='plan' the last plan.  Returns a ConjunctionResult: dmin, partner, tca per satellite and
+        the pairs at or below threshold_m."""
+        from . import conjunction as cj
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        res = [cj.screen(threshold=threshold_m, device=self.device, devices=self.devices, **w, **kw)
+               for w in self._screen_windows(what, samples_per_node, T0, T1)]
+        return res[0] if len(res) == 1 else cj.combine(res)
 
     @staticmethod
     def _check(status):
