@@ -562,6 +562,44 @@ int mpcx_conjunction_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_t *ns,
                                  int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs, int64_t *n_pairs,
                                  int32_t *status);
 
+/*
+ * Conjunction screening against a catalogue of foreign objects: rows are the constellation's satellites (eph [S][6][M]), columns
+ * the objects of a catalogue (cat [D][6][M]: debris, other operators' satellites), both on the same grid linspace(T0, T1, M) -- two
+ * mpcx_ephemeris_batch calls with the same M, T0, T1.  The rectangle S x D is computed, not the square of the union.
+ *
+ * mpcx_conjunction_cross_screen: for the rows i = row0 .. row0 + nrows - 1 against every object j = 0 .. D-1, over every grid
+ * interval, skipping an interval where either of the two has a NaN among the six values of either end.  d = p_cat - p_sat and
+ * w = v_cat - v_sat at the two ends, then the chord, the Newton steps and the interval's distance and time exactly as in
+ * mpcx_conjunction_screen: the pair (i, j) gets the bits that screen gives the pair (i, S + j) of the union [eph; cat].
+ * Per row: dmin [nrows] (m), partner [nrows] (an index into the CATALOGUE; -1: none), tca [nrows] (s) -- the smallest distance, of
+ * equal ones the smaller j, then the earlier interval; a row with no valid interval against any object gets +inf, -1, NaN; an
+ * object that is never on the grid is never a partner.
+ * threshold > 0: every pair (i, j), i among the rows, whose minimum over all intervals is <= threshold is appended once to
+ * pairs [max_pairs][4] = (i, j, distance, time), in no particular order; *n_pairs is the number of such pairs even when it
+ * exceeds max_pairs.  threshold <= 0: no list, *n_pairs = 0 (n_pairs may be NULL).
+ * M < 2, S < 1, D < 1, T1 <= T0, max_pairs < 0, rows outside 0 .. S-1: MPCX_E_BADARG, nothing enqueued.
+ * The host variant takes eph and cat in host memory; the _dev variant takes device pointers throughout (n_pairs too) and a
+ * workspace of mpcx_conjunction_cross_workspace_bytes(S, D, M) bytes (0 for S < 1, D < 1 or M < 2; the instant-major copies and
+ * the partial minima; contents unspecified on entry and exit).  Results do not depend on the block of rows a row is computed in.
+ *
+ * mpcx_conjunction_cross_screen_traj: everything in one call, from trajectories (host pointers; the constellation's n, ns, Y, units,
+ * span and the catalogue's own cat_n, cat_ns, cat_Y, cat_units, cat_span, as mpcx_ephemeris_batch takes them) to results; neither
+ * ephemeris leaves HBM.  status [S], cat_status [D] (each may be NULL): the two ephemerides'.  Same bits as the three calls.
+ */
+size_t mpcx_conjunction_cross_workspace_bytes(int S, int D, int M);
+int mpcx_conjunction_cross_screen(mpcx_ctx *ctx, int S, int D, int M, const double *eph, const double *cat, double T0, double T1,
+                                  int row0, int nrows, double threshold, int max_pairs, double *dmin, int32_t *partner,
+                                  double *tca, double *pairs, int64_t *n_pairs);
+int mpcx_conjunction_cross_screen_dev(mpcx_ctx *ctx, int S, int D, int M, const double *eph, const double *cat, double T0,
+                                      double T1, int row0, int nrows, double threshold, int max_pairs, double *dmin,
+                                      int32_t *partner, double *tca, double *pairs, int64_t *n_pairs, void *workspace,
+                                      void *stream);
+int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
+                                       const double *span, int D, int cat_n, const int32_t *cat_ns, const double *cat_Y,
+                                       const double *cat_units, const double *cat_span, int M, double T0, double T1, int row0,
+                                       int nrows, double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca,
+                                       double *pairs, int64_t *n_pairs, int32_t *status, int32_t *cat_status);
+
 #ifdef __cplusplus
 }
 #endif

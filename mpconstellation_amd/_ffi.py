@@ -116,6 +116,15 @@ _SIGS = {
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpcx_conjunction_screen_traj": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                                C.c_double, C.c_int, _dp, _ip, _dp, _dp, _lp, _ip]),
+    # the constellation against a catalogue of foreign objects (rows x columns instead of the union's square)
+    "mpcx_conjunction_cross_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_conjunction_cross_screen": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double,
+                                                C.c_int, _dp, _ip, _dp, _dp, _lp]),
+    "mpcx_conjunction_cross_screen_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                    C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mpcx_conjunction_cross_screen_traj": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int,
+                                                     C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _lp,
+                                                     _ip, _ip]),
 }
 
 

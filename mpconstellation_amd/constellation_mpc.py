@@ -288,6 +288,23 @@ class ConstellationMPC:
                for w in self._screen_windows(what, samples_per_node, T0, T1)]
         return res[0] if len(res) == 1 else cj.combine(res)
 
+    def screen_against(self, catalogue, threshold_m, samples_per_node=4, what="flown", T0=None, T1=None, max_pairs=None):
+        """Closest approaches of the constellation to a catalogue of foreign objects (conjunction.screen_against).  catalogue =
+        (Y, units, span) or (Y, units, span, ns): the objects' trajectories in their own units, span in the seconds of `screen`'s
+        times (since the start of the first flown segment, or of the plan).  The windows are `screen`'s: the constellation's spans
+        alone decide T0 and T1; an object outside its span there is NaN and is ignored.  Flown windows are combined
+        (conjunction.combine).  Returns a ConjunctionResult: dmin, partner (a catalogue index), tca per satellite and the pairs
+        (satellite, object) at or below threshold_m; status and cat_status are the ephemerides' when there is one window (a plan,
+        one flown segment) and None when several were combined."""
+        from . import conjunction as cj
+        if len(catalogue) not in (3, 4):
+            raise ValueError(f"catalogue: expected (Y, units, span) or (Y, units, span, ns), got {len(catalogue)} items")
+        cat = dict(zip(("cat_Y", "cat_units", "cat_span", "cat_ns"), catalogue))
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        res = [cj.screen_against(threshold=threshold_m, device=self.device, devices=self.devices, **w, **cat, **kw)
+               for w in self._screen_windows(what, samples_per_node, T0, T1)]
+        return res[0] if len(res) == 1 else cj.combine(res)
+
     @staticmethod
     def _check(status):
         if (status == 1).any():
