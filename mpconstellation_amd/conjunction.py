@@ -2,13 +2,13 @@
 
 Everything else in the package works on one satellite in its own units (SatelliteScale: length = its start radius, time = its
 own orbital period), so node k of two trajectories is two different instants in two different lengths, and nothing looks at two
-satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip):
+satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kernel and one host path behind both screens):
 
   common_clock   resamples trajectories at M common instants in metres and m/s (cubic Hermite on the node positions and velocities);
   screen         the closest approach of every ordered pair over every grid interval -- per satellite the nearest other one, how
                  near and when, and with a threshold the list of pairs that come closer than it;
   screen_against the same for a constellation against a catalogue of foreign objects (debris, other operators' satellites): the
-                 rectangle satellites x objects (csrc/conjunction_cross.hip), not the square of the union;
+                 rectangle satellites x objects, not the square of the union;
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
@@ -82,6 +82,28 @@ def common_clock(Y, units, span, M, T0, T1, ns=None, device=0, return_status=Fal
     return (eph, status) if return_status else eph
 
 
+def _check_options(who, T0, T1, threshold, max_pairs):
+    """the options screen and screen_against share -> the threshold as the library takes it (0.0: no list)"""
+    if T0 is None or T1 is None:
+        raise ValueError(f"{who}: T0 and T1 (the common grid's first and last instant, seconds) are required")
+    if int(max_pairs) != max_pairs or max_pairs < 0:
+        raise ValueError(f"max_pairs: need an integer >= 0, got {max_pairs}")
+    thr = 0.0 if threshold is None else float(threshold)
+    if not thr == thr:
+        raise ValueError("threshold is NaN")
+    return thr
+
+
+def _check_ephemeris(eph, M, name="eph", count="S"):
+    """an (N, 6, M) ephemeris argument; M: what the caller gave beside it, or None"""
+    eph = _ffi.as_f64(eph)
+    if eph.ndim != 3 or eph.shape[1] != 6 or eph.shape[0] < 1:
+        raise ValueError(f"{name}: expected ({count}, 6, M), got {eph.shape}")
+    if M is not None and int(M) != eph.shape[2]:
+        raise ValueError(f"M = {M} but {name} has {eph.shape[2]} instants")
+    return eph
+
+
 def screen(eph=None, T0=None, T1=None, threshold=None, max_pairs=DEFAULT_MAX_PAIRS, device=0, devices=None, *, Y=None, units=None,
            span=None, ns=None, M=None):
     """The closest approach of every pair on the common grid linspace(T0, T1, M).  Either eph (S, 6, M) from common_clock, or the
@@ -90,61 +112,15 @@ def screen(eph=None, T0=None, T1=None, threshold=None, max_pairs=DEFAULT_MAX_PAI
     (sharding.sharded_call); every device holds the whole ephemeris, results are written in place, the bits are those of one device."""
     if (eph is None) == (Y is None):
         raise ValueError("screen: give either eph or the trajectories Y, units, span, M")
-    if T0 is None or T1 is None:
-        raise ValueError("screen: T0 and T1 (the common grid's first and last instant, seconds) are required")
-    if int(max_pairs) != max_pairs or max_pairs < 0:
-        raise ValueError(f"max_pairs: need an integer >= 0, got {max_pairs}")
-    thr = 0.0 if threshold is None else float(threshold)
-    if not thr == thr:
-        raise ValueError("threshold is NaN")
+    thr = _check_options("screen", T0, T1, threshold, max_pairs)
     if eph is not None:
-        eph = _ffi.as_f64(eph)
-        if eph.ndim != 3 or eph.shape[1] != 6 or eph.shape[0] < 1:
-            raise ValueError(f"eph: expected (S, 6, M), got {eph.shape}")
-        if M is not None and int(M) != eph.shape[2]:
-            raise ValueError(f"M = {M} but eph has {eph.shape[2]} instants")
-        S, M = eph.shape[0], eph.shape[2]
-        src = (eph,)
+        eph = _check_ephemeris(eph, M)
+        src, M = (eph,), eph.shape[2]
     else:
         if M is None:
             raise ValueError("screen: M (the number of common instants) is required with trajectories")
         src = _check_trajectories(Y, units, span, ns)
-        S = src[0].shape[0]
-    M, T0, T1 = _check_grid(M, T0, T1)
-    out = dict(dmin=np.empty(S), partner=np.empty(S, dtype=np.int32), tca=np.empty(S))
-    how = dict(src=src, S=S, M=M, T0=T0, T1=T1, thr=thr, max_pairs=int(max_pairs) if thr > 0.0 else 0)
-    rows = np.arange(S)
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        parts = sharded_call(_screen_call, devices, [rows], out, **how)
-    else:
-        if devices is not None and len(devices) == 1:
-            device = int(devices[0])
-        parts = [_screen_call(rows, device=device, slot=0, out=out, **how)]
-    pairs = sort_pairs(np.concatenate([p for p, _, _ in parts]))[:int(max_pairs)]
-    status = parts[0][2]
-    return ConjunctionResult(out["dmin"], out["partner"], out["tca"], pairs, sum(n for _, n, _ in parts), status)
-
-
-def _screen_call(rows, *, device, slot, out, src, S, M, T0, T1, thr, max_pairs):
-    """One block of rows on context (device, slot): dmin, partner, tca into `out` (the block's views); returns the block's pairs
-    (those whose smaller index is one of its rows), how many there are, and the ephemeris status (fused call) or None."""
-    row0, nrows = int(rows[0]), len(rows)
-    pairs = np.zeros((max_pairs, 4))
-    n_pairs = np.zeros(1, dtype=np.int64)
-    tail = (T0, T1, row0, nrows, thr, max_pairs, _ffi.dptr(out["dmin"]), _ffi.iptr(out["partner"]), _ffi.dptr(out["tca"]), _ffi.dptr(pairs),
-            n_pairs.ctypes.data_as(_ffi._lp))
-    ctx = _ffi.context(device, slot)
-    status = None
-    if len(src) == 1:
-        _ffi.call("mpcx_conjunction_screen", ctx, S, M, _ffi.dptr(src[0]), *tail)
-    else:
-        Y, units, span, ns = src
-        status = np.zeros(S, dtype=np.int32)
-        _ffi.call("mpcx_conjunction_screen_traj", ctx, S, Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), M,
-                  *tail, _ffi.iptr(status))
-    n = int(n_pairs[0])
-    return pairs[:min(n, max_pairs)], n, status
+    return _screen(src, None, M, T0, T1, thr, max_pairs, device, devices)
 
 
 def screen_against(eph=None, cat_eph=None, T0=None, T1=None, threshold=None, max_pairs=DEFAULT_MAX_PAIRS, device=0, devices=None, *,
@@ -163,67 +139,64 @@ def screen_against(eph=None, cat_eph=None, T0=None, T1=None, threshold=None, max
                          "trajectories; put the one given as trajectories on the grid with common_clock first")
     if given_eph == given_traj:
         raise ValueError("screen_against: give either eph and cat_eph, or the trajectories Y, units, span and cat_Y, cat_units, cat_span with M")
-    if T0 is None or T1 is None:
-        raise ValueError("screen_against: T0 and T1 (the common grid's first and last instant, seconds) are required")
-    if int(max_pairs) != max_pairs or max_pairs < 0:
-        raise ValueError(f"max_pairs: need an integer >= 0, got {max_pairs}")
-    thr = 0.0 if threshold is None else float(threshold)
-    if not thr == thr:
-        raise ValueError("threshold is NaN")
+    thr = _check_options("screen_against", T0, T1, threshold, max_pairs)
     if given_eph:
         if eph is None or cat_eph is None:
             raise ValueError("screen_against: eph and cat_eph are both required")
-        eph, cat_eph = _ffi.as_f64(eph), _ffi.as_f64(cat_eph)
-        if eph.ndim != 3 or eph.shape[1] != 6 or eph.shape[0] < 1:
-            raise ValueError(f"eph: expected (S, 6, M), got {eph.shape}")
-        if cat_eph.ndim != 3 or cat_eph.shape[1] != 6 or cat_eph.shape[0] < 1:
-            raise ValueError(f"cat_eph: expected (D, 6, M), got {cat_eph.shape}")
+        eph, cat_eph = _check_ephemeris(eph, M), _check_ephemeris(cat_eph, None, "cat_eph", "D")
         if cat_eph.shape[2] != eph.shape[2]:
             raise ValueError(f"eph has {eph.shape[2]} instants but cat_eph {cat_eph.shape[2]}: both must be on the same grid")
-        if M is not None and int(M) != eph.shape[2]:
-            raise ValueError(f"M = {M} but eph has {eph.shape[2]} instants")
-        S, D, M = eph.shape[0], cat_eph.shape[0], eph.shape[2]
-        rows_src, cat_src = (eph,), (cat_eph,)
+        src, cat, M = (eph,), (cat_eph,), eph.shape[2]
     else:
         if Y is None or cat_Y is None:
             raise ValueError("screen_against: Y and cat_Y are both required")
         if M is None:
             raise ValueError("screen_against: M (the number of common instants) is required with trajectories")
-        rows_src, cat_src = _check_trajectories(Y, units, span, ns), _check_trajectories(cat_Y, cat_units, cat_span, cat_ns, "cat_")
-        S, D = rows_src[0].shape[0], cat_src[0].shape[0]
+        src, cat = _check_trajectories(Y, units, span, ns), _check_trajectories(cat_Y, cat_units, cat_span, cat_ns, "cat_")
+    return _screen(src, cat, M, T0, T1, thr, max_pairs, device, devices)
+
+
+def _screen(src, cat, M, T0, T1, thr, max_pairs, device, devices):
+    """Both screens behind their argument checks.  src, cat: the rows' and the columns' side, each (eph,) or (Y, units, span, ns);
+    cat None: all pairs of src.  Blocks of rows go to the devices, their lists are joined and sorted."""
     M, T0, T1 = _check_grid(M, T0, T1)
+    S = src[0].shape[0]
     out = dict(dmin=np.empty(S), partner=np.empty(S, dtype=np.int32), tca=np.empty(S))
-    how = dict(src=rows_src, cat=cat_src, S=S, D=D, M=M, T0=T0, T1=T1, thr=thr, max_pairs=int(max_pairs) if thr > 0.0 else 0)
+    how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, thr=thr, max_pairs=int(max_pairs) if thr > 0.0 else 0)
     rows = np.arange(S)
     if devices is not None and len(devices) > 1:
         from .sharding import sharded_call
-        parts = sharded_call(_screen_against_call, devices, [rows], out, **how)
+        parts = sharded_call(_screen_call, devices, [rows], out, **how)
     else:
         if devices is not None and len(devices) == 1:
             device = int(devices[0])
-        parts = [_screen_against_call(rows, device=device, slot=0, out=out, **how)]
-    pairs = sort_pairs(np.concatenate([p for p, _, _, _ in parts]))[:int(max_pairs)]
-    return ConjunctionResult(out["dmin"], out["partner"], out["tca"], pairs, sum(n for _, n, _, _ in parts), parts[0][2], parts[0][3])
+        parts = [_screen_call(rows, device=device, slot=0, out=out, **how)]
+    pairs = sort_pairs(np.concatenate([p for p, _, _ in parts]))[:int(max_pairs)]
+    return ConjunctionResult(out["dmin"], out["partner"], out["tca"], pairs, sum(n for _, n, _ in parts), *parts[0][2])
 
 
-def _screen_against_call(rows, *, device, slot, out, src, cat, S, D, M, T0, T1, thr, max_pairs):
-    """One block of rows against the whole catalogue on context (device, slot): dmin, partner, tca into `out` (the block's views);
-    returns the block's pairs, how many there are, and the two ephemeris statuses (fused call) or None, None."""
+def _screen_call(rows, *, device, slot, out, src, cat, M, T0, T1, thr, max_pairs):
+    """One block of rows against all columns on context (device, slot): dmin, partner, tca into `out` (the block's views); returns
+    the block's pairs (all pairs: those whose smaller index is one of its rows), how many there are, and the ephemeris statuses
+    (status, cat_status) of the fused calls, None where there is none."""
     row0, nrows = int(rows[0]), len(rows)
     pairs = np.zeros((max_pairs, 4))
     n_pairs = np.zeros(1, dtype=np.int64)
     tail = (T0, T1, row0, nrows, thr, max_pairs, _ffi.dptr(out["dmin"]), _ffi.iptr(out["partner"]), _ffi.dptr(out["tca"]), _ffi.dptr(pairs),
             n_pairs.ctypes.data_as(_ffi._lp))
     ctx = _ffi.context(device, slot)
-    status = cat_status = None
+    name, sides = ("mpcx_conjunction_screen", [src]) if cat is None else ("mpcx_conjunction_cross_screen", [src, cat])
+    counts = [side[0].shape[0] for side in sides]                    # S [, D]
+    statuses = [None, None]
     if len(src) == 1:
-        _ffi.call("mpcx_conjunction_cross_screen", ctx, S, D, M, _ffi.dptr(src[0]), _ffi.dptr(cat[0]), *tail)
+        _ffi.call(name, ctx, *counts, M, *[_ffi.dptr(eph) for eph, in sides], *tail)
     else:
-        traj = lambda Y, units, span, ns: (Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span))
-        status, cat_status = np.zeros(S, dtype=np.int32), np.zeros(D, dtype=np.int32)
-        _ffi.call("mpcx_conjunction_cross_screen_traj", ctx, S, *traj(*src), D, *traj(*cat), M, *tail, _ffi.iptr(status), _ffi.iptr(cat_status))
+        traj = [a for N, (Y, units, span, ns) in zip(counts, sides)
+                for a in (N, Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span))]
+        statuses[:len(sides)] = [np.zeros(N, dtype=np.int32) for N in counts]
+        _ffi.call(name + "_traj", ctx, *traj, M, *tail, *[_ffi.iptr(st) for st in statuses[:len(sides)]])
     n = int(n_pairs[0])
-    return pairs[:min(n, max_pairs)], n, status, cat_status
+    return pairs[:min(n, max_pairs)], n, statuses
 
 
 def catalogue_trajectories(position_m, velocity_m_s, T0, T1, n, include_J2=True, device=0, devices=None):

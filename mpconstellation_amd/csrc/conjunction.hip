@@ -1,22 +1,40 @@
-// conjunction.hip -- the constellation on one clock, and the all-pairs closest approach on it (include/mpcx.h: mpcx_ephemeris_*,
-// mpcx_conjunction_*).  Every other kernel of the library works on one satellite in its own units (SatelliteScale: length = its
-// start radius, time = its own period), so node k of two satellites is two different instants in two different lengths.  Here
-//   ephemeris_kernel     resamples every trajectory at M common instants in metres and m/s: cubic Hermite in physical time on the
-//                        node positions and velocities (the state carries the velocity: C1, error h_n^4 / 384 max |p''''|);
-//   conjunction_kernel   for every ordered pair (i, j != i) and every grid interval the closest approach of the two Hermite
-//                        arcs -- chord minimum, then three Newton steps on d . d' -- reduced to one (distance, partner, time) per
-//                        row and, with a threshold, to a list of the pairs i < j that come closer than it.
-// Arithmetic that both orderings of a pair share: the difference is always (higher index) - (lower index), so (i, j) and (j, i)
-// run the same operations on the same operands and get the same bits; every reduction is a minimum under a total order
-// (distance, then partner index, then interval), so nothing depends on tiles, grid dimensions or device count.
-#include "conjunction_common.hpp"
+// conjunction.hip -- the constellation on one clock, and the closest approach of pairs on it (include/mpcx.h: mpcx_ephemeris_*,
+// mpcx_conjunction_*, mpcx_conjunction_cross_*).  Every other kernel of the library works on one satellite in its own units
+// (SatelliteScale: length = its start radius, time = its own period), so node k of two satellites is two different instants in
+// two different lengths.  Here
+//   ephemeris_kernel   resamples every trajectory at M common instants in metres and m/s: cubic Hermite in physical time on the
+//                      node positions and velocities (the state carries the velocity: C1, error h_n^4 / 384 max |p''''|);
+//   screen_kernel      for every (row, column) pair and every grid interval the closest approach of the two Hermite arcs -- chord
+//                      minimum, then three Newton steps on d . d' -- reduced to one (distance, partner, time) per row and, with a
+//                      threshold, to a list of the pairs that come closer than it.
+// Two screens launch it.  All pairs of one constellation (SELF): rows and columns are the same S satellites, the full square of
+// ordered pairs (i, j != i) is computed, the list holds the pairs i < j.  A constellation against a catalogue of foreign objects
+// (cross): rows are the S satellites, columns the D objects, the rectangle S x D is computed and not the square (S + D)^2 of the
+// union, the list holds every pair.
+// One arithmetic for a pair whoever looks at it: the difference is always (higher index) - (lower index) in SELF, so (i, j) and
+// (j, i) run the same operations on the same operands and get the same bits, and catalogue - satellite in cross, which is what
+// SELF computes for the pair (i, S + j) of the union [constellation; catalogue], bit for bit.  Every reduction is a minimum under
+// a total order (squared distance, then column index, then interval), so nothing depends on tiles, grid dimensions, row blocks
+// or device count.
+#include "mpcx_host.hpp"
+
+#include <math.h>
 
 namespace mpcx {
 
-constexpr int CJ_ROWS = 256;      // row satellites of a workgroup, one per lane
-constexpr int CJ_TC = 16;         // columns of a tile: a lane keeps the pair minimum of each in registers while it walks the grid
-constexpr int CJ_TM = 32;         // grid intervals staged in LDS at a time (TM + 1 instants)
-constexpr int CJ_MAXGROUPS = 64;  // column groups (gridDim.y) at the most: rows of partial minima in the workspace
+constexpr int CJ_TC = 16;             // columns of a tile: a lane keeps the pair minimum of each in registers while it walks the grid
+constexpr int CJ_MAXGROUPS = 64;      // all pairs: column groups (gridDim.y) at the most
+constexpr int CJX_WAVES = 2048;       // cross: waves the launch aims at, two on each of the 256 x 4 SIMDs, what the kernel's registers admit
+constexpr int CJX_WIDE_FROM = 512;    // cross: rows from which a workgroup takes 256 of them (four waves share the staged columns) instead of 64
+
+__device__ __forceinline__ double cj_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+__device__ __forceinline__ double cj_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
+
+// np.linspace(T0, T1, M)[m]: m * step, the last instant exactly T1 (a satellite whose span ends at T1 is still inside)
+__device__ __forceinline__ double cj_time(int m, int M, double T0, double T1, double h)
+{
+    return m == M - 1 ? T1 : T0 + (double)m * h;
+}
 
 struct EphArgs {
     int S, n, M;
@@ -61,65 +79,138 @@ __global__ __launch_bounds__(256) void ephemeris_kernel(EphArgs a)
     for (int c = 0; c < 6; ++c) a.eph[((size_t)s * 6 + c) * a.M + m] = o[c];
 }
 
-struct ConjArgs {
-    int S, M, row0, nrows, max_pairs;
+// eph [S][6][M] -> the screen's instant-major copy ephT [M][6][S] (the rows of one instant side by side: a row tile's loads
+// are coalesced, an instant's S x 48 B stay in L2 across the row tiles).  An end with a NaN in any of its six values becomes
+// NaN in all six, so that the screen tests positions only.  One lane per (instant, satellite).
+__global__ __launch_bounds__(256) void conjunction_transpose_kernel(int S, int M, const double *eph, double *ephT)
+{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)S * M) return;
+    const int m = (int)(idx / S), s = (int)(idx - (long)m * S);
+    double v[6];
+    bool nan = false;
+    for (int c = 0; c < 6; ++c) { v[c] = eph[((size_t)s * 6 + c) * M + m]; nan = nan || !(v[c] == v[c]); }
+    for (int c = 0; c < 6; ++c) ephT[((size_t)m * 6 + c) * S + s] = nan ? cj_nan() : v[c];
+}
+
+__device__ __forceinline__ double cj_dot(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// The closest approach of one pair inside one grid interval.  d0, d1: hi - lo position differences at the interval's ends;
+// cv0, cv1 / v0, v1: the column's and the row's velocities there (their difference, hi - lo, is formed only where the Newton
+// steps need it; up: the column is the higher index).  Distances are compared squared (the root is taken once, on the way out).  Updates
+// (best, tbest) when the interval comes closer: ends first, the interior point last, each only if strictly smaller.
+__device__ __forceinline__ void cj_interval(const double (&d0)[3], const double (&d1)[3], const double *cv0, const double *cv1,
+                                            const double (&v0)[3], const double (&v1)[3], bool up, double h, double t0, double t1,
+                                            double &best, double &tbest)
+{
+    const double q0 = cj_dot(d0, d0), q1 = cj_dot(d1, d1);
+    if (!(q0 == q0) || !(q1 == q1)) return;                       // an end outside a satellite's span
+    double q = q0, tq = t0;
+    if (q1 < q) { q = q1; tq = t1; }
+    const double D[3] = {d1[0] - d0[0], d1[1] - d0[1], d1[2] - d0[2]};
+    const double DD = cj_dot(D, D), b = cj_dot(d0, D);
+    double s = 0.0;
+    if (DD > 0.0 && DD < cj_inf()) {
+        s = -b / DD;
+        s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
+    }
+    if (s > 0.0 && s < 1.0) {
+        double a0[3], a1[3];                                      // h w0, h w1
+        for (int c = 0; c < 3; ++c) {
+            a0[c] = h * (up ? cv0[c] - v0[c] : v0[c] - cv0[c]);
+            a1[c] = h * (up ? cv1[c] - v1[c] : v1[c] - cv1[c]);
+        }
+        double x[3];
+        for (int it = 0; it < 4; ++it) {                          // three Newton steps, then the distance at the result
+            const double s2 = s * s, s3 = s2 * s;
+            const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + s, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
+            for (int c = 0; c < 3; ++c) x[c] = h00 * d0[c] + h10 * a0[c] + h01 * d1[c] + h11 * a1[c];
+            if (it == 3) break;
+            const double g00 = 6.0 * s2 - 6.0 * s, g10 = 3.0 * s2 - 4.0 * s + 1.0, g01 = -6.0 * s2 + 6.0 * s, g11 = 3.0 * s2 - 2.0 * s;
+            const double k00 = 12.0 * s - 6.0, k10 = 6.0 * s - 4.0, k01 = -12.0 * s + 6.0, k11 = 6.0 * s - 2.0;
+            double x1[3], x2[3];
+            for (int c = 0; c < 3; ++c) {
+                x1[c] = g00 * d0[c] + g10 * a0[c] + g01 * d1[c] + g11 * a1[c];
+                x2[c] = k00 * d0[c] + k10 * a0[c] + k01 * d1[c] + k11 * a1[c];
+            }
+            const double g = cj_dot(x, x1), gp = cj_dot(x1, x1) + cj_dot(x, x2);
+            if (gp > 0.0) {
+                s = s - g / gp;
+                s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
+            }
+        }
+        const double qs = cj_dot(x, x);
+        if (qs < q) { q = qs; tq = t0 + s * h; }
+    }
+    if (q < best) { best = q; tbest = tq; }
+}
+
+struct ScreenArgs {
+    int C, M, row0, nrows, max_pairs; // C columns; the launch's rows are row0 .. row0 + nrows - 1 of the caller's
     double T0, T1, h, thr;
-    const double *ephT;
+    const double *rowT;               // instant-major ends of the launch's rows [M][6][rstride], its first row at index 0
+    size_t rstride;
+    const double *colT;               // instant-major ends of the columns [M][6][C]
     double *pd2, *pt;                 // partial row minima [gridDim.y][nrows]: squared distance, time
-    int32_t *pj;                      //                                         partner
+    int32_t *pj;                      //                                         column index
     double *pairs;                    // [max_pairs][4]
     unsigned long long *count;
 };
 
-// One lane per row satellite, a workgroup of CJ_ROWS rows (blockIdx.x) that takes the column tiles blockIdx.y, blockIdx.y +
-// gridDim.y, ...  For one tile of CJ_TC columns a lane walks all grid intervals with the tile's pair minima in registers (the
-// minimum of a PAIR over the whole grid is what the pairs list needs); its own ends come from global memory once per interval
-// and serve the whole tile, the columns' ends are staged in LDS, CJ_TM intervals at a time, and read by every lane at the same
-// address (a broadcast, no bank conflict).  The full square is computed: a row's minimum needs no atomics.
-__global__ __launch_bounds__(CJ_ROWS) void conjunction_kernel(ConjArgs a)
+// One lane per row, a workgroup of ROWS rows (blockIdx.x) that takes the column tiles blockIdx.y, blockIdx.y + gridDim.y, ...
+// For one tile of CJ_TC columns a lane walks all grid intervals with the tile's pair minima in registers (the minimum of a PAIR
+// over the whole grid is what the pairs list needs); its own ends come coalesced from rowT once per interval and serve the whole
+// tile, the columns' ends are staged in LDS, TM intervals at a time, and read by every lane at the same address (a broadcast, no
+// bank conflict).  A row's minimum needs no atomics.  SELF: the columns are the rows' own constellation and row r is column
+// row0 + r -- that pair is skipped, the difference is (higher index) - (lower index), and the list takes a pair from its lower
+// row only.  Otherwise the difference is column - row and every pair is listed.  ROWS and gridDim.y are the launch's choice
+// (ScreenLaunch): 64-row workgroups are single waves, so that a few rows against many columns still put a wave with 64 live
+// lanes on every SIMD.
+template <int ROWS, int TM, bool SELF> __global__ __launch_bounds__(ROWS) void screen_kernel(ScreenArgs a)
 {
-    __shared__ double col[(CJ_TM + 1) * CJ_TC * 6];              // [instant of the chunk][column][px py pz vx vy vz]
+    __shared__ double col[(TM + 1) * CJ_TC * 6];                 // [instant of the chunk][column][px py pz vx vy vz]
     const int lane = threadIdx.x;
-    const int r = blockIdx.x * CJ_ROWS + lane;                   // row of the launch's block of rows
+    const int r = blockIdx.x * ROWS + lane;                      // row of the launch's block of rows
     const bool row_ok = r < a.nrows;
-    const int i = a.row0 + (row_ok ? r : 0);                     // (lanes past the last row load row0's ends and record nothing)
-    const size_t S = (size_t)a.S;
+    const size_t ir = row_ok ? r : 0;                            // (lanes past the last row load the first row's ends and record nothing)
+    const int i = a.row0 + (int)ir;                              // SELF: the row's index among the columns
+    const size_t R = a.rstride, C = (size_t)a.C;
     double bd2 = cj_inf(), bt = cj_nan();
     int bj = -1;
-    const int ntile = (a.S + CJ_TC - 1) / CJ_TC;
+    const int ntile = (a.C + CJ_TC - 1) / CJ_TC;
     for (int jt = blockIdx.y; jt < ntile; jt += gridDim.y) {
         const int j0 = jt * CJ_TC;
         double pd2[CJ_TC], pt[CJ_TC];
 #pragma unroll
         for (int jj = 0; jj < CJ_TC; ++jj) { pd2[jj] = cj_inf(); pt[jj] = cj_nan(); }
-        for (int m0 = 0; m0 < a.M - 1; m0 += CJ_TM) {
-            const int nm = a.M - 1 - m0 < CJ_TM ? a.M - 1 - m0 : CJ_TM;        // intervals of this chunk
+        for (int m0 = 0; m0 < a.M - 1; m0 += TM) {
+            const int nm = a.M - 1 - m0 < TM ? a.M - 1 - m0 : TM;                // intervals of this chunk
             __syncthreads();
-            for (int e = lane; e < (nm + 1) * CJ_TC * 6; e += CJ_ROWS) {
+            for (int e = lane; e < (nm + 1) * CJ_TC * 6; e += ROWS) {
                 const int mm = e / (CJ_TC * 6), q = e - mm * (CJ_TC * 6), c = q / CJ_TC, jj = q - c * CJ_TC;
                 const int j = j0 + jj;
-                col[(mm * CJ_TC + jj) * 6 + c] = j < a.S ? a.ephT[((size_t)(m0 + mm) * 6 + c) * S + j] : cj_nan();
+                col[(mm * CJ_TC + jj) * 6 + c] = j < a.C ? a.colT[((size_t)(m0 + mm) * 6 + c) * C + j] : cj_nan();
             }
             __syncthreads();
             double p0[3], v0[3], p1[3], v1[3];
             for (int c = 0; c < 3; ++c) {
-                p1[c] = a.ephT[((size_t)m0 * 6 + c) * S + i];
-                v1[c] = a.ephT[((size_t)m0 * 6 + 3 + c) * S + i];
+                p1[c] = a.rowT[((size_t)m0 * 6 + c) * R + ir];
+                v1[c] = a.rowT[((size_t)m0 * 6 + 3 + c) * R + ir];
             }
             for (int mm = 0; mm < nm; ++mm) {
                 const int m = m0 + mm;
                 for (int c = 0; c < 3; ++c) {
                     p0[c] = p1[c]; v0[c] = v1[c];
-                    p1[c] = a.ephT[((size_t)(m + 1) * 6 + c) * S + i];
-                    v1[c] = a.ephT[((size_t)(m + 1) * 6 + 3 + c) * S + i];
+                    p1[c] = a.rowT[((size_t)(m + 1) * 6 + c) * R + ir];
+                    v1[c] = a.rowT[((size_t)(m + 1) * 6 + 3 + c) * R + ir];
                 }
                 const double t0 = cj_time(m, a.M, a.T0, a.T1, a.h), t1 = cj_time(m + 1, a.M, a.T0, a.T1, a.h);
 #pragma unroll
                 for (int jj = 0; jj < CJ_TC; ++jj) {
                     const int j = j0 + jj;
-                    if (j == i || !row_ok) continue;
+                    if ((SELF && j == i) || !row_ok) continue;
                     const double *c0 = col + (mm * CJ_TC + jj) * 6, *c1 = c0 + CJ_TC * 6;
-                    const bool up = j > i;                                       // the column is the higher index: column - row
+                    const bool up = !SELF || j > i;                              // the column is the higher index: column - row
                     double d0[3], d1[3];
                     for (int c = 0; c < 3; ++c) {
                         d0[c] = up ? c0[c] - p0[c] : p0[c] - c0[c];
@@ -132,15 +223,15 @@ __global__ __launch_bounds__(CJ_ROWS) void conjunction_kernel(ConjArgs a)
 #pragma unroll
         for (int jj = 0; jj < CJ_TC; ++jj) {
             const int j = j0 + jj;
-            if (!(pd2[jj] < cj_inf())) continue;                                 // no valid interval for this pair (or j == i, j >= S)
+            if (!(pd2[jj] < cj_inf())) continue;                                 // no valid interval for this pair (or j == i, j >= C)
             if (pd2[jj] < bd2 || (pd2[jj] == bd2 && j < bj)) { bd2 = pd2[jj]; bt = pt[jj]; bj = j; }
-            if (a.thr > 0.0 && j > i) {
+            if (a.thr > 0.0 && (!SELF || j > i)) {
                 const double d = sqrt(pd2[jj]);
                 if (d <= a.thr) {
                     const unsigned long long at = atomicAdd(a.count, 1ULL);
                     if (at < (unsigned long long)a.max_pairs) {
                         double *o = a.pairs + at * 4;
-                        o[0] = (double)i; o[1] = (double)j; o[2] = d; o[3] = pt[jj];
+                        o[0] = (double)(a.row0 + r); o[1] = (double)j; o[2] = d; o[3] = pt[jj];
                     }
                 }
             }
@@ -152,32 +243,107 @@ __global__ __launch_bounds__(CJ_ROWS) void conjunction_kernel(ConjArgs a)
     }
 }
 
-// workspace: [ephT M*6*S][partial d2][partial t][partial j][eph S*6*M, the fused call's]
-struct ConjWorkspace {
-    double *ephT, *pd2, *pt, *eph;
+// the column groups' partial minima of every row -> dmin, partner, tca (a minimum under (distance, partner): any order gives it)
+__global__ __launch_bounds__(256) void conjunction_reduce_kernel(int nrows, int ngroups, const double *pd2, const double *pt, const int32_t *pj,
+                                                                 double *dmin, int32_t *partner, double *tca)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nrows) return;
+    double bd2 = cj_inf(), bt = cj_nan();
+    int bj = -1;
+    for (int g = 0; g < ngroups; ++g) {
+        const size_t at = (size_t)g * nrows + r;
+        const int j = pj[at];
+        if (j < 0) continue;
+        const double d2 = pd2[at];
+        if (bj < 0 || d2 < bd2 || (d2 == bd2 && j < bj)) { bd2 = d2; bt = pt[at]; bj = j; }
+    }
+    dmin[r] = bj < 0 ? cj_inf() : sqrt(bd2);
+    partner[r] = bj;
+    tca[r] = bt;
+}
+
+// The two screens as the host sees them: the name in the messages, and whether the columns are the rows' own constellation
+// (then the callers below pass D = S and cat = eph).
+struct Screen {
+    const char *name;
+    bool self;
+};
+constexpr Screen ALL_PAIRS{"conjunction_screen", true}, CROSS{"conjunction_cross_screen", false};
+
+// The launch shape of nrows rows against C columns: rows per workgroup, row tiles (gridDim.x), column groups (gridDim.y, at most
+// one per column tile).  All pairs: 256 rows always, enough groups for about four workgroups per compute unit whatever the number
+// of row tiles, at most CJ_MAXGROUPS.  Cross: 256 rows from CJX_WIDE_FROM rows on and 64 below, and as many groups as it takes to
+// reach CJX_WAVES waves.
+struct ScreenLaunch {
+    int rows, rowtiles, groups;
+    ScreenLaunch(bool self, int nrows, int C)
+    {
+        rows = self || nrows >= CJX_WIDE_FROM ? 256 : 64;
+        rowtiles = (nrows + rows - 1) / rows;
+        const int waves = rowtiles * (rows / 64), ntile = (C + CJ_TC - 1) / CJ_TC;
+        groups = self ? (1024 + rowtiles - 1) / rowtiles : (CJX_WAVES + waves - 1) / waves;
+        if (groups > ntile) groups = ntile;
+        if (self && groups > CJ_MAXGROUPS) groups = CJ_MAXGROUPS;
+    }
+};
+
+static size_t cj_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// workspace: [rowT M*6*S][colT M*6*D][partial d2][partial t][partial j], and behind them, for the fused calls alone, [eph S*6*M]
+// [cat D*6*M]: a _dev caller brings its ephemerides and does not pay for a second copy of them.  All pairs: the columns are the
+// rows, colT = rowT and cat = eph take no room of their own.  The partial minima are groups * nrows entries: at most
+// CJ_MAXGROUPS * S for all pairs; for cross at most (CJX_WAVES / waves + 1) * nrows with waves >= nrows / 64.
+struct ScreenWorkspace {
+    double *rowT, *colT, *pd2, *pt, *eph, *cat;
     int32_t *pj;
     size_t bytes;
-    ConjWorkspace(void *base, int S, int M)
+    ScreenWorkspace(void *base, bool self, int S, int D, int M, bool fused)
     {
         char *p = (char *)base;
-        const size_t e = cj_align((size_t)S * 6 * M * sizeof(double)), g = cj_align((size_t)CJ_MAXGROUPS * S * sizeof(double));
-        ephT = (double *)p; p += e;
+        const size_t e = cj_align((size_t)S * 6 * M * sizeof(double)), c = self ? 0 : cj_align((size_t)D * 6 * M * sizeof(double));
+        const size_t g = cj_align((self ? (size_t)CJ_MAXGROUPS * S : (size_t)CJX_WAVES * 64 + (size_t)S + 256) * sizeof(double));
+        rowT = colT = (double *)p; p += e;
+        if (!self) { colT = (double *)p; p += c; }
         pd2 = (double *)p; p += g;
         pt = (double *)p; p += g;
         pj = (int32_t *)p; p += g;
-        eph = (double *)p; p += e;
+        eph = cat = fused ? (double *)p : nullptr;
+        if (fused) {
+            p += e;
+            if (!self) { cat = (double *)p; p += c; }
+        }
         bytes = (size_t)(p - (char *)base);
     }
 };
 
-static int conj_check(mpcx_ctx *ctx, int S, int M, double T0, double T1, int row0, int nrows, double threshold, int max_pairs,
-                      const void *pairs, const void *n_pairs)
+// what every screen entry point is given behind its ephemerides
+struct ScreenCall {
+    int S, D, M;
+    double T0, T1;
+    int row0, nrows;
+    double threshold;
+    int max_pairs;
+    double *dmin;
+    int32_t *partner;
+    double *tca, *pairs;
+    int64_t *n_pairs;
+};
+
+static int screen_fail(mpcx_ctx *ctx, const char *name, const char *what)
 {
-    if (S < 1 || M < 2 || !(T1 > T0) || max_pairs < 0)
-        return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen: need S>=1, M>=2, T1>T0, max_pairs>=0");
-    if (row0 < 0 || nrows < 1 || row0 > S - nrows) return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen: rows row0 .. row0+nrows-1 must lie in 0 .. S-1");
-    if (threshold > 0.0 && (!n_pairs || (max_pairs > 0 && !pairs)))
-        return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen: a threshold needs n_pairs, and pairs when max_pairs > 0");
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", name, what);
+    return ctx_fail(ctx, MPCX_E_BADARG, msg);
+}
+
+static int screen_check(mpcx_ctx *ctx, const Screen &sc, const ScreenCall &c)
+{
+    if (c.S < 1 || c.D < 1 || c.M < 2 || !(c.T1 > c.T0) || c.max_pairs < 0)
+        return screen_fail(ctx, sc.name, sc.self ? "need S>=1, M>=2, T1>T0, max_pairs>=0" : "need S>=1, D>=1, M>=2, T1>T0, max_pairs>=0");
+    if (c.row0 < 0 || c.nrows < 1 || c.row0 > c.S - c.nrows) return screen_fail(ctx, sc.name, "rows row0 .. row0+nrows-1 must lie in 0 .. S-1");
+    if (c.threshold > 0.0 && (!c.n_pairs || (c.max_pairs > 0 && !c.pairs)))
+        return screen_fail(ctx, sc.name, "a threshold needs n_pairs, and pairs when max_pairs > 0");
     return MPCX_OK;
 }
 
@@ -187,6 +353,56 @@ static int eph_check(mpcx_ctx *ctx, int S, int n, int M, double T0, double T1)
     return MPCX_OK;
 }
 
+static unsigned cj_blocks(long lanes) { return (unsigned)((lanes + 255) / 256); }
+
+// transpose -> memset -> screen -> reduce on `st`, everything in device memory (the two _dev entry points, checked by them)
+static int screen_enqueue(mpcx_ctx *ctx, const Screen &sc, const ScreenCall &c, const double *eph, const double *cat, void *workspace,
+                          hipStream_t st)
+{
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    const ScreenWorkspace ws(workspace, sc.self, c.S, c.D, c.M, false);
+    // all pairs: one copy of the whole constellation is rows and columns; cross: the launch's rows alone, and the whole catalogue
+    const int trows = sc.self ? c.S : c.nrows;
+    hipLaunchKernelGGL(conjunction_transpose_kernel, dim3(cj_blocks((long)trows * c.M)), dim3(256), 0, st, trows, c.M,
+                       sc.self ? eph : eph + (size_t)c.row0 * 6 * c.M, ws.rowT);
+    MPCX_HIP(ctx, hipGetLastError());
+    if (!sc.self) {
+        hipLaunchKernelGGL(conjunction_transpose_kernel, dim3(cj_blocks((long)c.D * c.M)), dim3(256), 0, st, c.D, c.M, cat, ws.colT);
+        MPCX_HIP(ctx, hipGetLastError());
+    }
+    if (c.n_pairs) MPCX_HIP(ctx, hipMemsetAsync(c.n_pairs, 0, sizeof(int64_t), st));
+    const ScreenLaunch L(sc.self, c.nrows, c.D);
+    const ScreenArgs a{c.D, c.M, c.row0, c.nrows, c.max_pairs, c.T0, c.T1, (c.T1 - c.T0) / (double)(c.M - 1), c.threshold > 0.0 ? c.threshold : 0.0,
+                       sc.self ? ws.rowT + c.row0 : ws.rowT, (size_t)trows, ws.colT, ws.pd2, ws.pt, ws.pj, c.pairs, (unsigned long long *)c.n_pairs};
+    const dim3 grid((unsigned)L.rowtiles, (unsigned)L.groups);
+    if (sc.self) hipLaunchKernelGGL((screen_kernel<256, 32, true>), grid, dim3(256), 0, st, a);
+    else if (L.rows == 256) hipLaunchKernelGGL((screen_kernel<256, 32, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((screen_kernel<64, 16, false>), grid, dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(conjunction_reduce_kernel, dim3(cj_blocks(c.nrows)), dim3(256), 0, st, c.nrows, L.groups, ws.pd2, ws.pt, ws.pj, c.dmin,
+                       c.partner, c.tca);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
+// the part the four host-pointer screens share: the ephemerides already in HBM -> results in the caller's arrays
+static int screen_from_device(mpcx_ctx *ctx, DeviceArena &ar, const Screen &sc, const ScreenCall &c, const double *deph, const double *dcat,
+                              void *dws)
+{
+    ScreenCall d = c;
+    d.dmin = ar.alloc<double>(c.nrows); d.tca = ar.alloc<double>(c.nrows);
+    d.partner = ar.alloc<int32_t>(c.nrows);
+    d.pairs = c.threshold > 0.0 && c.max_pairs > 0 ? ar.alloc<double>((size_t)c.max_pairs * 4) : nullptr;
+    d.n_pairs = ar.alloc<int64_t>(1);
+    if (ar.failed()) return ar.code();
+    if (d.pairs) MPCX_HIP(ctx, hipMemsetAsync(d.pairs, 0, (size_t)c.max_pairs * 4 * sizeof(double), ctx->stream));
+    if (int rc = screen_enqueue(ctx, sc, d, deph, dcat, dws, ctx->stream)) return rc;
+    ar.download(c.dmin, d.dmin, c.nrows); ar.download(c.partner, d.partner, c.nrows); ar.download(c.tca, d.tca, c.nrows);
+    if (d.pairs) ar.download(c.pairs, d.pairs, (size_t)c.max_pairs * 4);
+    if (c.n_pairs) ar.download(c.n_pairs, d.n_pairs, 1);
+    return ar.finish();
+}
+
 }  // namespace mpcx
 
 using namespace mpcx;
@@ -194,7 +410,13 @@ using namespace mpcx;
 extern "C" size_t mpcx_conjunction_workspace_bytes(int S, int M)
 {
     if (S < 1 || M < 2) return 0;
-    return ConjWorkspace(nullptr, S, M).bytes;
+    return ScreenWorkspace(nullptr, true, S, S, M, true).bytes;      // (with the fused call's ephemeris: the value callers have sized by)
+}
+
+extern "C" size_t mpcx_conjunction_cross_workspace_bytes(int S, int D, int M)
+{
+    if (S < 1 || D < 1 || M < 2) return 0;
+    return ScreenWorkspace(nullptr, false, S, D, M, false).bytes;
 }
 
 extern "C" int mpcx_ephemeris_batch_dev(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
@@ -205,37 +427,7 @@ extern "C" int mpcx_ephemeris_batch_dev(mpcx_ctx *ctx, int S, int n, const int32
     if (!Y || !units || !span || !eph || !status) return ctx_fail(ctx, MPCX_E_BADARG, "ephemeris: Y, units, span, eph and status are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     EphArgs a{S, n, M, ns, Y, units, span, T0, T1, (T1 - T0) / (double)(M - 1), eph, status};
-    const long total = (long)S * M;
-    hipLaunchKernelGGL(ephemeris_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    MPCX_HIP(ctx, hipGetLastError());
-    return MPCX_OK;
-}
-
-extern "C" int mpcx_conjunction_screen_dev(mpcx_ctx *ctx, int S, int M, const double *eph, double T0, double T1, int row0, int nrows,
-                                           double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs,
-                                           int64_t *n_pairs, void *workspace, void *stream)
-{
-    if (!ctx) return MPCX_E_BADARG;
-    if (int rc = conj_check(ctx, S, M, T0, T1, row0, nrows, threshold, max_pairs, pairs, n_pairs)) return rc;
-    if (!eph || !dmin || !partner || !tca || !workspace) return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen: eph, dmin, partner, tca and workspace are required");
-    MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    ConjWorkspace ws(workspace, S, M);
-    const long total = (long)S * M;
-    hipLaunchKernelGGL(conjunction_transpose_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, M, eph, ws.ephT);
-    MPCX_HIP(ctx, hipGetLastError());
-    if (n_pairs) MPCX_HIP(ctx, hipMemsetAsync(n_pairs, 0, sizeof(int64_t), st));
-    // enough workgroups to fill the device (about four per compute unit) whatever the number of row tiles, at most one per column tile
-    const int rowtiles = (nrows + CJ_ROWS - 1) / CJ_ROWS, ntile = (S + CJ_TC - 1) / CJ_TC;
-    int groups = (1024 + rowtiles - 1) / rowtiles;
-    if (groups > ntile) groups = ntile;
-    if (groups > CJ_MAXGROUPS) groups = CJ_MAXGROUPS;
-    ConjArgs a{S, M, row0, nrows, max_pairs, T0, T1, (T1 - T0) / (double)(M - 1), threshold > 0.0 ? threshold : 0.0, ws.ephT,
-               ws.pd2, ws.pt, ws.pj, pairs, (unsigned long long *)n_pairs};
-    hipLaunchKernelGGL(conjunction_kernel, dim3((unsigned)rowtiles, (unsigned)groups), dim3(CJ_ROWS), 0, st, a);
-    MPCX_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(conjunction_reduce_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, st, nrows, groups, ws.pd2, ws.pt, ws.pj,
-                       dmin, partner, tca);
+    hipLaunchKernelGGL(ephemeris_kernel, dim3(cj_blocks((long)S * M)), dim3(256), 0, (hipStream_t)stream, a);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
 }
@@ -259,24 +451,28 @@ extern "C" int mpcx_ephemeris_batch(mpcx_ctx *ctx, int S, int n, const int32_t *
     return ar.finish();
 }
 
-// the part the two host-pointer screens share: eph already in HBM -> results in the caller's arrays
-static int conj_screen_from_device(mpcx_ctx *ctx, DeviceArena &ar, int S, int M, const double *deph, void *dws, double T0, double T1, int row0,
-                                   int nrows, double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs,
-                                   int64_t *n_pairs)
+extern "C" int mpcx_conjunction_screen_dev(mpcx_ctx *ctx, int S, int M, const double *eph, double T0, double T1, int row0, int nrows,
+                                           double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca, double *pairs,
+                                           int64_t *n_pairs, void *workspace, void *stream)
 {
-    const bool list = threshold > 0.0;
-    double *dd = ar.alloc<double>(nrows), *dt = ar.alloc<double>(nrows);
-    int32_t *dp = ar.alloc<int32_t>(nrows);
-    double *dpairs = list && max_pairs > 0 ? ar.alloc<double>((size_t)max_pairs * 4) : nullptr;
-    int64_t *dn = ar.alloc<int64_t>(1);
-    if (ar.failed()) return ar.code();
-    if (dpairs) MPCX_HIP(ctx, hipMemsetAsync(dpairs, 0, (size_t)max_pairs * 4 * sizeof(double), ctx->stream));
-    if (int rc = mpcx_conjunction_screen_dev(ctx, S, M, deph, T0, T1, row0, nrows, threshold, max_pairs, dd, dp, dt, dpairs, dn, dws, ctx->stream))
-        return rc;
-    ar.download(dmin, dd, nrows); ar.download(partner, dp, nrows); ar.download(tca, dt, nrows);
-    if (dpairs) ar.download(pairs, dpairs, (size_t)max_pairs * 4);
-    if (n_pairs) ar.download(n_pairs, dn, 1);
-    return ar.finish();
+    if (!ctx) return MPCX_E_BADARG;
+    const ScreenCall c{S, S, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
+    if (int rc = screen_check(ctx, ALL_PAIRS, c)) return rc;
+    if (!eph || !dmin || !partner || !tca || !workspace) return screen_fail(ctx, ALL_PAIRS.name, "eph, dmin, partner, tca and workspace are required");
+    return screen_enqueue(ctx, ALL_PAIRS, c, eph, eph, workspace, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_conjunction_cross_screen_dev(mpcx_ctx *ctx, int S, int D, int M, const double *eph, const double *cat, double T0,
+                                                 double T1, int row0, int nrows, double threshold, int max_pairs, double *dmin,
+                                                 int32_t *partner, double *tca, double *pairs, int64_t *n_pairs, void *workspace,
+                                                 void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const ScreenCall c{S, D, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
+    if (int rc = screen_check(ctx, CROSS, c)) return rc;
+    if (!eph || !cat || !dmin || !partner || !tca || !workspace)
+        return screen_fail(ctx, CROSS.name, "eph, cat, dmin, partner, tca and workspace are required");
+    return screen_enqueue(ctx, CROSS, c, eph, cat, workspace, (hipStream_t)stream);
 }
 
 extern "C" int mpcx_conjunction_screen(mpcx_ctx *ctx, int S, int M, const double *eph, double T0, double T1, int row0, int nrows,
@@ -284,14 +480,31 @@ extern "C" int mpcx_conjunction_screen(mpcx_ctx *ctx, int S, int M, const double
                                        int64_t *n_pairs)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (int rc = conj_check(ctx, S, M, T0, T1, row0, nrows, threshold, max_pairs, pairs, n_pairs)) return rc;
-    if (!eph || !dmin || !partner || !tca) return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen: eph, dmin, partner and tca are required");
+    const ScreenCall c{S, S, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
+    if (int rc = screen_check(ctx, ALL_PAIRS, c)) return rc;
+    if (!eph || !dmin || !partner || !tca) return screen_fail(ctx, ALL_PAIRS.name, "eph, dmin, partner and tca are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     double *de = ar.upload(eph, (size_t)S * 6 * M);
     char *dws = ar.alloc<char>(mpcx_conjunction_workspace_bytes(S, M));
     if (ar.failed()) return ar.code();
-    return conj_screen_from_device(ctx, ar, S, M, de, dws, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs);
+    return screen_from_device(ctx, ar, ALL_PAIRS, c, de, de, dws);
+}
+
+extern "C" int mpcx_conjunction_cross_screen(mpcx_ctx *ctx, int S, int D, int M, const double *eph, const double *cat, double T0, double T1,
+                                             int row0, int nrows, double threshold, int max_pairs, double *dmin, int32_t *partner,
+                                             double *tca, double *pairs, int64_t *n_pairs)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const ScreenCall c{S, D, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
+    if (int rc = screen_check(ctx, CROSS, c)) return rc;
+    if (!eph || !cat || !dmin || !partner || !tca) return screen_fail(ctx, CROSS.name, "eph, cat, dmin, partner and tca are required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *de = ar.upload(eph, (size_t)S * 6 * M), *dc = ar.upload(cat, (size_t)D * 6 * M);
+    char *dws = ar.alloc<char>(mpcx_conjunction_cross_workspace_bytes(S, D, M));
+    if (ar.failed()) return ar.code();
+    return screen_from_device(ctx, ar, CROSS, c, de, dc, dws);
 }
 
 extern "C" int mpcx_conjunction_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
@@ -300,9 +513,11 @@ extern "C" int mpcx_conjunction_screen_traj(mpcx_ctx *ctx, int S, int n, const i
                                             int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
+    const ScreenCall c{S, S, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
     if (int rc = eph_check(ctx, S, n, M, T0, T1)) return rc;
-    if (int rc = conj_check(ctx, S, M, T0, T1, row0, nrows, threshold, max_pairs, pairs, n_pairs)) return rc;
-    if (!Y || !units || !span || !dmin || !partner || !tca) return ctx_fail(ctx, MPCX_E_BADARG, "conjunction_screen_traj: Y, units, span, dmin, partner and tca are required");
+    if (int rc = screen_check(ctx, ALL_PAIRS, c)) return rc;
+    if (!Y || !units || !span || !dmin || !partner || !tca)
+        return screen_fail(ctx, "conjunction_screen_traj", "Y, units, span, dmin, partner and tca are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     double *dY = ar.upload(Y, (size_t)S * 7 * n), *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2);
@@ -310,8 +525,38 @@ extern "C" int mpcx_conjunction_screen_traj(mpcx_ctx *ctx, int S, int n, const i
     int32_t *dst = ar.alloc<int32_t>(S);
     char *dws = ar.alloc<char>(mpcx_conjunction_workspace_bytes(S, M));
     if (ar.failed()) return ar.code();
-    double *de = ConjWorkspace(dws, S, M).eph;                       // the ephemeris never leaves HBM
-    if (int rc = mpcx_ephemeris_batch_dev(ctx, S, n, dns, dY, du, dsp, M, T0, T1, de, dst, ctx->stream)) return rc;
+    const ScreenWorkspace ws(dws, true, S, S, M, true);              // the ephemeris never leaves HBM
+    if (int rc = mpcx_ephemeris_batch_dev(ctx, S, n, dns, dY, du, dsp, M, T0, T1, ws.eph, dst, ctx->stream)) return rc;
     if (status) ar.download(status, dst, S);
-    return conj_screen_from_device(ctx, ar, S, M, de, dws, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs);
+    return screen_from_device(ctx, ar, ALL_PAIRS, c, ws.eph, ws.eph, dws);
+}
+
+extern "C" int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_t *ns, const double *Y, const double *units,
+                                                  const double *span, int D, int cat_n, const int32_t *cat_ns, const double *cat_Y,
+                                                  const double *cat_units, const double *cat_span, int M, double T0, double T1, int row0,
+                                                  int nrows, double threshold, int max_pairs, double *dmin, int32_t *partner, double *tca,
+                                                  double *pairs, int64_t *n_pairs, int32_t *status, int32_t *cat_status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const ScreenCall c{S, D, M, T0, T1, row0, nrows, threshold, max_pairs, dmin, partner, tca, pairs, n_pairs};
+    if (S < 1 || D < 1 || M < 2 || n < 1 || cat_n < 1 || !(T1 > T0))
+        return screen_fail(ctx, "conjunction_cross_screen_traj", "need S>=1, D>=1, n>=1, cat_n>=1, M>=2, T1>T0");
+    if (int rc = screen_check(ctx, CROSS, c)) return rc;
+    if (!Y || !units || !span || !cat_Y || !cat_units || !cat_span || !dmin || !partner || !tca)
+        return screen_fail(ctx, "conjunction_cross_screen_traj", "Y, units, span, cat_Y, cat_units, cat_span, dmin, partner and tca are required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *dY = ar.upload(Y, (size_t)S * 7 * n), *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2);
+    int32_t *dns = ns ? ar.upload(ns, S) : nullptr;
+    double *cY = ar.upload(cat_Y, (size_t)D * 7 * cat_n), *cu = ar.upload(cat_units, (size_t)D * 2), *csp = ar.upload(cat_span, (size_t)D * 2);
+    int32_t *cns = cat_ns ? ar.upload(cat_ns, D) : nullptr;
+    int32_t *dst = ar.alloc<int32_t>(S), *cst = ar.alloc<int32_t>(D);
+    char *dws = ar.alloc<char>(ScreenWorkspace(nullptr, false, S, D, M, true).bytes);   // the screen's workspace, then the two ephemerides
+    if (ar.failed()) return ar.code();
+    const ScreenWorkspace ws(dws, false, S, D, M, true);            // neither ephemeris leaves HBM
+    if (int rc = mpcx_ephemeris_batch_dev(ctx, S, n, dns, dY, du, dsp, M, T0, T1, ws.eph, dst, ctx->stream)) return rc;
+    if (int rc = mpcx_ephemeris_batch_dev(ctx, D, cat_n, cns, cY, cu, csp, M, T0, T1, ws.cat, cst, ctx->stream)) return rc;
+    if (status) ar.download(status, dst, S);
+    if (cat_status) ar.download(cat_status, cst, D);
+    return screen_from_device(ctx, ar, CROSS, c, ws.eph, ws.cat, dws);
 }

@@ -1,4 +1,4 @@
-"""profiling helper: durations of the cross screen (two transposes + conjunction_cross_kernel + reduce, mpcx_conjunction_cross_screen_dev)
+"""profiling helper: durations of the cross screen (two transposes + screen_kernel + reduce, mpcx_conjunction_cross_screen_dev)
 by HIP events on its stream, a random LEO shell on M = 541 common instants (one orbit, 100 nodes per trajectory), at
 (S satellites, D catalogue objects) = (512, 4096), (64, 32768), (4096, 4096); and, at (512, 4096), of the only other way to the
 same answer: the all-pairs screen (mpcx_conjunction_screen_dev) of the union of 4608 objects, the two alternating on one device.

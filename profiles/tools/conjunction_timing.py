@@ -1,4 +1,4 @@
-"""profiling helper: durations of ephemeris_kernel and of the conjunction screen (transpose + conjunction_kernel + reduce) by HIP
+"""profiling helper: durations of ephemeris_kernel and of the conjunction screen (transpose + screen_kernel<256, 32, SELF> + reduce) by HIP
 events on their stream, S = 512 and 4096 satellites of a random LEO shell on M = 541 common instants (one orbit, 100 nodes per
 trajectory), and the fp64 rate they amount to.  --share: the share of valid pair-intervals that take the Newton steps, counted
 by the numpy restatement (host only, S = 512; minutes of numpy at 4096).

@@ -1,4 +1,4 @@
-"""Screening a constellation against a catalogue on the device (csrc/conjunction_cross.hip) against its numpy restatement
+"""Screening a constellation against a catalogue on the device (csrc/conjunction.hip) against its numpy restatement
 (conjunction_cross_reference.py), and bit for bit against the all-pairs screen of the union.
 
 Tolerances: those of test_conjunction_gpu.py (its `close`), which derives them -- partner identical (no ties, asserted),
@@ -45,7 +45,8 @@ def test_against_the_restatement(S, D, M):
 
 @pytest.mark.parametrize("S,D,M", [(17, 40, 34), (65, 100, 130)])
 def test_same_bits_as_the_union(S, D, M):
-    """the pair (i, j) is the pair (i, S + j) of the union [constellation; catalogue]: same function, same operands"""
+    """the pair (i, j) is the pair (i, S + j) of the union [constellation; catalogue]: the same kernel text with and without SELF,
+    the same operands"""
     from mpconstellation_amd import screen
     c = X.case(S, D, M)
     X.assert_no_ties_and_moving(c)

@@ -179,6 +179,38 @@ def test_fused_and_two_devices_hold_the_same_bits():
     assert bits(screen(devices=[0, 0, 0], **traj)) == bits(two_step)
 
 
+def test_blocks_of_rows_hold_the_whole_call_s_bits():
+    """mpcx_conjunction_screen for the whole square, and again for blocks of rows: a block's rows are read from the instant-major
+    copy of the whole constellation at row0 + lane, which only the two-device test reached with row0 > 0.  S = 300 makes row 257
+    the second workgroup's first lane and (299, 1) a block with one live lane; M = 34 is one interval past the 32-interval chunk."""
+    from mpconstellation_amd import _ffi
+    from mpconstellation_amd.conjunction import sort_pairs
+    S, M = 300, 34
+    c = R.case(S, M)
+    lib, ctx = _ffi.load(), _ffi.context(0)
+    eph = np.ascontiguousarray(c["eph"])
+    npair = S * (S - 1) // 2
+
+    def call(row0, nrows):
+        d, p, t = np.empty(nrows), np.empty(nrows, dtype=np.int32), np.empty(nrows)
+        pairs, n = np.zeros((npair, 4)), np.zeros(1, dtype=np.int64)
+        assert lib.mpcx_conjunction_screen(ctx, S, M, _ffi.dptr(eph), c["T0"], c["T1"], row0, nrows, 1e9, npair, _ffi.dptr(d), _ffi.iptr(p),
+                                           _ffi.dptr(t), _ffi.dptr(pairs), n.ctypes.data_as(_ffi._lp)) == 0
+        assert n[0] <= npair
+        return d, p, t, sort_pairs(pairs[:n[0]])
+    wd, wp, wt, wpairs = call(0, S)
+    assert len(wpairs) == npair and (wp >= 0).all()
+    lists = []
+    for row0, nrows in ((0, 257), (257, 43), (299, 1)):
+        d, p, t, pairs = call(row0, nrows)
+        rows = slice(row0, row0 + nrows)
+        assert d.tobytes() == wd[rows].tobytes() and p.tobytes() == wp[rows].tobytes() and t.tobytes() == wt[rows].tobytes(), (row0, nrows)
+        mine = wpairs[(wpairs[:, 0] >= row0) & (wpairs[:, 0] < row0 + nrows)]          # the pairs whose smaller index lies in the block
+        assert pairs.tobytes() == mine.tobytes(), (row0, nrows)
+        lists.append(pairs)
+    assert sort_pairs(np.concatenate(lists)).tobytes() == wpairs.tobytes()
+
+
 def test_c_abi_refuses_bad_arguments():
     from mpconstellation_amd import _ffi
     lib, ctx = _ffi.load(), _ffi.context(0)
