@@ -72,13 +72,13 @@ __device__ __forceinline__ double rsq_nr(double d)
 // here everything is arranged around one reciprocal each of |r|, m and |u| (round 3).  Results move by rounding only (a few
 // ulp per evaluation, 1e-13 on A_k, B_k against the reference's arrays; the accepted RK45 nodes are the same).
 struct Lin {
-    double Gt[3][3], gmt[3], acc[3], mdot, im, iun, un, irn;
+    double Gt[3][3], gmt[3], acc[3], im, irn;
 };
 
 // ATMO: the drag acceleration with dens_atmo = rho(h) / c.rho (atmo_density) in place of the fixed density.
 template <bool ATMO>
 __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)[3], double m, const double (&u)[3],
-                                         const SatConst &c, int flags, double tf, double inv_ve, double dens_atmo, Lin &L)
+                                         const SatConst &c, int flags, double tf, double dens_atmo, Lin &L)
 {
     const double rx = r[0], ry = r[1], rz = r[2];
     const double r2 = rx * rx + ry * ry + rz * rz;
@@ -121,10 +121,6 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
 #pragma unroll
         for (int i = 0; i < 3; ++i) L.acc[i] += coef * v[i];
     }
-    const double uu = u[0] * u[0] + u[1] * u[1] + u[2] * u[2];
-    L.iun = rsq_nr(fmax(uu, 1e-300));
-    L.un = uu * L.iun;
-    L.mdot = -L.un * inv_ve;
     L.im = im;
     L.irn = irn;
 }
@@ -168,25 +164,56 @@ __device__ __forceinline__ void drag_dv(const DragLin &d, const double (&v)[3], 
     out[2] = d.kvt * c2 + w * v[2];
 }
 
-// One evaluation of dPhi (linearize_discretize.py:262-290) for this lane's column.
-template <bool DRAG, bool ATMO>
-__device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], double ts,
-                                         double (&out)[7], int &err)
+// What a right-hand side or a quadrature node needs of its time alone: the held thrust, 1/|u|, |u| and the mass flow.  Stages
+// and nodes at one time share it (time_eval once) instead of repeating the hold and the |u| chain.
+//   stable: the call left the hold's cached interval as it found it, so a second call at this time would return these very
+//           bits (the cache decides between foh3_cached's two roundings of the weights) -- the condition for sharing;
+//   ferr:   the hold flagged its index (MPCX_ST_FOH), which a caller that shares the value repeats in the second call's place.
+struct TimePart {
+    double u[3], iun, un, mdot;
+    bool stable, ferr;
+};
+__device__ __forceinline__ void time_eval(RhsCtx &p, double ts, TimePart &T, int &err)
 {
-    double u[3];
-    foh3_cached(ts, p.us, p.Ku, p.ldu, p.foh, u, err);
+    const int k0 = p.foh.k;
+    int e = 0;
+    foh3_cached(ts, p.us, p.Ku, p.ldu, p.foh, T.u, e);
+    T.ferr = (e != 0);
+    if (e) err = e;
+    T.stable = (p.foh.k == k0);
+    const double uu = T.u[0] * T.u[0] + T.u[1] * T.u[1] + T.u[2] * T.u[2];
+    T.iun = rsq_nr(fmax(uu, 1e-300));
+    T.un = uu * T.iun;
+    T.mdot = -T.un * p.inv_ve;
+}
+
+// The part that depends on the state (r, v, m of the x column) at a given time part: the linearisation and, in the DRAG forms,
+// the drag partials (L.gmt then includes the drag's mass column).
+template <bool DRAG, bool ATMO>
+__device__ __forceinline__ void state_eval(const RhsCtx &p, const double (&r)[3], const double (&v)[3], double m, const TimePart &T,
+                                           Lin &L, DragLin &D)
+{
+    double dens = 0.0, drho = 0.0;
+    if constexpr (ATMO) dens = atmo_density(r, p.cst, p.atm, &drho);
+    lin_eval<ATMO>(r, v, m, T.u, p.cst, p.flags, p.tf, dens, L);
+    if constexpr (DRAG) D = drag_lin<ATMO>(v, p.cst, p.tf, dens, drho, L);
+}
+
+// One evaluation of dPhi (linearize_discretize.py:262-290) for this lane's column, at the time part T; L, D: the state part
+// it was formed with (the node after an accepted step takes the last stage's).
+template <bool DRAG, bool ATMO>
+__device__ __forceinline__ void rhs_state(RhsCtx &p, const double (&ys)[7], const TimePart &T,
+                                          double (&out)[7], int &err, Lin &L, DragLin &D)
+{
     const double r[3] = {bcast8<7>(ys[0]), bcast8<7>(ys[1]), bcast8<7>(ys[2])};
     // drag acts in the x column only: lane 7's own velocity -- except in the DRAG forms, whose Phi columns need the reference
     // velocity for the drag partials: broadcast from lane 7 like r and m
     const double v[3] = {DRAG ? bcast8<7>(ys[3]) : ys[3], DRAG ? bcast8<7>(ys[4]) : ys[4], DRAG ? bcast8<7>(ys[5]) : ys[5]};
     const double m = bcast8<7>(ys[6]);
     const double tf = p.tf;
-    double dens = 0.0, drho = 0.0;
-    if constexpr (ATMO) dens = atmo_density(r, p.cst, p.atm, &drho);
-    Lin L;
-    lin_eval<ATMO>(r, v, m, u, p.cst, p.flags, tf, p.inv_ve, dens, L);
+    state_eval<DRAG, ATMO>(p, r, v, m, T, L, D);
     double dv[3] = {0.0, 0.0, 0.0};
-    if constexpr (DRAG) drag_dv<ATMO>(drag_lin<ATMO>(v, p.cst, tf, dens, drho, L), v, r, ys[0], ys[1], ys[2], ys[3], ys[4], ys[5], dv);
+    if constexpr (DRAG) drag_dv<ATMO>(D, v, r, ys[0], ys[1], ys[2], ys[3], ys[4], ys[5], dv);
     const bool isx = (p.c == 7);
     if (isx && m <= 0.0) err = MPCX_ST_MASS;
 #pragma unroll
@@ -199,7 +226,22 @@ __device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], doubl
         if constexpr (DRAG) a += dv[i];
         out[3 + i] = isx ? tf * L.acc[i] : a;                // x column: tf * f(x, u)
     }
-    out[6] = isx ? tf * L.mdot : 0.0;
+    out[6] = isx ? tf * T.mdot : 0.0;
+}
+template <bool DRAG, bool ATMO>
+__device__ __forceinline__ void rhs_state(RhsCtx &p, const double (&ys)[7], const TimePart &T, double (&out)[7], int &err)
+{
+    Lin L;
+    DragLin D;
+    rhs_state<DRAG, ATMO>(p, ys, T, out, err, L, D);
+}
+template <bool DRAG, bool ATMO>
+__device__ __forceinline__ void rhs_eval(RhsCtx &p, const double (&ys)[7], double ts,
+                                         double (&out)[7], int &err)
+{
+    TimePart T;
+    time_eval(p, ts, T, err);
+    rhs_state<DRAG, ATMO>(p, ys, T, out, err);
 }
 
 // Solve P z = b for the 8 right-hand sides of a group at once, P distributed by columns: lane j < 6 holds column j in
@@ -252,36 +294,32 @@ __device__ __forceinline__ bool lu_solve_cols(double (&col)[6], double (&b)[6])
 
 // Quadrature integrand column of this lane at an accepted node (linearize_discretize.py:60-75):
 // g = Phi(t)^-1 [B lam-, B lam+, Sigma, xi][:, c]
+// (T, L, D: the time and state parts at (t, y) -- evaluated by node_integrand, or the last stage's where it was this very point)
 template <bool DRAG, bool ATMO>
-__device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
-                                               double t, double tau_k, double tau_kp1,
-                                               double (&g)[7], int &err)
+__device__ __forceinline__ void node_columns(RhsCtx &p, const double (&y)[7], const TimePart &T, const Lin &L, const DragLin &D,
+                                             double t, double tau_k, double tau_kp1,
+                                             double (&g)[7], int &err)
 {
     const int c = p.c;
     double x[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) x[i] = bcast8<7>(y[i]);
-    double u[3];
-    foh3_cached(t, p.us, p.Ku, p.ldu, p.foh, u, err);
+    const double (&u)[3] = T.u;
     const double lam_n = (tau_kp1 - t) / (tau_kp1 - tau_k);      // exact 1 and 0 at the interval's ends
     const double lam_p = (t - tau_k) / (tau_kp1 - tau_k);
     const double tf = p.tf;
 
     const double r[3] = {x[0], x[1], x[2]}, v[3] = {x[3], x[4], x[5]};
-    double dens = 0.0, drho = 0.0;
-    if constexpr (ATMO) dens = atmo_density(r, p.cst, p.atm, &drho);
-    Lin L;
-    lin_eval<ATMO>(r, v, x[6], u, p.cst, p.flags, tf, p.inv_ve, dens, L);
     double dv[3] = {0.0, 0.0, 0.0};                         // DRAG: xi's A x gains the velocity block and (in L.gmt) the mass column; ATMO: the position block too
-    if constexpr (DRAG) drag_dv<ATMO>(drag_lin<ATMO>(v, p.cst, tf, dens, drho, L), v, r, r[0], r[1], r[2], v[0], v[1], v[2], dv);
+    if constexpr (DRAG) drag_dv<ATMO>(D, v, r, r[0], r[1], r[2], v[0], v[1], v[2], dv);
 
     // B column (B_func :186-215), Sigma (:239-254), xi (:218-236)
     const int j = (c < 3) ? c : c - 3;
     const double uj = (j == 0) ? u[0] : (j == 1 ? u[1] : u[2]);
     const double lam = (c < 3) ? lam_n : lam_p;
     const double Bm = (tf * L.im) * lam;
-    const bool nou = L.un <= kEps;                        // B_func's guard: no mass-flow sensitivity at zero thrust
-    const double b6s = -(tf * (p.inv_ve * L.iun));        // tf * d mdot / d u_j = b6s * u_j
+    const bool nou = T.un <= kEps;                        // B_func's guard: no mass-flow sensitivity at zero thrust
+    const double b6s = -(tf * (p.inv_ve * T.iun));        // tf * d mdot / d u_j = b6s * u_j
     const double B6 = nou ? 0.0 : (b6s * uj) * lam;
     double xi[7];
     double bu6 = 0.0;
@@ -297,7 +335,7 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
         bu6 += nou ? 0.0 : (b6s * u[i]) * u[i];
     }
     xi[6] = -(0.0 + bu6);
-    const double sg[7] = {x[3], x[4], x[5], L.acc[0], L.acc[1], L.acc[2], L.mdot};      // Sigma = f(.; tf = 1)
+    const double sg[7] = {x[3], x[4], x[5], L.acc[0], L.acc[1], L.acc[2], T.mdot};      // Sigma = f(.; tf = 1)
 
     double R[7];
 #pragma unroll
@@ -317,6 +355,19 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
 #pragma unroll
     for (int i = 0; i < 6; ++i) g[i] = b[i];
     g[6] = R[6];
+}
+template <bool DRAG, bool ATMO>
+__device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
+                                               double t, double tau_k, double tau_kp1,
+                                               double (&g)[7], int &err)
+{
+    TimePart T;
+    time_eval(p, t, T, err);
+    const double r[3] = {bcast8<7>(y[0]), bcast8<7>(y[1]), bcast8<7>(y[2])}, v[3] = {bcast8<7>(y[3]), bcast8<7>(y[4]), bcast8<7>(y[5])};
+    Lin L;
+    DragLin D;
+    state_eval<DRAG, ATMO>(p, r, v, bcast8<7>(y[6]), T, L, D);
+    node_columns<DRAG, ATMO>(p, y, T, L, D, t, tau_k, tau_kp1, g, err);
 }
 
 // UNIFORM: Discretizer.use_uniform_steps (linearize_discretize.py:27-30, 50-53): the quadrature nodes are integrator_steps
@@ -453,6 +504,9 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
 
         double K1[7], K2[7], K3[7], K4[7], K5[7], K6[7], yt[7], yn[7];
         double se = 0.0;
+        TimePart T6;      // the last stage's time and state parts: (t + h, y_new), where the node of an accepted step is
+        Lin L6;
+        DragLin D6;
         if constexpr (METHOD == 23) {
             // rk_step (rk.py:14-70) with the RK23 tableau: two inner stages, y_new, and f(y_new) -- kept in K6, the slot of the
             // last stage in both methods (first-same-as-last: it becomes f of the next step)
@@ -464,7 +518,8 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             rhs_eval<DRAG, ATMO>(p, yt, t + RK23_C[2] * h, K2, err);
 #pragma unroll
             for (int i = 0; i < 7; ++i) yn[i] = y[i] + h * (f[i] * RK23_B[0] + K1[i] * RK23_B[1] + K2[i] * RK23_B[2]);
-            rhs_eval<DRAG, ATMO>(p, yn, t + h, K6, err);
+            time_eval(p, t + h, T6, err);
+            rhs_state<DRAG, ATMO>(p, yn, T6, K6, err, L6, D6);
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 K3[i] = 0.0; K4[i] = 0.0; K5[i] = 0.0;
@@ -493,12 +548,17 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         for (int i = 0; i < 7; ++i)
             yt[i] = y[i] + (f[i] * RK_A[5][0] + K1[i] * RK_A[5][1] + K2[i] * RK_A[5][2] +
                             K3[i] * RK_A[5][3] + K4[i] * RK_A[5][4]) * h;
-        rhs_eval<DRAG, ATMO>(p, yt, t + RK_C[5] * h, K5, err);
+        // RK_C[5] = 1: the last two stages are at one time, t + h, and share its time part -- unless the first call moved some
+        // lane's hold to another interval (then the second call decides again, as it always did)
+        static_assert(RK_C[5] == 1.0, "K5 and K6 share their time part");
+        time_eval(p, t + RK_C[5] * h, T6, err);
+        rhs_state<DRAG, ATMO>(p, yt, T6, K5, err);
 #pragma unroll
         for (int i = 0; i < 7; ++i)
             yn[i] = y[i] + h * (f[i] * RK_B[0] + K1[i] * RK_B[1] + K2[i] * RK_B[2] +
                                 K3[i] * RK_B[3] + K4[i] * RK_B[4] + K5[i] * RK_B[5]);
-        rhs_eval<DRAG, ATMO>(p, yn, t + h, K6, err);
+        if (!__all(T6.stable)) time_eval(p, t + h, T6, err);
+        rhs_state<DRAG, ATMO>(p, yn, T6, K6, err, L6, D6);
 
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
@@ -512,10 +572,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         const double error_norm = sqrt(group_sum(se)) / sqrt(56.0);
         bool accept = false;
         if (error_norm < 1.0) {
-            double factor = (error_norm == 0.0) ? RK_MAX_FACTOR
-                                                : fmin(RK_MAX_FACTOR, RK_SAFETY * pow(error_norm, kErrExp));
-            if (rejected) factor = fmin(1.0, factor);
-            if (active && !fail) { h_abs = h_try * factor; accept = true; }
+            if (active && !fail) { h_abs = rk_accepted_h_abs<METHOD>(h_abs, error_norm, h_try, a.max_step, rejected, t_new == t_bound); accept = true; }
         } else if (active && !fail) {
             // NaN error norms land here as in scipy (comparison false) and shrink the step
             h_abs = h_try * fmax(RK_MIN_FACTOR, RK_SAFETY * pow(error_norm, kErrExp));
@@ -592,7 +649,19 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         // node quadrature (wave-uniform call; only accepting groups commit)
         if (!UNIFORM && __any(accept)) {
             double g[7];
-            node_integrand<DRAG, ATMO>(p, y, t, tau_k, tau_kp1, g, err);
+            // The node is (t_new, y_new), and the last stage was evaluated at (t + h, y_new): where t + h is t_new to the bit and
+            // the stage's hold call left the cache alone (stable), the node's own evaluation would repeat the stage's, bit for
+            // bit.  A finished group's node is never committed and its hold is never read again.  If that covers the wave the
+            // node takes the stage's parts; a group that rejected or failed sends the wave through the evaluation.
+            const bool same = !active || (accept && t_old + h == t_new && T6.stable);
+            if (__all(same)) {
+                if (T6.ferr) err = MPCX_ST_FOH;      // (what the hold's second call at this time would have flagged)
+            } else {
+                time_eval(p, t, T6, err);
+                const double r[3] = {bcast8<7>(y[0]), bcast8<7>(y[1]), bcast8<7>(y[2])}, v[3] = {bcast8<7>(y[3]), bcast8<7>(y[4]), bcast8<7>(y[5])};
+                state_eval<DRAG, ATMO>(p, r, v, bcast8<7>(y[6]), T6, L6, D6);
+            }
+            node_columns<DRAG, ATMO>(p, y, T6, L6, D6, t, tau_k, tau_kp1, g, err);
             if (accept) {
                 const double d = h;          // ts[i+1] - ts[i]
 #pragma unroll

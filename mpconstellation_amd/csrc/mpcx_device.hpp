@@ -42,6 +42,45 @@ __device__ constexpr double RK23_B[3] = {2.0 / 9, 1.0 / 3, 4.0 / 9};
 __device__ constexpr double RK23_E[4] = {5.0 / 72, -1.0 / 12, -1.0 / 9, 1.0 / 8};
 __device__ constexpr double RK23_P[4][3] = {{1, -4.0 / 3, 5.0 / 9}, {0, 1, -2.0 / 3}, {0, 4.0 / 3, -8.0 / 9}, {0, -1, 1}};
 
+// scipy's step-size controller after an ACCEPTED step (rk.py:149-156): the step size h_abs that the next step starts from,
+//   h_try * factor,  factor = min(RK_MAX_FACTOR, RK_SAFETY * error_norm^(-1 / (q + 1))),  after a rejection min(1, factor)
+// (METHOD 45: q + 1 = 5, METHOD 23: q + 1 = 3; error_norm < 1) -- with the pow evaluated only where its value decides something.
+// The caller's next step clamps what this returns to [min_step, max_step] before anything reads it, and after that clamp the
+// result is the formula's, bit for bit:
+//  (a) at_bound: the step ended on the integration's end point.  No further step: h_abs stays what it is.
+//  (b) error_norm < 2^-18 (RK45; 2^-11 for RK23): RK_SAFETY * error_norm^(..) >= 10.9 (11.4) > RK_MAX_FACTOR with a margin no
+//      rounding of pow comes near, so factor = RK_MAX_FACTOR exactly.
+//  (c) not after a rejection, and error_norm * max_step^5 < (RK_SAFETY h_try)^5 / 2 (^3 for RK23), which is
+//      error_norm (max_step / (RK_SAFETY h_try))^5 < 1/2 without the division: then h_try RK_SAFETY error_norm^(-1/5) exceeds
+//      max_step by the factor 2^(1/5) = 1.15 (2^(1/3) = 1.26) at least, against relative errors of 1e-15 in both products and in
+//      pow.  With error_norm >= 2^-18 the bound also gives max_step / h_try < 0.9 * 2^(17/5) = 9.5 (0.9 * 2^(10/3) = 9.1) < RK_MAX_FACTOR,
+//      so h_try * factor > max_step on either side of the min, and the next step's clamp makes it max_step: any value above
+//      max_step does (not max_step itself, which would take the clamp's other arm).  The comparison is trusted only with
+//      (RK_SAFETY h_try)^5 far inside the normal range, where neither side can have lost its value to overflow or underflow.
+//  (d) otherwise: the formula.
+// Per lane; the pow is behind a branch of its own, which a wave with no lane in (d) skips.
+template <int METHOD>
+__host__ __device__ __forceinline__ double rk_accepted_h_abs(double h_abs, double error_norm, double h_try, double max_step,
+                                                             bool rejected, bool at_bound)
+{
+    constexpr double kExp = (METHOD == 23) ? -1.0 / 3.0 : -0.2;             // rk.py:93: -1 / (error_estimator_order + 1)
+    constexpr double kSmall = (METHOD == 23) ? 0x1p-11 : 0x1p-18;
+    if (at_bound) return h_abs;
+    double factor = RK_MAX_FACTOR;
+    if (!(error_norm < kSmall)) {
+        if (!rejected) {
+            const double sh = RK_SAFETY * h_try;
+            const double m2 = max_step * max_step, s2 = sh * sh;
+            const double mp = (METHOD == 23) ? m2 * max_step : (m2 * m2) * max_step;
+            const double sp = (METHOD == 23) ? s2 * sh : (s2 * s2) * sh;
+            if (error_norm * mp < 0.5 * sp && sp > 1e-250 && sp < 1e250) return 2.0 * max_step;
+        }
+        factor = fmin(RK_MAX_FACTOR, RK_SAFETY * pow(error_norm, kExp));
+    }
+    if (rejected) factor = fmin(1.0, factor);
+    return h_try * factor;
+}
+
 // Python / numpy float floor division (the `tau // dtau` of linearize_discretize.py:310)
 __device__ __forceinline__ double py_floordiv(double a, double b)
 {
