@@ -125,7 +125,17 @@ _SIGS = {
     "mpcx_conjunction_cross_screen_traj": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int,
                                                      C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _lp,
                                                      _ip, _ip]),
+    # collision probability of screened pairs: covariance along trajectories, then the encounter-plane integral per listed pair
+    "mpcx_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mpcx_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
+    "mpcx_covariance_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
+                                            _vp, _vp]),
+    "mpcx_collision_probability": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2 + [C.c_double, _dp, _ip]),
+    "mpcx_collision_probability_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
+                                       + [C.c_double, _vp, _vp, _vp]),
 }
+NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
+PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
 
 
 def _sat_twin(name):

@@ -9,12 +9,16 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
                  near and when, and with a threshold the list of pairs that come closer than it;
   screen_against the same for a constellation against a catalogue of foreign objects (debris, other operators' satellites): the
                  rectangle satellites x objects, not the square of the union;
-  catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against.
+  catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
+  covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
+  collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
+  catalogue_covariance    catalogue_trajectories followed by covariance.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
 import numpy as np
 
 from . import _ffi
+from .linearize_discretize import Discretizer
 
 DEFAULT_MAX_PAIRS = 65536
 
@@ -253,3 +257,169 @@ def combine(results):
     pairs = sort_pairs([(i, j, d, t) for (i, j), (d, t) in best.items()])
     total = max([len(pairs)] + [r.n_pairs_total for r in results])
     return ConjunctionResult(dmin, partner, tca, pairs, total)
+
+
+# ---- from a pairs list to collision probabilities (include/mpcx.h: mpcx_covariance_batch, mpcx_collision_probability; csrc/collision.hip)
+DEFAULT_MAX_STEP = Discretizer(None).ivp_max_step                        # the linearisation's step limit: whatever the Discretizer starts with
+
+
+class CollisionResult:
+    """For the n rows of `pairs` (i, j, distance, time), row for row: pc (n,) the collision probability, miss (n,) the miss distance
+    in the encounter plane (m), speed (n,) the relative speed (m/s), sigma (n, 2) the combined position uncertainty along the
+    principal axes of the encounter plane (m, larger first), mahalanobis (n,) the miss in units of it, status (n,) int32 MPCX_ST_*
+    (a row whose status is not 0 is NaN in all of them)."""
+
+    def __init__(self, pairs, out, status):
+        self.pairs, self.status = pairs, status
+        self.pc, self.miss, self.speed = out[:, _ffi.PC_P], out[:, _ffi.PC_MISS], out[:, _ffi.PC_SPEED]
+        self.sigma, self.mahalanobis = out[:, _ffi.PC_SIGMA1:_ffi.PC_SIGMA2 + 1], out[:, _ffi.PC_MAHAL]
+
+    def __repr__(self):
+        return f"CollisionResult(pairs={len(self.pairs)})"
+
+
+def _check_p0(P0, S, name="P0"):
+    P0 = _ffi.as_f64(P0)
+    if P0.shape == (6, 6):
+        P0 = np.broadcast_to(P0, (S, 6, 6))
+    if P0.shape != (S, 6, 6):
+        raise ValueError(f"{name}: expected (6, 6) or ({S}, 6, 6) covariances of position (m) and velocity (m/s), got {P0.shape}")
+    return _ffi.as_f64(P0)
+
+
+def _check_q(q, S):
+    if q is None:
+        return None
+    if np.ndim(q) not in (0, 1) or (np.ndim(q) == 1 and np.shape(q) != (S,)):
+        raise ValueError(f"q: expected a scalar or ({S},) acceleration noise densities (m^2/s^3), got {np.shape(q)}")
+    q = _ffi.per_sat(q, S)
+    if not (q >= 0.0).all():
+        raise ValueError("q: need densities >= 0")
+    return q
+
+
+def covariance(Y, units, span, consts, P0, U=None, ns=None, q=None, include_drag=False, include_J2=False, atmosphere=None,
+               max_step=DEFAULT_MAX_STEP, device=0, devices=None, return_status=False):
+    """The covariance of position (m) and velocity (m/s) at every node of S trajectories -> P (S, n, 6, 6).  Y (S, 7, n), units, span
+    [, ns] as common_clock takes them; consts (S, 8) each satellite's normalised constants; P0 (6, 6) or (S, 6, 6) the covariance at
+    the first node (its upper triangle is read); U (S, 3, n) the thrust at the nodes (None: zero thrust); q a scalar or (S,) white
+    acceleration noise in m^2/s^3.  The device linearises about (Y, U, span) under the model include_drag / include_J2 / atmosphere
+    (the Discretizer's) and chains the state-transition matrices of the node intervals: P_k+1 = Phi_k P_k Phi_k^T + q Q(h).
+    A satellite with a node count outside 2..n, an empty span or a time unit that is not positive and finite, a failed linearisation
+    or a non-finite P0 is NaN throughout
+    (return_status=True returns (P, status) with its MPCX_ST_* code); nodes past ns come back zero.  devices=[d0, d1, ...]: contiguous
+    blocks of satellites on several devices (sharding.sharded_call), written in place, the bits of one device."""
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, n = Y.shape
+    if n < 2:
+        raise ValueError(f"Y: a covariance needs at least 2 nodes, got {Y.shape}")
+    consts = _ffi.as_f64(consts)
+    if consts.shape != (S, _ffi.NCONST):
+        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
+    P0, q = _check_p0(P0, S), _check_q(q, S)
+    if U is not None:
+        U = _ffi.as_f64(U)
+        if U.shape != (S, 3, n):
+            raise ValueError(f"U: expected ({S}, 3, {n}) thrust at the nodes, got {U.shape}")
+    if not max_step > 0.0:
+        raise ValueError(f"max_step: need > 0, got {max_step}")
+    out = dict(P=_ffi.result_pool.take((S, n, 6, 6)), status=np.zeros(S, dtype=np.int32))
+    how = dict(flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
+    batched = [Y, units, span, consts, P0, U, ns, q]
+    if devices is not None and len(devices) > 1:
+        from .sharding import sharded_call
+        sharded_call(_covariance_call, devices, batched, out, **how)
+    else:
+        if devices is not None and len(devices) == 1:
+            device = int(devices[0])
+        _covariance_call(*batched, device=device, slot=0, out=out, **how)
+    return (out["P"], out["status"]) if return_status else out["P"]
+
+
+def _covariance_call(Y, units, span, consts, P0, U, ns, q, *, device, slot, out, flags, max_step, atmosphere):
+    """one block of satellites on context (device, slot), P and status into `out` (the block's views)"""
+    S, _, n = Y.shape
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_covariance_batch", ctx, S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr_opt(U), _ffi.dptr(units), _ffi.dptr(span),
+              _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(out["P"]), _ffi.iptr(out["status"]))
+
+
+def _check_side(Y, units, span, P, radius, ns, pre=""):
+    """one side of collision_probability: trajectories, their covariances and hard-body radii"""
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns, pre)
+    S, _, n = Y.shape
+    if n < 2:
+        raise ValueError(f"{pre}Y: need at least 2 nodes, got {Y.shape}")
+    if P is None or radius is None:
+        raise ValueError(f"{pre}P and {pre}radius are required with {pre}Y")
+    P = _ffi.as_f64(P)
+    if P.shape != (S, n, 6, 6):
+        raise ValueError(f"{pre}P: expected ({S}, {n}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
+    if np.ndim(radius) not in (0, 1) or (np.ndim(radius) == 1 and np.shape(radius) != (S,)):
+        raise ValueError(f"{pre}radius: expected a scalar or ({S},) hard-body radii in m, got {np.shape(radius)}")
+    return Y, units, span, P, _ffi.per_sat(radius, S), ns
+
+
+def collision_probability(pairs, radius, Y, units, span, P, ns=None, cat=None, mu=None, device=0, devices=None):
+    """The short-encounter collision probability of every listed pair -> CollisionResult.  pairs: (n, 4) rows (i, j, distance,
+    time in s) as screen and screen_against list them, or their ConjunctionResult; radius a scalar or (S,) hard-body radii (m);
+    Y, units, span [, ns] the trajectories that were screened and P (S, n, 6, 6) their covariances (covariance).  cat = (cat_Y,
+    cat_units, cat_span, cat_P, cat_radius[, cat_ns]): j indexes this catalogue (screen_against's lists); None: j indexes the
+    constellation (screen's).  mu: m^3/s^2, the constants' Earth value by default.  Each object's state and position covariance at
+    the pair's time come from its own nodes (cubic Hermite; the covariance of the nearest node carried over the rest of the way by
+    the two-body short-arc transition); the probability is the combined Gaussian's integral over the disc of the summed radii in
+    the plane across the relative velocity, by a fixed 64-point rule: accurate to 1e-13 relative for radius / sigma <= 2, 2e-6 at 8,
+    6e-3 at 20 (include/mpcx.h).  An empty list returns empty arrays without a library call.  devices=[d0, d1, ...]: contiguous
+    blocks of the list's rows on several devices (every device holds all trajectories), written in place, the bits of one device."""
+    from .constants import MU_EARTH
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    rows = _check_side(Y, units, span, P, radius, ns)
+    cols = None
+    if cat is not None:
+        if len(cat) not in (5, 6):
+            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
+        cols = _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
+    mu = float(MU_EARTH if mu is None else mu)
+    if not mu > 0.0:
+        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    n = pairs.shape[0]
+    out = dict(out=np.empty((n, _ffi.NPC)), status=np.zeros(n, dtype=np.int32))
+    if n:
+        how = dict(rows=rows, cols=cols, mu=mu)
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(_collision_call, devices, [pairs], out, **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            _collision_call(pairs, device=device, slot=0, out=out, **how)
+    return CollisionResult(pairs, out["out"], out["status"])
+
+
+def _collision_call(pairs, *, device, slot, out, rows, cols, mu):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    def side(sd):
+        if sd is None:
+            return (0, 0, None, None, None, None, None, None)
+        Y, units, span, P, radius, ns = sd
+        return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(P), _ffi.dptr(radius))
+    pairs = _ffi.as_f64(pairs)
+    _ffi.call("mpcx_collision_probability", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
+              _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+
+
+def catalogue_covariance(position_m, velocity_m_s, P0, T0, T1, n, q=None, include_J2=True, max_step=DEFAULT_MAX_STEP, device=0,
+                         devices=None):
+    """catalogue_trajectories followed by covariance -> (Y, units, span, P): a catalogue given as D state vectors at the epoch T0 with
+    the covariance P0 ((6, 6) or (D, 6, 6); m, m/s) of each, propagated to T1 and sampled at n nodes, no thrust and no drag, every
+    object linearised under its own SatelliteScale constants.  What collision_probability takes as cat, beside the radii."""
+    from .satellite_scale import SatelliteScale
+    Y, units, span = catalogue_trajectories(position_m, velocity_m_s, T0, T1, n, include_J2=include_J2, device=device, devices=devices)
+    state = np.column_stack([_ffi.as_f64(position_m), _ffi.as_f64(velocity_m_s), np.ones(len(Y))])
+    consts = np.stack([SatelliteScale(x=x).get_normalized_constants().as_vector() for x in state])
+    P = covariance(Y, units, span, consts, P0, q=q, include_J2=include_J2, max_step=max_step, device=device, devices=devices)
+    return Y, units, span, P

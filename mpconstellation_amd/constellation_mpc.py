@@ -305,6 +305,32 @@ class ConstellationMPC:
                for w in self._screen_windows(what, samples_per_node, T0, T1)]
         return res[0] if len(res) == 1 else cj.combine(res)
 
+    def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None):
+        """Collision probabilities of the last plan's close approaches -> (ConjunctionResult, CollisionResult).  The plan is screened
+        at threshold_m (screen(what='plan'); screen_against when catalogue = (Y, units, span, P, radius) or (Y, units, span, P,
+        radius, ns) is given: the objects' trajectories, their covariances -- conjunction.catalogue_covariance -- and hard-body
+        radii); P0 ((6, 6) or (S, 6, 6); m, m/s), the covariance of every satellite at the plan's first node, is propagated along
+        (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere (plan_drag, plan_J2) with the acceleration
+        noise q (conjunction.covariance), and every listed pair gets its probability (conjunction.collision_probability; radius_m a
+        scalar or (S,)).  The plan only: a linearisation needs the thrust a trajectory was flown with, and ConstellationMPC does not
+        keep the thrust of its flown segments."""
+        from . import conjunction as cj
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        cat = None
+        if catalogue is None:
+            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
+        else:
+            if len(catalogue) not in (5, 6):
+                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
+            cat = tuple(catalogue)
+            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
+                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
+        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
+                          include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+        return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
+
     @staticmethod
     def _check(status):
         if (status == 1).any():

@@ -1,0 +1,527 @@
+// collision.hip -- from a screen's pairs list to collision probabilities (include/mpcx.h: mpcx_covariance_*, mpcx_collision_probability*).
+//   covariance_kernel              chains the state-transition matrices the discretiser integrates anyway (the A block of every stage
+//                                  record) into a position / velocity covariance at every node of every trajectory, in m and m/s;
+//   collision_probability_kernel   for every listed pair: both objects' states and position covariances at the pair's time of closest
+//                                  approach, the encounter plane, and the Gaussian's integral over the combined hard-body disc in it
+//                                  (the short-encounter model), by a fixed 64-point Gauss-Legendre rule.
+// Both are small next to the discretisation in front of them: they are written for a fixed operation order (the numpy restatement
+// tests/collision_reference.py follows it line by line), not for speed.  No atomics, nothing crosses a workgroup.
+#include "mpcx_host.hpp"
+
+#include <math.h>
+
+namespace mpcx {
+
+__device__ __forceinline__ double cp_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+__device__ __forceinline__ bool cp_finite(double x) { return fabs(x) < __longlong_as_double(0x7ff0000000000000LL); }
+
+// ---------------------------------------------------------------- covariance along trajectories
+
+// tf [S] of the linearisation: the span in the satellite's own time unit.  A satellite whose span and time unit give no positive
+// finite tf -- an empty span, a time unit that is zero, negative or not finite -- is linearised with tf = 1, so that the
+// discretiser's step-size control never sees a value it was not written for; covariance_kernel makes the same test and gives that
+// satellite MPCX_ST_BADK and NaN whatever the discretiser returns.
+__global__ __launch_bounds__(256) void covariance_tf_kernel(int S, const double *units, const double *span, double *tf)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
+    tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
+}
+
+struct CovArgs {
+    int S, K;
+    const int32_t *Ks;
+    const double *stage, *units, *span, *P0, *q;
+    const int32_t *dstat;             // the discretiser's status [S]
+    double *P;
+    int32_t *status;
+};
+
+// One wave per satellite; lane l < 36 owns entry (l / 6, l % 6) of the 6 x 6 matrices, the other lanes only help with the fills.
+// Per node interval: Phi~ = D Phi D^-1 into LDS, T = Phi~ P, then N = T Phi~^T + q Q(h).  Entry (i, j) and entry (j, i) of N run
+// the same operations on the same operands -- the sum for (min, max) -- so P is symmetric to the bit.  Sums run m = 0 .. 5 in order.
+__global__ __launch_bounds__(64) void covariance_kernel(CovArgs a)
+{
+    __shared__ double phi[36], Pm[36], T[36];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const bool own = lane < 36;
+    const int i = own ? lane / 6 : 0, j = own ? lane - 6 * (lane / 6) : 0;
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const int nn = a.Ks ? a.Ks[s] : a.K;
+    const double ta = a.span[2 * s], tb = a.span[2 * s + 1], Tu = a.units[2 * s + 1];
+    const double qs = a.q ? a.q[s] : 0.0;
+    double pij = a.P0[(size_t)s * 36 + lo * 6 + hi];                 // the upper triangle alone is read
+    int st = MPCX_ST_OK;
+    const double tfv = (tb - ta) / Tu;                               // (covariance_tf_kernel's test: no positive finite tf, no linearisation)
+    if (nn < 2 || nn > a.K || !(tb > ta) || !(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
+    else if (a.dstat[s] != MPCX_ST_OK) st = a.dstat[s];
+    else if (__any(own && !cp_finite(pij))) st = MPCX_ST_NUMERIC;
+    double *Ps = a.P + (size_t)s * a.K * 36;
+    if (lane == 0) a.status[s] = st;
+    if (st != MPCX_ST_OK) {
+        for (int e = lane; e < a.K * 36; e += 64) Ps[e] = cp_nan();
+        return;
+    }
+    for (int e = nn * 36 + lane; e < a.K * 36; e += 64) Ps[e] = 0.0;  // columns past the satellite's count
+    const double h = (tb - ta) / (double)(nn - 1);
+    // q Q(h), entry (lo, hi): [[h^3/3 I, h^2/2 I], [h^2/2 I, h I]]
+    double Qe = 0.0;
+    if (hi < 3) Qe = lo == hi ? h * h * h / 3.0 : 0.0;
+    else if (lo < 3) Qe = hi - 3 == lo ? h * h / 2.0 : 0.0;
+    else Qe = lo == hi ? h : 0.0;
+    const double qQ = qs * Qe;
+    if (own) { Pm[lane] = pij; Ps[lane] = pij; }
+    for (int k = 0; k + 1 < nn; ++k) {
+        const double *A = a.stage + ((size_t)s * (a.K - 1) + k) * MPCX_STAGE_DOUBLES;      // 7 x 7, row-major: its upper-left 6 x 6
+        if (own) {
+            const double f = A[i * 7 + j];
+            phi[lane] = i < 3 && j >= 3 ? f * Tu : (i >= 3 && j < 3 ? f / Tu : f);
+        }
+        __syncthreads();
+        if (own) {
+            double acc = phi[i * 6] * Pm[j];
+#pragma unroll
+            for (int m = 1; m < 6; ++m) acc = acc + phi[i * 6 + m] * Pm[m * 6 + j];
+            T[lane] = acc;
+        }
+        __syncthreads();
+        if (own) {
+            double acc = T[lo * 6] * phi[hi * 6];
+#pragma unroll
+            for (int m = 1; m < 6; ++m) acc = acc + T[lo * 6 + m] * phi[hi * 6 + m];
+            pij = acc + qQ;
+            Pm[lane] = pij;
+            Ps[(size_t)(k + 1) * 36 + lane] = pij;
+        }
+        __syncthreads();
+    }
+}
+
+// workspace of the _dev call: [stage S (K-1) records][tf S][zero thrust S 3 K][discretiser status S]
+struct CovWorkspace {
+    double *stage, *tf, *uzero;
+    int32_t *dstat;
+    size_t bytes;
+    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+    CovWorkspace(void *base, int S, int K)
+    {
+        char *p = (char *)base;
+        stage = (double *)p; p += al((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES * sizeof(double));
+        tf = (double *)p; p += al((size_t)S * sizeof(double));
+        uzero = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
+        dstat = (int32_t *)p; p += al((size_t)S * sizeof(int32_t));
+        bytes = (size_t)(p - (char *)base);
+    }
+};
+
+static int cov_check(mpcx_ctx *ctx, int S, int K, int flags, double max_step)
+{
+    if (S < 1 || K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "covariance: need S>=1, K>=2");
+    if (!(max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "covariance: max_step must be > 0");
+    if (flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
+        return ctx_fail(ctx, MPCX_E_BADARG, "covariance: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
+    return ctx_check_atmosphere(ctx, flags, "covariance");
+}
+
+// ---------------------------------------------------------------- collision probability of listed pairs
+
+// numpy.polynomial.legendre.leggauss(64): node, weight on [-1, 1]
+static __device__ const double CP_GL[64][2] = {
+    {-0x1.ffa4e911f7533p-1, 0x1.d379f1845dc3ap-10},
+    {-0x1.fe204ab274eccp-1, 0x1.0fc7ac3ac343cp-8},
+    {-0x1.fb661ac8c85a9p-1, 0x1.aa46b24145fd3p-8},
+    {-0x1.f777d976cfadap-1, 0x1.21e400109d579p-7},
+    {-0x1.f257e4db5aabcp-1, 0x1.6df524de84ee7p-7},
+    {-0x1.ec09586b58faap-1, 0x1.b9283b35df9afp-7},
+    {-0x1.e490081f2891bp-1, 0x1.01a7c0a5c98e8p-6},
+    {-0x1.dbf07d935a5afp-1, 0x1.261ef40a7a2dbp-6},
+    {-0x1.d22ff5221288ap-1, 0x1.49e391bd2143ep-6},
+    {-0x1.c7545aa8c0dadp-1, 0x1.6cdfe10bba379p-6},
+    {-0x1.bb6445eadae2cp-1, 0x1.8efea346845aep-6},
+    {-0x1.ae66f68eedbc6p-1, 0x1.b02b2071c0c24p-6},
+    {-0x1.a0644fb6d8db8p-1, 0x1.d05133c3af976p-6},
+    {-0x1.9164d335425e2p-1, 0x1.ef5d57d53b4a7p-6},
+    {-0x1.81719c62ec68ep-1, 0x1.069e593b92362p-5},
+    {-0x1.70945a96f12c3p-1, 0x1.14ee9010d92e2p-5},
+    {-0x1.5ed74b4532f83p-1, 0x1.22969f7b5c8c0p-5},
+    {-0x1.4c4533c68b412p-1, 0x1.2f8e3ca7574ecp-5},
+    {-0x1.38e95ace7b3c3p-1, 0x1.3bcd87e50de17p-5},
+    {-0x1.24cf81925487fp-1, 0x1.474d117092814p-5},
+    {-0x1.1003dca600f34p-1, 0x1.5205ddf5a36d5p-5},
+    {-0x1.f52619257c3a1p-2, 0x1.5bf16accdf42fp-5},
+    {-0x1.c9142c5898fc5p-2, 0x1.6509b1efb8df0p-5},
+    {-0x1.9becb55272c9dp-2, 0x1.6d492da0c250dp-5},
+    {-0x1.6dcb1f0620fffp-2, 0x1.74aadbc614fafp-5},
+    {-0x1.3ecb6c46c76cbp-2, 0x1.7b2a40f3ccdd4p-5},
+    {-0x1.0f0a26c56e49cp-2, 0x1.80c36b24bdd16p-5},
+    {-0x1.bd489b79ec83bp-3, 0x1.8572f41fbb52cp-5},
+    {-0x1.5b6e88ad5c00ep-3, 0x1.89360387fe3aap-5},
+    {-0x1.f182ff48e8a27p-4, 0x1.8c0a5097676bap-5},
+    {-0x1.2afad5ee95ad0p-4, 0x1.8dee238192cd4p-5},
+    {-0x1.8ef487a8cbc32p-6, 0x1.8ee0567ee2e54p-5},
+    {0x1.8ef487a8cbc32p-6, 0x1.8ee0567ee2e54p-5},
+    {0x1.2afad5ee95ad0p-4, 0x1.8dee238192cd4p-5},
+    {0x1.f182ff48e8a27p-4, 0x1.8c0a5097676bap-5},
+    {0x1.5b6e88ad5c00ep-3, 0x1.89360387fe3aap-5},
+    {0x1.bd489b79ec83bp-3, 0x1.8572f41fbb52cp-5},
+    {0x1.0f0a26c56e49cp-2, 0x1.80c36b24bdd16p-5},
+    {0x1.3ecb6c46c76cbp-2, 0x1.7b2a40f3ccdd4p-5},
+    {0x1.6dcb1f0620fffp-2, 0x1.74aadbc614fafp-5},
+    {0x1.9becb55272c9dp-2, 0x1.6d492da0c250dp-5},
+    {0x1.c9142c5898fc5p-2, 0x1.6509b1efb8df0p-5},
+    {0x1.f52619257c3a1p-2, 0x1.5bf16accdf42fp-5},
+    {0x1.1003dca600f34p-1, 0x1.5205ddf5a36d5p-5},
+    {0x1.24cf81925487fp-1, 0x1.474d117092814p-5},
+    {0x1.38e95ace7b3c3p-1, 0x1.3bcd87e50de17p-5},
+    {0x1.4c4533c68b412p-1, 0x1.2f8e3ca7574ecp-5},
+    {0x1.5ed74b4532f83p-1, 0x1.22969f7b5c8c0p-5},
+    {0x1.70945a96f12c3p-1, 0x1.14ee9010d92e2p-5},
+    {0x1.81719c62ec68ep-1, 0x1.069e593b92362p-5},
+    {0x1.9164d335425e2p-1, 0x1.ef5d57d53b4a7p-6},
+    {0x1.a0644fb6d8db8p-1, 0x1.d05133c3af976p-6},
+    {0x1.ae66f68eedbc6p-1, 0x1.b02b2071c0c24p-6},
+    {0x1.bb6445eadae2cp-1, 0x1.8efea346845aep-6},
+    {0x1.c7545aa8c0dadp-1, 0x1.6cdfe10bba379p-6},
+    {0x1.d22ff5221288ap-1, 0x1.49e391bd2143ep-6},
+    {0x1.dbf07d935a5afp-1, 0x1.261ef40a7a2dbp-6},
+    {0x1.e490081f2891bp-1, 0x1.01a7c0a5c98e8p-6},
+    {0x1.ec09586b58faap-1, 0x1.b9283b35df9afp-7},
+    {0x1.f257e4db5aabcp-1, 0x1.6df524de84ee7p-7},
+    {0x1.f777d976cfadap-1, 0x1.21e400109d579p-7},
+    {0x1.fb661ac8c85a9p-1, 0x1.aa46b24145fd3p-8},
+    {0x1.fe204ab274eccp-1, 0x1.0fc7ac3ac343cp-8},
+    {0x1.ffa4e911f7533p-1, 0x1.d379f1845dc3ap-10},
+};
+
+// one side of the list: the objects a pair's row or column index selects
+struct CpSide {
+    int N, K;
+    const int32_t *Ks;
+    const double *Y, *units, *span, *P, *radius;
+};
+
+struct CpArgs {
+    int n;
+    const double *pairs;
+    CpSide row, col;
+    double mu;
+    double *out;
+    int32_t *status;
+};
+
+// Object `fidx` (an index as the pairs list holds it: a double) of one side at time t: position p, velocity v from the cubic Hermite
+// on its own nodes (ephemeris_kernel's formulas), position covariance C = (c00, c01, c02, c11, c12, c22) from the covariance at the
+// nearest node carried over dt by the short-arc two-body transition, radius.  Returns MPCX_ST_OK or MPCX_ST_BADK (no such object,
+// a node count outside 2..K, an empty span, t outside the span); on BADK nothing is written and no memory of the object is read.
+__device__ __forceinline__ int cp_object(const CpSide &sd, double fidx, double t, double mu, double (&p)[3], double (&v)[3], double (&C)[6],
+                                         double &radius)
+{
+    if (!(fidx >= 0.0 && fidx < (double)sd.N)) return MPCX_ST_BADK;
+    const int o = (int)fidx;
+    const int nn = sd.Ks ? sd.Ks[o] : sd.K;
+    const double ta = sd.span[2 * o], tb = sd.span[2 * o + 1];
+    if (nn < 2 || nn > sd.K || !(tb > ta) || !(t >= ta && t <= tb)) return MPCX_ST_BADK;
+    const double hn = (tb - ta) / (double)(nn - 1);
+    const double u = (t - ta) / hn;
+    int k = (int)u;
+    if (k > nn - 2) k = nn - 2;
+    if (k < 0) k = 0;
+    const double sg = u - (double)k, s2 = sg * sg, s3 = s2 * sg;
+    const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + sg, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
+    const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
+    const double L = sd.units[2 * o], V = L / sd.units[2 * o + 1];
+    const double *y = sd.Y + (size_t)o * 7 * sd.K;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double p0 = y[(size_t)c * sd.K + k] * L, p1 = y[(size_t)c * sd.K + k + 1] * L;
+        const double m0 = hn * (y[(size_t)(3 + c) * sd.K + k] * V), m1 = hn * (y[(size_t)(3 + c) * sd.K + k + 1] * V);
+        p[c] = h00 * p0 + h10 * m0 + h01 * p1 + h11 * m1;
+        v[c] = (g00 * p0 + g10 * m0 + g01 * p1 + g11 * m1) / hn;
+    }
+    // the nearest node, the time from it, and the gravity gradient there
+    const int kc = k + (sg >= 0.5 ? 1 : 0);
+    const double dt = t - (ta + (double)kc * hn);
+    double r[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = y[(size_t)c * sd.K + kc] * L;
+    const double r2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+    const double r1 = sqrt(r2), r5 = r2 * r2 * r1;
+    const double ca = dt * dt / 2.0, cb = dt * dt * dt / 6.0;
+    double F[3][6];                                                  // Phi_r = [ I + G dt^2/2 | dt I + G dt^3/6 ]
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const double G = mu * (3.0 * r[a] * r[b] - (a == b ? r2 : 0.0)) / r5;
+            F[a][b] = (a == b ? 1.0 : 0.0) + G * ca;
+            F[a][3 + b] = (a == b ? dt : 0.0) + G * cb;
+        }
+    }
+    const double *Pk = sd.P + ((size_t)o * sd.K + kc) * 36;
+    double M[3][6];                                                  // Phi_r P
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+        double col[6];
+#pragma unroll
+        for (int n = 0; n < 6; ++n) col[n] = Pk[n * 6 + m];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double acc = F[a][0] * col[0];
+#pragma unroll
+            for (int n = 1; n < 6; ++n) acc = acc + F[a][n] * col[n];
+            M[a][m] = acc;
+        }
+    }
+    int e = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            double acc = M[a][0] * F[b][0];
+#pragma unroll
+            for (int m = 1; m < 6; ++m) acc = acc + M[a][m] * F[b][m];
+            C[e++] = acc;
+        }
+    }
+    radius = sd.radius[o];
+    return MPCX_ST_OK;
+}
+
+// 1/2 [erf(b) - erf(a)] for a <= b, through erfc on the side where both are: the difference of two values near 1 keeps no digits
+__device__ __forceinline__ double cp_half_erf_diff(double a, double b)
+{
+    if (a > 0.0) return 0.5 * (erfc(a) - erfc(b));
+    if (b < 0.0) return 0.5 * (erfc(-b) - erfc(-a));
+    return 0.5 * (erf(b) - erf(a));
+}
+
+// One wave per pair, lane l is quadrature node l.  The setup is the same for all 64 lanes and computed by all of them; the sum is
+// an xor butterfly (every lane ends with the same bits), lane 0 stores.
+__global__ __launch_bounds__(64) void collision_probability_kernel(CpArgs a)
+{
+    const int pr = blockIdx.x, lane = threadIdx.x;
+    if (pr >= a.n) return;
+    const double *row = a.pairs + (size_t)pr * 4;
+    const double t = row[3];
+    double o[MPCX_NPC];
+#pragma unroll
+    for (int c = 0; c < MPCX_NPC; ++c) o[c] = cp_nan();
+    int st;
+    double pa[3], va[3], Ca[6], Ra, pb[3], vb[3], Cb[6], Rb;
+    st = cp_object(a.row, row[0], t, a.mu, pa, va, Ca, Ra);
+    if (st == MPCX_ST_OK) st = cp_object(a.col, row[1], t, a.mu, pb, vb, Cb, Rb);
+    if (st == MPCX_ST_OK) {
+        double d[3], w[3], Cs[6];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { d[c] = pb[c] - pa[c]; w[c] = vb[c] - va[c]; }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
+        const double wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        const double R = Ra + Rb;
+        if (!(wn > 0.0) || !cp_finite(wn) || !cp_finite(R)) st = MPCX_ST_NUMERIC;
+        else {
+            double ew[3], m[3], e1[3], e2[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ew[c] = w[c] / wn;
+            const double dw = d[0] * ew[0] + d[1] * ew[1] + d[2] * ew[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = d[c] - dw * ew[c];
+            const double mn = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+            if (mn > 0.0) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = m[c] / mn;
+            } else {
+                // the coordinate axis on which |e_w| is smallest (the first of equal ones), made orthogonal to e_w
+                int ax = 0;
+                double ea = ew[0];
+                if (fabs(ew[1]) < fabs(ea)) { ax = 1; ea = ew[1]; }
+                if (fabs(ew[2]) < fabs(ea)) { ax = 2; ea = ew[2]; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = (c == ax ? 1.0 : 0.0) - ea * ew[c];
+                const double en = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = e1[c] / en;
+            }
+            e2[0] = ew[1] * e1[2] - ew[2] * e1[1];
+            e2[1] = ew[2] * e1[0] - ew[0] * e1[2];
+            e2[2] = ew[0] * e1[1] - ew[1] * e1[0];
+            // C2 = E^T Cs E; Cs = (c00, c01, c02, c11, c12, c22)
+            double g1[3], g2[3];                                     // Cs e1, Cs e2
+            g1[0] = Cs[0] * e1[0] + Cs[1] * e1[1] + Cs[2] * e1[2];
+            g1[1] = Cs[1] * e1[0] + Cs[3] * e1[1] + Cs[4] * e1[2];
+            g1[2] = Cs[2] * e1[0] + Cs[4] * e1[1] + Cs[5] * e1[2];
+            g2[0] = Cs[0] * e2[0] + Cs[1] * e2[1] + Cs[2] * e2[2];
+            g2[1] = Cs[1] * e2[0] + Cs[3] * e2[1] + Cs[4] * e2[2];
+            g2[2] = Cs[2] * e2[0] + Cs[4] * e2[1] + Cs[5] * e2[2];
+            const double c11 = e1[0] * g1[0] + e1[1] * g1[1] + e1[2] * g1[2];
+            const double c12 = e1[0] * g2[0] + e1[1] * g2[1] + e1[2] * g2[2];
+            const double c22 = e2[0] * g2[0] + e2[1] * g2[1] + e2[2] * g2[2];
+            // eigenvalues l1 >= l2 (the smaller one as det / l1: no cancellation) and the angle of the first axis
+            const double tr = c11 + c22, df = c11 - c22;
+            const double l1 = 0.5 * (tr + sqrt(df * df + 4.0 * c12 * c12));
+            const double l2 = (c11 * c22 - c12 * c12) / l1;
+            if (!(l2 > 0.0) || !cp_finite(l2) || !cp_finite(l1)) st = MPCX_ST_NUMERIC;
+            else {
+                const double ph = 0.5 * atan2(2.0 * c12, df);
+                const double xm = mn * cos(ph), ym = -mn * sin(ph);
+                const double s1 = sqrt(l1), s2 = sqrt(l2);
+                double pc = 0.0;
+                if (R > 0.0) {
+                    const double th = 1.5707963267948966 * CP_GL[lane][0], wt = 1.5707963267948966 * CP_GL[lane][1];
+                    const double x = R * sin(th), cx = R * cos(th);
+                    const double den = 1.4142135623730951 * s2;
+                    const double band = cp_half_erf_diff((ym - cx) / den, (ym + cx) / den);
+                    const double z = (x - xm) / s1;
+                    double f = wt * (band * (exp(-0.5 * z * z) / (2.5066282746310002 * s1)) * cx);
+#pragma unroll
+                    for (int sh = 32; sh >= 1; sh >>= 1) f = f + __shfl_xor(f, sh);
+                    pc = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);
+                }
+                o[MPCX_PC_P] = pc; o[MPCX_PC_MISS] = mn; o[MPCX_PC_SPEED] = wn; o[MPCX_PC_SIGMA1] = s1; o[MPCX_PC_SIGMA2] = s2;
+                o[MPCX_PC_MAHAL] = sqrt(xm * xm / l1 + ym * ym / l2);
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < MPCX_NPC; ++c) a.out[(size_t)pr * MPCX_NPC + c] = o[c];
+        a.status[pr] = st;
+    }
+}
+
+struct CpCall {
+    int n;
+    const double *pairs;
+    int S, K;
+    const int32_t *Ks;
+    const double *Y, *units, *span, *P, *radius;
+    int D, cat_K;
+    const int32_t *cat_Ks;
+    const double *cat_Y, *cat_units, *cat_span, *cat_P, *cat_radius;
+    double mu;
+    double *out;
+    int32_t *status;
+};
+
+static int cp_check(mpcx_ctx *ctx, const CpCall &c)
+{
+    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: need n>=1, S>=1, K>=2, mu>0");
+    if (!c.pairs || !c.Y || !c.units || !c.span || !c.P || !c.radius || !c.out || !c.status)
+        return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: pairs, Y, units, span, P, radius, out and status are required");
+    if (c.cat_Y) {
+        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: a catalogue needs D>=1, cat_K>=2");
+        if (!c.cat_units || !c.cat_span || !c.cat_P || !c.cat_radius)
+            return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: cat_units, cat_span, cat_P and cat_radius are required with cat_Y");
+    }
+    return MPCX_OK;
+}
+
+}  // namespace mpcx
+
+using namespace mpcx;
+
+extern "C" size_t mpcx_covariance_workspace_bytes(int S, int K)
+{
+    if (S < 1 || K < 2) return 0;
+    return CovWorkspace(nullptr, S, K).bytes;
+}
+
+extern "C" int mpcx_covariance_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U, const double *units,
+                                         const double *span, const double *consts, int flags, double max_step, const double *P0,
+                                         const double *q, double *P, int32_t *status, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    if (int rc = cov_check(ctx, S, K, flags, max_step)) return rc;
+    if (!X || !units || !span || !consts || !P0 || !P || !status || !workspace)
+        return ctx_fail(ctx, MPCX_E_BADARG, "covariance: X, units, span, consts, P0, P, status and workspace are required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = (hipStream_t)stream;
+    const CovWorkspace ws(workspace, S, K);
+    hipLaunchKernelGGL(covariance_tf_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, units, span, ws.tf);
+    MPCX_HIP(ctx, hipGetLastError());
+    if (!U) MPCX_HIP(ctx, hipMemsetAsync(ws.uzero, 0, (size_t)S * 3 * K * sizeof(double), st));
+    if (int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, X, U ? U : ws.uzero, ws.tf, consts, flags, max_step, ws.stage, ws.dstat, st))
+        return rc;
+    const CovArgs a{S, K, Ks, ws.stage, units, span, P0, q, ws.dstat, P, status};
+    hipLaunchKernelGGL(covariance_kernel, dim3((unsigned)S), dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
+extern "C" int mpcx_covariance_batch(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U, const double *units,
+                                     const double *span, const double *consts, int flags, double max_step, const double *P0, const double *q,
+                                     double *P, int32_t *status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    if (int rc = cov_check(ctx, S, K, flags, max_step)) return rc;
+    if (!X || !units || !span || !consts || !P0 || !P || !status)
+        return ctx_fail(ctx, MPCX_E_BADARG, "covariance: X, units, span, consts, P0, P and status are required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *dX = ar.upload(X, (size_t)S * 7 * K), *dU = U ? ar.upload(U, (size_t)S * 3 * K) : nullptr;
+    double *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST);
+    double *dP0 = ar.upload(P0, (size_t)S * 36), *dq = q ? ar.upload(q, S) : nullptr;
+    int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr;
+    double *dP = ar.alloc<double>((size_t)S * K * 36);
+    int32_t *dst = ar.alloc<int32_t>(S);
+    char *dws = ar.alloc<char>(mpcx_covariance_workspace_bytes(S, K));
+    if (ar.failed()) return ar.code();
+    if (int rc = mpcx_covariance_batch_dev(ctx, S, K, dKs, dX, dU, du, dsp, dc, flags, max_step, dP0, dq, dP, dst, dws, ctx->stream)) return rc;
+    ar.download(P, dP, (size_t)S * K * 36);
+    ar.download(status, dst, S);
+    return ar.finish();
+}
+
+static int cp_enqueue(mpcx_ctx *ctx, const CpCall &c, hipStream_t st)
+{
+    const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
+    const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
+    const CpArgs a{c.n, c.pairs, row, col, c.mu, c.out, c.status};
+    hipLaunchKernelGGL(collision_probability_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
+extern "C" int mpcx_collision_probability_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                              const double *units, const double *span, const double *P, const double *radius, int D,
+                                              int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units,
+                                              const double *cat_span, const double *cat_P, const double *cat_radius, double mu, double *out,
+                                              int32_t *status, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const CpCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu, out, status};
+    if (int rc = cp_check(ctx, c)) return rc;
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    return cp_enqueue(ctx, c, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_collision_probability(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                          const double *units, const double *span, const double *P, const double *radius, int D, int cat_K,
+                                          const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                                          const double *cat_P, const double *cat_radius, double mu, double *out, int32_t *status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const CpCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu, out, status};
+    if (int rc = cp_check(ctx, c)) return rc;
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    CpCall d = c;
+    d.pairs = ar.upload(pairs, (size_t)n * 4);
+    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2);
+    d.P = ar.upload(P, (size_t)S * K * 36); d.radius = ar.upload(radius, S);
+    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
+    if (cat_Y) {
+        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
+        d.cat_span = ar.upload(cat_span, (size_t)D * 2); d.cat_P = ar.upload(cat_P, (size_t)D * cat_K * 36);
+        d.cat_radius = ar.upload(cat_radius, D);
+        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
+    }
+    d.out = ar.alloc<double>((size_t)n * MPCX_NPC);
+    d.status = ar.alloc<int32_t>(n);
+    if (ar.failed()) return ar.code();
+    if (int rc = cp_enqueue(ctx, d, ctx->stream)) return rc;
+    ar.download(out, d.out, (size_t)n * MPCX_NPC);
+    ar.download(status, d.status, n);
+    return ar.finish();
+}
