@@ -681,6 +681,94 @@ int mpcx_collision_probability_dev(mpcx_ctx *ctx, int n, const double *pairs, in
                                    const double *cat_span, const double *cat_P, const double *cat_radius, double mu, double *out,
                                    int32_t *status, void *stream);
 
+/*
+ * Avoidance manoeuvres for screened pairs from thrust sensitivities.  The screens say who comes close and when, the probability how
+ * much that matters; this says what to change in the plan.  For every row (i, j, distance, time t in s) of a pairs list: the
+ * derivative of the encounter-plane miss with respect to every thrust node of the plan (the B-plane sensitivity), by a backward
+ * (adjoint) sweep over the stage records the discretiser integrates anyway, and from it the least-effort thrust change that opens
+ * the miss to `target`.  Nothing in the reference does this.
+ *
+ * Inputs.  pairs [n][4] exactly as the screens write them (the distance is not read).  The row side is the constellation's plan,
+ * as mpcx_covariance_batch takes it: S, K, Ks, Y [S][7][K], U [S][3][K] (required), units, span, consts, flags, max_step; P
+ * [S][K][6][6] optional.  The column side D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P: cat_Y = NULL means j indexes the
+ * constellation (the all-pairs screen; the other cat_ arguments are ignored), otherwise the catalogue, as in
+ * mpcx_collision_probability.  mu in m^3/s^2.  target > 0.  who: 0 the row object i manoeuvres, 1 object j, 2 both; 1 and 2 only
+ * in the all-pairs form (a catalogue object is not ours to move).
+ *
+ * Linearisation: exactly mpcx_covariance_batch's -- tf = (span[1] - span[0]) / units[1], mpcx_discretize_stages_ragged_dev with
+ * Ku = K, Kus = Ks, once per call for all S satellites, into the call's workspace.  The input convention is the reference's
+ * (optimizer.py:334-335): x_k+1 = A_k x_k + B_kn[k] u_k + B_kp[k] u_k+1 + ..., B_kn multiplies the CURRENT node's thrust and B_kp
+ * the NEXT node's (with the two swapped the sensitivities of a thrusting LEO arc miss central differences of the nonlinear flow by
+ * 3.5 to 4.7 % of the largest entry instead of 0.24 to 0.35 %: tests/test_avoidance_host.py).  tf is held fixed: a thrust change
+ * does not move the nodes' times.
+ *
+ * Encounter frame.  Both objects' position and velocity at t by the cubic Hermite on their own nodes (mpcx_ephemeris_batch's
+ * formulas: u = (t - t_a) / h_n, k = clamp(floor u, 0, ns - 2), s = u - k), d = p_b - p_a, w = v_b - v_a, and e_w, e_1, e_2 exactly
+ * as mpcx_collision_probability defines them, its |m| = 0 rule included.  In this frame the miss is (|m|, 0).
+ *
+ * Sensitivities of a manoeuvring object (7-state adjoint, normalised units).  L, Tu its units, h_tau = tf / (ns - 1), h00, h10,
+ * h01, h11 the Hermite basis at s.  The library's own p(t) is linear in the two bracketing node states:
+ *   Lam_k+1 = L [h01 I | h_tau h11 I | 0],  Lam_k = L [h00 I | h_tau h10 I | 0]   (3 x 7, metres),
+ *   R = sgn [e_1 e_2 e_w]^T (3 x 3), sgn = -1 for object i (d = p_b - p_a), +1 for object j,
+ *   lam_k+1 = R Lam_k+1,  lam_k = lam_k+1 A_k + R Lam_k,  lam_m = lam_m+1 A_m for m = k-1 .. 0,
+ *   g_m = lam_m+1 B_kn[m] (m <= k) + lam_m B_kp[m-1] (1 <= m <= k+1):  3 x 3, metres per unit of normalised thrust at node m;
+ * g_k+1 = lam_k+1 B_kp[k], g_0 = lam_1 B_kn[0], g_m = 0 for m > k + 1.  Every sum runs its index in ascending order.
+ *
+ * Effort metric (physical, so that satellites in different units can share one manoeuvre).  c_m = (L / Tu^2) / Y[6][m]: m/s^2
+ * per unit of normalised thrust at node m; ghat_m = g_m / c_m; w_m = h_n seconds, halved at m = 0 and m = ns - 1 (the trapezoid
+ * rule).  The authority matrix of the encounter-plane rows is M = sum_m ghat_m[0:2] ghat_m[0:2]^T / w_m (2 x 2, symmetric); with
+ * who = 2, M = M_i + M_j.  det M <= 0 or a non-finite M: MPCX_ST_SINGULAR (no authority: t at the first node, say).
+ *
+ * Target metric.  With covariances W = C_2^-1, C_2 the combined 2 x 2 encounter-plane covariance exactly as
+ * mpcx_collision_probability forms it (nearest node, short-arc rows): target is a Mahalanobis distance.  P = NULL (and cat_P = NULL
+ * with a catalogue): W = I, target is a miss distance in metres.  One of P, cat_P without the other with a catalogue:
+ * MPCX_E_BADARG.  d0 = sqrt(m^T W m).
+ *
+ * Manoeuvre.  d0 >= target: no change -- du, DM1, DM2, DT, DV_*, UMAX_* are 0, D1 = D0, MISS1 = |m|, status OK.  Otherwise the
+ * encounter-plane displacement is dm = alpha p, p = M W (1, 0)^T: the direction in which m^T W m grows fastest per unit of effort;
+ * alpha >= 0 the root of (m + alpha p)^T W (m + alpha p) = target^2 in the cancellation-free form alpha = -c / (b + sqrt(b^2 - a c))
+ * (a = p^T W p, b = m^T W p, c = m^T W m - target^2).  With lambda = M^-1 dm every manoeuvring object gets
+ * da_m = ghat_m[0:2]^T lambda / w_m (m/s^2) and du_m = da_m / c_m (normalised thrust, the plan's own units).  This du is the exact
+ * least-effort (integral of |da|^2 dt, trapezoid rule) thrust change for that dm.  The DIRECTION is the first-order optimum, not
+ * the optimum over the whole target ellipse: with W = I or M W a multiple of the identity the two coincide; with an anisotropic W
+ * (axis ratio 10, the miss at 45 degrees to the axes) a scan over the ellipse finds a point that costs less -- by 5.4e-6 of the
+ * effort on the test scene (tests/test_avoidance_host.py, profiles/avoidance.txt): there is a gap, and there it is small.
+ *
+ * Outputs.  out [n][MPCX_NAV] (MPCX_AV_*); du [n][NS][3][K], NS = 2 in the all-pairs form (slot 0 = i, 1 = j) and 1 with a
+ * catalogue: nodes past k + 1 and the slot of an object that does not move are 0; sens [n][NS][3][3][K] (may be NULL: not written),
+ * the g_m ordered row, thrust component, node.  du and out have the same bits with and without sens.  status [n]: MPCX_ST_BADK an
+ * index outside its side, a node count outside 2..K, an empty span, t outside a span, a manoeuvring satellite without a positive
+ * finite tf; MPCX_ST_NUMERIC whatever has that status in mpcx_collision_probability (|w| zero or not finite, l_2 <= 0 or not
+ * finite); the discretiser's status of a manoeuvring satellite, passed on; MPCX_ST_SINGULAR as above.  A failed row is NaN in
+ * out, du and sens; its neighbours are untouched.  n < 1, S < 1, K < 2, mu <= 0, target not a positive finite number, who outside
+ * 0..2 or not 0 with a catalogue, max_step <= 0, an unknown flag or MPCX_FLAG_ATMO without drag or an atmosphere (as on
+ * mpcx_covariance_batch): MPCX_E_BADARG, nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_avoidance_workspace_bytes(n, S, K) bytes (the stage
+ * records, tf, the discretiser's status, the g_m when sens is NULL; 0 for n < 1, S < 1 or K < 2; contents unspecified on entry
+ * and exit).  Results do not depend on the launch shape, on the block of rows a row is computed in, or on the device count.
+ */
+enum { MPCX_AV_D0 = 0,      /* d0: the distance now, in the target's metric */
+       MPCX_AV_D1,          /* the predicted distance after the manoeuvre, in the target's metric */
+       MPCX_AV_DM1,         /* dm in the (e_1, e_2) frame, m */
+       MPCX_AV_DM2,
+       MPCX_AV_MISS1,       /* |m + dm|, m */
+       MPCX_AV_DT,          /* shift of the time of closest approach, -(e_w row of sum_m g_m du_m) / |w|, s */
+       MPCX_AV_DV_I,        /* sum_m w_m |da_m| per object, m/s (0 for one that does not move) */
+       MPCX_AV_DV_J,
+       MPCX_AV_UMAX_I,      /* max_m |du_m| per object, to compare with u_max */
+       MPCX_AV_UMAX_J,
+       MPCX_NAV };
+size_t mpcx_avoidance_workspace_bytes(int n, int S, int K);
+int mpcx_avoidance(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y, const double *U,
+                   const double *units, const double *span, const double *consts, int flags, double max_step, const double *P,
+                   int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                   const double *cat_P, double mu, double target, int who, double *out, double *du, double *sens, int32_t *status);
+int mpcx_avoidance_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y, const double *U,
+                       const double *units, const double *span, const double *consts, int flags, double max_step, const double *P,
+                       int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                       const double *cat_P, double mu, double target, int who, double *out, double *du, double *sens,
+                       int32_t *status, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

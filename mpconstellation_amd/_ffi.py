@@ -133,9 +133,18 @@ _SIGS = {
     "mpcx_collision_probability": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2 + [C.c_double, _dp, _ip]),
     "mpcx_collision_probability_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
                                        + [C.c_double, _vp, _vp, _vp]),
+    # avoidance manoeuvres for screened pairs: thrust sensitivities of the encounter-plane miss, least-effort thrust change
+    "mpcx_avoidance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_avoidance": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                 C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _ip]),
+    "mpcx_avoidance_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
+                                     C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
 }
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
+NAV = 10                                                                    # MPCX_NAV: columns of mpcx_avoidance's out
+AV_D0, AV_D1, AV_DM1, AV_DM2, AV_MISS1, AV_DT, AV_DV_I, AV_DV_J, AV_UMAX_I, AV_UMAX_J = range(NAV)
 
 
 def _sat_twin(name):

@@ -12,7 +12,9 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
-  catalogue_covariance    catalogue_trajectories followed by covariance.
+  catalogue_covariance    catalogue_trajectories followed by covariance;
+  avoidance      for every listed pair the derivative of the encounter-plane miss with respect to every thrust node of the plan, and
+                 the least-effort thrust change that opens the miss to a requested distance.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
 import numpy as np
@@ -423,3 +425,135 @@ def catalogue_covariance(position_m, velocity_m_s, P0, T0, T1, n, q=None, includ
     consts = np.stack([SatelliteScale(x=x).get_normalized_constants().as_vector() for x in state])
     P = covariance(Y, units, span, consts, P0, q=q, include_J2=include_J2, max_step=max_step, device=device, devices=devices)
     return Y, units, span, P
+
+
+# ---- from a pairs list to avoidance manoeuvres (include/mpcx.h: mpcx_avoidance; csrc/avoidance.hip)
+_WHO = {"i": 0, "j": 1, "both": 2}
+
+
+class AvoidanceResult:
+    """For the n rows of `pairs` (i, j, distance, time), row for row: d0 (n,) the distance now and d1 (n,) the predicted distance
+    after the manoeuvre, both in the target's metric (metres, or Mahalanobis with covariances); dm (n, 2) the encounter-plane
+    displacement in the (e_1, e_2) frame (m); miss1 (n,) the predicted miss |m + dm| (m); dt (n,) the shift of the time of closest
+    approach (s); dv (n, 2) the cost per object, sum of w_m |da_m| (m/s), and umax (n, 2) its largest thrust change max_m |du_m|
+    (normalised, to compare with u_max) -- column 0 object i, column 1 object j, 0 for one that does not move; du (n, NS, 3, K) the
+    thrust change per node in the plan's own units (NS = 2: slots i, j; NS = 1 against a catalogue), sens (n, NS, 3, 3, K) the
+    sensitivities g_m (row e_1 / e_2 / e_w, thrust component, node) or None; status (n,) int32 MPCX_ST_* (a row whose status is not
+    0 is NaN in all of them)."""
+
+    def __init__(self, pairs, out, du, sens, status):
+        self.pairs, self.du, self.sens, self.status = pairs, du, sens, status
+        self.d0, self.d1, self.miss1, self.dt = out[:, _ffi.AV_D0], out[:, _ffi.AV_D1], out[:, _ffi.AV_MISS1], out[:, _ffi.AV_DT]
+        self.dm = out[:, _ffi.AV_DM1:_ffi.AV_DM2 + 1]
+        self.dv, self.umax = out[:, _ffi.AV_DV_I:_ffi.AV_DV_J + 1], out[:, _ffi.AV_UMAX_I:_ffi.AV_UMAX_J + 1]
+        self.out = out
+
+    def __repr__(self):
+        return f"AvoidanceResult(pairs={len(self.pairs)})"
+
+    def apply(self, U, row):
+        """a copy of the plan thrust U (S, 3, K) with pair `row`'s du added to its satellites"""
+        U = np.array(U, dtype=np.float64)
+        if U.ndim != 3 or U.shape[1:] != self.du.shape[2:]:
+            raise ValueError(f"U: expected (S, 3, {self.du.shape[3]}) plan thrust, got {U.shape}")
+        if self.status[row] != 0:
+            raise ValueError(f"pair {row} has no manoeuvre: {_ffi.STATUS_TEXT.get(int(self.status[row]), int(self.status[row]))}")
+        for slot in range(self.du.shape[1]):
+            U[int(self.pairs[row, slot])] += self.du[row, slot]
+        return U
+
+
+def _check_cat(cat):
+    """cat = (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]) of avoidance -> (Y, units, span, ns, P or None)"""
+    if not 3 <= len(cat) <= 5:
+        raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]), got {len(cat)} items")
+    rest = list(cat[3:])
+    P = rest.pop(0) if rest and rest[0] is not None and np.ndim(rest[0]) == 4 else None
+    if len(rest) > 1:
+        raise ValueError("cat: after cat_span come cat_P (D, n, 6, 6) and cat_ns (D,), in this order")
+    Y, units, span, ns = _check_trajectories(cat[0], cat[1], cat[2], rest[0] if rest else None, "cat_")
+    if Y.shape[2] < 2:
+        raise ValueError(f"cat_Y: need at least 2 nodes, got {Y.shape}")
+    if P is not None:
+        P = _ffi.as_f64(P)
+        if P.shape != (Y.shape[0], Y.shape[2], 6, 6):
+            raise ValueError(f"cat_P: expected ({Y.shape[0]}, {Y.shape[2]}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
+    return Y, units, span, ns, P
+
+
+def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", include_drag=False, include_J2=False,
+              atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None, return_sensitivities=False, device=0, devices=None):
+    """The least-effort thrust change that opens every listed close approach to `target` -> AvoidanceResult.  pairs: (n, 4) rows
+    (i, j, distance, time in s) as screen and screen_against list them, or their ConjunctionResult; Y (S, 7, n), U (S, 3, n), units,
+    span, consts (S, 8) [, ns] the plan that was screened, linearised under include_drag / include_J2 / atmosphere as covariance
+    does.  P (S, n, 6, 6) (covariance): target is a Mahalanobis distance in the combined encounter-plane covariance; None: target is
+    a miss distance in metres.  cat = (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]): j indexes this catalogue and only the
+    satellite moves (cat_P exactly when P is given); None: j indexes the constellation and who = "i", "j" or "both" says which of the
+    two moves.  The device sweeps the adjoint of the encounter-plane miss backwards over the linearisation's A, B_kn, B_kp to the
+    derivative with respect to every thrust node (return_sensitivities=True returns them), and moves the miss in the direction that
+    gains distance fastest per unit of effort -- the first-order optimum, not the optimum over the whole target ellipse
+    (include/mpcx.h).  A pair already at or beyond the target gets du = 0.  An empty list returns empty arrays without a library
+    call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
+    from .constants import MU_EARTH
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    if not (np.ndim(target) == 0 and np.isfinite(target) and target > 0.0):
+        raise ValueError(f"target: need a positive finite distance, got {target}")
+    if who not in _WHO:
+        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, K = Y.shape
+    if K < 2:
+        raise ValueError(f"Y: need at least 2 nodes, got {Y.shape}")
+    U, consts = _ffi.as_f64(U), _ffi.as_f64(consts)
+    if U.shape != (S, 3, K):
+        raise ValueError(f"U: expected ({S}, 3, {K}) thrust at the nodes, got {U.shape}")
+    if consts.shape != (S, _ffi.NCONST):
+        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
+    if P is not None:
+        P = _ffi.as_f64(P)
+        if P.shape != (S, K, 6, 6):
+            raise ValueError(f"P: expected ({S}, {K}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
+    cols = None
+    if cat is not None:
+        cols = _check_cat(cat)
+        if who != "i":
+            raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
+        if (P is None) != (cols[4] is None):
+            raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
+    if not max_step > 0.0:
+        raise ValueError(f"max_step: need > 0, got {max_step}")
+    mu = float(MU_EARTH if mu is None else mu)
+    if not mu > 0.0:
+        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    n, NS = pairs.shape[0], 1 if cols is not None else 2
+    out = dict(out=np.empty((n, _ffi.NAV)), du=_ffi.result_pool.take((n, NS, 3, K)),
+               sens=_ffi.result_pool.take((n, NS, 3, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
+    if n:
+        how = dict(rows=(Y, U, units, span, consts, ns, P), cols=cols, mu=mu, target=float(target), who=_WHO[who],
+                   flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(_avoidance_call, devices, [pairs], out, **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            _avoidance_call(pairs, device=device, slot=0, out=out, **how)
+    return AvoidanceResult(pairs, out["out"], out["du"], out["sens"], out["status"])
+
+
+def _avoidance_call(pairs, *, device, slot, out, rows, cols, mu, target, who, flags, max_step, atmosphere):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    Y, U, units, span, consts, ns, P = rows
+    col = (0, 0, None, None, None, None, None)
+    if cols is not None:
+        cY, cunits, cspan, cns, cP = cols
+        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    pairs = _ffi.as_f64(pairs)
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_avoidance", ctx, len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
+              _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu, target, who,
+              _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))

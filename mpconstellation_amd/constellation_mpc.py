@@ -331,6 +331,35 @@ class ConstellationMPC:
                           include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
 
+    def avoidance(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i"):
+        """Avoidance manoeuvres for the last plan's close approaches -> (ConjunctionResult, AvoidanceResult).  The plan is screened
+        at threshold_m as collision_probability screens it (screen(what='plan'); screen_against when catalogue = (Y, units, span),
+        (Y, units, span, P) or (Y, units, span, P, ns) is given); with P0 ((6, 6) or (S, 6, 6); m, m/s) the satellites' covariance
+        is propagated along the plan with the acceleration noise q and `target` is a Mahalanobis distance (a catalogue then needs
+        its P), without it `target` is a miss distance in metres; every listed pair gets the least-effort thrust change of
+        conjunction.avoidance on (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere; who = 'i', 'j'
+        or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceResult.apply(plan U, row) is the changed
+        thrust table; feeding it back into the solver's constraints is not done here."""
+        from . import conjunction as cj
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
+        cat = None
+        if catalogue is None:
+            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
+        else:
+            if not 3 <= len(catalogue) <= 5:
+                raise ValueError(f"catalogue: expected (Y, units, span[, P][, ns]), got {len(catalogue)} items")
+            cat = tuple(catalogue)
+            cat_ns = cj._check_cat(cat)[3]
+            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2], cat_ns=cat_ns, **where, **w, **kw)
+        P = None
+        if P0 is not None:
+            P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
+        return screened, cj.avoidance(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, ns=w["ns"], P=P, cat=cat,
+                                      who=who, **model, **where)
+
     @staticmethod
     def _check(status):
         if (status == 1).any():

@@ -1,0 +1,79 @@
+"""profiling helper: duration of the avoidance manoeuvre by HIP events on its stream.
+  mpcx_avoidance_dev for n = 1024 and n = 65 536 rows in the all-pairs form: random pairs (i < j) of S = 4096 thrusting satellites of a
+  random LEO shell, K = 30 and K = 100 nodes over one orbit, at random times in the last 95 % of the span (the objects need not be
+  close: the target, 1e9 m, is beyond every pair, so every row sweeps and manoeuvres; every status 0, asserted), object i moving
+  (who = 0) and both moving (who = 2), without sens; beside it mpcx_discretize_stages_ragged_dev alone on the same plan (the call's
+  first step, once per call whatever n), the calls alternating: the sweep (tf kernel + avoidance_kernel) is the difference of the
+  medians.
+Every shape is warmed up WARM times and timed REPS times in one process; median, minimum and maximum are printed."""
+import ctypes as C, os, statistics, sys
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import conjunction_reference as R
+
+WARM, REPS = 3, 20
+
+import torch
+from mpconstellation_amd import _ffi
+from mpconstellation_amd.constellation import normalize_batch
+lib = _ffi.load(); ctx = _ffi.context(0)
+dev = torch.device("cuda", 0)
+p = lambda t: C.c_void_p(t.data_ptr())
+st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+T = lambda a, dt=torch.float64: torch.tensor(np.ascontiguousarray(a), dtype=dt, device=dev)
+E = lambda shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)
+
+
+def timed(fn):
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    assert fn() == 0
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def measure(runs):
+    """runs: name -> call; alternating; -> name -> median ms"""
+    for _ in range(WARM):
+        for fn in runs.values():
+            timed(fn)
+    ms = {k: [] for k in runs}
+    for _ in range(REPS):
+        for k, fn in runs.items():
+            ms[k].append(timed(fn))
+    for k, v in ms.items():
+        print(f"    {k:44s} median {statistics.median(v):8.3f} ms  min {min(v):8.3f}  max {max(v):8.3f}  ({len(v)} runs)", flush=True)
+    return {k: statistics.median(v) for k, v in ms.items()}
+
+
+S = 4096
+rng = np.random.default_rng(0)
+for K in (30, 100):
+    orb = R.random_orbits(S, seed=K)
+    T1 = 2 * np.pi / np.sqrt(R.MU_EARTH / 6.9e6 ** 3)
+    Y, units, span = R.trajectories(orb, K, (0.0, T1))
+    state = np.zeros((S, 7)); state[:, 0] = units[:, 0]; state[:, 6] = 1.0
+    consts = normalize_batch(state)[1]
+    dY, dU, du, dsp, dc = T(Y), T(0.01 * rng.standard_normal((S, 3, K))), T(units), T(span), T(consts)
+    dtf, stage, dst2 = T((span[:, 1] - span[:, 0]) / units[:, 1]), E((S, K - 1, _ffi.STAGE_DOUBLES)), E(S, torch.int32)
+    for n in (1024, 65536):
+        i = rng.integers(0, S - 1, n); j = rng.integers(i + 1, S)
+        pairs = np.column_stack([i, j, np.zeros(n), rng.uniform(0.05 * T1, T1, n)]).astype(np.float64)
+        dpairs, out, ddu, pst = T(pairs), E((n, _ffi.NAV)), E((n, 2, 3, K)), E(n, torch.int32)
+        ws = E(lib.mpcx_avoidance_workspace_bytes(n, S, K), torch.uint8)
+
+        def call(who):
+            return lambda: lib.mpcx_avoidance_dev(ctx, n, p(dpairs), S, K, None, p(dY), p(dU), p(du), p(dsp), p(dc), _ffi.FLAG_J2, 1e-2, None,
+                                                  0, 0, None, None, None, None, None, R.MU_EARTH, 1.0e9, who, p(out), p(ddu), None, p(pst), p(ws), st)
+        print(f"avoidance n {n} (all-pairs form, S {S}, K {K}, J2, target in metres, no sens)", flush=True)
+        med = measure({"mpcx_avoidance_dev, i moves": call(0), "mpcx_avoidance_dev, both move": call(2),
+                       "mpcx_discretize_stages_ragged_dev alone": lambda: lib.mpcx_discretize_stages_ragged_dev(
+                           ctx, S, K, None, K, None, p(dY), p(dU), p(dtf), p(dc), _ffi.FLAG_J2, 1e-2, p(stage), p(dst2), st)})
+        d = med["mpcx_discretize_stages_ragged_dev alone"]
+        for k in ("mpcx_avoidance_dev, i moves", "mpcx_avoidance_dev, both move"):
+            print(f"    the sweep, {k.split(', ')[1]} (difference of the medians): {med[k] - d:.3f} ms = {1e6 * (med[k] - d) / n:.1f} ns per pair, "
+                  f"{100.0 * (med[k] - d) / med[k]:.1f} % of the call", flush=True)
+        assert int(pst.abs().sum()) == 0 and bool(torch.isfinite(out).all()) and bool(torch.isfinite(ddu).all())
+        del dpairs, out, ddu, ws
+        torch.cuda.empty_cache()
