@@ -769,6 +769,102 @@ int mpcx_avoidance_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, 
                        const double *cat_P, double mu, double target, int who, double *out, double *du, double *sens,
                        int32_t *status, void *workspace, void *stream);
 
+/*
+ * Joint avoidance: all of a satellite's encounters under its thrust limit.  mpcx_avoidance answers every pair on its own; it does
+ * not know u_max, the plan's end state or the other pairs of the same satellite.  This call solves, for every satellite that has
+ * listed encounters, one small strictly convex problem built from the same sensitivities: one thrust change that opens all of the
+ * satellite's encounters at once, stays inside its thrust ball at every node and, optionally, leaves the plan's terminal position
+ * and velocity where they were to first order ("avoid and return").  Nothing in the reference does this.
+ *
+ * Inputs.  pairs [n][4], the row side S, K, Ks, Y, U, units, span, consts, flags, max_step, P, the column side D .. cat_P, mu and
+ * target exactly as mpcx_avoidance takes them, and the same single linearisation per call for all S satellites.  mover [n] int32:
+ * 0 object i of the row moves, 1 object j (NULL: all 0); every pair has exactly one mover.  With a catalogue 1 is MPCX_E_BADARG
+ * (the _dev variant cannot read the list on the host: such a row, or any other value, gets MPCX_ST_BADK and belongs to nobody).
+ * u_max [S] the thrust limit per satellite in the plan's normalised units (NULL, or +inf for a satellite: no ball).
+ * hold_terminal != 0: the terminal rows below.  tol > 0 (the wrappers' default is 1e-10), max_iter >= 1 (default 50).
+ * sat0, nsat: the block of satellites sat0 .. sat0 + nsat - 1 this call computes, as the screens take row0, nrows; all arrays keep
+ * their full shapes, the call writes the block's satellites and the rows of the list they own (a row whose mover is no satellite
+ * 0 .. S-1 is written by the call whose block starts at satellite 0) and leaves every other element alone.
+ *
+ * The problem of satellite s.  Its rows are the pairs it moves for, in ascending order of their position in the list, r of them;
+ * ns = Ks[s] nodes; unknowns du_m in R^3, m = 0 .. ns-1, in the plan's normalised thrust units, tf fixed.
+ *   minimise 1/2 sum_m D_m |du_m|^2,  D_m = w_m c_m^2 with w_m, c_m of mpcx_avoidance (the effort integral of |da|^2 dt, trapezoid rule)
+ *   (1) for each row p: sum_m a_p,m . du_m >= b_p.  Frame e_w, e_1, e_2, the miss m = (|m|, 0), W and g_m are mpcx_avoidance's, in
+ *       its operation order, for the one object that moves; q = W (1, 0)^T / sqrt(W11), d0 = |m| sqrt(W11),
+ *       a_p,m = q_1 g_m[0, :] + q_2 g_m[1, :], b_p = target - d0.  Without covariances (W = I) a_p,m = g_m[0, :] with the bits of
+ *       mpcx_avoidance's sens.  This is the tangent half-plane of the target ellipse: by Cauchy-Schwarz in the W metric
+ *       q^T (m + dm) >= target implies sqrt((m + dm)^T W (m + dm)) >= target, so a met row is never short of the target to first
+ *       order.  Rows already at or beyond the target stay in the problem (b_p <= 0): another row's manoeuvre must not close them.
+ *   (2) |ubar_m + du_m| <= u_max[s] at every node, ubar = U[s].
+ *   (3) hold_terminal: sum_m T_m du_m = 0, T_m (6 x 3) the derivative of the last node's normalised position and velocity with
+ *       respect to u_m: the adjoint recursion of mpcx_avoidance seeded with [I_6 | 0] at node ns - 1 and swept over the whole
+ *       horizon (lam_ns-1 = [I_6 | 0], lam_m = lam_m+1 A_m, T_m = lam_m+1 B_kn[m] (m <= ns-2) + lam_m B_kp[m-1] (m >= 1)).
+ * Method.  Multipliers z = (y in R^6 free, lambda in R^r >= 0); an encounter row is taken in units of the target (a / target,
+ * b / target, lambda * target), the terminal rows as they are.  du_m(z) = proj_ball(ubar_m + (A^T z)_m / D_m) - ubar_m in closed
+ * form per node; F(z) = [T du(z); min(c_p lambda_p, (a_p du(z) - b_p) / target)] = 0 is solved from z = 0 by a semismooth Newton
+ * iteration.  c_p = sum_m |a_p,m / target|^2 / D_m is the row's own authority, what a multiplier of 1 moves the row by when it acts
+ * alone: it brings multiplier and slack to one scale, whatever the units of the target (with the bare min(lambda, slack) a row whose
+ * multiplier must come back from 1e5 to 0 never passes the step control).
+ * Row p is active when c_p lambda_p > its slack.  H = sum_m A_m J_m A_m^T / D_m with J_m the projection's Jacobian (the nodes in
+ * ascending order).  On the active rows H dz = -F + H[., inactive] lambda, on the inactive ones dz = -lambda.  Cholesky of the
+ * active block; a pivot at or below 1e-12 of its own diagonal entry is "not positive definite".  z + t dz with t = 1, 1/2, ... (30
+ * halvings at most) until max |F| falls or is <= tol.  Converged: max |F| <= tol, every inactive row's lambda exactly 0, no lambda
+ * negative.
+ *
+ * Outputs.  du [S][3][K]: the thrust change; zero for a satellite without rows and for nodes past ns.  sat_out [S][MPCX_NAJ]
+ * (MPCX_AJ_*), all zero for a satellite without rows.  row_out [n][MPCX_NAR] (MPCX_AR_*): D0 comes from the pair alone; the other
+ * four are NaN unless the owning satellite's status is OK.  rows [n][3][K] (may be NULL): the a_p, zero past the row's node k + 1.
+ * tsens [S][6][3][K] (may be NULL): the T_m, zero past ns, all zero for a satellite whose problem was not set up (no rows, a failed
+ * row, too many rows) or without hold_terminal.  Results have the same bits with and without rows and tsens.
+ * row_status [n]: mpcx_avoidance's per-pair statuses (BADK, NUMERIC, the discretiser's; there is no per-pair SINGULAR here), BADK
+ * for a bad mover.  A failed row is NaN in row_out and rows.  sat_status [S]: the first status that is not OK among the
+ * satellite's rows in list order; else MPCX_ST_BADK with more than MPCX_AJ_MAX_ROWS rows; else MPCX_ST_INFEASIBLE when the ball
+ * alone forbids a row, sum_m (u_max |a_p,m| - a_p,m . ubar_m) < b_p, tested before the first iteration; else MPCX_ST_SINGULAR when
+ * the Newton matrix on the active rows is not positive definite (dependent rows -- two identical active rows are SINGULAR, they do
+ * not share a multiplier --, an active encounter at the first node, 3 ns < 6 + r); else MPCX_ST_MAXITER without convergence within
+ * max_iter, when no step length reduces max |F|, or on a non-finite iterate.  A satellite whose status is not OK is NaN in du and
+ * sat_out; the other satellites are untouched by it.  A satellite without rows has status OK.
+ * n < 1, S < 1, K < 2, mu <= 0, target or tol not positive and finite, max_iter < 1, a block outside 0 .. S-1 or nsat < 1,
+ * max_step <= 0, a bad flag (as mpcx_avoidance), P without cat_P or the reverse with a catalogue, a bad mover (host variant):
+ * MPCX_E_BADARG, nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_avoidance_joint_workspace_bytes(n, S, K) bytes (stage
+ * records, tf, the discretiser's status, the g_m, the rows when rows is NULL, per-pair scalars and owners, the T_m when tsens is
+ * NULL, the projection's Jacobians; 0 for n < 1, S < 1 or K < 2; contents unspecified on entry and exit).  The g_m and the rows are
+ * 12 n K doubles: 630 MB at n = 65 536, K = 100 -- a list that long is better given in blocks of pairs per satellite block.  One wave per pair, one
+ * wave per satellite; every sum runs in ascending index order or in a fixed butterfly and nothing crosses a workgroup: results do
+ * not depend on the launch shape, on the block of satellites, on the device count, or on pairs that belong to other satellites.
+ */
+#define MPCX_AJ_MAX_ROWS 8
+enum { MPCX_AJ_COST = 0,    /* 1/2 sum_m D_m |du_m|^2, (m/s^2)^2 s */
+       MPCX_AJ_DV,          /* sum_m w_m |da_m|, m/s */
+       MPCX_AJ_UMAX,        /* max_m |ubar_m + du_m|, normalised */
+       MPCX_AJ_ROWS,        /* r: the satellite's rows */
+       MPCX_AJ_ACTIVE,      /* rows with lambda > 0 */
+       MPCX_AJ_ONBALL,      /* nodes the ball projects */
+       MPCX_AJ_ITERS,       /* Newton iterations */
+       MPCX_AJ_RESIDUAL,    /* final max |F| (encounter rows in units of the target) */
+       MPCX_NAJ };
+enum { MPCX_AR_D0 = 0,      /* d0: the distance now, in the target's metric */
+       MPCX_AR_MARGIN,      /* the linear margin q^T (m + dm) = d0 + sum_m a_p,m . du_m, to compare with target */
+       MPCX_AR_DIST,        /* the predicted distance sqrt((m + dm)^T W (m + dm)), dm = sum_m g_m[0:2] du_m */
+       MPCX_AR_LAMBDA,      /* the row's multiplier, in the row's own units (effort per unit of the target's metric) */
+       MPCX_AR_DT,          /* shift of the time of closest approach, -(e_w row of sum_m g_m du_m) / |w|, s */
+       MPCX_NAR };
+size_t mpcx_avoidance_joint_workspace_bytes(int n, int S, int K);
+int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                         const double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                         double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
+                         const double *cat_units, const double *cat_span, const double *cat_P, double mu, double target,
+                         const double *u_max, int hold_terminal, double tol, int max_iter, int sat0, int nsat, double *du,
+                         double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status);
+int mpcx_avoidance_joint_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                             const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                             int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                             const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
+                             double target, const double *u_max, int hold_terminal, double tol, int max_iter, int sat0, int nsat,
+                             double *du, double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status,
+                             int32_t *row_status, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,11 +140,23 @@ _SIGS = {
     "mpcx_avoidance_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
                                      C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    # joint avoidance: all of a satellite's encounters under its thrust limit, one small convex problem per manoeuvring satellite
+    "mpcx_avoidance_joint_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_avoidance_joint": (C.c_int, [_vp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                       C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_double, C.c_int,
+                                       C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "mpcx_avoidance_joint_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
+                                           C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
+                                           C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
 NAV = 10                                                                    # MPCX_NAV: columns of mpcx_avoidance's out
 AV_D0, AV_D1, AV_DM1, AV_DM2, AV_MISS1, AV_DT, AV_DV_I, AV_DV_J, AV_UMAX_I, AV_UMAX_J = range(NAV)
+NAJ, NAR, AJ_MAX_ROWS = 8, 5, 8                                             # MPCX_NAJ, MPCX_NAR: columns of mpcx_avoidance_joint's sat_out, row_out
+AJ_COST, AJ_DV, AJ_UMAX, AJ_ROWS, AJ_ACTIVE, AJ_ONBALL, AJ_ITERS, AJ_RESIDUAL = range(NAJ)
+AR_D0, AR_MARGIN, AR_DIST, AR_LAMBDA, AR_DT = range(NAR)
+AJ_DEFAULT_TOL, AJ_DEFAULT_MAX_ITER = 1e-10, 50
 
 
 def _sat_twin(name):

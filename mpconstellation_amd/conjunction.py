@@ -15,6 +15,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   catalogue_covariance    catalogue_trajectories followed by covariance;
   avoidance      for every listed pair the derivative of the encounter-plane miss with respect to every thrust node of the plan, and
                  the least-effort thrust change that opens the miss to a requested distance.
+  avoidance_joint   per manoeuvring satellite ONE thrust change that opens all of its listed encounters at once, inside its thrust
+                 limit, and optionally holds the plan's terminal state.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
 import numpy as np
@@ -557,3 +559,157 @@ def _avoidance_call(pairs, *, device, slot, out, rows, cols, mu, target, who, fl
     _ffi.call("mpcx_avoidance", ctx, len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
               _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu, target, who,
               _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
+
+
+# ---- all of a satellite's encounters under its thrust limit (include/mpcx.h: mpcx_avoidance_joint; csrc/avoidance_joint.hip)
+class AvoidanceJointResult:
+    """Per satellite (S,): du (S, 3, K) the thrust change in the plan's own units (zero for a satellite without rows and for nodes
+    past ns), cost (1/2 sum D |du|^2), dv (sum of w_m |da_m|, m/s), umax (the largest |ubar + du|, normalised), n_rows, n_active
+    (rows with a positive multiplier), n_on_ball (nodes the thrust ball projects), iters, residual (final max |F|), status
+    (int32 MPCX_ST_*; a satellite whose status is not 0 is NaN in all of them), tsens (S, 6, 3, K) the terminal sensitivities T_m
+    or None.  Per row of `pairs` (n,): mover (0: object i moves, 1: object j), d0 the distance now, margin the linear margin
+    q^T (m + dm) (to compare with the target), d1 the predicted distance sqrt((m + dm)^T W (m + dm)), lam the row's multiplier,
+    dt the shift of the time of closest approach (s), row_status, rows (n, 3, K) the a_p or None, and coupled (n,) bool: the
+    row's object that does NOT move is itself moved by another row of the list, which this row's prediction ignores."""
+
+    def __init__(self, pairs, mover, du, sat_out, row_out, rows, tsens, status, row_status, coupled):
+        self.pairs, self.mover, self.du, self.rows, self.tsens, self.status, self.row_status, self.coupled = \
+            pairs, mover, du, rows, tsens, status, row_status, coupled
+        self.cost, self.dv, self.umax = sat_out[:, _ffi.AJ_COST], sat_out[:, _ffi.AJ_DV], sat_out[:, _ffi.AJ_UMAX]
+        self.n_rows, self.n_active, self.n_on_ball = sat_out[:, _ffi.AJ_ROWS], sat_out[:, _ffi.AJ_ACTIVE], sat_out[:, _ffi.AJ_ONBALL]
+        self.iters, self.residual = sat_out[:, _ffi.AJ_ITERS], sat_out[:, _ffi.AJ_RESIDUAL]
+        self.d0, self.margin, self.d1 = row_out[:, _ffi.AR_D0], row_out[:, _ffi.AR_MARGIN], row_out[:, _ffi.AR_DIST]
+        self.lam, self.dt = row_out[:, _ffi.AR_LAMBDA], row_out[:, _ffi.AR_DT]
+        self.sat_out, self.row_out = sat_out, row_out
+
+    def __repr__(self):
+        return f"AvoidanceJointResult(pairs={len(self.pairs)}, satellites={len(self.du)})"
+
+    def apply(self, U):
+        """a copy of the plan thrust U (S, 3, K) with every satellite's du added; raises for a satellite whose status is not 0"""
+        U = np.array(U, dtype=np.float64)
+        if U.shape != self.du.shape:
+            raise ValueError(f"U: expected {self.du.shape} plan thrust, got {U.shape}")
+        bad = np.flatnonzero(self.status != 0)
+        if len(bad):
+            s = int(bad[0])
+            raise ValueError(f"satellite {s} has no manoeuvre: {_ffi.STATUS_TEXT.get(int(self.status[s]), int(self.status[s]))}")
+        return U + self.du
+
+
+def _check_mover(who, n, against_catalogue):
+    """who = 'i', 'j' or an (n,) array of 0 / 1 -> mover (n,) int32"""
+    if isinstance(who, str):
+        if who not in ("i", "j"):
+            raise ValueError(f"who: expected 'i', 'j' or an ({n},) array of 0 (object i moves) / 1 (object j), got {who!r}")
+        mover = np.full(n, _WHO[who], dtype=np.int32)
+    else:
+        w = np.asarray(who)
+        if w.shape != (n,) or not np.isin(w, (0, 1)).all():
+            raise ValueError(f"who: expected 'i', 'j' or an ({n},) array of 0 (object i moves) / 1 (object j), got shape {w.shape}")
+        mover = np.ascontiguousarray(w, dtype=np.int32)
+    if against_catalogue and mover.any():
+        raise ValueError("who: against a catalogue only the satellite can manoeuvre (who='i', or all 0)")
+    return mover
+
+
+def _coupled(pairs, mover, against_catalogue):
+    """rows whose object that does not move is moved by another row"""
+    n = len(pairs)
+    if against_catalogue or n == 0:
+        return np.zeros(n, dtype=bool)
+    at = np.arange(n)
+    moving, other = pairs[at, mover], pairs[at, 1 - mover]
+    return np.isin(other, moving)
+
+
+def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", u_max=None, hold_terminal=True,
+                    tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, include_drag=False, include_J2=False, atmosphere=None,
+                    max_step=DEFAULT_MAX_STEP, mu=None, return_rows=False, return_terminal=False, device=0, devices=None):
+    """One thrust change per manoeuvring satellite that opens ALL of its listed close approaches to `target` at once, stays inside
+    its thrust ball |U + du| <= u_max at every node and, with hold_terminal, leaves the plan's last position and velocity where they
+    were to first order -> AvoidanceJointResult.  pairs, target, Y, U, units, span, consts, ns, P, cat and the model as `avoidance`
+    takes them; who = "i", "j" or an (n,) array of 0 / 1: which object of each pair moves (exactly one; against a catalogue the
+    satellite).  u_max: a scalar or (S,) normalised thrust limits, None: no ball.  A satellite's rows are the pairs it moves for, at
+    most 8; every row is the tangent half-plane of its target ellipse, so a met row is at or beyond the target to first order, and
+    rows already beyond it stay in the problem.  The device solves the strictly convex problem per satellite by a semismooth Newton
+    iteration to max |F| <= tol (include/mpcx.h).  return_rows / return_terminal: the rows a_p (n, 3, K) and the terminal
+    sensitivities (S, 6, 3, K).  An empty list returns zeros without a library call.  devices=[d0, d1, ...]: contiguous blocks of
+    satellites on several devices (every device holds the whole plan and list), written in place, the bits of one device."""
+    from .constants import MU_EARTH
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    if not (np.ndim(target) == 0 and np.isfinite(target) and target > 0.0):
+        raise ValueError(f"target: need a positive finite distance, got {target}")
+    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"tol: need a positive finite number, got {tol}")
+    if not (np.ndim(max_iter) == 0 and int(max_iter) == max_iter and max_iter >= 1):
+        raise ValueError(f"max_iter: need an integer >= 1, got {max_iter}")
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, K = Y.shape
+    if K < 2:
+        raise ValueError(f"Y: need at least 2 nodes, got {Y.shape}")
+    U, consts = _ffi.as_f64(U), _ffi.as_f64(consts)
+    if U.shape != (S, 3, K):
+        raise ValueError(f"U: expected ({S}, 3, {K}) thrust at the nodes, got {U.shape}")
+    if consts.shape != (S, _ffi.NCONST):
+        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
+    if P is not None:
+        P = _ffi.as_f64(P)
+        if P.shape != (S, K, 6, 6):
+            raise ValueError(f"P: expected ({S}, {K}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
+    cols = None
+    if cat is not None:
+        cols = _check_cat(cat)
+        if (P is None) != (cols[4] is None):
+            raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
+    n = pairs.shape[0]
+    mover = _check_mover(who, n, cols is not None)
+    if u_max is not None:
+        if np.ndim(u_max) not in (0, 1) or (np.ndim(u_max) == 1 and np.shape(u_max) != (S,)):
+            raise ValueError(f"u_max: expected a scalar or ({S},) normalised thrust limits, got {np.shape(u_max)}")
+        u_max = _ffi.per_sat(u_max, S)
+        if not (u_max > 0.0).all():
+            raise ValueError("u_max: need positive limits (inf: no ball)")
+    if not max_step > 0.0:
+        raise ValueError(f"max_step: need > 0, got {max_step}")
+    mu = float(MU_EARTH if mu is None else mu)
+    if not mu > 0.0:
+        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    out = dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
+               rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
+               sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32))
+    if n:
+        how = dict(pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols, mu=mu, target=float(target),
+                   hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter), flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
+                   max_step=float(max_step), atmosphere=atmosphere, whole=out)
+        index = np.arange(S)
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(_avoidance_joint_call, devices, [index], None, **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            _avoidance_joint_call(index, device=device, slot=0, out=None, **how)
+    return AvoidanceJointResult(pairs, mover, out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"],
+                                out["row_status"], _coupled(pairs, mover, cols is not None))
+
+
+def _avoidance_joint_call(index, *, device, slot, out, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere,
+                          whole):
+    """the block of satellites index[0] .. index[-1] on context (device, slot): the library writes the block's satellites and the
+    rows they own into the whole result set `whole`, and nothing else of it"""
+    Y, U, units, span, consts, ns, P, u_max = rows
+    col = (0, 0, None, None, None, None, None)
+    if cols is not None:
+        cY, cunits, cspan, cns, cP = cols
+        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_avoidance_joint", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
+              _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
+              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, int(index[0]), len(index), _ffi.dptr(whole["du"]), _ffi.dptr(whole["sat_out"]),
+              _ffi.dptr(whole["row_out"]), _ffi.dptr_opt(whole["rows"]), _ffi.dptr_opt(whole["tsens"]), _ffi.iptr(whole["sat_status"]),
+              _ffi.iptr(whole["row_status"]))

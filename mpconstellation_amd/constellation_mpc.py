@@ -331,15 +331,10 @@ class ConstellationMPC:
                           include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
 
-    def avoidance(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i"):
-        """Avoidance manoeuvres for the last plan's close approaches -> (ConjunctionResult, AvoidanceResult).  The plan is screened
-        at threshold_m as collision_probability screens it (screen(what='plan'); screen_against when catalogue = (Y, units, span),
-        (Y, units, span, P) or (Y, units, span, P, ns) is given); with P0 ((6, 6) or (S, 6, 6); m, m/s) the satellites' covariance
-        is propagated along the plan with the acceleration noise q and `target` is a Mahalanobis distance (a catalogue then needs
-        its P), without it `target` is a miss distance in metres; every listed pair gets the least-effort thrust change of
-        conjunction.avoidance on (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere; who = 'i', 'j'
-        or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceResult.apply(plan U, row) is the changed
-        thrust table; feeding it back into the solver's constraints is not done here (DESIGN.md section 8)."""
+    def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
+        """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the
+        constellation, or against catalogue = (Y, units, span[, P][, ns])), the plan's covariance when P0 is given, the catalogue as
+        a tuple, and the planning model and device keywords -> (w, screened, P, cat, model, where)"""
         from . import conjunction as cj
         (w,) = self._screen_windows("plan", samples_per_node)
         kw = {} if max_pairs is None else {"max_pairs": max_pairs}
@@ -357,8 +352,41 @@ class ConstellationMPC:
         P = None
         if P0 is not None:
             P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
+        return w, screened, P, cat, model, where
+
+    def avoidance(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i"):
+        """Avoidance manoeuvres for the last plan's close approaches -> (ConjunctionResult, AvoidanceResult).  The plan is screened
+        at threshold_m as collision_probability screens it (screen(what='plan'); screen_against when catalogue = (Y, units, span),
+        (Y, units, span, P) or (Y, units, span, P, ns) is given); with P0 ((6, 6) or (S, 6, 6); m, m/s) the satellites' covariance
+        is propagated along the plan with the acceleration noise q and `target` is a Mahalanobis distance (a catalogue then needs
+        its P), without it `target` is a miss distance in metres; every listed pair gets the least-effort thrust change of
+        conjunction.avoidance on (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere; who = 'i', 'j'
+        or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceResult.apply(plan U, row) is the changed
+        thrust table; feeding it back into the solver's constraints is not done here (DESIGN.md section 8)."""
+        from . import conjunction as cj
+        w, screened, P, cat, model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
         return screened, cj.avoidance(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, ns=w["ns"], P=P, cat=cat,
                                       who=who, **model, **where)
+
+    def avoidance_joint(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i",
+                        hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, return_rows=False,
+                        return_terminal=False):
+        """One manoeuvre per satellite for ALL of the last plan's close approaches it moves for -> (ConjunctionResult,
+        AvoidanceJointResult).  The plan is screened and, with P0, its covariance propagated exactly as `avoidance` does; every
+        manoeuvring satellite then gets the thrust change of conjunction.avoidance_joint on (plan X, plan U, plan_tf, plan_K) under
+        the planning model: all of its encounters opened to `target` at once, inside its own thrust limit -- the upper bound of
+        this instance's u_lim option, per-satellite tables included -- and, with hold_terminal, the plan's last position and
+        velocity held to first order.  who = 'i' or 'j'; an (n,) array of 0 / 1 only for a caller who has screened the same plan at
+        the same threshold before (screen(what='plan') / screen_against) and so knows the list.  AvoidanceJointResult.apply(plan U)
+        is the changed thrust table; the solver-side encounter rows remain open, this call is their check."""
+        from . import conjunction as cj
+        w, screened, P, cat, model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
+        from .optimizer import DEFAULT_OPTIONS
+        u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
+        u_max = np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
+        return screened, cj.avoidance_joint(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, ns=w["ns"], P=P,
+                                            cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol, max_iter=max_iter,
+                                            return_rows=return_rows, return_terminal=return_terminal, **model, **where)
 
     @staticmethod
     def _check(status):

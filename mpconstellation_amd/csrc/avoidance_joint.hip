@@ -1,0 +1,762 @@
+// avoidance_joint.hip -- all of a satellite's encounters under its thrust limit (include/mpcx.h: mpcx_avoidance_joint*).
+//   aj_rows_kernel    one wave per listed pair: the encounter frame, the adjoint sweep over A | B_kn | B_kp and the g_m of the ONE object
+//                     that moves -- avoidance_kernel's code (avoidance.hip) restated expression for expression, so that with W = I the
+//                     row has the bits of mpcx_avoidance's sens -- contracted to the tangent half-plane row a_p and its right-hand side.
+//   aj_solve_kernel   one wave per satellite that has rows: its row indices in ascending list order, the terminal sweep (the same
+//                     recursion with six rows, seeded [I_6 | 0] at the last node), and the strictly convex problem by the semismooth
+//                     Newton iteration of the header: a lane-strided pass over the nodes for du(z) and the projection's Jacobian, one
+//                     lane per entry of H and of the residual (sums over the nodes in ascending order), a Cholesky in LDS.
+// Nothing crosses a workgroup; every sum runs in ascending index order or in the xor butterfly's fixed order: the results depend on
+// the inputs alone (tests/avoidance_joint_reference.py restates them).  Plain vector loads and stores throughout.
+#include "collision_device.hpp"
+
+#include <string.h>
+#include <vector>
+
+namespace mpcx {
+
+enum { AJ_REC = 91, AJ_REC_PAD = 96, AJ_MAXR = MPCX_AJ_MAX_ROWS, AJ_NZ = 6 + MPCX_AJ_MAX_ROWS, AJ_LINE_SEARCH = 30 };
+enum { AJI_D0 = 0, AJI_B, AJI_Q1, AJI_Q2, AJI_MN, AJI_WN, AJI_W11, AJI_W12, AJI_W22, AJ_INFO = 10 };      // per-pair record of the workspace
+#define AJ_PIVOT_REL 1e-12
+
+__global__ __launch_bounds__(256) void aj_tf_kernel(int S, const double *units, const double *span, double *tf)
+{
+    // covariance_tf_kernel's rule (collision.hip): no positive finite tf, no linearisation -- tf = 1 and MPCX_ST_BADK in the rows
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
+    tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
+}
+
+struct AjArgs {
+    int n, S, K, sat0, nsat, have_cat, have_P, hold, max_iter;
+    const double *pairs;
+    const int32_t *mover;             // [n] or NULL
+    CpSide row, col;
+    const double *U;                  // [S][3][K]
+    const double *stage;              // [S][K-1][MPCX_STAGE_DOUBLES]
+    const int32_t *dstat;             // the discretiser's status [S]
+    const double *u_max;              // [S] or NULL
+    double mu, target, tol;
+    double *g;                        // workspace [n][3][3][K]: the g_m of the object that moves
+    double *a;                        // [n][3][K]: `rows` when the caller gave it, otherwise the workspace
+    double *info;                     // workspace [n][AJ_INFO]
+    int32_t *owner;                   // workspace [n]: the satellite a row belongs to, -1: none
+    double *T;                        // [S][6][3][K]: `tsens` when the caller gave it, otherwise the workspace
+    int zero_T;                       // T is tsens: what the sweep does not reach is part of the result
+    double *jd;                       // workspace [S][6][K]: the projection's Jacobian over D_m, upper triangle
+    double *du, *sat_out, *row_out;
+    int32_t *sat_status, *row_status;
+};
+
+__device__ __forceinline__ double aj_wave_sum(double x)
+{
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) x = x + __shfl_xor(x, sh);
+    return x;
+}
+__device__ __forceinline__ double aj_wave_max(double x)
+{
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) x = fmax(x, __shfl_xor(x, sh));
+    return x;
+}
+
+// The adjoint sweep of avoidance_kernel for NR rows, run by one wave: lam_kme+1 = seed_hi, lam_kme = lam_kme+1 A_kme + seed_lo,
+// lam_q = lam_q+1 A_q; g_q+1 = lam_q+2 B_kn[q+1] + lam_q+1 B_kp[q], g_0 = lam_1 B_kn[0], written to g[(row * 3 + component) * K + node]
+// for the nodes 0 .. kme + 1.  Lane e < 7 NR owns entry e of lam, lane e < 3 NR entry e of g_m; a node's record is fetched one node
+// ahead of its arithmetic.  Called by the whole wave; ends with a barrier (g is read back by other lanes).
+template <int NR>
+__device__ __forceinline__ void aj_sweep(int lane, const double *srec, int kme, double seed_hi, double seed_lo, double *g, size_t K,
+                                         double *rec, double *lam)
+{
+    constexpr int NL = NR * 7, NG = NR * 3;
+    const int lr = lane < NL ? lane / 7 : 0, lc = lane < NL ? lane - 7 * (lane / 7) : 0;
+    const int gr = lane < NG ? lane / 3 : 0, gc = lane < NG ? lane - 3 * (lane / 3) : 0;
+    if (lane < NL) lam[lane] = seed_hi;
+    double r0 = 0.0, r1 = 0.0;                                       // the record in flight: entries lane, lane + 64 (< 91)
+    {
+        const double *rp = srec + (size_t)kme * MPCX_STAGE_DOUBLES;
+        r0 = rp[lane];
+        if (lane + 64 < AJ_REC) r1 = rp[lane + 64];
+    }
+    double carry = 0.0;                                              // lam_q+2 B_kn[q+1], entry (gr, gc)
+    for (int q = kme; q >= 0; --q) {
+        rec[lane] = r0;
+        if (lane + 64 < AJ_REC) rec[lane + 64] = r1;
+        __syncthreads();
+        if (q >= 1) {                                                // the next node's record, ahead of this node's arithmetic
+            const double *rp = srec + (size_t)(q - 1) * MPCX_STAGE_DOUBLES;
+            r0 = rp[lane];
+            if (lane + 64 < AJ_REC) r1 = rp[lane + 64];
+        }
+        double lnew = 0.0;
+        if (lane < NG) {
+            double gn = lam[gr * 7] * rec[49 + gc], gp = lam[gr * 7] * rec[70 + gc];
+#pragma unroll
+            for (int x = 1; x < 7; ++x) {
+                gn = gn + lam[gr * 7 + x] * rec[49 + x * 3 + gc];
+                gp = gp + lam[gr * 7 + x] * rec[70 + x * 3 + gc];
+            }
+            g[(size_t)lane * K + q + 1] = q == kme ? gp : carry + gp;
+            carry = gn;
+        }
+        if (lane < NL) {
+            lnew = lam[lr * 7] * rec[lc];
+#pragma unroll
+            for (int x = 1; x < 7; ++x) lnew = lnew + lam[lr * 7 + x] * rec[x * 7 + lc];
+            if (q == kme) lnew = lnew + seed_lo;
+        }
+        __syncthreads();
+        if (lane < NL) lam[lane] = lnew;                             // lam_q
+    }
+    if (lane < NG) g[(size_t)lane * K] = carry;                      // g_0 = lam_1 B_kn[0]
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void aj_rows_kernel(AjArgs a)
+{
+    __shared__ double rec[AJ_REC_PAD], lam[24];
+    const int pr = blockIdx.x, lane = threadIdx.x;
+    if (pr >= a.n) return;
+    const double *row = a.pairs + (size_t)pr * 4;
+    const double t = row[3];
+    const size_t K = (size_t)a.K;
+    const int mvr = a.mover ? a.mover[pr] : 0;
+    const double fm = mvr ? row[1] : row[0];
+    const bool mover_ok = (mvr == 0 || (mvr == 1 && !a.have_cat)) && fm >= 0.0 && fm < (double)a.S;
+    const int own = mover_ok ? (int)fm : -1;
+    if (lane == 0) a.owner[pr] = own;
+    // a call computes the rows of its own block of satellites; a row nobody owns is reported by the block that starts at satellite 0
+    if (own < 0 ? a.sat0 != 0 : (own < a.sat0 || own >= a.sat0 + a.nsat)) return;
+    double *g = a.g + (size_t)pr * 9 * K, *ar = a.a + (size_t)pr * 3 * K;
+
+    // ---- both objects at t, the statuses that end the row, the encounter frame and the target's metric (wave-uniform)
+    double pa[3], va[3], pb[3], vb[3];
+    CpNode nda, ndb;
+    int st = mover_ok ? MPCX_ST_OK : MPCX_ST_BADK;
+    if (st == MPCX_ST_OK) st = cp_state(a.row, row[0], t, pa, va, nda);
+    if (st == MPCX_ST_OK) st = cp_state(a.col, row[1], t, pb, vb, ndb);
+    int mk = 0, mnn = 2, mo = 0;
+    double htau = 0.0, Lm = 0.0, h00 = 0.0, h10 = 0.0, h01 = 0.0, h11 = 0.0;
+    if (st == MPCX_ST_OK) {
+        const CpNode &nd = mvr ? ndb : nda;                          // (the object that moves is one of the constellation: the row side)
+        const double L = a.row.units[2 * nd.o], Tu = a.row.units[2 * nd.o + 1];
+        const double tfv = (a.row.span[2 * nd.o + 1] - a.row.span[2 * nd.o]) / Tu;
+        if (!(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
+        else if (a.dstat[nd.o] != MPCX_ST_OK) st = a.dstat[nd.o];
+        mk = nd.k; mnn = nd.nn; mo = nd.o;
+        htau = tfv / (double)(nd.nn - 1);
+        Lm = L;
+        h00 = nd.h00; h10 = nd.h10; h01 = nd.h01; h11 = nd.h11;
+    }
+    double ew[3], e1[3], e2[3], mn = 0.0, wn = 0.0, W11 = 1.0, W12 = 0.0, W22 = 1.0;
+    if (st == MPCX_ST_OK) {
+        // the frame of collision_probability_kernel, in its operation order
+        double d[3], w[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { d[c] = pb[c] - pa[c]; w[c] = vb[c] - va[c]; }
+        wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        if (!(wn > 0.0) || !cp_finite(wn)) st = MPCX_ST_NUMERIC;
+        else {
+            double m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ew[c] = w[c] / wn;
+            const double dw = d[0] * ew[0] + d[1] * ew[1] + d[2] * ew[2];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = d[c] - dw * ew[c];
+            mn = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+            if (mn > 0.0) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = m[c] / mn;
+            } else {
+                int ax = 0;
+                double ea = ew[0];
+                if (fabs(ew[1]) < fabs(ea)) { ax = 1; ea = ew[1]; }
+                if (fabs(ew[2]) < fabs(ea)) { ax = 2; ea = ew[2]; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = (c == ax ? 1.0 : 0.0) - ea * ew[c];
+                const double en = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e1[c] = e1[c] / en;
+            }
+            e2[0] = ew[1] * e1[2] - ew[2] * e1[1];
+            e2[1] = ew[2] * e1[0] - ew[0] * e1[2];
+            e2[2] = ew[0] * e1[1] - ew[1] * e1[0];
+            if (a.have_P) {
+                double Ca[6], Cb[6], Cs[6], g1[3], g2[3];
+                cp_covariance(a.row, nda, t, a.mu, Ca);
+                cp_covariance(a.col, ndb, t, a.mu, Cb);
+#pragma unroll
+                for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
+                g1[0] = Cs[0] * e1[0] + Cs[1] * e1[1] + Cs[2] * e1[2];
+                g1[1] = Cs[1] * e1[0] + Cs[3] * e1[1] + Cs[4] * e1[2];
+                g1[2] = Cs[2] * e1[0] + Cs[4] * e1[1] + Cs[5] * e1[2];
+                g2[0] = Cs[0] * e2[0] + Cs[1] * e2[1] + Cs[2] * e2[2];
+                g2[1] = Cs[1] * e2[0] + Cs[3] * e2[1] + Cs[4] * e2[2];
+                g2[2] = Cs[2] * e2[0] + Cs[4] * e2[1] + Cs[5] * e2[2];
+                const double c11 = e1[0] * g1[0] + e1[1] * g1[1] + e1[2] * g1[2];
+                const double c12 = e1[0] * g2[0] + e1[1] * g2[1] + e1[2] * g2[2];
+                const double c22 = e2[0] * g2[0] + e2[1] * g2[1] + e2[2] * g2[2];
+                const double tr = c11 + c22, df = c11 - c22;
+                const double l1 = 0.5 * (tr + sqrt(df * df + 4.0 * c12 * c12));
+                const double det = c11 * c22 - c12 * c12;
+                const double l2 = det / l1;
+                if (!(l2 > 0.0) || !cp_finite(l2) || !cp_finite(l1)) st = MPCX_ST_NUMERIC;
+                else { W11 = c22 / det; W12 = -c12 / det; W22 = c11 / det; }      // W = C_2^-1
+            }
+        }
+    }
+
+    double o[MPCX_NAR];
+#pragma unroll
+    for (int c = 0; c < MPCX_NAR; ++c) o[c] = cp_nan();
+    if (st == MPCX_ST_OK) {
+        // ---- the adjoint sweep of the object that moves.  R Lam of the two bracketing nodes, entry (lr, lc):
+        //      sgn [e_1 e_2 e_w]^T L [hp I | h_tau hv I | 0]
+        const int lr = lane < 21 ? lane / 7 : 0, lc = lane < 21 ? lane - 7 * (lane / 7) : 0;
+        double seed_hi = 0.0, seed_lo = 0.0;
+        {
+            const double sgn = mvr ? 1.0 : -1.0;
+            double Rv[3];
+#pragma unroll
+            for (int x = 0; x < 3; ++x) Rv[x] = sgn * (lr == 0 ? e1[x] : (lr == 1 ? e2[x] : ew[x]));
+            const int cc = lc < 3 ? lc : lc - 3;
+            const double Rc = cc == 0 ? Rv[0] : (cc == 1 ? Rv[1] : Rv[2]);
+            const double L = Lm, ht = htau;
+            if (lc < 3) { seed_hi = (L * h01) * Rc; seed_lo = (L * h00) * Rc; }
+            else if (lc < 6) { seed_hi = (L * (ht * h11)) * Rc; seed_lo = (L * (ht * h10)) * Rc; }
+        }
+        for (int e = 0; e < 9; ++e)                                  // the nodes past k + 1
+            for (int m = mk + 2 + lane; m < a.K; m += 64) g[(size_t)e * K + m] = 0.0;
+        aj_sweep<3>(lane, a.stage + (size_t)mo * (K - 1) * MPCX_STAGE_DOUBLES, mk, seed_hi, seed_lo, g, K, rec, lam);
+
+        // ---- the tangent half-plane of the target ellipse: q = W (1, 0)^T / sqrt(W11), a_m = q_1 g_m[0, :] + q_2 g_m[1, :]
+        const double sq = sqrt(W11), q1 = W11 / sq, q2 = W12 / sq;
+        const double d0 = sqrt(mn * W11 * mn);
+        for (int c = 0; c < 3; ++c)
+            for (int m = lane; m < a.K; m += 64) {
+                const double g0 = g[(size_t)c * K + m];
+                ar[(size_t)c * K + m] = a.have_P ? q1 * g0 + q2 * g[(size_t)(3 + c) * K + m] : g0;
+            }
+        if (lane == 0) {
+            double *in = a.info + (size_t)pr * AJ_INFO;
+            in[AJI_D0] = d0; in[AJI_B] = a.target - d0; in[AJI_Q1] = q1; in[AJI_Q2] = q2; in[AJI_MN] = mn; in[AJI_WN] = wn;
+            in[AJI_W11] = W11; in[AJI_W12] = W12; in[AJI_W22] = W22;
+        }
+        o[MPCX_AR_D0] = d0;
+    } else {
+        for (size_t e = lane; e < 3 * K; e += 64) ar[e] = cp_nan();
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < MPCX_NAR; ++c) a.row_out[(size_t)pr * MPCX_NAR + c] = o[c];
+        a.row_status[pr] = st;
+    }
+}
+
+// what the passes over the nodes need of the satellite (wave-uniform)
+struct AjSat {
+    int ns, ne, r, nz;
+    double hn, cfac, umax, target;
+    bool ball;
+    const double *mass, *ubar, *T;    // Y[s][6][.], U[s], T[s]
+    double *du, *jd;
+    const double *a;                  // all rows [n][3][K]
+    size_t K;
+};
+
+// entry (component c, node m) of constraint row i: the terminal rows first, then the encounter rows.  The problem takes an encounter
+// row in units of the target; the division is applied once to the row's multiplier, residual and entries of H, not to every entry.
+__device__ __forceinline__ double aj_entry(const AjSat &sa, const int *idx, int i, int c, int m)
+{
+    return i < sa.ne ? sa.T[((size_t)i * 3 + c) * sa.K + m] : sa.a[((size_t)idx[i - sa.ne] * 3 + c) * sa.K + m];
+}
+
+// du(z) at every node and the projection's Jacobian over D_m, then F(z) = [T du; min(c lambda, slack)]: slack (LDS, r), F (LDS, nz).
+// Returns max |F|, NaN when an entry is not finite.  nball: this lane's count of nodes on the ball.
+__device__ __forceinline__ double aj_evaluate(const AjSat &sa, const int *idx, const double *z, const double *bh, const double *cs, double *F,
+                                              double *slack, int lane, int &nball)
+{
+    nball = 0;
+    for (int m = lane; m < sa.ns; m += 64) {
+        double v[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i < sa.nz; ++i) {
+            const double zi = i < sa.ne ? z[i] : z[i] / sa.target;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = v[c] + zi * aj_entry(sa, idx, i, c, m);
+        }
+        const double cm = sa.cfac / sa.mass[m];
+        const double wm = (m == 0 || m == sa.ns - 1) ? 0.5 * sa.hn : sa.hn;
+        const double D = wm * cm * cm;
+        double ub[3], p[3], J[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};                       // (00, 01, 02, 11, 12, 22)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { ub[c] = sa.ubar[(size_t)c * sa.K + m]; p[c] = ub[c] + v[c] / D; }
+        const double pn = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+        if (sa.ball && pn > sa.umax) {
+            const double sc = sa.umax / pn;
+            const double ph[3] = {p[0] / pn, p[1] / pn, p[2] / pn};
+            J[0] = sc * (1.0 - ph[0] * ph[0]); J[1] = sc * (0.0 - ph[0] * ph[1]); J[2] = sc * (0.0 - ph[0] * ph[2]);
+            J[3] = sc * (1.0 - ph[1] * ph[1]); J[4] = sc * (0.0 - ph[1] * ph[2]); J[5] = sc * (1.0 - ph[2] * ph[2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[c] = p[c] * sc;
+            ++nball;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) sa.du[(size_t)c * sa.K + m] = p[c] - ub[c];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) sa.jd[(size_t)e * sa.K + m] = J[e] / D;
+    }
+    __syncthreads();
+    if (lane < sa.nz) {
+        double res = 0.0;
+        for (int m = 0; m < sa.ns; ++m)
+            res = res + (aj_entry(sa, idx, lane, 0, m) * sa.du[m] + aj_entry(sa, idx, lane, 1, m) * sa.du[sa.K + m]
+                         + aj_entry(sa, idx, lane, 2, m) * sa.du[2 * sa.K + m]);
+        if (lane < sa.ne) F[lane] = res;
+        else {
+            const double s = res / sa.target - bh[lane - sa.ne];
+            slack[lane - sa.ne] = s;
+            F[lane] = fmin(cs[lane - sa.ne] * z[lane], s);
+            if (!cp_finite(z[lane]) || !cp_finite(s)) F[lane] = cp_nan();
+        }
+    }
+    __syncthreads();
+    double mF = 0.0;
+    bool bad = false;
+    for (int i = 0; i < sa.nz; ++i) {
+        const double f = fabs(F[i]);
+        if (!cp_finite(f)) bad = true;
+        mF = fmax(mF, f);
+    }
+    return bad ? cp_nan() : mF;
+}
+
+__global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
+{
+    __shared__ double rec[AJ_REC_PAD], lam[48];
+    __shared__ double z[AJ_NZ], zn[AJ_NZ], dz[AJ_NZ], F[AJ_NZ], slack[AJ_MAXR], bh[AJ_MAXR], cs[AJ_MAXR], gd[AJ_NZ];
+    __shared__ double H[AJ_NZ][AJ_NZ], G[AJ_NZ][AJ_NZ + 1];
+    __shared__ int idx[AJ_MAXR], act[AJ_NZ];
+    const int lane = threadIdx.x;
+    if ((int)blockIdx.x >= a.nsat) return;
+    const int s = a.sat0 + (int)blockIdx.x;
+    const size_t K = (size_t)a.K;
+    double *du = a.du + (size_t)s * 3 * K, *so = a.sat_out + (size_t)s * MPCX_NAJ;
+    double *Ts = a.T + (size_t)s * 18 * K;
+
+    // ---- the satellite's rows in ascending list order, and the first status among them that is not OK
+    int cnt = 0, st = MPCX_ST_OK;
+    for (int base = 0; base < a.n; base += 64) {
+        const int p = base + lane;
+        const bool mine = p < a.n && a.owner[p] == s;
+        unsigned long long mask = __ballot(mine);
+        while (mask) {
+            const int bit = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const int q = base + bit;
+            if (cnt < AJ_MAXR && lane == 0) idx[cnt] = q;
+            if (st == MPCX_ST_OK) st = a.row_status[q];
+            ++cnt;
+        }
+    }
+    __syncthreads();
+    if (st == MPCX_ST_OK && cnt > AJ_MAXR) st = MPCX_ST_BADK;
+    const int r = cnt > AJ_MAXR ? AJ_MAXR : cnt;
+
+    if (cnt == 0 || st != MPCX_ST_OK) {                              // nothing to do, or nothing that can be done
+        const double fill = cnt == 0 ? 0.0 : cp_nan();
+        for (size_t e = lane; e < 3 * K; e += 64) du[e] = fill;
+        if (a.zero_T)
+            for (size_t e = lane; e < 18 * K; e += 64) Ts[e] = 0.0;
+        if (lane < MPCX_NAJ) so[lane] = fill;
+        if (lane == 0) a.sat_status[s] = st;
+        return;
+    }
+
+    // (a row that is OK has checked the satellite's node count, span, tf and linearisation)
+    AjSat sa;
+    sa.ns = a.row.Ks ? a.row.Ks[s] : a.K;
+    sa.ne = a.hold ? 6 : 0; sa.r = r; sa.nz = sa.ne + r;
+    const double L = a.row.units[2 * s], Tu = a.row.units[2 * s + 1];
+    sa.hn = (a.row.span[2 * s + 1] - a.row.span[2 * s]) / (double)(sa.ns - 1);
+    sa.cfac = L / (Tu * Tu);
+    sa.umax = a.u_max ? a.u_max[s] : __longlong_as_double(0x7ff0000000000000LL);
+    sa.ball = sa.umax < __longlong_as_double(0x7ff0000000000000LL);
+    sa.target = a.target;
+    sa.mass = a.row.Y + ((size_t)s * 7 + 6) * K; sa.ubar = a.U + (size_t)s * 3 * K; sa.T = Ts;
+    sa.du = du; sa.jd = a.jd + (size_t)s * 6 * K; sa.a = a.a; sa.K = K;
+    const int nz = sa.nz, ne = sa.ne, ns = sa.ns;
+
+    for (int c = 0; c < 3; ++c)                                      // nodes past ns
+        for (int m = ns + lane; m < a.K; m += 64) du[(size_t)c * K + m] = 0.0;
+    if (a.hold) {
+        // ---- the terminal sweep: lam_ns-1 = [I_6 | 0], over the whole horizon
+        for (int e = 0; e < 18; ++e)
+            for (int m = ns + lane; m < a.K; m += 64) Ts[(size_t)e * K + m] = 0.0;
+        const int lr = lane < 42 ? lane / 7 : 0, lc = lane < 42 ? lane - 7 * (lane / 7) : 0;
+        aj_sweep<6>(lane, a.stage + (size_t)s * (K - 1) * MPCX_STAGE_DOUBLES, ns - 2, lane < 42 && lr == lc ? 1.0 : 0.0, 0.0, Ts, K, rec, lam);
+    } else if (a.zero_T) {
+        for (size_t e = lane; e < 18 * K; e += 64) Ts[e] = 0.0;
+    }
+
+    // ---- a row the ball alone forbids: sum_m (u_max |a_m| - a_m . ubar_m) < b
+    if (lane < r) bh[lane] = a.info[(size_t)idx[lane] * AJ_INFO + AJI_B] / a.target;
+    bool infeasible = false;
+    if (sa.ball && lane < r) {
+        const double *ap = a.a + (size_t)idx[lane] * 3 * K;
+        double reach = 0.0;
+        for (int m = 0; m < ns; ++m) {
+            const double a0 = ap[m], a1 = ap[K + m], a2 = ap[2 * K + m];
+            reach = reach + (sa.umax * sqrt(a0 * a0 + a1 * a1 + a2 * a2) - (a0 * sa.ubar[m] + a1 * sa.ubar[K + m] + a2 * sa.ubar[2 * K + m]));
+        }
+        infeasible = reach < a.info[(size_t)idx[lane] * AJ_INFO + AJI_B];
+    }
+    if (__ballot(infeasible)) st = MPCX_ST_INFEASIBLE;
+    // ---- a row's own authority c_p = sum_m |a_p,m / target|^2 / D_m: what a multiplier of 1 moves the row by when it acts alone
+    if (lane < r) {
+        const double *ap = a.a + (size_t)idx[lane] * 3 * K;
+        double c = 0.0;
+        for (int m = 0; m < ns; ++m) {
+            const double cm = sa.cfac / sa.mass[m];
+            const double wm = (m == 0 || m == ns - 1) ? 0.5 * sa.hn : sa.hn;
+            const double a0 = ap[m] / a.target, a1 = ap[K + m] / a.target, a2 = ap[2 * K + m] / a.target;
+            c = c + (a0 * a0 + a1 * a1 + a2 * a2) / (wm * cm * cm);
+        }
+        cs[lane] = c;
+    }
+
+    // ---- the semismooth Newton iteration on F(z) = [T du(z); min(c lambda, (a du(z) - b) / target)]
+    int iters = 0, nball = 0;
+    double mF = 0.0;
+    if (st == MPCX_ST_OK) {
+        if (lane < nz) z[lane] = 0.0;
+        __syncthreads();
+        mF = aj_evaluate(sa, idx, z, bh, cs, F, slack, lane, nball);
+        for (;;) {
+            if (!cp_finite(mF)) { st = MPCX_ST_MAXITER; break; }
+            // the active rows, and whether this is the solution: F small, an inactive row's multiplier exactly 0, none negative
+            if (lane < nz) act[lane] = lane < ne || cs[lane - ne] * z[lane] > slack[lane - ne];
+            __syncthreads();
+            bool done = mF <= a.tol;
+            for (int i = ne; i < nz; ++i)
+                if ((!act[i] && z[i] != 0.0) || z[i] < 0.0) done = false;
+            if (done) break;
+            if (iters == a.max_iter) { st = MPCX_ST_MAXITER; break; }
+            // H = sum_m A_m J_m A_m^T / D_m, one lane per entry of the upper triangle, the nodes in ascending order
+            for (int e = lane; e < nz * (nz + 1) / 2; e += 64) {
+                int i = 0, rem = e;
+                while (rem >= nz - i) { rem -= nz - i; ++i; }
+                const int j = i + rem;
+                double h = 0.0;
+                for (int m = 0; m < ns; ++m) {
+                    const double x0 = aj_entry(sa, idx, i, 0, m), x1 = aj_entry(sa, idx, i, 1, m), x2 = aj_entry(sa, idx, i, 2, m);
+                    const double y0 = aj_entry(sa, idx, j, 0, m), y1 = aj_entry(sa, idx, j, 1, m), y2 = aj_entry(sa, idx, j, 2, m);
+                    const double *jm = sa.jd + m;
+                    const double J00 = jm[0], J01 = jm[K], J02 = jm[2 * K], J11 = jm[3 * K], J12 = jm[4 * K], J22 = jm[5 * K];
+                    h = h + (x0 * (J00 * y0 + J01 * y1 + J02 * y2) + x1 * (J01 * y0 + J11 * y1 + J12 * y2) + x2 * (J02 * y0 + J12 * y1 + J22 * y2));
+                }
+                if (i >= ne) h = h / a.target;
+                if (j >= ne) h = h / a.target;
+                H[i][j] = h; H[j][i] = h;
+            }
+            __syncthreads();
+            // G dz = rhs: the Newton step on the active rows, dz = -lambda on the inactive ones
+            double rv = 0.0;
+            if (lane < nz) {
+                if (act[lane]) {
+                    rv = -F[lane];
+                    for (int j = ne; j < nz; ++j)
+                        if (!act[j]) rv = rv + H[lane][j] * z[j];
+                } else rv = -z[lane];
+                for (int j = 0; j < nz; ++j) G[lane][j] = act[lane] && act[j] ? H[lane][j] : (lane == j ? 1.0 : 0.0);
+                gd[lane] = act[lane] ? H[lane][lane] : 1.0;
+            }
+            __syncthreads();
+            bool singular = false;
+            for (int j = 0; j < nz && !singular; ++j) {              // Cholesky, right-looking, row i on lane i
+                const double d = G[j][j];
+                if (!(d > AJ_PIVOT_REL * gd[j])) { singular = true; break; }
+                const double sd = sqrt(d);
+                double lij = 0.0;
+                if (lane > j && lane < nz) lij = G[lane][j] / sd;
+                __syncthreads();
+                if (lane > j && lane < nz) G[lane][j] = lij;
+                if (lane == j) G[j][j] = sd;
+                __syncthreads();
+                if (lane > j && lane < nz)
+                    for (int k = j + 1; k <= lane; ++k) G[lane][k] = G[lane][k] - lij * G[k][j];
+                __syncthreads();
+            }
+            if (singular) { st = MPCX_ST_SINGULAR; break; }
+            for (int j = 0; j < nz; ++j) {                           // L y = rhs
+                const double yj = __shfl(rv, j) / G[j][j];
+                if (lane == j) rv = yj;
+                else if (lane > j && lane < nz) rv = rv - G[lane][j] * yj;
+            }
+            for (int j = nz - 1; j >= 0; --j) {                      // L^T dz = y
+                const double xj = __shfl(rv, j) / G[j][j];
+                if (lane == j) rv = xj;
+                else if (lane < j) rv = rv - G[j][lane] * xj;
+            }
+            if (lane < nz) dz[lane] = rv;
+            __syncthreads();
+            // halve the step on max |F| (t = 1 takes an inactive row's multiplier to 0 exactly)
+            double tstep = 1.0, mFn = 0.0;
+            bool ok = false;
+            for (int ls = 0; ls < AJ_LINE_SEARCH; ++ls) {
+                if (lane < nz) zn[lane] = z[lane] + tstep * dz[lane];
+                __syncthreads();
+                mFn = aj_evaluate(sa, idx, zn, bh, cs, F, slack, lane, nball);
+                if (mFn < mF || mFn <= a.tol) { ok = true; break; }
+                tstep = 0.5 * tstep;
+            }
+            ++iters;
+            if (!ok) { st = MPCX_ST_MAXITER; break; }
+            if (lane < nz) z[lane] = zn[lane];
+            mF = mFn;
+            __syncthreads();
+        }
+    }
+
+    if (st != MPCX_ST_OK) {                                          // defined results: NaN
+        for (size_t e = lane; e < 3 * K; e += 64) du[e] = cp_nan();
+        if (lane < MPCX_NAJ) so[lane] = cp_nan();
+        if (lane == 0) a.sat_status[s] = st;
+        return;
+    }
+
+    // ---- what the manoeuvre costs and where it ends
+    double scost = 0.0, sdv = 0.0, smax = 0.0;
+    for (int m = lane; m < ns; m += 64) {
+        const double cm = sa.cfac / sa.mass[m];
+        const double wm = (m == 0 || m == ns - 1) ? 0.5 * sa.hn : sa.hn;
+        const double d0 = du[m], d1 = du[K + m], d2 = du[2 * K + m];
+        const double u0 = sa.ubar[m] + d0, u1 = sa.ubar[K + m] + d1, u2 = sa.ubar[2 * K + m] + d2;
+        const double da0 = cm * d0, da1 = cm * d1, da2 = cm * d2;
+        scost = scost + (wm * cm * cm) * (d0 * d0 + d1 * d1 + d2 * d2);
+        sdv = sdv + wm * sqrt(da0 * da0 + da1 * da1 + da2 * da2);
+        smax = fmax(smax, sqrt(u0 * u0 + u1 * u1 + u2 * u2));
+    }
+    const double cost = 0.5 * aj_wave_sum(scost), dv = aj_wave_sum(sdv), umx = aj_wave_max(smax), nb = aj_wave_sum((double)nball);
+    int nact = 0;
+    for (int i = ne; i < nz; ++i) nact += z[i] > 0.0 ? 1 : 0;
+    if (lane == 0) {
+        so[MPCX_AJ_COST] = cost; so[MPCX_AJ_DV] = dv; so[MPCX_AJ_UMAX] = umx; so[MPCX_AJ_ROWS] = (double)r; so[MPCX_AJ_ACTIVE] = (double)nact;
+        so[MPCX_AJ_ONBALL] = nb; so[MPCX_AJ_ITERS] = (double)iters; so[MPCX_AJ_RESIDUAL] = mF;
+        a.sat_status[s] = st;
+    }
+    // ---- per row: the displacement in the frame, g_m du_m summed over the nodes (lane 4 p + c: rows e_1, e_2, e_w of g, then a)
+    double sum = 0.0;
+    if (lane < 4 * r) {
+        const int p = lane >> 2, c = lane & 3;
+        const double *gp = c < 3 ? a.g + ((size_t)idx[p] * 9 + (size_t)c * 3) * K : a.a + (size_t)idx[p] * 3 * K;
+        for (int m = 0; m < ns; ++m) sum = sum + (gp[m] * du[m] + gp[K + m] * du[K + m] + gp[2 * K + m] * du[2 * K + m]);
+    }
+    const int p4 = (lane >> 2) << 2;
+    const double dm1 = __shfl(sum, p4), dm2 = __shfl(sum, p4 + 1), along = __shfl(sum, p4 + 2), adu = __shfl(sum, p4 + 3);
+    if (lane < 4 * r && (lane & 3) == 0) {
+        const int p = lane >> 2;
+        const double *in = a.info + (size_t)idx[p] * AJ_INFO;
+        double *ro = a.row_out + (size_t)idx[p] * MPCX_NAR;
+        const double x1 = in[AJI_MN] + dm1, W11 = in[AJI_W11], W12 = in[AJI_W12], W22 = in[AJI_W22];
+        ro[MPCX_AR_MARGIN] = in[AJI_D0] + adu;
+        ro[MPCX_AR_DIST] = sqrt(x1 * (W11 * x1 + W12 * dm2) + dm2 * (W12 * x1 + W22 * dm2));
+        ro[MPCX_AR_LAMBDA] = z[ne + p] / a.target;
+        ro[MPCX_AR_DT] = -along / in[AJI_WN];
+    }
+}
+
+// workspace of the _dev call: [stage S (K-1) records][tf S][discretiser status S][g n 3 3 K][a n 3 K][info n][owner n][T S 6 3 K][jd S 6 K]
+struct AjWorkspace {
+    double *stage, *tf, *g, *a, *info, *T, *jd;
+    int32_t *dstat, *owner;
+    size_t bytes;
+    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+    AjWorkspace(void *base, int n, int S, int K)
+    {
+        char *p = (char *)base;
+        stage = (double *)p; p += al((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES * sizeof(double));
+        tf = (double *)p; p += al((size_t)S * sizeof(double));
+        dstat = (int32_t *)p; p += al((size_t)S * sizeof(int32_t));
+        g = (double *)p; p += al((size_t)n * 9 * K * sizeof(double));
+        a = (double *)p; p += al((size_t)n * 3 * K * sizeof(double));
+        info = (double *)p; p += al((size_t)n * AJ_INFO * sizeof(double));
+        owner = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
+        T = (double *)p; p += al((size_t)S * 18 * K * sizeof(double));
+        jd = (double *)p; p += al((size_t)S * 6 * K * sizeof(double));
+        bytes = (size_t)(p - (char *)base);
+    }
+};
+
+struct AjCall {
+    int n;
+    const double *pairs;
+    const int32_t *mover;
+    int S, K;
+    const int32_t *Ks;
+    const double *Y, *U, *units, *span, *consts;
+    int flags;
+    double max_step;
+    const double *P;
+    int D, cat_K;
+    const int32_t *cat_Ks;
+    const double *cat_Y, *cat_units, *cat_span, *cat_P;
+    double mu, target;
+    const double *u_max;
+    int hold_terminal;
+    double tol;
+    int max_iter, sat0, nsat;
+    double *du, *sat_out, *row_out, *rows, *tsens;
+    int32_t *sat_status, *row_status;
+};
+
+static int aj_check(mpcx_ctx *ctx, const AjCall &c)
+{
+    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: need n>=1, S>=1, K>=2, mu>0");
+    if (!(c.target > 0.0) || !(c.target < __builtin_inf()))
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: target must be a positive finite number");
+    if (!(c.tol > 0.0) || !(c.tol < __builtin_inf()) || c.max_iter < 1)
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: tol must be a positive finite number and max_iter >= 1");
+    if (c.sat0 < 0 || c.nsat < 1 || c.sat0 > c.S - c.nsat)
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: the block sat0 .. sat0 + nsat - 1 must lie in 0 .. S - 1, nsat >= 1");
+    if (!(c.max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: max_step must be > 0");
+    if (c.flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
+    if (!c.pairs || !c.Y || !c.U || !c.units || !c.span || !c.consts || !c.du || !c.sat_out || !c.row_out || !c.sat_status || !c.row_status)
+        return ctx_fail(ctx, MPCX_E_BADARG,
+                        "avoidance_joint: pairs, Y, U, units, span, consts, du, sat_out, row_out, sat_status and row_status are required");
+    if (c.cat_Y) {
+        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: a catalogue needs D>=1, cat_K>=2");
+        if (!c.cat_units || !c.cat_span) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: cat_units and cat_span are required with cat_Y");
+        if ((c.P != nullptr) != (c.cat_P != nullptr))
+            return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: P and cat_P come together (a Mahalanobis target) or not at all (metres)");
+    }
+    return ctx_check_atmosphere(ctx, c.flags, "avoidance_joint");
+}
+
+static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream_t st)
+{
+    const AjWorkspace ws(workspace, c.n, c.S, c.K);
+    hipLaunchKernelGGL(aj_tf_kernel, dim3((unsigned)((c.S + 255) / 256)), dim3(256), 0, st, c.S, c.units, c.span, ws.tf);
+    MPCX_HIP(ctx, hipGetLastError());
+    if (int rc = mpcx_discretize_stages_ragged_dev(ctx, c.S, c.K, c.Ks, c.K, c.Ks, c.Y, c.U, ws.tf, c.consts, c.flags, c.max_step, ws.stage,
+                                                   ws.dstat, st))
+        return rc;
+    AjArgs a;
+    a.n = c.n; a.S = c.S; a.K = c.K; a.sat0 = c.sat0; a.nsat = c.nsat; a.have_cat = c.cat_Y != nullptr; a.have_P = c.P != nullptr;
+    a.hold = c.hold_terminal != 0; a.max_iter = c.max_iter;
+    a.pairs = c.pairs; a.mover = c.mover;
+    a.row = CpSide{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, nullptr};
+    a.col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, nullptr} : a.row;
+    a.U = c.U; a.stage = ws.stage; a.dstat = ws.dstat; a.u_max = c.u_max;
+    a.mu = c.mu; a.target = c.target; a.tol = c.tol;
+    a.g = ws.g; a.a = c.rows ? c.rows : ws.a; a.info = ws.info; a.owner = ws.owner;
+    a.T = c.tsens ? c.tsens : ws.T; a.zero_T = c.tsens != nullptr; a.jd = ws.jd;
+    a.du = c.du; a.sat_out = c.sat_out; a.row_out = c.row_out; a.sat_status = c.sat_status; a.row_status = c.row_status;
+    hipLaunchKernelGGL(aj_rows_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(aj_solve_kernel, dim3((unsigned)c.nsat), dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
+}  // namespace mpcx
+
+using namespace mpcx;
+
+extern "C" size_t mpcx_avoidance_joint_workspace_bytes(int n, int S, int K)
+{
+    if (n < 1 || S < 1 || K < 2) return 0;
+    return AjWorkspace(nullptr, n, S, K).bytes;
+}
+
+extern "C" int mpcx_avoidance_joint_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                        const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                                        int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                                        const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
+                                        double target, const double *u_max, int hold_terminal, double tol, int max_iter, int sat0, int nsat,
+                                        double *du, double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status,
+                                        int32_t *row_status, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const AjCall c{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,
+                   cat_P, mu, target, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    if (int rc = aj_check(ctx, c)) return rc;
+    if (!workspace)
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: a workspace of mpcx_avoidance_joint_workspace_bytes(n, S, K) bytes is required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    return aj_enqueue(ctx, c, workspace, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                    const double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                                    double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
+                                    const double *cat_units, const double *cat_span, const double *cat_P, double mu, double target,
+                                    const double *u_max, int hold_terminal, double tol, int max_iter, int sat0, int nsat, double *du,
+                                    double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const AjCall c{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,
+                   cat_P, mu, target, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    if (int rc = aj_check(ctx, c)) return rc;
+    if (mover)
+        for (int r = 0; r < n; ++r)
+            if (mover[r] < 0 || mover[r] > 1 || (cat_Y && mover[r] != 0))
+                return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: mover is 0 (object i) or 1 (object j); against a catalogue only 0");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    AjCall d = c;
+    d.pairs = ar.upload(pairs, (size_t)n * 4);
+    d.mover = mover ? ar.upload(mover, (size_t)n) : nullptr;
+    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.U = ar.upload(U, (size_t)S * 3 * K);
+    d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2); d.consts = ar.upload(consts, (size_t)S * MPCX_NCONST);
+    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
+    d.P = P ? ar.upload(P, (size_t)S * K * 36) : nullptr;
+    d.u_max = u_max ? ar.upload(u_max, (size_t)S) : nullptr;
+    if (cat_Y) {
+        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
+        d.cat_span = ar.upload(cat_span, (size_t)D * 2);
+        d.cat_P = cat_P ? ar.upload(cat_P, (size_t)D * cat_K * 36) : nullptr;
+        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
+    }
+    // the device arrays have the caller's shapes; what comes back is the block's satellites and the rows they own
+    d.du = ar.alloc<double>((size_t)S * 3 * K);
+    d.sat_out = ar.alloc<double>((size_t)S * MPCX_NAJ);
+    d.row_out = ar.alloc<double>((size_t)n * MPCX_NAR);
+    d.rows = rows ? ar.alloc<double>((size_t)n * 3 * K) : nullptr;
+    d.tsens = tsens ? ar.alloc<double>((size_t)S * 18 * K) : nullptr;
+    d.sat_status = ar.alloc<int32_t>(S);
+    d.row_status = ar.alloc<int32_t>(n);
+    if (ar.failed()) return ar.code();
+    void *ws = ctx_workspace(ctx, mpcx_avoidance_joint_workspace_bytes(n, S, K));
+    if (!ws) return MPCX_E_NOMEM;
+    if (int rc = aj_enqueue(ctx, d, ws, ctx->stream)) return rc;
+    const size_t s0 = (size_t)sat0, ns = (size_t)nsat;
+    ar.download(du + s0 * 3 * K, d.du + s0 * 3 * K, ns * 3 * K);
+    ar.download(sat_out + s0 * MPCX_NAJ, d.sat_out + s0 * MPCX_NAJ, ns * MPCX_NAJ);
+    if (tsens) ar.download(tsens + s0 * 18 * K, d.tsens + s0 * 18 * K, ns * 18 * K);
+    ar.download(sat_status + s0, d.sat_status + s0, ns);
+    // the rows of the list: only those the block owns reach the caller's arrays (a row nobody owns: with the block that starts at 0)
+    const bool whole = sat0 == 0 && nsat == S;
+    std::vector<double> h_out, h_rows;
+    std::vector<int32_t> h_st;
+    if (!whole) {
+        h_out.resize((size_t)n * MPCX_NAR); h_st.resize((size_t)n);
+        if (rows) h_rows.resize((size_t)n * 3 * K);
+    }
+    ar.download(whole ? row_out : h_out.data(), d.row_out, (size_t)n * MPCX_NAR);
+    ar.download(whole ? row_status : h_st.data(), d.row_status, (size_t)n);
+    if (rows) ar.download(whole ? rows : h_rows.data(), d.rows, (size_t)n * 3 * K);
+    if (int rc = ar.finish()) return rc;
+    if (!whole)
+        for (int r = 0; r < n; ++r) {
+            const double fm = (mover && mover[r]) ? pairs[(size_t)r * 4 + 1] : pairs[(size_t)r * 4];
+            const bool owned = fm >= 0.0 && fm < (double)S;
+            if (owned ? ((int)fm < sat0 || (int)fm >= sat0 + nsat) : sat0 != 0) continue;
+            memcpy(row_out + (size_t)r * MPCX_NAR, h_out.data() + (size_t)r * MPCX_NAR, MPCX_NAR * sizeof(double));
+            row_status[r] = h_st[(size_t)r];
+            if (rows) memcpy(rows + (size_t)r * 3 * K, h_rows.data() + (size_t)r * 3 * K, (size_t)3 * K * sizeof(double));
+        }
+    return MPCX_OK;
+}
