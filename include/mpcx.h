@@ -601,6 +601,48 @@ int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, const int32_
                                        double *pairs, int64_t *n_pairs, int32_t *status, int32_t *cat_status);
 
 /*
+ * The closest approach of LISTED pairs: what the two screens compute for a pair, for the n pairs of a list alone -- n x M work
+ * where a screen does S^2 x M or S x D x M.  A list that a screen made is looked at again after something changed the
+ * trajectories (a manoeuvre flown, an orbit update of a few objects) without screening everybody against everybody once more.
+ *
+ * mpcx_conjunction_pairs: pairs [n][4], rows (i, j, -, -) as the screens list them; only columns 0 and 1 are read.  eph [S][6][M]
+ * and, with D > 0, cat [D][6][M] on the grid linspace(T0, T1, M), as the screens take them.  D > 0: i indexes eph and j the
+ * catalogue, d = p_cat - p_sat (mpcx_conjunction_cross_screen's pair).  D = 0 (cat NULL): i and j both index eph, in either order,
+ * d = p_hi - p_lo (mpcx_conjunction_screen's pair; (i, j) and (j, i) get the same bits).  Per pair every grid interval is treated
+ * exactly as mpcx_conjunction_screen describes, with the same skipping of intervals that have a NaN among the six values of an
+ * end, and the pair's minimum is the smallest squared distance, of equal ones the earliest interval.
+ *   out [n][4] = (i, j, distance in m, time in s) in list order, i and j as given; +inf and NaN for a pair without a valid interval.
+ *   status [n]: MPCX_ST_OK; MPCX_ST_BADK for an index that is not a whole number inside its side, or i == j with D = 0 -- distance
+ *   and time of that row are NaN and the other rows are not affected.
+ * The distance and time of a pair are, bit for bit, those the screens list for it on the same eph, cat, M, T0, T1 (the same source
+ * expressions, compiled with -ffp-contract=on; a minimum under a total order, so the result does not depend on how the intervals
+ * are dealt out to lanes).  n < 1, S < 1, D < 0, M < 2, T1 <= T0, a missing array, cat given with D = 0 or missing with D > 0:
+ * MPCX_E_BADARG, nothing enqueued.  The host variant takes host pointers; the _dev variant device pointers throughout, no
+ * workspace, and enqueues one kernel on `stream`.
+ *
+ * mpcx_conjunction_pairs_traj: from trajectories, as mpcx_conjunction_screen_traj (D = 0; the cat_ arguments NULL / 0) and
+ * mpcx_conjunction_cross_screen_traj (D > 0) take them; the ephemerides never leave HBM.  eph_status [S], cat_status [D]: the two
+ * ephemerides' statuses (host variant: each may be NULL; cat_status is not written with D = 0).  Same bits as mpcx_ephemeris_batch
+ * followed by mpcx_conjunction_pairs.  The _dev variant takes device pointers throughout (eph_status required, cat_status
+ * required with D > 0) and a workspace of mpcx_conjunction_pairs_workspace_bytes(S, D, M) bytes (the ephemerides; 0 for S < 1,
+ * D < 0 or M < 2; contents unspecified on entry and exit).
+ */
+size_t mpcx_conjunction_pairs_workspace_bytes(int S, int D, int M);
+int mpcx_conjunction_pairs(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                           double T0, double T1, double *out, int32_t *status);
+int mpcx_conjunction_pairs_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                               double T0, double T1, double *out, int32_t *status, void *stream);
+int mpcx_conjunction_pairs_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                double *out, int32_t *status, int32_t *eph_status, int32_t *cat_status);
+int mpcx_conjunction_pairs_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                    const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                    const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                    double T1, double *out, int32_t *status, int32_t *eph_status, int32_t *cat_status,
+                                    void *workspace, void *stream);
+
+/*
  * Collision probability of screened pairs.  A miss distance alone says nothing: the two orbit uncertainties decide whether 200 m
  * is an emergency or noise.  Two steps, both on the device: a covariance propagated along every trajectory, and for every row
  * (i, j, distance, time) of a screen's pairs list the short-encounter collision probability in the encounter plane.  The reference

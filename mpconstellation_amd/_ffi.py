@@ -125,6 +125,14 @@ _SIGS = {
     "mpcx_conjunction_cross_screen_traj": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, C.c_int,
                                                      C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _dp, _dp, _lp,
                                                      _ip, _ip]),
+    # the closest approach of listed pairs alone (a screen's list looked at again on changed trajectories)
+    "mpcx_conjunction_pairs_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_conjunction_pairs": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, _ip]),
+    "mpcx_conjunction_pairs_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mpcx_conjunction_pairs_traj": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp] * 2
+                                    + [C.c_int, C.c_double, C.c_double, _dp, _ip, _ip, _ip]),
+    "mpcx_conjunction_pairs_traj_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp] * 2
+                                        + [C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     # collision probability of screened pairs: covariance along trajectories, then the encounter-plane integral per listed pair
     "mpcx_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mpcx_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),

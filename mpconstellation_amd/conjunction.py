@@ -9,6 +9,7 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
                  near and when, and with a threshold the list of pairs that come closer than it;
   screen_against the same for a constellation against a catalogue of foreign objects (debris, other operators' satellites): the
                  rectangle satellites x objects, not the square of the union;
+  screen_pairs   the closest approach of the pairs of a list alone, with the bits the screens give them;
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
@@ -205,6 +206,83 @@ def _screen_call(rows, *, device, slot, out, src, cat, M, T0, T1, thr, max_pairs
         _ffi.call(name + "_traj", ctx, *traj, M, *tail, *[_ffi.iptr(st) for st in statuses[:len(sides)]])
     n = int(n_pairs[0])
     return pairs[:min(n, max_pairs)], n, statuses
+
+
+def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, *, Y=None, units=None, span=None, ns=None, cat_Y=None,
+                 cat_units=None, cat_span=None, cat_ns=None, M=None):
+    """The closest approach of the LISTED pairs alone on the common grid linspace(T0, T1, M): n x M work where the screens do
+    S^2 x M -- a screen's list looked at again after the trajectories changed.  pairs: (n, 4) rows (i, j, ., .) as screen and
+    screen_against list them, or their ConjunctionResult; only i and j are read.  Both sides as the screens take them: eph [,
+    cat_eph], or the trajectories Y, units, span [, ns] [and cat_Y, cat_units, cat_span [, cat_ns]] with M.  With a catalogue j
+    indexes it; without one j indexes the constellation and either order of (i, j) is accepted.  Returns (out, status): out (n, 4)
+    rows (i, j, distance, time) in list order -- (+inf, NaN) for a pair without a common valid interval -- and status (n,) int32,
+    MPCX_ST_BADK = 9 with NaN distance and time for an index outside its side or i == j.  From trajectories it returns (out, status,
+    eph_status, cat_status), the ephemerides' statuses as the screens return them (cat_status None without a catalogue).  Distance
+    and time of a pair are bit for bit what screen / screen_against list for it on the same inputs.  An empty list returns empty
+    arrays without a library call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices (every device
+    holds both sides), written in place, the bits of one device."""
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    given_eph, given_traj = eph is not None or cat_eph is not None, Y is not None or cat_Y is not None
+    if given_eph == given_traj:
+        raise ValueError("screen_pairs: give either eph [, cat_eph], or the trajectories Y, units, span [, cat_Y, cat_units, cat_span] with M")
+    if T0 is None or T1 is None:
+        raise ValueError("screen_pairs: T0 and T1 (the common grid's first and last instant, seconds) are required")
+    cat = None
+    if given_eph:
+        if eph is None:
+            raise ValueError("screen_pairs: cat_eph needs eph")
+        eph = _check_ephemeris(eph, M)
+        src, M = (eph,), eph.shape[2]
+        if cat_eph is not None:
+            cat_eph = _check_ephemeris(cat_eph, None, "cat_eph", "D")
+            if cat_eph.shape[2] != M:
+                raise ValueError(f"eph has {M} instants but cat_eph {cat_eph.shape[2]}: both must be on the same grid")
+            cat = (cat_eph,)
+    else:
+        if Y is None:
+            raise ValueError("screen_pairs: cat_Y needs Y")
+        if M is None:
+            raise ValueError("screen_pairs: M (the number of common instants) is required with trajectories")
+        src = _check_trajectories(Y, units, span, ns)
+        if cat_Y is not None:
+            cat = _check_trajectories(cat_Y, cat_units, cat_span, cat_ns, "cat_")
+    M, T0, T1 = _check_grid(M, T0, T1)
+    n = pairs.shape[0]
+    out = dict(out=np.empty((n, 4)), status=np.zeros(n, dtype=np.int32))
+    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
+    if n:
+        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1)
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    return (out["out"], out["status"], *statuses) if given_traj else (out["out"], out["status"])
+
+
+def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views); returns the ephemeris statuses
+    [status, cat_status] of the calls from trajectories, None where there is none"""
+    pairs = _ffi.as_f64(pairs)
+    ctx = _ffi.context(device, slot)
+    S, D = src[0].shape[0], 0 if cat is None else cat[0].shape[0]
+    tail = (T0, T1, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+    if len(src) == 1:
+        _ffi.call("mpcx_conjunction_pairs", ctx, len(pairs), _ffi.dptr(pairs), S, D, M, _ffi.dptr(src[0]),
+                  _ffi.dptr_opt(None if cat is None else cat[0]), *tail)
+        return [None, None]
+    sides = [(N, side[0].shape[2], _ffi.iptr_opt(side[3]), _ffi.dptr(side[0]), _ffi.dptr(side[1]), _ffi.dptr(side[2])) if side is not None
+             else (0, 0, None, None, None, None) for N, side in ((S, src), (D, cat))]
+    statuses = [np.zeros(S, dtype=np.int32), None if cat is None else np.zeros(D, dtype=np.int32)]
+    _ffi.call("mpcx_conjunction_pairs_traj", ctx, len(pairs), _ffi.dptr(pairs), *sides[0], *sides[1], M, *tail,
+              *[_ffi.iptr_opt(st) for st in statuses])
+    return statuses
 
 
 def catalogue_trajectories(position_m, velocity_m_s, T0, T1, n, include_J2=True, device=0, devices=None):

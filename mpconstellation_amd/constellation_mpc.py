@@ -224,14 +224,30 @@ class ConstellationMPC:
         n_eval = int(self.sim_base_res * tf)
         # SequenceController(tf_u, tf_sim = interval): end_tau = tf_u / interval; the flight rides in the update's call
         flown = self.update(y0, fly=(tf, self.interval, n_eval, self.include_drag, self.include_J2, 0.001))
-        if flown is None:                                                    # (verbose path: the flight as its own call)
-            U = self._plan[1]
-            y, st, _ = self._timed("truth_propagation", propagate_batch, y0, tf, self.consts,
-                                   (_ffi.CTRL_SEQUENCE, U, U.shape[2], self.plan_tf / self.interval), n_eval,
-                                   self.include_drag, self.include_J2, 0.001, self.device, Kus=self.plan_K, devices=self.devices,
-                                   atmosphere=self.atmosphere)
-        else:
-            y, st = flown
+        y, st = self._fly_stored_plan(y0, tf, n_eval) if flown is None else flown      # (verbose path: the flight as its own call)
+        self._segment_flown(y, st, tf, n_eval)
+
+    def fly_plan(self, tf=1):
+        """Fly tf under the truth model with the plan the instance HOLDS (the last update's, or one put in its place), without
+        planning again: run_segment without its update -- the same playback of the thrust table (SequenceController(tf_u,
+        tf_sim = interval)), the same bookkeeping (the satellites' states, the flown segment), and the horizon is left alone."""
+        if self._plan is None:
+            raise ValueError("fly_plan: the instance holds no plan yet (update or run_segment)")
+        n_eval = int(self.sim_base_res * tf)
+        y, st = self._fly_stored_plan(self._y0(), tf, n_eval)
+        self._segment_flown(y, st, tf, n_eval)
+
+    def _fly_stored_plan(self, y0, tf, n_eval):
+        """the stored plan's thrust table played back from y0 over tf under the truth model -> (y, status)"""
+        U = self._plan[1]
+        y, st, _ = self._timed("truth_propagation", propagate_batch, y0, tf, self.consts,
+                               (_ffi.CTRL_SEQUENCE, U, U.shape[2], self.plan_tf / self.interval), n_eval,
+                               self.include_drag, self.include_J2, 0.001, self.device, Kus=self.plan_K, devices=self.devices,
+                               atmosphere=self.atmosphere)
+        return y, st
+
+    def _segment_flown(self, y, st, tf, n_eval):
+        """run_segment's tail: check the flight, move the satellites to its end, keep the segment"""
         self._check(st)
         t = np.linspace(0, 1, n_eval)
         f = self._f

@@ -6,8 +6,10 @@
 //                      node positions and velocities (the state carries the velocity: C1, error h_n^4 / 384 max |p''''|);
 //   screen_kernel      for every (row, column) pair and every grid interval the closest approach of the two Hermite arcs -- chord
 //                      minimum, then three Newton steps on d . d' -- reduced to one (distance, partner, time) per row and, with a
-//                      threshold, to a list of the pairs that come closer than it.
-// Two screens launch it.  All pairs of one constellation (SELF): rows and columns are the same S satellites, the full square of
+//                      threshold, to a list of the pairs that come closer than it;
+//   pairs_kernel       the same closest approach for the pairs of a LIST (a screen's, flown again after a manoeuvre): one wave
+//                      per pair, n x M work, the bits the screens give the pair.
+// Two screens launch screen_kernel.  All pairs of one constellation (SELF): rows and columns are the same S satellites, the full square of
 // ordered pairs (i, j != i) is computed, the list holds the pairs i < j.  A constellation against a catalogue of foreign objects
 // (cross): rows are the S satellites, columns the D objects, the rectangle S x D is computed and not the square (S + D)^2 of the
 // union, the list holds every pair.
@@ -261,6 +263,85 @@ __global__ __launch_bounds__(256) void conjunction_reduce_kernel(int nrows, int 
     dmin[r] = bj < 0 ? cj_inf() : sqrt(bd2);
     partner[r] = bj;
     tca[r] = bt;
+}
+
+struct PairsArgs {
+    int n, S, D, M;                   // D = 0: j indexes the constellation as i does (all pairs); D > 0: the catalogue
+    double T0, T1, h;
+    const double *pairs;              // [n][4], columns 0 and 1 are read
+    const double *eph, *cat;          // [S][6][M], [D][6][M] (cat = eph when D = 0)
+    double *out;                      // [n][4]
+    int32_t *status;                  // [n]
+};
+
+// an index column of the list -> the index, -1 where it is not a whole number of 0 .. N-1 (NaN and infinities among them)
+__device__ __forceinline__ int cj_index(double x, int N) { return x >= 0.0 && x < (double)N && x == (double)(int)x ? (int)x : -1; }
+
+// one object's end at instant m from its rows of eph [6][M]; a NaN in any of the six values is a NaN in all of them
+// (conjunction_transpose_kernel's rule: the screen reads its ends behind it)
+__device__ __forceinline__ void cj_end(const double *e, int M, int m, double (&p)[3], double (&v)[3])
+{
+    bool nan = false;
+    for (int c = 0; c < 3; ++c) {
+        p[c] = e[(size_t)c * M + m]; v[c] = e[(size_t)(3 + c) * M + m];
+        nan = nan || !(p[c] == p[c]) || !(v[c] == v[c]);
+    }
+    for (int c = 0; c < 3; ++c) { p[c] = nan ? cj_nan() : p[c]; v[c] = nan ? cj_nan() : v[c]; }
+}
+
+// The closest approach of LISTED pairs: n x M work where the screens do S^2 x M.  One wave per pair (blockIdx.x = the list's row);
+// lane l takes the grid intervals l, l + 64, ... in ascending order through cj_interval, with the row / column roles and `up` as
+// screen_kernel forms them (row = i, column = j; the difference is (higher index) - (lower index), against a catalogue column - row),
+// so an interval's (q, t) are the screen's bits.  The screen keeps a pair's minimum over the intervals in ascending order, each only
+// if strictly smaller: the smallest q, of equal ones the earliest interval.  Here every lane keeps (q, t, interval) of its own
+// intervals under that rule and an xor butterfly takes the minimum under (q, interval) over the lanes -- a total order, so every
+// lane ends with the same triple and the result does not depend on how the intervals were dealt out.  Lane 0 stores.
+__global__ __launch_bounds__(64) void pairs_kernel(PairsArgs a)
+{
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const bool cross = a.D > 0;
+    const double xi = a.pairs[(size_t)r * 4], xj = a.pairs[(size_t)r * 4 + 1];
+    const int i = cj_index(xi, a.S), j = cj_index(xj, cross ? a.D : a.S);
+    double *o = a.out + (size_t)r * 4;
+    if (i < 0 || j < 0 || (!cross && i == j)) {                      // (the whole wave: it reads nothing of the ephemerides)
+        if (lane == 0) { o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan(); a.status[r] = MPCX_ST_BADK; }
+        return;
+    }
+    const bool up = cross || j > i;                                  // the column is the higher index: column - row
+    const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
+    double best = cj_inf(), tbest = cj_nan();
+    int mbest = 0x7fffffff;
+    for (int m = lane; m < a.M - 1; m += 64) {
+        double p0[3], v0[3], p1[3], v1[3], c0[6], c1[6];
+        {
+            double cp[3], cv[3];
+            cj_end(er, a.M, m, p0, v0); cj_end(er, a.M, m + 1, p1, v1);
+            cj_end(ec, a.M, m, cp, cv);
+            for (int c = 0; c < 3; ++c) { c0[c] = cp[c]; c0[3 + c] = cv[c]; }
+            cj_end(ec, a.M, m + 1, cp, cv);
+            for (int c = 0; c < 3; ++c) { c1[c] = cp[c]; c1[3 + c] = cv[c]; }
+        }
+        const double t0 = cj_time(m, a.M, a.T0, a.T1, a.h), t1 = cj_time(m + 1, a.M, a.T0, a.T1, a.h);
+        double d0[3], d1[3];
+        for (int c = 0; c < 3; ++c) {
+            d0[c] = up ? c0[c] - p0[c] : p0[c] - c0[c];
+            d1[c] = up ? c1[c] - p1[c] : p1[c] - c1[c];
+        }
+        const double before = best;
+        cj_interval(d0, d1, c0 + 3, c1 + 3, v0, v1, up, a.h, t0, t1, best, tbest);
+        if (best < before) mbest = m;
+    }
+    for (int w = 32; w >= 1; w >>= 1) {
+        const double qo = __shfl_xor(best, w), to = __shfl_xor(tbest, w);
+        const int mo = __shfl_xor(mbest, w);
+        if (qo < best || (qo == best && mo < mbest)) { best = qo; tbest = to; mbest = mo; }
+    }
+    if (lane == 0) {
+        o[0] = xi; o[1] = xj;
+        o[2] = best < cj_inf() ? sqrt(best) : cj_inf();              // no valid interval: +inf, NaN, as the screens' rows have it
+        o[3] = best < cj_inf() ? tbest : cj_nan();
+        a.status[r] = MPCX_ST_OK;
+    }
 }
 
 // The two screens as the host sees them: the name in the messages, and whether the columns are the rows' own constellation
@@ -559,4 +640,143 @@ extern "C" int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, c
     if (status) ar.download(status, dst, S);
     if (cat_status) ar.download(cat_status, cst, D);
     return screen_from_device(ctx, ar, CROSS, c, ws.eph, ws.cat, dws);
+}
+
+// ---- listed pairs
+namespace mpcx {
+
+struct PairsCall {
+    int n, S, D, M;
+    double T0, T1;
+};
+
+static int pairs_check(mpcx_ctx *ctx, const char *name, const PairsCall &c)
+{
+    if (c.n < 1 || c.S < 1 || c.D < 0 || c.M < 2 || !(c.T1 > c.T0)) return screen_fail(ctx, name, "need n>=1, S>=1, D>=0, M>=2, T1>T0");
+    return MPCX_OK;
+}
+
+// the two ephemerides of the _traj calls: [eph S*6*M][cat D*6*M]
+struct PairsWorkspace {
+    double *eph, *cat;
+    size_t bytes;
+    PairsWorkspace(void *base, int S, int D, int M)
+    {
+        char *p = (char *)base;
+        eph = (double *)p; p += cj_align((size_t)S * 6 * M * sizeof(double));
+        cat = D > 0 ? (double *)p : eph;
+        if (D > 0) p += cj_align((size_t)D * 6 * M * sizeof(double));
+        bytes = (size_t)(p - (char *)base);
+    }
+};
+
+// pairs_kernel on `st`, everything in device memory
+static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs, const double *eph, const double *cat, double *out,
+                         int32_t *status, hipStream_t st)
+{
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    const PairsArgs a{c.n, c.S, c.D, c.M, c.T0, c.T1, (c.T1 - c.T0) / (double)(c.M - 1), pairs, eph, c.D > 0 ? cat : eph, out, status};
+    hipLaunchKernelGGL(pairs_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
+}  // namespace mpcx
+
+extern "C" size_t mpcx_conjunction_pairs_workspace_bytes(int S, int D, int M)
+{
+    if (S < 1 || D < 0 || M < 2) return 0;
+    return PairsWorkspace(nullptr, S, D, M).bytes;
+}
+
+extern "C" int mpcx_conjunction_pairs_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph,
+                                          const double *cat, double T0, double T1, double *out, int32_t *status, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const PairsCall c{n, S, D, M, T0, T1};
+    if (int rc = pairs_check(ctx, "conjunction_pairs", c)) return rc;
+    if (!pairs || !eph || !out || !status || (D > 0) != (cat != nullptr))
+        return screen_fail(ctx, "conjunction_pairs", "pairs, eph, out and status are required, and cat exactly when D > 0");
+    return pairs_enqueue(ctx, c, pairs, eph, cat, out, status, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_conjunction_pairs(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                                      double T0, double T1, double *out, int32_t *status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const PairsCall c{n, S, D, M, T0, T1};
+    if (int rc = pairs_check(ctx, "conjunction_pairs", c)) return rc;
+    if (!pairs || !eph || !out || !status || (D > 0) != (cat != nullptr))
+        return screen_fail(ctx, "conjunction_pairs", "pairs, eph, out and status are required, and cat exactly when D > 0");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *dp = ar.upload(pairs, (size_t)n * 4), *de = ar.upload(eph, (size_t)S * 6 * M);
+    double *dc = D > 0 ? ar.upload(cat, (size_t)D * 6 * M) : nullptr;
+    double *dout = ar.alloc<double>((size_t)n * 4);
+    int32_t *dst = ar.alloc<int32_t>(n);
+    if (ar.failed()) return ar.code();
+    if (int rc = pairs_enqueue(ctx, c, dp, de, dc, dout, dst, ctx->stream)) return rc;
+    ar.download(out, dout, (size_t)n * 4);
+    ar.download(status, dst, n);
+    return ar.finish();
+}
+
+extern "C" int mpcx_conjunction_pairs_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                               const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                               const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                               double T1, double *out, int32_t *status, int32_t *eph_status, int32_t *cat_status,
+                                               void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const PairsCall c{n, S, D, M, T0, T1};
+    if (int rc = pairs_check(ctx, "conjunction_pairs_traj", c)) return rc;
+    if (nn < 1 || (D > 0 && cat_n < 1)) return screen_fail(ctx, "conjunction_pairs_traj", "need n>=1 nodes on each side");
+    if (!pairs || !Y || !units || !span || !out || !status || !eph_status || !workspace)
+        return screen_fail(ctx, "conjunction_pairs_traj", "pairs, Y, units, span, out, status, eph_status and workspace are required");
+    if (D > 0 ? !cat_Y || !cat_units || !cat_span || !cat_status : cat_Y != nullptr)
+        return screen_fail(ctx, "conjunction_pairs_traj", "cat_Y, cat_units, cat_span and cat_status are required exactly when D > 0");
+    const PairsWorkspace ws(workspace, S, D, M);
+    if (int rc = mpcx_ephemeris_batch_dev(ctx, S, nn, ns, Y, units, span, M, T0, T1, ws.eph, eph_status, stream)) return rc;
+    if (D > 0)
+        if (int rc = mpcx_ephemeris_batch_dev(ctx, D, cat_n, cat_ns, cat_Y, cat_units, cat_span, M, T0, T1, ws.cat, cat_status, stream)) return rc;
+    return pairs_enqueue(ctx, c, pairs, ws.eph, ws.cat, out, status, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_conjunction_pairs_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                           const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                           const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                           double *out, int32_t *status, int32_t *eph_status, int32_t *cat_status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const PairsCall c{n, S, D, M, T0, T1};
+    if (int rc = pairs_check(ctx, "conjunction_pairs_traj", c)) return rc;
+    if (nn < 1 || (D > 0 && cat_n < 1)) return screen_fail(ctx, "conjunction_pairs_traj", "need n>=1 nodes on each side");
+    if (!pairs || !Y || !units || !span || !out || !status)
+        return screen_fail(ctx, "conjunction_pairs_traj", "pairs, Y, units, span, out and status are required");
+    if (D > 0 ? !cat_Y || !cat_units || !cat_span : cat_Y != nullptr)
+        return screen_fail(ctx, "conjunction_pairs_traj", "cat_Y, cat_units and cat_span are required exactly when D > 0");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *dp = ar.upload(pairs, (size_t)n * 4);
+    double *dY = ar.upload(Y, (size_t)S * 7 * nn), *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2);
+    int32_t *dns = ns ? ar.upload(ns, S) : nullptr;
+    double *cY = nullptr, *cu = nullptr, *csp = nullptr;
+    int32_t *cns = nullptr, *cst = nullptr;
+    if (D > 0) {
+        cY = ar.upload(cat_Y, (size_t)D * 7 * cat_n); cu = ar.upload(cat_units, (size_t)D * 2); csp = ar.upload(cat_span, (size_t)D * 2);
+        cns = cat_ns ? ar.upload(cat_ns, D) : nullptr;
+        cst = ar.alloc<int32_t>(D);
+    }
+    int32_t *est = ar.alloc<int32_t>(S), *dst = ar.alloc<int32_t>(n);
+    double *dout = ar.alloc<double>((size_t)n * 4);
+    char *dws = ar.alloc<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));      // neither ephemeris leaves HBM
+    if (ar.failed()) return ar.code();
+    if (int rc = mpcx_conjunction_pairs_traj_dev(ctx, n, dp, S, nn, dns, dY, du, dsp, D, cat_n, cns, cY, cu, csp, M, T0, T1, dout, dst, est, cst,
+                                                 dws, ctx->stream))
+        return rc;
+    ar.download(out, dout, (size_t)n * 4);
+    ar.download(status, dst, n);
+    if (eph_status) ar.download(eph_status, est, S);
+    if (D > 0 && cat_status) ar.download(cat_status, cst, D);
+    return ar.finish();
 }
