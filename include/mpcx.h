@@ -907,6 +907,72 @@ int mpcx_avoidance_joint_dev(mpcx_ctx *ctx, int n, const double *pairs, const in
                              double *du, double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status,
                              int32_t *row_status, void *workspace, void *stream);
 
+/*
+ * Iterated avoidance: the manoeuvre flown again, looked at again and corrected, on the device.  mpcx_avoidance_joint stops at a
+ * first-order answer that nothing flies: flown through the nonlinear dynamics it falls short of the target by some 1e-3 of it, the
+ * held end state drifts, and a row whose other object is moved by another row (the wrappers' `coupled`) is not corrected at all.
+ * This call closes the loop for the whole list and all S satellites on one device -- a coupled row needs every mover's new
+ * trajectory in every round, so there is no block form (no sat0, nsat).
+ *
+ * Inputs.  Everything mpcx_avoidance_joint takes except sat0 and nsat; `flags` is the model of the flight AND of the linearisation.
+ * M, T0, T1: the re-screen's grid linspace(T0, T1, M), as mpcx_conjunction_pairs_traj takes it.  prop_max_step > 0: the flight's
+ * step limit.  rounds >= 0: the number of corrections.  P and cat_P stay as given over all passes.
+ *
+ * Passes t = 0 .. rounds + 1.
+ *   t = 0: mpcx_avoidance_joint on (pairs, Y, U) as given; du, sat_out, row_out, rows, tsens and the statuses have its bits.  A
+ *     satellite FLIES when this pass gave it rows and status MPCX_ST_OK (a finite du); who flies never changes afterwards.
+ *   t >= 1, the flight: U_t = U + du_t-1 for a satellite that flies, U otherwise.  Y_t[s] of a satellite that flies is
+ *     mpcx_propagate_batch_ragged_dev from Y[s][:, 0] over tf = (span[1] - span[0]) / units[1] under MPCX_CTRL_SEQUENCE with the table
+ *     U_t[s], Kus = n_evals = Ks, end_tau = 1, max_step = prop_max_step (columns past Ks[s] zero); every other satellite keeps Y[s].
+ *   t >= 1, the re-screen: mpcx_conjunction_pairs_traj_dev of the given list on Y_t (and the catalogue); its out [n][4] IS this
+ *     pass's list.  A row without a valid interval (+inf, NaN) gets the status the joint call gives a row with that time.
+ *   t >= 1, the solve: one linearisation about (Y_t, U_t), the rows of the joint call, and per satellite the joint call's problem
+ *     with three changes.  The unknown du is the TOTAL change from the given U (the centre of the ball projection and the origin the
+ *     effort is measured from: du_m(z) = proj_ball(U_m + (A^T z)_m / D_m) - U_m, and MPCX_AJ_UMAX, _COST, _DV are of U + du and du);
+ *     row p reads sum_m a_p,m . du_m >= b_p + sum_m a_p,m . (U_t,m - U_m), the ball-alone INFEASIBLE test uses that value and U; the
+ *     terminal rows read sum_m T_m du_m = sum_m T_m du_t-1,m - (Y_t[0:6, ns-1] - Y[0:6, ns-1]) -- the end state is held to the GIVEN
+ *     plan's; the iteration starts from the z of the satellite's last converged solve instead of 0 (a cold start of a later round does
+ *     not converge in general).  D_m takes the mass row of Y_t.  row_out's MARGIN, DIST and DT are predictions from this pass's
+ *     linearisation for the change U + du - U_t.
+ *   t = rounds + 1: the flight, the re-screen and the rows' d0, no solve: every call returns its answer AS FLOWN.
+ * Failures.  Pass 0's result is taken as it is: NaN on failure; such a satellite never flies and counts as not moving.  For t >= 1 a
+ * solve that fails (any status of the joint call) or a flight that fails (the rollout's status; its Y_t is the given Y[s]) keeps
+ * du_t-1, sat_out and the satellite's rows of row_out as they were, reports its status in sat_status and FREEZES the satellite: no
+ * more solves, and it keeps flying du_t-1.  rounds_done [S]: the index of the last pass whose solve was accepted (-1: none, or no rows).
+ *
+ * Outputs.  The joint call's: du [S][3][K] the total change from U, sat_out and row_out of the last accepted solve, sat_status,
+ * row_status; rows [n][3][K] and tsens [S][6][3][K] (each may be NULL) of the last pass that solved (pass `rounds`; a satellite left
+ * alone by it keeps what an earlier pass wrote).  Y_out [S][7][K]: the last flight.  pairs_out [n][4]: the last re-screen.
+ * hist_d0, hist_tca [rounds + 2][n]: each pass's d0 in the target's metric and the time the row was
+ * taken at (pass 0: column 3 of pairs; later: the re-screen's).  hist_term [rounds + 2][S]: max |Y_t[0:6, ns-1] - Y[0:6, ns-1]|,
+ * normalised; 0 for a satellite that does not fly and in pass 0.  rhs_rows [n], rhs_term [S][6] (each may be NULL): the right-hand
+ * sides of pass `rounds`'s solve in the rows' own units (NaN / 0 for rows and satellites that pass left alone).
+ * Every sum keeps a fixed order; results do not depend on the launch shape or on which optional outputs are asked for.
+ * Argument errors are the joint call's, plus rounds < 0, M < 2, T1 <= T0, prop_max_step <= 0, a missing required output:
+ * MPCX_E_BADARG, nothing enqueued.  The _dev variant takes device pointers throughout and a workspace of
+ * mpcx_avoidance_refine_workspace_bytes(n, S, K, D, M) bytes (D = 0 without a catalogue; 0 for n < 1, S < 1, K < 2, D < 0 or M < 2;
+ * contents unspecified on entry and exit); it enqueues everything on `stream`, the number of passes is fixed and nothing is read back
+ * or waited for between them.
+ */
+size_t mpcx_avoidance_refine_workspace_bytes(int n, int S, int K, int D, int M);
+int mpcx_avoidance_refine(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                          const double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                          double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
+                          const double *cat_units, const double *cat_span, const double *cat_P, double mu, double target,
+                          const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double T1,
+                          double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows, double *tsens,
+                          int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0,
+                          double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term);
+int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                              const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                              int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                              const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
+                              double target, const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0,
+                              double T1, double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows,
+                              double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out,
+                              double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows,
+                              double *rhs_term, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,16 @@ _SIGS = {
     "mpcx_avoidance_joint_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
                                            C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
                                            C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # iterated avoidance: the joint manoeuvre flown again, re-screened and corrected, a fixed number of rounds on the device
+    "mpcx_avoidance_refine_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mpcx_avoidance_refine": (C.c_int, [_vp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                        C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_double, C.c_int,
+                                        C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                        _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "mpcx_avoidance_refine_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
+                                            C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
+                                            C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)

@@ -18,6 +18,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
                  the least-effort thrust change that opens the miss to a requested distance.
   avoidance_joint   per manoeuvring satellite ONE thrust change that opens all of its listed encounters at once, inside its thrust
                  limit, and optionally holds the plan's terminal state.
+  avoidance_refine  that manoeuvre flown through the nonlinear dynamics, re-screened, linearised and corrected, a fixed number of
+                 rounds on the device: the answer as flown.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
 import numpy as np
@@ -701,19 +703,8 @@ def _coupled(pairs, mover, against_catalogue):
     return np.isin(other, moving)
 
 
-def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", u_max=None, hold_terminal=True,
-                    tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, include_drag=False, include_J2=False, atmosphere=None,
-                    max_step=DEFAULT_MAX_STEP, mu=None, return_rows=False, return_terminal=False, device=0, devices=None):
-    """One thrust change per manoeuvring satellite that opens ALL of its listed close approaches to `target` at once, stays inside
-    its thrust ball |U + du| <= u_max at every node and, with hold_terminal, leaves the plan's last position and velocity where they
-    were to first order -> AvoidanceJointResult.  pairs, target, Y, U, units, span, consts, ns, P, cat and the model as `avoidance`
-    takes them; who = "i", "j" or an (n,) array of 0 / 1: which object of each pair moves (exactly one; against a catalogue the
-    satellite).  u_max: a scalar or (S,) normalised thrust limits, None: no ball.  A satellite's rows are the pairs it moves for, at
-    most 8; every row is the tangent half-plane of its target ellipse, so a met row is at or beyond the target to first order, and
-    rows already beyond it stay in the problem.  The device solves the strictly convex problem per satellite by a semismooth Newton
-    iteration to max |F| <= tol (include/mpcx.h).  return_rows / return_terminal: the rows a_p (n, 3, K) and the terminal
-    sensitivities (S, 6, 3, K).  An empty list returns zeros without a library call.  devices=[d0, d1, ...]: contiguous blocks of
-    satellites on several devices (every device holds the whole plan and list), written in place, the bits of one device."""
+def _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, tol, max_iter, max_step, mu):
+    """the checks avoidance_joint and avoidance_refine share -> (pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu)"""
     from .constants import MU_EARTH
     if isinstance(pairs, ConjunctionResult):
         pairs = pairs.pairs
@@ -757,6 +748,25 @@ def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, c
     mu = float(MU_EARTH if mu is None else mu)
     if not mu > 0.0:
         raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    return pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu
+
+
+def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", u_max=None, hold_terminal=True,
+                    tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, include_drag=False, include_J2=False, atmosphere=None,
+                    max_step=DEFAULT_MAX_STEP, mu=None, return_rows=False, return_terminal=False, device=0, devices=None):
+    """One thrust change per manoeuvring satellite that opens ALL of its listed close approaches to `target` at once, stays inside
+    its thrust ball |U + du| <= u_max at every node and, with hold_terminal, leaves the plan's last position and velocity where they
+    were to first order -> AvoidanceJointResult.  pairs, target, Y, U, units, span, consts, ns, P, cat and the model as `avoidance`
+    takes them; who = "i", "j" or an (n,) array of 0 / 1: which object of each pair moves (exactly one; against a catalogue the
+    satellite).  u_max: a scalar or (S,) normalised thrust limits, None: no ball.  A satellite's rows are the pairs it moves for, at
+    most 8; every row is the tangent half-plane of its target ellipse, so a met row is at or beyond the target to first order, and
+    rows already beyond it stay in the problem.  The device solves the strictly convex problem per satellite by a semismooth Newton
+    iteration to max |F| <= tol (include/mpcx.h).  return_rows / return_terminal: the rows a_p (n, 3, K) and the terminal
+    sensitivities (S, 6, 3, K).  An empty list returns zeros without a library call.  devices=[d0, d1, ...]: contiguous blocks of
+    satellites on several devices (every device holds the whole plan and list), written in place, the bits of one device."""
+    pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
+                                                                                     u_max, tol, max_iter, max_step, mu)
+    (S, _, K), n = Y.shape, pairs.shape[0]
     out = dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
                rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
                sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32))
@@ -791,3 +801,81 @@ def _avoidance_joint_call(index, *, device, slot, out, pairs, mover, rows, cols,
               target, _ffi.dptr_opt(u_max), hold, tol, max_iter, int(index[0]), len(index), _ffi.dptr(whole["du"]), _ffi.dptr(whole["sat_out"]),
               _ffi.dptr(whole["row_out"]), _ffi.dptr_opt(whole["rows"]), _ffi.dptr_opt(whole["tsens"]), _ffi.iptr(whole["sat_status"]),
               _ffi.iptr(whole["row_status"]))
+
+
+# ---- the joint manoeuvre flown again, re-screened and corrected (include/mpcx.h: mpcx_avoidance_refine; csrc/avoidance_joint.hip)
+class AvoidanceRefineResult(AvoidanceJointResult):
+    """AvoidanceJointResult of the last accepted solve -- du is the total change from the given U -- with the answer as flown:
+    Y_flown (S, 7, K) the last flight (the given trajectory for a satellite that does not fly), pairs_flown (n, 4) the last re-screen
+    of the list on it, d0_history and tca_history (rounds + 2, n) each pass's distance in the target's metric and its time,
+    terminal_history (rounds + 2, S) the largest normalised end-state difference from the given plan (0 for a satellite that does not
+    fly), rounds_done (S,) int32 the last pass whose solve was accepted (-1: none, or no rows), and rhs_rows (n,) / rhs_term (S, 6)
+    the last solve's right-hand sides or None.  A satellite whose later solve or flight failed keeps its earlier du and reports the
+    failure in status (apply raises for it as for any status that is not 0; U + du is there to be taken)."""
+
+    def __init__(self, joint, Y_flown, pairs_flown, d0_history, tca_history, terminal_history, rounds_done, rhs_rows, rhs_term):
+        super().__init__(*joint)
+        self.Y_flown, self.pairs_flown, self.d0_history, self.tca_history = Y_flown, pairs_flown, d0_history, tca_history
+        self.terminal_history, self.rounds_done, self.rhs_rows, self.rhs_term = terminal_history, rounds_done, rhs_rows, rhs_term
+
+    def __repr__(self):
+        return f"AvoidanceRefineResult(pairs={len(self.pairs)}, satellites={len(self.du)}, passes={len(self.d0_history)})"
+
+
+def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds=3, ns=None, P=None, cat=None, who="i", u_max=None,
+                     hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, include_drag=False, include_J2=False,
+                     atmosphere=None, max_step=DEFAULT_MAX_STEP, prop_max_step=1e-3, mu=None, return_rows=False, return_terminal=False,
+                     return_rhs=False, device=0, devices=None):
+    """avoidance_joint, then `rounds` times on the device: fly U + du through the nonlinear dynamics (include_drag / include_J2 /
+    atmosphere are the model of the flight and of the linearisation; prop_max_step the flight's step limit), look at the LISTED pairs
+    again on the grid linspace(T0, T1, M) (screen_pairs), linearise about what was flown and solve again -- the effort measured from
+    the given U, the end state held to the given plan's, the multipliers of the last solve as the start -- and once more fly and
+    re-screen -> AvoidanceRefineResult, the answer as flown.  All other arguments as avoidance_joint takes them.  rounds = 0 is
+    avoidance_joint followed by one flight and re-screen.  A row whose other object is moved by another row (`coupled`) sees that
+    object's new trajectory in every round.  An empty list returns zeros without a library call.  One device: every round needs every
+    mover's new trajectory, so there is no block form and devices with more than one entry raises ValueError."""
+    pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
+                                                                                     u_max, tol, max_iter, max_step, mu)
+    (S, _, K), n = Y.shape, pairs.shape[0]
+    M, T0, T1 = _check_grid(M, T0, T1)
+    if not (np.ndim(rounds) == 0 and int(rounds) == rounds and rounds >= 0):
+        raise ValueError(f"rounds: need an integer >= 0, got {rounds}")
+    if not prop_max_step > 0.0:
+        raise ValueError(f"prop_max_step: need > 0, got {prop_max_step}")
+    if devices is not None and len(devices) > 1:
+        raise ValueError(f"devices: avoidance_refine runs on one device (every round needs every mover's new trajectory), got {len(devices)}")
+    if devices is not None and len(devices) == 1:
+        device = int(devices[0])
+    rounds = int(rounds)
+    out = dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
+               rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
+               sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32),
+               Y_flown=Y.copy(), pairs_flown=pairs.copy(), d0=np.zeros((rounds + 2, n)), tca=np.zeros((rounds + 2, n)),
+               term=np.zeros((rounds + 2, S)), rounds_done=np.full(S, -1, dtype=np.int32),
+               rhs_rows=np.zeros(n) if return_rhs else None, rhs_term=np.zeros((S, 6)) if return_rhs else None)
+    if n:
+        _avoidance_refine_call(device=device, slot=0, out=out, pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols,
+                               mu=mu, target=float(target), hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter),
+                               flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere,
+                               grid=(M, T0, T1), prop_max_step=float(prop_max_step), rounds=rounds)
+    joint = (pairs, mover, out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"], out["row_status"],
+             _coupled(pairs, mover, cols is not None))
+    return AvoidanceRefineResult(joint, out["Y_flown"], out["pairs_flown"], out["d0"], out["tca"], out["term"], out["rounds_done"],
+                                 out["rhs_rows"], out["rhs_term"])
+
+
+def _avoidance_refine_call(*, device, slot, out, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere, grid,
+                           prop_max_step, rounds):
+    """the whole list and all satellites on context (device, slot), into `out`"""
+    Y, U, units, span, consts, ns, P, u_max = rows
+    col = (0, 0, None, None, None, None, None)
+    if cols is not None:
+        cY, cunits, cspan, cns, cP = cols
+        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_avoidance_refine", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
+              _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
+              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, *grid, prop_max_step, rounds, _ffi.dptr(out["du"]), _ffi.dptr(out["sat_out"]),
+              _ffi.dptr(out["row_out"]), _ffi.dptr_opt(out["rows"]), _ffi.dptr_opt(out["tsens"]), _ffi.iptr(out["sat_status"]),
+              _ffi.iptr(out["row_status"]), _ffi.dptr(out["Y_flown"]), _ffi.dptr(out["pairs_flown"]), _ffi.dptr(out["d0"]), _ffi.dptr(out["tca"]),
+              _ffi.dptr(out["term"]), _ffi.iptr(out["rounds_done"]), _ffi.dptr_opt(out["rhs_rows"]), _ffi.dptr_opt(out["rhs_term"]))

@@ -404,6 +404,37 @@ class ConstellationMPC:
                                             cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol, max_iter=max_iter,
                                             return_rows=return_rows, return_terminal=return_terminal, **model, **where)
 
+    def avoidance_refine(self, threshold_m, target, rounds=3, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i",
+                         hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, prop_max_step=1e-3, model="plan",
+                         install=False, return_rows=False, return_terminal=False, return_rhs=False):
+        """avoidance_joint's manoeuvre flown again, re-screened and corrected `rounds` times on the device -> (ConjunctionResult,
+        AvoidanceRefineResult).  The plan is screened as avoidance_joint screens it, u_max comes from this instance's u_lim option,
+        the re-screen's grid and span are the plan's screen window (samples_per_node).  model = 'plan' flies and linearises under the
+        planning model (plan_drag, plan_J2), 'truth' under the model the segments are flown with (include_drag, include_J2, the
+        atmosphere).  install=True puts Y_flown and U + du of every satellite whose status is 0 into the plan the instance holds, so
+        that fly_plan flies the refined manoeuvre."""
+        from . import conjunction as cj
+        if model not in ("plan", "truth"):
+            raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
+        w, screened, P, cat, plan_model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
+        if model == "truth":
+            plan_model = dict(include_drag=self.include_drag, include_J2=self.include_J2, atmosphere=self.atmosphere if self.include_drag else None)
+        from .optimizer import DEFAULT_OPTIONS
+        u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
+        u_max = np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
+        res = cj.avoidance_refine(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, w["M"], w["T0"], w["T1"],
+                                  rounds=rounds, ns=w["ns"], P=P, cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol,
+                                  max_iter=max_iter, prop_max_step=prop_max_step, return_rows=return_rows, return_terminal=return_terminal,
+                                  return_rhs=return_rhs, device=self.device, devices=None if self.devices is None else list(self.devices)[:1],
+                                  **plan_model)
+        if install:
+            ok = (res.status == 0) & np.isfinite(res.du).all(axis=(1, 2))
+            X, U = np.array(self._plan[0], dtype=np.float64), np.array(self._plan[1], dtype=np.float64)
+            X[ok] = res.Y_flown[ok]
+            U[ok] = U[ok] + res.du[ok]
+            self._plan = (X, U) + tuple(self._plan[2:])
+        return screened, res
+
     @staticmethod
     def _check(status):
         if (status == 1).any():

@@ -8,6 +8,8 @@
 //                     lane per entry of H and of the residual (sums over the nodes in ascending order), a Cholesky in LDS.
 // Nothing crosses a workgroup; every sum runs in ascending index order or in the xor butterfly's fixed order: the results depend on
 // the inputs alone (tests/avoidance_joint_reference.py restates them).  Plain vector loads and stores throughout.
+// At the end of the file: mpcx_avoidance_refine*, the loop around the joint call (fly, re-screen, linearise, solve again), which gives
+// aj_solve_kernel a reference thrust, a terminal right-hand side and a warm start -- all absent in the joint call itself.
 #include "collision_device.hpp"
 
 #include <string.h>
@@ -47,6 +49,15 @@ struct AjArgs {
     double *jd;                       // workspace [S][6][K]: the projection's Jacobian over D_m, upper triangle
     double *du, *sat_out, *row_out;
     int32_t *sat_status, *row_status;
+    // the refinement's inputs of aj_solve_kernel (mpcx_avoidance_refine); all absent in the joint call, whose code they leave alone
+    const double *uref = nullptr;     // [S][3][K]: the centre of the ball projection and the origin of the effort (NULL: U)
+    const double *trhs = nullptr;     // [S][6]: the terminal rows' right-hand side (NULL: 0)
+    const double *z0 = nullptr;       // [S][AJ_NZ]: the start of the iteration, y then lambda * target in row order (NULL: 0)
+    double *z_out = nullptr;          // [S][AJ_NZ]: the converged z (may be z0)
+    const int32_t *skip = nullptr;    // [S]: not 0: the satellite is left alone, nothing of it is written
+    int T_ready = 0;                  // T holds the terminal sweep already (ar_trhs_kernel ran it)
+    double *rhs_rows = nullptr;       // [n]: the encounter rows' right-hand sides as solved, in the rows' own units
+    double *rhs_term = nullptr;       // [S][6]: the terminal rows'
 };
 
 __device__ __forceinline__ double aj_wave_sum(double x)
@@ -260,7 +271,8 @@ struct AjSat {
     int ns, ne, r, nz;
     double hn, cfac, umax, target;
     bool ball;
-    const double *mass, *ubar, *T;    // Y[s][6][.], U[s], T[s]
+    const double *mass, *ctr, *T;     // Y[s][6][.], the centre of the projection (U[s]; uref[s] when given), T[s]
+    const double *trhs;               // the terminal rows' right-hand side [6] or NULL
     double *du, *jd;
     const double *a;                  // all rows [n][3][K]
     size_t K;
@@ -291,7 +303,7 @@ __device__ __forceinline__ double aj_evaluate(const AjSat &sa, const int *idx, c
         const double D = wm * cm * cm;
         double ub[3], p[3], J[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0};                       // (00, 01, 02, 11, 12, 22)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { ub[c] = sa.ubar[(size_t)c * sa.K + m]; p[c] = ub[c] + v[c] / D; }
+        for (int c = 0; c < 3; ++c) { ub[c] = sa.ctr[(size_t)c * sa.K + m]; p[c] = ub[c] + v[c] / D; }
         const double pn = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
         if (sa.ball && pn > sa.umax) {
             const double sc = sa.umax / pn;
@@ -313,7 +325,7 @@ __device__ __forceinline__ double aj_evaluate(const AjSat &sa, const int *idx, c
         for (int m = 0; m < sa.ns; ++m)
             res = res + (aj_entry(sa, idx, lane, 0, m) * sa.du[m] + aj_entry(sa, idx, lane, 1, m) * sa.du[sa.K + m]
                          + aj_entry(sa, idx, lane, 2, m) * sa.du[2 * sa.K + m]);
-        if (lane < sa.ne) F[lane] = res;
+        if (lane < sa.ne) F[lane] = sa.trhs ? res - sa.trhs[lane] : res;
         else {
             const double s = res / sa.target - bh[lane - sa.ne];
             slack[lane - sa.ne] = s;
@@ -341,6 +353,7 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
     const int lane = threadIdx.x;
     if ((int)blockIdx.x >= a.nsat) return;
     const int s = a.sat0 + (int)blockIdx.x;
+    if (a.skip && a.skip[s]) return;
     const size_t K = (size_t)a.K;
     double *du = a.du + (size_t)s * 3 * K, *so = a.sat_out + (size_t)s * MPCX_NAJ;
     double *Ts = a.T + (size_t)s * 18 * K;
@@ -384,13 +397,16 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
     sa.umax = a.u_max ? a.u_max[s] : __longlong_as_double(0x7ff0000000000000LL);
     sa.ball = sa.umax < __longlong_as_double(0x7ff0000000000000LL);
     sa.target = a.target;
-    sa.mass = a.row.Y + ((size_t)s * 7 + 6) * K; sa.ubar = a.U + (size_t)s * 3 * K; sa.T = Ts;
+    sa.mass = a.row.Y + ((size_t)s * 7 + 6) * K; sa.ctr = (a.uref ? a.uref : a.U) + (size_t)s * 3 * K; sa.T = Ts;
+    sa.trhs = a.trhs ? a.trhs + (size_t)s * 6 : nullptr;
     sa.du = du; sa.jd = a.jd + (size_t)s * 6 * K; sa.a = a.a; sa.K = K;
     const int nz = sa.nz, ne = sa.ne, ns = sa.ns;
 
     for (int c = 0; c < 3; ++c)                                      // nodes past ns
         for (int m = ns + lane; m < a.K; m += 64) du[(size_t)c * K + m] = 0.0;
-    if (a.hold) {
+    if (a.hold && a.T_ready) {
+        // (the terminal sweep is in T already)
+    } else if (a.hold) {
         // ---- the terminal sweep: lam_ns-1 = [I_6 | 0], over the whole horizon
         for (int e = 0; e < 18; ++e)
             for (int m = ns + lane; m < a.K; m += 64) Ts[(size_t)e * K + m] = 0.0;
@@ -401,16 +417,30 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
     }
 
     // ---- a row the ball alone forbids: sum_m (u_max |a_m| - a_m . ubar_m) < b
-    if (lane < r) bh[lane] = a.info[(size_t)idx[lane] * AJ_INFO + AJI_B] / a.target;
+    //      (with a reference thrust the unknown is the change from uref while the row is linearised about U: b + sum_m a_m . (U_m - uref_m))
+    double brow = 0.0;
+    if (lane < r) {
+        brow = a.info[(size_t)idx[lane] * AJ_INFO + AJI_B];
+        if (a.uref) {
+            const double *ap = a.a + (size_t)idx[lane] * 3 * K, *ul = a.U + (size_t)s * 3 * K;
+            double sh = 0.0;
+            for (int m = 0; m < ns; ++m)
+                sh = sh + (ap[m] * (ul[m] - sa.ctr[m]) + ap[K + m] * (ul[K + m] - sa.ctr[K + m]) + ap[2 * K + m] * (ul[2 * K + m] - sa.ctr[2 * K + m]));
+            brow = brow + sh;
+        }
+        bh[lane] = brow / a.target;
+        if (a.rhs_rows) a.rhs_rows[idx[lane]] = brow;
+    }
+    if (a.rhs_term && lane < 6) a.rhs_term[(size_t)s * 6 + lane] = sa.trhs && a.hold ? sa.trhs[lane] : 0.0;
     bool infeasible = false;
     if (sa.ball && lane < r) {
         const double *ap = a.a + (size_t)idx[lane] * 3 * K;
         double reach = 0.0;
         for (int m = 0; m < ns; ++m) {
             const double a0 = ap[m], a1 = ap[K + m], a2 = ap[2 * K + m];
-            reach = reach + (sa.umax * sqrt(a0 * a0 + a1 * a1 + a2 * a2) - (a0 * sa.ubar[m] + a1 * sa.ubar[K + m] + a2 * sa.ubar[2 * K + m]));
+            reach = reach + (sa.umax * sqrt(a0 * a0 + a1 * a1 + a2 * a2) - (a0 * sa.ctr[m] + a1 * sa.ctr[K + m] + a2 * sa.ctr[2 * K + m]));
         }
-        infeasible = reach < a.info[(size_t)idx[lane] * AJ_INFO + AJI_B];
+        infeasible = reach < brow;
     }
     if (__ballot(infeasible)) st = MPCX_ST_INFEASIBLE;
     // ---- a row's own authority c_p = sum_m |a_p,m / target|^2 / D_m: what a multiplier of 1 moves the row by when it acts alone
@@ -430,7 +460,7 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
     int iters = 0, nball = 0;
     double mF = 0.0;
     if (st == MPCX_ST_OK) {
-        if (lane < nz) z[lane] = 0.0;
+        if (lane < nz) z[lane] = a.z0 ? a.z0[(size_t)s * AJ_NZ + (lane < ne ? lane : 6 + lane - ne)] : 0.0;
         __syncthreads();
         mF = aj_evaluate(sa, idx, z, bh, cs, F, slack, lane, nball);
         for (;;) {
@@ -532,7 +562,7 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
         const double cm = sa.cfac / sa.mass[m];
         const double wm = (m == 0 || m == ns - 1) ? 0.5 * sa.hn : sa.hn;
         const double d0 = du[m], d1 = du[K + m], d2 = du[2 * K + m];
-        const double u0 = sa.ubar[m] + d0, u1 = sa.ubar[K + m] + d1, u2 = sa.ubar[2 * K + m] + d2;
+        const double u0 = sa.ctr[m] + d0, u1 = sa.ctr[K + m] + d1, u2 = sa.ctr[2 * K + m] + d2;
         const double da0 = cm * d0, da1 = cm * d1, da2 = cm * d2;
         scost = scost + (wm * cm * cm) * (d0 * d0 + d1 * d1 + d2 * d2);
         sdv = sdv + wm * sqrt(da0 * da0 + da1 * da1 + da2 * da2);
@@ -546,12 +576,19 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
         so[MPCX_AJ_ONBALL] = nb; so[MPCX_AJ_ITERS] = (double)iters; so[MPCX_AJ_RESIDUAL] = mF;
         a.sat_status[s] = st;
     }
+    if (a.z_out && lane < nz) a.z_out[(size_t)s * AJ_NZ + (lane < ne ? lane : 6 + lane - ne)] = z[lane];
     // ---- per row: the displacement in the frame, g_m du_m summed over the nodes (lane 4 p + c: rows e_1, e_2, e_w of g, then a)
     double sum = 0.0;
     if (lane < 4 * r) {
         const int p = lane >> 2, c = lane & 3;
         const double *gp = c < 3 ? a.g + ((size_t)idx[p] * 9 + (size_t)c * 3) * K : a.a + (size_t)idx[p] * 3 * K;
-        for (int m = 0; m < ns; ++m) sum = sum + (gp[m] * du[m] + gp[K + m] * du[K + m] + gp[2 * K + m] * du[2 * K + m]);
+        if (a.uref) {                                                // from the linearisation's thrust: uref + du - U
+            const double *ul = a.U + (size_t)s * 3 * K;
+            for (int m = 0; m < ns; ++m)
+                sum = sum + (gp[m] * (du[m] - (ul[m] - sa.ctr[m])) + gp[K + m] * (du[K + m] - (ul[K + m] - sa.ctr[K + m]))
+                             + gp[2 * K + m] * (du[2 * K + m] - (ul[2 * K + m] - sa.ctr[2 * K + m])));
+        } else
+            for (int m = 0; m < ns; ++m) sum = sum + (gp[m] * du[m] + gp[K + m] * du[K + m] + gp[2 * K + m] * du[2 * K + m]);
     }
     const int p4 = (lane >> 2) << 2;
     const double dm1 = __shfl(sum, p4), dm2 = __shfl(sum, p4 + 1), along = __shfl(sum, p4 + 2), adu = __shfl(sum, p4 + 3);
@@ -564,6 +601,32 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
         ro[MPCX_AR_DIST] = sqrt(x1 * (W11 * x1 + W12 * dm2) + dm2 * (W12 * x1 + W22 * dm2));
         ro[MPCX_AR_LAMBDA] = z[ne + p] / a.target;
         ro[MPCX_AR_DT] = -along / in[AJI_WN];
+    }
+}
+
+// The refinement's terminal right-hand side (mpcx_avoidance_refine): the terminal sweep of the pass's linearisation into T -- the solve
+// that follows finds it there (T_ready) -- and trhs = sum_m T_m du_prev_m - (Y_t[0:6, ns-1] - Y0[0:6, ns-1]), the nodes in ascending
+// order: the end state is held to the GIVEN plan's.  One wave per satellite that is still refined (its node count was checked by the
+// rows of the first pass).
+__global__ __launch_bounds__(64) void ar_trhs_kernel(AjArgs a, const double *du_prev, const double *Y0, double *trhs)
+{
+    __shared__ double rec[AJ_REC_PAD], lam[48];
+    const int lane = threadIdx.x, s = blockIdx.x;
+    if (s >= a.S || (a.skip && a.skip[s])) return;
+    const size_t K = (size_t)a.K;
+    const int ns = a.row.Ks ? a.row.Ks[s] : a.K;
+    if (ns < 2 || ns > a.K) return;
+    double *Ts = a.T + (size_t)s * 18 * K;
+    for (int e = 0; e < 18; ++e)
+        for (int m = ns + lane; m < a.K; m += 64) Ts[(size_t)e * K + m] = 0.0;
+    const int lr = lane < 42 ? lane / 7 : 0, lc = lane < 42 ? lane - 7 * (lane / 7) : 0;
+    aj_sweep<6>(lane, a.stage + (size_t)s * (K - 1) * MPCX_STAGE_DOUBLES, ns - 2, lane < 42 && lr == lc ? 1.0 : 0.0, 0.0, Ts, K, rec, lam);
+    if (lane < 6) {
+        const double *tp = Ts + (size_t)lane * 3 * K, *dp = du_prev + (size_t)s * 3 * K;
+        double t = 0.0;
+        for (int m = 0; m < ns; ++m) t = t + (tp[m] * dp[m] + tp[K + m] * dp[K + m] + tp[2 * K + m] * dp[2 * K + m]);
+        const size_t e = ((size_t)s * 7 + lane) * K + (ns - 1);
+        trhs[(size_t)s * 6 + lane] = t - (a.row.Y[e] - Y0[e]);
     }
 }
 
@@ -635,7 +698,18 @@ static int aj_check(mpcx_ctx *ctx, const AjCall &c)
     return ctx_check_atmosphere(ctx, c.flags, "avoidance_joint");
 }
 
-static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream_t st)
+// what a pass of the refinement adds to the joint call (all NULL / 0 with solve = 1: the joint call)
+struct AjPass {
+    const double *uref = nullptr, *z0 = nullptr;
+    double *z_out = nullptr;
+    const int32_t *skip = nullptr;
+    double *trhs = nullptr;           // [S][6] buffer: filled by ar_trhs_kernel from du_prev and Y0, then the solve's right-hand side
+    const double *du_prev = nullptr, *Y0 = nullptr;
+    double *rhs_rows = nullptr, *rhs_term = nullptr;
+    int solve = 1;                    // 0: the rows alone (d0 of the last flight)
+};
+
+static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream_t st, const AjPass &x = AjPass())
 {
     const AjWorkspace ws(workspace, c.n, c.S, c.K);
     hipLaunchKernelGGL(aj_tf_kernel, dim3((unsigned)((c.S + 255) / 256)), dim3(256), 0, st, c.S, c.units, c.span, ws.tf);
@@ -656,6 +730,13 @@ static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream
     a.du = c.du; a.sat_out = c.sat_out; a.row_out = c.row_out; a.sat_status = c.sat_status; a.row_status = c.row_status;
     hipLaunchKernelGGL(aj_rows_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
+    if (!x.solve) return MPCX_OK;
+    a.uref = x.uref; a.z0 = x.z0; a.z_out = x.z_out; a.skip = x.skip; a.rhs_rows = x.rhs_rows; a.rhs_term = x.rhs_term;
+    if (x.trhs && a.hold) {
+        hipLaunchKernelGGL(ar_trhs_kernel, dim3((unsigned)c.S), dim3(64), 0, st, a, x.du_prev, x.Y0, x.trhs);
+        MPCX_HIP(ctx, hipGetLastError());
+        a.trhs = x.trhs; a.T_ready = 1;
+    }
     hipLaunchKernelGGL(aj_solve_kernel, dim3((unsigned)c.nsat), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
@@ -760,3 +841,307 @@ extern "C" int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, c
         }
     return MPCX_OK;
 }
+
+// ---- iterated avoidance: the manoeuvre flown, looked at and corrected again (include/mpcx.h: mpcx_avoidance_refine*)
+//   pass 0            the joint call as it is
+//   pass t >= 1       ar_apply_kernel   U_t = U + du_t-1 for a satellite that flies (rows and a finite du at pass 0), U otherwise
+//                     propagate         every satellite from its first node under U_t
+//                     ar_select_kernel  Y_t: the flight of a satellite that flies, the given trajectory otherwise; the end-state history;
+//                                       a failed flight freezes the satellite
+//                     the re-screen     mpcx_conjunction_pairs_traj_dev on Y_t: its out IS the pass's list
+//                     linearisation about (Y_t, U_t), aj_rows_kernel, ar_trhs_kernel, aj_solve_kernel (uref = U, z0 from the last solve)
+//                                       into trial arrays; ar_accept_kernel takes them over or freezes the satellite
+//   pass rounds + 1   the same without the solve: every answer is returned as flown
+// Everything is enqueued on one stream; the number of passes is fixed, nothing is read back in between.  One block per satellite or
+// one thread per element, no sum crosses a thread: the results depend on the inputs alone.
+namespace mpcx {
+
+__global__ __launch_bounds__(64) void ar_init_kernel(int S, int K, int n, const double *Y, const double *sat_out, const int32_t *sat_status,
+                                                     int32_t *flies, int32_t *skip, int32_t *rounds_done, double *y0, double *end_tau,
+                                                     double *hist_term, double *z, double *rhs_rows, double *rhs_term, int pass0)
+{
+    // pass0 = 1 (before the first solve): what the solve may leave unwritten; 0 (after it): who flies
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (pass0) {
+        if (e < S * AJ_NZ) z[e] = 0.0;
+        if (rhs_rows && e < n) rhs_rows[e] = cp_nan();
+        if (rhs_term && e < S * 6) rhs_term[e] = 0.0;
+        return;
+    }
+    if (e >= S) return;
+    const int f = sat_status[e] == MPCX_ST_OK && sat_out[(size_t)e * MPCX_NAJ + MPCX_AJ_ROWS] > 0.0;
+    flies[e] = f; skip[e] = !f; rounds_done[e] = f ? 0 : -1;
+    for (int c = 0; c < 7; ++c) y0[(size_t)e * 7 + c] = Y[((size_t)e * 7 + c) * K];
+    end_tau[e] = 1.0;
+    hist_term[e] = 0.0;
+}
+
+__global__ __launch_bounds__(256) void ar_hist_kernel(int n, const double *row_out, const double *pairs, double *hist_d0, double *hist_tca)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    hist_d0[p] = row_out[(size_t)p * MPCX_NAR + MPCX_AR_D0];
+    hist_tca[p] = pairs[(size_t)p * 4 + 3];
+}
+
+__global__ __launch_bounds__(256) void ar_apply_kernel(int S, int K, const double *U, const double *du, const int32_t *flies, double *Ut)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)S * 3 * K) return;
+    const int s = (int)(e / ((size_t)3 * K));
+    Ut[e] = flies[s] ? U[e] + du[e] : U[e];
+}
+
+__global__ __launch_bounds__(64) void ar_select_kernel(int S, int K, const int32_t *Ks, const double *Y, const double *Yp, const int32_t *pst,
+                                                       const int32_t *flies, int32_t *skip, int32_t *sat_status, double *Yt, double *hist_term)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    if (s >= S) return;
+    const int ns = Ks ? Ks[s] : K;
+    const bool flown = flies[s] && pst[s] == MPCX_ST_OK;
+    const size_t base = (size_t)s * 7 * K;
+    for (int e = lane; e < 7 * K; e += 64) {
+        const int m = e % K;
+        Yt[base + e] = flown ? (m < ns ? Yp[base + e] : 0.0) : Y[base + e];
+    }
+    if (lane == 0) {
+        double dev = 0.0;
+        if (flown)
+            for (int c = 0; c < 6; ++c) dev = fmax(dev, fabs(Yp[base + (size_t)c * K + (ns - 1)] - Y[base + (size_t)c * K + (ns - 1)]));
+        hist_term[s] = dev;
+        if (flies[s] && !flown && !skip[s]) { skip[s] = 1; sat_status[s] = pst[s]; }       // a failed flight: frozen, du stays
+    }
+}
+
+__global__ __launch_bounds__(64) void ar_accept_kernel(int n, int K, int t, const int32_t *owner, const double *du_try, const double *sat_try,
+                                                       const double *row_try, const int32_t *sat_st_try, const int32_t *row_st_try,
+                                                       int32_t *skip, double *du, double *sat_out, double *row_out, int32_t *sat_status,
+                                                       int32_t *row_status, int32_t *rounds_done)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    if (skip[s]) return;                                             // (wave-uniform; written below by lane 0 after everybody has read it)
+    const int st = sat_st_try[s];
+    __syncthreads();
+    if (st != MPCX_ST_OK) {                                          // a failed solve: frozen, du stays, the status is reported
+        if (lane == 0) { skip[s] = 1; sat_status[s] = st; }
+        return;
+    }
+    for (int e = lane; e < 3 * K; e += 64) du[(size_t)s * 3 * K + e] = du_try[(size_t)s * 3 * K + e];
+    if (lane < MPCX_NAJ) sat_out[(size_t)s * MPCX_NAJ + lane] = sat_try[(size_t)s * MPCX_NAJ + lane];
+    for (int p = lane; p < n; p += 64)
+        if (owner[p] == s) {
+            for (int c = 0; c < MPCX_NAR; ++c) row_out[(size_t)p * MPCX_NAR + c] = row_try[(size_t)p * MPCX_NAR + c];
+            row_status[p] = row_st_try[p];
+        }
+    if (lane == 0) { sat_status[s] = MPCX_ST_OK; rounds_done[s] = t; }
+}
+
+struct ArCall {
+    AjCall j;
+    int M;
+    double T0, T1, prop_max_step;
+    int rounds;
+    double *Y_out, *pairs_out, *hist_d0, *hist_tca, *hist_term;
+    int32_t *rounds_done;
+    double *rhs_rows, *rhs_term;
+};
+
+// [the joint call's workspace][the re-screen's][U_t S 3 K][flight S 7 K][y0 S 7][end_tau S][du S 3 K][sat_out S][row_out n][z S 14][trhs S 6]
+// [flight status, steps, trial status, flies, skip: S each][trial row status, re-screen status: n each][ephemeris status S, D]
+struct ArWorkspace {
+    void *aj, *scr;
+    double *Ut, *Yp, *y0, *end_tau, *du_try, *sat_try, *row_try, *z, *trhs;
+    int32_t *pst, *nsteps, *sat_st_try, *flies, *skip, *row_st_try, *scr_st, *eph_st, *cat_st;
+    size_t bytes;
+    ArWorkspace(void *base, int n, int S, int K, int D, int M)
+    {
+        char *p = (char *)base;
+        auto al = AjWorkspace::al;
+        aj = p; p += al(AjWorkspace(nullptr, n, S, K).bytes);
+        scr = p; p += al(mpcx_conjunction_pairs_workspace_bytes(S, D, M));
+        Ut = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
+        Yp = (double *)p; p += al((size_t)S * 7 * K * sizeof(double));
+        y0 = (double *)p; p += al((size_t)S * 7 * sizeof(double));
+        end_tau = (double *)p; p += al((size_t)S * sizeof(double));
+        du_try = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
+        sat_try = (double *)p; p += al((size_t)S * MPCX_NAJ * sizeof(double));
+        row_try = (double *)p; p += al((size_t)n * MPCX_NAR * sizeof(double));
+        z = (double *)p; p += al((size_t)S * AJ_NZ * sizeof(double));
+        trhs = (double *)p; p += al((size_t)S * 6 * sizeof(double));
+        int32_t **per_sat[] = {&pst, &nsteps, &sat_st_try, &flies, &skip, &eph_st};
+        for (int32_t **q : per_sat) { *q = (int32_t *)p; p += al((size_t)S * sizeof(int32_t)); }
+        row_st_try = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
+        scr_st = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
+        cat_st = (int32_t *)p; p += al((size_t)(D > 0 ? D : 1) * sizeof(int32_t));
+        bytes = (size_t)(p - (char *)base);
+    }
+};
+
+static int ar_check(mpcx_ctx *ctx, const ArCall &c)
+{
+    if (int rc = aj_check(ctx, c.j)) return rc;
+    if (c.rounds < 0) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: rounds must be >= 0");
+    if (c.M < 2 || !(c.T1 > c.T0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: the re-screen's grid needs M >= 2 and T1 > T0");
+    if (!(c.prop_max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: prop_max_step must be > 0");
+    if (!c.Y_out || !c.pairs_out || !c.hist_d0 || !c.hist_tca || !c.hist_term || !c.rounds_done)
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: Y_out, pairs_out, hist_d0, hist_tca, hist_term and rounds_done are required");
+    return MPCX_OK;
+}
+
+static int ar_enqueue(mpcx_ctx *ctx, const ArCall &c, void *workspace, hipStream_t st)
+{
+    const AjCall &j = c.j;
+    const int n = j.n, S = j.S, K = j.K, D = j.cat_Y ? j.D : 0;
+    const ArWorkspace ws(workspace, n, S, K, D, c.M);
+    const AjWorkspace aw(ws.aj, n, S, K);
+    const unsigned gS = (unsigned)((S + 63) / 64), gn = (unsigned)((n + 255) / 256);
+    const int most = S * AJ_NZ > n ? S * AJ_NZ : n;
+    hipLaunchKernelGGL(ar_init_kernel, dim3((unsigned)((most + 63) / 64)), dim3(64), 0, st, S, K, n, j.Y, j.sat_out, j.sat_status, ws.flies, ws.skip,
+                       c.rounds_done, ws.y0, ws.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 1);
+    MPCX_HIP(ctx, hipGetLastError());
+    // ---- pass 0: the joint call on what was given
+    AjPass first;
+    first.z_out = ws.z;
+    if (c.rounds == 0) { first.rhs_rows = c.rhs_rows; first.rhs_term = c.rhs_term; }
+    if (int rc = aj_enqueue(ctx, j, ws.aj, st, first)) return rc;
+    hipLaunchKernelGGL(ar_init_kernel, dim3(gS), dim3(64), 0, st, S, K, n, j.Y, j.sat_out, j.sat_status, ws.flies, ws.skip, c.rounds_done, ws.y0,
+                       ws.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 0);
+    MPCX_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(ar_hist_kernel, dim3(gn), dim3(256), 0, st, n, j.row_out, j.pairs, c.hist_d0, c.hist_tca);
+    MPCX_HIP(ctx, hipGetLastError());
+    for (int t = 1; t <= c.rounds + 1; ++t) {
+        const bool solve = t <= c.rounds;
+        const size_t total = (size_t)S * 3 * K;
+        hipLaunchKernelGGL(ar_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, K, j.U, j.du, ws.flies, ws.Ut);
+        MPCX_HIP(ctx, hipGetLastError());
+        if (int rc = mpcx_propagate_batch_ragged_dev(ctx, S, K, j.Ks, ws.y0, aw.tf, j.consts, j.flags, MPCX_CTRL_SEQUENCE, ws.Ut, K, j.Ks, ws.end_tau,
+                                                     c.prop_max_step, ws.Yp, ws.pst, ws.nsteps, st))
+            return rc;
+        hipLaunchKernelGGL(ar_select_kernel, dim3((unsigned)S), dim3(64), 0, st, S, K, j.Ks, j.Y, ws.Yp, ws.pst, ws.flies, ws.skip, j.sat_status,
+                           c.Y_out, c.hist_term + (size_t)t * S);
+        MPCX_HIP(ctx, hipGetLastError());
+        if (int rc = mpcx_conjunction_pairs_traj_dev(ctx, n, j.pairs, S, K, j.Ks, c.Y_out, j.units, j.span, D, D ? j.cat_K : 0, D ? j.cat_Ks : nullptr,
+                                                     D ? j.cat_Y : nullptr, D ? j.cat_units : nullptr, D ? j.cat_span : nullptr, c.M, c.T0, c.T1,
+                                                     c.pairs_out, ws.scr_st, ws.eph_st, D ? ws.cat_st : nullptr, ws.scr, st))
+            return rc;
+        AjCall q = j;
+        q.pairs = c.pairs_out; q.Y = c.Y_out; q.U = ws.Ut;
+        q.du = ws.du_try; q.sat_out = ws.sat_try; q.row_out = ws.row_try; q.sat_status = ws.sat_st_try; q.row_status = ws.row_st_try;
+        if (!solve) { q.rows = nullptr; q.tsens = nullptr; }
+        AjPass x;
+        x.solve = solve;
+        if (solve) {
+            x.uref = j.U; x.z0 = ws.z; x.z_out = ws.z; x.skip = ws.skip; x.trhs = ws.trhs; x.du_prev = j.du; x.Y0 = j.Y;
+            if (t == c.rounds) { x.rhs_rows = c.rhs_rows; x.rhs_term = c.rhs_term; }
+        }
+        if (int rc = aj_enqueue(ctx, q, ws.aj, st, x)) return rc;
+        hipLaunchKernelGGL(ar_hist_kernel, dim3(gn), dim3(256), 0, st, n, ws.row_try, c.pairs_out, c.hist_d0 + (size_t)t * n, c.hist_tca + (size_t)t * n);
+        MPCX_HIP(ctx, hipGetLastError());
+        if (solve) {
+            hipLaunchKernelGGL(ar_accept_kernel, dim3((unsigned)S), dim3(64), 0, st, n, K, t, aw.owner, ws.du_try, ws.sat_try, ws.row_try, ws.sat_st_try,
+                               ws.row_st_try, ws.skip, j.du, j.sat_out, j.row_out, j.sat_status, j.row_status, c.rounds_done);
+            MPCX_HIP(ctx, hipGetLastError());
+        }
+    }
+    return MPCX_OK;
+}
+
+}  // namespace mpcx
+
+extern "C" size_t mpcx_avoidance_refine_workspace_bytes(int n, int S, int K, int D, int M)
+{
+    if (n < 1 || S < 1 || K < 2 || D < 0 || M < 2) return 0;
+    return ArWorkspace(nullptr, n, S, K, D, M).bytes;
+}
+
+#define MPCX_AR_CALL                                                                                                                        \
+    ArCall{AjCall{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,     \
+                  cat_P, mu, target, u_max, hold_terminal, tol, max_iter, 0, S, du, sat_out, row_out, rows, tsens, sat_status, row_status},  \
+           M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, rhs_term}
+
+extern "C" int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                         const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                                         int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                                         const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
+                                         double target, const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0,
+                                         double T1, double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows,
+                                         double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out,
+                                         double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows,
+                                         double *rhs_term, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const ArCall c = MPCX_AR_CALL;
+    if (int rc = ar_check(ctx, c)) return rc;
+    if (!workspace)
+        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: a workspace of mpcx_avoidance_refine_workspace_bytes(n, S, K, D, M) bytes is required");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    return ar_enqueue(ctx, c, workspace, (hipStream_t)stream);
+}
+
+extern "C" int mpcx_avoidance_refine(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                     const double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                                     double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
+                                     const double *cat_units, const double *cat_span, const double *cat_P, double mu, double target,
+                                     const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double T1,
+                                     double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows, double *tsens,
+                                     int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0,
+                                     double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    const ArCall c = MPCX_AR_CALL;
+    if (int rc = ar_check(ctx, c)) return rc;
+    if (mover)
+        for (int r = 0; r < n; ++r)
+            if (mover[r] < 0 || mover[r] > 1 || (cat_Y && mover[r] != 0))
+                return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: mover is 0 (object i) or 1 (object j); against a catalogue only 0");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    ArCall d = c;
+    AjCall &j = d.j;
+    j.pairs = ar.upload(pairs, (size_t)n * 4);
+    j.mover = mover ? ar.upload(mover, (size_t)n) : nullptr;
+    j.Y = ar.upload(Y, (size_t)S * 7 * K); j.U = ar.upload(U, (size_t)S * 3 * K);
+    j.units = ar.upload(units, (size_t)S * 2); j.span = ar.upload(span, (size_t)S * 2); j.consts = ar.upload(consts, (size_t)S * MPCX_NCONST);
+    j.Ks = Ks ? ar.upload(Ks, S) : nullptr;
+    j.P = P ? ar.upload(P, (size_t)S * K * 36) : nullptr;
+    j.u_max = u_max ? ar.upload(u_max, (size_t)S) : nullptr;
+    if (cat_Y) {
+        j.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); j.cat_units = ar.upload(cat_units, (size_t)D * 2);
+        j.cat_span = ar.upload(cat_span, (size_t)D * 2);
+        j.cat_P = cat_P ? ar.upload(cat_P, (size_t)D * cat_K * 36) : nullptr;
+        j.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
+    }
+    const size_t np = (size_t)rounds + 2;
+    j.du = ar.alloc<double>((size_t)S * 3 * K);
+    j.sat_out = ar.alloc<double>((size_t)S * MPCX_NAJ);
+    j.row_out = ar.alloc<double>((size_t)n * MPCX_NAR);
+    j.rows = rows ? ar.alloc<double>((size_t)n * 3 * K) : nullptr;
+    j.tsens = tsens ? ar.alloc<double>((size_t)S * 18 * K) : nullptr;
+    j.sat_status = ar.alloc<int32_t>(S);
+    j.row_status = ar.alloc<int32_t>(n);
+    d.Y_out = ar.alloc<double>((size_t)S * 7 * K); d.pairs_out = ar.alloc<double>((size_t)n * 4);
+    d.hist_d0 = ar.alloc<double>(np * n); d.hist_tca = ar.alloc<double>(np * n); d.hist_term = ar.alloc<double>(np * S);
+    d.rounds_done = ar.alloc<int32_t>(S);
+    d.rhs_rows = rhs_rows ? ar.alloc<double>((size_t)n) : nullptr;
+    d.rhs_term = rhs_term ? ar.alloc<double>((size_t)S * 6) : nullptr;
+    const size_t wbytes = mpcx_avoidance_refine_workspace_bytes(n, S, K, cat_Y ? D : 0, M);
+    if (ar.failed()) return ar.code();
+    void *ws = ctx_workspace(ctx, wbytes);
+    if (!ws) return MPCX_E_NOMEM;
+    if (int rc = ar_enqueue(ctx, d, ws, ctx->stream)) return rc;
+    ar.download(du, j.du, (size_t)S * 3 * K);
+    ar.download(sat_out, j.sat_out, (size_t)S * MPCX_NAJ);
+    ar.download(row_out, j.row_out, (size_t)n * MPCX_NAR);
+    if (rows) ar.download(rows, j.rows, (size_t)n * 3 * K);
+    if (tsens) ar.download(tsens, j.tsens, (size_t)S * 18 * K);
+    ar.download(sat_status, j.sat_status, (size_t)S);
+    ar.download(row_status, j.row_status, (size_t)n);
+    ar.download(Y_out, d.Y_out, (size_t)S * 7 * K);
+    ar.download(pairs_out, d.pairs_out, (size_t)n * 4);
+    ar.download(hist_d0, d.hist_d0, np * n); ar.download(hist_tca, d.hist_tca, np * n); ar.download(hist_term, d.hist_term, np * S);
+    ar.download(rounds_done, d.rounds_done, (size_t)S);
+    if (rhs_rows) ar.download(rhs_rows, d.rhs_rows, (size_t)n);
+    if (rhs_term) ar.download(rhs_term, d.rhs_term, (size_t)S * 6);
+    return ar.finish();
+}
+#undef MPCX_AR_CALL
