@@ -484,13 +484,18 @@ def collision_probability(pairs, radius, Y, units, span, P, ns=None, cat=None, m
     return CollisionResult(pairs, out["out"], out["status"])
 
 
+def _side_args(Y, units, span, ns, P):
+    """one side of a pairs list as the library takes it: (count, row length, ns, Y, units, span, P); Y None: the side is absent"""
+    if Y is None:
+        return (0, 0, None, None, None, None, None)
+    return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr_opt(P))
+
+
 def _collision_call(pairs, *, device, slot, out, rows, cols, mu):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
     def side(sd):
-        if sd is None:
-            return (0, 0, None, None, None, None, None, None)
-        Y, units, span, P, radius, ns = sd
-        return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(P), _ffi.dptr(radius))
+        Y, units, span, P, radius, ns = sd if sd is not None else (None,) * 6
+        return _side_args(Y, units, span, ns, P) + (_ffi.dptr_opt(radius),)
     pairs = _ffi.as_f64(pairs)
     _ffi.call("mpcx_collision_probability", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
               _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
@@ -563,19 +568,9 @@ def _check_cat(cat):
     return Y, units, span, ns, P
 
 
-def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", include_drag=False, include_J2=False,
-              atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None, return_sensitivities=False, device=0, devices=None):
-    """The least-effort thrust change that opens every listed close approach to `target` -> AvoidanceResult.  pairs: (n, 4) rows
-    (i, j, distance, time in s) as screen and screen_against list them, or their ConjunctionResult; Y (S, 7, n), U (S, 3, n), units,
-    span, consts (S, 8) [, ns] the plan that was screened, linearised under include_drag / include_J2 / atmosphere as covariance
-    does.  P (S, n, 6, 6) (covariance): target is a Mahalanobis distance in the combined encounter-plane covariance; None: target is
-    a miss distance in metres.  cat = (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]): j indexes this catalogue and only the
-    satellite moves (cat_P exactly when P is given); None: j indexes the constellation and who = "i", "j" or "both" says which of the
-    two moves.  The device sweeps the adjoint of the encounter-plane miss backwards over the linearisation's A, B_kn, B_kp to the
-    derivative with respect to every thrust node (return_sensitivities=True returns them), and moves the miss in the direction that
-    gains distance fastest per unit of effort -- the first-order optimum, not the optimum over the whole target ellipse
-    (include/mpcx.h).  A pair already at or beyond the target gets du = 0.  An empty list returns empty arrays without a library
-    call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
+def _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu):
+    """the checks every avoidance call makes of the list, the target, the plan, the covariances, the catalogue and the model
+    -> (pairs, Y, U, units, span, consts, ns, P, cols, mu)"""
     from .constants import MU_EARTH
     if isinstance(pairs, ConjunctionResult):
         pairs = pairs.pairs
@@ -584,8 +579,6 @@ def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=Non
         raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
     if not (np.ndim(target) == 0 and np.isfinite(target) and target > 0.0):
         raise ValueError(f"target: need a positive finite distance, got {target}")
-    if who not in _WHO:
-        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
     Y, units, span, ns = _check_trajectories(Y, units, span, ns)
     S, _, K = Y.shape
     if K < 2:
@@ -602,8 +595,6 @@ def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=Non
     cols = None
     if cat is not None:
         cols = _check_cat(cat)
-        if who != "i":
-            raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
         if (P is None) != (cols[4] is None):
             raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
     if not max_step > 0.0:
@@ -611,7 +602,28 @@ def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=Non
     mu = float(MU_EARTH if mu is None else mu)
     if not mu > 0.0:
         raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
-    n, NS = pairs.shape[0], 1 if cols is not None else 2
+    return pairs, Y, U, units, span, consts, ns, P, cols, mu
+
+
+def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", include_drag=False, include_J2=False,
+              atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None, return_sensitivities=False, device=0, devices=None):
+    """The least-effort thrust change that opens every listed close approach to `target` -> AvoidanceResult.  pairs: (n, 4) rows
+    (i, j, distance, time in s) as screen and screen_against list them, or their ConjunctionResult; Y (S, 7, n), U (S, 3, n), units,
+    span, consts (S, 8) [, ns] the plan that was screened, linearised under include_drag / include_J2 / atmosphere as covariance
+    does.  P (S, n, 6, 6) (covariance): target is a Mahalanobis distance in the combined encounter-plane covariance; None: target is
+    a miss distance in metres.  cat = (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]): j indexes this catalogue and only the
+    satellite moves (cat_P exactly when P is given); None: j indexes the constellation and who = "i", "j" or "both" says which of the
+    two moves.  The device sweeps the adjoint of the encounter-plane miss backwards over the linearisation's A, B_kn, B_kp to the
+    derivative with respect to every thrust node (return_sensitivities=True returns them), and moves the miss in the direction that
+    gains distance fastest per unit of effort -- the first-order optimum, not the optimum over the whole target ellipse
+    (include/mpcx.h).  A pair already at or beyond the target gets du = 0.  An empty list returns empty arrays without a library
+    call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
+    if who not in _WHO:
+        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
+    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu)
+    if cols is not None and who != "i":
+        raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
+    n, K, NS = pairs.shape[0], Y.shape[2], 1 if cols is not None else 2
     out = dict(out=np.empty((n, _ffi.NAV)), du=_ffi.result_pool.take((n, NS, 3, K)),
                sens=_ffi.result_pool.take((n, NS, 3, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
     if n:
@@ -630,10 +642,7 @@ def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=Non
 def _avoidance_call(pairs, *, device, slot, out, rows, cols, mu, target, who, flags, max_step, atmosphere):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
     Y, U, units, span, consts, ns, P = rows
-    col = (0, 0, None, None, None, None, None)
-    if cols is not None:
-        cY, cunits, cspan, cns, cP = cols
-        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    col = _side_args(*(cols if cols is not None else (None,) * 5))
     pairs = _ffi.as_f64(pairs)
     ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
     _ffi.call("mpcx_avoidance", ctx, len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
@@ -705,50 +714,27 @@ def _coupled(pairs, mover, against_catalogue):
 
 def _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, tol, max_iter, max_step, mu):
     """the checks avoidance_joint and avoidance_refine share -> (pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu)"""
-    from .constants import MU_EARTH
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
-    if not (np.ndim(target) == 0 and np.isfinite(target) and target > 0.0):
-        raise ValueError(f"target: need a positive finite distance, got {target}")
     if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
         raise ValueError(f"tol: need a positive finite number, got {tol}")
     if not (np.ndim(max_iter) == 0 and int(max_iter) == max_iter and max_iter >= 1):
         raise ValueError(f"max_iter: need an integer >= 1, got {max_iter}")
-    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
-    S, _, K = Y.shape
-    if K < 2:
-        raise ValueError(f"Y: need at least 2 nodes, got {Y.shape}")
-    U, consts = _ffi.as_f64(U), _ffi.as_f64(consts)
-    if U.shape != (S, 3, K):
-        raise ValueError(f"U: expected ({S}, 3, {K}) thrust at the nodes, got {U.shape}")
-    if consts.shape != (S, _ffi.NCONST):
-        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
-    if P is not None:
-        P = _ffi.as_f64(P)
-        if P.shape != (S, K, 6, 6):
-            raise ValueError(f"P: expected ({S}, {K}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
-    cols = None
-    if cat is not None:
-        cols = _check_cat(cat)
-        if (P is None) != (cols[4] is None):
-            raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
-    n = pairs.shape[0]
-    mover = _check_mover(who, n, cols is not None)
+    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu)
+    mover = _check_mover(who, pairs.shape[0], cols is not None)
     if u_max is not None:
+        S = Y.shape[0]
         if np.ndim(u_max) not in (0, 1) or (np.ndim(u_max) == 1 and np.shape(u_max) != (S,)):
             raise ValueError(f"u_max: expected a scalar or ({S},) normalised thrust limits, got {np.shape(u_max)}")
         u_max = _ffi.per_sat(u_max, S)
         if not (u_max > 0.0).all():
             raise ValueError("u_max: need positive limits (inf: no ball)")
-    if not max_step > 0.0:
-        raise ValueError(f"max_step: need > 0, got {max_step}")
-    mu = float(MU_EARTH if mu is None else mu)
-    if not mu > 0.0:
-        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
     return pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu
+
+
+def _joint_arrays(S, K, n, return_rows, return_terminal):
+    """the result arrays of the joint call: what the library writes for every satellite and every row of the list"""
+    return dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
+                rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
+                sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32))
 
 
 def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", u_max=None, hold_terminal=True,
@@ -767,9 +753,7 @@ def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, c
     pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
                                                                                      u_max, tol, max_iter, max_step, mu)
     (S, _, K), n = Y.shape, pairs.shape[0]
-    out = dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
-               rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
-               sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32))
+    out = _joint_arrays(S, K, n, return_rows, return_terminal)
     if n:
         how = dict(pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols, mu=mu, target=float(target),
                    hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter), flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
@@ -791,10 +775,7 @@ def _avoidance_joint_call(index, *, device, slot, out, pairs, mover, rows, cols,
     """the block of satellites index[0] .. index[-1] on context (device, slot): the library writes the block's satellites and the
     rows they own into the whole result set `whole`, and nothing else of it"""
     Y, U, units, span, consts, ns, P, u_max = rows
-    col = (0, 0, None, None, None, None, None)
-    if cols is not None:
-        cY, cunits, cspan, cns, cP = cols
-        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    col = _side_args(*(cols if cols is not None else (None,) * 5))
     ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
     _ffi.call("mpcx_avoidance_joint", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
               _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
@@ -847,11 +828,8 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
     rounds = int(rounds)
-    out = dict(du=np.zeros((S, 3, K)), sat_out=np.zeros((S, _ffi.NAJ)), row_out=np.zeros((n, _ffi.NAR)),
-               rows=np.zeros((n, 3, K)) if return_rows else None, tsens=np.zeros((S, 6, 3, K)) if return_terminal else None,
-               sat_status=np.zeros(S, dtype=np.int32), row_status=np.zeros(n, dtype=np.int32),
-               Y_flown=Y.copy(), pairs_flown=pairs.copy(), d0=np.zeros((rounds + 2, n)), tca=np.zeros((rounds + 2, n)),
-               term=np.zeros((rounds + 2, S)), rounds_done=np.full(S, -1, dtype=np.int32),
+    out = dict(_joint_arrays(S, K, n, return_rows, return_terminal), Y_flown=Y.copy(), pairs_flown=pairs.copy(),
+               d0=np.zeros((rounds + 2, n)), tca=np.zeros((rounds + 2, n)), term=np.zeros((rounds + 2, S)), rounds_done=np.full(S, -1, dtype=np.int32),
                rhs_rows=np.zeros(n) if return_rhs else None, rhs_term=np.zeros((S, 6)) if return_rhs else None)
     if n:
         _avoidance_refine_call(device=device, slot=0, out=out, pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols,
@@ -868,10 +846,7 @@ def _avoidance_refine_call(*, device, slot, out, pairs, mover, rows, cols, mu, t
                            prop_max_step, rounds):
     """the whole list and all satellites on context (device, slot), into `out`"""
     Y, U, units, span, consts, ns, P, u_max = rows
-    col = (0, 0, None, None, None, None, None)
-    if cols is not None:
-        cY, cunits, cspan, cns, cP = cols
-        col = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), _ffi.dptr(cY), _ffi.dptr(cunits), _ffi.dptr(cspan), _ffi.dptr_opt(cP))
+    col = _side_args(*(cols if cols is not None else (None,) * 5))
     ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
     _ffi.call("mpcx_avoidance_refine", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
               _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,

@@ -8,18 +8,12 @@
 // doubles of its record) is fetched by the half in one pass of three loads per lane, the next node's before the arithmetic of this
 // one.  Everything else is wave-uniform setup or a lane-strided pass over the nodes closed by an xor butterfly: the operation order
 // is fixed (tests/avoidance_reference.py restates it), nothing depends on the launch.  LDS: two records and two lam, whatever K.
+// The frame, the encounter-plane covariance, the movers' setup, the sweep's seeds and its node step are collision_device.hpp's, where
+// collision.hip and avoidance_joint.hip take them from too; this file keeps the sweep's two-half-wave loop and the manoeuvre.
 #include "collision_device.hpp"
+#include "encounter_host.hpp"
 
 namespace mpcx {
-
-__global__ __launch_bounds__(256) void avoidance_tf_kernel(int S, const double *units, const double *span, double *tf)
-{
-    // covariance_tf_kernel's rule (collision.hip): no positive finite tf, no linearisation -- tf = 1 and MPCX_ST_BADK in the sweep
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= S) return;
-    const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
-    tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
-}
 
 struct AvArgs {
     int n, K, NS, who;                // K: the constellation's row length (stage records, du, sens); NS: slots of du and sens per pair
@@ -34,45 +28,25 @@ struct AvArgs {
     int32_t *status;
 };
 
-enum { AV_REC = 91, AV_REC_PAD = 96, AV_LAM = 21, AV_LAM_PAD = 24 };
+enum { AV_LAM = 21, AV_LAM_PAD = 24 };
 
-__device__ __forceinline__ double av_wave_sum(double x)
-{
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) x = x + __shfl_xor(x, sh);
-    return x;
-}
-__device__ __forceinline__ double av_wave_max(double x)
-{
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) x = fmax(x, __shfl_xor(x, sh));
-    return x;
-}
-
-// what the passes over the nodes need of one manoeuvring object (wave-uniform)
-struct AvMover {
-    int slot, k, nn;
-    double hn, cfac;                  // node spacing in s; (L / Tu^2): c_m = cfac / mass_m
-    const double *mass;               // Y[o][6][.]
-};
-
-// effort-scaled encounter-plane rows of node m, its trapezoid weight and c_m; also the raw e_w row
-__device__ __forceinline__ void av_node(const AvMover &mv, const double *g, size_t K, int m, double (&gh)[2][3], double (&gw)[3], double &wm,
-                                        double &cm)
+// effort-scaled encounter-plane rows of node m of the mover in slot `slot`, its trapezoid weight and c_m; also the raw e_w row
+__device__ __forceinline__ void av_node(const CpMover &mv, int slot, const double *g, size_t K, int m, double (&gh)[2][3], double (&gw)[3],
+                                        double &wm, double &cm)
 {
     cm = mv.cfac / mv.mass[m];
     wm = (m == 0 || m == mv.nn - 1) ? 0.5 * mv.hn : mv.hn;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        gh[0][c] = g[((size_t)mv.slot * 9 + c) * K + m] / cm;
-        gh[1][c] = g[((size_t)mv.slot * 9 + 3 + c) * K + m] / cm;
-        gw[c] = g[((size_t)mv.slot * 9 + 6 + c) * K + m];
+        gh[0][c] = g[((size_t)slot * 9 + c) * K + m] / cm;
+        gh[1][c] = g[((size_t)slot * 9 + 3 + c) * K + m] / cm;
+        gw[c] = g[((size_t)slot * 9 + 6 + c) * K + m];
     }
 }
 
 __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
 {
-    __shared__ double rec[2][AV_REC_PAD], lam[2][AV_LAM_PAD];
+    __shared__ double rec[2][CP_REC_PAD], lam[2][AV_LAM_PAD];
     const int pr = blockIdx.x, lane = threadIdx.x, h = lane >> 5, ll = lane & 31;
     if (pr >= a.n) return;
     const double *row = a.pairs + (size_t)pr * 4;
@@ -89,77 +63,29 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
     CpNode nda, ndb;
     int st = cp_state(a.row, row[0], t, pa, va, nda);
     if (st == MPCX_ST_OK) st = cp_state(a.col, row[1], t, pb, vb, ndb);
-    AvMover mv[2] = {};
-    double htau[2] = {0.0, 0.0}, Lm[2] = {0.0, 0.0};
+    CpMover mv[2] = {};
     if (st == MPCX_ST_OK) {
 #pragma unroll
         for (int sl = 0; sl < 2; ++sl) {
             if (!moves[sl] || st != MPCX_ST_OK) continue;
-            const CpNode &nd = sl ? ndb : nda;                       // (a manoeuvring object is one of the constellation: the row side)
-            const double L = a.row.units[2 * nd.o], Tu = a.row.units[2 * nd.o + 1];
-            const double tfv = (a.row.span[2 * nd.o + 1] - a.row.span[2 * nd.o]) / Tu;
-            if (!(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
-            else if (a.dstat[nd.o] != MPCX_ST_OK) st = a.dstat[nd.o];
-            mv[sl] = AvMover{sl, nd.k, nd.nn, nd.hn, L / (Tu * Tu), a.row.Y + ((size_t)nd.o * 7 + 6) * K};
-            htau[sl] = tfv / (double)(nd.nn - 1);
-            Lm[sl] = L;
+            st = cp_mover(a.row, a.dstat, sl ? ndb : nda, K, mv[sl]);
         }
     }
     double ew[3], e1[3], e2[3], mn = 0.0, wn = 0.0, W11 = 1.0, W12 = 0.0, W22 = 1.0;
     if (st == MPCX_ST_OK) {
-        // the frame of collision_probability_kernel, in its operation order
         double d[3], w[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { d[c] = pb[c] - pa[c]; w[c] = vb[c] - va[c]; }
-        wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-        if (!(wn > 0.0) || !cp_finite(wn)) st = MPCX_ST_NUMERIC;
-        else {
-            double m[3];
+        st = cp_frame(d, w, wn, ew, mn, e1, e2);
+        if (st == MPCX_ST_OK && a.have_P) {
+            double Ca[6], Cb[6], Cs[6];
+            CpPlane pl;
+            cp_covariance(a.row, nda, t, a.mu, Ca);
+            cp_covariance(a.col, ndb, t, a.mu, Cb);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) ew[c] = w[c] / wn;
-            const double dw = d[0] * ew[0] + d[1] * ew[1] + d[2] * ew[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) m[c] = d[c] - dw * ew[c];
-            mn = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-            if (mn > 0.0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = m[c] / mn;
-            } else {
-                int ax = 0;
-                double ea = ew[0];
-                if (fabs(ew[1]) < fabs(ea)) { ax = 1; ea = ew[1]; }
-                if (fabs(ew[2]) < fabs(ea)) { ax = 2; ea = ew[2]; }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = (c == ax ? 1.0 : 0.0) - ea * ew[c];
-                const double en = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = e1[c] / en;
-            }
-            e2[0] = ew[1] * e1[2] - ew[2] * e1[1];
-            e2[1] = ew[2] * e1[0] - ew[0] * e1[2];
-            e2[2] = ew[0] * e1[1] - ew[1] * e1[0];
-            if (a.have_P) {
-                double Ca[6], Cb[6], Cs[6], g1[3], g2[3];
-                cp_covariance(a.row, nda, t, a.mu, Ca);
-                cp_covariance(a.col, ndb, t, a.mu, Cb);
-#pragma unroll
-                for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
-                g1[0] = Cs[0] * e1[0] + Cs[1] * e1[1] + Cs[2] * e1[2];
-                g1[1] = Cs[1] * e1[0] + Cs[3] * e1[1] + Cs[4] * e1[2];
-                g1[2] = Cs[2] * e1[0] + Cs[4] * e1[1] + Cs[5] * e1[2];
-                g2[0] = Cs[0] * e2[0] + Cs[1] * e2[1] + Cs[2] * e2[2];
-                g2[1] = Cs[1] * e2[0] + Cs[3] * e2[1] + Cs[4] * e2[2];
-                g2[2] = Cs[2] * e2[0] + Cs[4] * e2[1] + Cs[5] * e2[2];
-                const double c11 = e1[0] * g1[0] + e1[1] * g1[1] + e1[2] * g1[2];
-                const double c12 = e1[0] * g2[0] + e1[1] * g2[1] + e1[2] * g2[2];
-                const double c22 = e2[0] * g2[0] + e2[1] * g2[1] + e2[2] * g2[2];
-                const double tr = c11 + c22, df = c11 - c22;
-                const double l1 = 0.5 * (tr + sqrt(df * df + 4.0 * c12 * c12));
-                const double det = c11 * c22 - c12 * c12;
-                const double l2 = det / l1;
-                if (!(l2 > 0.0) || !cp_finite(l2) || !cp_finite(l1)) st = MPCX_ST_NUMERIC;
-                else { W11 = c22 / det; W12 = -c12 / det; W22 = c11 / det; }      // W = C_2^-1
-            }
+            for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
+            st = cp_plane_covariance(Cs, e1, e2, pl);
+            if (st == MPCX_ST_OK) { W11 = pl.c22 / pl.det; W12 = -pl.c12 / pl.det; W22 = pl.c11 / pl.det; }      // W = C_2^-1
         }
     }
 
@@ -171,19 +97,11 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
         const double *srec = a.stage + (size_t)(h ? ndb.o : nda.o) * (K - 1) * MPCX_STAGE_DOUBLES;     // (read only where `mine`)
         const int lr = ll < AV_LAM ? ll / 7 : 0, lc = ll < AV_LAM ? ll - 7 * (ll / 7) : 0;             // entry of lam
         const int gr = ll < 9 ? ll / 3 : 0, gc = ll < 9 ? ll - 3 * (ll / 3) : 0;                       // entry of g_m
-        // R Lam of the two bracketing nodes, entry (lr, lc): sgn [e_1 e_2 e_w]^T L [hp I | h_tau hv I | 0]
-        double seed_hi = 0.0, seed_lo = 0.0;
+        double seed_hi = 0.0, seed_lo = 0.0;                         // R Lam of the two bracketing nodes, entry (lr, lc)
         {
-            const double sgn = h ? 1.0 : -1.0;
-            double Rv[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) Rv[x] = sgn * (lr == 0 ? e1[x] : (lr == 1 ? e2[x] : ew[x]));
-            const int cc = lc < 3 ? lc : lc - 3;
-            const double Rc = cc == 0 ? Rv[0] : (cc == 1 ? Rv[1] : Rv[2]);
-            const double L = h ? Lm[1] : Lm[0], ht = h ? htau[1] : htau[0];
-            const double h00 = h ? ndb.h00 : nda.h00, h10 = h ? ndb.h10 : nda.h10, h01 = h ? ndb.h01 : nda.h01, h11 = h ? ndb.h11 : nda.h11;
-            if (lc < 3) { seed_hi = (L * h01) * Rc; seed_lo = (L * h00) * Rc; }
-            else if (lc < 6) { seed_hi = (L * (ht * h11)) * Rc; seed_lo = (L * (ht * h10)) * Rc; }
+            const CpNode &nd = h ? ndb : nda;
+            cp_sweep_seed(h ? 1.0 : -1.0, e1, e2, ew, h ? mv[1].L : mv[0].L, h ? mv[1].htau : mv[0].htau, nd.h00, nd.h10, nd.h01, nd.h11, lr, lc,
+                          seed_hi, seed_lo);
         }
         if (a.zero_g) {                                              // nodes past k + 1, and the slot of an object that does not move
 #pragma unroll
@@ -199,41 +117,24 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
         if (mine && kmax <= kme) {
             const double *rp = srec + (size_t)kmax * MPCX_STAGE_DOUBLES;
             r0 = rp[ll]; r1 = rp[ll + 32];
-            if (ll + 64 < AV_REC) r2 = rp[ll + 64];
+            if (ll + 64 < CP_REC) r2 = rp[ll + 64];
         }
         double carry = 0.0;                                          // lam_q+2 B_kn[q+1], entry (gr, gc)
         for (int q = kmax; q >= 0; --q) {
             const bool act = mine && q <= kme;
             if (act) {
                 rec[h][ll] = r0; rec[h][ll + 32] = r1;
-                if (ll + 64 < AV_REC) rec[h][ll + 64] = r2;
+                if (ll + 64 < CP_REC) rec[h][ll + 64] = r2;
             }
             __syncthreads();
             if (mine && q >= 1 && q - 1 <= kme) {                    // the next node's record, ahead of this node's arithmetic
                 const double *rp = srec + (size_t)(q - 1) * MPCX_STAGE_DOUBLES;
                 r0 = rp[ll]; r1 = rp[ll + 32];
-                if (ll + 64 < AV_REC) r2 = rp[ll + 64];
+                if (ll + 64 < CP_REC) r2 = rp[ll + 64];
             }
             double lnew = 0.0;
-            if (act) {
-                const double *lm = lam[h], *rc = rec[h];
-                if (ll < 9) {
-                    double gn = lm[gr * 7] * rc[49 + gc], gp = lm[gr * 7] * rc[70 + gc];
-#pragma unroll
-                    for (int x = 1; x < 7; ++x) {
-                        gn = gn + lm[gr * 7 + x] * rc[49 + x * 3 + gc];
-                        gp = gp + lm[gr * 7 + x] * rc[70 + x * 3 + gc];
-                    }
-                    g[((size_t)h * 9 + ll) * K + q + 1] = q == kme ? gp : carry + gp;          // g_q+1 = lam_q+2 B_kn[q+1] + lam_q+1 B_kp[q]
-                    carry = gn;
-                }
-                if (ll < AV_LAM) {
-                    lnew = lm[lr * 7] * rc[lc];
-#pragma unroll
-                    for (int x = 1; x < 7; ++x) lnew = lnew + lm[lr * 7 + x] * rc[x * 7 + lc];
-                    if (q == kme) lnew = lnew + seed_lo;
-                }
-            }
+            if (act)
+                lnew = cp_sweep_node(lam[h], rec[h], q == kme, ll < 9, gr, gc, g + ((size_t)h * 9 + ll) * K + q + 1, carry, ll < AV_LAM, lr, lc, seed_lo);
             __syncthreads();
             if (act && ll < AV_LAM) lam[h][ll] = lnew;               // lam_q
         }
@@ -248,12 +149,12 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
             double s11 = 0.0, s12 = 0.0, s22 = 0.0;
             for (int m = lane; m <= mv[sl].k + 1; m += 64) {
                 double gh[2][3], gw[3], wm, cm;
-                av_node(mv[sl], g, K, m, gh, gw, wm, cm);
+                av_node(mv[sl], sl, g, K, m, gh, gw, wm, cm);
                 s11 = s11 + (gh[0][0] * gh[0][0] + gh[0][1] * gh[0][1] + gh[0][2] * gh[0][2]) / wm;
                 s12 = s12 + (gh[0][0] * gh[1][0] + gh[0][1] * gh[1][1] + gh[0][2] * gh[1][2]) / wm;
                 s22 = s22 + (gh[1][0] * gh[1][0] + gh[1][1] * gh[1][1] + gh[1][2] * gh[1][2]) / wm;
             }
-            M11 = M11 + av_wave_sum(s11); M12 = M12 + av_wave_sum(s12); M22 = M22 + av_wave_sum(s22);
+            M11 = M11 + cp_wave_sum(s11); M12 = M12 + cp_wave_sum(s12); M22 = M22 + cp_wave_sum(s22);
         }
         const double detM = M11 * M22 - M12 * M12;
         if (!(detM > 0.0) || !cp_finite(detM) || !cp_finite(M11) || !cp_finite(M22)) st = MPCX_ST_SINGULAR;
@@ -281,7 +182,7 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
                 double sdv = 0.0, sum = 0.0, sal = 0.0;
                 for (int m = lane; m <= mv[sl].k + 1; m += 64) {
                     double gh[2][3], gw[3], wm, cm, da[3], dn[3];
-                    av_node(mv[sl], g, K, m, gh, gw, wm, cm);
+                    av_node(mv[sl], sl, g, K, m, gh, gw, wm, cm);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         da[c] = (gh[0][c] * l1 + gh[1][c] * l2) / wm;
@@ -292,8 +193,8 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
                     sum = fmax(sum, sqrt(dn[0] * dn[0] + dn[1] * dn[1] + dn[2] * dn[2]));
                     sal = sal + (gw[0] * dn[0] + gw[1] * dn[1] + gw[2] * dn[2]);
                 }
-                dv[sl] = av_wave_sum(sdv); um[sl] = av_wave_max(sum);
-                along = along + av_wave_sum(sal);
+                dv[sl] = cp_wave_sum(sdv); um[sl] = cp_wave_max(sum);
+                along = along + cp_wave_sum(sal);
             }
             const double x1 = mn + dm1;
             o[MPCX_AV_D0] = d0;
@@ -317,36 +218,20 @@ __global__ __launch_bounds__(64) void avoidance_kernel(AvArgs a)
     }
 }
 
-// workspace of the _dev call: [stage S (K-1) records][tf S][discretiser status S][g n 2 3 3 K]
-struct AvWorkspace {
-    double *stage, *tf, *g;
-    int32_t *dstat;
+// workspace of the _dev call: [the linearisation's][g n 2 3 3 K]
+struct AvWorkspace : LinWorkspace {
+    double *g;
     size_t bytes;
-    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
     AvWorkspace(void *base, int n, int S, int K)
     {
-        char *p = (char *)base;
-        stage = (double *)p; p += al((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES * sizeof(double));
-        tf = (double *)p; p += al((size_t)S * sizeof(double));
-        dstat = (int32_t *)p; p += al((size_t)S * sizeof(int32_t));
-        g = (double *)p; p += al((size_t)n * 2 * 9 * K * sizeof(double));
-        bytes = (size_t)(p - (char *)base);
+        Carver c(base);
+        carve(c, S, K);
+        g = c.take<double>((size_t)n * 2 * 9 * K);
+        bytes = c.bytes();
     }
 };
 
-struct AvCall {
-    int n;
-    const double *pairs;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *U, *units, *span, *consts;
-    int flags;
-    double max_step;
-    const double *P;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P;
-    double mu, target;
+struct AvCall : EncProblem {
     int who;
     double *out, *du, *sens;
     int32_t *status;
@@ -354,32 +239,16 @@ struct AvCall {
 
 static int av_check(mpcx_ctx *ctx, const AvCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: need n>=1, S>=1, K>=2, mu>0");
-    if (!(c.target > 0.0) || !(c.target < __builtin_inf())) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: target must be a positive finite number");
-    if (c.who < 0 || c.who > 2) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: who is 0 (object i), 1 (object j) or 2 (both)");
-    if (!(c.max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: max_step must be > 0");
-    if (c.flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
-    if (!c.pairs || !c.Y || !c.U || !c.units || !c.span || !c.consts || !c.out || !c.du || !c.status)
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: pairs, Y, U, units, span, consts, out, du and status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: cat_units and cat_span are required with cat_Y");
-        if (c.who != 0) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: only the row object can manoeuvre against a catalogue (who = 0)");
-        if ((c.P != nullptr) != (c.cat_P != nullptr))
-            return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: P and cat_P come together (a Mahalanobis target) or not at all (metres)");
-    }
-    return ctx_check_atmosphere(ctx, c.flags, "avoidance");
+    if (int rc = enc_check(ctx, c, "avoidance", c.out && c.du && c.status, "out, du and status")) return rc;
+    if (c.who < 0 || c.who > 2) return enc_fail(ctx, "avoidance", "who is 0 (object i), 1 (object j) or 2 (both)");
+    if (c.cat_Y && c.who != 0) return enc_fail(ctx, "avoidance", "only the row object can manoeuvre against a catalogue (who = 0)");
+    return MPCX_OK;
 }
 
 static int av_enqueue(mpcx_ctx *ctx, const AvCall &c, void *workspace, hipStream_t st)
 {
     const AvWorkspace ws(workspace, c.n, c.S, c.K);
-    hipLaunchKernelGGL(avoidance_tf_kernel, dim3((unsigned)((c.S + 255) / 256)), dim3(256), 0, st, c.S, c.units, c.span, ws.tf);
-    MPCX_HIP(ctx, hipGetLastError());
-    if (int rc = mpcx_discretize_stages_ragged_dev(ctx, c.S, c.K, c.Ks, c.K, c.Ks, c.Y, c.U, ws.tf, c.consts, c.flags, c.max_step, ws.stage,
-                                                   ws.dstat, st))
-        return rc;
+    if (int rc = enc_linearise(ctx, c, ws, st)) return rc;
     const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, nullptr};
     const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, nullptr} : row;
     const AvArgs a{c.n, c.K, c.cat_Y ? 1 : 2, c.who, c.pairs, row, col, c.P != nullptr, ws.stage, ws.dstat, c.mu, c.target,
@@ -406,8 +275,8 @@ extern "C" int mpcx_avoidance_dev(mpcx_ctx *ctx, int n, const double *pairs, int
                                   double *sens, int32_t *status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AvCall c{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                   mu, target, who, out, du, sens, status};
+    const AvCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
+                    mu, target}, who, out, du, sens, status};
     if (int rc = av_check(ctx, c)) return rc;
     if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: a workspace of mpcx_avoidance_workspace_bytes(n, S, K) bytes is required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
@@ -421,24 +290,14 @@ extern "C" int mpcx_avoidance(mpcx_ctx *ctx, int n, const double *pairs, int S, 
                               int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AvCall c{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                   mu, target, who, out, du, sens, status};
+    const AvCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
+                    mu, target}, who, out, du, sens, status};
     if (int rc = av_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     AvCall d = c;
     const size_t NS = cat_Y ? 1 : 2;
-    d.pairs = ar.upload(pairs, (size_t)n * 4);
-    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.U = ar.upload(U, (size_t)S * 3 * K);
-    d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2); d.consts = ar.upload(consts, (size_t)S * MPCX_NCONST);
-    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    d.P = P ? ar.upload(P, (size_t)S * K * 36) : nullptr;
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        d.cat_span = ar.upload(cat_span, (size_t)D * 2);
-        d.cat_P = cat_P ? ar.upload(cat_P, (size_t)D * cat_K * 36) : nullptr;
-        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
+    enc_upload(ar, d);
     d.out = ar.alloc<double>((size_t)n * MPCX_NAV);
     d.du = ar.alloc<double>((size_t)n * NS * 3 * K);
     d.sens = sens ? ar.alloc<double>((size_t)n * NS * 9 * K) : nullptr;

@@ -1,7 +1,8 @@
 // avoidance_joint.hip -- all of a satellite's encounters under its thrust limit (include/mpcx.h: mpcx_avoidance_joint*).
 //   aj_rows_kernel    one wave per listed pair: the encounter frame, the adjoint sweep over A | B_kn | B_kp and the g_m of the ONE object
-//                     that moves -- avoidance_kernel's code (avoidance.hip) restated expression for expression, so that with W = I the
-//                     row has the bits of mpcx_avoidance's sens -- contracted to the tangent half-plane row a_p and its right-hand side.
+//                     that moves -- the functions of collision_device.hpp that avoidance_kernel (avoidance.hip) calls too, so that with
+//                     W = I the row has the bits of mpcx_avoidance's sens -- contracted to the tangent half-plane row a_p and its
+//                     right-hand side.
 //   aj_solve_kernel   one wave per satellite that has rows: its row indices in ascending list order, the terminal sweep (the same
 //                     recursion with six rows, seeded [I_6 | 0] at the last node), and the strictly convex problem by the semismooth
 //                     Newton iteration of the header: a lane-strided pass over the nodes for du(z) and the projection's Jacobian, one
@@ -11,24 +12,16 @@
 // At the end of the file: mpcx_avoidance_refine*, the loop around the joint call (fly, re-screen, linearise, solve again), which gives
 // aj_solve_kernel a reference thrust, a terminal right-hand side and a warm start -- all absent in the joint call itself.
 #include "collision_device.hpp"
+#include "encounter_host.hpp"
 
 #include <string.h>
 #include <vector>
 
 namespace mpcx {
 
-enum { AJ_REC = 91, AJ_REC_PAD = 96, AJ_MAXR = MPCX_AJ_MAX_ROWS, AJ_NZ = 6 + MPCX_AJ_MAX_ROWS, AJ_LINE_SEARCH = 30 };
+enum { AJ_MAXR = MPCX_AJ_MAX_ROWS, AJ_NZ = 6 + MPCX_AJ_MAX_ROWS, AJ_LINE_SEARCH = 30 };
 enum { AJI_D0 = 0, AJI_B, AJI_Q1, AJI_Q2, AJI_MN, AJI_WN, AJI_W11, AJI_W12, AJI_W22, AJ_INFO = 10 };      // per-pair record of the workspace
 #define AJ_PIVOT_REL 1e-12
-
-__global__ __launch_bounds__(256) void aj_tf_kernel(int S, const double *units, const double *span, double *tf)
-{
-    // covariance_tf_kernel's rule (collision.hip): no positive finite tf, no linearisation -- tf = 1 and MPCX_ST_BADK in the rows
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= S) return;
-    const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
-    tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
-}
 
 struct AjArgs {
     int n, S, K, sat0, nsat, have_cat, have_P, hold, max_iter;
@@ -60,74 +53,9 @@ struct AjArgs {
     double *rhs_term = nullptr;       // [S][6]: the terminal rows'
 };
 
-__device__ __forceinline__ double aj_wave_sum(double x)
-{
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) x = x + __shfl_xor(x, sh);
-    return x;
-}
-__device__ __forceinline__ double aj_wave_max(double x)
-{
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) x = fmax(x, __shfl_xor(x, sh));
-    return x;
-}
-
-// The adjoint sweep of avoidance_kernel for NR rows, run by one wave: lam_kme+1 = seed_hi, lam_kme = lam_kme+1 A_kme + seed_lo,
-// lam_q = lam_q+1 A_q; g_q+1 = lam_q+2 B_kn[q+1] + lam_q+1 B_kp[q], g_0 = lam_1 B_kn[0], written to g[(row * 3 + component) * K + node]
-// for the nodes 0 .. kme + 1.  Lane e < 7 NR owns entry e of lam, lane e < 3 NR entry e of g_m; a node's record is fetched one node
-// ahead of its arithmetic.  Called by the whole wave; ends with a barrier (g is read back by other lanes).
-template <int NR>
-__device__ __forceinline__ void aj_sweep(int lane, const double *srec, int kme, double seed_hi, double seed_lo, double *g, size_t K,
-                                         double *rec, double *lam)
-{
-    constexpr int NL = NR * 7, NG = NR * 3;
-    const int lr = lane < NL ? lane / 7 : 0, lc = lane < NL ? lane - 7 * (lane / 7) : 0;
-    const int gr = lane < NG ? lane / 3 : 0, gc = lane < NG ? lane - 3 * (lane / 3) : 0;
-    if (lane < NL) lam[lane] = seed_hi;
-    double r0 = 0.0, r1 = 0.0;                                       // the record in flight: entries lane, lane + 64 (< 91)
-    {
-        const double *rp = srec + (size_t)kme * MPCX_STAGE_DOUBLES;
-        r0 = rp[lane];
-        if (lane + 64 < AJ_REC) r1 = rp[lane + 64];
-    }
-    double carry = 0.0;                                              // lam_q+2 B_kn[q+1], entry (gr, gc)
-    for (int q = kme; q >= 0; --q) {
-        rec[lane] = r0;
-        if (lane + 64 < AJ_REC) rec[lane + 64] = r1;
-        __syncthreads();
-        if (q >= 1) {                                                // the next node's record, ahead of this node's arithmetic
-            const double *rp = srec + (size_t)(q - 1) * MPCX_STAGE_DOUBLES;
-            r0 = rp[lane];
-            if (lane + 64 < AJ_REC) r1 = rp[lane + 64];
-        }
-        double lnew = 0.0;
-        if (lane < NG) {
-            double gn = lam[gr * 7] * rec[49 + gc], gp = lam[gr * 7] * rec[70 + gc];
-#pragma unroll
-            for (int x = 1; x < 7; ++x) {
-                gn = gn + lam[gr * 7 + x] * rec[49 + x * 3 + gc];
-                gp = gp + lam[gr * 7 + x] * rec[70 + x * 3 + gc];
-            }
-            g[(size_t)lane * K + q + 1] = q == kme ? gp : carry + gp;
-            carry = gn;
-        }
-        if (lane < NL) {
-            lnew = lam[lr * 7] * rec[lc];
-#pragma unroll
-            for (int x = 1; x < 7; ++x) lnew = lnew + lam[lr * 7 + x] * rec[x * 7 + lc];
-            if (q == kme) lnew = lnew + seed_lo;
-        }
-        __syncthreads();
-        if (lane < NL) lam[lane] = lnew;                             // lam_q
-    }
-    if (lane < NG) g[(size_t)lane * K] = carry;                      // g_0 = lam_1 B_kn[0]
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(64) void aj_rows_kernel(AjArgs a)
 {
-    __shared__ double rec[AJ_REC_PAD], lam[24];
+    __shared__ double rec[CP_REC_PAD], lam[24];
     const int pr = blockIdx.x, lane = threadIdx.x;
     if (pr >= a.n) return;
     const double *row = a.pairs + (size_t)pr * 4;
@@ -148,74 +76,24 @@ __global__ __launch_bounds__(64) void aj_rows_kernel(AjArgs a)
     int st = mover_ok ? MPCX_ST_OK : MPCX_ST_BADK;
     if (st == MPCX_ST_OK) st = cp_state(a.row, row[0], t, pa, va, nda);
     if (st == MPCX_ST_OK) st = cp_state(a.col, row[1], t, pb, vb, ndb);
-    int mk = 0, mnn = 2, mo = 0;
-    double htau = 0.0, Lm = 0.0, h00 = 0.0, h10 = 0.0, h01 = 0.0, h11 = 0.0;
-    if (st == MPCX_ST_OK) {
-        const CpNode &nd = mvr ? ndb : nda;                          // (the object that moves is one of the constellation: the row side)
-        const double L = a.row.units[2 * nd.o], Tu = a.row.units[2 * nd.o + 1];
-        const double tfv = (a.row.span[2 * nd.o + 1] - a.row.span[2 * nd.o]) / Tu;
-        if (!(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
-        else if (a.dstat[nd.o] != MPCX_ST_OK) st = a.dstat[nd.o];
-        mk = nd.k; mnn = nd.nn; mo = nd.o;
-        htau = tfv / (double)(nd.nn - 1);
-        Lm = L;
-        h00 = nd.h00; h10 = nd.h10; h01 = nd.h01; h11 = nd.h11;
-    }
+    CpMover mv = {};
+    const CpNode &ndm = mvr ? ndb : nda;                             // (the object that moves is one of the constellation: the row side)
+    if (st == MPCX_ST_OK) st = cp_mover(a.row, a.dstat, ndm, K, mv);
     double ew[3], e1[3], e2[3], mn = 0.0, wn = 0.0, W11 = 1.0, W12 = 0.0, W22 = 1.0;
     if (st == MPCX_ST_OK) {
-        // the frame of collision_probability_kernel, in its operation order
         double d[3], w[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { d[c] = pb[c] - pa[c]; w[c] = vb[c] - va[c]; }
-        wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-        if (!(wn > 0.0) || !cp_finite(wn)) st = MPCX_ST_NUMERIC;
-        else {
-            double m[3];
+        st = cp_frame(d, w, wn, ew, mn, e1, e2);
+        if (st == MPCX_ST_OK && a.have_P) {
+            double Ca[6], Cb[6], Cs[6];
+            CpPlane pl;
+            cp_covariance(a.row, nda, t, a.mu, Ca);
+            cp_covariance(a.col, ndb, t, a.mu, Cb);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) ew[c] = w[c] / wn;
-            const double dw = d[0] * ew[0] + d[1] * ew[1] + d[2] * ew[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) m[c] = d[c] - dw * ew[c];
-            mn = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-            if (mn > 0.0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = m[c] / mn;
-            } else {
-                int ax = 0;
-                double ea = ew[0];
-                if (fabs(ew[1]) < fabs(ea)) { ax = 1; ea = ew[1]; }
-                if (fabs(ew[2]) < fabs(ea)) { ax = 2; ea = ew[2]; }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = (c == ax ? 1.0 : 0.0) - ea * ew[c];
-                const double en = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = e1[c] / en;
-            }
-            e2[0] = ew[1] * e1[2] - ew[2] * e1[1];
-            e2[1] = ew[2] * e1[0] - ew[0] * e1[2];
-            e2[2] = ew[0] * e1[1] - ew[1] * e1[0];
-            if (a.have_P) {
-                double Ca[6], Cb[6], Cs[6], g1[3], g2[3];
-                cp_covariance(a.row, nda, t, a.mu, Ca);
-                cp_covariance(a.col, ndb, t, a.mu, Cb);
-#pragma unroll
-                for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
-                g1[0] = Cs[0] * e1[0] + Cs[1] * e1[1] + Cs[2] * e1[2];
-                g1[1] = Cs[1] * e1[0] + Cs[3] * e1[1] + Cs[4] * e1[2];
-                g1[2] = Cs[2] * e1[0] + Cs[4] * e1[1] + Cs[5] * e1[2];
-                g2[0] = Cs[0] * e2[0] + Cs[1] * e2[1] + Cs[2] * e2[2];
-                g2[1] = Cs[1] * e2[0] + Cs[3] * e2[1] + Cs[4] * e2[2];
-                g2[2] = Cs[2] * e2[0] + Cs[4] * e2[1] + Cs[5] * e2[2];
-                const double c11 = e1[0] * g1[0] + e1[1] * g1[1] + e1[2] * g1[2];
-                const double c12 = e1[0] * g2[0] + e1[1] * g2[1] + e1[2] * g2[2];
-                const double c22 = e2[0] * g2[0] + e2[1] * g2[1] + e2[2] * g2[2];
-                const double tr = c11 + c22, df = c11 - c22;
-                const double l1 = 0.5 * (tr + sqrt(df * df + 4.0 * c12 * c12));
-                const double det = c11 * c22 - c12 * c12;
-                const double l2 = det / l1;
-                if (!(l2 > 0.0) || !cp_finite(l2) || !cp_finite(l1)) st = MPCX_ST_NUMERIC;
-                else { W11 = c22 / det; W12 = -c12 / det; W22 = c11 / det; }      // W = C_2^-1
-            }
+            for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
+            st = cp_plane_covariance(Cs, e1, e2, pl);
+            if (st == MPCX_ST_OK) { W11 = pl.c22 / pl.det; W12 = -pl.c12 / pl.det; W22 = pl.c11 / pl.det; }      // W = C_2^-1
         }
     }
 
@@ -223,24 +101,13 @@ __global__ __launch_bounds__(64) void aj_rows_kernel(AjArgs a)
 #pragma unroll
     for (int c = 0; c < MPCX_NAR; ++c) o[c] = cp_nan();
     if (st == MPCX_ST_OK) {
-        // ---- the adjoint sweep of the object that moves.  R Lam of the two bracketing nodes, entry (lr, lc):
-        //      sgn [e_1 e_2 e_w]^T L [hp I | h_tau hv I | 0]
+        // ---- the adjoint sweep of the object that moves, seeded with R Lam of the two bracketing nodes, entry (lr, lc)
         const int lr = lane < 21 ? lane / 7 : 0, lc = lane < 21 ? lane - 7 * (lane / 7) : 0;
         double seed_hi = 0.0, seed_lo = 0.0;
-        {
-            const double sgn = mvr ? 1.0 : -1.0;
-            double Rv[3];
-#pragma unroll
-            for (int x = 0; x < 3; ++x) Rv[x] = sgn * (lr == 0 ? e1[x] : (lr == 1 ? e2[x] : ew[x]));
-            const int cc = lc < 3 ? lc : lc - 3;
-            const double Rc = cc == 0 ? Rv[0] : (cc == 1 ? Rv[1] : Rv[2]);
-            const double L = Lm, ht = htau;
-            if (lc < 3) { seed_hi = (L * h01) * Rc; seed_lo = (L * h00) * Rc; }
-            else if (lc < 6) { seed_hi = (L * (ht * h11)) * Rc; seed_lo = (L * (ht * h10)) * Rc; }
-        }
+        cp_sweep_seed(mvr ? 1.0 : -1.0, e1, e2, ew, mv.L, mv.htau, ndm.h00, ndm.h10, ndm.h01, ndm.h11, lr, lc, seed_hi, seed_lo);
         for (int e = 0; e < 9; ++e)                                  // the nodes past k + 1
-            for (int m = mk + 2 + lane; m < a.K; m += 64) g[(size_t)e * K + m] = 0.0;
-        aj_sweep<3>(lane, a.stage + (size_t)mo * (K - 1) * MPCX_STAGE_DOUBLES, mk, seed_hi, seed_lo, g, K, rec, lam);
+            for (int m = mv.k + 2 + lane; m < a.K; m += 64) g[(size_t)e * K + m] = 0.0;
+        aj_sweep<3>(lane, a.stage + (size_t)mv.o * (K - 1) * MPCX_STAGE_DOUBLES, mv.k, seed_hi, seed_lo, g, K, rec, lam);
 
         // ---- the tangent half-plane of the target ellipse: q = W (1, 0)^T / sqrt(W11), a_m = q_1 g_m[0, :] + q_2 g_m[1, :]
         const double sq = sqrt(W11), q1 = W11 / sq, q2 = W12 / sq;
@@ -346,7 +213,7 @@ __device__ __forceinline__ double aj_evaluate(const AjSat &sa, const int *idx, c
 
 __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
 {
-    __shared__ double rec[AJ_REC_PAD], lam[48];
+    __shared__ double rec[CP_REC_PAD], lam[48];
     __shared__ double z[AJ_NZ], zn[AJ_NZ], dz[AJ_NZ], F[AJ_NZ], slack[AJ_MAXR], bh[AJ_MAXR], cs[AJ_MAXR], gd[AJ_NZ];
     __shared__ double H[AJ_NZ][AJ_NZ], G[AJ_NZ][AJ_NZ + 1];
     __shared__ int idx[AJ_MAXR], act[AJ_NZ];
@@ -568,7 +435,7 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
         sdv = sdv + wm * sqrt(da0 * da0 + da1 * da1 + da2 * da2);
         smax = fmax(smax, sqrt(u0 * u0 + u1 * u1 + u2 * u2));
     }
-    const double cost = 0.5 * aj_wave_sum(scost), dv = aj_wave_sum(sdv), umx = aj_wave_max(smax), nb = aj_wave_sum((double)nball);
+    const double cost = 0.5 * cp_wave_sum(scost), dv = cp_wave_sum(sdv), umx = cp_wave_max(smax), nb = cp_wave_sum((double)nball);
     int nact = 0;
     for (int i = ne; i < nz; ++i) nact += z[i] > 0.0 ? 1 : 0;
     if (lane == 0) {
@@ -610,7 +477,7 @@ __global__ __launch_bounds__(64) void aj_solve_kernel(AjArgs a)
 // rows of the first pass).
 __global__ __launch_bounds__(64) void ar_trhs_kernel(AjArgs a, const double *du_prev, const double *Y0, double *trhs)
 {
-    __shared__ double rec[AJ_REC_PAD], lam[48];
+    __shared__ double rec[CP_REC_PAD], lam[48];
     const int lane = threadIdx.x, s = blockIdx.x;
     if (s >= a.S || (a.skip && a.skip[s])) return;
     const size_t K = (size_t)a.K;
@@ -630,42 +497,27 @@ __global__ __launch_bounds__(64) void ar_trhs_kernel(AjArgs a, const double *du_
     }
 }
 
-// workspace of the _dev call: [stage S (K-1) records][tf S][discretiser status S][g n 3 3 K][a n 3 K][info n][owner n][T S 6 3 K][jd S 6 K]
-struct AjWorkspace {
-    double *stage, *tf, *g, *a, *info, *T, *jd;
-    int32_t *dstat, *owner;
+// workspace of the _dev call: [the linearisation's][g n 3 3 K][a n 3 K][info n][owner n][T S 6 3 K][jd S 6 K]
+struct AjWorkspace : LinWorkspace {
+    double *g, *a, *info, *T, *jd;
+    int32_t *owner;
     size_t bytes;
-    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
     AjWorkspace(void *base, int n, int S, int K)
     {
-        char *p = (char *)base;
-        stage = (double *)p; p += al((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES * sizeof(double));
-        tf = (double *)p; p += al((size_t)S * sizeof(double));
-        dstat = (int32_t *)p; p += al((size_t)S * sizeof(int32_t));
-        g = (double *)p; p += al((size_t)n * 9 * K * sizeof(double));
-        a = (double *)p; p += al((size_t)n * 3 * K * sizeof(double));
-        info = (double *)p; p += al((size_t)n * AJ_INFO * sizeof(double));
-        owner = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
-        T = (double *)p; p += al((size_t)S * 18 * K * sizeof(double));
-        jd = (double *)p; p += al((size_t)S * 6 * K * sizeof(double));
-        bytes = (size_t)(p - (char *)base);
+        Carver c(base);
+        carve(c, S, K);
+        g = c.take<double>((size_t)n * 9 * K);
+        a = c.take<double>((size_t)n * 3 * K);
+        info = c.take<double>((size_t)n * AJ_INFO);
+        owner = c.take<int32_t>((size_t)n);
+        T = c.take<double>((size_t)S * 18 * K);
+        jd = c.take<double>((size_t)S * 6 * K);
+        bytes = c.bytes();
     }
 };
 
-struct AjCall {
-    int n;
-    const double *pairs;
+struct AjCall : EncProblem {
     const int32_t *mover;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *U, *units, *span, *consts;
-    int flags;
-    double max_step;
-    const double *P;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P;
-    double mu, target;
     const double *u_max;
     int hold_terminal;
     double tol;
@@ -676,26 +528,31 @@ struct AjCall {
 
 static int aj_check(mpcx_ctx *ctx, const AjCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: need n>=1, S>=1, K>=2, mu>0");
-    if (!(c.target > 0.0) || !(c.target < __builtin_inf()))
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: target must be a positive finite number");
+    if (int rc = enc_check(ctx, c, "avoidance_joint", c.du && c.sat_out && c.row_out && c.sat_status && c.row_status,
+                           "du, sat_out, row_out, sat_status and row_status"))
+        return rc;
     if (!(c.tol > 0.0) || !(c.tol < __builtin_inf()) || c.max_iter < 1)
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: tol must be a positive finite number and max_iter >= 1");
+        return enc_fail(ctx, "avoidance_joint", "tol must be a positive finite number and max_iter >= 1");
     if (c.sat0 < 0 || c.nsat < 1 || c.sat0 > c.S - c.nsat)
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: the block sat0 .. sat0 + nsat - 1 must lie in 0 .. S - 1, nsat >= 1");
-    if (!(c.max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: max_step must be > 0");
-    if (c.flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
-        return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
-    if (!c.pairs || !c.Y || !c.U || !c.units || !c.span || !c.consts || !c.du || !c.sat_out || !c.row_out || !c.sat_status || !c.row_status)
-        return ctx_fail(ctx, MPCX_E_BADARG,
-                        "avoidance_joint: pairs, Y, U, units, span, consts, du, sat_out, row_out, sat_status and row_status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: cat_units and cat_span are required with cat_Y");
-        if ((c.P != nullptr) != (c.cat_P != nullptr))
-            return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: P and cat_P come together (a Mahalanobis target) or not at all (metres)");
-    }
-    return ctx_check_atmosphere(ctx, c.flags, "avoidance_joint");
+        return enc_fail(ctx, "avoidance_joint", "the block sat0 .. sat0 + nsat - 1 must lie in 0 .. S - 1, nsat >= 1");
+    return MPCX_OK;
+}
+
+// the problem's and the joint call's own host arrays replaced by copies on the device, and the device arrays of its results: they
+// have the caller's shapes, whatever block of satellites the call computes
+static void aj_stage(DeviceArena &ar, AjCall &d)
+{
+    const size_t n = (size_t)d.n, S = (size_t)d.S, K = (size_t)d.K;
+    enc_upload(ar, d);
+    d.mover = d.mover ? ar.upload(d.mover, n) : nullptr;
+    d.u_max = d.u_max ? ar.upload(d.u_max, S) : nullptr;
+    d.du = ar.alloc<double>(S * 3 * K);
+    d.sat_out = ar.alloc<double>(S * MPCX_NAJ);
+    d.row_out = ar.alloc<double>(n * MPCX_NAR);
+    d.rows = d.rows ? ar.alloc<double>(n * 3 * K) : nullptr;
+    d.tsens = d.tsens ? ar.alloc<double>(S * 18 * K) : nullptr;
+    d.sat_status = ar.alloc<int32_t>(S);
+    d.row_status = ar.alloc<int32_t>(n);
 }
 
 // what a pass of the refinement adds to the joint call (all NULL / 0 with solve = 1: the joint call)
@@ -712,11 +569,7 @@ struct AjPass {
 static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream_t st, const AjPass &x = AjPass())
 {
     const AjWorkspace ws(workspace, c.n, c.S, c.K);
-    hipLaunchKernelGGL(aj_tf_kernel, dim3((unsigned)((c.S + 255) / 256)), dim3(256), 0, st, c.S, c.units, c.span, ws.tf);
-    MPCX_HIP(ctx, hipGetLastError());
-    if (int rc = mpcx_discretize_stages_ragged_dev(ctx, c.S, c.K, c.Ks, c.K, c.Ks, c.Y, c.U, ws.tf, c.consts, c.flags, c.max_step, ws.stage,
-                                                   ws.dstat, st))
-        return rc;
+    if (int rc = enc_linearise(ctx, c, ws, st)) return rc;
     AjArgs a;
     a.n = c.n; a.S = c.S; a.K = c.K; a.sat0 = c.sat0; a.nsat = c.nsat; a.have_cat = c.cat_Y != nullptr; a.have_P = c.P != nullptr;
     a.hold = c.hold_terminal != 0; a.max_iter = c.max_iter;
@@ -761,8 +614,8 @@ extern "C" int mpcx_avoidance_joint_dev(mpcx_ctx *ctx, int n, const double *pair
                                         int32_t *row_status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AjCall c{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,
-                   cat_P, mu, target, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    const AjCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
+                    mu, target}, mover, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
     if (int rc = aj_check(ctx, c)) return rc;
     if (!workspace)
         return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: a workspace of mpcx_avoidance_joint_workspace_bytes(n, S, K) bytes is required");
@@ -778,37 +631,14 @@ extern "C" int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, c
                                     double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AjCall c{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,
-                   cat_P, mu, target, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    const AjCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
+                    mu, target}, mover, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
     if (int rc = aj_check(ctx, c)) return rc;
-    if (mover)
-        for (int r = 0; r < n; ++r)
-            if (mover[r] < 0 || mover[r] > 1 || (cat_Y && mover[r] != 0))
-                return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: mover is 0 (object i) or 1 (object j); against a catalogue only 0");
+    if (int rc = check_mover(ctx, c, mover, "avoidance_joint")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     AjCall d = c;
-    d.pairs = ar.upload(pairs, (size_t)n * 4);
-    d.mover = mover ? ar.upload(mover, (size_t)n) : nullptr;
-    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.U = ar.upload(U, (size_t)S * 3 * K);
-    d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2); d.consts = ar.upload(consts, (size_t)S * MPCX_NCONST);
-    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    d.P = P ? ar.upload(P, (size_t)S * K * 36) : nullptr;
-    d.u_max = u_max ? ar.upload(u_max, (size_t)S) : nullptr;
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        d.cat_span = ar.upload(cat_span, (size_t)D * 2);
-        d.cat_P = cat_P ? ar.upload(cat_P, (size_t)D * cat_K * 36) : nullptr;
-        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
-    // the device arrays have the caller's shapes; what comes back is the block's satellites and the rows they own
-    d.du = ar.alloc<double>((size_t)S * 3 * K);
-    d.sat_out = ar.alloc<double>((size_t)S * MPCX_NAJ);
-    d.row_out = ar.alloc<double>((size_t)n * MPCX_NAR);
-    d.rows = rows ? ar.alloc<double>((size_t)n * 3 * K) : nullptr;
-    d.tsens = tsens ? ar.alloc<double>((size_t)S * 18 * K) : nullptr;
-    d.sat_status = ar.alloc<int32_t>(S);
-    d.row_status = ar.alloc<int32_t>(n);
+    aj_stage(ar, d);
     if (ar.failed()) return ar.code();
     void *ws = ctx_workspace(ctx, mpcx_avoidance_joint_workspace_bytes(n, S, K));
     if (!ws) return MPCX_E_NOMEM;
@@ -955,25 +785,23 @@ struct ArWorkspace {
     size_t bytes;
     ArWorkspace(void *base, int n, int S, int K, int D, int M)
     {
-        char *p = (char *)base;
-        auto al = AjWorkspace::al;
-        aj = p; p += al(AjWorkspace(nullptr, n, S, K).bytes);
-        scr = p; p += al(mpcx_conjunction_pairs_workspace_bytes(S, D, M));
-        Ut = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
-        Yp = (double *)p; p += al((size_t)S * 7 * K * sizeof(double));
-        y0 = (double *)p; p += al((size_t)S * 7 * sizeof(double));
-        end_tau = (double *)p; p += al((size_t)S * sizeof(double));
-        du_try = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
-        sat_try = (double *)p; p += al((size_t)S * MPCX_NAJ * sizeof(double));
-        row_try = (double *)p; p += al((size_t)n * MPCX_NAR * sizeof(double));
-        z = (double *)p; p += al((size_t)S * AJ_NZ * sizeof(double));
-        trhs = (double *)p; p += al((size_t)S * 6 * sizeof(double));
-        int32_t **per_sat[] = {&pst, &nsteps, &sat_st_try, &flies, &skip, &eph_st};
-        for (int32_t **q : per_sat) { *q = (int32_t *)p; p += al((size_t)S * sizeof(int32_t)); }
-        row_st_try = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
-        scr_st = (int32_t *)p; p += al((size_t)n * sizeof(int32_t));
-        cat_st = (int32_t *)p; p += al((size_t)(D > 0 ? D : 1) * sizeof(int32_t));
-        bytes = (size_t)(p - (char *)base);
+        Carver c(base);
+        aj = c.take<char>(AjWorkspace(nullptr, n, S, K).bytes);
+        scr = c.take<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));
+        Ut = c.take<double>((size_t)S * 3 * K);
+        Yp = c.take<double>((size_t)S * 7 * K);
+        y0 = c.take<double>((size_t)S * 7);
+        end_tau = c.take<double>((size_t)S);
+        du_try = c.take<double>((size_t)S * 3 * K);
+        sat_try = c.take<double>((size_t)S * MPCX_NAJ);
+        row_try = c.take<double>((size_t)n * MPCX_NAR);
+        z = c.take<double>((size_t)S * AJ_NZ);
+        trhs = c.take<double>((size_t)S * 6);
+        for (int32_t **q : {&pst, &nsteps, &sat_st_try, &flies, &skip, &eph_st}) *q = c.take<int32_t>((size_t)S);
+        row_st_try = c.take<int32_t>((size_t)n);
+        scr_st = c.take<int32_t>((size_t)n);
+        cat_st = c.take<int32_t>((size_t)(D > 0 ? D : 1));
+        bytes = c.bytes();
     }
 };
 
@@ -1055,8 +883,8 @@ extern "C" size_t mpcx_avoidance_refine_workspace_bytes(int n, int S, int K, int
 }
 
 #define MPCX_AR_CALL                                                                                                                        \
-    ArCall{AjCall{n, pairs, mover, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span,     \
-                  cat_P, mu, target, u_max, hold_terminal, tol, max_iter, 0, S, du, sat_out, row_out, rows, tsens, sat_status, row_status},  \
+    ArCall{AjCall{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,   \
+                   mu, target}, mover, u_max, hold_terminal, tol, max_iter, 0, S, du, sat_out, row_out, rows, tsens, sat_status, row_status}, \
            M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, rhs_term}
 
 extern "C" int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
@@ -1090,35 +918,13 @@ extern "C" int mpcx_avoidance_refine(mpcx_ctx *ctx, int n, const double *pairs, 
     if (!ctx) return MPCX_E_BADARG;
     const ArCall c = MPCX_AR_CALL;
     if (int rc = ar_check(ctx, c)) return rc;
-    if (mover)
-        for (int r = 0; r < n; ++r)
-            if (mover[r] < 0 || mover[r] > 1 || (cat_Y && mover[r] != 0))
-                return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: mover is 0 (object i) or 1 (object j); against a catalogue only 0");
+    if (int rc = check_mover(ctx, c.j, mover, "avoidance_refine")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     ArCall d = c;
     AjCall &j = d.j;
-    j.pairs = ar.upload(pairs, (size_t)n * 4);
-    j.mover = mover ? ar.upload(mover, (size_t)n) : nullptr;
-    j.Y = ar.upload(Y, (size_t)S * 7 * K); j.U = ar.upload(U, (size_t)S * 3 * K);
-    j.units = ar.upload(units, (size_t)S * 2); j.span = ar.upload(span, (size_t)S * 2); j.consts = ar.upload(consts, (size_t)S * MPCX_NCONST);
-    j.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    j.P = P ? ar.upload(P, (size_t)S * K * 36) : nullptr;
-    j.u_max = u_max ? ar.upload(u_max, (size_t)S) : nullptr;
-    if (cat_Y) {
-        j.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); j.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        j.cat_span = ar.upload(cat_span, (size_t)D * 2);
-        j.cat_P = cat_P ? ar.upload(cat_P, (size_t)D * cat_K * 36) : nullptr;
-        j.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
+    aj_stage(ar, j);
     const size_t np = (size_t)rounds + 2;
-    j.du = ar.alloc<double>((size_t)S * 3 * K);
-    j.sat_out = ar.alloc<double>((size_t)S * MPCX_NAJ);
-    j.row_out = ar.alloc<double>((size_t)n * MPCX_NAR);
-    j.rows = rows ? ar.alloc<double>((size_t)n * 3 * K) : nullptr;
-    j.tsens = tsens ? ar.alloc<double>((size_t)S * 18 * K) : nullptr;
-    j.sat_status = ar.alloc<int32_t>(S);
-    j.row_status = ar.alloc<int32_t>(n);
     d.Y_out = ar.alloc<double>((size_t)S * 7 * K); d.pairs_out = ar.alloc<double>((size_t)n * 4);
     d.hist_d0 = ar.alloc<double>(np * n); d.hist_tca = ar.alloc<double>(np * n); d.hist_term = ar.alloc<double>(np * S);
     d.rounds_done = ar.alloc<int32_t>(S);

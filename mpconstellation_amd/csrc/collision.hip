@@ -6,7 +6,10 @@
 //                                  (the short-encounter model), by a fixed 64-point Gauss-Legendre rule.
 // Both are small next to the discretisation in front of them: they are written for a fixed operation order (the numpy restatement
 // tests/collision_reference.py follows it line by line), not for speed.  No atomics, nothing crosses a workgroup.
-#include "collision_device.hpp"      // cp_nan, cp_finite, CpSide, cp_object: shared with avoidance.hip
+// The encounter frame, the encounter-plane covariance and the butterfly are collision_device.hpp's, shared with avoidance.hip and
+// avoidance_joint.hip; the linearisation step enc_linearise (encounter_host.hpp) is defined here, for them and for the covariance.
+#include "collision_device.hpp"
+#include "encounter_host.hpp"
 
 #include <math.h>
 
@@ -15,15 +18,22 @@ namespace mpcx {
 // ---------------------------------------------------------------- covariance along trajectories
 
 // tf [S] of the linearisation: the span in the satellite's own time unit.  A satellite whose span and time unit give no positive
-// finite tf -- an empty span, a time unit that is zero, negative or not finite -- is linearised with tf = 1, so that the
-// discretiser's step-size control never sees a value it was not written for; covariance_kernel makes the same test and gives that
-// satellite MPCX_ST_BADK and NaN whatever the discretiser returns.
-__global__ __launch_bounds__(256) void covariance_tf_kernel(int S, const double *units, const double *span, double *tf)
+// finite tf -- an empty span, a time unit that is zero, negative or not finite -- is linearised with tf = 1 (enc_linearise);
+// covariance_kernel and cp_mover make the same test and give that satellite MPCX_ST_BADK and NaN whatever the discretiser returns.
+__global__ __launch_bounds__(256) void enc_tf_kernel(int S, const double *units, const double *span, double *tf)
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
     const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
     tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
+}
+
+int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream)
+{
+    hipLaunchKernelGGL(enc_tf_kernel, dim3((unsigned)((p.S + 255) / 256)), dim3(256), 0, stream, p.S, p.units, p.span, ws.tf);
+    MPCX_HIP(ctx, hipGetLastError());
+    return mpcx_discretize_stages_ragged_dev(ctx, p.S, p.K, p.Ks, p.K, p.Ks, p.Y, p.U, ws.tf, p.consts, p.flags, p.max_step, ws.stage, ws.dstat,
+                                             stream);
 }
 
 struct CovArgs {
@@ -50,7 +60,7 @@ __global__ __launch_bounds__(64) void covariance_kernel(CovArgs a)
     const double qs = a.q ? a.q[s] : 0.0;
     double pij = a.P0[(size_t)s * 36 + lo * 6 + hi];                 // the upper triangle alone is read
     int st = MPCX_ST_OK;
-    const double tfv = (tb - ta) / Tu;                               // (covariance_tf_kernel's test: no positive finite tf, no linearisation)
+    const double tfv = (tb - ta) / Tu;                               // (enc_tf_kernel's test: no positive finite tf, no linearisation)
     if (nn < 2 || nn > a.K || !(tb > ta) || !(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
     else if (a.dstat[s] != MPCX_ST_OK) st = a.dstat[s];
     else if (__any(own && !cp_finite(pij))) st = MPCX_ST_NUMERIC;
@@ -95,20 +105,16 @@ __global__ __launch_bounds__(64) void covariance_kernel(CovArgs a)
     }
 }
 
-// workspace of the _dev call: [stage S (K-1) records][tf S][zero thrust S 3 K][discretiser status S]
-struct CovWorkspace {
-    double *stage, *tf, *uzero;
-    int32_t *dstat;
+// workspace of the _dev call: [the linearisation's][zero thrust S 3 K]
+struct CovWorkspace : LinWorkspace {
+    double *uzero;
     size_t bytes;
-    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
     CovWorkspace(void *base, int S, int K)
     {
-        char *p = (char *)base;
-        stage = (double *)p; p += al((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES * sizeof(double));
-        tf = (double *)p; p += al((size_t)S * sizeof(double));
-        uzero = (double *)p; p += al((size_t)S * 3 * K * sizeof(double));
-        dstat = (int32_t *)p; p += al((size_t)S * sizeof(int32_t));
-        bytes = (size_t)(p - (char *)base);
+        Carver c(base);
+        carve(c, S, K);
+        uzero = c.take<double>((size_t)S * 3 * K);
+        bytes = c.bytes();
     }
 };
 
@@ -229,70 +235,31 @@ __global__ __launch_bounds__(64) void collision_probability_kernel(CpArgs a)
         for (int c = 0; c < 3; ++c) { d[c] = pb[c] - pa[c]; w[c] = vb[c] - va[c]; }
 #pragma unroll
         for (int c = 0; c < 6; ++c) Cs[c] = Ca[c] + Cb[c];
-        const double wn = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
         const double R = Ra + Rb;
-        if (!(wn > 0.0) || !cp_finite(wn) || !cp_finite(R)) st = MPCX_ST_NUMERIC;
-        else {
-            double ew[3], m[3], e1[3], e2[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) ew[c] = w[c] / wn;
-            const double dw = d[0] * ew[0] + d[1] * ew[1] + d[2] * ew[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) m[c] = d[c] - dw * ew[c];
-            const double mn = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-            if (mn > 0.0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = m[c] / mn;
-            } else {
-                // the coordinate axis on which |e_w| is smallest (the first of equal ones), made orthogonal to e_w
-                int ax = 0;
-                double ea = ew[0];
-                if (fabs(ew[1]) < fabs(ea)) { ax = 1; ea = ew[1]; }
-                if (fabs(ew[2]) < fabs(ea)) { ax = 2; ea = ew[2]; }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = (c == ax ? 1.0 : 0.0) - ea * ew[c];
-                const double en = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) e1[c] = e1[c] / en;
+        double wn, mn, ew[3], e1[3], e2[3];
+        CpPlane pl;
+        st = cp_frame(d, w, wn, ew, mn, e1, e2);
+        if (st == MPCX_ST_OK && !cp_finite(R)) st = MPCX_ST_NUMERIC;
+        if (st == MPCX_ST_OK) st = cp_plane_covariance(Cs, e1, e2, pl);
+        if (st == MPCX_ST_OK) {
+            // the angle of the first principal axis
+            const double c12 = pl.c12, df = pl.c11 - pl.c22, l1 = pl.l1, l2 = pl.l2;
+            const double ph = 0.5 * atan2(2.0 * c12, df);
+            const double xm = mn * cos(ph), ym = -mn * sin(ph);
+            const double s1 = sqrt(l1), s2 = sqrt(l2);
+            double pc = 0.0;
+            if (R > 0.0) {
+                const double th = 1.5707963267948966 * CP_GL[lane][0], wt = 1.5707963267948966 * CP_GL[lane][1];
+                const double x = R * sin(th), cx = R * cos(th);
+                const double den = 1.4142135623730951 * s2;
+                const double band = cp_half_erf_diff((ym - cx) / den, (ym + cx) / den);
+                const double z = (x - xm) / s1;
+                double f = wt * (band * (exp(-0.5 * z * z) / (2.5066282746310002 * s1)) * cx);
+                f = cp_wave_sum(f);
+                pc = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);
             }
-            e2[0] = ew[1] * e1[2] - ew[2] * e1[1];
-            e2[1] = ew[2] * e1[0] - ew[0] * e1[2];
-            e2[2] = ew[0] * e1[1] - ew[1] * e1[0];
-            // C2 = E^T Cs E; Cs = (c00, c01, c02, c11, c12, c22)
-            double g1[3], g2[3];                                     // Cs e1, Cs e2
-            g1[0] = Cs[0] * e1[0] + Cs[1] * e1[1] + Cs[2] * e1[2];
-            g1[1] = Cs[1] * e1[0] + Cs[3] * e1[1] + Cs[4] * e1[2];
-            g1[2] = Cs[2] * e1[0] + Cs[4] * e1[1] + Cs[5] * e1[2];
-            g2[0] = Cs[0] * e2[0] + Cs[1] * e2[1] + Cs[2] * e2[2];
-            g2[1] = Cs[1] * e2[0] + Cs[3] * e2[1] + Cs[4] * e2[2];
-            g2[2] = Cs[2] * e2[0] + Cs[4] * e2[1] + Cs[5] * e2[2];
-            const double c11 = e1[0] * g1[0] + e1[1] * g1[1] + e1[2] * g1[2];
-            const double c12 = e1[0] * g2[0] + e1[1] * g2[1] + e1[2] * g2[2];
-            const double c22 = e2[0] * g2[0] + e2[1] * g2[1] + e2[2] * g2[2];
-            // eigenvalues l1 >= l2 (the smaller one as det / l1: no cancellation) and the angle of the first axis
-            const double tr = c11 + c22, df = c11 - c22;
-            const double l1 = 0.5 * (tr + sqrt(df * df + 4.0 * c12 * c12));
-            const double l2 = (c11 * c22 - c12 * c12) / l1;
-            if (!(l2 > 0.0) || !cp_finite(l2) || !cp_finite(l1)) st = MPCX_ST_NUMERIC;
-            else {
-                const double ph = 0.5 * atan2(2.0 * c12, df);
-                const double xm = mn * cos(ph), ym = -mn * sin(ph);
-                const double s1 = sqrt(l1), s2 = sqrt(l2);
-                double pc = 0.0;
-                if (R > 0.0) {
-                    const double th = 1.5707963267948966 * CP_GL[lane][0], wt = 1.5707963267948966 * CP_GL[lane][1];
-                    const double x = R * sin(th), cx = R * cos(th);
-                    const double den = 1.4142135623730951 * s2;
-                    const double band = cp_half_erf_diff((ym - cx) / den, (ym + cx) / den);
-                    const double z = (x - xm) / s1;
-                    double f = wt * (band * (exp(-0.5 * z * z) / (2.5066282746310002 * s1)) * cx);
-#pragma unroll
-                    for (int sh = 32; sh >= 1; sh >>= 1) f = f + __shfl_xor(f, sh);
-                    pc = f < 0.0 ? 0.0 : (f > 1.0 ? 1.0 : f);
-                }
-                o[MPCX_PC_P] = pc; o[MPCX_PC_MISS] = mn; o[MPCX_PC_SPEED] = wn; o[MPCX_PC_SIGMA1] = s1; o[MPCX_PC_SIGMA2] = s2;
-                o[MPCX_PC_MAHAL] = sqrt(xm * xm / l1 + ym * ym / l2);
-            }
+            o[MPCX_PC_P] = pc; o[MPCX_PC_MISS] = mn; o[MPCX_PC_SPEED] = wn; o[MPCX_PC_SIGMA1] = s1; o[MPCX_PC_SIGMA2] = s2;
+            o[MPCX_PC_MAHAL] = sqrt(xm * xm / l1 + ym * ym / l2);
         }
     }
     if (lane == 0) {
@@ -350,11 +317,11 @@ extern "C" int mpcx_covariance_batch_dev(mpcx_ctx *ctx, int S, int K, const int3
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     const CovWorkspace ws(workspace, S, K);
-    hipLaunchKernelGGL(covariance_tf_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, S, units, span, ws.tf);
-    MPCX_HIP(ctx, hipGetLastError());
     if (!U) MPCX_HIP(ctx, hipMemsetAsync(ws.uzero, 0, (size_t)S * 3 * K * sizeof(double), st));
-    if (int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, X, U ? U : ws.uzero, ws.tf, consts, flags, max_step, ws.stage, ws.dstat, st))
-        return rc;
+    EncProblem lin{};
+    lin.S = S; lin.K = K; lin.Ks = Ks; lin.Y = X; lin.U = U ? U : ws.uzero; lin.units = units; lin.span = span; lin.consts = consts;
+    lin.flags = flags; lin.max_step = max_step;
+    if (int rc = enc_linearise(ctx, lin, ws, st)) return rc;
     const CovArgs a{S, K, Ks, ws.stage, units, span, P0, q, ws.dstat, P, status};
     hipLaunchKernelGGL(covariance_kernel, dim3((unsigned)S), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());

@@ -1,0 +1,114 @@
+// encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint* and mpcx_avoidance_refine* share, and the
+// linearisation step they share with mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the
+// workspace carver.
+#pragma once
+#include "mpcx_host.hpp"
+
+namespace mpcx {
+
+// a listed-pairs problem as every avoidance entry point takes it: the list, the plan that was screened, the model of its linearisation,
+// the covariances and the catalogue (both optional), the target
+struct EncProblem {
+    int n;
+    const double *pairs;
+    int S, K;
+    const int32_t *Ks;
+    const double *Y, *U, *units, *span, *consts;
+    int flags;
+    double max_step;
+    const double *P;
+    int D, cat_K;
+    const int32_t *cat_Ks;
+    const double *cat_Y, *cat_units, *cat_span, *cat_P;
+    double mu, target;
+};
+
+inline int enc_fail(mpcx_ctx *ctx, const char *name, const char *what)
+{
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", name, what);
+    return ctx_fail(ctx, MPCX_E_BADARG, msg);
+}
+
+// The argument tests of the call `name` that every avoidance entry point makes.  outputs_given / outputs: whether the call's own
+// required output arrays are all there, and their names as the message lists them behind the inputs.
+inline int enc_check(mpcx_ctx *ctx, const EncProblem &p, const char *name, bool outputs_given, const char *outputs)
+{
+    if (p.n < 1 || p.S < 1 || p.K < 2 || !(p.mu > 0.0)) return enc_fail(ctx, name, "need n>=1, S>=1, K>=2, mu>0");
+    if (!(p.target > 0.0) || !(p.target < __builtin_inf())) return enc_fail(ctx, name, "target must be a positive finite number");
+    if (!(p.max_step > 0.0)) return enc_fail(ctx, name, "max_step must be > 0");
+    if (p.flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
+        return enc_fail(ctx, name, "flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
+    if (!p.pairs || !p.Y || !p.U || !p.units || !p.span || !p.consts || !outputs_given) {
+        char what[192];
+        snprintf(what, sizeof what, "pairs, Y, U, units, span, consts, %s are required", outputs);
+        return enc_fail(ctx, name, what);
+    }
+    if (p.cat_Y) {
+        if (p.D < 1 || p.cat_K < 2) return enc_fail(ctx, name, "a catalogue needs D>=1, cat_K>=2");
+        if (!p.cat_units || !p.cat_span) return enc_fail(ctx, name, "cat_units and cat_span are required with cat_Y");
+        if ((p.P != nullptr) != (p.cat_P != nullptr))
+            return enc_fail(ctx, name, "P and cat_P come together (a Mahalanobis target) or not at all (metres)");
+    }
+    return ctx_check_atmosphere(ctx, p.flags, name);
+}
+
+// which object of every pair moves (host array [n] or NULL: object i)
+inline int check_mover(mpcx_ctx *ctx, const EncProblem &p, const int32_t *mover, const char *name)
+{
+    if (mover)
+        for (int r = 0; r < p.n; ++r)
+            if (mover[r] < 0 || mover[r] > 1 || (p.cat_Y && mover[r] != 0))
+                return enc_fail(ctx, name, "mover is 0 (object i) or 1 (object j); against a catalogue only 0");
+    return MPCX_OK;
+}
+
+// the problem's host arrays replaced by copies on the device
+inline void enc_upload(DeviceArena &ar, EncProblem &p)
+{
+    const size_t S = (size_t)p.S, K = (size_t)p.K, D = (size_t)p.D, cK = (size_t)p.cat_K;
+    p.pairs = ar.upload(p.pairs, (size_t)p.n * 4);
+    p.Y = ar.upload(p.Y, S * 7 * K); p.U = ar.upload(p.U, S * 3 * K);
+    p.units = ar.upload(p.units, S * 2); p.span = ar.upload(p.span, S * 2); p.consts = ar.upload(p.consts, S * MPCX_NCONST);
+    p.Ks = p.Ks ? ar.upload(p.Ks, S) : nullptr;
+    p.P = p.P ? ar.upload(p.P, S * K * 36) : nullptr;
+    if (p.cat_Y) {
+        p.cat_Y = ar.upload(p.cat_Y, D * 7 * cK); p.cat_units = ar.upload(p.cat_units, D * 2);
+        p.cat_span = ar.upload(p.cat_span, D * 2);
+        p.cat_P = p.cat_P ? ar.upload(p.cat_P, D * cK * 36) : nullptr;
+        p.cat_Ks = p.cat_Ks ? ar.upload(p.cat_Ks, D) : nullptr;
+    }
+}
+
+// a workspace cut into regions, each rounded up to 256 bytes
+struct Carver {
+    char *base, *p;
+    explicit Carver(void *b) : base((char *)b), p((char *)b) {}
+    template <typename T> T *take(size_t n)
+    {
+        T *r = (T *)p;
+        p += (n * sizeof(T) + 255) & ~(size_t)255;
+        return r;
+    }
+    size_t bytes() const { return (size_t)(p - base); }
+};
+
+// the regions every linearising call's workspace starts with: [stage S (K-1) records][tf S][discretiser status S]
+struct LinWorkspace {
+    double *stage, *tf;
+    int32_t *dstat;
+    void carve(Carver &c, int S, int K)
+    {
+        stage = c.take<double>((size_t)S * (K - 1) * MPCX_STAGE_DOUBLES);
+        tf = c.take<double>((size_t)S);
+        dstat = c.take<int32_t>((size_t)S);
+    }
+};
+
+// The linearisation about (p.Y, p.U) under p.flags, p.max_step: tf [S], the span in each satellite's own time unit (1 where that is
+// not positive and finite: the discretiser's step-size control never sees a value it was not written for, and the kernels that read
+// the records make the same test and give that satellite MPCX_ST_BADK), then the stage records and the discretiser's status.
+// Reads S, K, Ks, Y, U, units, span, consts, flags, max_step of p.  (collision.hip)
+int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream);
+
+}  // namespace mpcx

@@ -202,6 +202,58 @@ def _rel(sc, row):
     return pb - pa, vb - va
 
 
+def scene_with_zero_miss(n):
+    """collision_reference.encounter_scene(n) and one more catalogue object that is WHERE its satellite is at the pair's time: it has
+    the satellite's units, span and node count, the time is one at which both Hermite parameters are exactly 0 -- (t - ta) / hn an
+    integer in floating point, so that both positions are the node's own product y L -- and its position row at that node is the
+    satellite's; it crosses at 1 rad.  The miss of that pair is exactly 0: the frame's e_1 comes from the fallback on the smallest
+    axis.  -> rows, cat = (Y, units, span, P, radius, ns), pairs (n + 1, 4)"""
+    base = C.encounter_scene(n)
+    (Y, units, span, P, radius, _), (cY, cunits, cspan, cP, cradius, cns) = base["rows"], base["cat"]
+    K, i = Y.shape[2], 2
+    ta, L, Tu = span[i, 0], units[i, 0], units[i, 1]
+    hn = (span[i, 1] - ta) / float(K - 1)                               # (cp_state's expressions)
+    k, t = next((k, t) for k in range(K // 2, K - 2) for t in np.nextafter(ta + k * hn, [-np.inf, np.inf, 0.0]).tolist() + [ta + k * hn]
+                if (t - ta) / hn == float(k))
+    p, v = Y[i, :3, k] * L, Y[i, 3:6, k] * (L / Tu)
+    ph = p / np.linalg.norm(p)
+    vh = v - (v @ ph) * ph; vh /= np.linalg.norm(vh)
+    y, (Lo, To) = C.circular_through(p, np.cos(1.0) * vh + np.sin(1.0) * np.cross(ph, vh), t, K, span[i])
+    y[:3] *= Lo / L; y[3:6] *= (Lo / To) / (L / Tu)                     # in the satellite's units
+    y[:3, k] = Y[i, :3, k]
+    rng = np.random.default_rng(77)
+    cat = (np.concatenate([cY, y[None]]), np.concatenate([cunits, units[i:i + 1]]), np.concatenate([cspan, span[i:i + 1]]),
+           np.concatenate([cP, C.random_covariances(rng, 1, K)]), np.append(cradius, 5.0), np.append(cns, K).astype(np.int32))
+    return base["rows"], cat, np.concatenate([base["pairs"], [[i, n, 0.0, t]]])
+
+
+def test_one_encounter_across_calls():
+    """collision_probability, avoidance and avoidance_joint run ONE encounter frame (collision_device.hpp): on the same list, with a
+    target in metres, the miss of the first, D0 of the second and d0 of the third have the same bits -- the pair with a miss of
+    exactly 0 included -- and the speed the first reports is the |w| the second divides by in DT = -sum_m g_m[e_w] . du_m / |w|.
+    That sum is the device's butterfly over the nodes and numpy's here: the two differ by at most (3 K + 2) eps sum |terms| (the bound
+    of a floating-point sum of 3 K terms in any order, and the products), the division adds 2 eps |DT|."""
+    from mpconstellation_amd import _ffi, avoidance, avoidance_joint, collision_probability
+    rows, cat, pairs = scene_with_zero_miss(7)
+    Y, units, span, P, radius, _ = rows
+    cY, cunits, cspan, cP, cradius, cns = cat
+    S, _, K = Y.shape
+    U, consts = np.zeros((S, 3, K)), scale_constants(units[:, 0])
+    cp = collision_probability(pairs, radius, Y, units, span, P, cat=cat)
+    av = avoidance(pairs, 1000.0, Y, U, units, span, consts, cat=(cY, cunits, cspan, cns), return_sensitivities=True)
+    aj = avoidance_joint(pairs, 1000.0, Y, U, units, span, consts, cat=(cY, cunits, cspan, cns))
+    print("miss", cp.miss, "speed", cp.speed, "statuses", cp.status, av.status, aj.row_status, aj.status)
+    assert len(pairs) == 8 and not cp.status.any() and not av.status.any() and not aj.row_status.any()
+    assert cp.miss[-1] == 0.0 and (cp.miss[:-1] > 0.0).all()
+    assert cp.miss.tobytes() == av.out[:, _ffi.AV_D0].tobytes() == aj.d0.tobytes()
+    terms = av.sens[:, 0, 2] * av.du[:, 0]                                # (n, 3, K): the e_w row of g_m times du_m
+    eps = np.finfo(np.float64).eps
+    bound = (3 * K + 2) * eps * np.abs(terms).sum(axis=(1, 2)) / cp.speed + 2 * eps * np.abs(av.dt)
+    worst = np.abs(-terms.sum(axis=(1, 2)) / cp.speed - av.dt) / bound
+    print(f"DT against -sum g_w du / speed: worst difference / bound {worst.max():.3e}")
+    assert av.du.any(axis=(1, 2, 3)).all() and (worst <= 1.0).all()
+
+
 def test_statuses_in_one_call():
     """good, t past a span (BADK), j out of range (BADK), t exactly at the first node (SINGULAR: nothing before it to thrust with),
     already beyond the target (OK, du = 0, D1 = D0): failed rows all NaN, the good rows the bits of a call without the bad ones"""
