@@ -643,6 +643,64 @@ int mpcx_conjunction_pairs_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, i
                                     void *workspace, void *stream);
 
 /*
+ * EVERY close approach of listed pairs.  mpcx_conjunction_pairs gives a pair's global minimum over the grid, which is all there is
+ * in a window shorter than an orbit; over several revolutions two objects on crossing orbits come close about twice per
+ * revolution, and each of those encounters has its own probability and wants its own look at a manoeuvre.  These calls return
+ * them all, below a threshold, as rows (i, j, distance, time) -- the form every call that takes a pairs list takes, each row on
+ * its own with the row's time as the encounter.
+ *
+ * The definition.  For a pair and the grid intervals m = 0 .. M-2 let (q_m, t_m) be the squared distance and the time that
+ * mpcx_conjunction_screen describes for interval m ALONE, with the operands of mpcx_conjunction_pairs (D > 0: d = p_cat - p_sat;
+ * D = 0: d = p_hi - p_lo); q_m = +inf ("absent") where either object has a NaN among the six values of either end.  Interval m
+ * holds an EVENT iff
+ *   q_m < +inf,  q_m < q_m-1 (strictly),  q_m <= q_m+1,
+ * where a neighbour that is absent or does not exist (m = 0, m = M-2) counts as +inf.  A minimum exactly on a grid node is seen by
+ * both adjoining intervals with the same bits; the strict / non-strict pair gives it to the earlier one, once.
+ * The threshold is applied to the events, afterwards, with the screens' comparison: sqrt(q_m) <= threshold.  threshold <= 0 keeps
+ * every event.
+ * An event is an EDGE event when the distance is still falling where the pair's common span ends: interval m has no valid left
+ * neighbour and t_m is the interval's first instant, or no valid right neighbour and t_m is its last instant (those times are
+ * assigned, not computed: the comparison is exact).  Edge events are reported and flagged, not dropped -- the screens list such
+ * minima too.
+ * Two things follow.  The event of a pair with the smallest distance, the earliest of equal ones, taken at threshold <= 0, carries
+ * bit for bit the distance and time mpcx_conjunction_pairs returns for the pair (both order by (q, interval), and the earliest of
+ * the equal smallest is strictly below its left neighbour).  (i, j) and (j, i) give the same events.
+ *
+ * mpcx_conjunction_events: pairs, S, D, M, eph, cat, T0, T1 as mpcx_conjunction_pairs takes them; max_events = E >= 1 slots per pair.
+ *   events [n][E][4]  rows (i, j, distance in m, time in s), i and j as given: the pair's events in ascending interval order, which
+ *                     is ascending time -- the EARLIEST E of them when there are more
+ *   info   [n][E][2]  int32 (grid interval, 1 for an edge event else 0)
+ *   count  [n]        int32: the events found (at or below the threshold), which may exceed E: a list that was cut off shows
+ *   status [n]        MPCX_ST_OK (a pair without a valid interval has count 0); MPCX_ST_BADK for an index that is not a whole number
+ *                     inside its side, or i == j with D = 0: count 0, and the other rows are not affected
+ * The slots from min(count, E) on are written too: (i, j, NaN, NaN) and (-1, 0), so every byte of the outputs is defined.
+ * n = 0 is a successful call that does nothing.  n < 0, S < 1, D < 0, M < 2, T1 <= T0, max_events < 1, a NaN threshold, a missing
+ * array, cat given with D = 0 or missing with D > 0: MPCX_E_BADARG, nothing enqueued.  The host variant takes host pointers; the
+ * _dev variant device pointers throughout, no workspace, and enqueues one kernel on `stream`.
+ *
+ * mpcx_conjunction_events_traj: from trajectories, argument for argument as mpcx_conjunction_pairs_traj; eph_status, cat_status and
+ * the _dev variant's workspace of mpcx_conjunction_events_workspace_bytes(S, D, M) bytes likewise.  Same bits as
+ * mpcx_ephemeris_batch followed by mpcx_conjunction_events.
+ */
+size_t mpcx_conjunction_events_workspace_bytes(int S, int D, int M);
+int mpcx_conjunction_events(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                            double T0, double T1, double threshold, int max_events, double *events, int32_t *info, int32_t *count,
+                            int32_t *status);
+int mpcx_conjunction_events_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                                double T0, double T1, double threshold, int max_events, double *events, int32_t *info,
+                                int32_t *count, int32_t *status, void *stream);
+int mpcx_conjunction_events_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                 const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                 const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                 double threshold, int max_events, double *events, int32_t *info, int32_t *count, int32_t *status,
+                                 int32_t *eph_status, int32_t *cat_status);
+int mpcx_conjunction_events_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                     const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                     const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                     double T1, double threshold, int max_events, double *events, int32_t *info, int32_t *count,
+                                     int32_t *status, int32_t *eph_status, int32_t *cat_status, void *workspace, void *stream);
+
+/*
  * Collision probability of screened pairs.  A miss distance alone says nothing: the two orbit uncertainties decide whether 200 m
  * is an emergency or noise.  Two steps, both on the device: a covariance propagated along every trajectory, and for every row
  * (i, j, distance, time) of a screen's pairs list the short-encounter collision probability in the encounter plane.  The reference

@@ -12,13 +12,15 @@ from .simulator import Simulator, propagate_batch
 from .constellation_mpc import ConstellationMPC
 from .atmosphere import Atmosphere
 from . import conjunction
-from .conjunction import (common_clock, screen, screen_against, screen_pairs, catalogue_trajectories, ConjunctionResult, covariance,
+from .conjunction import (common_clock, screen, screen_against, screen_pairs, screen_events, EncounterEvents, cumulative_probability,
+                          catalogue_trajectories, ConjunctionResult, covariance,
                           collision_probability, catalogue_covariance, CollisionResult, avoidance, AvoidanceResult,
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult)
 
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
            "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC", "Atmosphere",
-           "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "catalogue_trajectories", "ConjunctionResult", "covariance",
+           "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "screen_events", "EncounterEvents",
+           "cumulative_probability", "catalogue_trajectories", "ConjunctionResult", "covariance",
            "collision_probability", "catalogue_covariance", "CollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult"]

@@ -133,6 +133,16 @@ _SIGS = {
                                     + [C.c_int, C.c_double, C.c_double, _dp, _ip, _ip, _ip]),
     "mpcx_conjunction_pairs_traj_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp] * 2
                                         + [C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # every close approach of listed pairs below a threshold (the pairs calls with threshold, max_events and four outputs)
+    "mpcx_conjunction_events_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_conjunction_events": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int,
+                                          _dp, _ip, _ip, _ip]),
+    "mpcx_conjunction_events_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double,
+                                              C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mpcx_conjunction_events_traj": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp] * 2
+                                     + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, _ip, _ip, _ip]),
+    "mpcx_conjunction_events_traj_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp] * 2
+                                         + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # collision probability of screened pairs: covariance along trajectories, then the encounter-plane integral per listed pair
     "mpcx_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mpcx_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),

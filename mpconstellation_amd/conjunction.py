@@ -10,6 +10,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   screen_against the same for a constellation against a catalogue of foreign objects (debris, other operators' satellites): the
                  rectangle satellites x objects, not the square of the union;
   screen_pairs   the closest approach of the pairs of a list alone, with the bits the screens give them;
+  screen_events  EVERY close approach of the listed pairs below a threshold (a window of several revolutions holds about two per
+                 revolution), as rows that every call below takes; cumulative_probability joins their probabilities per pair;
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
@@ -210,6 +212,42 @@ def _screen_call(rows, *, device, slot, out, src, cat, M, T0, T1, thr, max_pairs
     return pairs[:min(n, max_pairs)], n, statuses
 
 
+def _check_list_call(who, pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units, cat_span, cat_ns, M):
+    """the checks screen_pairs and screen_events make of the list, the two sides and the grid -> (pairs, src, cat, M, T0, T1,
+    given_traj); src, cat: each side as (eph,) or (Y, units, span, ns), cat None without a catalogue"""
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    given_eph, given_traj = eph is not None or cat_eph is not None, Y is not None or cat_Y is not None
+    if given_eph == given_traj:
+        raise ValueError(f"{who}: give either eph [, cat_eph], or the trajectories Y, units, span [, cat_Y, cat_units, cat_span] with M")
+    if T0 is None or T1 is None:
+        raise ValueError(f"{who}: T0 and T1 (the common grid's first and last instant, seconds) are required")
+    cat = None
+    if given_eph:
+        if eph is None:
+            raise ValueError(f"{who}: cat_eph needs eph")
+        eph = _check_ephemeris(eph, M)
+        src, M = (eph,), eph.shape[2]
+        if cat_eph is not None:
+            cat_eph = _check_ephemeris(cat_eph, None, "cat_eph", "D")
+            if cat_eph.shape[2] != M:
+                raise ValueError(f"eph has {M} instants but cat_eph {cat_eph.shape[2]}: both must be on the same grid")
+            cat = (cat_eph,)
+    else:
+        if Y is None:
+            raise ValueError(f"{who}: cat_Y needs Y")
+        if M is None:
+            raise ValueError(f"{who}: M (the number of common instants) is required with trajectories")
+        src = _check_trajectories(Y, units, span, ns)
+        if cat_Y is not None:
+            cat = _check_trajectories(cat_Y, cat_units, cat_span, cat_ns, "cat_")
+    M, T0, T1 = _check_grid(M, T0, T1)
+    return pairs, src, cat, M, T0, T1, given_traj
+
+
 def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, *, Y=None, units=None, span=None, ns=None, cat_Y=None,
                  cat_units=None, cat_span=None, cat_ns=None, M=None):
     """The closest approach of the LISTED pairs alone on the common grid linspace(T0, T1, M): n x M work where the screens do
@@ -223,36 +261,8 @@ def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, 
     and time of a pair are bit for bit what screen / screen_against list for it on the same inputs.  An empty list returns empty
     arrays without a library call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices (every device
     holds both sides), written in place, the bits of one device."""
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
-    given_eph, given_traj = eph is not None or cat_eph is not None, Y is not None or cat_Y is not None
-    if given_eph == given_traj:
-        raise ValueError("screen_pairs: give either eph [, cat_eph], or the trajectories Y, units, span [, cat_Y, cat_units, cat_span] with M")
-    if T0 is None or T1 is None:
-        raise ValueError("screen_pairs: T0 and T1 (the common grid's first and last instant, seconds) are required")
-    cat = None
-    if given_eph:
-        if eph is None:
-            raise ValueError("screen_pairs: cat_eph needs eph")
-        eph = _check_ephemeris(eph, M)
-        src, M = (eph,), eph.shape[2]
-        if cat_eph is not None:
-            cat_eph = _check_ephemeris(cat_eph, None, "cat_eph", "D")
-            if cat_eph.shape[2] != M:
-                raise ValueError(f"eph has {M} instants but cat_eph {cat_eph.shape[2]}: both must be on the same grid")
-            cat = (cat_eph,)
-    else:
-        if Y is None:
-            raise ValueError("screen_pairs: cat_Y needs Y")
-        if M is None:
-            raise ValueError("screen_pairs: M (the number of common instants) is required with trajectories")
-        src = _check_trajectories(Y, units, span, ns)
-        if cat_Y is not None:
-            cat = _check_trajectories(cat_Y, cat_units, cat_span, cat_ns, "cat_")
-    M, T0, T1 = _check_grid(M, T0, T1)
+    pairs, src, cat, M, T0, T1, given_traj = _check_list_call("screen_pairs", pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units,
+                                                              cat_span, cat_ns, M)
     n = pairs.shape[0]
     out = dict(out=np.empty((n, 4)), status=np.zeros(n, dtype=np.int32))
     statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
@@ -268,23 +278,104 @@ def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, 
     return (out["out"], out["status"], *statuses) if given_traj else (out["out"], out["status"])
 
 
-def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1):
+def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1, events=None):
     """one block of the list's rows on context (device, slot), into `out` (the block's views); returns the ephemeris statuses
-    [status, cat_status] of the calls from trajectories, None where there is none"""
+    [status, cat_status] of the calls from trajectories, None where there is none.  events = (threshold, max_events): every close
+    approach (mpcx_conjunction_events*) into out's events, info, count and status instead of the closest one into out and status"""
     pairs = _ffi.as_f64(pairs)
     ctx = _ffi.context(device, slot)
     S, D = src[0].shape[0], 0 if cat is None else cat[0].shape[0]
-    tail = (T0, T1, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+    if events is None:
+        name, tail = "mpcx_conjunction_pairs", (T0, T1, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+    else:
+        name, tail = "mpcx_conjunction_events", (T0, T1, *events, _ffi.dptr(out["events"]), _ffi.iptr(out["info"]), _ffi.iptr(out["count"]),
+                                                 _ffi.iptr(out["status"]))
     if len(src) == 1:
-        _ffi.call("mpcx_conjunction_pairs", ctx, len(pairs), _ffi.dptr(pairs), S, D, M, _ffi.dptr(src[0]),
+        _ffi.call(name, ctx, len(pairs), _ffi.dptr(pairs), S, D, M, _ffi.dptr(src[0]),
                   _ffi.dptr_opt(None if cat is None else cat[0]), *tail)
         return [None, None]
     sides = [(N, side[0].shape[2], _ffi.iptr_opt(side[3]), _ffi.dptr(side[0]), _ffi.dptr(side[1]), _ffi.dptr(side[2])) if side is not None
              else (0, 0, None, None, None, None) for N, side in ((S, src), (D, cat))]
     statuses = [np.zeros(S, dtype=np.int32), None if cat is None else np.zeros(D, dtype=np.int32)]
-    _ffi.call("mpcx_conjunction_pairs_traj", ctx, len(pairs), _ffi.dptr(pairs), *sides[0], *sides[1], M, *tail,
-              *[_ffi.iptr_opt(st) for st in statuses])
+    _ffi.call(name + "_traj", ctx, len(pairs), _ffi.dptr(pairs), *sides[0], *sides[1], M, *tail, *[_ffi.iptr_opt(st) for st in statuses])
     return statuses
+
+
+DEFAULT_MAX_EVENTS = 16
+
+
+class EncounterEvents:
+    """Every close approach of the n pairs of a list (screen_events).  Per stored event, list order first, then time: events (n_ev, 4)
+    rows (i, j, distance in m, time in s) -- a valid `pairs` argument for collision_probability, avoidance, avoidance_joint and
+    screen_pairs, which treat every row on its own with the row's time as the encounter --, row (n_ev,) the list row the event
+    belongs to, interval (n_ev,) its grid interval, edge (n_ev,) bool: the distance is still falling where the pair's common
+    span ends.  Per list row: count (n,) the events found, truncated (n,) bool count > max_events (the earliest max_events are
+    stored), status (n,) int32 MPCX_ST_* (9: an index outside its side or i == j; count 0).  eph_status, cat_status: the
+    ephemerides' statuses from trajectories, else None."""
+
+    def __init__(self, events, info, count, status, eph_status=None, cat_status=None):
+        """from the library's padded blocks: events (n, E, 4), info (n, E, 2), count (n,), status (n,)"""
+        events, info, count = np.asarray(events, dtype=np.float64), np.asarray(info, dtype=np.int32), np.asarray(count, dtype=np.int32)
+        if events.ndim != 3 or events.shape[2] != 4 or info.shape != events.shape[:2] + (2,) or count.shape != events.shape[:1]:
+            raise ValueError(f"expected events (n, E, 4), info (n, E, 2) and count (n,), got {events.shape}, {info.shape}, {count.shape}")
+        n, E = events.shape[:2]
+        stored = np.arange(E)[None, :] < np.minimum(count, E)[:, None]   # (n, E): row-major, so list order first, then slot = time
+        self.max_events = E
+        self.events = np.ascontiguousarray(events[stored]).reshape(-1, 4)
+        self.row = np.nonzero(stored)[0]
+        self.interval, self.edge = info[stored][:, 0], info[stored][:, 1] != 0
+        self.count, self.truncated, self.status = count, count > E, np.asarray(status, dtype=np.int32)
+        self.eph_status, self.cat_status = eph_status, cat_status
+
+    def __repr__(self):
+        return f"EncounterEvents(pairs={len(self.count)}, events={len(self.events)} of {int(self.count.sum())})"
+
+
+def screen_events(pairs, T0, T1, threshold=None, max_events=DEFAULT_MAX_EVENTS, eph=None, cat_eph=None, device=0, devices=None, *, Y=None,
+                  units=None, span=None, ns=None, cat_Y=None, cat_units=None, cat_span=None, cat_ns=None, M=None):
+    """EVERY close approach of the listed pairs on the common grid linspace(T0, T1, M) -> EncounterEvents.  screen_pairs returns a
+    pair's global minimum, which is the only one in a window shorter than an orbit; over several revolutions two objects on crossing
+    orbits come close about twice per revolution.  An event is a local minimum of the per-interval closest approach over the grid
+    (include/mpcx.h: mpcx_conjunction_events); threshold (metres; None or <= 0: every event) keeps those at or below it, and at most
+    max_events per pair are stored, the earliest.  pairs and both sides exactly as screen_pairs takes them.  The closest event of
+    a pair carries, bit for bit, screen_pairs' distance and time for it; (i, j) and (j, i) give the same events.  An empty list
+    returns an empty result without a library call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several
+    devices (every device holds both sides), written in place, the bits of one device."""
+    pairs, src, cat, M, T0, T1, given_traj = _check_list_call("screen_events", pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units,
+                                                              cat_span, cat_ns, M)
+    if int(max_events) != max_events or max_events < 1:
+        raise ValueError(f"max_events: need an integer >= 1, got {max_events}")
+    thr = 0.0 if threshold is None else float(threshold)
+    if not thr == thr:
+        raise ValueError("threshold is NaN")
+    n, E = pairs.shape[0], int(max_events)
+    out = dict(events=np.empty((n, E, 4)), info=np.empty((n, E, 2), dtype=np.int32), count=np.zeros(n, dtype=np.int32),
+               status=np.zeros(n, dtype=np.int32))
+    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
+    if n:
+        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, events=(thr, E))
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    return EncounterEvents(out["events"], out["info"], out["count"], out["status"], *statuses)
+
+
+def cumulative_probability(events, pc):
+    """The probability of at least one collision per list row of `events` (EncounterEvents): 1 - prod (1 - pc_e) over the row's
+    events, taken as -expm1(sum log1p(-pc_e)) so that many small probabilities add up without cancellation.  pc (n_ev,): the
+    events' probabilities, row for row of events.events (collision_probability(events.events, ...).pc, or that CollisionResult).
+    A row with an event whose pc is NaN is NaN; a row without events is 0.  The encounters are taken as independent."""
+    pc = np.asarray(pc.pc if isinstance(pc, CollisionResult) else pc, dtype=np.float64)
+    if pc.shape != events.row.shape:
+        raise ValueError(f"pc: expected ({len(events.row)},) probabilities, one per stored event, got {pc.shape}")
+    total = np.zeros(len(events.count))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        np.add.at(total, events.row, np.log1p(-pc))
+        return 0.0 - np.expm1(total)
 
 
 def catalogue_trajectories(position_m, velocity_m_s, T0, T1, n, include_J2=True, device=0, devices=None):

@@ -370,6 +370,36 @@ class ConstellationMPC:
             P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
         return w, screened, P, cat, model, where
 
+    def encounters(self, threshold_m, P0=None, radius_m=None, q=None, samples_per_node=4, max_pairs=None, max_events=16, catalogue=None):
+        """EVERY close approach of the last plan's listed pairs, not only the closest -> (ConjunctionResult, EncounterEvents).  The
+        plan is screened at threshold_m as `avoidance` screens it (screen(what='plan'); screen_against with a catalogue), and
+        conjunction.screen_events returns every encounter of the listed pairs at or below the same threshold, at most max_events
+        per pair: a plan of several revolutions holds about two per revolution for crossing orbits.  With P0 ((6, 6) or (S, 6, 6);
+        m, m/s) and radius_m (a scalar or (S,)) it returns (ConjunctionResult, EncounterEvents, CollisionResult, cumulative): the
+        plan's covariance is propagated as collision_probability propagates it, every event gets its own probability
+        (conjunction.collision_probability over events.events) and every listed pair the probability of at least one collision
+        over its events (conjunction.cumulative_probability, (n,)).  catalogue = (Y, units, span) or (Y, units, span, ns) for the
+        events alone; (Y, units, span, P, radius) or (Y, units, span, P, radius, ns) with P0 and radius_m, as collision_probability
+        takes it.  The plan only, as there."""
+        from . import conjunction as cj
+        if (P0 is None) != (radius_m is None):
+            raise ValueError("P0 and radius_m come together (probabilities) or not at all (the events alone)")
+        cat, cat_kw, trajectories = None, {}, None
+        if catalogue is not None:
+            cat = tuple(catalogue)
+            if len(cat) not in ((5, 6) if P0 is not None else (3, 4)):
+                raise ValueError("catalogue: expected (Y, units, span, P, radius[, ns]) with P0 and radius_m, (Y, units, span[, ns]) "
+                                 f"without, got {len(cat)} items")
+            cat_ns = cat[-1] if len(cat) in (4, 6) else None
+            trajectories = cat[:3] if cat_ns is None else cat[:3] + (cat_ns,)
+            cat_kw = dict(cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2], cat_ns=cat_ns)
+        w, screened, P, _, _, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, trajectories, P0, q)
+        events = cj.screen_events(screened, threshold=threshold_m, max_events=max_events, **w, **cat_kw, **where)
+        if P0 is None:
+            return screened, events
+        col = cj.collision_probability(events.events, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
+        return screened, events, col, cj.cumulative_probability(events, col.pc)
+
     def avoidance(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i"):
         """Avoidance manoeuvres for the last plan's close approaches -> (ConjunctionResult, AvoidanceResult).  The plan is screened
         at threshold_m as collision_probability screens it (screen(what='plan'); screen_against when catalogue = (Y, units, span),

@@ -8,7 +8,9 @@
 //                      minimum, then three Newton steps on d . d' -- reduced to one (distance, partner, time) per row and, with a
 //                      threshold, to a list of the pairs that come closer than it;
 //   pairs_kernel       the same closest approach for the pairs of a LIST (a screen's, flown again after a manoeuvre): one wave
-//                      per pair, n x M work, the bits the screens give the pair.
+//                      per pair, n x M work, the bits the screens give the pair;
+//   events_kernel      EVERY close approach of the listed pairs: the local minima of the per-interval distance over the grid, one
+//                      wave per pair, in the pairs-row form (i, j, distance, time) that the rest of the chain takes.
 // Two screens launch screen_kernel.  All pairs of one constellation (SELF): rows and columns are the same S satellites, the full square of
 // ordered pairs (i, j != i) is computed, the list holds the pairs i < j.  A constellation against a catalogue of foreign objects
 // (cross): rows are the S satellites, columns the D objects, the rectangle S x D is computed and not the square (S + D)^2 of the
@@ -289,6 +291,29 @@ __device__ __forceinline__ void cj_end(const double *e, int M, int m, double (&p
     for (int c = 0; c < 3; ++c) { p[c] = nan ? cj_nan() : p[c]; v[c] = nan ? cj_nan() : v[c]; }
 }
 
+// Grid interval m of a listed pair through cj_interval into (best, tbest).  er, ec: the rows of the ephemerides of object i (the
+// row) and object j (the column); the row / column roles and `up` are screen_kernel's, so the interval's (q, t) are the screen's bits.
+__device__ __forceinline__ void cj_pair_interval(const PairsArgs &a, const double *er, const double *ec, bool up, int m, double &best,
+                                                 double &tbest)
+{
+    double p0[3], v0[3], p1[3], v1[3], c0[6], c1[6];
+    {
+        double cp[3], cv[3];
+        cj_end(er, a.M, m, p0, v0); cj_end(er, a.M, m + 1, p1, v1);
+        cj_end(ec, a.M, m, cp, cv);
+        for (int c = 0; c < 3; ++c) { c0[c] = cp[c]; c0[3 + c] = cv[c]; }
+        cj_end(ec, a.M, m + 1, cp, cv);
+        for (int c = 0; c < 3; ++c) { c1[c] = cp[c]; c1[3 + c] = cv[c]; }
+    }
+    const double t0 = cj_time(m, a.M, a.T0, a.T1, a.h), t1 = cj_time(m + 1, a.M, a.T0, a.T1, a.h);
+    double d0[3], d1[3];
+    for (int c = 0; c < 3; ++c) {
+        d0[c] = up ? c0[c] - p0[c] : p0[c] - c0[c];
+        d1[c] = up ? c1[c] - p1[c] : p1[c] - c1[c];
+    }
+    cj_interval(d0, d1, c0 + 3, c1 + 3, v0, v1, up, a.h, t0, t1, best, tbest);
+}
+
 // The closest approach of LISTED pairs: n x M work where the screens do S^2 x M.  One wave per pair (blockIdx.x = the list's row);
 // lane l takes the grid intervals l, l + 64, ... in ascending order through cj_interval, with the row / column roles and `up` as
 // screen_kernel forms them (row = i, column = j; the difference is (higher index) - (lower index), against a catalogue column - row),
@@ -312,23 +337,8 @@ __global__ __launch_bounds__(64) void pairs_kernel(PairsArgs a)
     double best = cj_inf(), tbest = cj_nan();
     int mbest = 0x7fffffff;
     for (int m = lane; m < a.M - 1; m += 64) {
-        double p0[3], v0[3], p1[3], v1[3], c0[6], c1[6];
-        {
-            double cp[3], cv[3];
-            cj_end(er, a.M, m, p0, v0); cj_end(er, a.M, m + 1, p1, v1);
-            cj_end(ec, a.M, m, cp, cv);
-            for (int c = 0; c < 3; ++c) { c0[c] = cp[c]; c0[3 + c] = cv[c]; }
-            cj_end(ec, a.M, m + 1, cp, cv);
-            for (int c = 0; c < 3; ++c) { c1[c] = cp[c]; c1[3 + c] = cv[c]; }
-        }
-        const double t0 = cj_time(m, a.M, a.T0, a.T1, a.h), t1 = cj_time(m + 1, a.M, a.T0, a.T1, a.h);
-        double d0[3], d1[3];
-        for (int c = 0; c < 3; ++c) {
-            d0[c] = up ? c0[c] - p0[c] : p0[c] - c0[c];
-            d1[c] = up ? c1[c] - p1[c] : p1[c] - c1[c];
-        }
         const double before = best;
-        cj_interval(d0, d1, c0 + 3, c1 + 3, v0, v1, up, a.h, t0, t1, best, tbest);
+        cj_pair_interval(a, er, ec, up, m, best, tbest);
         if (best < before) mbest = m;
     }
     for (int w = 32; w >= 1; w >>= 1) {
@@ -342,6 +352,80 @@ __global__ __launch_bounds__(64) void pairs_kernel(PairsArgs a)
         o[3] = best < cj_inf() ? tbest : cj_nan();
         a.status[r] = MPCX_ST_OK;
     }
+}
+
+struct EventsArgs {
+    PairsArgs p;                      // p.out: events [n][E][4]
+    double thr;                       // metres; <= 0: every event
+    int E;                            // slots per pair
+    int32_t *info, *count;            // [n][E][2] = (interval, edge), [n]
+};
+
+// EVERY close approach of listed pairs (include/mpcx.h: mpcx_conjunction_events).  With (q_m, t_m) what cj_interval gives interval
+// m alone (best = +inf; q_m = +inf where an end is invalid), interval m holds an event iff q_m < +inf, q_m < q_m-1 and q_m <= q_m+1,
+// a neighbour that is absent or does not exist counting as +inf: the local minima of the per-interval distance, a minimum on a
+// grid node (the same bits in both adjoining intervals) given to the earlier interval once.  One wave per pair as in pairs_kernel,
+// but the wave walks the grid in chunks of 64 CONSECUTIVE intervals, lane l taking interval 64 c + l, so that the neighbours are the
+// lanes beside it: q_m-1 comes from the lane below (lane 0: `carry`, the previous chunk's lane 63), q_m+1 from the lane above
+// (lane 63: the next chunk's lane 0).  For that last one chunk c - 1 is decided after chunk c has been computed -- a one-chunk
+// software pipeline with the pending (q, t) in four registers; the pass after the last chunk decides it against "absent", and the
+// first pass decides a pending chunk that is all absent and so holds no event (no special case, and no peeled copy of the loop).  The
+// threshold is applied to the events, sqrt(q) <= thr as the screens compare.  The event lanes of a chunk take consecutive slots
+// behind the running count (a ballot and the population count of the lanes below) and store their own rows, so the events leave
+// in ascending interval order and the first E of them are kept; the slots behind them are filled with (i, j, NaN, NaN), (-1, 0).
+// No LDS, no atomics: nothing depends on anything but the pair.  Compiled for exactly six waves per SIMD, pairs_kernel's occupancy:
+// left alone the compiler takes 87 VGPRs (five waves) and spills 12 SGPRs into the lanes of one of them, and with a minimum of six
+// alone (__launch_bounds__(64, 6)) it spills to scratch; aimed at six it schedules for 80 VGPRs and needs neither
+// (profiles/conjunction_events.txt).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void events_kernel(EventsArgs e)
+{
+    const PairsArgs &a = e.p;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const bool cross = a.D > 0;
+    const double xi = a.pairs[(size_t)r * 4], xj = a.pairs[(size_t)r * 4 + 1];
+    const int i = cj_index(xi, a.S), j = cj_index(xj, cross ? a.D : a.S);
+    double *ev = a.out + (size_t)r * e.E * 4;
+    int32_t *inf = e.info + (size_t)r * e.E * 2;
+    const bool bad = i < 0 || j < 0 || (!cross && i == j);           // (the whole wave: it reads nothing of the ephemerides)
+    int found = 0;
+    if (!bad) {
+        const bool up = cross || j > i;                              // the column is the higher index: column - row
+        const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
+        const int nchunk = (a.M - 1 + 63) / 64;
+        double qp = cj_inf(), tp = cj_nan();                         // the pending chunk's interval of this lane
+        double carry = cj_inf();                                     // q of the interval before the pending chunk's first
+        for (int c = 0; c <= nchunk; ++c) {
+            const int m = 64 * c + lane;
+            double q = cj_inf(), t = cj_nan();
+            if (m < a.M - 1) cj_pair_interval(a, er, ec, up, m, q, t);
+            const int mp = m - 64;
+            double left = __shfl_up(qp, 1), right = __shfl_down(qp, 1);
+            const double next = __shfl(q, 0);
+            if (lane == 0) left = carry;
+            if (lane == 63) right = next;
+            const double d = sqrt(qp);
+            const bool event = qp < cj_inf() && qp < left && qp <= right && (!(e.thr > 0.0) || d <= e.thr);
+            const unsigned long long lanes = __ballot(event);
+            const int slot = found + __popcll(lanes & ((1ULL << lane) - 1ULL));
+            if (event && slot < e.E) {
+                // still closing where the pair's common span ends: the time is an assigned end of the interval, so == is exact
+                const bool edge = (!(left < cj_inf()) && tp == cj_time(mp, a.M, a.T0, a.T1, a.h)) ||
+                                  (!(right < cj_inf()) && tp == cj_time(mp + 1, a.M, a.T0, a.T1, a.h));
+                double *o = ev + (size_t)slot * 4;
+                o[0] = xi; o[1] = xj; o[2] = d; o[3] = tp;
+                inf[2 * slot] = mp; inf[2 * slot + 1] = edge ? 1 : 0;
+            }
+            found += __popcll(lanes);
+            carry = __shfl(qp, 63);
+            qp = q; tp = t;
+        }
+    }
+    for (int s = (found < e.E ? found : e.E) + lane; s < e.E; s += 64) {
+        double *o = ev + (size_t)s * 4;
+        o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan();
+        inf[2 * s] = -1; inf[2 * s + 1] = 0;
+    }
+    if (lane == 0) { e.count[r] = found; a.status[r] = bad ? MPCX_ST_BADK : MPCX_ST_OK; }
 }
 
 // The two screens as the host sees them: the name in the messages, and whether the columns are the rows' own constellation
@@ -642,18 +726,48 @@ extern "C" int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, c
     return screen_from_device(ctx, ar, CROSS, c, ws.eph, ws.cat, dws);
 }
 
-// ---- listed pairs
+// ---- listed pairs: the closest approach of each (mpcx_conjunction_pairs*), or every close approach (mpcx_conjunction_events*)
 namespace mpcx {
 
+// what every list entry point is given behind its list and its two sides; events: every close approach below the threshold
+// (events_kernel, max_events slots per pair) instead of the closest one (pairs_kernel)
 struct PairsCall {
     int n, S, D, M;
     double T0, T1;
+    bool events;
+    double threshold;
+    int max_events;
+    size_t rows() const { return (size_t)n * (events ? (size_t)max_events : 1); }       // rows of four doubles in the first output
 };
+
+// the outputs: rows = out [n][4] and status [n]; the events calls have rows = events [n][E][4], info [n][E][2] and count [n] too
+struct PairsOut {
+    double *rows;
+    int32_t *status, *info, *count;
+    bool complete(const PairsCall &c) const { return rows && status && (!c.events || (info && count)); }
+};
+
+// the names in the messages
+struct PairsNames {
+    const char *call, *traj, *outs, *outs_list;
+};
+constexpr PairsNames PAIRS{"conjunction_pairs", "conjunction_pairs_traj", "out and status", "out, status"};
+constexpr PairsNames EVENTS{"conjunction_events", "conjunction_events_traj", "events, info, count and status", "events, info, count, status"};
 
 static int pairs_check(mpcx_ctx *ctx, const char *name, const PairsCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.D < 0 || c.M < 2 || !(c.T1 > c.T0)) return screen_fail(ctx, name, "need n>=1, S>=1, D>=0, M>=2, T1>T0");
+    if (!c.events && c.n < 1) return screen_fail(ctx, name, "need n>=1, S>=1, D>=0, M>=2, T1>T0");
+    if (c.n < 0 || c.S < 1 || c.D < 0 || c.M < 2 || !(c.T1 > c.T0)) return screen_fail(ctx, name, "need n>=0, S>=1, D>=0, M>=2, T1>T0");
+    if (c.events && (c.max_events < 1 || !(c.threshold == c.threshold)))
+        return screen_fail(ctx, name, "need max_events>=1 and a threshold that is not NaN");
     return MPCX_OK;
+}
+
+static int pairs_missing(mpcx_ctx *ctx, const char *name, const char *fmt, const char *outs)
+{
+    char what[160];
+    snprintf(what, sizeof what, fmt, outs);
+    return screen_fail(ctx, name, what);
 }
 
 // the two ephemerides of the _traj calls: [eph S*6*M][cat D*6*M]
@@ -670,15 +784,122 @@ struct PairsWorkspace {
     }
 };
 
-// pairs_kernel on `st`, everything in device memory
-static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs, const double *eph, const double *cat, double *out,
-                         int32_t *status, hipStream_t st)
+// pairs_kernel or events_kernel on `st`, everything in device memory
+static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs, const double *eph, const double *cat, const PairsOut &o,
+                         hipStream_t st)
 {
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    const PairsArgs a{c.n, c.S, c.D, c.M, c.T0, c.T1, (c.T1 - c.T0) / (double)(c.M - 1), pairs, eph, c.D > 0 ? cat : eph, out, status};
-    hipLaunchKernelGGL(pairs_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
+    const PairsArgs a{c.n, c.S, c.D, c.M, c.T0, c.T1, (c.T1 - c.T0) / (double)(c.M - 1), pairs, eph, c.D > 0 ? cat : eph, o.rows, o.status};
+    if (c.events) {
+        const EventsArgs e{a, c.threshold > 0.0 ? c.threshold : 0.0, c.max_events, o.info, o.count};
+        hipLaunchKernelGGL(events_kernel, dim3((unsigned)c.n), dim3(64), 0, st, e);
+    } else
+        hipLaunchKernelGGL(pairs_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
+}
+
+// device arrays for the outputs of a host-pointer call, and their way back
+static PairsOut pairs_out_alloc(DeviceArena &ar, const PairsCall &c)
+{
+    PairsOut d{ar.alloc<double>(c.rows() * 4), ar.alloc<int32_t>(c.n), nullptr, nullptr};
+    if (c.events) { d.info = ar.alloc<int32_t>(c.rows() * 2); d.count = ar.alloc<int32_t>(c.n); }
+    return d;
+}
+
+static void pairs_out_download(DeviceArena &ar, const PairsCall &c, const PairsOut &o, const PairsOut &d)
+{
+    ar.download(o.rows, d.rows, c.rows() * 4);
+    ar.download(o.status, d.status, c.n);
+    if (c.events) { ar.download(o.info, d.info, c.rows() * 2); ar.download(o.count, d.count, c.n); }
+}
+
+// the four forms of a list call behind their extern "C" names (n = 0 passes pairs_check for the events calls only: nothing to do)
+static int pairs_dev(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, const double *pairs, const double *eph, const double *cat,
+                     const PairsOut &o, void *stream)
+{
+    if (int rc = pairs_check(ctx, nm.call, c)) return rc;
+    if (c.n == 0) return MPCX_OK;
+    if (!pairs || !eph || !o.complete(c) || (c.D > 0) != (cat != nullptr))
+        return pairs_missing(ctx, nm.call, "pairs, eph, %s are required, and cat exactly when D > 0", nm.outs);
+    return pairs_enqueue(ctx, c, pairs, eph, cat, o, (hipStream_t)stream);
+}
+
+static int pairs_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, const double *pairs, const double *eph, const double *cat,
+                      const PairsOut &o)
+{
+    if (int rc = pairs_check(ctx, nm.call, c)) return rc;
+    if (c.n == 0) return MPCX_OK;
+    if (!pairs || !eph || !o.complete(c) || (c.D > 0) != (cat != nullptr))
+        return pairs_missing(ctx, nm.call, "pairs, eph, %s are required, and cat exactly when D > 0", nm.outs);
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    double *dp = ar.upload(pairs, (size_t)c.n * 4), *de = ar.upload(eph, (size_t)c.S * 6 * c.M);
+    double *dc = c.D > 0 ? ar.upload(cat, (size_t)c.D * 6 * c.M) : nullptr;
+    const PairsOut d = pairs_out_alloc(ar, c);
+    if (ar.failed()) return ar.code();
+    if (int rc = pairs_enqueue(ctx, c, dp, de, dc, d, ctx->stream)) return rc;
+    pairs_out_download(ar, c, o, d);
+    return ar.finish();
+}
+
+// one side's trajectories as mpcx_ephemeris_batch takes them
+struct PairsSide {
+    int n;
+    const int32_t *ns;
+    const double *Y, *units, *span;
+};
+
+static int pairs_traj_dev(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, const double *pairs, const PairsSide &sat,
+                          const PairsSide &cat, const PairsOut &o, int32_t *eph_status, int32_t *cat_status, void *workspace, void *stream)
+{
+    if (int rc = pairs_check(ctx, nm.traj, c)) return rc;
+    if (c.n == 0) return MPCX_OK;
+    if (sat.n < 1 || (c.D > 0 && cat.n < 1)) return screen_fail(ctx, nm.traj, "need n>=1 nodes on each side");
+    if (!pairs || !sat.Y || !sat.units || !sat.span || !o.complete(c) || !eph_status || !workspace)
+        return pairs_missing(ctx, nm.traj, "pairs, Y, units, span, %s, eph_status and workspace are required", nm.outs_list);
+    if (c.D > 0 ? !cat.Y || !cat.units || !cat.span || !cat_status : cat.Y != nullptr)
+        return screen_fail(ctx, nm.traj, "cat_Y, cat_units, cat_span and cat_status are required exactly when D > 0");
+    const PairsWorkspace ws(workspace, c.S, c.D, c.M);
+    if (int rc = mpcx_ephemeris_batch_dev(ctx, c.S, sat.n, sat.ns, sat.Y, sat.units, sat.span, c.M, c.T0, c.T1, ws.eph, eph_status, stream)) return rc;
+    if (c.D > 0)
+        if (int rc = mpcx_ephemeris_batch_dev(ctx, c.D, cat.n, cat.ns, cat.Y, cat.units, cat.span, c.M, c.T0, c.T1, ws.cat, cat_status, stream))
+            return rc;
+    return pairs_enqueue(ctx, c, pairs, ws.eph, ws.cat, o, (hipStream_t)stream);
+}
+
+static int pairs_traj_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, const double *pairs, const PairsSide &sat,
+                           const PairsSide &cat, const PairsOut &o, int32_t *eph_status, int32_t *cat_status)
+{
+    if (int rc = pairs_check(ctx, nm.traj, c)) return rc;
+    if (c.n == 0) return MPCX_OK;
+    if (sat.n < 1 || (c.D > 0 && cat.n < 1)) return screen_fail(ctx, nm.traj, "need n>=1 nodes on each side");
+    if (!pairs || !sat.Y || !sat.units || !sat.span || !o.complete(c))
+        return pairs_missing(ctx, nm.traj, "pairs, Y, units, span, %s are required", nm.outs);
+    if (c.D > 0 ? !cat.Y || !cat.units || !cat.span : cat.Y != nullptr)
+        return screen_fail(ctx, nm.traj, "cat_Y, cat_units and cat_span are required exactly when D > 0");
+    MPCX_HIP(ctx, hipSetDevice(ctx->device));
+    DeviceArena ar(ctx);
+    const int S = c.S, D = c.D;
+    double *dp = ar.upload(pairs, (size_t)c.n * 4);
+    PairsSide ds{sat.n, sat.ns ? ar.upload(sat.ns, S) : nullptr, ar.upload(sat.Y, (size_t)S * 7 * sat.n), ar.upload(sat.units, (size_t)S * 2),
+                 ar.upload(sat.span, (size_t)S * 2)};
+    PairsSide dc{cat.n, nullptr, nullptr, nullptr, nullptr};
+    int32_t *cst = nullptr;
+    if (D > 0) {
+        dc = PairsSide{cat.n, cat.ns ? ar.upload(cat.ns, D) : nullptr, ar.upload(cat.Y, (size_t)D * 7 * cat.n), ar.upload(cat.units, (size_t)D * 2),
+                       ar.upload(cat.span, (size_t)D * 2)};
+        cst = ar.alloc<int32_t>(D);
+    }
+    int32_t *est = ar.alloc<int32_t>(S);
+    const PairsOut d = pairs_out_alloc(ar, c);
+    char *dws = ar.alloc<char>(PairsWorkspace(nullptr, S, D, c.M).bytes);                // neither ephemeris leaves HBM
+    if (ar.failed()) return ar.code();
+    if (int rc = pairs_traj_dev(ctx, nm, c, dp, ds, dc, d, est, cst, dws, ctx->stream)) return rc;
+    pairs_out_download(ar, c, o, d);
+    if (eph_status) ar.download(eph_status, est, S);
+    if (D > 0 && cat_status) ar.download(cat_status, cst, D);
+    return ar.finish();
 }
 
 }  // namespace mpcx
@@ -693,32 +914,14 @@ extern "C" int mpcx_conjunction_pairs_dev(mpcx_ctx *ctx, int n, const double *pa
                                           const double *cat, double T0, double T1, double *out, int32_t *status, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const PairsCall c{n, S, D, M, T0, T1};
-    if (int rc = pairs_check(ctx, "conjunction_pairs", c)) return rc;
-    if (!pairs || !eph || !out || !status || (D > 0) != (cat != nullptr))
-        return screen_fail(ctx, "conjunction_pairs", "pairs, eph, out and status are required, and cat exactly when D > 0");
-    return pairs_enqueue(ctx, c, pairs, eph, cat, out, status, (hipStream_t)stream);
+    return pairs_dev(ctx, PAIRS, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0}, pairs, eph, cat, PairsOut{out, status, nullptr, nullptr}, stream);
 }
 
 extern "C" int mpcx_conjunction_pairs(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
                                       double T0, double T1, double *out, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const PairsCall c{n, S, D, M, T0, T1};
-    if (int rc = pairs_check(ctx, "conjunction_pairs", c)) return rc;
-    if (!pairs || !eph || !out || !status || (D > 0) != (cat != nullptr))
-        return screen_fail(ctx, "conjunction_pairs", "pairs, eph, out and status are required, and cat exactly when D > 0");
-    MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    DeviceArena ar(ctx);
-    double *dp = ar.upload(pairs, (size_t)n * 4), *de = ar.upload(eph, (size_t)S * 6 * M);
-    double *dc = D > 0 ? ar.upload(cat, (size_t)D * 6 * M) : nullptr;
-    double *dout = ar.alloc<double>((size_t)n * 4);
-    int32_t *dst = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    if (int rc = pairs_enqueue(ctx, c, dp, de, dc, dout, dst, ctx->stream)) return rc;
-    ar.download(out, dout, (size_t)n * 4);
-    ar.download(status, dst, n);
-    return ar.finish();
+    return pairs_host(ctx, PAIRS, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0}, pairs, eph, cat, PairsOut{out, status, nullptr, nullptr});
 }
 
 extern "C" int mpcx_conjunction_pairs_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
@@ -728,18 +931,9 @@ extern "C" int mpcx_conjunction_pairs_traj_dev(mpcx_ctx *ctx, int n, const doubl
                                                void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const PairsCall c{n, S, D, M, T0, T1};
-    if (int rc = pairs_check(ctx, "conjunction_pairs_traj", c)) return rc;
-    if (nn < 1 || (D > 0 && cat_n < 1)) return screen_fail(ctx, "conjunction_pairs_traj", "need n>=1 nodes on each side");
-    if (!pairs || !Y || !units || !span || !out || !status || !eph_status || !workspace)
-        return screen_fail(ctx, "conjunction_pairs_traj", "pairs, Y, units, span, out, status, eph_status and workspace are required");
-    if (D > 0 ? !cat_Y || !cat_units || !cat_span || !cat_status : cat_Y != nullptr)
-        return screen_fail(ctx, "conjunction_pairs_traj", "cat_Y, cat_units, cat_span and cat_status are required exactly when D > 0");
-    const PairsWorkspace ws(workspace, S, D, M);
-    if (int rc = mpcx_ephemeris_batch_dev(ctx, S, nn, ns, Y, units, span, M, T0, T1, ws.eph, eph_status, stream)) return rc;
-    if (D > 0)
-        if (int rc = mpcx_ephemeris_batch_dev(ctx, D, cat_n, cat_ns, cat_Y, cat_units, cat_span, M, T0, T1, ws.cat, cat_status, stream)) return rc;
-    return pairs_enqueue(ctx, c, pairs, ws.eph, ws.cat, out, status, (hipStream_t)stream);
+    return pairs_traj_dev(ctx, PAIRS, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0}, pairs, PairsSide{nn, ns, Y, units, span},
+                          PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{out, status, nullptr, nullptr}, eph_status, cat_status,
+                          workspace, stream);
 }
 
 extern "C" int mpcx_conjunction_pairs_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
@@ -748,35 +942,51 @@ extern "C" int mpcx_conjunction_pairs_traj(mpcx_ctx *ctx, int n, const double *p
                                            double *out, int32_t *status, int32_t *eph_status, int32_t *cat_status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const PairsCall c{n, S, D, M, T0, T1};
-    if (int rc = pairs_check(ctx, "conjunction_pairs_traj", c)) return rc;
-    if (nn < 1 || (D > 0 && cat_n < 1)) return screen_fail(ctx, "conjunction_pairs_traj", "need n>=1 nodes on each side");
-    if (!pairs || !Y || !units || !span || !out || !status)
-        return screen_fail(ctx, "conjunction_pairs_traj", "pairs, Y, units, span, out and status are required");
-    if (D > 0 ? !cat_Y || !cat_units || !cat_span : cat_Y != nullptr)
-        return screen_fail(ctx, "conjunction_pairs_traj", "cat_Y, cat_units and cat_span are required exactly when D > 0");
-    MPCX_HIP(ctx, hipSetDevice(ctx->device));
-    DeviceArena ar(ctx);
-    double *dp = ar.upload(pairs, (size_t)n * 4);
-    double *dY = ar.upload(Y, (size_t)S * 7 * nn), *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2);
-    int32_t *dns = ns ? ar.upload(ns, S) : nullptr;
-    double *cY = nullptr, *cu = nullptr, *csp = nullptr;
-    int32_t *cns = nullptr, *cst = nullptr;
-    if (D > 0) {
-        cY = ar.upload(cat_Y, (size_t)D * 7 * cat_n); cu = ar.upload(cat_units, (size_t)D * 2); csp = ar.upload(cat_span, (size_t)D * 2);
-        cns = cat_ns ? ar.upload(cat_ns, D) : nullptr;
-        cst = ar.alloc<int32_t>(D);
-    }
-    int32_t *est = ar.alloc<int32_t>(S), *dst = ar.alloc<int32_t>(n);
-    double *dout = ar.alloc<double>((size_t)n * 4);
-    char *dws = ar.alloc<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));      // neither ephemeris leaves HBM
-    if (ar.failed()) return ar.code();
-    if (int rc = mpcx_conjunction_pairs_traj_dev(ctx, n, dp, S, nn, dns, dY, du, dsp, D, cat_n, cns, cY, cu, csp, M, T0, T1, dout, dst, est, cst,
-                                                 dws, ctx->stream))
-        return rc;
-    ar.download(out, dout, (size_t)n * 4);
-    ar.download(status, dst, n);
-    if (eph_status) ar.download(eph_status, est, S);
-    if (D > 0 && cat_status) ar.download(cat_status, cst, D);
-    return ar.finish();
+    return pairs_traj_host(ctx, PAIRS, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0}, pairs, PairsSide{nn, ns, Y, units, span},
+                           PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{out, status, nullptr, nullptr}, eph_status, cat_status);
+}
+
+// ---- every close approach of the listed pairs: the same four forms on events_kernel.  An empty list (n = 0) is a successful call
+// that does nothing: a screen that lists no pair is no error
+
+extern "C" size_t mpcx_conjunction_events_workspace_bytes(int S, int D, int M) { return mpcx_conjunction_pairs_workspace_bytes(S, D, M); }
+
+extern "C" int mpcx_conjunction_events_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph,
+                                           const double *cat, double T0, double T1, double threshold, int max_events, double *events,
+                                           int32_t *info, int32_t *count, int32_t *status, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_dev(ctx, EVENTS, PairsCall{n, S, D, M, T0, T1, true, threshold, max_events}, pairs, eph, cat, PairsOut{events, status, info, count},
+                     stream);
+}
+
+extern "C" int mpcx_conjunction_events(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                                       double T0, double T1, double threshold, int max_events, double *events, int32_t *info,
+                                       int32_t *count, int32_t *status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_host(ctx, EVENTS, PairsCall{n, S, D, M, T0, T1, true, threshold, max_events}, pairs, eph, cat, PairsOut{events, status, info, count});
+}
+
+extern "C" int mpcx_conjunction_events_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                                const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                                const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                                double T1, double threshold, int max_events, double *events, int32_t *info, int32_t *count,
+                                                int32_t *status, int32_t *eph_status, int32_t *cat_status, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_traj_dev(ctx, EVENTS, PairsCall{n, S, D, M, T0, T1, true, threshold, max_events}, pairs, PairsSide{nn, ns, Y, units, span},
+                          PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{events, status, info, count}, eph_status, cat_status,
+                          workspace, stream);
+}
+
+extern "C" int mpcx_conjunction_events_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                            const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                            const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                            double threshold, int max_events, double *events, int32_t *info, int32_t *count,
+                                            int32_t *status, int32_t *eph_status, int32_t *cat_status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_traj_host(ctx, EVENTS, PairsCall{n, S, D, M, T0, T1, true, threshold, max_events}, pairs, PairsSide{nn, ns, Y, units, span},
+                           PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{events, status, info, count}, eph_status, cat_status);
 }
