@@ -701,6 +701,52 @@ int mpcx_conjunction_events_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, 
                                      int32_t *status, int32_t *eph_status, int32_t *cat_status, void *workspace, void *stream);
 
 /*
+ * The close approach of a listed row NEAREST THE ROW'S OWN TIME: an encounter followed through re-screens.  mpcx_conjunction_pairs
+ * returns a pair's global minimum, so after a manoeuvre every row of a pair that mpcx_conjunction_events listed several times reads
+ * the same encounter; these calls return, for every row, the encounter the row was listed for.
+ *
+ * The definition.  Rows are (i, j, -, t_row) on the grid linspace(T0, T1, M); columns 0, 1 and 3 are read.  An event is exactly
+ * mpcx_conjunction_events' event WITHOUT a threshold (the caller needs the distance of an encounter that a manoeuvre has opened
+ * beyond any): interval m holds one iff q_m < +inf, q_m < q_m-1 and q_m <= q_m+1, an absent neighbour counting as +inf, with (q_m,
+ * t_m) of interval m alone and the operands of mpcx_conjunction_pairs.  The row's answer is the event that minimises the key
+ * (|t_m - t_row|, m) -- a total order: of two events equally far from t_row the one in the earlier interval.  max_shift (seconds)
+ * > 0 admits only events with |t_m - t_row| <= max_shift; max_shift <= 0 is unlimited.
+ *   out    [n][4]  (i, j, distance in m, time in s) in list order, i and j as given
+ *   info   [n][2]  int32 (grid interval, 1 for an edge event else 0), mpcx_conjunction_events' edge rule; may be NULL
+ *   status [n]     MPCX_ST_OK, or MPCX_ST_BADK
+ * A row with no event, or none within max_shift: (i, j, +inf, NaN), info (-1, 0), MPCX_ST_OK -- mpcx_conjunction_pairs' row without
+ * a valid interval.  An index that is not a whole number inside its side, i == j with D = 0, or a t_row that is NaN or infinite:
+ * (i, j, NaN, NaN), info (-1, 0), MPCX_ST_BADK, and the other rows are not affected.  A finite t_row outside [T0, T1] is a time
+ * like any other: it picks the first or the last event.  Every byte of the outputs is defined.
+ * Two things follow.  A row of mpcx_conjunction_events' output, given back on the same inputs, returns its own distance, time,
+ * interval and edge flag bit for bit (its |t_m - t_row| is 0, and two events never share a time); so does a row of
+ * mpcx_conjunction_pairs' output.  (i, j) and (j, i) give the same bits.
+ * n = 0 is a successful call that does nothing.  n < 0, S < 1, D < 0, M < 2, T1 <= T0, a NaN max_shift, a missing pairs, eph, out
+ * or status, cat given with D = 0 or missing with D > 0: MPCX_E_BADARG with "conjunction_track" in the message, nothing enqueued.
+ * The host variant takes host pointers; the _dev variant device pointers throughout, no workspace, and enqueues one kernel on
+ * `stream`.
+ *
+ * mpcx_conjunction_track_traj: from trajectories, argument for argument as mpcx_conjunction_pairs_traj; eph_status, cat_status and
+ * the _dev variant's workspace of mpcx_conjunction_track_workspace_bytes(S, D, M) bytes (= mpcx_conjunction_pairs_workspace_bytes)
+ * likewise.  Same bits as mpcx_ephemeris_batch followed by mpcx_conjunction_track.
+ */
+size_t mpcx_conjunction_track_workspace_bytes(int S, int D, int M);
+int mpcx_conjunction_track(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                           double T0, double T1, double max_shift, double *out, int32_t *info, int32_t *status);
+int mpcx_conjunction_track_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                               double T0, double T1, double max_shift, double *out, int32_t *info, int32_t *status, void *stream);
+int mpcx_conjunction_track_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                double max_shift, double *out, int32_t *info, int32_t *status, int32_t *eph_status,
+                                int32_t *cat_status);
+int mpcx_conjunction_track_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                    const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                    const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                    double T1, double max_shift, double *out, int32_t *info, int32_t *status, int32_t *eph_status,
+                                    int32_t *cat_status, void *workspace, void *stream);
+
+/*
  * Collision probability of screened pairs.  A miss distance alone says nothing: the two orbit uncertainties decide whether 200 m
  * is an emergency or noise.  Two steps, both on the device: a covariance propagated along every trajectory, and for every row
  * (i, j, distance, time) of a screen's pairs list the short-encounter collision probability in the encounter plane.  The reference
@@ -1030,6 +1076,41 @@ int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const i
                               double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out,
                               double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows,
                               double *rhs_term, void *workspace, void *stream);
+
+/*
+ * mpcx_avoidance_refine_tracked: mpcx_avoidance_refine for a list that holds SEVERAL encounters of one pair (the rows of
+ * mpcx_conjunction_events).  With mpcx_conjunction_pairs_traj_dev as the re-screen every row of a pair carries the pair's global
+ * minimum from pass 1 on: two identical rows make the solve singular (MPCX_ST_SINGULAR) under the hold, and without it the second
+ * encounter is never looked at again.  Here the re-screen of every pass t >= 1 is mpcx_conjunction_track_traj_dev of the GIVEN list
+ * on Y_t with this call's max_shift (info NULL): each row follows the event nearest the time it was given, column 3 of `pairs`, in
+ * every pass -- not the time the pass before found.  Everything else is mpcx_avoidance_refine word for word: the arguments (plus
+ * max_shift after rounds), the passes, the outputs, the workspace and its size, the failures.  On a list whose every row is its
+ * pair's only event within reach both calls return the same bits.
+ * A row that loses its event -- none on Y_t, or none within max_shift -- is (+inf, NaN) in that pass's list, exactly the row
+ * without a valid interval of mpcx_avoidance_refine: the joint call gives a row with a NaN time MPCX_ST_BADK, so the pass's solve
+ * of the satellite that moves for it fails with that status, the satellite keeps du_t-1, reports MPCX_ST_BADK in sat_status and is
+ * frozen (no more solves, it keeps flying du_t-1); hist_d0 and hist_tca of the row are NaN in that pass.
+ * A NaN max_shift is MPCX_E_BADARG; max_shift <= 0 is unlimited.
+ */
+int mpcx_avoidance_refine_tracked(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                  const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                                  int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                                  const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
+                                  double target, const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0,
+                                  double T1, double prop_max_step, int rounds, double max_shift, double *du, double *sat_out,
+                                  double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out,
+                                  double *pairs_out, double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done,
+                                  double *rhs_rows, double *rhs_term);
+int mpcx_avoidance_refine_tracked_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                      const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                                      int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
+                                      const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P,
+                                      double mu, double target, const double *u_max, int hold_terminal, double tol, int max_iter, int M,
+                                      double T0, double T1, double prop_max_step, int rounds, double max_shift, double *du,
+                                      double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status,
+                                      int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0, double *hist_tca,
+                                      double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term, void *workspace,
+                                      void *stream);
 
 #ifdef __cplusplus
 }

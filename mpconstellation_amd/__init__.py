@@ -12,7 +12,7 @@ from .simulator import Simulator, propagate_batch
 from .constellation_mpc import ConstellationMPC
 from .atmosphere import Atmosphere
 from . import conjunction
-from .conjunction import (common_clock, screen, screen_against, screen_pairs, screen_events, EncounterEvents, cumulative_probability,
+from .conjunction import (common_clock, screen, screen_against, screen_pairs, screen_events, screen_track, EncounterEvents, cumulative_probability,
                           catalogue_trajectories, ConjunctionResult, covariance,
                           collision_probability, catalogue_covariance, CollisionResult, avoidance, AvoidanceResult,
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult)
@@ -20,7 +20,7 @@ from .conjunction import (common_clock, screen, screen_against, screen_pairs, sc
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
            "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC", "Atmosphere",
-           "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "screen_events", "EncounterEvents",
+           "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "screen_events", "screen_track", "EncounterEvents",
            "cumulative_probability", "catalogue_trajectories", "ConjunctionResult", "covariance",
            "collision_probability", "catalogue_covariance", "CollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult"]

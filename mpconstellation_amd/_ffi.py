@@ -143,6 +143,15 @@ _SIGS = {
                                      + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, _ip, _ip, _ip]),
     "mpcx_conjunction_events_traj_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp] * 2
                                          + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the close approach nearest each listed row's own time (the pairs calls with max_shift and an optional info output)
+    "mpcx_conjunction_track_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mpcx_conjunction_track": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _ip, _ip]),
+    "mpcx_conjunction_track_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                             _vp, _vp]),
+    "mpcx_conjunction_track_traj": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp] * 2
+                                    + [C.c_int, C.c_double, C.c_double, C.c_double, _dp, _ip, _ip, _ip, _ip]),
+    "mpcx_conjunction_track_traj_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp] * 2
+                                        + [C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # collision probability of screened pairs: covariance along trajectories, then the encounter-plane integral per listed pair
     "mpcx_covariance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "mpcx_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
@@ -176,6 +185,15 @@ _SIGS = {
                                             C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the same loop with the re-screen that follows each row's own encounter (max_shift after rounds)
+    "mpcx_avoidance_refine_tracked": (C.c_int, [_vp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                                C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, C.c_double, C.c_double, _dp, C.c_int, C.c_double, C.c_int,
+                                                C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "mpcx_avoidance_refine_tracked_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
+                                                    C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
+                                                    C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)

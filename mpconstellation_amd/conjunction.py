@@ -12,6 +12,7 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   screen_pairs   the closest approach of the pairs of a list alone, with the bits the screens give them;
   screen_events  EVERY close approach of the listed pairs below a threshold (a window of several revolutions holds about two per
                  revolution), as rows that every call below takes; cumulative_probability joins their probabilities per pair;
+  screen_track   of those close approaches the one nearest each listed row's own time: an encounter followed through re-screens;
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
@@ -21,7 +22,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   avoidance_joint   per manoeuvring satellite ONE thrust change that opens all of its listed encounters at once, inside its thrust
                  limit, and optionally holds the plan's terminal state.
   avoidance_refine  that manoeuvre flown through the nonlinear dynamics, re-screened, linearised and corrected, a fixed number of
-                 rounds on the device: the answer as flown.
+                 rounds on the device: the answer as flown; with track=True every row follows its own encounter (screen_track), which
+                 a list of screen_events' rows needs.
 
 The device does all of it (4096 satellites are 8.4 M pairs times the grid); there is no host path."""
 import numpy as np
@@ -278,14 +280,17 @@ def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, 
     return (out["out"], out["status"], *statuses) if given_traj else (out["out"], out["status"])
 
 
-def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1, events=None):
+def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1, events=None, track=None):
     """one block of the list's rows on context (device, slot), into `out` (the block's views); returns the ephemeris statuses
     [status, cat_status] of the calls from trajectories, None where there is none.  events = (threshold, max_events): every close
-    approach (mpcx_conjunction_events*) into out's events, info, count and status instead of the closest one into out and status"""
+    approach (mpcx_conjunction_events*) into out's events, info, count and status instead of the closest one into out and status;
+    track = max_shift: the close approach nearest each row's time (mpcx_conjunction_track*) into out's out, info and status"""
     pairs = _ffi.as_f64(pairs)
     ctx = _ffi.context(device, slot)
     S, D = src[0].shape[0], 0 if cat is None else cat[0].shape[0]
-    if events is None:
+    if track is not None:
+        name, tail = "mpcx_conjunction_track", (T0, T1, track, _ffi.dptr(out["out"]), _ffi.iptr(out["info"]), _ffi.iptr(out["status"]))
+    elif events is None:
         name, tail = "mpcx_conjunction_pairs", (T0, T1, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
     else:
         name, tail = "mpcx_conjunction_events", (T0, T1, *events, _ffi.dptr(out["events"]), _ffi.iptr(out["info"]), _ffi.iptr(out["count"]),
@@ -362,6 +367,50 @@ def screen_events(pairs, T0, T1, threshold=None, max_events=DEFAULT_MAX_EVENTS, 
                 device = int(devices[0])
             statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
     return EncounterEvents(out["events"], out["info"], out["count"], out["status"], *statuses)
+
+
+def _check_max_shift(max_shift):
+    """max_shift as the library takes it: None -> 0.0 (unlimited)"""
+    if max_shift is None:
+        return 0.0
+    if not (np.ndim(max_shift) == 0 and max_shift == max_shift):
+        raise ValueError(f"max_shift: need a number of seconds that is not NaN (None or <= 0: unlimited), got {max_shift}")
+    return float(max_shift)
+
+
+def screen_track(pairs, T0, T1, max_shift=None, eph=None, cat_eph=None, device=0, devices=None, *, Y=None, units=None, span=None, ns=None,
+                 cat_Y=None, cat_units=None, cat_span=None, cat_ns=None, M=None):
+    """The close approach of every LISTED row that lies nearest the row's own time, on the common grid linspace(T0, T1, M): an
+    encounter followed through a re-screen.  screen_pairs returns a pair's global minimum, so after a manoeuvre two rows of the same
+    pair (screen_events lists one per encounter) both read the same encounter; here each row (i, j, ., t_row) gets, of the pair's
+    events as screen_events defines them WITHOUT a threshold, the one that minimises (|t - t_row|, grid interval).  pairs: (n, 4)
+    rows, a ConjunctionResult or an EncounterEvents (its .events); columns 0, 1 and 3 are read.  Both sides exactly as screen_pairs
+    takes them.  max_shift (seconds; None or <= 0: unlimited): only events with |t - t_row| <= max_shift count.  Returns (out, info,
+    status): out (n, 4) rows (i, j, distance, time) in list order, info (n, 2) int32 (grid interval, 1 for an edge event else 0),
+    status (n,) int32.  A row without an event, or with none inside max_shift, is (+inf, NaN), info (-1, 0), status 0; an index
+    outside its side, i == j without a catalogue, or a t_row that is NaN or infinite is (NaN, NaN), (-1, 0), MPCX_ST_BADK = 9.  A
+    finite t_row outside [T0, T1] picks the first or the last event.  From trajectories it returns (out, info, status, eph_status,
+    cat_status).  A row of screen_events' or screen_pairs' output, given back on the same inputs, returns its own distance, time,
+    interval and edge bit for bit.  An empty list returns empty arrays without a library call.  devices=[d0, d1, ...]: contiguous
+    blocks of the list's rows on several devices (every device holds both sides), written in place, the bits of one device."""
+    if isinstance(pairs, EncounterEvents):
+        pairs = pairs.events
+    pairs, src, cat, M, T0, T1, given_traj = _check_list_call("screen_track", pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units,
+                                                              cat_span, cat_ns, M)
+    shift = _check_max_shift(max_shift)
+    n = pairs.shape[0]
+    out = dict(out=np.empty((n, 4)), info=np.empty((n, 2), dtype=np.int32), status=np.zeros(n, dtype=np.int32))
+    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
+    if n:
+        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, track=shift)
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    return (out["out"], out["info"], out["status"], *statuses) if given_traj else (out["out"], out["info"], out["status"])
 
 
 def cumulative_probability(events, pc):
@@ -897,7 +946,7 @@ class AvoidanceRefineResult(AvoidanceJointResult):
 def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds=3, ns=None, P=None, cat=None, who="i", u_max=None,
                      hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, include_drag=False, include_J2=False,
                      atmosphere=None, max_step=DEFAULT_MAX_STEP, prop_max_step=1e-3, mu=None, return_rows=False, return_terminal=False,
-                     return_rhs=False, device=0, devices=None):
+                     return_rhs=False, device=0, devices=None, track=False, max_shift=None):
     """avoidance_joint, then `rounds` times on the device: fly U + du through the nonlinear dynamics (include_drag / include_J2 /
     atmosphere are the model of the flight and of the linearisation; prop_max_step the flight's step limit), look at the LISTED pairs
     again on the grid linspace(T0, T1, M) (screen_pairs), linearise about what was flown and solve again -- the effort measured from
@@ -905,7 +954,16 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
     re-screen -> AvoidanceRefineResult, the answer as flown.  All other arguments as avoidance_joint takes them.  rounds = 0 is
     avoidance_joint followed by one flight and re-screen.  A row whose other object is moved by another row (`coupled`) sees that
     object's new trajectory in every round.  An empty list returns zeros without a library call.  One device: every round needs every
-    mover's new trajectory, so there is no block form and devices with more than one entry raises ValueError."""
+    mover's new trajectory, so there is no block form and devices with more than one entry raises ValueError.
+    track=True (mpcx_avoidance_refine_tracked): the re-screen is screen_track of the GIVEN list, so every row follows, in every pass,
+    the encounter nearest the time it was given with -- what a list with several encounters of one pair (screen_events' rows) needs:
+    under screen_pairs all rows of a pair read the pair's global minimum after the first flight, identical rows make the solve
+    singular under the hold, and the other encounters are never looked at again.  max_shift (seconds; None or <= 0: unlimited): how
+    far from its given time a row's encounter may be found; a row that loses its encounter reads (+inf, NaN), its mover's solve
+    fails with MPCX_ST_BADK = 9 and the satellite is frozen with the manoeuvre it had.  max_shift is read only with track=True; with
+    track=False nothing changes."""
+    if isinstance(pairs, EncounterEvents):
+        pairs = pairs.events
     pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
                                                                                      u_max, tol, max_iter, max_step, mu)
     (S, _, K), n = Y.shape, pairs.shape[0]
@@ -919,6 +977,7 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
     if devices is not None and len(devices) == 1:
         device = int(devices[0])
     rounds = int(rounds)
+    shift = _check_max_shift(max_shift) if track else None
     out = dict(_joint_arrays(S, K, n, return_rows, return_terminal), Y_flown=Y.copy(), pairs_flown=pairs.copy(),
                d0=np.zeros((rounds + 2, n)), tca=np.zeros((rounds + 2, n)), term=np.zeros((rounds + 2, S)), rounds_done=np.full(S, -1, dtype=np.int32),
                rhs_rows=np.zeros(n) if return_rhs else None, rhs_term=np.zeros((S, 6)) if return_rhs else None)
@@ -926,7 +985,7 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
         _avoidance_refine_call(device=device, slot=0, out=out, pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols,
                                mu=mu, target=float(target), hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter),
                                flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere,
-                               grid=(M, T0, T1), prop_max_step=float(prop_max_step), rounds=rounds)
+                               grid=(M, T0, T1), prop_max_step=float(prop_max_step), rounds=rounds, track=shift)
     joint = (pairs, mover, out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"], out["row_status"],
              _coupled(pairs, mover, cols is not None))
     return AvoidanceRefineResult(joint, out["Y_flown"], out["pairs_flown"], out["d0"], out["tca"], out["term"], out["rounds_done"],
@@ -934,14 +993,15 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
 
 
 def _avoidance_refine_call(*, device, slot, out, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere, grid,
-                           prop_max_step, rounds):
-    """the whole list and all satellites on context (device, slot), into `out`"""
+                           prop_max_step, rounds, track=None):
+    """the whole list and all satellites on context (device, slot), into `out`; track = max_shift: the tracked re-screen"""
     Y, U, units, span, consts, ns, P, u_max = rows
     col = _side_args(*(cols if cols is not None else (None,) * 5))
     ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_avoidance_refine", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
+    name, mode = ("mpcx_avoidance_refine", ()) if track is None else ("mpcx_avoidance_refine_tracked", (track,))
+    _ffi.call(name, ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
               _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
-              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, *grid, prop_max_step, rounds, _ffi.dptr(out["du"]), _ffi.dptr(out["sat_out"]),
+              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, *grid, prop_max_step, rounds, *mode, _ffi.dptr(out["du"]), _ffi.dptr(out["sat_out"]),
               _ffi.dptr(out["row_out"]), _ffi.dptr_opt(out["rows"]), _ffi.dptr_opt(out["tsens"]), _ffi.iptr(out["sat_status"]),
               _ffi.iptr(out["row_status"]), _ffi.dptr(out["Y_flown"]), _ffi.dptr(out["pairs_flown"]), _ffi.dptr(out["d0"]), _ffi.dptr(out["tca"]),
               _ffi.dptr(out["term"]), _ffi.iptr(out["rounds_done"]), _ffi.dptr_opt(out["rhs_rows"]), _ffi.dptr_opt(out["rhs_term"]))

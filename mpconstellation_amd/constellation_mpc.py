@@ -436,13 +436,18 @@ class ConstellationMPC:
 
     def avoidance_refine(self, threshold_m, target, rounds=3, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i",
                          hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, prop_max_step=1e-3, model="plan",
-                         install=False, return_rows=False, return_terminal=False, return_rhs=False):
+                         install=False, return_rows=False, return_terminal=False, return_rhs=False, events=False, max_events=16):
         """avoidance_joint's manoeuvre flown again, re-screened and corrected `rounds` times on the device -> (ConjunctionResult,
         AvoidanceRefineResult).  The plan is screened as avoidance_joint screens it, u_max comes from this instance's u_lim option,
         the re-screen's grid and span are the plan's screen window (samples_per_node).  model = 'plan' flies and linearises under the
         planning model (plan_drag, plan_J2), 'truth' under the model the segments are flown with (include_drag, include_J2, the
         atmosphere).  install=True puts Y_flown and U + du of every satellite whose status is 0 into the plan the instance holds, so
-        that fly_plan flies the refined manoeuvre."""
+        that fly_plan flies the refined manoeuvre.
+        events=True: EVERY close approach of the listed pairs at or below threshold_m is opened, not only each pair's closest -- the
+        list is conjunction.screen_events' (at most max_events per pair, as `encounters` lists them), every row follows its own
+        encounter through the re-screens (conjunction.avoidance_refine(track=True)), and the return is (ConjunctionResult,
+        EncounterEvents, AvoidanceRefineResult) with the result's rows in events.events' order.  A satellite that moves for more
+        than MPCX_AJ_MAX_ROWS = 8 rows gets MPCX_ST_BADK = 9 as from avoidance_joint; who as an array has one entry per event then."""
         from . import conjunction as cj
         if model not in ("plan", "truth"):
             raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
@@ -452,7 +457,12 @@ class ConstellationMPC:
         from .optimizer import DEFAULT_OPTIONS
         u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
         u_max = np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
-        res = cj.avoidance_refine(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, w["M"], w["T0"], w["T1"],
+        found = None
+        if events:
+            cat_kw = {} if cat is None else dict(cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2], cat_ns=cj._check_cat(cat)[3])
+            found = cj.screen_events(screened, threshold=threshold_m, max_events=max_events, **w, **cat_kw, **where)
+        res = cj.avoidance_refine(screened if found is None else found.events, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts,
+                                  w["M"], w["T0"], w["T1"], track=found is not None,
                                   rounds=rounds, ns=w["ns"], P=P, cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol,
                                   max_iter=max_iter, prop_max_step=prop_max_step, return_rows=return_rows, return_terminal=return_terminal,
                                   return_rhs=return_rhs, device=self.device, devices=None if self.devices is None else list(self.devices)[:1],
@@ -463,7 +473,7 @@ class ConstellationMPC:
             X[ok] = res.Y_flown[ok]
             U[ok] = U[ok] + res.du[ok]
             self._plan = (X, U) + tuple(self._plan[2:])
-        return screened, res
+        return (screened, res) if found is None else (screened, found, res)
 
     @staticmethod
     def _check(status):

@@ -678,7 +678,9 @@ extern "C" int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, c
 //                     propagate         every satellite from its first node under U_t
 //                     ar_select_kernel  Y_t: the flight of a satellite that flies, the given trajectory otherwise; the end-state history;
 //                                       a failed flight freezes the satellite
-//                     the re-screen     mpcx_conjunction_pairs_traj_dev on Y_t: its out IS the pass's list
+//                     the re-screen     mpcx_conjunction_pairs_traj_dev on Y_t: its out IS the pass's list.  Tracked (mpcx_avoidance_
+//                                       refine_tracked*): mpcx_conjunction_track_traj_dev of the GIVEN list, whose column 3 is the time
+//                                       each row follows in every pass -- a pair listed twice keeps its two encounters apart
 //                     linearisation about (Y_t, U_t), aj_rows_kernel, ar_trhs_kernel, aj_solve_kernel (uref = U, z0 from the last solve)
 //                                       into trial arrays; ar_accept_kernel takes them over or freezes the satellite
 //   pass rounds + 1   the same without the solve: every answer is returned as flown
@@ -774,6 +776,8 @@ struct ArCall {
     double *Y_out, *pairs_out, *hist_d0, *hist_tca, *hist_term;
     int32_t *rounds_done;
     double *rhs_rows, *rhs_term;
+    bool track = false;                                              // the re-screen follows each row's own encounter (track_kernel)
+    double max_shift = 0.0;                                          //   at most this far from the row's given time; <= 0: unlimited
 };
 
 // [the joint call's workspace][the re-screen's][U_t S 3 K][flight S 7 K][y0 S 7][end_tau S][du S 3 K][sat_out S][row_out n][z S 14][trhs S 6]
@@ -787,7 +791,7 @@ struct ArWorkspace {
     {
         Carver c(base);
         aj = c.take<char>(AjWorkspace(nullptr, n, S, K).bytes);
-        scr = c.take<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));
+        scr = c.take<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));       // (the tracked re-screen's is the same size)
         Ut = c.take<double>((size_t)S * 3 * K);
         Yp = c.take<double>((size_t)S * 7 * K);
         y0 = c.take<double>((size_t)S * 7);
@@ -811,6 +815,7 @@ static int ar_check(mpcx_ctx *ctx, const ArCall &c)
     if (c.rounds < 0) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: rounds must be >= 0");
     if (c.M < 2 || !(c.T1 > c.T0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: the re-screen's grid needs M >= 2 and T1 > T0");
     if (!(c.prop_max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: prop_max_step must be > 0");
+    if (c.track && !(c.max_shift == c.max_shift)) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine_tracked: max_shift is NaN");
     if (!c.Y_out || !c.pairs_out || !c.hist_d0 || !c.hist_tca || !c.hist_term || !c.rounds_done)
         return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: Y_out, pairs_out, hist_d0, hist_tca, hist_term and rounds_done are required");
     return MPCX_OK;
@@ -848,9 +853,14 @@ static int ar_enqueue(mpcx_ctx *ctx, const ArCall &c, void *workspace, hipStream
         hipLaunchKernelGGL(ar_select_kernel, dim3((unsigned)S), dim3(64), 0, st, S, K, j.Ks, j.Y, ws.Yp, ws.pst, ws.flies, ws.skip, j.sat_status,
                            c.Y_out, c.hist_term + (size_t)t * S);
         MPCX_HIP(ctx, hipGetLastError());
-        if (int rc = mpcx_conjunction_pairs_traj_dev(ctx, n, j.pairs, S, K, j.Ks, c.Y_out, j.units, j.span, D, D ? j.cat_K : 0, D ? j.cat_Ks : nullptr,
-                                                     D ? j.cat_Y : nullptr, D ? j.cat_units : nullptr, D ? j.cat_span : nullptr, c.M, c.T0, c.T1,
-                                                     c.pairs_out, ws.scr_st, ws.eph_st, D ? ws.cat_st : nullptr, ws.scr, st))
+        if (int rc = c.track ? mpcx_conjunction_track_traj_dev(ctx, n, j.pairs, S, K, j.Ks, c.Y_out, j.units, j.span, D, D ? j.cat_K : 0,
+                                                               D ? j.cat_Ks : nullptr, D ? j.cat_Y : nullptr, D ? j.cat_units : nullptr,
+                                                               D ? j.cat_span : nullptr, c.M, c.T0, c.T1, c.max_shift, c.pairs_out, nullptr,
+                                                               ws.scr_st, ws.eph_st, D ? ws.cat_st : nullptr, ws.scr, st)
+                             : mpcx_conjunction_pairs_traj_dev(ctx, n, j.pairs, S, K, j.Ks, c.Y_out, j.units, j.span, D, D ? j.cat_K : 0,
+                                                               D ? j.cat_Ks : nullptr, D ? j.cat_Y : nullptr, D ? j.cat_units : nullptr,
+                                                               D ? j.cat_span : nullptr, c.M, c.T0, c.T1, c.pairs_out, ws.scr_st, ws.eph_st,
+                                                               D ? ws.cat_st : nullptr, ws.scr, st))
             return rc;
         AjCall q = j;
         q.pairs = c.pairs_out; q.Y = c.Y_out; q.U = ws.Ut;
@@ -882,23 +892,17 @@ extern "C" size_t mpcx_avoidance_refine_workspace_bytes(int n, int S, int K, int
     return ArWorkspace(nullptr, n, S, K, D, M).bytes;
 }
 
-#define MPCX_AR_CALL                                                                                                                        \
+// the arguments of the four entry points below as an ArCall; TRACK, SHIFT: the re-screen's mode
+#define MPCX_AR_CALL(TRACK, SHIFT)                                                                                                          \
     ArCall{AjCall{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,   \
                    mu, target}, mover, u_max, hold_terminal, tol, max_iter, 0, S, du, sat_out, row_out, rows, tsens, sat_status, row_status}, \
-           M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, rhs_term}
+           M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, rhs_term, TRACK, SHIFT}
 
-extern "C" int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
-                                         const double *Y, const double *U, const double *units, const double *span, const double *consts,
-                                         int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks,
-                                         const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu,
-                                         double target, const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0,
-                                         double T1, double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows,
-                                         double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out,
-                                         double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows,
-                                         double *rhs_term, void *workspace, void *stream)
+namespace mpcx {
+
+// device pointers throughout in `c`
+static int ar_dev(mpcx_ctx *ctx, const ArCall &c, void *workspace, void *stream)
 {
-    if (!ctx) return MPCX_E_BADARG;
-    const ArCall c = MPCX_AR_CALL;
     if (int rc = ar_check(ctx, c)) return rc;
     if (!workspace)
         return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_refine: a workspace of mpcx_avoidance_refine_workspace_bytes(n, S, K, D, M) bytes is required");
@@ -906,48 +910,97 @@ extern "C" int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pai
     return ar_enqueue(ctx, c, workspace, (hipStream_t)stream);
 }
 
-extern "C" int mpcx_avoidance_refine(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
-                                     const double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
-                                     double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
-                                     const double *cat_units, const double *cat_span, const double *cat_P, double mu, double target,
-                                     const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double T1,
-                                     double prop_max_step, int rounds, double *du, double *sat_out, double *row_out, double *rows, double *tsens,
-                                     int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0,
-                                     double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term)
+// host pointers throughout in `c`: staged, enqueued, and the results brought back into c's own arrays
+static int ar_host(mpcx_ctx *ctx, const ArCall &c)
 {
-    if (!ctx) return MPCX_E_BADARG;
-    const ArCall c = MPCX_AR_CALL;
     if (int rc = ar_check(ctx, c)) return rc;
-    if (int rc = check_mover(ctx, c.j, mover, "avoidance_refine")) return rc;
+    if (int rc = check_mover(ctx, c.j, c.j.mover, "avoidance_refine")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     ArCall d = c;
     AjCall &j = d.j;
     aj_stage(ar, j);
-    const size_t np = (size_t)rounds + 2;
+    const int n = c.j.n, S = c.j.S, K = c.j.K;
+    const size_t np = (size_t)c.rounds + 2;
     d.Y_out = ar.alloc<double>((size_t)S * 7 * K); d.pairs_out = ar.alloc<double>((size_t)n * 4);
     d.hist_d0 = ar.alloc<double>(np * n); d.hist_tca = ar.alloc<double>(np * n); d.hist_term = ar.alloc<double>(np * S);
     d.rounds_done = ar.alloc<int32_t>(S);
-    d.rhs_rows = rhs_rows ? ar.alloc<double>((size_t)n) : nullptr;
-    d.rhs_term = rhs_term ? ar.alloc<double>((size_t)S * 6) : nullptr;
-    const size_t wbytes = mpcx_avoidance_refine_workspace_bytes(n, S, K, cat_Y ? D : 0, M);
+    d.rhs_rows = c.rhs_rows ? ar.alloc<double>((size_t)n) : nullptr;
+    d.rhs_term = c.rhs_term ? ar.alloc<double>((size_t)S * 6) : nullptr;
+    const size_t wbytes = mpcx_avoidance_refine_workspace_bytes(n, S, K, c.j.cat_Y ? c.j.D : 0, c.M);
     if (ar.failed()) return ar.code();
     void *ws = ctx_workspace(ctx, wbytes);
     if (!ws) return MPCX_E_NOMEM;
     if (int rc = ar_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(du, j.du, (size_t)S * 3 * K);
-    ar.download(sat_out, j.sat_out, (size_t)S * MPCX_NAJ);
-    ar.download(row_out, j.row_out, (size_t)n * MPCX_NAR);
-    if (rows) ar.download(rows, j.rows, (size_t)n * 3 * K);
-    if (tsens) ar.download(tsens, j.tsens, (size_t)S * 18 * K);
-    ar.download(sat_status, j.sat_status, (size_t)S);
-    ar.download(row_status, j.row_status, (size_t)n);
-    ar.download(Y_out, d.Y_out, (size_t)S * 7 * K);
-    ar.download(pairs_out, d.pairs_out, (size_t)n * 4);
-    ar.download(hist_d0, d.hist_d0, np * n); ar.download(hist_tca, d.hist_tca, np * n); ar.download(hist_term, d.hist_term, np * S);
-    ar.download(rounds_done, d.rounds_done, (size_t)S);
-    if (rhs_rows) ar.download(rhs_rows, d.rhs_rows, (size_t)n);
-    if (rhs_term) ar.download(rhs_term, d.rhs_term, (size_t)S * 6);
+    ar.download(c.j.du, j.du, (size_t)S * 3 * K);
+    ar.download(c.j.sat_out, j.sat_out, (size_t)S * MPCX_NAJ);
+    ar.download(c.j.row_out, j.row_out, (size_t)n * MPCX_NAR);
+    if (c.j.rows) ar.download(c.j.rows, j.rows, (size_t)n * 3 * K);
+    if (c.j.tsens) ar.download(c.j.tsens, j.tsens, (size_t)S * 18 * K);
+    ar.download(c.j.sat_status, j.sat_status, (size_t)S);
+    ar.download(c.j.row_status, j.row_status, (size_t)n);
+    ar.download(c.Y_out, d.Y_out, (size_t)S * 7 * K);
+    ar.download(c.pairs_out, d.pairs_out, (size_t)n * 4);
+    ar.download(c.hist_d0, d.hist_d0, np * n); ar.download(c.hist_tca, d.hist_tca, np * n); ar.download(c.hist_term, d.hist_term, np * S);
+    ar.download(c.rounds_done, d.rounds_done, (size_t)S);
+    if (c.rhs_rows) ar.download(c.rhs_rows, d.rhs_rows, (size_t)n);
+    if (c.rhs_term) ar.download(c.rhs_term, d.rhs_term, (size_t)S * 6);
     return ar.finish();
+}
+
+}  // namespace mpcx
+
+extern "C" int mpcx_avoidance_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks, const
+                                         double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                                         double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const
+                                         double *cat_units, const double *cat_span, const double *cat_P, double mu, double target, const double
+                                         *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double T1, double prop_max_step, int
+                                         rounds, double *du, double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status,
+                                         int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0, double *hist_tca, double
+                                         *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return ar_dev(ctx, MPCX_AR_CALL(false, 0.0), workspace, stream);
+}
+
+extern "C" int mpcx_avoidance_refine(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks, const double
+                                     *Y, const double *U, const double *units, const double *span, const double *consts, int flags, double max_step,
+                                     const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const
+                                     double *cat_span, const double *cat_P, double mu, double target, const double *u_max, int hold_terminal, double
+                                     tol, int max_iter, int M, double T0, double T1, double prop_max_step, int rounds, double *du, double *sat_out,
+                                     double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double
+                                     *pairs_out, double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows,
+                                     double *rhs_term)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return ar_host(ctx, MPCX_AR_CALL(false, 0.0));
+}
+
+// ---- the same loop with the re-screen that follows each row's own encounter (mpcx_conjunction_track_traj_dev)
+extern "C" int mpcx_avoidance_refine_tracked_dev(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks,
+                                                 const double *Y, const double *U, const double *units, const double *span, const double *consts,
+                                                 int flags, double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double
+                                                 *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P, double mu, double
+                                                 target, const double *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double
+                                                 T1, double prop_max_step, int rounds, double max_shift, double *du, double *sat_out, double
+                                                 *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out,
+                                                 double *pairs_out, double *hist_d0, double *hist_tca, double *hist_term, int32_t *rounds_done,
+                                                 double *rhs_rows, double *rhs_term, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return ar_dev(ctx, MPCX_AR_CALL(true, max_shift), workspace, stream);
+}
+
+extern "C" int mpcx_avoidance_refine_tracked(mpcx_ctx *ctx, int n, const double *pairs, const int32_t *mover, int S, int K, const int32_t *Ks, const
+                                             double *Y, const double *U, const double *units, const double *span, const double *consts, int flags,
+                                             double max_step, const double *P, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const
+                                             double *cat_units, const double *cat_span, const double *cat_P, double mu, double target, const double
+                                             *u_max, int hold_terminal, double tol, int max_iter, int M, double T0, double T1, double prop_max_step,
+                                             int rounds, double max_shift, double *du, double *sat_out, double *row_out, double *rows, double
+                                             *tsens, int32_t *sat_status, int32_t *row_status, double *Y_out, double *pairs_out, double *hist_d0,
+                                             double *hist_tca, double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return ar_host(ctx, MPCX_AR_CALL(true, max_shift));
 }
 #undef MPCX_AR_CALL

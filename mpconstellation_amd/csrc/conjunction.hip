@@ -10,7 +10,9 @@
 //   pairs_kernel       the same closest approach for the pairs of a LIST (a screen's, flown again after a manoeuvre): one wave
 //                      per pair, n x M work, the bits the screens give the pair;
 //   events_kernel      EVERY close approach of the listed pairs: the local minima of the per-interval distance over the grid, one
-//                      wave per pair, in the pairs-row form (i, j, distance, time) that the rest of the chain takes.
+//                      wave per pair, in the pairs-row form (i, j, distance, time) that the rest of the chain takes;
+//   track_kernel       of those close approaches the one nearest each listed row's own time: an encounter followed through the
+//                      re-screens of a manoeuvre, where pairs_kernel would jump to the pair's global minimum.
 // Two screens launch screen_kernel.  All pairs of one constellation (SELF): rows and columns are the same S satellites, the full square of
 // ordered pairs (i, j != i) is computed, the list holds the pairs i < j.  A constellation against a catalogue of foreign objects
 // (cross): rows are the S satellites, columns the D objects, the rectangle S x D is computed and not the square (S + D)^2 of the
@@ -428,6 +430,90 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     if (lane == 0) { e.count[r] = found; a.status[r] = bad ? MPCX_ST_BADK : MPCX_ST_OK; }
 }
 
+struct TrackArgs {
+    PairsArgs p;                      // p.pairs: column 3 is the time to follow; p.out: [n][4]
+    double max_shift;                 // seconds; <= 0: unlimited
+    int32_t *info;                    // [n][2] = (interval, edge), or NULL
+};
+
+// The close approach of a listed row that lies NEAREST THE ROW'S OWN TIME (include/mpcx.h: mpcx_conjunction_track): of the events
+// events_kernel finds without a threshold, the one that minimises (|t_m - t_row|, m) -- a total order, so a tie goes to the earlier
+// interval.  pairs_kernel follows a pair's global minimum, which after a manoeuvre is no longer the encounter the row was listed
+// for when the pair has several; this follows the encounter.  One wave per row and events_kernel's walk: chunks of 64 consecutive
+// intervals, the neighbours from the lanes beside and the chunk carry, chunk c - 1 decided after chunk c is computed.  The event
+// predicate and the edge rule are restated here operation for operation on the same operands (events_kernel is left as it is: its
+// registers are tuned), so an event has the bits events_kernel stores for it.  There is no threshold -- the caller needs the distance
+// of an encounter that a manoeuvre has opened beyond any -- and so no square root per lane.  Every lane keeps the key of its best
+// candidate, |dt| and the interval, in three registers; an xor butterfly takes the minimum under (|dt|, interval) after the last
+// pass; then three lanes evaluate the winning interval and its two neighbours once more -- cj_pair_interval on the same operands,
+// so the same bits -- for the event's (q, t) and its edge flag, and one lane takes the one root and stores.  (Carrying q, t and the
+// edge flag of the candidate through the loop instead costs five more registers across cj_interval's Newton steps: at six waves per
+// SIMD that build spilt four VGPRs to scratch, profiles/conjunction_track.txt.)  No LDS, no atomics: nothing depends on anything
+// but the row.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void track_kernel(TrackArgs e)
+{
+    const PairsArgs &a = e.p;
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const bool cross = a.D > 0;
+    const double xi = a.pairs[(size_t)r * 4], xj = a.pairs[(size_t)r * 4 + 1], trow = a.pairs[(size_t)r * 4 + 3];
+    const int i = cj_index(xi, a.S), j = cj_index(xj, cross ? a.D : a.S);
+    double *o = a.out + (size_t)r * 4;
+    // (the whole wave: it reads nothing of the ephemerides; trow - trow is 0 for a finite time and NaN otherwise)
+    if (i < 0 || j < 0 || (!cross && i == j) || !(trow - trow == 0.0)) {
+        if (lane == 0) {
+            o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan();
+            if (e.info) { e.info[2 * (size_t)r] = -1; e.info[2 * (size_t)r + 1] = 0; }
+            a.status[r] = MPCX_ST_BADK;
+        }
+        return;
+    }
+    const bool up = cross || j > i;                                  // the column is the higher index: column - row
+    const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
+    const int nchunk = (a.M - 1 + 63) / 64;
+    double qp = cj_inf(), tp = cj_nan();                             // the pending chunk's interval of this lane
+    double carry = cj_inf();                                         // q of the interval before the pending chunk's first
+    double bdt = cj_inf();                                           // this lane's best candidate: |dt| and the interval
+    int bm = 0x7fffffff;                                             //   (INT_MAX: none)
+    for (int c = 0; c <= nchunk; ++c) {
+        const int m = 64 * c + lane;
+        double q = cj_inf(), t = cj_nan();
+        if (m < a.M - 1) cj_pair_interval(a, er, ec, up, m, q, t);
+        const int mp = m - 64;
+        double left = __shfl_up(qp, 1), right = __shfl_down(qp, 1);
+        const double next = __shfl(q, 0);
+        if (lane == 0) left = carry;
+        if (lane == 63) right = next;
+        const bool event = qp < cj_inf() && qp < left && qp <= right;
+        const double dt = fabs(tp - trow);
+        // (a lane's intervals ascend, so its own ties keep the earlier; the comparison is the butterfly's all the same)
+        if (event && (!(e.max_shift > 0.0) || dt <= e.max_shift) && (dt < bdt || (dt == bdt && mp < bm))) { bdt = dt; bm = mp; }
+        carry = __shfl(qp, 63);
+        qp = q; tp = t;
+    }
+    for (int w = 32; w >= 1; w >>= 1) {
+        const double dto = __shfl_xor(bdt, w);
+        const int mo = __shfl_xor(bm, w);
+        if (dto < bdt || (dto == bdt && mo < bm)) { bdt = dto; bm = mo; }
+    }
+    // Every lane holds the winner.  Lanes 0, 1, 2 evaluate the intervals bm - 1, bm, bm + 1 once more: the event's (q, t) and its two
+    // neighbours' q, from which lane 1 restates events_kernel's edge rule on the same operands.
+    const bool have = bm != 0x7fffffff;
+    const int mw = bm - 1 + lane;
+    double q = cj_inf(), t = cj_nan();
+    if (have && lane < 3 && mw >= 0 && mw < a.M - 1) cj_pair_interval(a, er, ec, up, mw, q, t);
+    const double left = __shfl_up(q, 1), right = __shfl_down(q, 1);
+    if (lane == 1) {
+        // still closing where the pair's common span ends: the time is an assigned end of the interval, so == is exact
+        const bool edge = have && ((!(left < cj_inf()) && t == cj_time(bm, a.M, a.T0, a.T1, a.h)) ||
+                                   (!(right < cj_inf()) && t == cj_time(bm + 1, a.M, a.T0, a.T1, a.h)));
+        o[0] = xi; o[1] = xj;
+        o[2] = have ? sqrt(q) : cj_inf();                            // no event (within max_shift): +inf, NaN, as pairs_kernel's
+        o[3] = have ? t : cj_nan();                                  // row without a valid interval
+        if (e.info) { e.info[2 * (size_t)r] = have ? bm : -1; e.info[2 * (size_t)r + 1] = edge ? 1 : 0; }
+        a.status[r] = MPCX_ST_OK;
+    }
+}
+
 // The two screens as the host sees them: the name in the messages, and whether the columns are the rows' own constellation
 // (then the callers below pass D = S and cat = eph).
 struct Screen {
@@ -726,21 +812,26 @@ extern "C" int mpcx_conjunction_cross_screen_traj(mpcx_ctx *ctx, int S, int n, c
     return screen_from_device(ctx, ar, CROSS, c, ws.eph, ws.cat, dws);
 }
 
-// ---- listed pairs: the closest approach of each (mpcx_conjunction_pairs*), or every close approach (mpcx_conjunction_events*)
+// ---- listed pairs: the closest approach of each (mpcx_conjunction_pairs*), every close approach (mpcx_conjunction_events*), or
+// the close approach nearest each row's own time (mpcx_conjunction_track*)
 namespace mpcx {
 
 // what every list entry point is given behind its list and its two sides; events: every close approach below the threshold
-// (events_kernel, max_events slots per pair) instead of the closest one (pairs_kernel)
+// (events_kernel, max_events slots per pair) instead of the closest one (pairs_kernel); track: the close approach nearest the row's
+// time, at most max_shift away (track_kernel)
 struct PairsCall {
     int n, S, D, M;
     double T0, T1;
     bool events;
     double threshold;
     int max_events;
+    bool track = false;
+    double max_shift = 0.0;
     size_t rows() const { return (size_t)n * (events ? (size_t)max_events : 1); }       // rows of four doubles in the first output
 };
 
-// the outputs: rows = out [n][4] and status [n]; the events calls have rows = events [n][E][4], info [n][E][2] and count [n] too
+// the outputs: rows = out [n][4] and status [n]; the events calls have rows = events [n][E][4], info [n][E][2] and count [n] too;
+// the track calls may have info [n][2]
 struct PairsOut {
     double *rows;
     int32_t *status, *info, *count;
@@ -753,13 +844,15 @@ struct PairsNames {
 };
 constexpr PairsNames PAIRS{"conjunction_pairs", "conjunction_pairs_traj", "out and status", "out, status"};
 constexpr PairsNames EVENTS{"conjunction_events", "conjunction_events_traj", "events, info, count and status", "events, info, count, status"};
+constexpr PairsNames TRACK{"conjunction_track", "conjunction_track_traj", "out and status", "out, status"};
 
 static int pairs_check(mpcx_ctx *ctx, const char *name, const PairsCall &c)
 {
-    if (!c.events && c.n < 1) return screen_fail(ctx, name, "need n>=1, S>=1, D>=0, M>=2, T1>T0");
+    if (!c.events && !c.track && c.n < 1) return screen_fail(ctx, name, "need n>=1, S>=1, D>=0, M>=2, T1>T0");
     if (c.n < 0 || c.S < 1 || c.D < 0 || c.M < 2 || !(c.T1 > c.T0)) return screen_fail(ctx, name, "need n>=0, S>=1, D>=0, M>=2, T1>T0");
     if (c.events && (c.max_events < 1 || !(c.threshold == c.threshold)))
         return screen_fail(ctx, name, "need max_events>=1 and a threshold that is not NaN");
+    if (c.track && !(c.max_shift == c.max_shift)) return screen_fail(ctx, name, "need a max_shift that is not NaN");
     return MPCX_OK;
 }
 
@@ -784,7 +877,7 @@ struct PairsWorkspace {
     }
 };
 
-// pairs_kernel or events_kernel on `st`, everything in device memory
+// pairs_kernel, events_kernel or track_kernel on `st`, everything in device memory
 static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs, const double *eph, const double *cat, const PairsOut &o,
                          hipStream_t st)
 {
@@ -793,17 +886,21 @@ static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs,
     if (c.events) {
         const EventsArgs e{a, c.threshold > 0.0 ? c.threshold : 0.0, c.max_events, o.info, o.count};
         hipLaunchKernelGGL(events_kernel, dim3((unsigned)c.n), dim3(64), 0, st, e);
+    } else if (c.track) {
+        const TrackArgs t{a, c.max_shift > 0.0 ? c.max_shift : 0.0, o.info};
+        hipLaunchKernelGGL(track_kernel, dim3((unsigned)c.n), dim3(64), 0, st, t);
     } else
         hipLaunchKernelGGL(pairs_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
     return MPCX_OK;
 }
 
-// device arrays for the outputs of a host-pointer call, and their way back
-static PairsOut pairs_out_alloc(DeviceArena &ar, const PairsCall &c)
+// device arrays for the outputs `o` of a host-pointer call, and their way back (a track call's info only where it is asked for)
+static PairsOut pairs_out_alloc(DeviceArena &ar, const PairsCall &c, const PairsOut &o)
 {
     PairsOut d{ar.alloc<double>(c.rows() * 4), ar.alloc<int32_t>(c.n), nullptr, nullptr};
     if (c.events) { d.info = ar.alloc<int32_t>(c.rows() * 2); d.count = ar.alloc<int32_t>(c.n); }
+    if (c.track && o.info) d.info = ar.alloc<int32_t>(c.rows() * 2);
     return d;
 }
 
@@ -812,9 +909,10 @@ static void pairs_out_download(DeviceArena &ar, const PairsCall &c, const PairsO
     ar.download(o.rows, d.rows, c.rows() * 4);
     ar.download(o.status, d.status, c.n);
     if (c.events) { ar.download(o.info, d.info, c.rows() * 2); ar.download(o.count, d.count, c.n); }
+    if (c.track && o.info) ar.download(o.info, d.info, c.rows() * 2);
 }
 
-// the four forms of a list call behind their extern "C" names (n = 0 passes pairs_check for the events calls only: nothing to do)
+// the four forms of a list call behind their extern "C" names (n = 0 passes pairs_check for the events and track calls only: nothing to do)
 static int pairs_dev(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, const double *pairs, const double *eph, const double *cat,
                      const PairsOut &o, void *stream)
 {
@@ -836,7 +934,7 @@ static int pairs_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, c
     DeviceArena ar(ctx);
     double *dp = ar.upload(pairs, (size_t)c.n * 4), *de = ar.upload(eph, (size_t)c.S * 6 * c.M);
     double *dc = c.D > 0 ? ar.upload(cat, (size_t)c.D * 6 * c.M) : nullptr;
-    const PairsOut d = pairs_out_alloc(ar, c);
+    const PairsOut d = pairs_out_alloc(ar, c, o);
     if (ar.failed()) return ar.code();
     if (int rc = pairs_enqueue(ctx, c, dp, de, dc, d, ctx->stream)) return rc;
     pairs_out_download(ar, c, o, d);
@@ -892,7 +990,7 @@ static int pairs_traj_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall 
         cst = ar.alloc<int32_t>(D);
     }
     int32_t *est = ar.alloc<int32_t>(S);
-    const PairsOut d = pairs_out_alloc(ar, c);
+    const PairsOut d = pairs_out_alloc(ar, c, o);
     char *dws = ar.alloc<char>(PairsWorkspace(nullptr, S, D, c.M).bytes);                // neither ephemeris leaves HBM
     if (ar.failed()) return ar.code();
     if (int rc = pairs_traj_dev(ctx, nm, c, dp, ds, dc, d, est, cst, dws, ctx->stream)) return rc;
@@ -989,4 +1087,47 @@ extern "C" int mpcx_conjunction_events_traj(mpcx_ctx *ctx, int n, const double *
     if (!ctx) return MPCX_E_BADARG;
     return pairs_traj_host(ctx, EVENTS, PairsCall{n, S, D, M, T0, T1, true, threshold, max_events}, pairs, PairsSide{nn, ns, Y, units, span},
                            PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{events, status, info, count}, eph_status, cat_status);
+}
+
+// ---- the close approach nearest each row's own time: the same four forms on track_kernel; n = 0 does nothing, info may be NULL
+
+extern "C" size_t mpcx_conjunction_track_workspace_bytes(int S, int D, int M) { return mpcx_conjunction_pairs_workspace_bytes(S, D, M); }
+
+extern "C" int mpcx_conjunction_track_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph,
+                                          const double *cat, double T0, double T1, double max_shift, double *out, int32_t *info,
+                                          int32_t *status, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_dev(ctx, TRACK, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0, true, max_shift}, pairs, eph, cat, PairsOut{out, status, info, nullptr},
+                     stream);
+}
+
+extern "C" int mpcx_conjunction_track(mpcx_ctx *ctx, int n, const double *pairs, int S, int D, int M, const double *eph, const double *cat,
+                                      double T0, double T1, double max_shift, double *out, int32_t *info, int32_t *status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_host(ctx, TRACK, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0, true, max_shift}, pairs, eph, cat, PairsOut{out, status, info, nullptr});
+}
+
+extern "C" int mpcx_conjunction_track_traj_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                               const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                               const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0,
+                                               double T1, double max_shift, double *out, int32_t *info, int32_t *status, int32_t *eph_status,
+                                               int32_t *cat_status, void *workspace, void *stream)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_traj_dev(ctx, TRACK, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0, true, max_shift}, pairs, PairsSide{nn, ns, Y, units, span},
+                          PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{out, status, info, nullptr}, eph_status, cat_status,
+                          workspace, stream);
+}
+
+extern "C" int mpcx_conjunction_track_traj(mpcx_ctx *ctx, int n, const double *pairs, int S, int nn, const int32_t *ns, const double *Y,
+                                           const double *units, const double *span, int D, int cat_n, const int32_t *cat_ns,
+                                           const double *cat_Y, const double *cat_units, const double *cat_span, int M, double T0, double T1,
+                                           double max_shift, double *out, int32_t *info, int32_t *status, int32_t *eph_status,
+                                           int32_t *cat_status)
+{
+    if (!ctx) return MPCX_E_BADARG;
+    return pairs_traj_host(ctx, TRACK, PairsCall{n, S, D, M, T0, T1, false, 0.0, 0, true, max_shift}, pairs, PairsSide{nn, ns, Y, units, span},
+                           PairsSide{cat_n, cat_ns, cat_Y, cat_units, cat_span}, PairsOut{out, status, info, nullptr}, eph_status, cat_status);
 }
