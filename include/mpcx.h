@@ -828,6 +828,73 @@ int mpcx_collision_probability_dev(mpcx_ctx *ctx, int n, const double *pairs, in
                                    int32_t *status, void *stream);
 
 /*
+ * mpcx_collision_probability_window: the collision probability of listed rows over a time window, for encounters the
+ * short-encounter model above does not cover.  That model takes the relative motion as a straight line, freezes both position
+ * covariances at the pair's time, ignores velocity uncertainty and integrates in the plane across the relative velocity: right for
+ * crossing orbits at km/s, wrong for neighbours in one shell or satellites deployed together, which pass at cm/s to m/s over minutes
+ * to a revolution (at zero relative speed it has no plane at all: MPCX_ST_NUMERIC).  This call has no encounter plane.
+ * Arguments: those of mpcx_collision_probability, then half_window [n] in seconds and panels (1 .. MPCX_PW_MAX_PANELS).
+ * Per row (i, j, ., t) the window is [t_a, t_b] = [t - h, t + h] cut to both objects' spans.  Index, node count, span and t are tested
+ * as above, on both objects at t (MPCX_ST_BADK); h not positive and finite, or t_b <= t_a: MPCX_ST_BADK; R = radius_i + radius_j not
+ * finite: MPCX_ST_NUMERIC; R <= 0: P, START, ENTRIES and RATE_MAX are 0, T_RATE_MAX = t_a, status MPCX_ST_OK, no covariance is read.
+ * The model.  At a time tau the relative state (rho, nu) is Gaussian with mean (d, w) = (p_b - p_a, v_b - v_a) -- the cubic Hermite
+ * on each object's own nodes and its derivative, as above -- and covariance [[A, B^T], [B, D]] = the sum of the two objects' 6 x 6
+ * covariances, each carried from its nearest node over dt by the short-arc transition with its velocity rows, Sigma = Phi P_kc Phi^T,
+ *   Phi = [[I + G0 dt^2/2, dt I + G0 dt^3/6], [(G0 + 4 Gm + Ge) dt/6 + G0^2 dt^3/6, I + (2 Gm + Ge) dt^2/6]].
+ * The position rows, and with them A, are mpcx_collision_probability's C to the letter: G0 is the gradient at the node, the first
+ * neglected term G' dt^3/6, order (n dt)^3 in units of the mean motion n.  The velocity rows are their derivative, int_0^dt G(s)
+ * Phi_r(s) ds, by Simpson's rule on the gradient at the node, at the middle (Gm) and at the end (Ge) of the arc, the positions there
+ * r + v s + a s^2/2 from the node's own velocity v and two-body acceleration a = -mu r / |r|^3; they neglect order (n dt)^4.  (With
+ * the node's gradient alone, [G0 dt, I + G0 dt^2/2], the velocity-position block neglects G' dt^2/2, order (n dt)^2.)  Measured
+ * against a finite-difference transition at half a node interval, eccentricity 0.15: the whole matrix is off by 7.3e-4 relative at
+ * 31 nodes per revolution ((n dt)^3 = 1.15e-3) and 2.0e-5 at 101 (3.1e-5); the velocity rows alone by 1.4e-4 and 1.2e-6.
+ * The rate at which probability enters the sphere |rho| = R is (Rice; Coppola), with x = R n - d on the unit sphere,
+ *   rate(tau) = R^2 oint N_3(R n; d, A) E[(-n . nu)^+ | rho = R n] dOmega,   E = s phi(v0 / s) - v0 Phi(-v0 / s),
+ *   v0 = n . (w + B A^-1 x),   s^2 = n^T (D - B A^-1 B^T) n   (s^2 <= 0: E = max(-v0, 0)),
+ * evaluated through A = L L^T (closed form; a pivot that is not positive and finite at any time node, or a relative speed or a
+ * result that is not finite: MPCX_ST_NUMERIC): z = L^-1 x, N_3 = (2 pi)^-3/2 exp(-|z|^2 / 2) / det L, B A^-1 x = W z with W = B L^-T,
+ * D - B A^-1 B^T = D - W W^T.  The result is
+ *   START + ENTRIES,   START = P(|rho(t_a)| <= R) (a ball integral),   ENTRIES = int_t_a^t_b rate dtau,
+ * the probability of being inside at t_a plus the expected number of entries.  That is the probability of a collision in the
+ * window exactly when no sample path enters the sphere twice in it, and an UPPER BOUND otherwise; P = min(1, START + ENTRIES).
+ * Intended use: one window per event of mpcx_conjunction_events, joined per pair as independent events.
+ * Fixed rules, no adaptivity.  Time: `panels` equal panels of [t_a, t_b], the 64-point Gauss-Legendre rule on each.  Sphere: the
+ * pole along w(tau) (|w| = 0: the x axis), e_1 from the coordinate axis on which the pole's component is smallest (the |m| = 0 rule
+ * above), e_2 = pole x e_1; cos theta split at the equator -- without velocity uncertainty the integrand has a kink on n . w = 0 --
+ * with 8 Gauss-Legendre nodes on [-1, 0] and 8 on [0, 1], times 32 azimuths (k + 1/2) 2 pi / 32: 512 points.  Ball: 8
+ * Gauss-Legendre radii on [0, R] times the same sphere rule, at t_a.
+ * Accuracy domain of the rules (tests/test_collision_window_host.py).  Against mpcx_collision_probability's integral in its own
+ * domain (7 km/s, no velocity uncertainty, window +-(8 sigma_max + R) / |w|, misses up to 2 sigma, anisotropic): relative error
+ * 1.3e-14 for R / sigma_min <= 2 and 8.8e-7 at 4 with 4 panels, 4.7e-7 for R / sigma_min <= 2 with 1 panel.  Ball term against the
+ * non-central chi-square (misses up to 3 sigma): 1.2e-15 for R / sigma <= 1, 2.1e-11 at 2.  A slow encounter with velocity
+ * uncertainty (0.25 m/s over 1200 s, R = 30 m, sigma 40 .. 120 m) against 400 000 sampled straight paths: 0.045460 at 1, 2 and 4
+ * panels, inside the sampling error 3.3e-4.  The window must resolve the rate: in those cases a panel is 4 (8 sigma_max + R) / |w|
+ * long at 1 panel and a quarter of that at 4.
+ * out [n][MPCX_NPW] (MPCX_PW_*), status [n]; a row whose status is not MPCX_ST_OK is NaN in every column; the other rows are
+ * untouched by it.  n < 1, S < 1, K < 2, mu <= 0, a catalogue with D < 1 or cat_K < 2, panels outside 1 .. MPCX_PW_MAX_PANELS, a
+ * required array NULL: MPCX_E_BADARG, nothing enqueued.  The _dev variant takes device pointers throughout and needs no workspace.
+ */
+enum { MPCX_PW_P = 0,       /* min(1, START + ENTRIES) */
+       MPCX_PW_START,       /* P(|rho(t_a)| <= R) */
+       MPCX_PW_ENTRIES,     /* the expected number of entries into the sphere over [t_a, t_b] */
+       MPCX_PW_RATE_MAX,    /* the largest rate at a time node, 1/s */
+       MPCX_PW_T_RATE_MAX,  /* its time (the earliest of equal ones), s */
+       MPCX_PW_TA,          /* the window used, s */
+       MPCX_PW_TB,
+       MPCX_NPW };
+enum { MPCX_PW_MAX_PANELS = 64 };
+int mpcx_collision_probability_window(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                      const double *units, const double *span, const double *P, const double *radius, int D,
+                                      int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units,
+                                      const double *cat_span, const double *cat_P, const double *cat_radius, double mu,
+                                      const double *half_window, int panels, double *out, int32_t *status);
+int mpcx_collision_probability_window_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                          const double *units, const double *span, const double *P, const double *radius, int D,
+                                          int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units,
+                                          const double *cat_span, const double *cat_P, const double *cat_radius, double mu,
+                                          const double *half_window, int panels, double *out, int32_t *status, void *stream);
+
+/*
  * Avoidance manoeuvres for screened pairs from thrust sensitivities.  The screens say who comes close and when, the probability how
  * much that matters; this says what to change in the plan.  For every row (i, j, distance, time t in s) of a pairs list: the
  * derivative of the encounter-plane miss with respect to every thrust node of the plan (the B-plane sensitivity), by a backward

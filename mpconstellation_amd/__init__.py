@@ -14,7 +14,8 @@ from .atmosphere import Atmosphere
 from . import conjunction
 from .conjunction import (common_clock, screen, screen_against, screen_pairs, screen_events, screen_track, EncounterEvents, cumulative_probability,
                           catalogue_trajectories, ConjunctionResult, covariance,
-                          collision_probability, catalogue_covariance, CollisionResult, avoidance, AvoidanceResult,
+                          collision_probability, catalogue_covariance, CollisionResult, collision_probability_window,
+                          encounter_half_window, WindowCollisionResult, avoidance, AvoidanceResult,
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult)
 
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
@@ -22,5 +23,6 @@ __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer
            "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC", "Atmosphere",
            "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "screen_events", "screen_track", "EncounterEvents",
            "cumulative_probability", "catalogue_trajectories", "ConjunctionResult", "covariance",
-           "collision_probability", "catalogue_covariance", "CollisionResult", "avoidance", "AvoidanceResult",
+           "collision_probability", "catalogue_covariance", "CollisionResult", "collision_probability_window", "encounter_half_window",
+           "WindowCollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult"]

@@ -160,6 +160,11 @@ _SIGS = {
     "mpcx_collision_probability": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2 + [C.c_double, _dp, _ip]),
     "mpcx_collision_probability_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
                                        + [C.c_double, _vp, _vp, _vp]),
+    # the same list over a time window: the ball at its start plus the expected entries, from the full 6 x 6 covariances
+    "mpcx_collision_probability_window": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2
+                                          + [C.c_double, _dp, C.c_int, _dp, _ip]),
+    "mpcx_collision_probability_window_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
+                                              + [C.c_double, _vp, C.c_int, _vp, _vp, _vp]),
     # avoidance manoeuvres for screened pairs: thrust sensitivities of the encounter-plane miss, least-effort thrust change
     "mpcx_avoidance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mpcx_avoidance": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
@@ -197,6 +202,8 @@ _SIGS = {
 }
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
+NPW, PW_MAX_PANELS = 7, 64                                                  # MPCX_NPW: columns of mpcx_collision_probability_window's out
+PW_P, PW_START, PW_ENTRIES, PW_RATE_MAX, PW_T_RATE_MAX, PW_TA, PW_TB = range(NPW)
 NAV = 10                                                                    # MPCX_NAV: columns of mpcx_avoidance's out
 AV_D0, AV_D1, AV_DM1, AV_DM2, AV_MISS1, AV_DT, AV_DV_I, AV_DV_J, AV_UMAX_I, AV_UMAX_J = range(NAV)
 NAJ, NAR, AJ_MAX_ROWS = 8, 5, 8                                             # MPCX_NAJ, MPCX_NAR: columns of mpcx_avoidance_joint's sat_out, row_out

@@ -16,6 +16,9 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
+  collision_probability_window   for encounters too slow for that model (neighbours in one shell, satellites deployed together):
+                 the probability over a time window from the time-varying relative state and the full 6 x 6 covariances;
+                 encounter_half_window is the window inside which the two models must agree;
   catalogue_covariance    catalogue_trajectories followed by covariance;
   avoidance      for every listed pair the derivative of the encounter-plane miss with respect to every thrust node of the plan, and
                  the least-effort thrust change that opens the miss to a requested distance.
@@ -416,9 +419,10 @@ def screen_track(pairs, T0, T1, max_shift=None, eph=None, cat_eph=None, device=0
 def cumulative_probability(events, pc):
     """The probability of at least one collision per list row of `events` (EncounterEvents): 1 - prod (1 - pc_e) over the row's
     events, taken as -expm1(sum log1p(-pc_e)) so that many small probabilities add up without cancellation.  pc (n_ev,): the
-    events' probabilities, row for row of events.events (collision_probability(events.events, ...).pc, or that CollisionResult).
+    events' probabilities, row for row of events.events (collision_probability(events.events, ...).pc, or that CollisionResult; a
+    WindowCollisionResult of collision_probability_window over the same rows gives its p, one window per event).
     A row with an event whose pc is NaN is NaN; a row without events is 0.  The encounters are taken as independent."""
-    pc = np.asarray(pc.pc if isinstance(pc, CollisionResult) else pc, dtype=np.float64)
+    pc = np.asarray(pc.pc if isinstance(pc, CollisionResult) else pc.p if isinstance(pc, WindowCollisionResult) else pc, dtype=np.float64)
     if pc.shape != events.row.shape:
         raise ValueError(f"pc: expected ({len(events.row)},) probabilities, one per stored event, got {pc.shape}")
     total = np.zeros(len(events.count))
@@ -639,6 +643,107 @@ def _collision_call(pairs, *, device, slot, out, rows, cols, mu):
     pairs = _ffi.as_f64(pairs)
     _ffi.call("mpcx_collision_probability", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
               _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+
+
+# ---- the same list over a time window (include/mpcx.h: mpcx_collision_probability_window; csrc/collision_window.hip)
+DEFAULT_PANELS = 4
+
+
+class WindowCollisionResult:
+    """For the n rows of `pairs` (i, j, distance, time), row for row: p (n,) = min(1, start + entries), start (n,) the probability
+    of being within the summed radii at the window's start, entries (n,) the expected number of entries into that sphere during
+    the window, rate_max (n,) the largest entry rate at a time node (1/s) and t_rate_max (n,) its time (s), window (n, 2) the window
+    used (the requested one cut to both objects' spans), status (n,) int32 MPCX_ST_* (a row whose status is not 0 is NaN in all of
+    them)."""
+
+    def __init__(self, pairs, out, status):
+        self.pairs, self.status = pairs, status
+        self.p, self.start, self.entries = out[:, _ffi.PW_P], out[:, _ffi.PW_START], out[:, _ffi.PW_ENTRIES]
+        self.rate_max, self.t_rate_max, self.window = out[:, _ffi.PW_RATE_MAX], out[:, _ffi.PW_T_RATE_MAX], out[:, _ffi.PW_TA:_ffi.PW_TB + 1]
+
+    def __repr__(self):
+        return f"WindowCollisionResult(pairs={len(self.pairs)})"
+
+
+def encounter_half_window(col, radius_sum, nsigma=8):
+    """(nsigma sigma_1 + R) / speed per row of a CollisionResult, in seconds: the half window about the closest approach outside
+    which the short-encounter model puts no probability -- the window inside which collision_probability_window and
+    collision_probability must agree where the latter holds.  radius_sum: a scalar or (n,) summed hard-body radii R (m).  inf
+    where the speed is 0 or NaN (a failed row, an encounter without relative motion): the caller chooses a window there."""
+    if not isinstance(col, CollisionResult):
+        raise ValueError(f"col: expected a CollisionResult, got {type(col).__name__}")
+    n = len(col.speed)
+    if np.ndim(radius_sum) not in (0, 1) or (np.ndim(radius_sum) == 1 and np.shape(radius_sum) != (n,)):
+        raise ValueError(f"radius_sum: expected a scalar or ({n},) summed radii in m, got {np.shape(radius_sum)}")
+    if not (np.ndim(nsigma) == 0 and nsigma > 0.0):
+        raise ValueError(f"nsigma: need a number > 0, got {nsigma}")
+    R = np.broadcast_to(np.asarray(radius_sum, dtype=np.float64), (n,))
+    speed = np.asarray(col.speed, dtype=np.float64)
+    moving = speed > 0.0                                                 # (False for NaN)
+    h = np.full(n, np.inf)
+    h[moving] = (float(nsigma) * np.asarray(col.sigma, dtype=np.float64)[moving, 0] + R[moving]) / speed[moving]
+    return h
+
+
+def collision_probability_window(pairs, radius, Y, units, span, P, half_window, panels=DEFAULT_PANELS, ns=None, cat=None, mu=None,
+                                 device=0, devices=None):
+    """The collision probability of every listed row over the time window [t - half_window, t + half_window] about the row's time
+    -> WindowCollisionResult.  For encounters the short-encounter model of collision_probability does not cover: relative speeds of
+    cm/s to m/s over minutes to a revolution, down to no relative motion at all.  pairs: (n, 4) rows (i, j, distance, time in s), a
+    ConjunctionResult or an EncounterEvents (its .events: one window per event); radius, Y, units, span, P [, ns], cat and mu exactly
+    as collision_probability takes them; half_window a scalar or (n,) of seconds (encounter_half_window for rows that have a
+    relative speed); panels: the window is cut into that many equal panels of 64 time nodes (1 .. 64).  At every time node both
+    objects' states come from their own nodes and their full 6 x 6 covariances are carried over from the nearest node; the result
+    is the probability of being within the summed radii at the window's start plus the expected number of entries into that sphere
+    during the window (a sphere integral of 512 points per time node): the probability of a collision in the window when no path
+    enters twice, an upper bound otherwise (include/mpcx.h).  The window is cut to both objects' spans; a half window that is not
+    positive and finite, or an empty cut window, is status 9 for that row.  An empty list returns empty arrays without a library call.
+    devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices (every device holds all trajectories), written in
+    place, the bits of one device."""
+    from .constants import MU_EARTH
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    elif isinstance(pairs, EncounterEvents):
+        pairs = pairs.events
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time), a ConjunctionResult or an EncounterEvents, got {pairs.shape}")
+    rows = _check_side(Y, units, span, P, radius, ns)
+    cols = None
+    if cat is not None:
+        if len(cat) not in (5, 6):
+            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
+        cols = _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
+    mu = float(MU_EARTH if mu is None else mu)
+    if not mu > 0.0:
+        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    n = pairs.shape[0]
+    if half_window is None or np.ndim(half_window) not in (0, 1) or (np.ndim(half_window) == 1 and np.shape(half_window) != (n,)):
+        raise ValueError(f"half_window: expected a scalar or ({n},) seconds, got {None if half_window is None else np.shape(half_window)}")
+    half = _ffi.per_sat(half_window, n)
+    if np.ndim(panels) != 0 or int(panels) != panels or not 1 <= panels <= _ffi.PW_MAX_PANELS:
+        raise ValueError(f"panels: need an integer in 1 .. {_ffi.PW_MAX_PANELS}, got {panels}")
+    out = dict(out=np.empty((n, _ffi.NPW)), status=np.zeros(n, dtype=np.int32))
+    if n:
+        how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels))
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(_collision_window_call, devices, [pairs, half], out, **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            _collision_window_call(pairs, half, device=device, slot=0, out=out, **how)
+    return WindowCollisionResult(pairs, out["out"], out["status"])
+
+
+def _collision_window_call(pairs, half, *, device, slot, out, rows, cols, mu, panels):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    def side(sd):
+        Y, units, span, P, radius, ns = sd if sd is not None else (None,) * 6
+        return _side_args(Y, units, span, ns, P) + (_ffi.dptr_opt(radius),)
+    pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
+    _ffi.call("mpcx_collision_probability_window", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
+              _ffi.dptr(half), panels, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
 
 
 def catalogue_covariance(position_m, velocity_m_s, P0, T0, T1, n, q=None, include_J2=True, max_step=DEFAULT_MAX_STEP, device=0,

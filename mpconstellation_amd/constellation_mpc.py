@@ -347,6 +347,33 @@ class ConstellationMPC:
                           include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
 
+    def collision_probability_window(self, threshold_m, P0, radius_m, half_window, panels=4, q=None, samples_per_node=4, max_pairs=None,
+                                     catalogue=None):
+        """collision_probability and the window probability of the same rows -> (ConjunctionResult, CollisionResult,
+        WindowCollisionResult).  The screening arguments, P0, radius_m, q and catalogue are collision_probability's, and the first two
+        results are what it returns; every listed pair also gets its probability over [t - half_window, t + half_window]
+        (conjunction.collision_probability_window on the same plan, covariances and radii; half_window a scalar or one per listed
+        pair, in seconds; panels as there).  For the pairs of a constellation that pass each other slowly the short-encounter figure
+        is outside its model, and without relative speed it fails: the window figure is the one to read there.  The plan only."""
+        from . import conjunction as cj
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        cat = None
+        if catalogue is None:
+            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
+        else:
+            if len(catalogue) not in (5, 6):
+                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
+            cat = tuple(catalogue)
+            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
+                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
+        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
+                          include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+        plan = dict(ns=w["ns"], cat=cat, **where)
+        return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
+                cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
+
     def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
         """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the
         constellation, or against catalogue = (Y, units, span[, P][, ns])), the plan's covariance when P0 is given, the catalogue as

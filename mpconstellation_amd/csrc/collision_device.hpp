@@ -6,6 +6,8 @@
 //   the thrust sensitivities       cp_mover (what a manoeuvring object brings to the sweep), cp_sweep_seed, cp_sweep_node (one node of
 //                                  the adjoint recursion, g_m stored), aj_sweep (the recursion for NR rows on a whole wave)
 //   cp_wave_sum, cp_wave_max       the xor butterfly: every lane ends with the same bits
+//   CP_GL                          the 64-point Gauss-Legendre rule, one copy for collision_probability_kernel and
+//                                  collision_window_kernel (collision_window.hip; its own functions: collision_window_device.hpp)
 // The build contracts a multiply-add only inside one expression: the expressions below are the operation order of all three files
 // (tests/collision_reference.py and tests/avoidance_reference.py restate them).
 #pragma once
@@ -128,6 +130,75 @@ __device__ __forceinline__ int cp_object(const CpSide &sd, double fidx, double t
     radius = sd.radius[nd.o];
     return MPCX_ST_OK;
 }
+
+// numpy.polynomial.legendre.leggauss(64): node, weight on [-1, 1] (collision_probability_kernel; the time rule of
+// collision_window_kernel)
+static __device__ const double CP_GL[64][2] = {
+    {-0x1.ffa4e911f7533p-1, 0x1.d379f1845dc3ap-10},
+    {-0x1.fe204ab274eccp-1, 0x1.0fc7ac3ac343cp-8},
+    {-0x1.fb661ac8c85a9p-1, 0x1.aa46b24145fd3p-8},
+    {-0x1.f777d976cfadap-1, 0x1.21e400109d579p-7},
+    {-0x1.f257e4db5aabcp-1, 0x1.6df524de84ee7p-7},
+    {-0x1.ec09586b58faap-1, 0x1.b9283b35df9afp-7},
+    {-0x1.e490081f2891bp-1, 0x1.01a7c0a5c98e8p-6},
+    {-0x1.dbf07d935a5afp-1, 0x1.261ef40a7a2dbp-6},
+    {-0x1.d22ff5221288ap-1, 0x1.49e391bd2143ep-6},
+    {-0x1.c7545aa8c0dadp-1, 0x1.6cdfe10bba379p-6},
+    {-0x1.bb6445eadae2cp-1, 0x1.8efea346845aep-6},
+    {-0x1.ae66f68eedbc6p-1, 0x1.b02b2071c0c24p-6},
+    {-0x1.a0644fb6d8db8p-1, 0x1.d05133c3af976p-6},
+    {-0x1.9164d335425e2p-1, 0x1.ef5d57d53b4a7p-6},
+    {-0x1.81719c62ec68ep-1, 0x1.069e593b92362p-5},
+    {-0x1.70945a96f12c3p-1, 0x1.14ee9010d92e2p-5},
+    {-0x1.5ed74b4532f83p-1, 0x1.22969f7b5c8c0p-5},
+    {-0x1.4c4533c68b412p-1, 0x1.2f8e3ca7574ecp-5},
+    {-0x1.38e95ace7b3c3p-1, 0x1.3bcd87e50de17p-5},
+    {-0x1.24cf81925487fp-1, 0x1.474d117092814p-5},
+    {-0x1.1003dca600f34p-1, 0x1.5205ddf5a36d5p-5},
+    {-0x1.f52619257c3a1p-2, 0x1.5bf16accdf42fp-5},
+    {-0x1.c9142c5898fc5p-2, 0x1.6509b1efb8df0p-5},
+    {-0x1.9becb55272c9dp-2, 0x1.6d492da0c250dp-5},
+    {-0x1.6dcb1f0620fffp-2, 0x1.74aadbc614fafp-5},
+    {-0x1.3ecb6c46c76cbp-2, 0x1.7b2a40f3ccdd4p-5},
+    {-0x1.0f0a26c56e49cp-2, 0x1.80c36b24bdd16p-5},
+    {-0x1.bd489b79ec83bp-3, 0x1.8572f41fbb52cp-5},
+    {-0x1.5b6e88ad5c00ep-3, 0x1.89360387fe3aap-5},
+    {-0x1.f182ff48e8a27p-4, 0x1.8c0a5097676bap-5},
+    {-0x1.2afad5ee95ad0p-4, 0x1.8dee238192cd4p-5},
+    {-0x1.8ef487a8cbc32p-6, 0x1.8ee0567ee2e54p-5},
+    {0x1.8ef487a8cbc32p-6, 0x1.8ee0567ee2e54p-5},
+    {0x1.2afad5ee95ad0p-4, 0x1.8dee238192cd4p-5},
+    {0x1.f182ff48e8a27p-4, 0x1.8c0a5097676bap-5},
+    {0x1.5b6e88ad5c00ep-3, 0x1.89360387fe3aap-5},
+    {0x1.bd489b79ec83bp-3, 0x1.8572f41fbb52cp-5},
+    {0x1.0f0a26c56e49cp-2, 0x1.80c36b24bdd16p-5},
+    {0x1.3ecb6c46c76cbp-2, 0x1.7b2a40f3ccdd4p-5},
+    {0x1.6dcb1f0620fffp-2, 0x1.74aadbc614fafp-5},
+    {0x1.9becb55272c9dp-2, 0x1.6d492da0c250dp-5},
+    {0x1.c9142c5898fc5p-2, 0x1.6509b1efb8df0p-5},
+    {0x1.f52619257c3a1p-2, 0x1.5bf16accdf42fp-5},
+    {0x1.1003dca600f34p-1, 0x1.5205ddf5a36d5p-5},
+    {0x1.24cf81925487fp-1, 0x1.474d117092814p-5},
+    {0x1.38e95ace7b3c3p-1, 0x1.3bcd87e50de17p-5},
+    {0x1.4c4533c68b412p-1, 0x1.2f8e3ca7574ecp-5},
+    {0x1.5ed74b4532f83p-1, 0x1.22969f7b5c8c0p-5},
+    {0x1.70945a96f12c3p-1, 0x1.14ee9010d92e2p-5},
+    {0x1.81719c62ec68ep-1, 0x1.069e593b92362p-5},
+    {0x1.9164d335425e2p-1, 0x1.ef5d57d53b4a7p-6},
+    {0x1.a0644fb6d8db8p-1, 0x1.d05133c3af976p-6},
+    {0x1.ae66f68eedbc6p-1, 0x1.b02b2071c0c24p-6},
+    {0x1.bb6445eadae2cp-1, 0x1.8efea346845aep-6},
+    {0x1.c7545aa8c0dadp-1, 0x1.6cdfe10bba379p-6},
+    {0x1.d22ff5221288ap-1, 0x1.49e391bd2143ep-6},
+    {0x1.dbf07d935a5afp-1, 0x1.261ef40a7a2dbp-6},
+    {0x1.e490081f2891bp-1, 0x1.01a7c0a5c98e8p-6},
+    {0x1.ec09586b58faap-1, 0x1.b9283b35df9afp-7},
+    {0x1.f257e4db5aabcp-1, 0x1.6df524de84ee7p-7},
+    {0x1.f777d976cfadap-1, 0x1.21e400109d579p-7},
+    {0x1.fb661ac8c85a9p-1, 0x1.aa46b24145fd3p-8},
+    {0x1.fe204ab274eccp-1, 0x1.0fc7ac3ac343cp-8},
+    {0x1.ffa4e911f7533p-1, 0x1.d379f1845dc3ap-10},
+};
 
 __device__ __forceinline__ double cp_wave_sum(double x)
 {
