@@ -983,6 +983,116 @@ int mpcx_avoidance_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, 
                        int32_t *status, void *workspace, void *stream);
 
 /*
+ * mpcx_collision_window_sensitivity: mpcx_collision_probability_window together with its derivative with respect to every thrust
+ * node of the object or objects that move.  mpcx_avoidance aims at a distance in the encounter plane; a slow pair has no such plane
+ * (|w| = 0: MPCX_ST_NUMERIC there), and well before that the plane covariance has dropped what the window model carries.  This is
+ * the derivative a target on the window probability needs.
+ * Arguments: those of mpcx_collision_probability_window (P, radius and, with a catalogue, cat_P, cat_radius required) with the plan
+ * side of mpcx_avoidance -- U, consts, flags, max_step -- and who (0 / 1 / 2: object i, object j, both; 1 and 2 only in the all-pairs
+ * form).  Linearisation: mpcx_avoidance's, word for word -- one mpcx_discretize_stages_ragged_dev per call into the workspace, tf
+ * fixed, x_k+1 = A_k x_k + B_kn[k] u_k + B_kp[k] u_k+1.
+ * What is differentiated.  Q = START + ENTRIES, the unclamped sum (P = min(1, Q) is not).  The thrust moves only the MEAN relative
+ * state (d(tau), w(tau)).  Held fixed: the node covariances and their short-arc carry, the window [t_a, t_b], the row's time, and the
+ * sphere rule's pole (in the continuum the integral does not depend on it).  Neglected with that: the change of the carried
+ * covariance with the moved node states, relative order (n dt)^2 |dr| / |r| through the gravity gradient of the short arc -- for a
+ * manoeuvre of metres on an orbit of 7e6 m below 1e-6 of the covariance --, and the change the manoeuvre makes to the covariance's
+ * own propagation (mpcx_covariance_batch is not run again: P is the caller's).
+ * The state gradient.  With the notation above (x = R n - d, z = L^-1 x, W = B L^-T) and Phi = Phi(-v0 / s):
+ *   dN_3/dd = N_3 L^-T z,   dE/dv0 = -Phi (s^2 <= 0: -1 where v0 < 0, else 0),   dv0/dw = n,   dv0/dd = -L^-T W^T n,
+ * so that per point d(N_3 E)/dd = N_3 L^-T (E z + Phi W^T n) and d(N_3 E)/dw = -N_3 Phi n.  Per time node q, omega_q its weight
+ * (half a panel's length times the Gauss-Legendre weight), with the sphere rule, radii and panels of the window call:
+ *   c_q = omega_q R^2 cden [ L^-T sum wq dens (E z + Phi W^T n)  |  -sum wq dens Phi n ]     (1 x 6: d, then w),
+ * the two sums run with the rate's, point by point in its order, and L^-T is applied once.  The ball term at t_a gives
+ * dSTART/dd = cden L^-T (sum over the ball of N_3's weights times z), lanes and butterfly as for START, and nothing for w.
+ * The adjoint sweep.  An object's position and velocity at tau are linear in its two bracketing node states (cp_state's Hermite;
+ * h.., g.. the position's and the velocity's basis at s, h_n the node spacing in s, h_tau in the object's time unit, V = L / Tu):
+ *   dp/dy_k = L [h00 I | h_tau h10 I | 0],  dv/dy_k = [(L g00 / h_n) I | V g10 I | 0],  node k+1 with h01, h11, g01, g11.
+ * c_q puts sgn (c_q,d dp/dy + c_q,w dv/dy) on each of the two (sgn = -1 for object i, +1 for object j, as in mpcx_avoidance).  The
+ * per-node sources sigma_m (1 x 7, the mass entry 0) are these shares summed over q in ascending order of q, the ball term last.  Then
+ *   lam_ke+1 = sigma_ke+1 (ke the interval of the last time node),  lam_m = lam_m+1 A_m + sigma_m,
+ *   g_m = lam_m+1 B_kn[m] (m <= ke) + lam_m B_kp[m-1] (1 <= m <= ke + 1),   g_m = 0 for m > ke + 1.
+ * Outputs.  out [n][MPCX_NPW]: the bytes mpcx_collision_probability_window returns for the row.  sens [n][NS][3][K]: dQ/du_m per
+ * unit of normalised thrust, NS = 2 in the all-pairs form (slot 0 = i, 1 = j) and 1 with a catalogue; 0 for an object that does not
+ * move.  state_grad [n][64 panels + 1][6] (may be NULL; the other results have the same bits with and without it): the c_q, the ball
+ * term last.  status [n]: the window call's statuses; then, for a row with a sphere, MPCX_ST_BADK for a manoeuvring satellite without
+ * a positive finite tf and the discretiser's status of one, passed on.  A failed row is NaN in out, sens and state_grad; its
+ * neighbours are untouched.  R <= 0: out as the window call gives it, sens = 0, state_grad = 0, MPCX_ST_OK, no mover is looked at.
+ * Argument errors: the window call's and mpcx_avoidance's (who, max_step, flags), MPCX_E_BADARG, nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_collision_window_sensitivity_workspace_bytes(n, S, K,
+ * panels) bytes (the stage records, tf, the discretiser's status, the node sources; 0 for n < 1, S < 1, K < 2 or panels outside
+ * 1 .. MPCX_PW_MAX_PANELS; contents unspecified on entry and exit).  One wave per row, no atomics; results do not depend on the
+ * launch shape, on the block of rows a row is computed in, or on the device count.
+ */
+size_t mpcx_collision_window_sensitivity_workspace_bytes(int n, int S, int K, int panels);
+int mpcx_collision_window_sensitivity(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                      const double *U, const double *units, const double *span, const double *consts, int flags,
+                                      double max_step, const double *P, const double *radius, int D, int cat_K, const int32_t *cat_Ks,
+                                      const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P,
+                                      const double *cat_radius, double mu, const double *half_window, int panels, int who, double *out,
+                                      double *sens, double *state_grad, int32_t *status);
+int mpcx_collision_window_sensitivity_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                          const double *U, const double *units, const double *span, const double *consts, int flags,
+                                          double max_step, const double *P, const double *radius, int D, int cat_K,
+                                          const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                                          const double *cat_P, const double *cat_radius, double mu, const double *half_window, int panels,
+                                          int who, double *out, double *sens, double *state_grad, int32_t *status, void *workspace,
+                                          void *stream);
+
+/*
+ * mpcx_avoidance_window: for every listed row the thrust change of least effort, to first order, that brings the window
+ * probability Q = START + ENTRIES down to target_p (strictly between 0 and 1).  Arguments: those of
+ * mpcx_collision_window_sensitivity, then target_p, tol > 0 and max_eval >= 1.
+ * Direction.  With mpcx_avoidance's effort metric (c_m, w_m, ghat_m = g_m / c_m, g_m the row's sens): steepest descent of Q per unit
+ * of effort, da_m = -ghat_m / w_m and du_m(alpha) = alpha (da_m / c_m) for every object that moves.  Gamma = sum_m |ghat_m|^2 / w_m
+ * (both movers with who = 2; per object lane-strided over the nodes, closed by the butterfly): to first order Q(alpha) = Q(0) -
+ * alpha Gamma.  Gamma not positive and finite: MPCX_ST_SINGULAR -- a row whose two objects are one trajectory (d = 0: Q has a
+ * stationary point there), a window that ends in the first node's reach of no thrust.
+ * Only the dynamics are linearised, not the probability.  The response to du(1) is dx_0 = 0, dx_k+1 = A_k dx_k + B_kn[k] du_k +
+ * B_kp[k] du_k+1, carried to every time node by the Hermite bases above with the sign sgn; Q(alpha) is the window rule -- all 64
+ * panels x 512 points and the ball -- at the means (d + alpha dd, w + alpha dw) with the row's own covariances, frames (the pole of
+ * the unmoved w) and rules.  Q(0) has mpcx_collision_probability_window's bits.
+ * Step.  Q(0) <= target_p (tested first; a row without a sphere is there): du = 0, P1 = P0, everything else 0, MPCX_ST_OK.
+ * Otherwise alpha_1 = Q(0) ln(Q(0) / target_p) / Gamma, the first-order step in ln Q; alpha is doubled until Q(alpha) <= target_p;
+ * then the bracket [lo, hi] is closed on f = ln Q(alpha) - ln target_p by the Illinois rule: alpha = lo + (hi - lo) f_lo / (f_lo -
+ * f_hi), replaced by the middle when it is not strictly inside the bracket; the end that is kept twice running has its f halved.
+ * It stops at the first alpha with |f| <= tol, in either phase.  At most max_eval evaluations of Q(alpha), alpha > 0, are made:
+ * without one left while doubling MPCX_ST_INFEASIBLE, while closing MPCX_ST_MAXITER.  An evaluation that is not finite:
+ * MPCX_ST_NUMERIC.
+ * Outputs.  out [n][MPCX_NAW] (MPCX_AW_*); du [n][NS][3][K] laid out as mpcx_avoidance's; sens [n][NS][3][K] (may be NULL) with
+ * mpcx_collision_window_sensitivity's bits, whatever the manoeuvre's status; status [n]: that call's statuses, then the ones above.
+ * A failed row is NaN in out and du; its neighbours are untouched.  target_p outside (0, 1), tol not positive and finite, max_eval <
+ * 1 and whatever mpcx_collision_window_sensitivity refuses: MPCX_E_BADARG, nothing enqueued.  The _dev variant takes device
+ * pointers throughout and a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K, panels) bytes.  One wave per row; results
+ * do not depend on the launch shape, on the block of rows a row is computed in, or on the device count.
+ * Not done here: the covariances are not propagated again under the manoeuvre, the manoeuvre is not flown and corrected, and these
+ * rows do not enter mpcx_avoidance_joint or mpcx_avoidance_refine (sens is what they would need).
+ */
+enum { MPCX_AW_P0 = 0,      /* Q(0) = START + ENTRIES now (unclamped) */
+       MPCX_AW_P1,          /* Q(alpha), the window rule at the moved means */
+       MPCX_AW_ALPHA,       /* the step along the direction */
+       MPCX_AW_DQ_LINEAR,   /* -alpha Gamma: the first-order prediction, to compare with P1 - P0 */
+       MPCX_AW_DV_I,        /* sum_m w_m |da_m| per object, m/s (0 for one that does not move) */
+       MPCX_AW_DV_J,
+       MPCX_AW_UMAX_I,      /* max_m |du_m| per object, to compare with u_max */
+       MPCX_AW_UMAX_J,
+       MPCX_AW_EVALS,       /* evaluations of Q(alpha) made */
+       MPCX_NAW };
+size_t mpcx_avoidance_window_workspace_bytes(int n, int S, int K, int panels);
+int mpcx_avoidance_window(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y, const double *U,
+                          const double *units, const double *span, const double *consts, int flags, double max_step, const double *P,
+                          const double *radius, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units,
+                          const double *cat_span, const double *cat_P, const double *cat_radius, double mu, const double *half_window,
+                          int panels, int who, double target_p, double tol, int max_eval, double *out, double *du, double *sens,
+                          int32_t *status);
+int mpcx_avoidance_window_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                              const double *U, const double *units, const double *span, const double *consts, int flags,
+                              double max_step, const double *P, const double *radius, int D, int cat_K, const int32_t *cat_Ks,
+                              const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P,
+                              const double *cat_radius, double mu, const double *half_window, int panels, int who, double target_p,
+                              double tol, int max_eval, double *out, double *du, double *sens, int32_t *status, void *workspace,
+                              void *stream);
+
+/*
  * Joint avoidance: all of a satellite's encounters under its thrust limit.  mpcx_avoidance answers every pair on its own; it does
  * not know u_max, the plan's end state or the other pairs of the same satellite.  This call solves, for every satellite that has
  * listed encounters, one small strictly convex problem built from the same sensitivities: one thrust change that opens all of the

@@ -172,6 +172,21 @@ _SIGS = {
     "mpcx_avoidance_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp,
                                      C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    # avoidance for slow encounters: the window probability's derivative with respect to the thrust nodes, a target on that probability
+    "mpcx_collision_window_sensitivity_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mpcx_collision_window_sensitivity": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double,
+                                                    _dp, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int,
+                                                    C.c_int, _dp, _dp, _dp, _ip]),
+    "mpcx_collision_window_sensitivity_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                                        C.c_double, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double,
+                                                        _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mpcx_avoidance_window_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mpcx_avoidance_window": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp,
+                                        C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int, C.c_int, C.c_double,
+                                        C.c_double, C.c_int, _dp, _dp, _dp, _ip]),
+    "mpcx_avoidance_window_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp,
+                                            C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_double,
+                                            C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     # joint avoidance: all of a satellite's encounters under its thrust limit, one small convex problem per manoeuvring satellite
     "mpcx_avoidance_joint_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mpcx_avoidance_joint": (C.c_int, [_vp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
@@ -206,6 +221,9 @@ NPW, PW_MAX_PANELS = 7, 64                                                  # MP
 PW_P, PW_START, PW_ENTRIES, PW_RATE_MAX, PW_T_RATE_MAX, PW_TA, PW_TB = range(NPW)
 NAV = 10                                                                    # MPCX_NAV: columns of mpcx_avoidance's out
 AV_D0, AV_D1, AV_DM1, AV_DM2, AV_MISS1, AV_DT, AV_DV_I, AV_DV_J, AV_UMAX_I, AV_UMAX_J = range(NAV)
+NAW = 9                                                                     # MPCX_NAW: columns of mpcx_avoidance_window's out
+AW_P0, AW_P1, AW_ALPHA, AW_DQ_LINEAR, AW_DV_I, AW_DV_J, AW_UMAX_I, AW_UMAX_J, AW_EVALS = range(NAW)
+AW_DEFAULT_TOL, AW_DEFAULT_MAX_EVAL = 1e-6, 40
 NAJ, NAR, AJ_MAX_ROWS = 8, 5, 8                                             # MPCX_NAJ, MPCX_NAR: columns of mpcx_avoidance_joint's sat_out, row_out
 AJ_COST, AJ_DV, AJ_UMAX, AJ_ROWS, AJ_ACTIVE, AJ_ONBALL, AJ_ITERS, AJ_RESIDUAL = range(NAJ)
 AR_D0, AR_MARGIN, AR_DIST, AR_LAMBDA, AR_DT = range(NAR)

@@ -895,6 +895,157 @@ def _avoidance_call(pairs, *, device, slot, out, rows, cols, mu, target, who, fl
               _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
 
 
+# ---- avoidance for slow encounters (include/mpcx.h: mpcx_collision_window_sensitivity, mpcx_avoidance_window;
+# csrc/collision_window.hip, csrc/avoidance_window.hip)
+class WindowSensitivityResult(WindowCollisionResult):
+    """WindowCollisionResult of the rows -- the bytes collision_probability_window returns -- and sens (n, NS, 3, K): the derivative of
+    start + entries with respect to every thrust node (thrust component, node; the plan's normalised units) of the objects that move
+    (NS = 2: slots i, j; NS = 1 against a catalogue; 0 for one that does not move), state_grad (n, 64 panels + 1, 6) the derivative
+    with respect to the mean relative position and velocity at every time node, weighted, the ball term last, or None."""
+
+    def __init__(self, pairs, out, sens, state_grad, status):
+        super().__init__(pairs, out, status)
+        self.sens, self.state_grad = sens, state_grad
+
+    def __repr__(self):
+        return f"WindowSensitivityResult(pairs={len(self.pairs)})"
+
+
+class AvoidanceWindowResult:
+    """For the n rows of `pairs` (i, j, distance, time), row for row: p0 (n,) the window figure start + entries now and p1 (n,) the
+    same rule at the moved means, alpha (n,) the step, dq_linear (n,) the first-order prediction of p1 - p0, dv (n, 2) the cost per
+    object, sum of w_m |da_m| (m/s), and umax (n, 2) its largest thrust change max_m |du_m| (normalised) -- column 0 object i, column
+    1 object j, 0 for one that does not move --, evals (n,) the evaluations of the window rule made; du (n, NS, 3, K) the thrust
+    change per node in the plan's own units (NS = 2: slots i, j; NS = 1 against a catalogue), sens (n, NS, 3, K) the derivative of
+    start + entries with respect to the thrust nodes or None; status (n,) int32 MPCX_ST_* (a row whose status is not 0 is NaN in out
+    and du)."""
+
+    def __init__(self, pairs, out, du, sens, status):
+        self.pairs, self.du, self.sens, self.status = pairs, du, sens, status
+        self.p0, self.p1, self.alpha, self.dq_linear = out[:, _ffi.AW_P0], out[:, _ffi.AW_P1], out[:, _ffi.AW_ALPHA], out[:, _ffi.AW_DQ_LINEAR]
+        self.dv, self.umax = out[:, _ffi.AW_DV_I:_ffi.AW_DV_J + 1], out[:, _ffi.AW_UMAX_I:_ffi.AW_UMAX_J + 1]
+        self.evals = out[:, _ffi.AW_EVALS]
+        self.out = out
+
+    def __repr__(self):
+        return f"AvoidanceWindowResult(pairs={len(self.pairs)})"
+
+    apply = AvoidanceResult.apply
+
+
+def _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu):
+    """the checks both window avoidance calls make: _encounter_problem's of the list, the plan and the model, and
+    collision_probability_window's of the covariances, the radii, the half windows and the panels -> (pairs, rows, cols, half, mu)"""
+    if who not in _WHO:
+        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
+    if isinstance(pairs, EncounterEvents):
+        pairs = pairs.events
+    if P is None:
+        raise ValueError("P: the covariances at the nodes (covariance) are required")
+    cat3 = None
+    if cat is not None:
+        if len(cat) not in (5, 6):
+            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
+        if who != "i":
+            raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
+        cat3 = (cat[0], cat[1], cat[2], cat[3]) + ((cat[5],) if len(cat) == 6 and cat[5] is not None else ())
+    pairs, Y, U, units, span, consts, ns, P, _, mu = _encounter_problem(pairs, 1.0, Y, U, units, span, consts, ns, P, cat3, max_step, mu)
+    rows = _check_side(Y, units, span, P, radius, ns)
+    cols = None if cat is None else _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
+    n = pairs.shape[0]
+    if half_window is None or np.ndim(half_window) not in (0, 1) or (np.ndim(half_window) == 1 and np.shape(half_window) != (n,)):
+        raise ValueError(f"half_window: expected a scalar or ({n},) seconds, got {None if half_window is None else np.shape(half_window)}")
+    if np.ndim(panels) != 0 or int(panels) != panels or not 1 <= panels <= _ffi.PW_MAX_PANELS:
+        raise ValueError(f"panels: need an integer in 1 .. {_ffi.PW_MAX_PANELS}, got {panels}")
+    return pairs, rows + (U, consts), cols, _ffi.per_sat(half_window, n), mu
+
+
+def _window_run(call, pairs, half, out, how, device, devices):
+    if len(pairs):
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(call, devices, [pairs, half], out, **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            call(pairs, half, device=device, slot=0, out=out, **how)
+
+
+def collision_window_sensitivity(pairs, radius, Y, U, units, span, consts, P, half_window, panels=DEFAULT_PANELS, ns=None, cat=None,
+                                 who="i", include_drag=False, include_J2=False, atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None,
+                                 return_state_gradient=False, device=0, devices=None):
+    """collision_probability_window together with the derivative of start + entries with respect to every thrust node of the objects
+    that move -> WindowSensitivityResult.  pairs, radius, Y, units, span, P, half_window, panels [, ns], cat and mu exactly as
+    collision_probability_window takes them (an EncounterEvents included); U (S, 3, n), consts (S, 8) and include_drag / include_J2 /
+    atmosphere / max_step the plan and the model of its linearisation as avoidance takes them; who = "i", "j" or "both" says which
+    object of a row moves (against a catalogue only "i").  The thrust moves the mean relative state only: the covariances, the window
+    and the row's time are held (include/mpcx.h).  An empty list returns empty arrays without a library call.  devices=[d0, d1,
+    ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
+    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
+    n, K, NS = pairs.shape[0], rows[0].shape[2], 1 if cols is not None else 2
+    out = dict(out=np.empty((n, _ffi.NPW)), sens=_ffi.result_pool.take((n, NS, 3, K)),
+               state_grad=_ffi.result_pool.take((n, 64 * int(panels) + 1, 6)) if return_state_gradient else None,
+               status=np.zeros(n, dtype=np.int32))
+    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
+               max_step=float(max_step), atmosphere=atmosphere)
+    _window_run(_window_sensitivity_call, pairs, half, out, how, device, devices)
+    return WindowSensitivityResult(pairs, out["out"], out["sens"], out["state_grad"], out["status"])
+
+
+def _window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step):
+    """the arguments both calls share, from n to who"""
+    Y, units, span, P, radius, ns, U, consts = rows
+    cY, cunits, cspan, cP, cradius, cns = cols if cols is not None else (None,) * 6
+    return (len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units),
+            _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P), _ffi.dptr(radius), *_side_args(cY, cunits, cspan, cns, cP),
+            _ffi.dptr_opt(cradius), mu, _ffi.dptr(half), panels, who)
+
+
+def _window_sensitivity_call(pairs, half, *, device, slot, out, rows, cols, mu, panels, who, flags, max_step, atmosphere):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_collision_window_sensitivity", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step),
+              _ffi.dptr(out["out"]), _ffi.dptr(out["sens"]), _ffi.dptr_opt(out.get("state_grad")), _ffi.iptr(out["status"]))
+
+
+def avoidance_window(pairs, target_p, radius, Y, U, units, span, consts, P, half_window, panels=DEFAULT_PANELS, ns=None, cat=None,
+                     who="i", tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, include_drag=False, include_J2=False,
+                     atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None, return_sensitivities=False, device=0, devices=None):
+    """The thrust change of least effort, to first order, that brings the window probability of every listed row down to target_p
+    -> AvoidanceWindowResult.  For the rows collision_probability_window is for: pairs too slow for an encounter plane, which
+    avoidance cannot aim at.  The arguments are collision_window_sensitivity's, with target_p strictly between 0 and 1, tol the
+    tolerance on |ln(p1 / target_p)| and max_eval the most evaluations of the window rule a row may use.  The direction is steepest
+    descent of start + entries per unit of effort from its derivative (return_sensitivities=True returns it); the step along it is
+    found on the window rule itself, evaluated at the means moved through the linearised dynamics -- the probability is not
+    linearised -- by doubling and then closing a bracket (include/mpcx.h).  A row at or below target_p gets du = 0; a row without a
+    direction (the same object twice) is status 4, one that runs out of evaluations 8 while doubling and 5 while closing.  The
+    covariances are held as given and the manoeuvre is not flown again here.  An empty list returns empty arrays without a library
+    call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
+    if not (np.ndim(target_p) == 0 and 0.0 < target_p < 1.0):
+        raise ValueError(f"target_p: need a probability strictly between 0 and 1, got {target_p}")
+    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"tol: need a positive finite number, got {tol}")
+    if np.ndim(max_eval) != 0 or int(max_eval) != max_eval or max_eval < 1:
+        raise ValueError(f"max_eval: need an integer >= 1, got {max_eval}")
+    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
+    n, K, NS = pairs.shape[0], rows[0].shape[2], 1 if cols is not None else 2
+    out = dict(out=np.empty((n, _ffi.NAW)), du=_ffi.result_pool.take((n, NS, 3, K)),
+               sens=_ffi.result_pool.take((n, NS, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
+    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
+               max_step=float(max_step), atmosphere=atmosphere, target_p=float(target_p), tol=float(tol), max_eval=int(max_eval))
+    _window_run(_avoidance_window_call, pairs, half, out, how, device, devices)
+    return AvoidanceWindowResult(pairs, out["out"], out["du"], out["sens"], out["status"])
+
+
+def _avoidance_window_call(pairs, half, *, device, slot, out, rows, cols, mu, panels, who, flags, max_step, atmosphere, target_p, tol, max_eval):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_avoidance_window", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step), target_p, tol, max_eval,
+              _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
+
+
 # ---- all of a satellite's encounters under its thrust limit (include/mpcx.h: mpcx_avoidance_joint; csrc/avoidance_joint.hip)
 class AvoidanceJointResult:
     """Per satellite (S,): du (S, 3, K) the thrust change in the plan's own units (zero for a satellite without rows and for nodes

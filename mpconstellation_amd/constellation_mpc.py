@@ -374,6 +374,35 @@ class ConstellationMPC:
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
                 cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
 
+    def avoidance_window(self, threshold_m, P0, radius_m, half_window, target_p, panels=4, q=None, samples_per_node=4, max_pairs=None,
+                         catalogue=None, who="i", tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL):
+        """Avoidance for the last plan's slow close approaches -> (ConjunctionResult, WindowCollisionResult, AvoidanceWindowResult).
+        The plan is screened and its covariance propagated exactly as collision_probability_window does (the same arguments);
+        every listed pair gets its window probability and the thrust change of conjunction.avoidance_window on (plan X, plan U,
+        plan_tf, plan_K) under the planning model's flags and atmosphere that brings that probability down to target_p; who = 'i',
+        'j' or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceWindowResult.apply(plan U, row) is
+        the changed thrust table.  The covariances are not propagated again under the manoeuvre and nothing is flown (DESIGN.md
+        section 8).  The plan only."""
+        from . import conjunction as cj
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
+        cat = None
+        if catalogue is None:
+            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
+        else:
+            if len(catalogue) not in (5, 6):
+                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
+            cat = tuple(catalogue)
+            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
+                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
+        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
+        plan = dict(ns=w["ns"], cat=cat, **where)
+        return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
+                cj.avoidance_window(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
+                                    panels=panels, who=who, tol=tol, max_eval=max_eval, **model, **plan))
+
     def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
         """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the
         constellation, or against catalogue = (Y, units, span[, P][, ns])), the plan's covariance when P0 is given, the catalogue as

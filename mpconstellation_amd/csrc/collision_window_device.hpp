@@ -1,11 +1,16 @@
-// collision_window_device.hpp -- the device functions of collision_window_kernel (collision_window.hip), beside the encounter core
+// collision_window_device.hpp -- the device functions of the kernels of collision_window.hip, beside the encounter core
 // (collision_device.hpp), whose cp_state, CP_GL and butterflies they use.
 //   an object at a time node       cw_covariance_add (the nearest node's 6 x 6 covariance carried over, added to the pair's sum)
 //   the relative state at a node   cw_node: mean (d, w), the sphere rule's frame (cw_pole), the Cholesky factor of the position block
 //                                  and what the conditional velocity needs of the other blocks (cw_factor)
 //   the sphere                     cw_point (point (j, k) of the 512), cw_whiten, cw_rate (the entry rate), cw_ball_share (a lane's
 //                                  64 points of the ball term)
-// The expressions below are the operation order; tests/collision_window_reference.py restates them line by line.
+//   the derivative                 cw_node_at (cw_node, and where the time falls on both objects' nodes), cw_rate_grad and
+//                                  cw_ball_share_grad (the rate and the ball share with their gradients with respect to the mean),
+//                                  cw_unwhiten, cw_basis (the Hermite bases of position and velocity on the bracketing node states):
+//                                  collision_window_sensitivity_kernel and avoidance_window_kernel (avoidance_window.hip)
+// The expressions below are the operation order; tests/collision_window_reference.py restates them line by line, and
+// tests/avoidance_window_reference.py the derivative's.
 #pragma once
 #include "collision_device.hpp"
 
@@ -218,11 +223,12 @@ __device__ __forceinline__ int cw_factor(const double (&Sg)[21], CwNode &nd)
 }
 
 // The pair (fi, fj) at the time tau: both objects by cp_state, their carried covariances summed as they are formed, the frame and
-// the factor.  MPCX_ST_BADK from cp_state, MPCX_ST_NUMERIC from cw_factor or for a relative speed that is not finite.
-__device__ __forceinline__ int cw_node(const CpSide &row, const CpSide &col, double fi, double fj, double tau, double mu, CwNode &nd)
+// the factor.  MPCX_ST_BADK from cp_state, MPCX_ST_NUMERIC from cw_factor or for a relative speed that is not finite.  na, nb: where
+// tau falls on the two objects' nodes.
+__device__ __forceinline__ int cw_node_at(const CpSide &row, const CpSide &col, double fi, double fj, double tau, double mu, CwNode &nd,
+                                          CpNode &na, CpNode &nb)
 {
     double pa[3], va[3], pb[3], vb[3];
-    CpNode na, nb;
     int st = cp_state(row, fi, tau, pa, va, na);
     if (st == MPCX_ST_OK) st = cp_state(col, fj, tau, pb, vb, nb);
     if (st != MPCX_ST_OK) return st;
@@ -236,6 +242,11 @@ __device__ __forceinline__ int cw_node(const CpSide &row, const CpSide &col, dou
     const bool finite = cw_pole(nd);
     st = cw_factor(Sg, nd);
     return st == MPCX_ST_OK && !finite ? MPCX_ST_NUMERIC : st;
+}
+__device__ __forceinline__ int cw_node(const CpSide &row, const CpSide &col, double fi, double fj, double tau, double mu, CwNode &nd)
+{
+    CpNode na, nb;
+    return cw_node_at(row, col, fi, fj, tau, mu, nd, na, nb);
 }
 
 // Point (j, k) of the sphere rule: cos theta node j of 16 (the 8 Gauss-Legendre nodes on [-1, 0], then on [0, 1]: the integrand's
@@ -309,6 +320,101 @@ __device__ __forceinline__ double cw_ball_share(const CwNode &nd, double R, int 
         }
     }
     return wr * acc;
+}
+
+// ---- the derivative with respect to the mean relative state (collision_window_sensitivity_kernel, avoidance_window_kernel)
+
+// L^-T u
+__device__ __forceinline__ void cw_unwhiten(const CwNode &nd, double u0, double u1, double u2, double (&x)[3])
+{
+    x[0] = nd.i00 * u0 + nd.i10 * u1 + nd.i20 * u2;
+    x[1] = nd.i11 * u1 + nd.i21 * u2;
+    x[2] = nd.i22 * u2;
+}
+
+// cw_rate and its derivative with respect to the mean (d, w) at fixed covariance and frame -> the rate (cw_rate's bits: the same
+// expressions), cg = (d rate / d d | d rate / d w).  Per point, with Phi = Phi(-v0 / s) (s2 <= 0: 1 where v0 < 0, else 0):
+//   d/dd [N_3 E] = N_3 L^-T (E z + Phi W^T n),   d/dw [N_3 E] = -N_3 Phi n;
+// the whitened sums u = sum wq dens (E z + Phi W^T n) and v = sum wq dens Phi n run with the rate's, L^-T is applied once.
+__device__ __forceinline__ double cw_rate_grad(const CwNode &nd, double R, double (&cg)[6])
+{
+    double acc = 0.0, u0 = 0.0, u1 = 0.0, u2 = 0.0, v0s = 0.0, v1s = 0.0, v2s = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < CW_NMU; ++j) {
+#pragma unroll 1
+        for (int k = 0; k < CW_NAZ; ++k) {
+            double n[3], z0, z1, z2;
+            const double wq = cw_point(nd, j, k, n);
+            cw_whiten(nd, n, R, z0, z1, z2);
+            const double dens = exp(-0.5 * (z0 * z0 + z1 * z1 + z2 * z2));
+            const double v0 = n[0] * (nd.w[0] + (nd.W[0][0] * z0 + nd.W[0][1] * z1 + nd.W[0][2] * z2))
+                              + n[1] * (nd.w[1] + (nd.W[1][0] * z0 + nd.W[1][1] * z1 + nd.W[1][2] * z2))
+                              + n[2] * (nd.w[2] + (nd.W[2][0] * z0 + nd.W[2][1] * z1 + nd.W[2][2] * z2));
+            const double s2 = n[0] * (nd.Sc[0] * n[0] + nd.Sc[1] * n[1] + nd.Sc[2] * n[2]) + n[1] * (nd.Sc[1] * n[0] + nd.Sc[3] * n[1] + nd.Sc[4] * n[2])
+                              + n[2] * (nd.Sc[2] * n[0] + nd.Sc[4] * n[1] + nd.Sc[5] * n[2]);
+            double E, Phi;
+            if (s2 > 0.0) {
+                const double s = sqrt(s2), a = v0 / s;
+                Phi = 0.5 * erfc(a * CW_INV_SQRT2);
+                E = s * (exp(-0.5 * a * a) * CW_INV_SQRT_2PI) - v0 * Phi;
+            } else {
+                Phi = v0 < 0.0 ? 1.0 : 0.0;
+                E = fmax(-v0, 0.0);
+            }
+            acc = acc + wq * (dens * E);
+            const double wd = wq * dens, wp = wd * Phi;
+            u0 = u0 + wd * (E * z0 + Phi * (nd.W[0][0] * n[0] + nd.W[1][0] * n[1] + nd.W[2][0] * n[2]));
+            u1 = u1 + wd * (E * z1 + Phi * (nd.W[0][1] * n[0] + nd.W[1][1] * n[1] + nd.W[2][1] * n[2]));
+            u2 = u2 + wd * (E * z2 + Phi * (nd.W[0][2] * n[0] + nd.W[1][2] * n[1] + nd.W[2][2] * n[2]));
+            v0s = v0s + wp * n[0]; v1s = v1s + wp * n[1]; v2s = v2s + wp * n[2];
+        }
+    }
+    const double sc = (R * R) * nd.cden;
+    double gd[3];
+    cw_unwhiten(nd, u0, u1, u2, gd);
+    cg[0] = sc * gd[0]; cg[1] = sc * gd[1]; cg[2] = sc * gd[2];
+    cg[3] = -(sc * v0s); cg[4] = -(sc * v1s); cg[5] = -(sc * v2s);
+    return sc * acc;
+}
+
+// cw_ball_share (its bits) and the lane's share gz of the whitened sum of N_3 z over the ball: cden L^-T (the wave's sum of gz) is
+// the derivative of the ball term with respect to d
+__device__ __forceinline__ double cw_ball_share_grad(const CwNode &nd, double R, int lane, double (&gz)[3])
+{
+    const int i = lane >> 3, j0 = 2 * (lane & 7);
+    const double r = R * (0.5 + 0.5 * CP_GL8[i][0]);
+    const double wr = ((0.5 * R) * CP_GL8[i][1]) * (r * r);
+    double acc = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma unroll 1
+    for (int j = j0; j < j0 + 2; ++j) {
+#pragma unroll 2
+        for (int k = 0; k < CW_NAZ; ++k) {
+            double n[3], z0, z1, z2;
+            const double wq = cw_point(nd, j, k, n);
+            cw_whiten(nd, n, r, z0, z1, z2);
+            const double ex = exp(-0.5 * (z0 * z0 + z1 * z1 + z2 * z2));
+            acc = acc + wq * ex;                                         // (cw_ball_share's expression: one multiply-add)
+            const double e = wq * ex;
+            a0 = a0 + e * z0; a1 = a1 + e * z1; a2 = a2 + e * z2;
+        }
+    }
+    gz[0] = wr * a0; gz[1] = wr * a1; gz[2] = wr * a2;
+    return wr * acc;
+}
+
+// How the position (m) and the velocity (m/s) of an object at a time inside interval k of its nodes depend on the two bracketing node
+// states in normalised units, (y_pos[k], y_vel[k], y_pos[k+1], y_vel[k+1]): cp_state's Hermite bases h.. and g.., the position's in
+// mpcx_avoidance's form L [h I | h_tau h I]
+struct CwBasis {
+    double p[4], v[4];
+};
+__device__ __forceinline__ void cw_basis(const CpNode &nd, double L, double Tu, double htau, CwBasis &b)
+{
+    const double sg = nd.sg, s2 = sg * sg;
+    const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
+    const double V = L / Tu;
+    b.p[0] = L * nd.h00; b.p[1] = L * (htau * nd.h10); b.p[2] = L * nd.h01; b.p[3] = L * (htau * nd.h11);
+    b.v[0] = (L * g00) / nd.hn; b.v[1] = V * g10; b.v[2] = (L * g01) / nd.hn; b.v[3] = V * g11;
 }
 
 }  // namespace mpcx

@@ -1,6 +1,6 @@
-// encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint* and mpcx_avoidance_refine* share, and the
-// linearisation step they share with mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the
-// workspace carver.
+// encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint*, mpcx_avoidance_refine*,
+// mpcx_collision_window_sensitivity* and mpcx_avoidance_window* share, and the linearisation step they share with
+// mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver.
 #pragma once
 #include "mpcx_host.hpp"
 
@@ -110,5 +110,30 @@ struct LinWorkspace {
 // the records make the same test and give that satellite MPCX_ST_BADK), then the stage records and the discretiser's status.
 // Reads S, K, Ks, Y, U, units, span, consts, flags, max_step of p.  (collision.hip)
 int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream);
+
+// mpcx_collision_window_sensitivity* as its entry points take it, and as mpcx_avoidance_window* (avoidance_window.hip) runs it
+// first: the problem (its `target` is not read), the window call's own arguments, who moves, the outputs
+struct CwsCall : EncProblem {
+    const double *radius, *cat_radius, *half;
+    int panels, who;
+    double *out, *sens, *state_grad;
+    int32_t *status;
+};
+
+// workspace of the sensitivity: [the linearisation's][node sources n 2 K 6]
+struct CwsWorkspace : LinWorkspace {
+    double *src;
+    void carve_cws(Carver &c, int n, int S, int K)
+    {
+        carve(c, S, K);
+        src = c.take<double>((size_t)n * 2 * K * 6);
+    }
+};
+
+// The argument tests of both calls (`name` in the messages) and the sensitivity kernel on linearised stage records.  (collision_window.hip)
+int cws_check(mpcx_ctx *ctx, const CwsCall &c, const char *name, bool outputs_given, const char *outputs);
+int cws_enqueue(mpcx_ctx *ctx, const CwsCall &c, const CwsWorkspace &ws, hipStream_t stream);
+// the call's host arrays replaced by copies on the device
+void cws_upload(DeviceArena &ar, CwsCall &c);
 
 }  // namespace mpcx
