@@ -1064,8 +1064,9 @@ int mpcx_collision_window_sensitivity_dev(mpcx_ctx *ctx, int n, const double *pa
  * 1 and whatever mpcx_collision_window_sensitivity refuses: MPCX_E_BADARG, nothing enqueued.  The _dev variant takes device
  * pointers throughout and a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K, panels) bytes.  One wave per row; results
  * do not depend on the launch shape, on the block of rows a row is computed in, or on the device count.
- * Not done here: the covariances are not propagated again under the manoeuvre, the manoeuvre is not flown and corrected, and these
- * rows do not enter mpcx_avoidance_joint or mpcx_avoidance_refine (sens is what they would need).
+ * Not done here: the covariances are not propagated again under the manoeuvre and the manoeuvre is not flown and corrected
+ * (mpcx_avoidance_window_refine below does both), and these rows do not enter mpcx_avoidance_joint or mpcx_avoidance_refine (sens
+ * is what they would need).
  */
 enum { MPCX_AW_P0 = 0,      /* Q(0) = START + ENTRIES now (unclamped) */
        MPCX_AW_P1,          /* Q(alpha), the window rule at the moved means */
@@ -1091,6 +1092,80 @@ int mpcx_avoidance_window_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, 
                               const double *cat_radius, double mu, const double *half_window, int panels, int who, double target_p,
                               double tol, int max_eval, double *out, double *du, double *sens, int32_t *status, void *workspace,
                               void *stream);
+
+/*
+ * mpcx_avoidance_window_refine: mpcx_avoidance_window, then `rounds` times on the device: fly the manoeuvre, look at the row again
+ * on what was flown, linearise about it and correct; then fly and look once more -- the answer is returned AS FLOWN.  What
+ * mpcx_avoidance_refine is to the distance-based manoeuvres.  Arguments: those of mpcx_avoidance_window, then prop_max_step > 0 (the
+ * flight's step limit), rounds >= 0, the tracker's grid M, T0, T1 and max_shift, recov (0 / 1) and q [S] (may be NULL: 0; read only
+ * with recov).  M = 0: every row keeps its given time (T0, T1, max_shift are ignored).  M >= 2: the row's time is found again in
+ * every pass by mpcx_conjunction_track_traj_dev of the row AS GIVEN (column 3 of pairs, in every pass: the time is not carried from
+ * pass to pass) on the pass's two trajectories over linspace(T0, T1, M); max_shift <= 0: unlimited.
+ * Rows are independent.  du [n][NS][3][K] is row-private, as mpcx_avoidance_window's: every row flies its own copy of the object or
+ * objects that move for it, two rows that move one satellite do not see each other.  So the call has a block form: any block of
+ * rows gives the bits of the whole list.  (Inside: a virtual constellation of n NS trajectories gathered after pass 0, the list
+ * re-indexed to (r NS, r NS + 1), against a catalogue to (r, j).  Only rows that passed pass 0 are gathered.)
+ * Passes t = 0 .. rounds + 1, a fixed number, all on one stream, nothing read back in between.
+ *   t = 0: mpcx_avoidance_window on the inputs as given; out, du, sens and status have its bits.  A row FLIES when its status is
+ *     MPCX_ST_OK and its ALPHA > 0; who flies never changes.  A failed row is NaN throughout and never flies; a row at or below
+ *     target_p has du = 0, does not fly, and its histories repeat pass 0's figure and the given time.
+ *   t >= 1, flight: for every slot of a flying row that moves U_t = U[o] + du_t-1 and Y_t from Y[o][:, 0] by
+ *     mpcx_propagate_batch_ragged_dev exactly as mpcx_avoidance_refine flies (MPCX_CTRL_SEQUENCE, Kus = n_evals = Ks[o], end_tau = 1,
+ *     tf = (span[1] - span[0]) / units[1], max_step = prop_max_step, columns past Ks[o] zero), under `flags`, the model of the flight
+ *     and of the linearisation.  A slot that does not move keeps the given trajectory.
+ *   t >= 1, time: t_t, the given time (M = 0) or the tracker's.
+ *   t >= 1, covariances: recov = 0: P and cat_P as given.  recov = 1: every moving slot's covariance is mpcx_covariance_batch's chain
+ *     about (Y_t, U_t) from P[o][0] and q[o], over the pass's own stage records (the last pass linearises for this alone).
+ *   t >= 1, figure: Q_t = START + ENTRIES of mpcx_collision_probability_window for (i, j, ., t_t), the row's half_window and
+ *     panels, on the pass's trajectories and covariances: the bits the public call returns for that data.
+ *   1 <= t <= rounds, solve: |ln(Q_t / target_p)| <= tol accepts du_t-1 unchanged with 0 evaluations.  Otherwise g =
+ *     mpcx_collision_window_sensitivity's sens about (Y_t, U_t) (its bits), the unit direction e_m and Gamma_t formed from g exactly
+ *     as mpcx_avoidance_window forms them (the mass row Y_t's), c0 = -sum g_m du_t-1,m summed in the order slot, node, component.
+ *     The unknown is the TOTAL change from the given U, du(alpha) = alpha e: the least-effort change on the linearised constraint with
+ *     the effort measured from the given plan.  Two forward chains over the pass's records give X_e, the response to e, and X_prev,
+ *     the response to du_t-1; Q_t(alpha) is mpcx_avoidance_window's rule with the mean moved by sgn (alpha X_e - X_prev), on the
+ *     pass's frames and covariances.  alpha_1 = (c0 + Q_t ln(Q_t / target_p)) / Gamma_t (with du_t-1 = 0 pass 0's formula); Gamma_t
+ *     not positive and finite: MPCX_ST_SINGULAR; alpha_1 not positive and finite: MPCX_ST_NUMERIC.  On f = ln Q_t(alpha) - ln
+ *     target_p: stop at the first |f| <= tol; f(alpha_1) > 0: double alpha until f <= 0; f(alpha_1) < 0: halve alpha until f > 0;
+ *     then the bracket is closed by pass 0's Illinois rule.  At most max_eval evaluations per pass: none left while bracketing
+ *     MPCX_ST_INFEASIBLE, while closing MPCX_ST_MAXITER; an evaluation that is not finite MPCX_ST_NUMERIC.
+ *   t = rounds + 1: flight, time, covariances and figure only.
+ * A failure at t >= 1 -- the flight's status, the discretiser's, a lost event (+inf, NaN from the tracker: MPCX_ST_BADK), the
+ * figure's or a solve's status -- FREEZES the row: it keeps du_t-1, reports the status in `status`, is not solved again, keeps
+ * flying du_t-1, and its histories continue.
+ * Outputs.  out [n][MPCX_NAW]: P0 is pass 0's Q; P1, ALPHA and DQ_LINEAR = c0 - alpha Gamma_t of the last accepted solve (a pass
+ * accepted with 0 evaluations sets P1 = Q_t alone); DV_* and UMAX_* of the total du; EVALS summed over the passes.  du: the total
+ * change.  status [n].  rounds_done [n]: the last pass whose solve was accepted (-1: none, or the row does not fly).  Y_out
+ * [n][NS][7][K]: the last flight; a slot that does not move is a copy of the given trajectory.  P_out [n][NS][K][6][6] (may be NULL;
+ * written with recov).  hist_p, hist_t [rounds + 2][n]: Q_t and t_t (pass 0: Q(0), the given time).  hist_pred [rounds + 1][n]: each
+ * solve's P1, NaN where nothing was solved.  sens (may be NULL): of the last pass that linearised for a solve.
+ * Argument errors: mpcx_avoidance_window's, and rounds < 0, prop_max_step <= 0, M = 1, M < 0, T1 <= T0 or a NaN max_shift with
+ * M >= 2, recov outside 0 / 1, a missing required output (P_out and sens alone may be NULL): MPCX_E_BADARG, nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_avoidance_window_refine_workspace_bytes(n, S, K, D, M,
+ * panels) bytes (D = 0 without a catalogue; 0 for n < 1, S < 1, K < 2, D < 0, M = 1, M < 0 or panels outside 1 ..
+ * MPCX_PW_MAX_PANELS).  One wave per row, no atomics, every sum in a fixed order: results do not depend on the launch shape, on the
+ * block of rows a row is computed in, on which optional outputs are asked for, or on the device count.
+ * Not done here: these rows do not enter mpcx_avoidance_joint (two rows of one satellite get two manoeuvres), and the row's time is
+ * not carried from pass to pass.
+ */
+size_t mpcx_avoidance_window_refine_workspace_bytes(int n, int S, int K, int D, int M, int panels);
+int mpcx_avoidance_window_refine(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                 const double *U, const double *units, const double *span, const double *consts, int flags,
+                                 double max_step, const double *P, const double *radius, int D, int cat_K, const int32_t *cat_Ks,
+                                 const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P,
+                                 const double *cat_radius, double mu, const double *half_window, int panels, int who, double target_p,
+                                 double tol, int max_eval, double prop_max_step, int rounds, int M, double T0, double T1,
+                                 double max_shift, int recov, const double *q, double *out, double *du, double *sens, int32_t *status,
+                                 int32_t *rounds_done, double *Y_out, double *P_out, double *hist_p, double *hist_t, double *hist_pred);
+int mpcx_avoidance_window_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                     const double *U, const double *units, const double *span, const double *consts, int flags,
+                                     double max_step, const double *P, const double *radius, int D, int cat_K, const int32_t *cat_Ks,
+                                     const double *cat_Y, const double *cat_units, const double *cat_span, const double *cat_P,
+                                     const double *cat_radius, double mu, const double *half_window, int panels, int who,
+                                     double target_p, double tol, int max_eval, double prop_max_step, int rounds, int M, double T0,
+                                     double T1, double max_shift, int recov, const double *q, double *out, double *du, double *sens,
+                                     int32_t *status, int32_t *rounds_done, double *Y_out, double *P_out, double *hist_p,
+                                     double *hist_t, double *hist_pred, void *workspace, void *stream);
 
 /*
  * Joint avoidance: all of a satellite's encounters under its thrust limit.  mpcx_avoidance answers every pair on its own; it does

@@ -17,7 +17,8 @@ from .conjunction import (common_clock, screen, screen_against, screen_pairs, sc
                           collision_probability, catalogue_covariance, CollisionResult, collision_probability_window,
                           encounter_half_window, WindowCollisionResult, avoidance, AvoidanceResult,
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult,
-                          collision_window_sensitivity, WindowSensitivityResult, avoidance_window, AvoidanceWindowResult)
+                          collision_window_sensitivity, WindowSensitivityResult, avoidance_window, AvoidanceWindowResult,
+                          avoidance_window_refine, AvoidanceWindowRefineResult)
 
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
@@ -27,4 +28,5 @@ __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer
            "collision_probability", "catalogue_covariance", "CollisionResult", "collision_probability_window", "encounter_half_window",
            "WindowCollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult",
-           "collision_window_sensitivity", "WindowSensitivityResult", "avoidance_window", "AvoidanceWindowResult"]
+           "collision_window_sensitivity", "WindowSensitivityResult", "avoidance_window", "AvoidanceWindowResult",
+           "avoidance_window_refine", "AvoidanceWindowRefineResult"]

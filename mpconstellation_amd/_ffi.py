@@ -187,6 +187,18 @@ _SIGS = {
     "mpcx_avoidance_window_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp,
                                             C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, C.c_int, C.c_int, C.c_double,
                                             C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the window manoeuvre flown, re-evaluated and corrected, a fixed number of rounds on the device (after max_eval: prop_max_step,
+    # rounds, M, T0, T1, max_shift, recov, q)
+    "mpcx_avoidance_window_refine_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mpcx_avoidance_window_refine": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                               _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp, C.c_int, C.c_int,
+                                               C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double,
+                                               C.c_double, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "mpcx_avoidance_window_refine_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double,
+                                                   _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, C.c_int,
+                                                   C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
+                                                   C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp]),
     # joint avoidance: all of a satellite's encounters under its thrust limit, one small convex problem per manoeuvring satellite
     "mpcx_avoidance_joint_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mpcx_avoidance_joint": (C.c_int, [_vp, C.c_int, _dp, _ip, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,

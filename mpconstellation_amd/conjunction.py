@@ -1046,6 +1046,100 @@ def _avoidance_window_call(pairs, half, *, device, slot, out, rows, cols, mu, pa
               _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
 
 
+# ---- the window manoeuvre flown, re-evaluated and corrected (include/mpcx.h: mpcx_avoidance_window_refine;
+# csrc/avoidance_window_refine.hip)
+class AvoidanceWindowRefineResult(AvoidanceWindowResult):
+    """AvoidanceWindowResult of the last accepted solve -- p0 is pass 0's figure, du the total change from the given U, evals summed
+    over the passes -- with the answer as flown: Y_flown (n, NS, 7, K) every row's own last flight (a slot that does not move is a
+    copy of the given trajectory), P_flown (n, NS, K, 6, 6) the covariances of that flight or None (recov), p_history and t_history
+    (rounds + 2, n) each pass's window figure start + entries and the time it was taken about (pass 0: the given list; a row that
+    does not fly repeats both), p_predicted (rounds + 1, n) each solve's p1 (NaN where nothing was solved), rounds_done (n,) int32
+    the last pass whose solve was accepted (-1: none, or the row does not fly).  A row whose later flight, linearisation, tracking or
+    solve failed keeps its earlier du and reports the failure in status (apply raises for it as for any status that is not 0; U + du
+    is there to be taken)."""
+
+    def __init__(self, pairs, out, du, sens, status, Y_flown, P_flown, p_history, t_history, p_predicted, rounds_done):
+        super().__init__(pairs, out, du, sens, status)
+        self.Y_flown, self.P_flown, self.p_history, self.t_history = Y_flown, P_flown, p_history, t_history
+        self.p_predicted, self.rounds_done = p_predicted, rounds_done
+
+    def __repr__(self):
+        return f"AvoidanceWindowRefineResult(pairs={len(self.pairs)}, passes={len(self.p_history)})"
+
+
+def avoidance_window_refine(pairs, target_p, radius, Y, U, units, span, consts, P, half_window, rounds=2, track=None, max_shift=None,
+                            recov=False, q=None, prop_max_step=1e-3, panels=DEFAULT_PANELS, ns=None, cat=None, who="i",
+                            tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, include_drag=False, include_J2=False,
+                            atmosphere=None, max_step=DEFAULT_MAX_STEP, mu=None, return_sensitivities=False, return_covariances=True,
+                            device=0, devices=None):
+    """avoidance_window, then `rounds` times on the device: fly U + du through the nonlinear dynamics (include_drag / include_J2 /
+    atmosphere are the model of the flight and of the linearisation; prop_max_step the flight's step limit), take the window figure
+    again on what was flown, linearise about it and solve again for the TOTAL change from the given U -- and once more fly and look
+    -> AvoidanceWindowRefineResult, the answer as flown.  All other arguments as avoidance_window takes them.  rounds = 0 is
+    avoidance_window followed by one flight and one figure.  track = (M, T0, T1): every row's time is found again in every pass by
+    screen_track of the row AS GIVEN on the pass's trajectories over linspace(T0, T1, M), at most max_shift seconds away (None or
+    <= 0: unlimited); a row that loses its event is frozen with MPCX_ST_BADK = 9.  track = None: every row keeps its given time.
+    recov=True: the covariances of every object that moves are propagated again along its flight (covariance's chain from P[o][0]
+    and q, a scalar or (S,), None: 0) and returned as P_flown (return_covariances=False: not returned); False: P is held as given.
+    Rows are independent -- every row flies its own copy of the objects that move for it, two rows that move one satellite do not see
+    each other -- so nothing is installed anywhere and the call has a block form: devices=[d0, d1, ...] deals contiguous blocks of
+    the list's rows to several devices, written in place, the bits of one device.  An empty list returns empty arrays without a
+    library call."""
+    if not (np.ndim(target_p) == 0 and 0.0 < target_p < 1.0):
+        raise ValueError(f"target_p: need a probability strictly between 0 and 1, got {target_p}")
+    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"tol: need a positive finite number, got {tol}")
+    if np.ndim(max_eval) != 0 or int(max_eval) != max_eval or max_eval < 1:
+        raise ValueError(f"max_eval: need an integer >= 1, got {max_eval}")
+    if not (np.ndim(rounds) == 0 and int(rounds) == rounds and rounds >= 0):
+        raise ValueError(f"rounds: need an integer >= 0, got {rounds}")
+    if not prop_max_step > 0.0:
+        raise ValueError(f"prop_max_step: need > 0, got {prop_max_step}")
+    if track is None:
+        grid = (0, 0.0, 0.0, 0.0)
+    else:
+        if np.ndim(track) != 1 or len(track) != 3:
+            raise ValueError(f"track: expected None or (M, T0, T1), got {track!r}")
+        grid = (*_check_grid(*track), _check_max_shift(max_shift))
+    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
+    (S, _, K), n, NS, rounds, recov = rows[0].shape, pairs.shape[0], 1 if cols is not None else 2, int(rounds), bool(recov)
+    q = _check_q(q, S) if recov else None
+    out = dict(out=np.empty((n, _ffi.NAW)), du=_ffi.result_pool.take((n, NS, 3, K)),
+               sens=_ffi.result_pool.take((n, NS, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32),
+               rounds_done=np.full(n, -1, dtype=np.int32), Y_flown=_ffi.result_pool.take((n, NS, 7, K)),
+               P_flown=_ffi.result_pool.take((n, NS, K, 6, 6)) if recov and return_covariances else None)
+    hist = dict(p_history=np.empty((rounds + 2, n)), t_history=np.empty((rounds + 2, n)), p_predicted=np.empty((rounds + 1, n)))
+    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
+               max_step=float(max_step), atmosphere=atmosphere, target_p=float(target_p), tol=float(tol), max_eval=int(max_eval),
+               prop_max_step=float(prop_max_step), rounds=rounds, grid=grid, recov=int(recov), q=q)
+    if n:
+        if devices is not None and len(devices) > 1:
+            from .sharding import sharded_call
+            sharded_call(_avoidance_window_refine_call, devices, [pairs, half], dict(out, **{k: (a, 1) for k, a in hist.items()}), **how)
+        else:
+            if devices is not None and len(devices) == 1:
+                device = int(devices[0])
+            _avoidance_window_refine_call(pairs, half, device=device, slot=0, out=dict(out, **hist), **how)
+    return AvoidanceWindowRefineResult(pairs, out["out"], out["du"], out["sens"], out["status"], out["Y_flown"], out["P_flown"],
+                                       hist["p_history"], hist["t_history"], hist["p_predicted"], out["rounds_done"])
+
+
+def _avoidance_window_refine_call(pairs, half, *, device, slot, out, rows, cols, mu, panels, who, flags, max_step, atmosphere, target_p, tol,
+                                  max_eval, prop_max_step, rounds, grid, recov, q):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views; a block's columns of the histories go
+    through contiguous temporaries)"""
+    pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    hist = {k: out[k] if out[k].flags.c_contiguous else np.empty(out[k].shape) for k in ("p_history", "t_history", "p_predicted")}
+    _ffi.call("mpcx_avoidance_window_refine", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step), target_p, tol,
+              max_eval, prop_max_step, rounds, *grid, recov, _ffi.dptr_opt(q), _ffi.dptr(out["out"]), _ffi.dptr(out["du"]),
+              _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]), _ffi.iptr(out["rounds_done"]), _ffi.dptr(out["Y_flown"]),
+              _ffi.dptr_opt(out.get("P_flown")), _ffi.dptr(hist["p_history"]), _ffi.dptr(hist["t_history"]), _ffi.dptr(hist["p_predicted"]))
+    for k, a in hist.items():
+        if a is not out[k]:
+            out[k][...] = a
+
+
 # ---- all of a satellite's encounters under its thrust limit (include/mpcx.h: mpcx_avoidance_joint; csrc/avoidance_joint.hip)
 class AvoidanceJointResult:
     """Per satellite (S,): du (S, 3, K) the thrust change in the plan's own units (zero for a satellite without rows and for nodes

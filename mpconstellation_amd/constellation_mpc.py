@@ -381,8 +381,8 @@ class ConstellationMPC:
         every listed pair gets its window probability and the thrust change of conjunction.avoidance_window on (plan X, plan U,
         plan_tf, plan_K) under the planning model's flags and atmosphere that brings that probability down to target_p; who = 'i',
         'j' or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceWindowResult.apply(plan U, row) is
-        the changed thrust table.  The covariances are not propagated again under the manoeuvre and nothing is flown (DESIGN.md
-        section 8).  The plan only."""
+        the changed thrust table.  The covariances are not propagated again under the manoeuvre and nothing is flown
+        (avoidance_window_refine does both).  The plan only."""
         from . import conjunction as cj
         (w,) = self._screen_windows("plan", samples_per_node)
         kw = {} if max_pairs is None else {"max_pairs": max_pairs}
@@ -402,6 +402,44 @@ class ConstellationMPC:
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.avoidance_window(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
                                     panels=panels, who=who, tol=tol, max_eval=max_eval, **model, **plan))
+
+    def avoidance_window_refine(self, threshold_m, P0, radius_m, half_window, target_p, rounds=2, model="plan", recov=True, panels=4, q=None,
+                                samples_per_node=4, max_pairs=None, catalogue=None, who="i", track=True, max_shift=None,
+                                tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, prop_max_step=1e-3):
+        """avoidance_window's manoeuvres flown again, re-evaluated and corrected `rounds` times on the device -> (ConjunctionResult,
+        WindowCollisionResult, AvoidanceWindowRefineResult).  The plan is screened and its covariance propagated exactly as
+        avoidance_window does (the same arguments); every listed pair then goes through conjunction.avoidance_window_refine on (plan X,
+        plan U, plan_tf, plan_K): its time is tracked on the plan's screen window (samples_per_node; track=False holds it on the given
+        time), with recov the covariances of the satellites that move are propagated again along every flight with the same q.  model
+        = 'plan' flies and linearises under the planning model (plan_drag, plan_J2), 'truth' under the model the segments are flown
+        with (include_drag, include_J2, the atmosphere).  Nothing is installed: the manoeuvres are row-private, and two rows that move
+        one satellite can conflict (AvoidanceWindowRefineResult.apply(plan U, row) is one row's changed thrust table).  The plan
+        only."""
+        from . import conjunction as cj
+        if model not in ("plan", "truth"):
+            raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        plan_model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
+        cat = None
+        if catalogue is None:
+            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
+        else:
+            if len(catalogue) not in (5, 6):
+                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
+            cat = tuple(catalogue)
+            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
+                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
+        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **plan_model, **where)
+        if model == "truth":
+            plan_model = dict(include_drag=self.include_drag, include_J2=self.include_J2, atmosphere=self.atmosphere if self.include_drag else None)
+        plan = dict(ns=w["ns"], cat=cat, **where)
+        return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
+                cj.avoidance_window_refine(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
+                                           rounds=rounds, track=(w["M"], w["T0"], w["T1"]) if track else None, max_shift=max_shift, recov=recov,
+                                           q=q, prop_max_step=prop_max_step, panels=panels, who=who, tol=tol, max_eval=max_eval, **plan_model,
+                                           **plan))
 
     def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
         """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the

@@ -285,25 +285,19 @@ struct AwWorkspace : CwsWorkspace {
     }
 };
 
-struct AwCall : CwsCall {
-    double tol;
-    int max_eval;
-    double *du;
-};
-
 static const char *const AW_NAME = "avoidance_window";
 
-static int aw_check(mpcx_ctx *ctx, const AwCall &c)
+int aw_check(mpcx_ctx *ctx, const AwCall &c, const char *name)
 {
-    if (int rc = cws_check(ctx, c, AW_NAME, c.out && c.du && c.status, "P, radius, half_window, out, du and status")) return rc;
-    if (!(c.target > 0.0 && c.target < 1.0)) return enc_fail(ctx, AW_NAME, "target_p must lie strictly between 0 and 1");
-    if (!(c.tol > 0.0) || !(c.tol < __builtin_inf())) return enc_fail(ctx, AW_NAME, "tol must be a positive finite number");
-    if (c.max_eval < 1) return enc_fail(ctx, AW_NAME, "max_eval must be >= 1");
+    if (int rc = cws_check(ctx, c, name, c.out && c.du && c.status, "P, radius, half_window, out, du and status")) return rc;
+    if (!(c.target > 0.0 && c.target < 1.0)) return enc_fail(ctx, name, "target_p must lie strictly between 0 and 1");
+    if (!(c.tol > 0.0) || !(c.tol < __builtin_inf())) return enc_fail(ctx, name, "tol must be a positive finite number");
+    if (c.max_eval < 1) return enc_fail(ctx, name, "max_eval must be >= 1");
     return MPCX_OK;
 }
 
 // c.out / c.status are the manoeuvre's; the sensitivity kernel's own go to the workspace
-static int aw_enqueue(mpcx_ctx *ctx, const AwCall &c, void *workspace, hipStream_t st)
+int aw_enqueue(mpcx_ctx *ctx, const AwCall &c, void *workspace, hipStream_t st)
 {
     const AwWorkspace ws(workspace, c.n, c.S, c.K);
     if (int rc = enc_linearise(ctx, c, ws, st)) return rc;
@@ -341,7 +335,7 @@ extern "C" int mpcx_avoidance_window_dev(mpcx_ctx *ctx, int n, const double *pai
     if (!ctx) return MPCX_E_BADARG;
     const AwCall c{{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
                      mu, target_p}, radius, cat_radius, half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du};
-    if (int rc = aw_check(ctx, c)) return rc;
+    if (int rc = aw_check(ctx, c, AW_NAME)) return rc;
     if (!workspace)
         return enc_fail(ctx, AW_NAME, "a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K, panels) bytes is required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
@@ -358,7 +352,7 @@ extern "C" int mpcx_avoidance_window(mpcx_ctx *ctx, int n, const double *pairs, 
     if (!ctx) return MPCX_E_BADARG;
     const AwCall c{{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
                      mu, target_p}, radius, cat_radius, half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du};
-    if (int rc = aw_check(ctx, c)) return rc;
+    if (int rc = aw_check(ctx, c, AW_NAME)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     AwCall d = c;

@@ -105,6 +105,15 @@ __global__ __launch_bounds__(64) void covariance_kernel(CovArgs a)
     }
 }
 
+int cov_enqueue(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const int32_t *dstat, const double *units,
+                const double *span, const double *P0, const double *q, double *P, int32_t *status, hipStream_t stream)
+{
+    const CovArgs a{S, K, Ks, stage, units, span, P0, q, dstat, P, status};
+    hipLaunchKernelGGL(covariance_kernel, dim3((unsigned)S), dim3(64), 0, stream, a);
+    MPCX_HIP(ctx, hipGetLastError());
+    return MPCX_OK;
+}
+
 // workspace of the _dev call: [the linearisation's][zero thrust S 3 K]
 struct CovWorkspace : LinWorkspace {
     double *uzero;
@@ -254,10 +263,7 @@ extern "C" int mpcx_covariance_batch_dev(mpcx_ctx *ctx, int S, int K, const int3
     lin.S = S; lin.K = K; lin.Ks = Ks; lin.Y = X; lin.U = U ? U : ws.uzero; lin.units = units; lin.span = span; lin.consts = consts;
     lin.flags = flags; lin.max_step = max_step;
     if (int rc = enc_linearise(ctx, lin, ws, st)) return rc;
-    const CovArgs a{S, K, Ks, ws.stage, units, span, P0, q, ws.dstat, P, status};
-    hipLaunchKernelGGL(covariance_kernel, dim3((unsigned)S), dim3(64), 0, st, a);
-    MPCX_HIP(ctx, hipGetLastError());
-    return MPCX_OK;
+    return cov_enqueue(ctx, S, K, Ks, ws.stage, ws.dstat, units, span, P0, q, P, status, st);
 }
 
 extern "C" int mpcx_covariance_batch(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U, const double *units,

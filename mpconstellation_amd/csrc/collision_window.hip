@@ -12,7 +12,7 @@
 // The window rule is written three times: here, in collision_window_sensitivity_kernel below (with cw_rate_grad and
 // cw_ball_share_grad beside cw_rate and cw_ball_share) and in aw_eval (avoidance_window.hip).  The copies keep this kernel's
 // registers and bytes as they were; a change to the rule is a change to all three, and tests/test_avoidance_window_gpu.py holds
-// the second to this kernel's bytes.
+// the second to this kernel's bytes.  (A fourth copy, awr_eval in avoidance_window_refine.hip, is aw_eval with two responses.)
 //   collision_window_sensitivity_kernel   the same figure (the same bytes) together with its derivative with respect to every thrust
 //                             node of the objects that move (include/mpcx.h: mpcx_collision_window_sensitivity*): the gradient with
 //                             respect to the mean relative state at every time node, carried onto the bracketing node states and

@@ -1,5 +1,5 @@
 // encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint*, mpcx_avoidance_refine*,
-// mpcx_collision_window_sensitivity* and mpcx_avoidance_window* share, and the linearisation step they share with
+// mpcx_collision_window_sensitivity*, mpcx_avoidance_window* and mpcx_avoidance_window_refine* share, and the linearisation step they share with
 // mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver.
 #pragma once
 #include "mpcx_host.hpp"
@@ -135,5 +135,23 @@ int cws_check(mpcx_ctx *ctx, const CwsCall &c, const char *name, bool outputs_gi
 int cws_enqueue(mpcx_ctx *ctx, const CwsCall &c, const CwsWorkspace &ws, hipStream_t stream);
 // the call's host arrays replaced by copies on the device
 void cws_upload(DeviceArena &ar, CwsCall &c);
+
+// mpcx_avoidance_window* as its entry points take it, and as mpcx_avoidance_window_refine* (avoidance_window_refine.hip) runs it
+// as its pass 0
+struct AwCall : CwsCall {
+    double tol;
+    int max_eval;
+    double *du;
+};
+
+// The argument tests of mpcx_avoidance_window* and the call itself on a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K,
+// panels) bytes.  (avoidance_window.hip)
+int aw_check(mpcx_ctx *ctx, const AwCall &c, const char *name);
+int aw_enqueue(mpcx_ctx *ctx, const AwCall &c, void *workspace, hipStream_t stream);
+
+// mpcx_covariance_batch's chain over stage records that are there already: P [S][K][6][6] and status [S] from P0 [S][6][6], q [S]
+// or NULL.  (collision.hip)
+int cov_enqueue(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *stage, const int32_t *dstat, const double *units,
+                const double *span, const double *P0, const double *q, double *P, int32_t *status, hipStream_t stream);
 
 }  // namespace mpcx
