@@ -15,13 +15,12 @@
 //   pass rounds + 1   the same without the solve: the answer is returned as flown
 // Everything is enqueued on one stream, the number of passes is fixed, nothing is read back in between.  A failure at t >= 1
 // freezes the row: it keeps du_t-1, reports the status, is not solved again and keeps flying.
-// awr_solve_kernel is avoidance_window_kernel about what was flown: one wave per row, the direction and Gamma from the pass's
-// sensitivities, two forward chains over the pass's stage records (the response to the unit direction e and to du_t-1, the two
-// half-waves on the two objects), the window rule at the means moved by sgn (alpha X_e - X_prev), the search from alpha_1 =
-// (c0 + Q_t ln(Q_t / target_p)) / Gamma_t.  The window rule is written here a fourth time (collision_window.hip names the other
-// three): awr_eval is aw_eval with awr_shift between cw_node_at and cw_rate.  No atomics, nothing crosses a workgroup; every sum
+// awr_solve_kernel is avoidance_window_kernel about what was flown, on the same device functions (avoidance_window_device.hpp, with
+// a previous response): one wave per row, the direction and Gamma from the pass's sensitivities, two forward chains over the pass's
+// stage records (the response to the unit direction e and to du_t-1), the window rule at the means moved by sgn (alpha X_e -
+// X_prev), the search from alpha_1 = (c0 + Q_t ln(Q_t / target_p)) / Gamma_t.  No atomics, nothing crosses a workgroup; every sum
 // has a fixed order.  tests/avoidance_window_refine_reference.py restates the loop.
-#include "collision_window_device.hpp"
+#include "avoidance_window_device.hpp"
 #include "encounter_host.hpp"
 
 #include <math.h>
@@ -171,127 +170,17 @@ __global__ __launch_bounds__(256) void awr_hist_kernel(int n, const double *fig,
 
 // ---------------------------------------------------------------- the solve about what was flown
 
-struct AwrArgs {
-    int n, K, NS, who, t;             // K: the row length (stage records, du, sens); NS: slots of du and sens per row; t: the pass
-    const double *pairs;              // the pass's list
-    CpSide row, col;                  // the virtual constellation with the pass's trajectories and covariances; the columns
-    double mu;
-    int panels;
-    const double *stage;              // the pass's linearisation [V][K-1][MPCX_STAGE_DOUBLES] and the discretiser's status [V]
-    const int32_t *dstat;
-    double target, tol;
-    int max_eval;
-    const double *wout;               // the sensitivity kernel's out [n][MPCX_NPW], status [n] and sens [n][NS][3][K] on the pass's data
-    const int32_t *wstat;
-    const double *g;
-    double *e, *dx;                   // workspace: the unit direction [n][NS][3][K]; the responses [n][2 (e, du_t-1)][2][K][6]
-    double *out, *du, *sens;          // the call's own; sens may be NULL
-    int32_t *status;
+// the pass's list, the virtual constellation with the pass's trajectories and covariances (and the columns), the pass's
+// linearisation [V][K-1][MPCX_STAGE_DOUBLES] with the discretiser's status [V], the sensitivity kernel's answers on the pass's data;
+// dx: the responses [n][2 (e, du_t-1)][2][K][6]; out, du, status: the call's own
+struct AwrArgs : AwArgs {
+    int t;                            // the pass
+    double *e;                        // workspace: the unit direction [n][NS][3][K]
+    double *sens;                     // the call's own; may be NULL
     const int32_t *flies;
     int32_t *frozen, *rounds_done;
     double *pred;                     // hist_pred of this pass [n]
 };
-
-struct AwrMover {
-    bool moves;
-    CpMover mv;
-    double Tu;
-};
-struct AwrRow {
-    double fi, fj, ta, hp, R;
-    AwrMover m0, m1;                  // slot 0 (object i), slot 1 (object j): a selection, never an address
-    const double *xe, *xp;            // [2][K][6] each
-    size_t K;
-    __device__ __forceinline__ const AwrMover &slot(int sl) const { return sl ? m1 : m0; }
-    __device__ __forceinline__ AwrMover &slot(int sl) { return sl ? m1 : m0; }
-};
-
-// the mean relative state at the time the two objects were placed at nq, moved by sgn (alpha X_e - X_prev)
-__device__ __forceinline__ void awr_shift(const AwrRow &r, const CpNode (&nq)[2], double alpha, CwNode &nd)
-{
-    double de[3] = {0.0, 0.0, 0.0}, we[3] = {0.0, 0.0, 0.0}, dp[3] = {0.0, 0.0, 0.0}, wp[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        if (!r.slot(sl).moves) continue;
-        CwBasis b;
-        cw_basis(nq[sl], r.slot(sl).mv.L, r.slot(sl).Tu, r.slot(sl).mv.htau, b);
-        const double sgn = sl ? 1.0 : -1.0;
-        const size_t at = ((size_t)sl * r.K + nq[sl].k) * 6;
-        const double *e0 = r.xe + at, *e1 = e0 + 6, *p0 = r.xp + at, *p1 = p0 + 6;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            de[c] = de[c] + sgn * (b.p[0] * e0[c] + b.p[1] * e0[3 + c] + b.p[2] * e1[c] + b.p[3] * e1[3 + c]);
-            we[c] = we[c] + sgn * (b.v[0] * e0[c] + b.v[1] * e0[3 + c] + b.v[2] * e1[c] + b.v[3] * e1[3 + c]);
-            dp[c] = dp[c] + sgn * (b.p[0] * p0[c] + b.p[1] * p0[3 + c] + b.p[2] * p1[c] + b.p[3] * p1[3 + c]);
-            wp[c] = wp[c] + sgn * (b.v[0] * p0[c] + b.v[1] * p0[3 + c] + b.v[2] * p1[c] + b.v[3] * p1[3 + c]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { nd.d[c] = nd.d[c] + (alpha * de[c] - dp[c]); nd.w[c] = nd.w[c] + (alpha * we[c] - wp[c]); }
-}
-
-// Q_t(alpha): aw_eval's rule on the pass's frames and covariances.  Called by the whole wave; the same bits on every lane.
-__device__ __forceinline__ double awr_eval(const AwrArgs &a, const AwrRow &r, double alpha, int lane, int &st)
-{
-    double entries = 0.0;
-    CwNode nd;
-    CpNode nq[2];
-    for (int p = 0; p < a.panels; ++p) {
-        const double tau = (r.ta + (double)p * r.hp) + (0.5 * r.hp) * (1.0 + CP_GL[lane][0]);
-        const int sl = cw_node_at(a.row, a.col, r.fi, r.fj, tau, a.mu, nd, nq[0], nq[1]);
-        if (__any(sl != MPCX_ST_OK)) { st = MPCX_ST_NUMERIC; return cp_nan(); }
-        awr_shift(r, nq, alpha, nd);
-        const double rate = cw_rate(nd, r.R);
-        entries = entries + cp_wave_sum(((0.5 * r.hp) * CP_GL[lane][1]) * rate);
-    }
-    if (cw_node_at(a.row, a.col, r.fi, r.fj, r.ta, a.mu, nd, nq[0], nq[1]) != MPCX_ST_OK) { st = MPCX_ST_NUMERIC; return cp_nan(); }
-    awr_shift(r, nq, alpha, nd);
-    const double start = nd.cden * cp_wave_sum(cw_ball_share(nd, r.R, lane));
-    return start + entries;
-}
-
-// The response x_0 = 0, x_k+1 = A_k x_k + B_kn[k] u_k + B_kp[k] u_k+1 of the movers to u [NS][3][K] at the nodes 0 .. ke + 1 into
-// x [2][K][6]: avoidance_window_kernel's chain.  Called by the whole block; ends behind a barrier.
-__device__ __forceinline__ void awr_chain(const AwrArgs &a, const AwrRow &r, const int (&ke)[2], const double *u, double *x,
-                                          double (&rec)[2][CP_REC_PAD], double (&xs)[2][8], int h, int ll)
-{
-    const size_t K = r.K;
-    const bool mine = h < a.NS && r.slot(h).moves;
-    const int kme = h ? ke[1] : ke[0];
-    const int kmax = r.m0.moves ? (r.m1.moves && ke[1] > ke[0] ? ke[1] : ke[0]) : ke[1];
-    const double *srec = a.stage + (size_t)(h ? r.m1.mv.o : r.m0.mv.o) * (K - 1) * MPCX_STAGE_DOUBLES;     // (read only where `mine`)
-    const double *uh = u + (size_t)h * 3 * K;
-    double *xh = x + (size_t)h * K * 6;
-    if (mine && ll < 7) {
-        xs[h][ll] = 0.0;
-        if (ll < 6) xh[ll] = 0.0;
-    }
-    for (int q = 0; q <= kmax; ++q) {
-        const bool act = mine && q <= kme;
-        if (act) {
-            const double *rp = srec + (size_t)q * MPCX_STAGE_DOUBLES;
-            rec[h][ll] = rp[ll]; rec[h][ll + 32] = rp[ll + 32];
-            if (ll + 64 < CP_REC) rec[h][ll + 64] = rp[ll + 64];
-        }
-        __syncthreads();
-        double xn = 0.0;
-        if (act && ll < 7) {
-            xn = rec[h][ll * 7] * xs[h][0];
-#pragma unroll
-            for (int c = 1; c < 7; ++c) xn = xn + rec[h][ll * 7 + c] * xs[h][c];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xn = xn + rec[h][49 + ll * 3 + c] * uh[(size_t)c * K + q];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xn = xn + rec[h][70 + ll * 3 + c] * uh[(size_t)c * K + q + 1];
-        }
-        __syncthreads();
-        if (act && ll < 7) {
-            xs[h][ll] = xn;
-            if (ll < 6) xh[(size_t)(q + 1) * 6 + ll] = xn;
-        }
-    }
-    __syncthreads();                                                 // x is read back by other lanes
-}
 
 __global__ __launch_bounds__(64) void awr_solve_kernel(AwrArgs a)
 {
@@ -299,8 +188,6 @@ __global__ __launch_bounds__(64) void awr_solve_kernel(AwrArgs a)
     const int pr = blockIdx.x, lane = threadIdx.x, h = lane >> 5, ll = lane & 31;
     if (pr >= a.n) return;
     if (!a.flies[pr] || a.frozen[pr]) return;                        // (wave-uniform; frozen is written below by lane 0 at the very end)
-    const double *row = a.pairs + (size_t)pr * 4;
-    const double t = row[3];
     const size_t K = (size_t)a.K, per = (size_t)a.NS * 3 * K;
     const double *g = a.g + (size_t)pr * per, *wo = a.wout + (size_t)pr * MPCX_NPW;
     double *du = a.du + (size_t)pr * per, *e = a.e + (size_t)pr * per, *dx = a.dx + (size_t)pr * 4 * K * 6;
@@ -317,55 +204,11 @@ __global__ __launch_bounds__(64) void awr_solve_kernel(AwrArgs a)
         const double f0 = log(Qt / a.target);
         if (fabs(f0) <= a.tol) kept = true;
         else {
-            AwrRow r;
-            r.fi = row[0]; r.fj = row[1]; r.ta = wo[MPCX_PW_TA]; r.hp = (wo[MPCX_PW_TB] - wo[MPCX_PW_TA]) / (double)a.panels;
-            r.m0.moves = a.who != 1; r.m1.moves = a.NS == 2 && a.who != 0;
-            r.xe = dx; r.xp = dx + 2 * K * 6; r.K = K;
-            // both objects at t and at the window's end (the sensitivity kernel passed these tests: the statuses are OK)
-            CpNode n0[2], ne[2];
-            {
-                double p[3], v[3];
-                cp_state(a.row, r.fi, t, p, v, n0[0]);
-                cp_state(a.col, r.fj, t, p, v, n0[1]);
-                cp_state(a.row, r.fi, wo[MPCX_PW_TB], p, v, ne[0]);
-                cp_state(a.col, r.fj, wo[MPCX_PW_TB], p, v, ne[1]);
-            }
-            r.R = a.row.radius[n0[0].o] + a.col.radius[n0[1].o];
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                r.slot(sl).mv = CpMover{};
-                r.slot(sl).Tu = 1.0;
-                if (!r.slot(sl).moves) continue;
-                cp_mover(a.row, a.dstat, n0[sl], K, r.slot(sl).mv);
-                r.slot(sl).Tu = a.row.units[2 * r.slot(sl).mv.o + 1];
-            }
-            // ---- the unit direction e (du for alpha = 1) and Gamma_t: avoidance_window_kernel's, the mass row Y_t's
-#pragma unroll
-            for (int sl = 0; sl < 2; ++sl) {
-                if (sl >= a.NS) continue;
-                const int nn = r.slot(sl).moves ? r.slot(sl).mv.nn : 0;
-                for (int c = 0; c < 3; ++c)
-                    for (int m = nn + lane; m < a.K; m += 64) e[((size_t)sl * 3 + c) * K + m] = 0.0;
-                if (!r.slot(sl).moves) continue;
-                double sG = 0.0, sdv = 0.0, sum = 0.0;
-                for (int m = lane; m < nn; m += 64) {
-                    const double cm = r.slot(sl).mv.cfac / r.slot(sl).mv.mass[m];
-                    const double wm = (m == 0 || m == nn - 1) ? 0.5 * r.slot(sl).mv.hn : r.slot(sl).mv.hn;
-                    double gh[3], da[3], dn[3];
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        gh[c] = g[((size_t)sl * 3 + c) * K + m] / cm;
-                        da[c] = -gh[c] / wm;
-                        dn[c] = da[c] / cm;
-                        e[((size_t)sl * 3 + c) * K + m] = dn[c];
-                    }
-                    sG = sG + (gh[0] * gh[0] + gh[1] * gh[1] + gh[2] * gh[2]) / wm;
-                    sdv = sdv + wm * sqrt(da[0] * da[0] + da[1] * da[1] + da[2] * da[2]);
-                    sum = fmax(sum, sqrt(dn[0] * dn[0] + dn[1] * dn[1] + dn[2] * dn[2]));
-                }
-                Gam = Gam + cp_wave_sum(sG);
-                dv[sl] = cp_wave_sum(sdv); um[sl] = cp_wave_max(sum);
-            }
+            AwRow r;
+            int ke[2];
+            aw_row(a, a.pairs + (size_t)pr * 4, wo, dx, dx + 2 * K * 6, r, ke);
+            // ---- the unit direction e (du for alpha = 1) and Gamma_t: the mass row Y_t's
+            aw_direction(a, r, g, e, lane, Gam, dv, um);
             // ---- c0 = -sum g_m du_t-1,m in the order slot, node, component (every lane the same sum)
             {
                 double s = 0.0;
@@ -379,18 +222,15 @@ __global__ __launch_bounds__(64) void awr_solve_kernel(AwrArgs a)
             if (st == MPCX_ST_OK && (!(alpha > 0.0) || !cp_finite(alpha))) st = MPCX_ST_NUMERIC;
             __syncthreads();                                         // e is read back by other lanes below
             if (st == MPCX_ST_OK) {
-                const int ke[2] = {ne[0].k, ne[1].k};
-                awr_chain(a, r, ke, e, dx, rec, xs, h, ll);
-                awr_chain(a, r, ke, du, dx + 2 * K * 6, rec, xs, h, ll);
-
-                // ---- the step: from alpha_1 double until f <= 0 or halve until f > 0, then close the bracket on f = ln Q_t(alpha) -
-                // ln target_p by avoidance_window_kernel's Illinois rule
+                aw_chain(a, r, ke, e, dx, rec, xs, h, ll);
+                aw_chain(a, r, ke, du, dx + 2 * K * 6, rec, xs, h, ll);
+                // ---- the step: from alpha_1 double until f <= 0 or halve until f > 0, then close the bracket
                 double lo = 0.0, flo = 0.0, hi = 0.0, fhi = 0.0;
                 bool found = false, bracket = false;
                 int dir = 0;                                         // +1: doubling, -1: halving
                 while (st == MPCX_ST_OK && !found && !bracket) {     // bracketing
                     if (evals == a.max_eval) { st = MPCX_ST_INFEASIBLE; break; }
-                    Q1 = awr_eval(a, r, alpha, lane, st);
+                    Q1 = aw_eval<true>(a, r, alpha, lane, st);
                     ++evals;
                     if (st != MPCX_ST_OK) break;
                     if (!(Q1 >= 0.0) || !cp_finite(Q1) || !cp_finite(alpha) || !(alpha > 0.0)) { st = MPCX_ST_NUMERIC; break; }
@@ -408,27 +248,7 @@ __global__ __launch_bounds__(64) void awr_solve_kernel(AwrArgs a)
                         alpha = 0.5 * alpha;
                     }
                 }
-                int side = 0;
-                while (st == MPCX_ST_OK && !found) {                 // closing
-                    if (evals == a.max_eval) { st = MPCX_ST_MAXITER; break; }
-                    alpha = lo + (hi - lo) * (flo / (flo - fhi));
-                    if (!(alpha > lo && alpha < hi)) alpha = 0.5 * (lo + hi);
-                    Q1 = awr_eval(a, r, alpha, lane, st);
-                    ++evals;
-                    if (st != MPCX_ST_OK) break;
-                    if (!(Q1 >= 0.0) || !cp_finite(Q1)) { st = MPCX_ST_NUMERIC; break; }
-                    const double f = log(Q1 / a.target);
-                    if (fabs(f) <= a.tol) { found = true; break; }
-                    if (f > 0.0) {
-                        lo = alpha; flo = f;
-                        if (side == 1) fhi = 0.5 * fhi;
-                        side = 1;
-                    } else {
-                        hi = alpha; fhi = f;
-                        if (side == -1) flo = 0.5 * flo;
-                        side = -1;
-                    }
-                }
+                aw_close<true>(a, r, lane, lo, flo, hi, fhi, found, alpha, Q1, evals, st);
                 if (st == MPCX_ST_OK) {                              // accepted: du = alpha e, the total change from the given U
 #pragma unroll
                     for (int sl = 0; sl < 2; ++sl) {
@@ -586,11 +406,11 @@ static int awr_enqueue(mpcx_ctx *ctx, const AwrCall &c, void *workspace, hipStre
         if (!solve) continue;
         q.out = ws.wout; q.status = ws.wstat; q.sens = ws.g; q.state_grad = nullptr;
         if (int rc = cws_enqueue(ctx, q, ws.lin, st)) return rc;
-        const CpSide row{V, K, q.Ks, q.Y, q.units, q.span, q.P, q.radius};
-        const CpSide col = w.cat_Y ? CpSide{w.D, w.cat_K, w.cat_Ks, w.cat_Y, w.cat_units, w.cat_span, w.cat_P, w.cat_radius} : row;
-        const AwrArgs a{n, K, NS, w.who, t, ws.pairs_t, row, col, w.mu, w.panels, ws.lin.stage, ws.lin.dstat, w.target, c.w.tol, c.w.max_eval,
-                        ws.wout, ws.wstat, ws.g, ws.e, ws.dx, w.out, w.du, w.sens, w.status, ws.flies, ws.frozen, c.rounds_done,
-                        c.hist_pred + (size_t)t * np};
+        CpSide row, col;
+        enc_sides(q, row, col);
+        const AwrArgs a{{n, K, NS, w.who, ws.pairs_t, row, col, w.mu, w.panels, ws.lin.stage, ws.lin.dstat, w.target, w.tol, w.max_eval,
+                         ws.wout, ws.wstat, ws.g, ws.dx, w.out, w.du, w.status},
+                        t, ws.e, w.sens, ws.flies, ws.frozen, c.rounds_done, c.hist_pred + (size_t)t * np};
         hipLaunchKernelGGL(awr_solve_kernel, dim3((unsigned)n), dim3(64), 0, st, a);
         MPCX_HIP(ctx, hipGetLastError());
     }
@@ -609,9 +429,7 @@ extern "C" size_t mpcx_avoidance_window_refine_workspace_bytes(int n, int S, int
 
 // the arguments of the two entry points below as an AwrCall
 #define MPCX_AWR_CALL                                                                                                                         \
-    AwrCall{AwCall{{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, \
-                     mu, target_p}, radius, cat_radius, half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du},         \
-            prop_max_step, rounds, M, T0, T1, max_shift, recov, q, rounds_done, Y_out, P_out, hist_p, hist_t, hist_pred}
+    AwrCall{MPCX_AW_CALL, prop_max_step, rounds, M, T0, T1, max_shift, recov, q, rounds_done, Y_out, P_out, hist_p, hist_t, hist_pred}
 
 extern "C" int mpcx_avoidance_window_refine_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
                                                 const double *U, const double *units, const double *span, const double *consts, int flags,

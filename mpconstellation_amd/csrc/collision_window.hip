@@ -9,10 +9,14 @@
 // time (collision_window_device.hpp: cw_node), then the 512 sphere points in a wave-uniform loop (cw_rate).  Panels are a loop.  The
 // ball term is dealt over the lanes.  Sums are the xor butterfly, lane 0 stores.  No LDS, no atomics, nothing crosses a workgroup.
 // Written for a fixed operation order (tests/collision_window_reference.py follows it line by line).
-// The window rule is written three times: here, in collision_window_sensitivity_kernel below (with cw_rate_grad and
-// cw_ball_share_grad beside cw_rate and cw_ball_share) and in aw_eval (avoidance_window.hip).  The copies keep this kernel's
-// registers and bytes as they were; a change to the rule is a change to all three, and tests/test_avoidance_window_gpu.py holds
-// the second to this kernel's bytes.  (A fourth copy, awr_eval in avoidance_window_refine.hip, is aw_eval with two responses.)
+// The window rule's panel loop is stated three times, and a change to the rule is a change to all three:
+//   collision_window_kernel               cw_node, cw_rate, the largest rate and its time; a failed node keeps BADK apart from NUMERIC
+//   collision_window_sensitivity_kernel   cw_node_at, cw_rate_grad, the gradient scattered to the node sources; the same statuses
+//   aw_eval (avoidance_window_device.hpp) cw_node_at, the mean shifted, cw_rate; any failed node is MPCX_ST_NUMERIC
+// They call different functions between the same sums and map a failed node to a status differently; one loop for all three would
+// need hooks for both, which is more to read than three short loops.  What does not differ is written once
+// (collision_window_device.hpp: cw_row, cw_out, cw_out_empty, cw_store), and tests/test_avoidance_window_gpu.py holds the second
+// statement to the first one's bytes.
 //   collision_window_sensitivity_kernel   the same figure (the same bytes) together with its derivative with respect to every thrust
 //                             node of the objects that move (include/mpcx.h: mpcx_collision_window_sensitivity*): the gradient with
 //                             respect to the mean relative state at every time node, carried onto the bracketing node states and
@@ -45,27 +49,11 @@ __global__ __launch_bounds__(64) void collision_window_kernel(CwArgs a)
     double o[MPCX_NPW];
 #pragma unroll
     for (int c = 0; c < MPCX_NPW; ++c) o[c] = cp_nan();
-    // the row's own tests (wave-uniform): both objects at t, the half window, the clipped window, the radius
-    int st;
     double ta = 0.0, tb = 0.0, R = 0.0;
-    {
-        double p[3], v[3];
-        CpNode na, nb;
-        st = cp_state(a.row, fi, t, p, v, na);
-        if (st == MPCX_ST_OK) st = cp_state(a.col, fj, t, p, v, nb);
-        if (st == MPCX_ST_OK && !(h > 0.0 && cp_finite(h))) st = MPCX_ST_BADK;
-        if (st == MPCX_ST_OK) {
-            ta = fmax(fmax(t - h, a.row.span[2 * na.o]), a.col.span[2 * nb.o]);
-            tb = fmin(fmin(t + h, a.row.span[2 * na.o + 1]), a.col.span[2 * nb.o + 1]);
-            if (!(tb > ta)) st = MPCX_ST_BADK;
-            R = a.row.radius[na.o] + a.col.radius[nb.o];
-            if (st == MPCX_ST_OK && !cp_finite(R)) st = MPCX_ST_NUMERIC;
-        }
-    }
-    if (st == MPCX_ST_OK && !(R > 0.0)) {
-        o[MPCX_PW_P] = 0.0; o[MPCX_PW_START] = 0.0; o[MPCX_PW_ENTRIES] = 0.0; o[MPCX_PW_RATE_MAX] = 0.0;
-        o[MPCX_PW_T_RATE_MAX] = ta; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
-    } else if (st == MPCX_ST_OK) {
+    CpNode na, nb;
+    int st = cw_row(a.row, a.col, fi, fj, t, h, ta, tb, R, na, nb);
+    if (st == MPCX_ST_OK && !(R > 0.0)) cw_out_empty(o, ta, tb);
+    else if (st == MPCX_ST_OK) {
         const double ninf = -__longlong_as_double(0x7ff0000000000000LL);
         const double hp = (tb - ta) / (double)a.panels;
         double entries = 0.0, rmax = ninf, tmax = ta;
@@ -88,18 +76,11 @@ __global__ __launch_bounds__(64) void collision_window_kernel(CwArgs a)
                 const double start = nd.cden * cp_wave_sum(cw_ball_share(nd, R, lane));
                 const double total = start + entries;
                 if (!cp_finite(total)) st = MPCX_ST_NUMERIC;
-                else {
-                    o[MPCX_PW_P] = fmin(total, 1.0); o[MPCX_PW_START] = start; o[MPCX_PW_ENTRIES] = entries; o[MPCX_PW_RATE_MAX] = rmax;
-                    o[MPCX_PW_T_RATE_MAX] = tmax; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
-                }
+                else cw_out(o, total, start, entries, rmax, tmax, ta, tb);
             }
         }
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < MPCX_NPW; ++c) a.out[(size_t)pr * MPCX_NPW + c] = o[c];
-        a.status[pr] = st;
-    }
+    if (lane == 0) cw_store(o, st, a.out + (size_t)pr * MPCX_NPW, a.status + pr);
 }
 
 // the call as both entry points take it
@@ -139,8 +120,8 @@ static int cw_check(mpcx_ctx *ctx, const CwCall &c)
 
 static int cw_enqueue(mpcx_ctx *ctx, const CwCall &c, hipStream_t st)
 {
-    const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
-    const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
+    CpSide row, col;
+    enc_sides(c, row, col);
     const CwArgs a{c.n, c.pairs, row, col, c.mu, c.half, c.panels, c.out, c.status};
     hipLaunchKernelGGL(collision_window_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
@@ -165,8 +146,8 @@ struct CwsArgs {
 
 enum { CWS_LAM_PAD = 8 };
 
-// One wave per row, lane l time node l of the current panel, as collision_window_kernel -- whose tests, sums and stores this kernel
-// repeats expression for expression: `out` has its bits.  Beside the rate every lane forms c_q (cw_rate_grad) and, for every object
+// One wave per row, lane l time node l of the current panel, as collision_window_kernel -- whose tests and stores this kernel
+// shares (cw_row, cw_out) and whose sums it repeats expression for expression: `out` has its bits.  Beside the rate every lane forms c_q (cw_rate_grad) and, for every object
 // that moves, what c_q puts on the two node states that bracket its time (cw_basis) into LDS; then lane m - k0 owns node m of the
 // panel's nodes k0 .. k1 + 1 and adds the 64 lanes' shares to its source in the order of the lanes.  The ball term is added last.
 // The adjoint sweep is avoidance_kernel's: the two half-waves run the two objects side by side, lanes 0..6 of a half own lam, lanes
@@ -186,23 +167,9 @@ __global__ __launch_bounds__(64) void collision_window_sensitivity_kernel(CwsArg
     double o[MPCX_NPW];
 #pragma unroll
     for (int c = 0; c < MPCX_NPW; ++c) o[c] = cp_nan();
-    // the row's own tests (wave-uniform), collision_window_kernel's
-    int st;
     double ta = 0.0, tb = 0.0, R = 0.0;
     CpNode n0[2];
-    {
-        double p[3], v[3];
-        st = cp_state(a.row, fi, t, p, v, n0[0]);
-        if (st == MPCX_ST_OK) st = cp_state(a.col, fj, t, p, v, n0[1]);
-        if (st == MPCX_ST_OK && !(hw > 0.0 && cp_finite(hw))) st = MPCX_ST_BADK;
-        if (st == MPCX_ST_OK) {
-            ta = fmax(fmax(t - hw, a.row.span[2 * n0[0].o]), a.col.span[2 * n0[1].o]);
-            tb = fmin(fmin(t + hw, a.row.span[2 * n0[0].o + 1]), a.col.span[2 * n0[1].o + 1]);
-            if (!(tb > ta)) st = MPCX_ST_BADK;
-            R = a.row.radius[n0[0].o] + a.col.radius[n0[1].o];
-            if (st == MPCX_ST_OK && !cp_finite(R)) st = MPCX_ST_NUMERIC;
-        }
-    }
+    int st = cw_row(a.row, a.col, fi, fj, t, hw, ta, tb, R, n0[0], n0[1]);
     const bool empty = st == MPCX_ST_OK && !(R > 0.0);               // no sphere: nothing to differentiate, no mover is looked at
     // the movers' own status counts behind the window rule's (the header's order): it is kept aside until the rule has run
     CpMover mv[2] = {};
@@ -215,10 +182,8 @@ __global__ __launch_bounds__(64) void collision_window_sensitivity_kernel(CwsArg
             if (stm == MPCX_ST_OK) stm = s1;
         }
     }
-    if (empty) {
-        o[MPCX_PW_P] = 0.0; o[MPCX_PW_START] = 0.0; o[MPCX_PW_ENTRIES] = 0.0; o[MPCX_PW_RATE_MAX] = 0.0;
-        o[MPCX_PW_T_RATE_MAX] = ta; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
-    } else if (st == MPCX_ST_OK) {
+    if (empty) cw_out_empty(o, ta, tb);
+    else if (st == MPCX_ST_OK) {
         for (size_t e = lane; e < 2 * K * 6; e += 64) src[e] = 0.0;
         __syncthreads();
         const double ninf = -__longlong_as_double(0x7ff0000000000000LL);
@@ -299,8 +264,7 @@ __global__ __launch_bounds__(64) void collision_window_sensitivity_kernel(CwsArg
                 const double total = start + entries;
                 if (!cp_finite(total)) st = MPCX_ST_NUMERIC;
                 else {
-                    o[MPCX_PW_P] = fmin(total, 1.0); o[MPCX_PW_START] = start; o[MPCX_PW_ENTRIES] = entries; o[MPCX_PW_RATE_MAX] = rmax;
-                    o[MPCX_PW_T_RATE_MAX] = tmax; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
+                    cw_out(o, total, start, entries, rmax, tmax, ta, tb);
                     if (lane == 0) {
                         if (sg) {
 #pragma unroll
@@ -381,11 +345,7 @@ __global__ __launch_bounds__(64) void collision_window_sensitivity_kernel(CwsArg
         if (sg)
             for (size_t e = lane; e < NQ * 6; e += 64) sg[e] = f;
     }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < MPCX_NPW; ++c) a.out[(size_t)pr * MPCX_NPW + c] = o[c];
-        a.status[pr] = st;
-    }
+    if (lane == 0) cw_store(o, st, a.out + (size_t)pr * MPCX_NPW, a.status + pr);
 }
 
 int cws_check(mpcx_ctx *ctx, const CwsCall &c, const char *name, bool outputs_given, const char *outputs)
@@ -402,8 +362,8 @@ int cws_check(mpcx_ctx *ctx, const CwsCall &c, const char *name, bool outputs_gi
 
 int cws_enqueue(mpcx_ctx *ctx, const CwsCall &c, const CwsWorkspace &ws, hipStream_t st)
 {
-    const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
-    const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
+    CpSide row, col;
+    enc_sides(c, row, col);
     const CwsArgs a{c.n, c.K, c.cat_Y ? 1 : 2, c.who, c.pairs, row, col, c.mu, c.half, c.panels, ws.stage, ws.dstat,
                     c.out, c.sens, c.state_grad, ws.src, c.status};
     hipLaunchKernelGGL(collision_window_sensitivity_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);

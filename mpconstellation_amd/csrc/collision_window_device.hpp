@@ -3,12 +3,13 @@
 //   an object at a time node       cw_covariance_add (the nearest node's 6 x 6 covariance carried over, added to the pair's sum)
 //   the relative state at a node   cw_node: mean (d, w), the sphere rule's frame (cw_pole), the Cholesky factor of the position block
 //                                  and what the conditional velocity needs of the other blocks (cw_factor)
+//   a row of the list              cw_row (its own tests: the window, the radius), cw_out, cw_out_empty, cw_store (its row of `out`)
 //   the sphere                     cw_point (point (j, k) of the 512), cw_whiten, cw_rate (the entry rate), cw_ball_share (a lane's
 //                                  64 points of the ball term)
 //   the derivative                 cw_node_at (cw_node, and where the time falls on both objects' nodes), cw_rate_grad and
 //                                  cw_ball_share_grad (the rate and the ball share with their gradients with respect to the mean),
 //                                  cw_unwhiten, cw_basis (the Hermite bases of position and velocity on the bracketing node states):
-//                                  collision_window_sensitivity_kernel and avoidance_window_kernel (avoidance_window.hip)
+//                                  collision_window_sensitivity_kernel and the window manoeuvres (avoidance_window_device.hpp)
 // The expressions below are the operation order; tests/collision_window_reference.py restates them line by line, and
 // tests/avoidance_window_reference.py the derivative's.
 #pragma once
@@ -247,6 +248,45 @@ __device__ __forceinline__ int cw_node(const CpSide &row, const CpSide &col, dou
 {
     CpNode na, nb;
     return cw_node_at(row, col, fi, fj, tau, mu, nd, na, nb);
+}
+
+// The row's own tests (wave-uniform) in the order of their statuses: both objects at t (na, nb), the half window h, the window
+// clipped to both spans [ta, tb], the radius R = radius_i + radius_j.  R <= 0 passes: the row has no sphere (cw_out_empty).
+__device__ __forceinline__ int cw_row(const CpSide &row, const CpSide &col, double fi, double fj, double t, double h, double &ta, double &tb,
+                                      double &R, CpNode &na, CpNode &nb)
+{
+    double p[3], v[3];
+    int st = cp_state(row, fi, t, p, v, na);
+    if (st == MPCX_ST_OK) st = cp_state(col, fj, t, p, v, nb);
+    if (st == MPCX_ST_OK && !(h > 0.0 && cp_finite(h))) st = MPCX_ST_BADK;
+    if (st == MPCX_ST_OK) {
+        ta = fmax(fmax(t - h, row.span[2 * na.o]), col.span[2 * nb.o]);
+        tb = fmin(fmin(t + h, row.span[2 * na.o + 1]), col.span[2 * nb.o + 1]);
+        if (!(tb > ta)) st = MPCX_ST_BADK;
+        R = row.radius[na.o] + col.radius[nb.o];
+        if (st == MPCX_ST_OK && !cp_finite(R)) st = MPCX_ST_NUMERIC;
+    }
+    return st;
+}
+
+// a row of `out`: the figure START + ENTRIES = total (finite), and the row without a sphere
+__device__ __forceinline__ void cw_out(double (&o)[MPCX_NPW], double total, double start, double entries, double rmax, double tmax, double ta,
+                                       double tb)
+{
+    o[MPCX_PW_P] = fmin(total, 1.0); o[MPCX_PW_START] = start; o[MPCX_PW_ENTRIES] = entries; o[MPCX_PW_RATE_MAX] = rmax;
+    o[MPCX_PW_T_RATE_MAX] = tmax; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
+}
+__device__ __forceinline__ void cw_out_empty(double (&o)[MPCX_NPW], double ta, double tb)
+{
+    o[MPCX_PW_P] = 0.0; o[MPCX_PW_START] = 0.0; o[MPCX_PW_ENTRIES] = 0.0; o[MPCX_PW_RATE_MAX] = 0.0;
+    o[MPCX_PW_T_RATE_MAX] = ta; o[MPCX_PW_TA] = ta; o[MPCX_PW_TB] = tb;
+}
+// the row and its status to memory (one lane's work)
+__device__ __forceinline__ void cw_store(const double (&o)[MPCX_NPW], int st, double *out, int32_t *status)
+{
+#pragma unroll
+    for (int c = 0; c < MPCX_NPW; ++c) out[c] = o[c];
+    *status = st;
 }
 
 // Point (j, k) of the sphere rule: cos theta node j of 16 (the 8 Gauss-Legendre nodes on [-1, 0], then on [0, 1]: the integrand's

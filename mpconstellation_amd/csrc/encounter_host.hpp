@@ -2,6 +2,7 @@
 // mpcx_collision_window_sensitivity*, mpcx_avoidance_window* and mpcx_avoidance_window_refine* share, and the linearisation step they share with
 // mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver.
 #pragma once
+#include "collision_device.hpp"                                     // CpSide
 #include "mpcx_host.hpp"
 
 namespace mpcx {
@@ -120,6 +121,14 @@ struct CwsCall : EncProblem {
     int32_t *status;
 };
 
+// The two sides of the list of a window call (CwsCall, or collision_window.hip's CwCall: the same names) as its kernels take them:
+// the constellation, and the catalogue where there is one, else the constellation again.
+template <typename Call> inline void enc_sides(const Call &c, CpSide &row, CpSide &col)
+{
+    row = CpSide{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
+    col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
+}
+
 // workspace of the sensitivity: [the linearisation's][node sources n 2 K 6]
 struct CwsWorkspace : LinWorkspace {
     double *src;
@@ -143,6 +152,10 @@ struct AwCall : CwsCall {
     int max_eval;
     double *du;
 };
+// the arguments of an entry point of either, under their names in include/mpcx.h, as an AwCall
+#define MPCX_AW_CALL                                                                                                                  \
+    AwCall{{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, \
+             mu, target_p}, radius, cat_radius, half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du}
 
 // The argument tests of mpcx_avoidance_window* and the call itself on a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K,
 // panels) bytes.  (avoidance_window.hip)
