@@ -783,6 +783,54 @@ int mpcx_covariance_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, co
                               const double *q, double *P, int32_t *status, void *workspace, void *stream);
 
 /*
+ * mpcx_covariance_thrust_batch: mpcx_covariance_batch with a third source of uncertainty, the execution error of the thrust (the
+ * Gates model: magnitude and pointing errors, each with a fixed and a proportional part).  mpcx_covariance_batch treats the thrust
+ * table as known exactly; after a burn its execution error is the dominant new uncertainty, and a burn sized to "4 sigma" under a
+ * perfect-execution covariance is not a 4-sigma burn.  Arguments as mpcx_covariance_batch, with U required, and
+ *   exec [S][MPCX_NEXEC] = (s_fm, s_pm, s_fp, s_pp, u_off) per satellite, m_var0 [S] the mass variance at the first node in the
+ *   satellite's own mass unit squared (NULL: 0)  ->  P [S][K][6][6], Pm [S][K][7] (optional, NULL: not returned), status [S].
+ * Execution error at a node.  The executed thrust at node k is u_k + e_k; the e_k are independent between nodes, zero-mean and
+ * Gaussian, and between nodes the error is interpolated by the same first-order hold as the plan -- the discretisation the stage
+ * records already describe, x_k+1 = A_k x_k + B_kn[k] u_k + B_kp[k] u_k+1.  With u^ = u_k / |u_k|:
+ *   Sigma_k = s_par^2 u^ u^T + s_perp^2 (I - u^ u^T),  s_par^2 = s_fm^2 + (s_pm |u_k|)^2,  s_perp^2 = s_fp^2 + (s_pp |u_k|)^2.
+ * s_fm, s_fp and u_off are in the satellite's own normalised thrust unit, as U is; s_pm is a fraction; s_pp is in radians, per
+ * transverse axis.  A node with |u_k| <= u_off (or a |u_k| that is not a number) has Sigma_k = 0: the engine is off there, so there
+ * is no error and no direction is needed.  u_off >= 0 is required.
+ * The chain runs over all seven states -- a thrust error changes the mass flow, and a mass error changes later accelerations through
+ * A[3:6][6] -- in the units of mpcx_covariance_batch extended by the mass, which stays in the satellite's own mass unit:
+ * D = diag(L, L, L, V, V, V, 1), V = L / Tu; Phi~_k = D A_k D^-1, Bn~ = D B_kn[k], Bp~ = D B_kp[k].  x_k is correlated with e_k,
+ * because e_k entered the previous interval through B_kp, so the 7 x 3 cross-covariance C_k = Cov(x_k, e_k) is carried:
+ *   P_0 = [[P0, 0], [0, m_var0]],  C_0 = 0,
+ *   Y     = (Phi~_k C_k) Bn~^T,
+ *   P_k+1 = ((((Phi~_k P_k) Phi~_k^T + (Y + Y^T)) + (Bn~ Sigma_k) Bn~^T) + (Bp~ Sigma_k+1) Bp~^T) + q Q(h),
+ *   C_k+1 = Bp~ Sigma_k+1,
+ * q Q(h) on the 6 x 6 block as in mpcx_covariance_batch.  Sums run their index in ascending order; entry (i, j) is computed as entry
+ * (min, max) and mirrored, so P is symmetric to the bit.
+ * P is the position / velocity block (m, m/s), which every consumer of mpcx_covariance_batch's P takes unchanged; Pm is row 6 of the
+ * 7 x 7: the mass covariances with position and velocity, and the mass variance.
+ * The zero case is mpcx_covariance_batch, to the bit: for a satellite whose exec row is all zero and whose m_var0 is 0, every added
+ * term is an exact zero and the seventh term of each product is x * 0, and the 6-term prefix of each sum is written as
+ * mpcx_covariance_batch's kernel writes it (a zero may differ in sign).  That holds per satellite inside a mixed batch; no
+ * satellite is handed to the other kernel.
+ * status: mpcx_covariance_batch's, in its order; then a negative or non-finite exec entry, or a negative or non-finite m_var0:
+ * MPCX_ST_NUMERIC.  A failed satellite is NaN in P and Pm at all K nodes and the other satellites are untouched; otherwise the nodes
+ * past Ks[s] come back zero.  S < 1, K < 2, max_step <= 0, an unknown flag, MPCX_FLAG_ATMO without drag or without an atmosphere on
+ * the context, or a NULL X, U, units, span, consts, P0, exec, P or status: MPCX_E_BADARG with "covariance_thrust" in the message,
+ * nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_covariance_thrust_workspace_bytes(S, K) bytes (the stage
+ * records, tf, the discretiser's status; 0 for S < 1 or K < 2; contents unspecified on entry and exit).
+ */
+#define MPCX_NEXEC 5
+size_t mpcx_covariance_thrust_workspace_bytes(int S, int K);
+int mpcx_covariance_thrust_batch(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U, const double *units,
+                                 const double *span, const double *consts, int flags, double max_step, const double *P0, const double *q,
+                                 const double *exec, const double *m_var0, double *P, double *Pm, int32_t *status);
+int mpcx_covariance_thrust_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U,
+                                     const double *units, const double *span, const double *consts, int flags, double max_step,
+                                     const double *P0, const double *q, const double *exec, const double *m_var0, double *P, double *Pm,
+                                     int32_t *status, void *workspace, void *stream);
+
+/*
  * mpcx_collision_probability: pairs [n][4] rows exactly as the screens write them, (i, j, distance, time in s); the distance is
  * not read.  The row side: S, K, Ks, Y [S][7][K], units, span (as mpcx_ephemeris_batch takes them), P [S][K][6][6] (m, m/s:
  * mpcx_covariance_batch's), radius [S] the hard-body radius in m.  The column side: the same eight arguments with D.  cat_Y = NULL:

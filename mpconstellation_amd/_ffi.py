@@ -157,6 +157,12 @@ _SIGS = {
     "mpcx_covariance_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip]),
     "mpcx_covariance_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                             _vp, _vp]),
+    # the same chain over all seven states with thrust execution errors (after q: exec, m_var0; after P: Pm)
+    "mpcx_covariance_thrust_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mpcx_covariance_thrust_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
+                                               _dp, _dp, _ip]),
+    "mpcx_covariance_thrust_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpcx_collision_probability": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2 + [C.c_double, _dp, _ip]),
     "mpcx_collision_probability_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
                                        + [C.c_double, _vp, _vp, _vp]),
@@ -227,6 +233,7 @@ _SIGS = {
                                                     C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+NEXEC = 5                                                                   # MPCX_NEXEC: (s_fm, s_pm, s_fp, s_pp, u_off) of mpcx_covariance_thrust_batch's exec
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
 NPW, PW_MAX_PANELS = 7, 64                                                  # MPCX_NPW: columns of mpcx_collision_probability_window's out

@@ -15,6 +15,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   screen_track   of those close approaches the one nearest each listed row's own time: an encounter followed through re-screens;
   catalogue_trajectories   a catalogue given as state vectors at an epoch, propagated to trajectories for screen_against;
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
+  covariance_thrust   the same with the execution errors of the thrust (the Gates model; gates_execution turns newtons into its
+                 figures): all seven states and both input blocks of the linearisation, for the covariance after a burn;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
   collision_probability_window   for encounters too slow for that model (neighbours in one shell, satellites deployed together):
                  the probability over a time window from the time-varying relative state and the full 6 x 6 covariances;
@@ -570,6 +572,93 @@ def _covariance_call(Y, units, span, consts, P0, U, ns, q, *, device, slot, out,
     ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
     _ffi.call("mpcx_covariance_batch", ctx, S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr_opt(U), _ffi.dptr(units), _ffi.dptr(span),
               _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(out["P"]), _ffi.iptr(out["status"]))
+
+
+def gates_execution(scales, fixed_magnitude_N=0.0, proportional_magnitude=0.0, fixed_pointing_N=0.0, proportional_pointing_rad=0.0, off_N=0.0):
+    """A Gates execution-error model given in physical units -- the fixed magnitude and pointing errors and the thrust below which the
+    engine counts as off in newtons, the proportional magnitude error as a fraction, the proportional pointing error in radians per
+    transverse axis; scalars or one value per satellite -- as covariance_thrust's execution (S, 5) = (s_fm, s_pm, s_fp, s_pp, u_off)
+    in EACH satellite's own thrust unit (SatelliteScale.units["force"]): the counterpart of constellation_mpc.normalised_limits."""
+    S = len(scales)
+    force = np.array([sc.units["force"] for sc in scales], dtype=np.float64)
+    per_sat = lambda v, name: _per_sat_named(v, S, name)
+    out = np.column_stack([per_sat(fixed_magnitude_N, "fixed_magnitude_N") / force, per_sat(proportional_magnitude, "proportional_magnitude"),
+                           per_sat(fixed_pointing_N, "fixed_pointing_N") / force, per_sat(proportional_pointing_rad, "proportional_pointing_rad"),
+                           per_sat(off_N, "off_N") / force])
+    if not (np.isfinite(out).all() and (out >= 0.0).all()):
+        raise ValueError("gates_execution: need finite figures >= 0")
+    return _ffi.as_f64(out)
+
+
+def _per_sat_named(v, S, name):
+    if np.ndim(v) not in (0, 1) or (np.ndim(v) == 1 and np.shape(v) != (S,)):
+        raise ValueError(f"{name}: expected a scalar or ({S},) values, got {np.shape(v)}")
+    return _ffi.per_sat(v, S)
+
+
+def _check_execution(execution, S):
+    execution = _ffi.as_f64(execution)
+    if execution.shape == (_ffi.NEXEC,):
+        execution = np.broadcast_to(execution, (S, _ffi.NEXEC))
+    if execution.shape != (S, _ffi.NEXEC):
+        raise ValueError(f"execution: expected ({_ffi.NEXEC},) or ({S}, {_ffi.NEXEC}) rows (s_fm, s_pm, s_fp, s_pp, u_off) "
+                         f"(gates_execution), got {execution.shape}")
+    return _ffi.as_f64(execution)
+
+
+def covariance_thrust(Y, units, span, consts, P0, U, execution, mass_var0=None, ns=None, q=None, include_drag=False, include_J2=False,
+                      atmosphere=None, max_step=DEFAULT_MAX_STEP, device=0, devices=None, return_status=False, return_mass=False):
+    """covariance with thrust execution errors -> P (S, n, 6, 6), what every consumer of covariance's P takes.  The arguments are
+    covariance's, with U (S, 3, n) required, and execution (5,) or (S, 5) = (s_fm, s_pm, s_fp, s_pp, u_off) in each satellite's own
+    thrust unit (gates_execution makes it from newtons): at every node the executed thrust is u_k + e_k, e_k independent between nodes
+    with covariance s_par^2 along u_k and s_perp^2 across it, s_par^2 = s_fm^2 + (s_pm |u_k|)^2, s_perp^2 = s_fp^2 + (s_pp |u_k|)^2, and
+    none where |u_k| <= u_off; mass_var0 a scalar or (S,) mass variance at the first node in the satellite's mass unit squared.  The
+    device chains all seven states of the linearisation with both first-order-hold input blocks (include/mpcx.h,
+    mpcx_covariance_thrust_batch).  A satellite whose execution row is zero and whose mass_var0 is 0 gets covariance's bits.
+    A failed satellite -- covariance's failures, or a negative or non-finite execution entry or mass_var0 -- is NaN throughout
+    (return_status=True appends status).  return_mass=True appends Pm (S, n, 7): the mass's covariances with position and velocity
+    and its variance.  The results come as P[, Pm][, status].  devices=[d0, d1, ...]: contiguous blocks of satellites on several
+    devices (sharding.sharded_call), the bits of one device."""
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, n = Y.shape
+    if n < 2:
+        raise ValueError(f"Y: a covariance needs at least 2 nodes, got {Y.shape}")
+    consts = _ffi.as_f64(consts)
+    if consts.shape != (S, _ffi.NCONST):
+        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
+    P0, q = _check_p0(P0, S), _check_q(q, S)
+    if U is None:
+        raise ValueError("U: covariance_thrust needs the thrust at the nodes (without thrust: covariance)")
+    U = _ffi.as_f64(U)
+    if U.shape != (S, 3, n):
+        raise ValueError(f"U: expected ({S}, 3, {n}) thrust at the nodes, got {U.shape}")
+    execution = _check_execution(execution, S)
+    mass_var0 = None if mass_var0 is None else _per_sat_named(mass_var0, S, "mass_var0")
+    if not max_step > 0.0:
+        raise ValueError(f"max_step: need > 0, got {max_step}")
+    out = dict(P=_ffi.result_pool.take((S, n, 6, 6)), status=np.zeros(S, dtype=np.int32))
+    if return_mass:
+        out["Pm"] = np.empty((S, n, 7))
+    how = dict(flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
+    batched = [Y, units, span, consts, P0, U, ns, q, execution, mass_var0]
+    if devices is not None and len(devices) > 1:
+        from .sharding import sharded_call
+        sharded_call(_covariance_thrust_call, devices, batched, out, **how)
+    else:
+        if devices is not None and len(devices) == 1:
+            device = int(devices[0])
+        _covariance_thrust_call(*batched, device=device, slot=0, out=out, **how)
+    res = (out["P"],) + ((out["Pm"],) if return_mass else ()) + ((out["status"],) if return_status else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _covariance_thrust_call(Y, units, span, consts, P0, U, ns, q, execution, mass_var0, *, device, slot, out, flags, max_step, atmosphere):
+    """one block of satellites on context (device, slot), P, Pm and status into `out` (the block's views)"""
+    S, _, n = Y.shape
+    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    _ffi.call("mpcx_covariance_thrust_batch", ctx, S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span),
+              _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(execution), _ffi.dptr_opt(mass_var0),
+              _ffi.dptr(out["P"]), _ffi.dptr_opt(out.get("Pm")), _ffi.iptr(out["status"]))
 
 
 def _check_side(Y, units, span, P, radius, ns, pre=""):

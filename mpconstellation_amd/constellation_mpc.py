@@ -321,13 +321,35 @@ class ConstellationMPC:
                for w in self._screen_windows(what, samples_per_node, T0, T1)]
         return res[0] if len(res) == 1 else cj.combine(res)
 
-    def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None):
+    def plan_covariance(self, P0, q=None, execution=None, mass_var0=None):
+        """The covariance (S, plan_K, 6, 6) of the last plan at its nodes under the planning model's flags and atmosphere (plan_drag,
+        plan_J2): conjunction.covariance along (plan X, plan U, plan_tf, plan_K) from P0 with the acceleration noise q when execution
+        is None, otherwise conjunction.covariance_thrust with the thrust execution errors execution ((5,) or (S, 5):
+        conjunction.gates_execution) and the mass variance mass_var0 at the first node."""
+        (w,) = self._screen_windows("plan", 1)                            # (the plan's nodes, units and span: the grid is not used)
+        return self._plan_covariance(w, P0, q, execution, mass_var0)
+
+    def _plan_covariance(self, w, P0, q, execution, mass_var0):
+        from . import conjunction as cj
+        where = dict(device=self.device, devices=self.devices)
+        if execution is None:
+            if mass_var0 is not None:
+                raise ValueError("mass_var0: a mass variance needs execution (covariance carries no mass)")
+            return cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
+                                 include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+        return cj.covariance_thrust(w["Y"], w["units"], w["span"], self.consts, P0, self._plan[1], execution, mass_var0=mass_var0, ns=w["ns"],
+                                    q=q, include_drag=self.plan_drag, include_J2=self.plan_J2,
+                                    atmosphere=self.atmosphere if self.plan_drag else None, **where)
+
+    def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None, execution=None,
+                              mass_var0=None):
         """Collision probabilities of the last plan's close approaches -> (ConjunctionResult, CollisionResult).  The plan is screened
         at threshold_m (screen(what='plan'); screen_against when catalogue = (Y, units, span, P, radius) or (Y, units, span, P,
         radius, ns) is given: the objects' trajectories, their covariances -- conjunction.catalogue_covariance -- and hard-body
         radii); P0 ((6, 6) or (S, 6, 6); m, m/s), the covariance of every satellite at the plan's first node, is propagated along
         (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere (plan_drag, plan_J2) with the acceleration
-        noise q (conjunction.covariance), and every listed pair gets its probability (conjunction.collision_probability; radius_m a
+        noise q (plan_covariance: conjunction.covariance, or with execution / mass_var0 conjunction.covariance_thrust, the covariance
+        with thrust execution errors), and every listed pair gets its probability (conjunction.collision_probability; radius_m a
         scalar or (S,)).  The plan only: a linearisation needs the thrust a trajectory was flown with, and ConstellationMPC does not
         keep the thrust of its flown segments."""
         from . import conjunction as cj
@@ -343,12 +365,11 @@ class ConstellationMPC:
             cat = tuple(catalogue)
             screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
                                          cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
-                          include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+        P = self._plan_covariance(w, P0, q, execution, mass_var0)
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
 
     def collision_probability_window(self, threshold_m, P0, radius_m, half_window, panels=4, q=None, samples_per_node=4, max_pairs=None,
-                                     catalogue=None):
+                                     catalogue=None, execution=None, mass_var0=None):
         """collision_probability and the window probability of the same rows -> (ConjunctionResult, CollisionResult,
         WindowCollisionResult).  The screening arguments, P0, radius_m, q and catalogue are collision_probability's, and the first two
         results are what it returns; every listed pair also gets its probability over [t - half_window, t + half_window]
@@ -368,8 +389,7 @@ class ConstellationMPC:
             cat = tuple(catalogue)
             screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
                                          cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
-                          include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+        P = self._plan_covariance(w, P0, q, execution, mass_var0)
         plan = dict(ns=w["ns"], cat=cat, **where)
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
                 cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
