@@ -35,6 +35,7 @@ import numpy as np
 
 from . import _ffi
 from .linearize_discretize import Discretizer
+from .sharding import dispatch
 
 DEFAULT_MAX_PAIRS = 65536
 
@@ -85,6 +86,57 @@ def _check_trajectories(Y, units, span, ns, pre=""):
     if ns is not None and np.shape(ns) != (S,):
         raise ValueError(f"{pre}ns: expected ({S},) node counts, got {np.shape(ns)}")
     return Y, units, span, _ffi.counts(ns, S)
+
+
+# ---- the checks and the marshalling that the calls below share
+def _as_pairs(pairs):
+    """the list of a call: (n, 4) rows, a ConjunctionResult (its .pairs) or an EncounterEvents (its .events)"""
+    if isinstance(pairs, ConjunctionResult):
+        pairs = pairs.pairs
+    elif isinstance(pairs, EncounterEvents):
+        pairs = pairs.events
+    pairs = _ffi.as_f64(pairs)
+    if pairs.ndim != 2 or pairs.shape[1] != 4:
+        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time), a ConjunctionResult or an EncounterEvents, got {pairs.shape}")
+    return pairs
+
+
+def _per_row(v, N, name, what):
+    """a scalar or (N,) argument `name` (its values are `what` in the message) as the (N,) float64 array the library takes"""
+    if v is None or np.ndim(v) not in (0, 1) or (np.ndim(v) == 1 and np.shape(v) != (N,)):
+        raise ValueError(f"{name}: expected a scalar or ({N},) {what}, got {None if v is None else np.shape(v)}")
+    return _ffi.per_sat(v, N)
+
+
+def _check_mu(mu):
+    from .constants import MU_EARTH
+    mu = float(MU_EARTH if mu is None else mu)
+    if not mu > 0.0:
+        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    return mu
+
+
+def _model(include_drag, include_J2, atmosphere, max_step):
+    """the model of a linearisation as the block functions take it: the keywords flags, max_step and atmosphere"""
+    if not max_step > 0.0:
+        raise ValueError(f"max_step: need > 0, got {max_step}")
+    return dict(flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
+
+
+def _context(device, slot, flags=0, atmosphere=None):
+    """context (device, slot), given the atmosphere first when the flags carry FLAG_ATMO"""
+    return _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+
+
+def _side_args(side, extras=0):
+    """one side of a call as the library takes it: count, row length, ns, Y, units, span and `extras` more pointers.  side =
+    (Y, units, span, ns) of _check_trajectories (extras 0), (Y, units, span, ns, P) of _check_cat (1: the covariances) or (Y, units,
+    span, P, radius, ns) of _check_side (2: the covariances and the radii); None: the side is absent"""
+    if side is None:
+        return (0, 0, None, None, None, None) + (None,) * extras
+    Y, units, span = side[:3]
+    ns, rest = (side[5], side[3:5]) if extras == 2 else (side[3], side[4:])
+    return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), *[_ffi.dptr_opt(a) for a in rest])
 
 
 def common_clock(Y, units, span, M, T0, T1, ns=None, device=0, return_status=False):
@@ -183,14 +235,7 @@ def _screen(src, cat, M, T0, T1, thr, max_pairs, device, devices):
     S = src[0].shape[0]
     out = dict(dmin=np.empty(S), partner=np.empty(S, dtype=np.int32), tca=np.empty(S))
     how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, thr=thr, max_pairs=int(max_pairs) if thr > 0.0 else 0)
-    rows = np.arange(S)
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        parts = sharded_call(_screen_call, devices, [rows], out, **how)
-    else:
-        if devices is not None and len(devices) == 1:
-            device = int(devices[0])
-        parts = [_screen_call(rows, device=device, slot=0, out=out, **how)]
+    parts = dispatch(_screen_call, [np.arange(S)], out, device, devices, **how)
     pairs = sort_pairs(np.concatenate([p for p, _, _ in parts]))[:int(max_pairs)]
     return ConjunctionResult(out["dmin"], out["partner"], out["tca"], pairs, sum(n for _, n, _ in parts), *parts[0][2])
 
@@ -211,10 +256,8 @@ def _screen_call(rows, *, device, slot, out, src, cat, M, T0, T1, thr, max_pairs
     if len(src) == 1:
         _ffi.call(name, ctx, *counts, M, *[_ffi.dptr(eph) for eph, in sides], *tail)
     else:
-        traj = [a for N, (Y, units, span, ns) in zip(counts, sides)
-                for a in (N, Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span))]
         statuses[:len(sides)] = [np.zeros(N, dtype=np.int32) for N in counts]
-        _ffi.call(name + "_traj", ctx, *traj, M, *tail, *[_ffi.iptr(st) for st in statuses[:len(sides)]])
+        _ffi.call(name + "_traj", ctx, *[a for side in sides for a in _side_args(side)], M, *tail, *[_ffi.iptr(st) for st in statuses[:len(sides)]])
     n = int(n_pairs[0])
     return pairs[:min(n, max_pairs)], n, statuses
 
@@ -222,11 +265,7 @@ def _screen_call(rows, *, device, slot, out, src, cat, M, T0, T1, thr, max_pairs
 def _check_list_call(who, pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units, cat_span, cat_ns, M):
     """the checks screen_pairs and screen_events make of the list, the two sides and the grid -> (pairs, src, cat, M, T0, T1,
     given_traj); src, cat: each side as (eph,) or (Y, units, span, ns), cat None without a catalogue"""
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    pairs = _as_pairs(pairs)
     given_eph, given_traj = eph is not None or cat_eph is not None, Y is not None or cat_Y is not None
     if given_eph == given_traj:
         raise ValueError(f"{who}: give either eph [, cat_eph], or the trajectories Y, units, span [, cat_Y, cat_units, cat_span] with M")
@@ -272,17 +311,15 @@ def screen_pairs(pairs, T0, T1, eph=None, cat_eph=None, device=0, devices=None, 
                                                               cat_span, cat_ns, M)
     n = pairs.shape[0]
     out = dict(out=np.empty((n, 4)), status=np.zeros(n, dtype=np.int32))
-    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
-    if n:
-        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1)
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    statuses = _screen_list(pairs, out, device, devices, src=src, cat=cat, M=M, T0=T0, T1=T1)
     return (out["out"], out["status"], *statuses) if given_traj else (out["out"], out["status"])
+
+
+def _screen_list(pairs, out, device, devices, **how):
+    """the blocks of a list's rows to the devices -> the ephemeris statuses of the first; an empty list makes no call and has none"""
+    if not len(pairs):
+        return [None, None]
+    return dispatch(_screen_pairs_call, [pairs], out, device, devices, **how)[0]
 
 
 def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1, events=None, track=None):
@@ -304,10 +341,9 @@ def _screen_pairs_call(pairs, *, device, slot, out, src, cat, M, T0, T1, events=
         _ffi.call(name, ctx, len(pairs), _ffi.dptr(pairs), S, D, M, _ffi.dptr(src[0]),
                   _ffi.dptr_opt(None if cat is None else cat[0]), *tail)
         return [None, None]
-    sides = [(N, side[0].shape[2], _ffi.iptr_opt(side[3]), _ffi.dptr(side[0]), _ffi.dptr(side[1]), _ffi.dptr(side[2])) if side is not None
-             else (0, 0, None, None, None, None) for N, side in ((S, src), (D, cat))]
     statuses = [np.zeros(S, dtype=np.int32), None if cat is None else np.zeros(D, dtype=np.int32)]
-    _ffi.call(name + "_traj", ctx, len(pairs), _ffi.dptr(pairs), *sides[0], *sides[1], M, *tail, *[_ffi.iptr_opt(st) for st in statuses])
+    _ffi.call(name + "_traj", ctx, len(pairs), _ffi.dptr(pairs), *_side_args(src), *_side_args(cat), M, *tail,
+              *[_ffi.iptr_opt(st) for st in statuses])
     return statuses
 
 
@@ -361,16 +397,7 @@ def screen_events(pairs, T0, T1, threshold=None, max_events=DEFAULT_MAX_EVENTS, 
     n, E = pairs.shape[0], int(max_events)
     out = dict(events=np.empty((n, E, 4)), info=np.empty((n, E, 2), dtype=np.int32), count=np.zeros(n, dtype=np.int32),
                status=np.zeros(n, dtype=np.int32))
-    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
-    if n:
-        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, events=(thr, E))
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    statuses = _screen_list(pairs, out, device, devices, src=src, cat=cat, M=M, T0=T0, T1=T1, events=(thr, E))
     return EncounterEvents(out["events"], out["info"], out["count"], out["status"], *statuses)
 
 
@@ -398,23 +425,12 @@ def screen_track(pairs, T0, T1, max_shift=None, eph=None, cat_eph=None, device=0
     cat_status).  A row of screen_events' or screen_pairs' output, given back on the same inputs, returns its own distance, time,
     interval and edge bit for bit.  An empty list returns empty arrays without a library call.  devices=[d0, d1, ...]: contiguous
     blocks of the list's rows on several devices (every device holds both sides), written in place, the bits of one device."""
-    if isinstance(pairs, EncounterEvents):
-        pairs = pairs.events
     pairs, src, cat, M, T0, T1, given_traj = _check_list_call("screen_track", pairs, T0, T1, eph, cat_eph, Y, units, span, ns, cat_Y, cat_units,
                                                               cat_span, cat_ns, M)
     shift = _check_max_shift(max_shift)
     n = pairs.shape[0]
     out = dict(out=np.empty((n, 4)), info=np.empty((n, 2), dtype=np.int32), status=np.zeros(n, dtype=np.int32))
-    statuses = [None, None]                                          # (an empty list: no ephemeris was computed)
-    if n:
-        how = dict(src=src, cat=cat, M=M, T0=T0, T1=T1, track=shift)
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            statuses = sharded_call(_screen_pairs_call, devices, [pairs], out, **how)[0]
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            statuses = _screen_pairs_call(pairs, device=device, slot=0, out=out, **how)
+    statuses = _screen_list(pairs, out, device, devices, src=src, cat=cat, M=M, T0=T0, T1=T1, track=shift)
     return (out["out"], out["info"], out["status"], *statuses) if given_traj else (out["out"], out["info"], out["status"])
 
 
@@ -520,12 +536,40 @@ def _check_p0(P0, S, name="P0"):
 def _check_q(q, S):
     if q is None:
         return None
-    if np.ndim(q) not in (0, 1) or (np.ndim(q) == 1 and np.shape(q) != (S,)):
-        raise ValueError(f"q: expected a scalar or ({S},) acceleration noise densities (m^2/s^3), got {np.shape(q)}")
-    q = _ffi.per_sat(q, S)
+    q = _per_row(q, S, "q", "acceleration noise densities (m^2/s^3)")
     if not (q >= 0.0).all():
         raise ValueError("q: need densities >= 0")
     return q
+
+
+def _check_plan(Y, U, units, span, consts, ns, P=None, few="need", thrust_optional=False):
+    """the plan a linearising call takes: trajectories of at least 2 nodes, the thrust at the nodes (None only where thrust_optional),
+    the constants, and the covariances at the nodes where there are any -> (Y, U, units, span, consts, ns, P)"""
+    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
+    S, _, K = Y.shape
+    if K < 2:
+        raise ValueError(f"Y: {few} at least 2 nodes, got {Y.shape}")
+    if U is not None or not thrust_optional:
+        U = _ffi.as_f64(U)
+        if U.shape != (S, 3, K):
+            raise ValueError(f"U: expected ({S}, 3, {K}) thrust at the nodes, got {U.shape}")
+    consts = _ffi.as_f64(consts)
+    if consts.shape != (S, _ffi.NCONST):
+        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
+    if P is not None:
+        P = _ffi.as_f64(P)
+        if P.shape != (S, K, 6, 6):
+            raise ValueError(f"P: expected ({S}, {K}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
+    return Y, U, units, span, consts, ns, P
+
+
+def _covariance_problem(Y, units, span, consts, P0, U, ns, q):
+    """what covariance and covariance_thrust share: the checks -> the batched inputs [Y, units, span, consts, P0, U, ns, q] and the
+    result arrays P and status"""
+    Y, U, units, span, consts, ns, _ = _check_plan(Y, U, units, span, consts, ns, few="a covariance needs", thrust_optional=True)
+    S, _, n = Y.shape
+    out = dict(P=_ffi.result_pool.take((S, n, 6, 6)), status=np.zeros(S, dtype=np.int32))
+    return [Y, units, span, consts, _check_p0(P0, S), U, ns, _check_q(q, S)], out
 
 
 def covariance(Y, units, span, consts, P0, U=None, ns=None, q=None, include_drag=False, include_J2=False, atmosphere=None,
@@ -539,39 +583,17 @@ def covariance(Y, units, span, consts, P0, U=None, ns=None, q=None, include_drag
     or a non-finite P0 is NaN throughout
     (return_status=True returns (P, status) with its MPCX_ST_* code); nodes past ns come back zero.  devices=[d0, d1, ...]: contiguous
     blocks of satellites on several devices (sharding.sharded_call), written in place, the bits of one device."""
-    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
-    S, _, n = Y.shape
-    if n < 2:
-        raise ValueError(f"Y: a covariance needs at least 2 nodes, got {Y.shape}")
-    consts = _ffi.as_f64(consts)
-    if consts.shape != (S, _ffi.NCONST):
-        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
-    P0, q = _check_p0(P0, S), _check_q(q, S)
-    if U is not None:
-        U = _ffi.as_f64(U)
-        if U.shape != (S, 3, n):
-            raise ValueError(f"U: expected ({S}, 3, {n}) thrust at the nodes, got {U.shape}")
-    if not max_step > 0.0:
-        raise ValueError(f"max_step: need > 0, got {max_step}")
-    out = dict(P=_ffi.result_pool.take((S, n, 6, 6)), status=np.zeros(S, dtype=np.int32))
-    how = dict(flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
-    batched = [Y, units, span, consts, P0, U, ns, q]
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        sharded_call(_covariance_call, devices, batched, out, **how)
-    else:
-        if devices is not None and len(devices) == 1:
-            device = int(devices[0])
-        _covariance_call(*batched, device=device, slot=0, out=out, **how)
+    batched, out = _covariance_problem(Y, units, span, consts, P0, U, ns, q)
+    dispatch(_covariance_call, batched, out, device, devices, **_model(include_drag, include_J2, atmosphere, max_step))
     return (out["P"], out["status"]) if return_status else out["P"]
 
 
 def _covariance_call(Y, units, span, consts, P0, U, ns, q, *, device, slot, out, flags, max_step, atmosphere):
     """one block of satellites on context (device, slot), P and status into `out` (the block's views)"""
     S, _, n = Y.shape
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_covariance_batch", ctx, S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr_opt(U), _ffi.dptr(units), _ffi.dptr(span),
-              _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(out["P"]), _ffi.iptr(out["status"]))
+    _ffi.call("mpcx_covariance_batch", _context(device, slot, flags, atmosphere), S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr_opt(U),
+              _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(out["P"]),
+              _ffi.iptr(out["status"]))
 
 
 def gates_execution(scales, fixed_magnitude_N=0.0, proportional_magnitude=0.0, fixed_pointing_N=0.0, proportional_pointing_rad=0.0, off_N=0.0):
@@ -581,19 +603,13 @@ def gates_execution(scales, fixed_magnitude_N=0.0, proportional_magnitude=0.0, f
     in EACH satellite's own thrust unit (SatelliteScale.units["force"]): the counterpart of constellation_mpc.normalised_limits."""
     S = len(scales)
     force = np.array([sc.units["force"] for sc in scales], dtype=np.float64)
-    per_sat = lambda v, name: _per_sat_named(v, S, name)
+    per_sat = lambda v, name: _per_row(v, S, name, "values")
     out = np.column_stack([per_sat(fixed_magnitude_N, "fixed_magnitude_N") / force, per_sat(proportional_magnitude, "proportional_magnitude"),
                            per_sat(fixed_pointing_N, "fixed_pointing_N") / force, per_sat(proportional_pointing_rad, "proportional_pointing_rad"),
                            per_sat(off_N, "off_N") / force])
     if not (np.isfinite(out).all() and (out >= 0.0).all()):
         raise ValueError("gates_execution: need finite figures >= 0")
     return _ffi.as_f64(out)
-
-
-def _per_sat_named(v, S, name):
-    if np.ndim(v) not in (0, 1) or (np.ndim(v) == 1 and np.shape(v) != (S,)):
-        raise ValueError(f"{name}: expected a scalar or ({S},) values, got {np.shape(v)}")
-    return _ffi.per_sat(v, S)
 
 
 def _check_execution(execution, S):
@@ -619,35 +635,14 @@ def covariance_thrust(Y, units, span, consts, P0, U, execution, mass_var0=None, 
     (return_status=True appends status).  return_mass=True appends Pm (S, n, 7): the mass's covariances with position and velocity
     and its variance.  The results come as P[, Pm][, status].  devices=[d0, d1, ...]: contiguous blocks of satellites on several
     devices (sharding.sharded_call), the bits of one device."""
-    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
-    S, _, n = Y.shape
-    if n < 2:
-        raise ValueError(f"Y: a covariance needs at least 2 nodes, got {Y.shape}")
-    consts = _ffi.as_f64(consts)
-    if consts.shape != (S, _ffi.NCONST):
-        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
-    P0, q = _check_p0(P0, S), _check_q(q, S)
     if U is None:
         raise ValueError("U: covariance_thrust needs the thrust at the nodes (without thrust: covariance)")
-    U = _ffi.as_f64(U)
-    if U.shape != (S, 3, n):
-        raise ValueError(f"U: expected ({S}, 3, {n}) thrust at the nodes, got {U.shape}")
-    execution = _check_execution(execution, S)
-    mass_var0 = None if mass_var0 is None else _per_sat_named(mass_var0, S, "mass_var0")
-    if not max_step > 0.0:
-        raise ValueError(f"max_step: need > 0, got {max_step}")
-    out = dict(P=_ffi.result_pool.take((S, n, 6, 6)), status=np.zeros(S, dtype=np.int32))
+    batched, out = _covariance_problem(Y, units, span, consts, P0, U, ns, q)
+    S, _, n = batched[0].shape
+    batched += [_check_execution(execution, S), None if mass_var0 is None else _per_row(mass_var0, S, "mass_var0", "values")]
     if return_mass:
         out["Pm"] = np.empty((S, n, 7))
-    how = dict(flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
-    batched = [Y, units, span, consts, P0, U, ns, q, execution, mass_var0]
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        sharded_call(_covariance_thrust_call, devices, batched, out, **how)
-    else:
-        if devices is not None and len(devices) == 1:
-            device = int(devices[0])
-        _covariance_thrust_call(*batched, device=device, slot=0, out=out, **how)
+    dispatch(_covariance_thrust_call, batched, out, device, devices, **_model(include_drag, include_J2, atmosphere, max_step))
     res = (out["P"],) + ((out["Pm"],) if return_mass else ()) + ((out["status"],) if return_status else ())
     return res[0] if len(res) == 1 else res
 
@@ -655,10 +650,9 @@ def covariance_thrust(Y, units, span, consts, P0, U, execution, mass_var0=None, 
 def _covariance_thrust_call(Y, units, span, consts, P0, U, ns, q, execution, mass_var0, *, device, slot, out, flags, max_step, atmosphere):
     """one block of satellites on context (device, slot), P, Pm and status into `out` (the block's views)"""
     S, _, n = Y.shape
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_covariance_thrust_batch", ctx, S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span),
-              _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(execution), _ffi.dptr_opt(mass_var0),
-              _ffi.dptr(out["P"]), _ffi.dptr_opt(out.get("Pm")), _ffi.iptr(out["status"]))
+    _ffi.call("mpcx_covariance_thrust_batch", _context(device, slot, flags, atmosphere), S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
+              _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(execution),
+              _ffi.dptr_opt(mass_var0), _ffi.dptr(out["P"]), _ffi.dptr_opt(out.get("Pm")), _ffi.iptr(out["status"]))
 
 
 def _check_side(Y, units, span, P, radius, ns, pre=""):
@@ -672,9 +666,24 @@ def _check_side(Y, units, span, P, radius, ns, pre=""):
     P = _ffi.as_f64(P)
     if P.shape != (S, n, 6, 6):
         raise ValueError(f"{pre}P: expected ({S}, {n}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
-    if np.ndim(radius) not in (0, 1) or (np.ndim(radius) == 1 and np.shape(radius) != (S,)):
-        raise ValueError(f"{pre}radius: expected a scalar or ({S},) hard-body radii in m, got {np.shape(radius)}")
-    return Y, units, span, P, _ffi.per_sat(radius, S), ns
+    return Y, units, span, P, _per_row(radius, S, pre + "radius", "hard-body radii in m"), ns
+
+
+def _check_cat_radii(cat):
+    """cat = (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]) of the probabilities -> _check_side's tuple; None stays None"""
+    if cat is None:
+        return None
+    if len(cat) not in (5, 6):
+        raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
+    return _check_side(*cat[:5], cat[5] if len(cat) == 6 else None, "cat_")
+
+
+def _check_window(half_window, panels, n):
+    """the window of every row of a list of n -> (half (n,), panels)"""
+    half = _per_row(half_window, n, "half_window", "seconds")
+    if np.ndim(panels) != 0 or int(panels) != panels or not 1 <= panels <= _ffi.PW_MAX_PANELS:
+        raise ValueError(f"panels: need an integer in 1 .. {_ffi.PW_MAX_PANELS}, got {panels}")
+    return half, int(panels)
 
 
 def collision_probability(pairs, radius, Y, units, span, P, ns=None, cat=None, mu=None, device=0, devices=None):
@@ -688,49 +697,19 @@ def collision_probability(pairs, radius, Y, units, span, P, ns=None, cat=None, m
     the plane across the relative velocity, by a fixed 64-point rule: accurate to 1e-13 relative for radius / sigma <= 2, 2e-6 at 8,
     6e-3 at 20 (include/mpcx.h).  An empty list returns empty arrays without a library call.  devices=[d0, d1, ...]: contiguous
     blocks of the list's rows on several devices (every device holds all trajectories), written in place, the bits of one device."""
-    from .constants import MU_EARTH
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
-    rows = _check_side(Y, units, span, P, radius, ns)
-    cols = None
-    if cat is not None:
-        if len(cat) not in (5, 6):
-            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
-        cols = _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
-    mu = float(MU_EARTH if mu is None else mu)
-    if not mu > 0.0:
-        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    pairs = _as_pairs(pairs)
+    how = dict(rows=_check_side(Y, units, span, P, radius, ns), cols=_check_cat_radii(cat), mu=_check_mu(mu))
     n = pairs.shape[0]
     out = dict(out=np.empty((n, _ffi.NPC)), status=np.zeros(n, dtype=np.int32))
     if n:
-        how = dict(rows=rows, cols=cols, mu=mu)
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(_collision_call, devices, [pairs], out, **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            _collision_call(pairs, device=device, slot=0, out=out, **how)
+        dispatch(_collision_call, [pairs], out, device, devices, **how)
     return CollisionResult(pairs, out["out"], out["status"])
-
-
-def _side_args(Y, units, span, ns, P):
-    """one side of a pairs list as the library takes it: (count, row length, ns, Y, units, span, P); Y None: the side is absent"""
-    if Y is None:
-        return (0, 0, None, None, None, None, None)
-    return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr_opt(P))
 
 
 def _collision_call(pairs, *, device, slot, out, rows, cols, mu):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
-    def side(sd):
-        Y, units, span, P, radius, ns = sd if sd is not None else (None,) * 6
-        return _side_args(Y, units, span, ns, P) + (_ffi.dptr_opt(radius),)
     pairs = _ffi.as_f64(pairs)
-    _ffi.call("mpcx_collision_probability", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
+    _ffi.call("mpcx_collision_probability", _context(device, slot), len(pairs), _ffi.dptr(pairs), *_side_args(rows, 2), *_side_args(cols, 2), mu,
               _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
 
 
@@ -762,11 +741,9 @@ def encounter_half_window(col, radius_sum, nsigma=8):
     if not isinstance(col, CollisionResult):
         raise ValueError(f"col: expected a CollisionResult, got {type(col).__name__}")
     n = len(col.speed)
-    if np.ndim(radius_sum) not in (0, 1) or (np.ndim(radius_sum) == 1 and np.shape(radius_sum) != (n,)):
-        raise ValueError(f"radius_sum: expected a scalar or ({n},) summed radii in m, got {np.shape(radius_sum)}")
+    R = _per_row(radius_sum, n, "radius_sum", "summed radii in m")
     if not (np.ndim(nsigma) == 0 and nsigma > 0.0):
         raise ValueError(f"nsigma: need a number > 0, got {nsigma}")
-    R = np.broadcast_to(np.asarray(radius_sum, dtype=np.float64), (n,))
     speed = np.asarray(col.speed, dtype=np.float64)
     moving = speed > 0.0                                                 # (False for NaN)
     h = np.full(n, np.inf)
@@ -789,50 +766,21 @@ def collision_probability_window(pairs, radius, Y, units, span, P, half_window, 
     positive and finite, or an empty cut window, is status 9 for that row.  An empty list returns empty arrays without a library call.
     devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices (every device holds all trajectories), written in
     place, the bits of one device."""
-    from .constants import MU_EARTH
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    elif isinstance(pairs, EncounterEvents):
-        pairs = pairs.events
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time), a ConjunctionResult or an EncounterEvents, got {pairs.shape}")
-    rows = _check_side(Y, units, span, P, radius, ns)
-    cols = None
-    if cat is not None:
-        if len(cat) not in (5, 6):
-            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
-        cols = _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
-    mu = float(MU_EARTH if mu is None else mu)
-    if not mu > 0.0:
-        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
+    pairs = _as_pairs(pairs)
+    how = dict(rows=_check_side(Y, units, span, P, radius, ns), cols=_check_cat_radii(cat), mu=_check_mu(mu))
     n = pairs.shape[0]
-    if half_window is None or np.ndim(half_window) not in (0, 1) or (np.ndim(half_window) == 1 and np.shape(half_window) != (n,)):
-        raise ValueError(f"half_window: expected a scalar or ({n},) seconds, got {None if half_window is None else np.shape(half_window)}")
-    half = _ffi.per_sat(half_window, n)
-    if np.ndim(panels) != 0 or int(panels) != panels or not 1 <= panels <= _ffi.PW_MAX_PANELS:
-        raise ValueError(f"panels: need an integer in 1 .. {_ffi.PW_MAX_PANELS}, got {panels}")
+    half, how["panels"] = _check_window(half_window, panels, n)
     out = dict(out=np.empty((n, _ffi.NPW)), status=np.zeros(n, dtype=np.int32))
     if n:
-        how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels))
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(_collision_window_call, devices, [pairs, half], out, **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            _collision_window_call(pairs, half, device=device, slot=0, out=out, **how)
+        dispatch(_collision_window_call, [pairs, half], out, device, devices, **how)
     return WindowCollisionResult(pairs, out["out"], out["status"])
 
 
 def _collision_window_call(pairs, half, *, device, slot, out, rows, cols, mu, panels):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
-    def side(sd):
-        Y, units, span, P, radius, ns = sd if sd is not None else (None,) * 6
-        return _side_args(Y, units, span, ns, P) + (_ffi.dptr_opt(radius),)
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
-    _ffi.call("mpcx_collision_probability_window", _ffi.context(device, slot), len(pairs), _ffi.dptr(pairs), *side(rows), *side(cols), mu,
-              _ffi.dptr(half), panels, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+    _ffi.call("mpcx_collision_probability_window", _context(device, slot), len(pairs), _ffi.dptr(pairs), *_side_args(rows, 2), *_side_args(cols, 2),
+              mu, _ffi.dptr(half), panels, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
 
 
 def catalogue_covariance(position_m, velocity_m_s, P0, T0, T1, n, q=None, include_J2=True, max_step=DEFAULT_MAX_STEP, device=0,
@@ -884,6 +832,15 @@ class AvoidanceResult:
         return U
 
 
+def _check_who(who, against_catalogue=False):
+    """who = 'i', 'j' or 'both' as the library takes it"""
+    if who not in _WHO:
+        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
+    if against_catalogue and who != "i":
+        raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
+    return _WHO[who]
+
+
 def _check_cat(cat):
     """cat = (cat_Y, cat_units, cat_span[, cat_P][, cat_ns]) of avoidance -> (Y, units, span, ns, P or None)"""
     if not 3 <= len(cat) <= 5:
@@ -902,41 +859,17 @@ def _check_cat(cat):
     return Y, units, span, ns, P
 
 
-def _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu):
-    """the checks every avoidance call makes of the list, the target, the plan, the covariances, the catalogue and the model
+def _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, mu):
+    """the checks every avoidance call makes of the list, the target, the plan, the covariances and the catalogue
     -> (pairs, Y, U, units, span, consts, ns, P, cols, mu)"""
-    from .constants import MU_EARTH
-    if isinstance(pairs, ConjunctionResult):
-        pairs = pairs.pairs
-    pairs = _ffi.as_f64(pairs)
-    if pairs.ndim != 2 or pairs.shape[1] != 4:
-        raise ValueError(f"pairs: expected (n, 4) rows (i, j, distance, time) or a ConjunctionResult, got {pairs.shape}")
+    pairs = _as_pairs(pairs)
     if not (np.ndim(target) == 0 and np.isfinite(target) and target > 0.0):
         raise ValueError(f"target: need a positive finite distance, got {target}")
-    Y, units, span, ns = _check_trajectories(Y, units, span, ns)
-    S, _, K = Y.shape
-    if K < 2:
-        raise ValueError(f"Y: need at least 2 nodes, got {Y.shape}")
-    U, consts = _ffi.as_f64(U), _ffi.as_f64(consts)
-    if U.shape != (S, 3, K):
-        raise ValueError(f"U: expected ({S}, 3, {K}) thrust at the nodes, got {U.shape}")
-    if consts.shape != (S, _ffi.NCONST):
-        raise ValueError(f"consts: expected ({S}, {_ffi.NCONST}) normalised constants per satellite, got {consts.shape}")
-    if P is not None:
-        P = _ffi.as_f64(P)
-        if P.shape != (S, K, 6, 6):
-            raise ValueError(f"P: expected ({S}, {K}, 6, 6) covariances at the nodes (covariance), got {P.shape}")
-    cols = None
-    if cat is not None:
-        cols = _check_cat(cat)
-        if (P is None) != (cols[4] is None):
-            raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
-    if not max_step > 0.0:
-        raise ValueError(f"max_step: need > 0, got {max_step}")
-    mu = float(MU_EARTH if mu is None else mu)
-    if not mu > 0.0:
-        raise ValueError(f"mu: need > 0 m^3/s^2, got {mu}")
-    return pairs, Y, U, units, span, consts, ns, P, cols, mu
+    plan = _check_plan(Y, U, units, span, consts, ns, P)
+    cols = None if cat is None else _check_cat(cat)
+    if cols is not None and (P is None) != (cols[4] is None):
+        raise ValueError("P and cat_P come together (a Mahalanobis target) or not at all (a target in metres)")
+    return (pairs, *plan, cols, _check_mu(mu))
 
 
 def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=None, who="i", include_drag=False, include_J2=False,
@@ -952,35 +885,30 @@ def avoidance(pairs, target, Y, U, units, span, consts, ns=None, P=None, cat=Non
     gains distance fastest per unit of effort -- the first-order optimum, not the optimum over the whole target ellipse
     (include/mpcx.h).  A pair already at or beyond the target gets du = 0.  An empty list returns empty arrays without a library
     call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
-    if who not in _WHO:
-        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
-    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu)
-    if cols is not None and who != "i":
-        raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
+    _check_who(who)
+    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, mu)
     n, K, NS = pairs.shape[0], Y.shape[2], 1 if cols is not None else 2
     out = dict(out=np.empty((n, _ffi.NAV)), du=_ffi.result_pool.take((n, NS, 3, K)),
                sens=_ffi.result_pool.take((n, NS, 3, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
+    how = dict(rows=(Y, U, units, span, consts, ns, P), cols=cols, mu=mu, target=float(target), who=_check_who(who, cols is not None),
+               **_model(include_drag, include_J2, atmosphere, max_step))
     if n:
-        how = dict(rows=(Y, U, units, span, consts, ns, P), cols=cols, mu=mu, target=float(target), who=_WHO[who],
-                   flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere)
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(_avoidance_call, devices, [pairs], out, **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            _avoidance_call(pairs, device=device, slot=0, out=out, **how)
+        dispatch(_avoidance_call, [pairs], out, device, devices, **how)
     return AvoidanceResult(pairs, out["out"], out["du"], out["sens"], out["status"])
+
+
+def _plan_args(Y, U, units, span, consts, ns, flags, max_step):
+    """the plan and the model of its linearisation as the library takes them, from S to max_step"""
+    return (Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags,
+            max_step)
 
 
 def _avoidance_call(pairs, *, device, slot, out, rows, cols, mu, target, who, flags, max_step, atmosphere):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
     Y, U, units, span, consts, ns, P = rows
-    col = _side_args(*(cols if cols is not None else (None,) * 5))
     pairs = _ffi.as_f64(pairs)
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_avoidance", ctx, len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
-              _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu, target, who,
+    _ffi.call("mpcx_avoidance", _context(device, slot, flags, atmosphere), len(pairs), _ffi.dptr(pairs),
+              *_plan_args(Y, U, units, span, consts, ns, flags, max_step), _ffi.dptr_opt(P), *_side_args(cols, 1), mu, target, who,
               _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
 
 
@@ -1022,42 +950,46 @@ class AvoidanceWindowResult:
     apply = AvoidanceResult.apply
 
 
-def _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu):
-    """the checks both window avoidance calls make: _encounter_problem's of the list, the plan and the model, and
-    collision_probability_window's of the covariances, the radii, the half windows and the panels -> (pairs, rows, cols, half, mu)"""
-    if who not in _WHO:
-        raise ValueError(f"who: expected 'i', 'j' or 'both', got {who!r}")
-    if isinstance(pairs, EncounterEvents):
-        pairs = pairs.events
+def _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, mu):
+    """the checks the window avoidance calls make: avoidance's of the list, the plan and who moves, and collision_probability_window's
+    of the covariances, the radii, the catalogue, the half windows and the panels -> the keywords pairs and half and those of the
+    block functions up to who"""
+    _check_who(who)
     if P is None:
         raise ValueError("P: the covariances at the nodes (covariance) are required")
-    cat3 = None
-    if cat is not None:
-        if len(cat) not in (5, 6):
-            raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_P, cat_radius[, cat_ns]), got {len(cat)} items")
-        if who != "i":
-            raise ValueError(f"who = {who!r}: against a catalogue only the satellite can manoeuvre (who='i')")
-        cat3 = (cat[0], cat[1], cat[2], cat[3]) + ((cat[5],) if len(cat) == 6 and cat[5] is not None else ())
-    pairs, Y, U, units, span, consts, ns, P, _, mu = _encounter_problem(pairs, 1.0, Y, U, units, span, consts, ns, P, cat3, max_step, mu)
-    rows = _check_side(Y, units, span, P, radius, ns)
-    cols = None if cat is None else _check_side(cat[0], cat[1], cat[2], cat[3], cat[4], cat[5] if len(cat) == 6 else None, "cat_")
-    n = pairs.shape[0]
-    if half_window is None or np.ndim(half_window) not in (0, 1) or (np.ndim(half_window) == 1 and np.shape(half_window) != (n,)):
-        raise ValueError(f"half_window: expected a scalar or ({n},) seconds, got {None if half_window is None else np.shape(half_window)}")
-    if np.ndim(panels) != 0 or int(panels) != panels or not 1 <= panels <= _ffi.PW_MAX_PANELS:
-        raise ValueError(f"panels: need an integer in 1 .. {_ffi.PW_MAX_PANELS}, got {panels}")
-    return pairs, rows + (U, consts), cols, _ffi.per_sat(half_window, n), mu
+    pairs = _as_pairs(pairs)
+    Y, U, units, span, consts, ns, P = _check_plan(Y, U, units, span, consts, ns, P)
+    cols = _check_cat_radii(cat)
+    half, panels = _check_window(half_window, panels, pairs.shape[0])
+    rows = _check_side(Y, units, span, P, radius, ns) + (U, consts)
+    return pairs, half, dict(rows=rows, cols=cols, mu=_check_mu(mu), panels=panels, who=_check_who(who, cols is not None))
 
 
-def _window_run(call, pairs, half, out, how, device, devices):
-    if len(pairs):
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(call, devices, [pairs, half], out, **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            call(pairs, half, device=device, slot=0, out=out, **how)
+def _window_arrays(n, how, return_sensitivities):
+    """the result arrays both window manoeuvres share, for a list of n rows of the problem `how`"""
+    K, NS = how["rows"][0].shape[2], 1 if how["cols"] is not None else 2
+    return dict(out=np.empty((n, _ffi.NAW)), du=_ffi.result_pool.take((n, NS, 3, K)),
+                sens=_ffi.result_pool.take((n, NS, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
+
+
+def _check_solve(target_p, tol, max_eval):
+    """the step search of the window manoeuvres as the block functions take it: the keywords target_p, tol and max_eval"""
+    if not (np.ndim(target_p) == 0 and 0.0 < target_p < 1.0):
+        raise ValueError(f"target_p: need a probability strictly between 0 and 1, got {target_p}")
+    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
+        raise ValueError(f"tol: need a positive finite number, got {tol}")
+    if np.ndim(max_eval) != 0 or int(max_eval) != max_eval or max_eval < 1:
+        raise ValueError(f"max_eval: need an integer >= 1, got {max_eval}")
+    return dict(target_p=float(target_p), tol=float(tol), max_eval=int(max_eval))
+
+
+def _check_rounds(rounds, prop_max_step):
+    """the flights of the refine calls -> (rounds, prop_max_step)"""
+    if not (np.ndim(rounds) == 0 and int(rounds) == rounds and rounds >= 0):
+        raise ValueError(f"rounds: need an integer >= 0, got {rounds}")
+    if not prop_max_step > 0.0:
+        raise ValueError(f"prop_max_step: need > 0, got {prop_max_step}")
+    return int(rounds), float(prop_max_step)
 
 
 def collision_window_sensitivity(pairs, radius, Y, U, units, span, consts, P, half_window, panels=DEFAULT_PANELS, ns=None, cat=None,
@@ -1070,31 +1002,29 @@ def collision_window_sensitivity(pairs, radius, Y, U, units, span, consts, P, ha
     object of a row moves (against a catalogue only "i").  The thrust moves the mean relative state only: the covariances, the window
     and the row's time are held (include/mpcx.h).  An empty list returns empty arrays without a library call.  devices=[d0, d1,
     ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
-    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
-    n, K, NS = pairs.shape[0], rows[0].shape[2], 1 if cols is not None else 2
+    pairs, half, how = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, mu)
+    n, K, NS = pairs.shape[0], how["rows"][0].shape[2], 1 if how["cols"] is not None else 2
     out = dict(out=np.empty((n, _ffi.NPW)), sens=_ffi.result_pool.take((n, NS, 3, K)),
-               state_grad=_ffi.result_pool.take((n, 64 * int(panels) + 1, 6)) if return_state_gradient else None,
+               state_grad=_ffi.result_pool.take((n, 64 * how["panels"] + 1, 6)) if return_state_gradient else None,
                status=np.zeros(n, dtype=np.int32))
-    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
-               max_step=float(max_step), atmosphere=atmosphere)
-    _window_run(_window_sensitivity_call, pairs, half, out, how, device, devices)
+    how.update(_model(include_drag, include_J2, atmosphere, max_step))
+    if n:
+        dispatch(_window_sensitivity_call, [pairs, half], out, device, devices, **how)
     return WindowSensitivityResult(pairs, out["out"], out["sens"], out["state_grad"], out["status"])
 
 
 def _window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step):
-    """the arguments both calls share, from n to who"""
+    """the arguments the window calls share, from n to who"""
     Y, units, span, P, radius, ns, U, consts = rows
-    cY, cunits, cspan, cP, cradius, cns = cols if cols is not None else (None,) * 6
-    return (len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units),
-            _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P), _ffi.dptr(radius), *_side_args(cY, cunits, cspan, cns, cP),
-            _ffi.dptr_opt(cradius), mu, _ffi.dptr(half), panels, who)
+    return (len(pairs), _ffi.dptr(pairs), *_plan_args(Y, U, units, span, consts, ns, flags, max_step), _ffi.dptr(P), _ffi.dptr(radius),
+            *_side_args(cols, 2), mu, _ffi.dptr(half), panels, who)
 
 
 def _window_sensitivity_call(pairs, half, *, device, slot, out, rows, cols, mu, panels, who, flags, max_step, atmosphere):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_collision_window_sensitivity", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step),
+    _ffi.call("mpcx_collision_window_sensitivity", _context(device, slot, flags, atmosphere),
+              *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step),
               _ffi.dptr(out["out"]), _ffi.dptr(out["sens"]), _ffi.dptr_opt(out.get("state_grad")), _ffi.iptr(out["status"]))
 
 
@@ -1111,27 +1041,20 @@ def avoidance_window(pairs, target_p, radius, Y, U, units, span, consts, P, half
     direction (the same object twice) is status 4, one that runs out of evaluations 8 while doubling and 5 while closing.  The
     covariances are held as given and the manoeuvre is not flown again here.  An empty list returns empty arrays without a library
     call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, written in place, the bits of one device."""
-    if not (np.ndim(target_p) == 0 and 0.0 < target_p < 1.0):
-        raise ValueError(f"target_p: need a probability strictly between 0 and 1, got {target_p}")
-    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
-        raise ValueError(f"tol: need a positive finite number, got {tol}")
-    if np.ndim(max_eval) != 0 or int(max_eval) != max_eval or max_eval < 1:
-        raise ValueError(f"max_eval: need an integer >= 1, got {max_eval}")
-    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
-    n, K, NS = pairs.shape[0], rows[0].shape[2], 1 if cols is not None else 2
-    out = dict(out=np.empty((n, _ffi.NAW)), du=_ffi.result_pool.take((n, NS, 3, K)),
-               sens=_ffi.result_pool.take((n, NS, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32))
-    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
-               max_step=float(max_step), atmosphere=atmosphere, target_p=float(target_p), tol=float(tol), max_eval=int(max_eval))
-    _window_run(_avoidance_window_call, pairs, half, out, how, device, devices)
+    solve = _check_solve(target_p, tol, max_eval)
+    pairs, half, how = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, mu)
+    how.update(_model(include_drag, include_J2, atmosphere, max_step), **solve)
+    out = _window_arrays(pairs.shape[0], how, return_sensitivities)
+    if len(pairs):
+        dispatch(_avoidance_window_call, [pairs, half], out, device, devices, **how)
     return AvoidanceWindowResult(pairs, out["out"], out["du"], out["sens"], out["status"])
 
 
 def _avoidance_window_call(pairs, half, *, device, slot, out, rows, cols, mu, panels, who, flags, max_step, atmosphere, target_p, tol, max_eval):
     """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_avoidance_window", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step), target_p, tol, max_eval,
+    _ffi.call("mpcx_avoidance_window", _context(device, slot, flags, atmosphere),
+              *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step), target_p, tol, max_eval,
               _ffi.dptr(out["out"]), _ffi.dptr(out["du"]), _ffi.dptr_opt(out.get("sens")), _ffi.iptr(out["status"]))
 
 
@@ -1174,41 +1097,25 @@ def avoidance_window_refine(pairs, target_p, radius, Y, U, units, span, consts, 
     each other -- so nothing is installed anywhere and the call has a block form: devices=[d0, d1, ...] deals contiguous blocks of
     the list's rows to several devices, written in place, the bits of one device.  An empty list returns empty arrays without a
     library call."""
-    if not (np.ndim(target_p) == 0 and 0.0 < target_p < 1.0):
-        raise ValueError(f"target_p: need a probability strictly between 0 and 1, got {target_p}")
-    if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
-        raise ValueError(f"tol: need a positive finite number, got {tol}")
-    if np.ndim(max_eval) != 0 or int(max_eval) != max_eval or max_eval < 1:
-        raise ValueError(f"max_eval: need an integer >= 1, got {max_eval}")
-    if not (np.ndim(rounds) == 0 and int(rounds) == rounds and rounds >= 0):
-        raise ValueError(f"rounds: need an integer >= 0, got {rounds}")
-    if not prop_max_step > 0.0:
-        raise ValueError(f"prop_max_step: need > 0, got {prop_max_step}")
+    solve = _check_solve(target_p, tol, max_eval)
+    rounds, prop_max_step = _check_rounds(rounds, prop_max_step)
     if track is None:
         grid = (0, 0.0, 0.0, 0.0)
     else:
         if np.ndim(track) != 1 or len(track) != 3:
             raise ValueError(f"track: expected None or (M, T0, T1), got {track!r}")
         grid = (*_check_grid(*track), _check_max_shift(max_shift))
-    pairs, rows, cols, half, mu = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, max_step, mu)
-    (S, _, K), n, NS, rounds, recov = rows[0].shape, pairs.shape[0], 1 if cols is not None else 2, int(rounds), bool(recov)
-    q = _check_q(q, S) if recov else None
-    out = dict(out=np.empty((n, _ffi.NAW)), du=_ffi.result_pool.take((n, NS, 3, K)),
-               sens=_ffi.result_pool.take((n, NS, 3, K)) if return_sensitivities else None, status=np.zeros(n, dtype=np.int32),
-               rounds_done=np.full(n, -1, dtype=np.int32), Y_flown=_ffi.result_pool.take((n, NS, 7, K)),
+    pairs, half, how = _window_problem(pairs, radius, Y, U, units, span, consts, P, half_window, panels, ns, cat, who, mu)
+    (S, _, K), n, recov = how["rows"][0].shape, pairs.shape[0], bool(recov)
+    out = _window_arrays(n, how, return_sensitivities)
+    NS = out["du"].shape[1]
+    out.update(rounds_done=np.full(n, -1, dtype=np.int32), Y_flown=_ffi.result_pool.take((n, NS, 7, K)),
                P_flown=_ffi.result_pool.take((n, NS, K, 6, 6)) if recov and return_covariances else None)
     hist = dict(p_history=np.empty((rounds + 2, n)), t_history=np.empty((rounds + 2, n)), p_predicted=np.empty((rounds + 1, n)))
-    how = dict(rows=rows, cols=cols, mu=mu, panels=int(panels), who=_WHO[who], flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
-               max_step=float(max_step), atmosphere=atmosphere, target_p=float(target_p), tol=float(tol), max_eval=int(max_eval),
-               prop_max_step=float(prop_max_step), rounds=rounds, grid=grid, recov=int(recov), q=q)
+    how.update(_model(include_drag, include_J2, atmosphere, max_step), **solve, prop_max_step=prop_max_step, rounds=rounds, grid=grid,
+               recov=int(recov), q=_check_q(q, S) if recov else None)
     if n:
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(_avoidance_window_refine_call, devices, [pairs, half], dict(out, **{k: (a, 1) for k, a in hist.items()}), **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            _avoidance_window_refine_call(pairs, half, device=device, slot=0, out=dict(out, **hist), **how)
+        dispatch(_avoidance_window_refine_call, [pairs, half], dict(out, **{k: (a, 1) for k, a in hist.items()}), device, devices, **how)
     return AvoidanceWindowRefineResult(pairs, out["out"], out["du"], out["sens"], out["status"], out["Y_flown"], out["P_flown"],
                                        hist["p_history"], hist["t_history"], hist["p_predicted"], out["rounds_done"])
 
@@ -1218,7 +1125,7 @@ def _avoidance_window_refine_call(pairs, half, *, device, slot, out, rows, cols,
     """one block of the list's rows on context (device, slot), into `out` (the block's views; a block's columns of the histories go
     through contiguous temporaries)"""
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    ctx = _context(device, slot, flags, atmosphere)
     hist = {k: out[k] if out[k].flags.c_contiguous else np.empty(out[k].shape) for k in ("p_history", "t_history", "p_predicted")}
     _ffi.call("mpcx_avoidance_window_refine", ctx, *_window_args(pairs, half, rows, cols, mu, panels, who, flags, max_step), target_p, tol,
               max_eval, prop_max_step, rounds, *grid, recov, _ffi.dptr_opt(q), _ffi.dptr(out["out"]), _ffi.dptr(out["du"]),
@@ -1291,22 +1198,20 @@ def _coupled(pairs, mover, against_catalogue):
     return np.isin(other, moving)
 
 
-def _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, tol, max_iter, max_step, mu):
-    """the checks avoidance_joint and avoidance_refine share -> (pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu)"""
+def _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, hold_terminal, tol, max_iter, mu):
+    """the checks avoidance_joint and avoidance_refine share -> the keywords their block functions share, from pairs to max_iter"""
     if not (np.ndim(tol) == 0 and np.isfinite(tol) and tol > 0.0):
         raise ValueError(f"tol: need a positive finite number, got {tol}")
     if not (np.ndim(max_iter) == 0 and int(max_iter) == max_iter and max_iter >= 1):
         raise ValueError(f"max_iter: need an integer >= 1, got {max_iter}")
-    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, max_step, mu)
+    pairs, Y, U, units, span, consts, ns, P, cols, mu = _encounter_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, mu)
     mover = _check_mover(who, pairs.shape[0], cols is not None)
     if u_max is not None:
-        S = Y.shape[0]
-        if np.ndim(u_max) not in (0, 1) or (np.ndim(u_max) == 1 and np.shape(u_max) != (S,)):
-            raise ValueError(f"u_max: expected a scalar or ({S},) normalised thrust limits, got {np.shape(u_max)}")
-        u_max = _ffi.per_sat(u_max, S)
+        u_max = _per_row(u_max, Y.shape[0], "u_max", "normalised thrust limits")
         if not (u_max > 0.0).all():
             raise ValueError("u_max: need positive limits (inf: no ball)")
-    return pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu
+    return dict(pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols, mu=mu, target=float(target),
+                hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter))
 
 
 def _joint_arrays(S, K, n, return_rows, return_terminal):
@@ -1329,38 +1234,40 @@ def avoidance_joint(pairs, target, Y, U, units, span, consts, ns=None, P=None, c
     iteration to max |F| <= tol (include/mpcx.h).  return_rows / return_terminal: the rows a_p (n, 3, K) and the terminal
     sensitivities (S, 6, 3, K).  An empty list returns zeros without a library call.  devices=[d0, d1, ...]: contiguous blocks of
     satellites on several devices (every device holds the whole plan and list), written in place, the bits of one device."""
-    pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
-                                                                                     u_max, tol, max_iter, max_step, mu)
-    (S, _, K), n = Y.shape, pairs.shape[0]
+    how = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, hold_terminal, tol, max_iter, mu)
+    how.update(_model(include_drag, include_J2, atmosphere, max_step))
+    (S, _, K), n = how["rows"][0].shape, len(how["pairs"])
     out = _joint_arrays(S, K, n, return_rows, return_terminal)
     if n:
-        how = dict(pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols, mu=mu, target=float(target),
-                   hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter), flags=_ffi.model_flags(include_drag, include_J2, atmosphere),
-                   max_step=float(max_step), atmosphere=atmosphere, whole=out)
-        index = np.arange(S)
-        if devices is not None and len(devices) > 1:
-            from .sharding import sharded_call
-            sharded_call(_avoidance_joint_call, devices, [index], None, **how)
-        else:
-            if devices is not None and len(devices) == 1:
-                device = int(devices[0])
-            _avoidance_joint_call(index, device=device, slot=0, out=None, **how)
-    return AvoidanceJointResult(pairs, mover, out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"],
-                                out["row_status"], _coupled(pairs, mover, cols is not None))
+        dispatch(_avoidance_joint_call, [np.arange(S)], None, device, devices, whole=out, **how)
+    return AvoidanceJointResult(*_joint_result(how, out))
+
+
+def _joint_result(how, out):
+    """AvoidanceJointResult's arguments from the problem and the result arrays"""
+    return (how["pairs"], how["mover"], out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"], out["row_status"],
+            _coupled(how["pairs"], how["mover"], how["cols"] is not None))
+
+
+def _joint_args(pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step):
+    """the arguments the joint calls share, from n to max_iter"""
+    Y, U, units, span, consts, ns, P, u_max = rows
+    return (len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), *_plan_args(Y, U, units, span, consts, ns, flags, max_step), _ffi.dptr_opt(P),
+            *_side_args(cols, 1), mu, target, _ffi.dptr_opt(u_max), hold, tol, max_iter)
+
+
+def _joint_outputs(out):
+    """the result arrays of _joint_arrays as the library takes them"""
+    return (_ffi.dptr(out["du"]), _ffi.dptr(out["sat_out"]), _ffi.dptr(out["row_out"]), _ffi.dptr_opt(out["rows"]), _ffi.dptr_opt(out["tsens"]),
+            _ffi.iptr(out["sat_status"]), _ffi.iptr(out["row_status"]))
 
 
 def _avoidance_joint_call(index, *, device, slot, out, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere,
                           whole):
     """the block of satellites index[0] .. index[-1] on context (device, slot): the library writes the block's satellites and the
     rows they own into the whole result set `whole`, and nothing else of it"""
-    Y, U, units, span, consts, ns, P, u_max = rows
-    col = _side_args(*(cols if cols is not None else (None,) * 5))
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
-    _ffi.call("mpcx_avoidance_joint", ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
-              _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
-              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, int(index[0]), len(index), _ffi.dptr(whole["du"]), _ffi.dptr(whole["sat_out"]),
-              _ffi.dptr(whole["row_out"]), _ffi.dptr_opt(whole["rows"]), _ffi.dptr_opt(whole["tsens"]), _ffi.iptr(whole["sat_status"]),
-              _ffi.iptr(whole["row_status"]))
+    _ffi.call("mpcx_avoidance_joint", _context(device, slot, flags, atmosphere),
+              *_joint_args(pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step), int(index[0]), len(index), *_joint_outputs(whole))
 
 
 # ---- the joint manoeuvre flown again, re-screened and corrected (include/mpcx.h: mpcx_avoidance_refine; csrc/avoidance_joint.hip)
@@ -1401,46 +1308,28 @@ def avoidance_refine(pairs, target, Y, U, units, span, consts, M, T0, T1, rounds
     far from its given time a row's encounter may be found; a row that loses its encounter reads (+inf, NaN), its mover's solve
     fails with MPCX_ST_BADK = 9 and the satellite is frozen with the manoeuvre it had.  max_shift is read only with track=True; with
     track=False nothing changes."""
-    if isinstance(pairs, EncounterEvents):
-        pairs = pairs.events
-    pairs, Y, U, units, span, consts, ns, P, cols, mover, u_max, mu = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who,
-                                                                                     u_max, tol, max_iter, max_step, mu)
+    how = _joint_problem(pairs, target, Y, U, units, span, consts, ns, P, cat, who, u_max, hold_terminal, tol, max_iter, mu)
+    pairs, Y = how["pairs"], how["rows"][0]
     (S, _, K), n = Y.shape, pairs.shape[0]
-    M, T0, T1 = _check_grid(M, T0, T1)
-    if not (np.ndim(rounds) == 0 and int(rounds) == rounds and rounds >= 0):
-        raise ValueError(f"rounds: need an integer >= 0, got {rounds}")
-    if not prop_max_step > 0.0:
-        raise ValueError(f"prop_max_step: need > 0, got {prop_max_step}")
+    rounds, prop_max_step = _check_rounds(rounds, prop_max_step)
     if devices is not None and len(devices) > 1:
         raise ValueError(f"devices: avoidance_refine runs on one device (every round needs every mover's new trajectory), got {len(devices)}")
-    if devices is not None and len(devices) == 1:
-        device = int(devices[0])
-    rounds = int(rounds)
-    shift = _check_max_shift(max_shift) if track else None
     out = dict(_joint_arrays(S, K, n, return_rows, return_terminal), Y_flown=Y.copy(), pairs_flown=pairs.copy(),
                d0=np.zeros((rounds + 2, n)), tca=np.zeros((rounds + 2, n)), term=np.zeros((rounds + 2, S)), rounds_done=np.full(S, -1, dtype=np.int32),
                rhs_rows=np.zeros(n) if return_rhs else None, rhs_term=np.zeros((S, 6)) if return_rhs else None)
+    how.update(_model(include_drag, include_J2, atmosphere, max_step), grid=_check_grid(M, T0, T1), prop_max_step=prop_max_step, rounds=rounds,
+               track=_check_max_shift(max_shift) if track else None, whole=out)
     if n:
-        _avoidance_refine_call(device=device, slot=0, out=out, pairs=pairs, mover=mover, rows=(Y, U, units, span, consts, ns, P, u_max), cols=cols,
-                               mu=mu, target=float(target), hold=1 if hold_terminal else 0, tol=float(tol), max_iter=int(max_iter),
-                               flags=_ffi.model_flags(include_drag, include_J2, atmosphere), max_step=float(max_step), atmosphere=atmosphere,
-                               grid=(M, T0, T1), prop_max_step=float(prop_max_step), rounds=rounds, track=shift)
-    joint = (pairs, mover, out["du"], out["sat_out"], out["row_out"], out["rows"], out["tsens"], out["sat_status"], out["row_status"],
-             _coupled(pairs, mover, cols is not None))
-    return AvoidanceRefineResult(joint, out["Y_flown"], out["pairs_flown"], out["d0"], out["tca"], out["term"], out["rounds_done"],
+        dispatch(_avoidance_refine_call, [], None, device, devices, **how)
+    return AvoidanceRefineResult(_joint_result(how, out), out["Y_flown"], out["pairs_flown"], out["d0"], out["tca"], out["term"], out["rounds_done"],
                                  out["rhs_rows"], out["rhs_term"])
 
 
-def _avoidance_refine_call(*, device, slot, out, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere, grid,
+def _avoidance_refine_call(*, device, slot, out, whole, pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step, atmosphere, grid,
                            prop_max_step, rounds, track=None):
-    """the whole list and all satellites on context (device, slot), into `out`; track = max_shift: the tracked re-screen"""
-    Y, U, units, span, consts, ns, P, u_max = rows
-    col = _side_args(*(cols if cols is not None else (None,) * 5))
-    ctx = _ffi.atmosphere_context(device, slot, atmosphere if flags & _ffi.FLAG_ATMO else None)
+    """the whole list and all satellites on context (device, slot), into `whole`; track = max_shift: the tracked re-screen"""
     name, mode = ("mpcx_avoidance_refine", ()) if track is None else ("mpcx_avoidance_refine_tracked", (track,))
-    _ffi.call(name, ctx, len(pairs), _ffi.dptr(pairs), _ffi.iptr(mover), Y.shape[0], Y.shape[2], _ffi.iptr_opt(ns),
-              _ffi.dptr(Y), _ffi.dptr(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr_opt(P), *col, mu,
-              target, _ffi.dptr_opt(u_max), hold, tol, max_iter, *grid, prop_max_step, rounds, *mode, _ffi.dptr(out["du"]), _ffi.dptr(out["sat_out"]),
-              _ffi.dptr(out["row_out"]), _ffi.dptr_opt(out["rows"]), _ffi.dptr_opt(out["tsens"]), _ffi.iptr(out["sat_status"]),
-              _ffi.iptr(out["row_status"]), _ffi.dptr(out["Y_flown"]), _ffi.dptr(out["pairs_flown"]), _ffi.dptr(out["d0"]), _ffi.dptr(out["tca"]),
-              _ffi.dptr(out["term"]), _ffi.iptr(out["rounds_done"]), _ffi.dptr_opt(out["rhs_rows"]), _ffi.dptr_opt(out["rhs_term"]))
+    _ffi.call(name, _context(device, slot, flags, atmosphere), *_joint_args(pairs, mover, rows, cols, mu, target, hold, tol, max_iter, flags, max_step),
+              *grid, prop_max_step, rounds, *mode, *_joint_outputs(whole), _ffi.dptr(whole["Y_flown"]), _ffi.dptr(whole["pairs_flown"]),
+              _ffi.dptr(whole["d0"]), _ffi.dptr(whole["tca"]), _ffi.dptr(whole["term"]), _ffi.iptr(whole["rounds_done"]),
+              _ffi.dptr_opt(whole["rhs_rows"]), _ffi.dptr_opt(whole["rhs_term"]))

@@ -44,6 +44,11 @@ def normalised_limits(scales, r_min=None, r_max=None, u_max=None, min_mass=None)
     return out
 
 
+def _catalogue_keywords(trajectories):
+    """a catalogue's trajectories (Y, units, span[, ns]) as the keywords conjunction's screens take; None: none"""
+    return {} if trajectories is None else dict(zip(("cat_Y", "cat_units", "cat_span", "cat_ns"), trajectories))
+
+
 class ConstellationMPC:
     def __init__(self, sats, base_res=100, tf_horizon=1, tf_interval=1, r_des=1.5, scp_iterations=2, sim_base_res=100,
                  include_drag=True, include_J2=True, device=0, strict=False, scales=None, verbose=False, devices=None,
@@ -315,9 +320,8 @@ class ConstellationMPC:
         from . import conjunction as cj
         if len(catalogue) not in (3, 4):
             raise ValueError(f"catalogue: expected (Y, units, span) or (Y, units, span, ns), got {len(catalogue)} items")
-        cat = dict(zip(("cat_Y", "cat_units", "cat_span", "cat_ns"), catalogue))
         kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        res = [cj.screen_against(threshold=threshold_m, device=self.device, devices=self.devices, **w, **cat, **kw)
+        res = [cj.screen_against(threshold=threshold_m, device=self.device, devices=self.devices, **w, **_catalogue_keywords(catalogue), **kw)
                for w in self._screen_windows(what, samples_per_node, T0, T1)]
         return res[0] if len(res) == 1 else cj.combine(res)
 
@@ -335,11 +339,65 @@ class ConstellationMPC:
         if execution is None:
             if mass_var0 is not None:
                 raise ValueError("mass_var0: a mass variance needs execution (covariance carries no mass)")
-            return cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, include_drag=self.plan_drag,
-                                 include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None, **where)
+            return cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **self._conjunction_model(),
+                                 **where)
         return cj.covariance_thrust(w["Y"], w["units"], w["span"], self.consts, P0, self._plan[1], execution, mass_var0=mass_var0, ns=w["ns"],
-                                    q=q, include_drag=self.plan_drag, include_J2=self.plan_J2,
-                                    atmosphere=self.atmosphere if self.plan_drag else None, **where)
+                                    q=q, **self._conjunction_model(), **where)
+
+    def _conjunction_model(self, model="plan"):
+        """the model keywords of conjunction's linearising calls: 'plan' the planning model (plan_drag, plan_J2), 'truth' the model the
+        segments are flown with (include_drag, include_J2); the atmosphere beside the drag"""
+        if model not in ("plan", "truth"):
+            raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
+        drag, J2 = (self.plan_drag, self.plan_J2) if model == "plan" else (self.include_drag, self.include_J2)
+        return dict(include_drag=drag, include_J2=J2, atmosphere=self.atmosphere if drag else None)
+
+    def _u_max(self):
+        """every satellite's thrust limit: the upper bound of this instance's u_lim option, per-satellite tables included"""
+        from .optimizer import DEFAULT_OPTIONS
+        u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
+        return np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
+
+    @staticmethod
+    def _catalogue_with_radii(catalogue):
+        """catalogue = (Y, units, span, P, radius[, ns]) -> (what conjunction's probabilities take as cat, its trajectories (Y, units, span,
+        ns) for the screen); None: (None, None)"""
+        if catalogue is None:
+            return None, None
+        if len(catalogue) not in (5, 6):
+            raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
+        cat = tuple(catalogue)
+        return cat, cat[:3] + (cat[5] if len(cat) == 6 else None,)
+
+    @staticmethod
+    def _catalogue_plain(catalogue):
+        """catalogue = (Y, units, span[, P][, ns]) -> (what conjunction's avoidance calls take as cat, its trajectories (Y, units, span, ns)
+        for the screen); None: (None, None)"""
+        if catalogue is None:
+            return None, None
+        if not 3 <= len(catalogue) <= 5:
+            raise ValueError(f"catalogue: expected (Y, units, span[, P][, ns]), got {len(catalogue)} items")
+        cat = tuple(catalogue)
+        counts = [a for a in cat[3:] if a is None or np.ndim(a) != 4]      # (what follows the span and is not P)
+        ns = counts[0] if counts else None
+        return cat, cat[:3] + (None if ns is None else np.ascontiguousarray(ns, dtype=np.int32),)
+
+    def _screen_plan(self, threshold_m, samples_per_node, max_pairs, trajectories=None):
+        """the last plan's screen window, its pairs list at threshold_m -- inside the constellation, or against the catalogue whose
+        trajectories = (Y, units, span, ns) are given -- and the device keywords -> (w, screened, where)"""
+        from . import conjunction as cj
+        (w,) = self._screen_windows("plan", samples_per_node)
+        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
+        where = dict(device=self.device, devices=self.devices)
+        screen = cj.screen if trajectories is None else cj.screen_against
+        return w, screen(threshold=threshold_m, **_catalogue_keywords(trajectories), **where, **w, **kw), where
+
+    def _plan_probabilities(self, threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution=None, mass_var0=None):
+        """what the probabilities and the window manoeuvres start from: the plan screened at threshold_m (against catalogue = (Y, units,
+        span, P, radius[, ns]) if given) and its covariance -> (w, screened, P, the keywords ns, cat, device and devices)"""
+        cat, trajectories = self._catalogue_with_radii(catalogue)
+        w, screened, where = self._screen_plan(threshold_m, samples_per_node, max_pairs, trajectories)
+        return w, screened, self._plan_covariance(w, P0, q, execution, mass_var0), dict(ns=w["ns"], cat=cat, **where)
 
     def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None, execution=None,
                               mass_var0=None):
@@ -353,20 +411,8 @@ class ConstellationMPC:
         scalar or (S,)).  The plan only: a linearisation needs the thrust a trajectory was flown with, and ConstellationMPC does not
         keep the thrust of its flown segments."""
         from . import conjunction as cj
-        (w,) = self._screen_windows("plan", samples_per_node)
-        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        where = dict(device=self.device, devices=self.devices)
-        cat = None
-        if catalogue is None:
-            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
-        else:
-            if len(catalogue) not in (5, 6):
-                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
-            cat = tuple(catalogue)
-            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
-                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = self._plan_covariance(w, P0, q, execution, mass_var0)
-        return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, ns=w["ns"], cat=cat, **where)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0)
+        return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan)
 
     def collision_probability_window(self, threshold_m, P0, radius_m, half_window, panels=4, q=None, samples_per_node=4, max_pairs=None,
                                      catalogue=None, execution=None, mass_var0=None):
@@ -377,20 +423,7 @@ class ConstellationMPC:
         pair, in seconds; panels as there).  For the pairs of a constellation that pass each other slowly the short-encounter figure
         is outside its model, and without relative speed it fails: the window figure is the one to read there.  The plan only."""
         from . import conjunction as cj
-        (w,) = self._screen_windows("plan", samples_per_node)
-        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        where = dict(device=self.device, devices=self.devices)
-        cat = None
-        if catalogue is None:
-            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
-        else:
-            if len(catalogue) not in (5, 6):
-                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
-            cat = tuple(catalogue)
-            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
-                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = self._plan_covariance(w, P0, q, execution, mass_var0)
-        plan = dict(ns=w["ns"], cat=cat, **where)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0)
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
                 cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
 
@@ -404,24 +437,10 @@ class ConstellationMPC:
         the changed thrust table.  The covariances are not propagated again under the manoeuvre and nothing is flown
         (avoidance_window_refine does both).  The plan only."""
         from . import conjunction as cj
-        (w,) = self._screen_windows("plan", samples_per_node)
-        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        where = dict(device=self.device, devices=self.devices)
-        model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
-        cat = None
-        if catalogue is None:
-            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
-        else:
-            if len(catalogue) not in (5, 6):
-                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
-            cat = tuple(catalogue)
-            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
-                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
-        plan = dict(ns=w["ns"], cat=cat, **where)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue)
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.avoidance_window(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
-                                    panels=panels, who=who, tol=tol, max_eval=max_eval, **model, **plan))
+                                    panels=panels, who=who, tol=tol, max_eval=max_eval, **self._conjunction_model(), **plan))
 
     def avoidance_window_refine(self, threshold_m, P0, radius_m, half_window, target_p, rounds=2, model="plan", recov=True, panels=4, q=None,
                                 samples_per_node=4, max_pairs=None, catalogue=None, who="i", track=True, max_shift=None,
@@ -436,53 +455,20 @@ class ConstellationMPC:
         one satellite can conflict (AvoidanceWindowRefineResult.apply(plan U, row) is one row's changed thrust table).  The plan
         only."""
         from . import conjunction as cj
-        if model not in ("plan", "truth"):
-            raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
-        (w,) = self._screen_windows("plan", samples_per_node)
-        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        where = dict(device=self.device, devices=self.devices)
-        plan_model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
-        cat = None
-        if catalogue is None:
-            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
-        else:
-            if len(catalogue) not in (5, 6):
-                raise ValueError(f"catalogue: expected (Y, units, span, P, radius) or (Y, units, span, P, radius, ns), got {len(catalogue)} items")
-            cat = tuple(catalogue)
-            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2],
-                                         cat_ns=cat[5] if len(cat) == 6 else None, **where, **w, **kw)
-        P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **plan_model, **where)
-        if model == "truth":
-            plan_model = dict(include_drag=self.include_drag, include_J2=self.include_J2, atmosphere=self.atmosphere if self.include_drag else None)
-        plan = dict(ns=w["ns"], cat=cat, **where)
+        flight = self._conjunction_model(model)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue)
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.avoidance_window_refine(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
                                            rounds=rounds, track=(w["M"], w["T0"], w["T1"]) if track else None, max_shift=max_shift, recov=recov,
-                                           q=q, prop_max_step=prop_max_step, panels=panels, who=who, tol=tol, max_eval=max_eval, **plan_model,
-                                           **plan))
+                                           q=q, prop_max_step=prop_max_step, panels=panels, who=who, tol=tol, max_eval=max_eval, **flight, **plan))
 
     def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
         """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the
         constellation, or against catalogue = (Y, units, span[, P][, ns])), the plan's covariance when P0 is given, the catalogue as
-        a tuple, and the planning model and device keywords -> (w, screened, P, cat, model, where)"""
-        from . import conjunction as cj
-        (w,) = self._screen_windows("plan", samples_per_node)
-        kw = {} if max_pairs is None else {"max_pairs": max_pairs}
-        where = dict(device=self.device, devices=self.devices)
-        model = dict(include_drag=self.plan_drag, include_J2=self.plan_J2, atmosphere=self.atmosphere if self.plan_drag else None)
-        cat = None
-        if catalogue is None:
-            screened = cj.screen(threshold=threshold_m, **where, **w, **kw)
-        else:
-            if not 3 <= len(catalogue) <= 5:
-                raise ValueError(f"catalogue: expected (Y, units, span[, P][, ns]), got {len(catalogue)} items")
-            cat = tuple(catalogue)
-            cat_ns = cj._check_cat(cat)[3]
-            screened = cj.screen_against(threshold=threshold_m, cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2], cat_ns=cat_ns, **where, **w, **kw)
-        P = None
-        if P0 is not None:
-            P = cj.covariance(w["Y"], w["units"], w["span"], self.consts, P0, U=self._plan[1], ns=w["ns"], q=q, **model, **where)
-        return w, screened, P, cat, model, where
+        a tuple and as the screens' keywords, and the device keywords -> (w, screened, P, cat, cat_kw, where)"""
+        cat, trajectories = self._catalogue_plain(catalogue)
+        w, screened, where = self._screen_plan(threshold_m, samples_per_node, max_pairs, trajectories)
+        return w, screened, None if P0 is None else self._plan_covariance(w, P0, q, None, None), cat, _catalogue_keywords(trajectories), where
 
     def encounters(self, threshold_m, P0=None, radius_m=None, q=None, samples_per_node=4, max_pairs=None, max_events=16, catalogue=None):
         """EVERY close approach of the last plan's listed pairs, not only the closest -> (ConjunctionResult, EncounterEvents).  The
@@ -524,9 +510,9 @@ class ConstellationMPC:
         or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceResult.apply(plan U, row) is the changed
         thrust table; feeding it back into the solver's constraints is not done here."""
         from . import conjunction as cj
-        w, screened, P, cat, model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
+        w, screened, P, cat, _, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
         return screened, cj.avoidance(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, ns=w["ns"], P=P, cat=cat,
-                                      who=who, **model, **where)
+                                      who=who, **self._conjunction_model(), **where)
 
     def avoidance_joint(self, threshold_m, target, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i",
                         hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, return_rows=False,
@@ -540,13 +526,10 @@ class ConstellationMPC:
         the same threshold before (screen(what='plan') / screen_against) and so knows the list.  AvoidanceJointResult.apply(plan U)
         is the changed thrust table; the solver-side encounter rows remain open, this call is their check."""
         from . import conjunction as cj
-        w, screened, P, cat, model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
-        from .optimizer import DEFAULT_OPTIONS
-        u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
-        u_max = np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
+        w, screened, P, cat, _, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
         return screened, cj.avoidance_joint(screened, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts, ns=w["ns"], P=P,
-                                            cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol, max_iter=max_iter,
-                                            return_rows=return_rows, return_terminal=return_terminal, **model, **where)
+                                            cat=cat, who=who, u_max=self._u_max(), hold_terminal=hold_terminal, tol=tol, max_iter=max_iter,
+                                            return_rows=return_rows, return_terminal=return_terminal, **self._conjunction_model(), **where)
 
     def avoidance_refine(self, threshold_m, target, rounds=3, P0=None, q=None, samples_per_node=4, max_pairs=None, catalogue=None, who="i",
                          hold_terminal=True, tol=_ffi.AJ_DEFAULT_TOL, max_iter=_ffi.AJ_DEFAULT_MAX_ITER, prop_max_step=1e-3, model="plan",
@@ -563,24 +546,15 @@ class ConstellationMPC:
         EncounterEvents, AvoidanceRefineResult) with the result's rows in events.events' order.  A satellite that moves for more
         than MPCX_AJ_MAX_ROWS = 8 rows gets MPCX_ST_BADK = 9 as from avoidance_joint; who as an array has one entry per event then."""
         from . import conjunction as cj
-        if model not in ("plan", "truth"):
-            raise ValueError(f"model: expected 'plan' or 'truth', got {model!r}")
-        w, screened, P, cat, plan_model, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
-        if model == "truth":
-            plan_model = dict(include_drag=self.include_drag, include_J2=self.include_J2, atmosphere=self.atmosphere if self.include_drag else None)
-        from .optimizer import DEFAULT_OPTIONS
-        u_lim = np.asarray({**DEFAULT_OPTIONS, **self.OPTIONS(self.horizon), **self.options}["u_lim"], dtype=np.float64)
-        u_max = np.ascontiguousarray(np.broadcast_to(u_lim[..., 1], (len(self.sats),)))
-        found = None
-        if events:
-            cat_kw = {} if cat is None else dict(cat_Y=cat[0], cat_units=cat[1], cat_span=cat[2], cat_ns=cj._check_cat(cat)[3])
-            found = cj.screen_events(screened, threshold=threshold_m, max_events=max_events, **w, **cat_kw, **where)
+        flight = self._conjunction_model(model)
+        w, screened, P, cat, cat_kw, where = self._screened_plan(threshold_m, samples_per_node, max_pairs, catalogue, P0, q)
+        found = cj.screen_events(screened, threshold=threshold_m, max_events=max_events, **w, **cat_kw, **where) if events else None
         res = cj.avoidance_refine(screened if found is None else found.events, target, w["Y"], self._plan[1], w["units"], w["span"], self.consts,
                                   w["M"], w["T0"], w["T1"], track=found is not None,
-                                  rounds=rounds, ns=w["ns"], P=P, cat=cat, who=who, u_max=u_max, hold_terminal=hold_terminal, tol=tol,
+                                  rounds=rounds, ns=w["ns"], P=P, cat=cat, who=who, u_max=self._u_max(), hold_terminal=hold_terminal, tol=tol,
                                   max_iter=max_iter, prop_max_step=prop_max_step, return_rows=return_rows, return_terminal=return_terminal,
                                   return_rhs=return_rhs, device=self.device, devices=None if self.devices is None else list(self.devices)[:1],
-                                  **plan_model)
+                                  **flight)
         if install:
             ok = (res.status == 0) & np.isfinite(res.du).all(axis=(1, 2))
             X, U = np.array(self._plan[0], dtype=np.float64), np.array(self._plan[1], dtype=np.float64)

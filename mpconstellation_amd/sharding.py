@@ -6,7 +6,8 @@ data-path collective.  Two ways to use several devices:
    sharded_call below -- one host thread and one mpcx context (own stream, own staging pools) per device, each solving its
    contiguous block and writing its results IN PLACE into its slice of ONE result set allocated for the whole constellation
    (the satellite axis is outermost everywhere, so a block's slice of a C-ordered array is itself contiguous: the library's
-   copy-out is the only pass over the results).  This replaces the reference's serial loop over the constellation
+   copy-out is the only pass over the results); dispatch is what a wrapper calls with its `device` and `devices` arguments: it
+   is sharded_call for several devices and one call on the whole arrays otherwise.  This replaces the reference's serial loop over the constellation
    (simulator.py:41,58).  (Until round 4 every block allocated its own arrays and the blocks were np.concatenate'd afterwards on
    one host thread: 267 MB at 65 536 x 30, the largest term of an 8-device step.)"""
 import threading
@@ -86,6 +87,19 @@ def sharded_call(fn, devices, batched, outs, *args, **kw):
         res = [f.result() for f in futs]
     last_call.update(blocks=spans, wall=(t_in, time.perf_counter()))
     return res
+
+
+def dispatch(fn, batched, outs, device, devices, slot=0, **kw):
+    """What every batched wrapper does with its device arguments -> the list of fn's return values.  devices with more than one
+    entry: sharded_call.  Otherwise ONE call fn(*batched, device=d, slot=slot, out=outs, **kw) with the whole arrays, d = devices[0]
+    where a list of one is given, else `device`.  outs as sharded_call takes it: None values are left out, an (array, 1) entry is
+    its array."""
+    if devices is not None and len(devices) > 1:
+        return sharded_call(fn, devices, batched, outs, **kw)
+    if devices is not None and len(devices) == 1:
+        device = int(devices[0])
+    whole = {name: a[0] if isinstance(a, tuple) else a for name, a in (outs or {}).items() if a is not None}
+    return [fn(*batched, device=device, slot=slot, out=whole, **kw)]
 
 
 def block_views(outs, first, count):

@@ -42,13 +42,8 @@ def propagate_batch(y0, tf, consts, law, n_eval, include_drag=False, include_J2=
                atmosphere=atmosphere if include_drag else None)
     out = dict(y=_ffi.result_pool.take((S, 7, n_eval)), status=np.zeros(S, dtype=np.int32), nsteps=np.zeros(S, dtype=np.int32),
                u=_ffi.result_pool.take((S, 3, n_eval)) if thrust else None)
-    if devices is not None and len(devices) > 1:
-        from .sharding import sharded_call
-        sharded_call(_propagate_call, devices, batched, out, **how)
-    else:
-        if devices is not None and len(devices) == 1:
-            device = int(devices[0])
-        _propagate_call(*batched, device=device, slot=slot, out=out, **how)
+    from .sharding import dispatch
+    dispatch(_propagate_call, batched, out, device, devices, slot, **how)
     return (out["y"], out["status"], out["nsteps"], out["u"]) if thrust else (out["y"], out["status"], out["nsteps"])
 
 
