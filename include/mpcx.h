@@ -1412,6 +1412,108 @@ int mpcx_avoidance_refine_tracked_dev(mpcx_ctx *ctx, int n, const double *pairs,
                                       double *hist_term, int32_t *rounds_done, double *rhs_rows, double *rhs_term, void *workspace,
                                       void *stream);
 
+/*
+ * mpcx_collision_probability_mc: the collision probability of listed rows by sampled flights through the truth model.  Every other
+ * probability of this library is a linearised Gaussian figure (chained transition matrices, a fixed quadrature rule); here n_samples
+ * worlds are drawn -- initial states, masses, thrust execution errors --, every object of every row is flown through the nonlinear
+ * dynamics by mpcx_propagate_batch_ragged_dev, and what is counted is how often the two flown objects come within R = radius_i +
+ * radius_j inside the row's window.  There is no white process noise: the figure corresponds to mpcx_covariance_batch /
+ * mpcx_covariance_thrust_batch with q = 0.  There is no mu argument: the flight takes mu from consts.
+ * Arguments.  n, pairs [n][4] rows exactly as the screens and mpcx_conjunction_events write them.  The row side: S, K, Ks, Y [S][7][K],
+ * U [S][3][K] (NULL: zero thrust), units, span, consts, flags as mpcx_covariance_batch takes them; prop_max_step > 0 the flight's
+ * step limit; P0 [S][6][6] in m and m/s at the FIRST node (its upper triangle is read); exec [S][MPCX_NEXEC] (NULL: perfect
+ * execution) and m_var0 [S] (NULL: 0) with mpcx_covariance_thrust_batch's meaning; radius [S].  The column side: D, cat_K, cat_Ks,
+ * cat_Y, cat_units, cat_span, cat_consts, cat_P0, cat_radius; cat_Y = NULL: the all-pairs form (j indexes the constellation, the
+ * other cat_ arguments are ignored); catalogue objects fly with zero thrust and no execution error under the same flags.
+ * half_window [n] in seconds; scan >= 1 scan intervals per window; n_samples >= 1; seed; max_flights: 0 the library's default
+ * (262144), otherwise an upper bound on the virtual trajectories of one side in flight at once, which bounds the workspace: samples
+ * are processed in chunks of floor(max_flights / (n NS)) samples, at least one per chunk (NS = 2 in the all-pairs form, 1 with a
+ * catalogue, whose side flies as many again).  The chunking changes no bit.
+ * One sample s is one world.  Every draw is Philox4x32-10 (ten rounds, multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 /
+ * BB67AE85) with key = (seed low word, seed high word) and counter = (s, object index, block, side), side 0 the constellation and 1
+ * the catalogue: the draws of object o in sample s do not depend on the list, the row, the chunking, the launch shape or the device,
+ * so a satellite that appears in several rows has the SAME flown trajectory in all of them, any block of rows gives the bits of
+ * the whole list, and the per-sample records of different rows are joint samples.  One block gives two uniforms, u = ((w_a >> 5) 2^26
+ * + (w_b >> 6) + 0.5) 2^-53 from the words (0, 1) and (2, 3) -- strictly inside (0, 1): in binary64 the + 0.5 is rounded to even above
+ * 2^52, and the one value midway between 1 - 2^-53 and 1 (all 53 bits set) is rounded down --
+ * and from them two normals, z_a = r cos(2 pi u_2), z_b = r sin(2 pi u_2), r = sqrt(-2 ln u_1).  Blocks 0-2:
+ * the six state normals z_0 .. z_5 (block b gives z_2b, z_2b+1); block 3: the mass normal (z_a); blocks 4 + 2k and 5 + 2k: the
+ * normals of thrust node k (z_1 = z_a, z_2 = z_b of the first, z_3 = z_a of the second).
+ *   initial state   x0 = Y[o][0:6, 0] + D^-1 L z, D = diag(L, L, L, V, V, V) the units, P0 = L L^T by columns for a positive
+ *                   SEMI-definite P0.  The zero-pivot rule: with d_j = P0_jj - sum_k<j L_jk^2, c_ij = P0_ji - sum_k<j L_ik L_jk and
+ *                   tol_j = 1e-12 P0_jj: d_j > tol_j is a regular pivot (L_jj = sqrt d_j, L_ij = c_ij / L_jj); |d_j| <= tol_j is a zero
+ *                   pivot, column j of L is zero and every c_ij^2 <= tol_j P0_ii is required; anything else -- d_j < -tol_j, a
+ *                   negative or non-finite diagonal entry -- cannot be factored: MPCX_ST_NUMERIC
+ *   mass            m0 = Y[o][6, 0] + sqrt(m_var0) z
+ *   thrust node k   u_k + s_par z_1 u^ + s_perp (z_2 e_1 + z_3 e_2), s_par, s_perp and u_off as in mpcx_covariance_thrust_batch, e_1 the
+ *                   coordinate axis on which |u^| is smallest (the first of equal ones) made orthogonal to u^ and normalised, e_2 = u^
+ *                   x e_1; nothing is added at a node with |u_k| <= u_off, and no draw is made there.
+ * Flight.  Every (row, slot, sample) is a virtual satellite flown by mpcx_propagate_batch_ragged_dev exactly as
+ * mpcx_avoidance_window_refine flies: MPCX_CTRL_SEQUENCE on the sample's thrust table (a zero table for U = NULL and for the
+ * catalogue), Kus = n_evals = Ks[o], end_tau = 1, tf = (span[1] - span[0]) / units[1], the given flags, prop_max_step.
+ * Scan, per (row, sample).  The window [t_a, t_b] is mpcx_collision_probability_window's: t +- half_window cut to both spans, with
+ * the same MPCX_ST_BADK tests (made on the given trajectories).  It is cut into `scan` equal intervals, instant i at t_a + i (t_b -
+ * t_a) / scan, the last one at t_b.  Both objects' positions and velocities at the instants come from mpcx_ephemeris_batch's cubic
+ * Hermite on their own FLOWN nodes; inside an interval the relative position is the cubic Hermite of the end differences and end
+ * relative velocities, and its minimum follows the screens' interval rule: the ends, the clamped minimum of the chord, three Newton
+ * steps.  With q0, q1, qmin the squared distances at an interval's ends and at its minimum: inside_start = q(t_a) <= R^2; an
+ * interval counts one ENTRY when q0 > R^2 and (q1 <= R^2 or qmin <= R^2); entries is their number; hit = inside_start or entries >= 1;
+ * (dmin, t_min) the smallest distance found and its time, the earliest of equal ones.  Two entries inside one scan interval count
+ * as one, and an exit and re-entry inside an interval that starts inside counts as none: that is the resolution `scan` must buy.
+ * Outputs.  counts [n][MPCX_NMCC] int64 (MPCX_MCC_*): integers, independent of any summation order.  out [n][MPCX_NMC] (MPCX_MC_*),
+ * formed on the device from the counts with N = N_OK = flown - failed:  P_HIT = hits / N;  SE_HIT = sqrt(P_HIT (1 - P_HIT) / N);
+ * START, ENTRIES the means per sample;  SE_BOUND = sqrt(var / N), var = (sum b^2 - (sum b)^2 / N) / (N - 1) the sample variance of
+ * b = inside_start + entries (0 for N = 1);  EXCESS = START + ENTRIES - P_HIT, how far the window rule's figure lies above the
+ * probability because paths re-enter;  TA, TB, N_OK.  status [n].  Optional, NULL allowed, and asking for them changes no other bit:
+ * samples [n][n_samples][MPCX_NMS] (MPCX_MS_*), Y_samples [n][NS][n_samples][7][K] and U_samples [n][NS][n_samples][3][K], the row
+ * side's flown trajectories and executed thrust tables (slot 0 = i, 1 = j; columns past Ks come back zero; a failed flight is NaN in
+ * Y_samples).
+ * status: the window call's statuses; then MPCX_ST_BADK for an object whose span and time unit give no positive finite tf;
+ * then MPCX_ST_NUMERIC for a P0 that cannot be factored, or a negative or non-finite exec entry or m_var0, of either object; then
+ * MPCX_ST_NUMERIC for a row of which no sample survived its flight.  A sample whose flight of either object ends with a status other
+ * than 0 (or without a finite distance: MPCX_ST_NUMERIC) is counted in FAILED and left out of every other count; its samples row is
+ * NaN, NaN, 0, 0, the status.  A failed row is NaN in out (and in samples' distances and Y_samples / U_samples), zero in counts, and
+ * leaves its neighbours alone.  R <= 0: zeros in out but TA, TB, zeros in counts and samples, MPCX_ST_OK, as in the window call.
+ * n < 1, S < 1, K < 2, prop_max_step <= 0, an unknown flag, MPCX_FLAG_ATMO without drag or without an atmosphere on the context, scan <
+ * 1, n_samples < 1, max_flights < 0, a catalogue with D < 1 or cat_K < 2 or without one of its arrays, a NULL pairs, Y, units, span,
+ * consts, P0, radius, half_window, counts, out or status: MPCX_E_BADARG with "collision_probability_mc" in the message, nothing
+ * enqueued.  The _dev variant takes device pointers throughout and a workspace of mpcx_collision_probability_mc_workspace_bytes(n,
+ * S, K, D, cat_K, n_samples, max_flights) bytes (D = 0: the all-pairs form; 0 for arguments the call would refuse; contents
+ * unspecified on entry and exit).  All passes are enqueued on one stream, their number is fixed by the arguments, nothing is read
+ * back; the counts are summed with 64-bit integer atomics.
+ */
+#define MPCX_NMCC 6
+enum { MPCX_MCC_FLOWN = 0,  /* samples flown */
+       MPCX_MCC_FAILED,     /* of them: a flight status other than 0 */
+       MPCX_MCC_START,      /* sum inside_start */
+       MPCX_MCC_ENTRIES,    /* sum entries */
+       MPCX_MCC_SQUARES,    /* sum (inside_start + entries)^2 */
+       MPCX_MCC_HIT };      /* sum hit */
+#define MPCX_NMC 9
+enum { MPCX_MC_P_HIT = 0, MPCX_MC_SE_HIT, MPCX_MC_START, MPCX_MC_ENTRIES, MPCX_MC_SE_BOUND, MPCX_MC_EXCESS, MPCX_MC_TA, MPCX_MC_TB,
+       MPCX_MC_N_OK };
+#define MPCX_NMS 5
+enum { MPCX_MS_DMIN = 0,    /* m */
+       MPCX_MS_T_MIN,       /* s */
+       MPCX_MS_INSIDE_START, MPCX_MS_ENTRIES,
+       MPCX_MS_STATUS };    /* the flight's MPCX_ST_* (slot 0's first, then the column object's) */
+size_t mpcx_collision_probability_mc_workspace_bytes(int n, int S, int K, int D, int cat_K, int n_samples, int max_flights);
+int mpcx_collision_probability_mc(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                  const double *U, const double *units, const double *span, const double *consts, int flags,
+                                  double prop_max_step, const double *P0, const double *exec, const double *m_var0, const double *radius,
+                                  int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y, const double *cat_units,
+                                  const double *cat_span, const double *cat_consts, const double *cat_P0, const double *cat_radius,
+                                  const double *half_window, int scan, int n_samples, uint64_t seed, int max_flights, int64_t *counts,
+                                  double *out, int32_t *status, double *samples, double *Y_samples, double *U_samples);
+int mpcx_collision_probability_mc_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                                      const double *U, const double *units, const double *span, const double *consts, int flags,
+                                      double prop_max_step, const double *P0, const double *exec, const double *m_var0,
+                                      const double *radius, int D, int cat_K, const int32_t *cat_Ks, const double *cat_Y,
+                                      const double *cat_units, const double *cat_span, const double *cat_consts, const double *cat_P0,
+                                      const double *cat_radius, const double *half_window, int scan, int n_samples, uint64_t seed,
+                                      int max_flights, int64_t *counts, double *out, int32_t *status, double *samples,
+                                      double *Y_samples, double *U_samples, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,8 +232,21 @@ _SIGS = {
                                                     C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, C.c_int, C.c_double,
                                                     C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _vp, _vp, _vp, _vp,
                                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the collision probability by sampled flights through the truth model (after flags: prop_max_step, P0, exec, m_var0, radius; the
+    # catalogue with its consts; half_window, scan, n_samples, seed, max_flights; counts, out, status, samples, Y_samples, U_samples)
+    "mpcx_collision_probability_mc_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "mpcx_collision_probability_mc": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
+                                                _dp, _dp, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int,
+                                                C.c_uint64, C.c_int, _lp, _dp, _ip, _dp, _dp, _dp]),
+    "mpcx_collision_probability_mc_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double,
+                                                    _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int,
+                                                    C.c_int, C.c_uint64, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-NEXEC = 5                                                                   # MPCX_NEXEC: (s_fm, s_pm, s_fp, s_pp, u_off) of mpcx_covariance_thrust_batch's exec
+NMCC, NMC, NMS = 6, 9, 5                                                    # MPCX_NMCC, MPCX_NMC, MPCX_NMS: columns of mpcx_collision_probability_mc's counts, out, samples
+MCC_FLOWN, MCC_FAILED, MCC_START, MCC_ENTRIES, MCC_SQUARES, MCC_HIT = range(NMCC)
+MC_P_HIT, MC_SE_HIT, MC_START, MC_ENTRIES, MC_SE_BOUND, MC_EXCESS, MC_TA, MC_TB, MC_N_OK = range(NMC)
+MS_DMIN, MS_T_MIN, MS_INSIDE_START, MS_ENTRIES, MS_STATUS = range(NMS)
+NEXEC = 5                                                                  # MPCX_NEXEC: (s_fm, s_pm, s_fp, s_pp, u_off) of mpcx_covariance_thrust_batch's exec
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
 NPW, PW_MAX_PANELS = 7, 64                                                  # MPCX_NPW: columns of mpcx_collision_probability_window's out
@@ -439,6 +452,10 @@ def dptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(_ip)
+
+
+def lptr(a):
+    return a.ctypes.data_as(_lp)
 
 
 def dptr_opt(a):

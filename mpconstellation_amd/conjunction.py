@@ -21,6 +21,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   collision_probability_window   for encounters too slow for that model (neighbours in one shell, satellites deployed together):
                  the probability over a time window from the time-varying relative state and the full 6 x 6 covariances;
                  encounter_half_window is the window inside which the two models must agree;
+  collision_probability_mc   the same rows by sampled flights through the nonlinear dynamics: initial states, masses and thrust
+                 execution errors drawn, flown and counted -- what the linearised figures above are held against;
   catalogue_covariance    catalogue_trajectories followed by covariance;
   avoidance      for every listed pair the derivative of the encounter-plane miss with respect to every thrust node of the plan, and
                  the least-effort thrust change that opens the miss to a requested distance.
@@ -781,6 +783,141 @@ def _collision_window_call(pairs, half, *, device, slot, out, rows, cols, mu, pa
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
     _ffi.call("mpcx_collision_probability_window", _context(device, slot), len(pairs), _ffi.dptr(pairs), *_side_args(rows, 2), *_side_args(cols, 2),
               mu, _ffi.dptr(half), panels, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+
+
+# ---- the same list by sampled flights through the truth model (include/mpcx.h: mpcx_collision_probability_mc; csrc/collision_mc.hip)
+DEFAULT_PROP_MAX_STEP = 1e-3                                             # the flights' step limit (avoidance_window_refine's)
+
+
+class MonteCarloCollisionResult:
+    """For the n rows of `pairs`, row for row, from N sampled worlds: p_hit (n,) the fraction of surviving samples in which the two
+    flown objects came within the summed radii during the window, se_hit (n,) its binomial standard error; start, entries (n,) the
+    sampled counterparts of the window rule's START and ENTRIES (the mean of inside_start, the mean number of entries), se_bound (n,)
+    the standard error of the mean of inside_start + entries; excess (n,) = start + entries - p_hit, what the window rule's figure
+    lies above the probability because paths re-enter; window (n, 2); n_ok (n,) the samples that survived their flights; counts (n, 6)
+    int64 = (flown, failed, sum inside_start, sum entries, sum (inside_start + entries)^2, sum hit); status (n,) int32 MPCX_ST_* (a
+    row whose status is not 0 is NaN in all but counts, which are 0).  With return_samples: samples (n, N, 5) = (dmin in m, t_min in
+    s, inside_start, entries, flight status) per sample; with return_trajectories: Y_samples (n, NS, N, 7, K) and U_samples
+    (n, NS, N, 3, K), the row side's flown trajectories and executed thrust tables (NS = 2: slots i, j; 1 with a catalogue)."""
+
+    def __init__(self, pairs, out, counts, status, samples=None, Y_samples=None, U_samples=None):
+        self.pairs, self.counts, self.status = pairs, counts, status
+        self.p_hit, self.se_hit, self.start, self.entries = (out[:, c] for c in (_ffi.MC_P_HIT, _ffi.MC_SE_HIT, _ffi.MC_START, _ffi.MC_ENTRIES))
+        self.se_bound, self.excess, self.n_ok = out[:, _ffi.MC_SE_BOUND], out[:, _ffi.MC_EXCESS], out[:, _ffi.MC_N_OK]
+        self.window = out[:, _ffi.MC_TA:_ffi.MC_TB + 1]
+        self.samples, self.Y_samples, self.U_samples = samples, Y_samples, U_samples
+
+    def __repr__(self):
+        return f"MonteCarloCollisionResult(pairs={len(self.pairs)}, samples={int(self.counts[:, _ffi.MCC_FLOWN].max(initial=0))})"
+
+    def cumulative(self, events):
+        """Per list row of `events` (EncounterEvents whose .events are this result's rows): the fraction of worlds with a hit in ANY of
+        the row's events -> (p (n_rows,), se (n_rows,)).  Sample s is the same world in every row (the draws of an object do not
+        depend on the row), so the per-sample records are joint samples; a world in which any of the row's events has a failed
+        flight is left out.  cumulative_probability joins the same events as if they were independent.  A row without events is 0;
+        a row with a failed event, or without a surviving world, is NaN.  Needs return_samples=True."""
+        if self.samples is None:
+            raise ValueError("cumulative: the per-sample records are needed (return_samples=True)")
+        if len(events.row) != len(self.pairs):
+            raise ValueError(f"cumulative: expected events with {len(self.pairs)} stored events, one per row of this result, got {len(events.row)}")
+        rows = len(events.count)
+        N = self.samples.shape[1]
+        hit = (self.samples[:, :, _ffi.MS_INSIDE_START] + self.samples[:, :, _ffi.MS_ENTRIES]) >= 1.0
+        good = self.samples[:, :, _ffi.MS_STATUS] == 0.0
+        any_hit, all_good, failed = np.zeros((rows, N), dtype=bool), np.ones((rows, N), dtype=bool), np.zeros(rows, dtype=bool)
+        for e, r in enumerate(np.asarray(events.row)):
+            any_hit[r] |= hit[e]
+            all_good[r] &= good[e]
+            failed[r] |= self.status[e] != 0
+        ok = all_good.sum(axis=1).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = (any_hit & all_good).sum(axis=1) / ok
+            se = np.sqrt(p * (1.0 - p) / ok)
+        p[failed], se[failed] = np.nan, np.nan
+        none = np.asarray(events.count) == 0
+        p[none], se[none] = 0.0, 0.0
+        return p, se
+
+
+def _check_mc_cat(cat):
+    """cat = (cat_Y, cat_units, cat_span, cat_consts, cat_P0, cat_radius[, cat_ns]) of collision_probability_mc -> (Y, units, span, ns,
+    consts, P0, radius); None stays None"""
+    if cat is None:
+        return None
+    if len(cat) not in (6, 7):
+        raise ValueError(f"cat: expected (cat_Y, cat_units, cat_span, cat_consts, cat_P0, cat_radius[, cat_ns]), got {len(cat)} items")
+    Y, units, span, ns = _check_trajectories(cat[0], cat[1], cat[2], cat[6] if len(cat) == 7 else None, "cat_")
+    D, _, K = Y.shape
+    if K < 2:
+        raise ValueError(f"cat_Y: need at least 2 nodes, got {Y.shape}")
+    consts = _ffi.as_f64(cat[3])
+    if consts.shape != (D, _ffi.NCONST):
+        raise ValueError(f"cat_consts: expected ({D}, {_ffi.NCONST}) normalised constants per object, got {consts.shape}")
+    return Y, units, span, ns, consts, _check_p0(cat[4], D, "cat_P0"), _per_row(cat[5], D, "cat_radius", "hard-body radii in m")
+
+
+def _check_samples(samples, seed, scan, max_flights):
+    for name, v, low in (("samples", samples, 1), ("scan", scan, 1), ("max_flights", max_flights, 0)):
+        if np.ndim(v) != 0 or int(v) != v or not low <= v < 2 ** 31:
+            raise ValueError(f"{name}: need an integer >= {low}, got {v}")
+    if np.ndim(seed) != 0 or int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed: need an integer in 0 .. 2^64 - 1, got {seed}")
+    return int(samples), int(seed), int(scan), int(max_flights)
+
+
+def collision_probability_mc(pairs, radius, Y, U, units, span, consts, P0, half_window, samples, seed=0, scan=64, execution=None,
+                             mass_var0=None, ns=None, cat=None, include_drag=False, include_J2=False, atmosphere=None,
+                             prop_max_step=DEFAULT_PROP_MAX_STEP, max_flights=0, return_samples=False, return_trajectories=False, device=0,
+                             devices=None):
+    """The collision probability of every listed row over [t - half_window, t + half_window] by `samples` sampled flights through the
+    nonlinear dynamics -> MonteCarloCollisionResult.  Nothing is linearised: in every sampled world each object starts from its first
+    node plus a draw from P0 ((6, 6) or (S, 6, 6); m, m/s; positive semi-definite), its mass plus a draw of variance mass_var0, flies
+    the plan's thrust U (S, 3, n; None: zero thrust) with the execution errors execution ((5,) or (S, 5), gates_execution; None:
+    perfect execution) drawn at every node, under the model include_drag / include_J2 / atmosphere with the step limit prop_max_step;
+    the window is scanned in `scan` intervals for the two flown objects coming within the summed radii (include/mpcx.h:
+    mpcx_collision_probability_mc).  pairs, radius, Y, units, span, consts [, ns] and half_window as collision_probability_window and
+    covariance take them.  cat = (cat_Y, cat_units, cat_span, cat_consts, cat_P0, cat_radius[, cat_ns]): j indexes this catalogue,
+    whose objects fly without thrust.  The figure corresponds to covariance / covariance_thrust with q = 0 followed by
+    collision_probability_window -- of which start + entries is the counterpart and p_hit what it bounds from above.
+    The draws are Philox on (seed, sample, object): the same seed gives the same bits whatever the list, the devices or max_flights
+    (0: the library's default; otherwise a bound on the trajectories in flight at once, hence on the workspace); a satellite in
+    several rows flies the same trajectory in all of them.  An empty list returns empty arrays without a library call.
+    devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices, the bits of one device."""
+    pairs = _as_pairs(pairs)
+    Y, U, units, span, consts, ns, _ = _check_plan(Y, U, units, span, consts, ns, thrust_optional=True)
+    S, _, K = Y.shape
+    cols = _check_mc_cat(cat)
+    n, NS = pairs.shape[0], 1 if cols is not None else 2
+    half, _ = _check_window(half_window, 1, n)
+    N, seed, scan, max_flights = _check_samples(samples, seed, scan, max_flights)
+    model = _model(include_drag, include_J2, atmosphere, prop_max_step)
+    how = dict(rows=(Y, U, units, span, consts, ns, _check_p0(P0, S), None if execution is None else _check_execution(execution, S),
+                     None if mass_var0 is None else _per_row(mass_var0, S, "mass_var0", "values"), _per_row(radius, S, "radius", "hard-body radii in m")),
+               cols=cols, scan=scan, samples=N, seed=seed, max_flights=max_flights, flags=model["flags"], prop_max_step=model["max_step"],
+               atmosphere=model["atmosphere"])
+    out = dict(out=np.empty((n, _ffi.NMC)), counts=np.zeros((n, _ffi.NMCC), dtype=np.int64), status=np.zeros(n, dtype=np.int32),
+               samples=np.empty((n, N, _ffi.NMS)) if return_samples else None,
+               Y_samples=np.empty((n, NS, N, 7, K)) if return_trajectories else None,
+               U_samples=np.empty((n, NS, N, 3, K)) if return_trajectories else None)
+    if n:
+        dispatch(_collision_mc_call, [pairs, half], out, device, devices, **how)
+    return MonteCarloCollisionResult(pairs, out["out"], out["counts"], out["status"], out["samples"], out["Y_samples"], out["U_samples"])
+
+
+def _collision_mc_call(pairs, half, *, device, slot, out, rows, cols, scan, samples, seed, max_flights, flags, prop_max_step, atmosphere):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    Y, U, units, span, consts, ns, P0, execution, mass_var0, radius = rows
+    pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
+    if cols is None:
+        cat = (0, 0) + (None,) * 7
+    else:
+        cY, cunits, cspan, cns, cconsts, cP0, cradius = cols
+        cat = (cY.shape[0], cY.shape[2], _ffi.iptr_opt(cns), *[_ffi.dptr(a) for a in (cY, cunits, cspan, cconsts, cP0, cradius)])
+    _ffi.call("mpcx_collision_probability_mc", _context(device, slot, flags, atmosphere), len(pairs), _ffi.dptr(pairs), Y.shape[0], Y.shape[2],
+              _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr_opt(U), _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, prop_max_step,
+              _ffi.dptr(P0), _ffi.dptr_opt(execution), _ffi.dptr_opt(mass_var0), _ffi.dptr(radius), *cat, _ffi.dptr(half), scan, samples, seed,
+              max_flights, _ffi.lptr(out["counts"]), _ffi.dptr(out["out"]), _ffi.iptr(out["status"]),
+              _ffi.dptr_opt(out.get("samples")), _ffi.dptr_opt(out.get("Y_samples")), _ffi.dptr_opt(out.get("U_samples")))
 
 
 def catalogue_covariance(position_m, velocity_m_s, P0, T0, T1, n, q=None, include_J2=True, max_step=DEFAULT_MAX_STEP, device=0,

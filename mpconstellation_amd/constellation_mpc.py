@@ -427,6 +427,25 @@ class ConstellationMPC:
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
                 cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
 
+    def collision_probability_mc(self, threshold_m, P0, radius_m, half_window, samples, seed=0, execution=None, mass_var0=None, scan=64,
+                                 panels=4, model="plan", samples_per_node=4, max_pairs=None, prop_max_step=1e-3, max_flights=0,
+                                 return_samples=False, return_trajectories=False):
+        """The window probability of the last plan's close approaches and its Monte Carlo counterpart side by side ->
+        (ConjunctionResult, WindowCollisionResult, MonteCarloCollisionResult).  The plan is screened at threshold_m inside the
+        constellation; the window figure is conjunction.collision_probability_window on plan_covariance(P0, execution=execution,
+        mass_var0=mass_var0) -- no acceleration noise: the samples have none --; the sampled figure is
+        conjunction.collision_probability_mc on the same rows, plan, P0, execution errors and radii: `samples` worlds drawn with
+        `seed` and flown under model = 'plan' (plan_drag, plan_J2, what the covariance was linearised under) or 'truth' (the model the
+        segments are flown with).  The plan only."""
+        from . import conjunction as cj
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, None, samples_per_node, max_pairs, None, execution, mass_var0)
+        plan.pop("cat")
+        return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
+                cj.collision_probability_mc(screened, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P0, half_window, samples,
+                                            seed=seed, scan=scan, execution=execution, mass_var0=mass_var0, prop_max_step=prop_max_step,
+                                            max_flights=max_flights, return_samples=return_samples, return_trajectories=return_trajectories,
+                                            **self._conjunction_model(model), **plan))
+
     def avoidance_window(self, threshold_m, P0, radius_m, half_window, target_p, panels=4, q=None, samples_per_node=4, max_pairs=None,
                          catalogue=None, who="i", tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL):
         """Avoidance for the last plan's slow close approaches -> (ConjunctionResult, WindowCollisionResult, AvoidanceWindowResult).
