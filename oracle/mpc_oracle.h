@@ -87,13 +87,18 @@ int oracle_discretize_mode_atm(int K, int Ku, const double *x, const double *u, 
                                double *node_y, int node_cap);
 
 /* simulator.py:164-189: solve_ivp(RK45, max_step, t_eval=linspace(0,1,n_eval)) with dense output.
- * y_out (7, n_eval) row-major as sol.y.  Returns 0, 1 = mass<=0, 2 = step too small. */
+ * y_out (7, n_eval) row-major as sol.y.  Returns 0, 1 = mass<=0, 2 = step too small, 3 = thrust table index out of range,
+ * 4 = y0 not finite (scipy raises ValueError before the first step; y_out is left as it was). */
 int oracle_propagate(const double y0[7], double tf, const double *cst, int flags,
                      const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
                      int32_t *nsteps);
 int oracle_propagate_atm(const double y0[7], double tf, const double *cst, int flags, const double *atm,
                          const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
                          int32_t *nsteps);
+/* the same, and nfev (optional): scipy's sol.nfev = 2 + 6 (accepted + rejected attempts) */
+int oracle_propagate_atm_counts(const double y0[7], double tf, const double *cst, int flags, const double *atm,
+                                const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
+                                int32_t *nsteps, int32_t *nfev);
 /* linearize_discretize.py:393-411 */
 void oracle_extract_uk(int K, const double *x, const double *t, const oracle_ctrl *ctrl, double *u);
 

@@ -40,8 +40,25 @@ int oracle_propagate_atm(const double y0[7], double tf, const double *cst, int f
                          const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
                          int32_t *nsteps)
 {
+    return oracle_propagate_atm_counts(y0, tf, cst, flags, atm, ctrl, n_eval, max_step, y_out, nsteps, 0);
+}
+
+/* nfev: the right-hand side evaluations as scipy's sol.nfev counts them -- two to start (rk.py:97, select_initial_step) and six
+ * per attempted step, so (nfev - 2) / 6 - nsteps attempts were rejected */
+int oracle_propagate_atm_counts(const double y0[7], double tf, const double *cst, int flags, const double *atm,
+                                const oracle_ctrl *ctrl, int n_eval, double max_step, double *y_out,
+                                int32_t *nsteps, int32_t *nfev)
+{
     prop_ctx ctx = {ctrl, tf, cst, flags, atm, 0};
     rk45 s;
+    /* scipy refuses such a start (base.py check_arguments: "All components of the initial state `y0` must be finite"); the
+     * stepper itself would shrink a NaN step for ever */
+    for (int i = 0; i < 7; ++i)
+        if (!isfinite(y0[i])) {
+            if (nsteps) *nsteps = 0;
+            if (nfev) *nfev = 0;
+            return 4;
+        }
     rk45_init(&s, 7, prop_rhs, &ctx, 0.0, y0, 1.0, max_step, 1e-3, 1e-6);
     int ei = 0, status = 0;
     double step = (n_eval > 1) ? 1.0 / (double)(n_eval - 1) : 0.0;
@@ -59,6 +76,7 @@ int oracle_propagate_atm(const double y0[7], double tf, const double *cst, int f
         }
     }
     if (nsteps) *nsteps = s.nsteps;
+    if (nfev) *nfev = s.nfev;
     if (ctx.err && !status) status = ctx.err;
     if (s.fun_err && !status) status = 1;
     return status;

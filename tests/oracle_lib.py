@@ -80,6 +80,8 @@ def lib():
                                                     C.c_int]
         _lib.oracle_propagate_atm.argtypes = [_dp, C.c_double, _dp, C.c_int, _dp, C.POINTER(OracleCtrl),
                                               C.c_int, C.c_double, _dp, _ip]
+        _lib.oracle_propagate_atm_counts.restype = C.c_int
+        _lib.oracle_propagate_atm_counts.argtypes = _lib.oracle_propagate_atm.argtypes + [_ip]
     return _lib
 
 
@@ -184,6 +186,19 @@ def propagate(y0, tf, cst, ctrl, n_eval, flags=0, max_step=1e-3, atmosphere=None
     rc = lib().oracle_propagate_atm(_p(y0), float(tf), _p(cst), flags, atm, C.byref(ctrl), n_eval, max_step,
                                 _p(out), ns.ctypes.data_as(_ip))
     return out, rc, int(ns[0])
+
+
+def propagate_counts(y0, tf, cst, ctrl, n_eval, flags=0, max_step=1e-3, atmosphere=None):
+    """propagate() with the attempts: -> (y, status, accepted steps, rejected attempts, nfev as scipy's sol.nfev counts it:
+    two evaluations to start, six per attempt)"""
+    y0, cst = _c(y0), _c(cst)
+    flags, _keep, atm = _atm(atmosphere, flags)
+    out = np.zeros((7, n_eval))
+    ns = np.zeros(2, dtype=np.int32)
+    rc = lib().oracle_propagate_atm_counts(_p(y0), float(tf), _p(cst), flags, atm, C.byref(ctrl), n_eval, max_step,
+                                           _p(out), ns[0:1].ctypes.data_as(_ip), ns[1:2].ctypes.data_as(_ip))
+    accepted, nfev = int(ns[0]), int(ns[1])
+    return out, rc, accepted, (nfev - 2) // 6 - accepted, nfev
 
 
 def extract_uk(x, t, ctrl):
