@@ -79,6 +79,17 @@ static int get_matrices(int K, int Ku, const double *x, const double *u, double 
     double y0[56];
     memset(y0, 0, sizeof y0);
     for (int i = 0; i < 7; ++i) { y0[i * 7 + i] = 1.0; y0[49 + i] = x[i * K + k]; }   /* :31-34 */
+    /* scipy refuses a start that is not finite (base.py check_arguments) and the reference's discretize dies of its ValueError;
+     * the stepper itself would shrink a NaN step for ever: status 5, the interval's outputs NaN, no nodes */
+    for (int i = 0; i < 7; ++i)
+        if (!isfinite(y0[49 + i])) {
+            for (int e = 0; e < 49; ++e) A_k[e] = NAN;
+            for (int e = 0; e < 21; ++e) B_kp[e] = B_kn[e] = NAN;
+            for (int e = 0; e < 7; ++e) Sigma_k[e] = xi_k[e] = NAN;
+            if (n_nodes) *n_nodes = 0;
+            if (n_fev) *n_fev = 0;
+            return 5;
+        }
     dphi_ctx ctx = {u, Ku, tf, cst, flags, atm, 0};
     rk45 s;
     /* :37-41; method = options['ivp_solver'] (:40): flag bit 8 = 'RK23', otherwise the default 'RK45' (:105) */

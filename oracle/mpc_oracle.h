@@ -71,7 +71,10 @@ int oracle_u_foh(double tau, const double *u, int Ku, double out[3]);
 
 /* D5+D7  linearize_discretize.py:8-82, 334-390.  x (7,K) row-major, u (3,Ku) row-major.
  * Outputs in the reference's shapes: A (K-1,7,7) Bp (K-1,7,3) Bn (K-1,7,3) Sigma (7,K-1) xi (7,K-1).
- * node_counts/nfev (K-1) optional.  node_t/node_y optional dumps (capacity node_cap rows). */
+ * node_counts/nfev (K-1) optional.  node_t/node_y optional dumps (capacity node_cap rows).
+ * Returns the first interval's status that is not 0: 1 = mass <= 0, 2 = step too small, 3 = thrust table index out of range,
+ * 4 = Phi not invertible, 5 = the interval's start node x[:, k] not finite (scipy raises ValueError before the first step; that
+ * interval's outputs are NaN and it has no nodes). */
 int oracle_discretize(int K, int Ku, const double *x, const double *u, double tf, const double *cst,
                       int flags, double max_step, double *A, double *Bp, double *Bn, double *Sigma,
                       double *xi, int32_t *node_counts, int32_t *node_nfev, double *node_t,

@@ -142,16 +142,24 @@ def u_foh(tau, u):
     return out, rc
 
 
-def discretize(x, u, tf, cst, flags=0, max_step=1e-2, dump_nodes=False, uniform_steps=0, atmosphere=None):
+# oracle_discretize*'s status -> the MPCX_ST_* code the device reports for the same input (include/mpcx.h).  The numbers agree up to
+# 4; 5 is a node of x that is not finite, which scipy refuses before the first step: the device has no such check, its error
+# norm is NaN on every attempt and the step shrinks by MIN_FACTOR to the floor -- MPCX_ST_STEP
+ST_START_NOT_FINITE = 5
+DEVICE_STATUS = {0: 0, 1: 1, 2: 2, 3: 3, 4: 4, ST_START_NOT_FINITE: 2}
+
+
+def discretize(x, u, tf, cst, flags=0, max_step=1e-2, dump_nodes=False, uniform_steps=0, atmosphere=None, node_rows=64):
     """uniform_steps = integrator_steps of Discretizer.use_uniform_steps (0: the default adaptive quadrature nodes);
-    atmosphere: with FLAG_DRAG, the density model in place of the fixed density"""
+    atmosphere: with FLAG_DRAG, the density model in place of the fixed density; node_rows: with dump_nodes, the rows the dump
+    has room for per interval (an interval of several orbits at max_step = 1 takes more than 64 steps)"""
     x, u, cst = _c(x), _c(u), _c(cst)
     flags, _keep, atm = _atm(atmosphere, flags)
     K, Ku = x.shape[1], u.shape[1]
     A = np.zeros((K - 1, 7, 7)); Bp = np.zeros((K - 1, 7, 3)); Bn = np.zeros((K - 1, 7, 3))
     Sig = np.zeros((7, K - 1)); xi = np.zeros((7, K - 1))
     cnt = np.zeros(K - 1, dtype=np.int32); nfev = np.zeros(K - 1, dtype=np.int32)
-    cap = max(64, int(uniform_steps) + 1) * (K - 1) if dump_nodes else 0
+    cap = max(int(node_rows), int(uniform_steps) + 1) * (K - 1) if dump_nodes else 0
     nt = np.zeros(max(cap, 1)); ny = np.zeros((max(cap, 1), 56))
     rc = lib().oracle_discretize_mode_atm(K, Ku, _p(x), _p(u), float(tf), _p(cst), flags, atm, max_step, int(uniform_steps), _p(A),
                                  _p(Bp), _p(Bn), _p(Sig), _p(xi), cnt.ctypes.data_as(_ip),
