@@ -34,6 +34,26 @@
 // combine_channels, each of which then saved and restored 112 registers to scratch per call: solve_kernel 5.34 -> 5.64 ms.
 #define MPCX_NO_TAIL __attribute__((disable_tail_calls))
 
+// Wide LDS reads and writes: two adjacent doubles of a 16-byte aligned LDS array as ONE access (ds_read_b128 / ds_write_b128).
+// The vector type carries the alignment, so the instruction does not depend on the vectoriser; the arrays read this way are
+// declared LDS_A16 and keep their rows on even element offsets (solve_riccati.hpp: Pn, WlLi).
+#define LDS_A16 alignas(16)
+namespace MPCX_NS {
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f64x2 lds_ld2(const double *p) { return *(const f64x2 *)__builtin_assume_aligned(p, 16); }
+__device__ __forceinline__ void lds_st2(double *p, double a, double b) { f64x2 v; v.x = a; v.y = b; *(f64x2 *)__builtin_assume_aligned(p, 16) = v; }
+// elements 0..6 of a 16-byte aligned row: three pairs and a single (the eighth double, where a row has one, is never touched)
+__device__ __forceinline__ void lds_ld7(const double *p, double (&x)[7])
+{
+    const f64x2 a = lds_ld2(p), b = lds_ld2(p + 2), c = lds_ld2(p + 4);
+    x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y; x[4] = c.x; x[5] = c.y; x[6] = p[6];
+}
+__device__ __forceinline__ void lds_st7(double *p, const double (&x)[7])
+{
+    lds_st2(p, x[0], x[1]); lds_st2(p + 2, x[2], x[3]); lds_st2(p + 4, x[4], x[5]); p[6] = x[6];
+}
+}  // namespace MPCX_NS
+
 #include "solve_phases.hpp"
 #include "solve_riccati.hpp"
 #ifdef MPCX_TP

@@ -57,6 +57,11 @@ constexpr int OPS_IN = 91 + 49 + 9 + 7 + SX_N;   // A 49 | Bn 21 | Bpm 21 | Wx 4
 #ifndef MPCX_PRIO_RIC
 #define MPCX_PRIO_RIC 3
 #endif
+// P_{k+1} and L^-1 [Pn | I] lie so that every vector the factorisation reads out of them is contiguous and starts on a 16-byte
+// boundary (lds_ld7: four reads for seven doubles): Pn row-major with row stride PS = 8, element (i, j) at i * PS + j; WlLi
+// transposed, column c of [X1 | X2] (c < 7: X1, c >= 7: X2) at c * PS + l, l = 0..6.  The eighth double of a row is padding:
+// never read, written only where Pn is zeroed as a whole.
+constexpr int PS = 8, PN_N = 7 * PS, WL_N = 14 * PS;
 struct Scratch {   // LDS working set of the recursion (and, between recursions, the staging area of newton_blocks)
     union {                        // the factorisation and the stand-alone sweeps never run at the same time
 #ifdef MPCX_TWO_WAVE
@@ -67,20 +72,23 @@ struct Scratch {   // LDS working set of the recursion (and, between recursions,
         double flat[2][FLAT_N];    // sweep operands of one node, double-buffered (fac record + A, Bpm, D)
     };
 #ifdef MPCX_TWO_WAVE
-    double Pn2[2][49];             // P_{k+1} is read by the second wave while the first writes P_k
-    double WlLi1[98];              // the second wave's own L^-1 [Pn | I]
+    LDS_A16 double Pn2[2][PN_N];   // P_{k+1} is read by the second wave while the first writes P_k
+    LDS_A16 double WlLi1[WL_N];    // the second wave's own L^-1 [Pn | I]
     int cmd, cmd_arg, good_flag;   // command of the first wave to the second (solve2w.hip), breakdown flag of a node
 #endif
 #ifdef MPCX_TP
     double flatB[2][FLAT_N];       // the pair's second wave sweeps its own channels at the same time: its own staging buffers
 #endif
-    double Pn[49], WlLi[98], Qyy[49];
+    LDS_A16 double Pn[PN_N];
+    LDS_A16 double WlLi[WL_N];
+    LDS_A16 double sink[64];       // target of the lanes that have nothing to write in a branch-free phase (16-byte aligned: a
+                                   // column of WlLi that no lane owns is written to its first eight doubles with wide stores)
+    double Qyy[49];
     double T[7 * FS];              // Pt F = [Pt A | Pt Bh]
-    double sink[64];               // target of the lanes that have nothing to write in a branch-free phase
     double Quy[21];
     double Quu[9];
     double zero;                   // constant 0 (addend of the tasks that have none)
-    double stage_pad[32 * (NB_N + RHS_LD) - 1129 > 0 ? 32 * (NB_N + RHS_LD) - 1129 : 1];   // newton_blocks stages 32 Newton + 32 rhs records here
+    double stage_pad[32 * (NB_N + RHS_LD) - 1150 > 0 ? 32 * (NB_N + RHS_LD) - 1150 : 1];   // newton_blocks stages 32 Newton + 32 rhs records here
 };
 
 static_assert(sizeof(Scratch) >= 32 * (NB_N + RHS_LD) * sizeof(double) && sizeof(Scratch) >= TR_N * CMB_LD * sizeof(double) && sizeof(Scratch) >= 64 * RHS_LD * sizeof(double), "newton_blocks stages 32 Newton and right-hand-side records in the recursion's scratch");
@@ -95,6 +103,20 @@ __device__ __forceinline__ double dotN(const double *a, int sa, const double *b,
 #pragma unroll
     for (int l = 0; l < N; ++l) acc += x[l] * y[l];
     return acc;
+}
+
+// The lower triangle of M = D + Pn, row by row (m[i (i + 1) / 2 + j], j <= i): each row of Pn in pairs, 16 reads for 28 doubles
+__device__ __forceinline__ void load_m_lower(const double *Pn, const double *D, double (&m)[28])
+{
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        double row[7];
+#pragma unroll
+        for (int j = 0; j + 1 <= i; j += 2) { const f64x2 v = lds_ld2(Pn + i * PS + j); row[j] = v.x; row[j + 1] = v.y; }
+        if ((i & 1) == 0) row[i] = Pn[i * PS + i];
+#pragma unroll
+        for (int j = 0; j <= i; ++j) m[i * (i + 1) / 2 + j] = row[j] + (i == j ? D[i] : 0.0);
+    }
 }
 
 #ifdef MPCX_PHASE_TIMING
@@ -161,7 +183,7 @@ __device__ __forceinline__ ChanIn chan_mask(const ChanRaw &cr, int c, int r, boo
 // P_k += om v v^T  -- the weight enters only through 1/ex, nothing of size ex is ever formed (condensed into the
 // blocks, 1e14 r r^T would leave no digit of the trust-region curvature 2 w_tr in the other directions).  Position term
 // first, thrust ball second (on the once-updated quantities).  Same arithmetic as the oracle's riccati_factor.
-// Pdst: the buffer of P_k the update goes to in the two-wave factorisation (its double-buffered copy; the one-wave one updates w.Pn).  fac: the node's factor
+// Pdst: the buffer of P_k (row stride PS) the update goes to in the two-wave factorisation (its double-buffered copy; the one-wave one updates w.Pn).  fac: the node's factor
 // record -- the one-wave factorisation stores the updated gain and Q_uu^-1 there itself; nullptr in the two-wave factorisation,
 // where they go to the node's LDS copies (o.Kg, o.Qi) and the second wave stores them.  One body for both (round 4 had it twice).
 template <bool TO_RECORD>
@@ -209,7 +231,7 @@ __device__ __noinline__ void stiff_stage_update(StageOps &o, Scratch &w, double 
         sm_v(qi, lo, v1l, v2l); sm_v(qj, hi, v1h, v2h);
         double *P = Pdst;
         if constexpr (TO_RECORD) P = w.Pn;          // (the one-wave factorisation's own buffer: an LDS address the compiler knows)
-        P[lane] += om1 * (v1l * v1h) + om2 * (v2l * v2h);
+        P[mi * PS + mj] += om1 * (v1l * v1h) + om2 * (v2l * v2h);
     }
     if (lane < 21) {
         const int r = lane / 7, c = lane - 7 * r;
@@ -314,7 +336,7 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
         stash(w.ops[(RF_HI - 1) % 3], RF_HI - 1);
         if (RF_LAST && lane < 49) w.ops[(RF_HI - 1) % 3].G2[(lane / 7) * FS + lane % 7] = sd.WxK[lane];
     } else {
-        for (int e = lane; e < 49; e += 64) w.Pn2[RF_HI & 1][e] = 0.0;       // P_K = 0 (read as "P of node k+1" by node K-1)
+        if (lane < PN_N) w.Pn2[RF_HI & 1][lane] = 0.0;                       // P_K = 0 (read as "P of node k+1" by node K-1)
         if (lane == 0) { w.zero = 0.0; w.good_flag = 1; }
     }
     WG_BARRIER();
@@ -417,10 +439,7 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
             if (dyn) {
                 // P2: LDL^T of M = D + Pn in registers; P3 (this wave's half): X1 = Lt^-1 Pn, lane c < 7 owns column c
                 double m[28];
-#pragma unroll
-                for (int i = 0, n = 0; i < 7; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j, ++n) m[n] = Pn[i * 7 + j] + (i == j ? o.D[i] : 0.0);
+                load_m_lower(Pn, o.D, m);
 #pragma unroll
                 for (int pp = 0; pp < 7; ++pp) {
                     const double d = m[pp * (pp + 1) / 2 + pp];
@@ -439,17 +458,12 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                 }
                 double x[7];
 #pragma unroll
-                for (int pp = 0; pp < 7; ++pp) x[pp] = Pn[pp * 7 + xc];
+                for (int pp = 0; pp < 7; ++pp) x[pp] = Pn[pp * PS + xc];
 #pragma unroll
                 for (int pp = 1; pp < 7; ++pp)
 #pragma unroll
                     for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
-                {
-                    double *dst = (lane < 7) ? &w.WlLi[lane] : &w.sink[lane];
-                    const int st = (lane < 7) ? 14 : 0;
-#pragma unroll
-                    for (int pp = 0; pp < 7; ++pp) dst[pp * st] = x[pp];
-                }
+                lds_st7((lane < 7) ? &w.WlLi[lane * PS] : &w.sink[0], x);
             }
             wsync();
             {
@@ -457,10 +471,11 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                 const bool on = lane < 49;
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
                 const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
-                double a1 = 0.0;
+                double a1 = 0.0, x1lo[7], x1hi[7];
+                lds_ld7(&w.WlLi[lo * PS], x1lo); lds_ld7(&w.WlLi[hi * PS], x1hi);
 #pragma unroll
-                for (int l = 0; l < 7; ++l) a1 += w.WlLi[l * 14 + lo] * (rd[l] * w.WlLi[l * 14 + hi]);
-                const double pt = dyn ? Pn[lo * 7 + hi] - a1 : 0.0;
+                for (int l = 0; l < 7; ++l) a1 += x1lo[l] * (rd[l] * x1hi[l]);
+                const double pt = dyn ? Pn[lo * PS + hi] - a1 : 0.0;
                 *(on ? &o.Pt[lane] : &w.sink[lane]) = pt;
                 if (keep_pt) ustore(s.ws, on ? s.o_fac + k * FAC_N + F_PT + lane : sink_e, pt);
                 wsync();
@@ -500,7 +515,7 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                     const double kj = Qi[l * 3] * qj[0] + Qi[l * 3 + 1] * qj[1] + Qi[l * 3 + 2] * qj[2];
                     a1 -= qi[l] * kj;
                 }
-                w.Pn2[k & 1][lane] = a1;
+                w.Pn2[k & 1][mi * PS + mj] = a1;
             }
             {
                 const bool on21 = lane < 21;
@@ -532,10 +547,7 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
 #endif
             if (dyn) {
                 double m[28], rd[7];
-#pragma unroll
-                for (int i = 0, n = 0; i < 7; ++i)
-#pragma unroll
-                    for (int j = 0; j <= i; ++j, ++n) m[n] = Pn[i * 7 + j] + (i == j ? o.D[i] : 0.0);
+                load_m_lower(Pn, o.D, m);
 #pragma unroll
                 for (int pp = 0; pp < 7; ++pp) {
                     const double d = m[pp * (pp + 1) / 2 + pp];
@@ -554,28 +566,23 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                 double x[7];
 #pragma unroll
                 for (int pp = 0; pp < 7; ++pp) {
-                    const double pv = Pn[pp * 7 + xc];
+                    const double pv = Pn[pp * PS + xc];
                     x[pp] = (lane < 7) ? pv : (lane - 7 == pp ? 1.0 : 0.0);
                 }
 #pragma unroll
                 for (int pp = 1; pp < 7; ++pp)
 #pragma unroll
                     for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
-                {
-                    double *dst = (lane < 14) ? &w.WlLi1[lane] : &w.sink[lane];
-                    const int st = (lane < 14) ? 14 : 0;
-#pragma unroll
-                    for (int pp = 0; pp < 7; ++pp) dst[pp * st] = x[pp];
-                }
+                lds_st7((lane < 14) ? &w.WlLi1[lane * PS] : &w.sink[8], x);
                 wsync();
                 // G = X1^T R X2, Minv = X2^T R X2 into the node's operand buffer and the factor record
                 const bool on = lane < 49;
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
-                double a2 = 0.0, a3 = 0.0;
+                double a2 = 0.0, a3 = 0.0, x1i[7], x2i[7], x2j[7];
+                lds_ld7(&w.WlLi1[ci * PS], x1i); lds_ld7(&w.WlLi1[(7 + ci) * PS], x2i); lds_ld7(&w.WlLi1[(7 + cj) * PS], x2j);
 #pragma unroll
                 for (int l = 0; l < 7; ++l) {
-                    const double x1i = w.WlLi1[l * 14 + ci], x2i = w.WlLi1[l * 14 + 7 + ci], x2j = w.WlLi1[l * 14 + 7 + cj];
-                    a2 += x1i * (rd[l] * x2j); a3 += x2i * (rd[l] * x2j);
+                    a2 += x1i[l] * (rd[l] * x2j[l]); a3 += x2i[l] * (rd[l] * x2j[l]);
                 }
                 *(on ? &o.G[lane] : &w.sink[lane]) = a2;
                 *(on ? &o.Minv[lane] : &w.sink[lane]) = a3;
@@ -608,7 +615,7 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
         if (RF_GOOD == 0) { good = false; break; }
     }
 #ifdef MPCX_TP
-    if (role == 0 && good && lane < 49) rg.Wout[lane] = w.Pn2[RF_LO & 1][lane];      // the segment's cost-to-go Hessian at its first node
+    if (role == 0 && good && lane < 49) rg.Wout[lane] = w.Pn2[RF_LO & 1][mi * PS + mj];     // the segment's cost-to-go Hessian at its first node
 #endif
     if (role == 1 && good) sweep_node(w.ops[RF_LO % 3], RF_LO);
     WG_BARRIER();
@@ -736,7 +743,7 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
     stash(BoolC<false>{}, w.ops[(K - 1) & 1], K - 1);
     // (the terminal node's Hessian -- soft part, capped rank-1 terms, AL term -- is a full matrix: from SatData)
     if (lane < 49) w.ops[(K - 1) & 1].G2[(lane / 7) * FS + lane % 7] = sd.WxK[lane];
-    for (int e = lane; e < 49; e += 64) w.Pn[e] = 0.0;
+    if (lane < PN_N) w.Pn[lane] = 0.0;
     if (lane == 0) w.zero = 0.0;
     WG_SYNC();
     const int mi = lane / 7, mj = lane - 7 * mi;
@@ -782,10 +789,7 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             // P2: LDL^T of M = D + Pn, redundantly in the registers of every lane (broadcast LDS reads, no exchange):
             // m holds the lower triangle, the strict part ends up as Lt.  Same arithmetic as the oracle's ldl_solve7.
             double m[28];
-#pragma unroll
-            for (int i = 0, n = 0; i < 7; ++i)
-#pragma unroll
-                for (int j = 0; j <= i; ++j, ++n) m[n] = w.Pn[i * 7 + j] + (i == j ? o.D[i] : 0.0);
+            load_m_lower(w.Pn, o.D, m);
             // fused backward sweep of node k+1 (its matrices are still in the other operand buffer), interleaved
             // with the pivots: one column of its first matrix-vector product per pivot
             const StageOps &on = w.ops[(k + 1) & 1];
@@ -811,19 +815,15 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             double x[7];
 #pragma unroll
             for (int pp = 0; pp < 7; ++pp) {
-                const double pv = w.Pn[pp * 7 + xc];
+                const double pv = w.Pn[pp * PS + xc];
                 x[pp] = (lane < 7) ? pv : (lane - 7 == pp ? 1.0 : 0.0);
             }
 #pragma unroll
             for (int pp = 1; pp < 7; ++pp)
 #pragma unroll
                 for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
-            {
-                double *dst = (lane < 14) ? &w.WlLi[lane] : &w.sink[lane];
-                const int st = (lane < 14) ? 14 : 0;
-#pragma unroll
-                for (int pp = 0; pp < 7; ++pp) dst[pp * st] = x[pp];
-            }
+            // (column lane of WlLi, contiguous: four stores; the lanes that own none write theirs to the head of the sink)
+            lds_st7((lane < 14) ? &w.WlLi[lane * PS] : &w.sink[0], x);
             sweep_finish(on, k + 1, sw_p, sw_qu);
             sweep_store(k + 1, sw_p, sw_qu);
         }
@@ -840,15 +840,15 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             if constexpr (dyn) {
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
                 const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
-                double a1 = 0.0;
+                double a1 = 0.0, x1i[7], x1lo[7], x1hi[7], x2i[7], x2j[7];
+                lds_ld7(&w.WlLi[ci * PS], x1i); lds_ld7(&w.WlLi[lo * PS], x1lo); lds_ld7(&w.WlLi[hi * PS], x1hi);
+                lds_ld7(&w.WlLi[(7 + ci) * PS], x2i); lds_ld7(&w.WlLi[(7 + cj) * PS], x2j);
 #pragma unroll
                 for (int l = 0; l < 7; ++l) {
-                    const double x1i = w.WlLi[l * 14 + ci], x1lo = w.WlLi[l * 14 + lo], x1hi = w.WlLi[l * 14 + hi];
-                    const double x2i = w.WlLi[l * 14 + 7 + ci], x2j = w.WlLi[l * 14 + 7 + cj];
-                    a1 += x1lo * (rd[l] * x1hi);
-                    a2 += x1i * (rd[l] * x2j); a3 += x2i * (rd[l] * x2j);
+                    a1 += x1lo[l] * (rd[l] * x1hi[l]);
+                    a2 += x1i[l] * (rd[l] * x2j[l]); a3 += x2i[l] * (rd[l] * x2j[l]);
                 }
-                pt = w.Pn[lo * 7 + hi] - a1;
+                pt = w.Pn[lo * PS + hi] - a1;
             }
             *(on ? &o.Pt[lane] : &w.sink[lane]) = pt;
             *(on ? &o.G[lane] : &w.sink[lane]) = a2;
@@ -903,7 +903,7 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
                 const double kj = Qi[l * 3] * qj[0] + Qi[l * 3 + 1] * qj[1] + Qi[l * 3 + 2] * qj[2];     // Kg(l, hi)
                 a1 -= qi[l] * kj;
             }
-            w.Pn[lane] = a1;
+            w.Pn[mi * PS + mj] = a1;
         }
         // (Qi is indexed with constants only and picked by selects: a register array indexed by a lane-dependent value
         //  is placed in scratch memory, and its store / load pair would sit behind an s_waitcnt vmcnt(0) in every node)
