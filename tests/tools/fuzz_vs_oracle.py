@@ -1,5 +1,6 @@
 """checking helper (GPU box): random satellites, horizons and option sets, device (mpc_step_batch through the C ABI) against the
 CPU oracle: status, iteration count, regularised iterations, |dX|, |dtf|.  The oracle is the checker here as in tests/.
+(Which constraints are ACTIVE at a solution is asserted, family by family and on every solve kernel, by tests/test_solve_active_gpu.py.)
 usage: python tests/tools/fuzz_vs_oracle.py [n_problems] [seed] [model] [atmosphere]      (lives under tests/: it uses oracle/ as the checker)
 model: letters of "dj" -- d: drag in the linearisation (S x 1e4 on every other problem), j: J2; "-": neither (the default).
 atmosphere (with d): "power", "exp" or "general" (tests/drag_cases.py); the density model on both sides instead of the fixed density."""
