@@ -784,24 +784,26 @@ struct ArCall {
 // [flight status, steps, trial status, flies, skip: S each][trial row status, re-screen status: n each][ephemeris status S, D]
 struct ArWorkspace {
     void *aj, *scr;
-    double *Ut, *Yp, *y0, *end_tau, *du_try, *sat_try, *row_try, *z, *trhs;
-    int32_t *pst, *nsteps, *sat_st_try, *flies, *skip, *row_st_try, *scr_st, *eph_st, *cat_st;
+    FlightSet f;                      // the constellation itself, not copies: Ks, tf and consts are the caller's (ar_enqueue), read only
+    double *du_try, *sat_try, *row_try, *z, *trhs;
+    int32_t *sat_st_try, *flies, *skip, *row_st_try, *scr_st, *eph_st, *cat_st;
     size_t bytes;
     ArWorkspace(void *base, int n, int S, int K, int D, int M)
     {
         Carver c(base);
         aj = c.take<char>(AjWorkspace(nullptr, n, S, K).bytes);
         scr = c.take<char>(mpcx_conjunction_pairs_workspace_bytes(S, D, M));       // (the tracked re-screen's is the same size)
-        Ut = c.take<double>((size_t)S * 3 * K);
-        Yp = c.take<double>((size_t)S * 7 * K);
-        y0 = c.take<double>((size_t)S * 7);
-        end_tau = c.take<double>((size_t)S);
+        f = FlightSet{};
+        f.Ut = c.take<double>((size_t)S * 3 * K);
+        f.Yp = c.take<double>((size_t)S * 7 * K);
+        f.y0 = c.take<double>((size_t)S * 7);
+        f.end_tau = c.take<double>((size_t)S);
         du_try = c.take<double>((size_t)S * 3 * K);
         sat_try = c.take<double>((size_t)S * MPCX_NAJ);
         row_try = c.take<double>((size_t)n * MPCX_NAR);
         z = c.take<double>((size_t)S * AJ_NZ);
         trhs = c.take<double>((size_t)S * 6);
-        for (int32_t **q : {&pst, &nsteps, &sat_st_try, &flies, &skip, &eph_st}) *q = c.take<int32_t>((size_t)S);
+        for (int32_t **q : {&f.pst, &f.nsteps, &sat_st_try, &flies, &skip, &eph_st}) *q = c.take<int32_t>((size_t)S);
         row_st_try = c.take<int32_t>((size_t)n);
         scr_st = c.take<int32_t>((size_t)n);
         cat_st = c.take<int32_t>((size_t)(D > 0 ? D : 1));
@@ -825,32 +827,31 @@ static int ar_enqueue(mpcx_ctx *ctx, const ArCall &c, void *workspace, hipStream
 {
     const AjCall &j = c.j;
     const int n = j.n, S = j.S, K = j.K, D = j.cat_Y ? j.D : 0;
-    const ArWorkspace ws(workspace, n, S, K, D, c.M);
+    ArWorkspace ws(workspace, n, S, K, D, c.M);
     const AjWorkspace aw(ws.aj, n, S, K);
+    ws.f.Ks = const_cast<int32_t *>(j.Ks); ws.f.tf = aw.tf; ws.f.consts = const_cast<double *>(j.consts);
     const unsigned gS = (unsigned)((S + 63) / 64), gn = (unsigned)((n + 255) / 256);
     const int most = S * AJ_NZ > n ? S * AJ_NZ : n;
     hipLaunchKernelGGL(ar_init_kernel, dim3((unsigned)((most + 63) / 64)), dim3(64), 0, st, S, K, n, j.Y, j.sat_out, j.sat_status, ws.flies, ws.skip,
-                       c.rounds_done, ws.y0, ws.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 1);
+                       c.rounds_done, ws.f.y0, ws.f.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 1);
     MPCX_HIP(ctx, hipGetLastError());
     // ---- pass 0: the joint call on what was given
     AjPass first;
     first.z_out = ws.z;
     if (c.rounds == 0) { first.rhs_rows = c.rhs_rows; first.rhs_term = c.rhs_term; }
     if (int rc = aj_enqueue(ctx, j, ws.aj, st, first)) return rc;
-    hipLaunchKernelGGL(ar_init_kernel, dim3(gS), dim3(64), 0, st, S, K, n, j.Y, j.sat_out, j.sat_status, ws.flies, ws.skip, c.rounds_done, ws.y0,
-                       ws.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 0);
+    hipLaunchKernelGGL(ar_init_kernel, dim3(gS), dim3(64), 0, st, S, K, n, j.Y, j.sat_out, j.sat_status, ws.flies, ws.skip, c.rounds_done, ws.f.y0,
+                       ws.f.end_tau, c.hist_term, ws.z, c.rhs_rows, c.rhs_term, 0);
     MPCX_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(ar_hist_kernel, dim3(gn), dim3(256), 0, st, n, j.row_out, j.pairs, c.hist_d0, c.hist_tca);
     MPCX_HIP(ctx, hipGetLastError());
     for (int t = 1; t <= c.rounds + 1; ++t) {
         const bool solve = t <= c.rounds;
         const size_t total = (size_t)S * 3 * K;
-        hipLaunchKernelGGL(ar_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, K, j.U, j.du, ws.flies, ws.Ut);
+        hipLaunchKernelGGL(ar_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, K, j.U, j.du, ws.flies, ws.f.Ut);
         MPCX_HIP(ctx, hipGetLastError());
-        if (int rc = mpcx_propagate_batch_ragged_dev(ctx, S, K, j.Ks, ws.y0, aw.tf, j.consts, j.flags, MPCX_CTRL_SEQUENCE, ws.Ut, K, j.Ks, ws.end_tau,
-                                                     c.prop_max_step, ws.Yp, ws.pst, ws.nsteps, st))
-            return rc;
-        hipLaunchKernelGGL(ar_select_kernel, dim3((unsigned)S), dim3(64), 0, st, S, K, j.Ks, j.Y, ws.Yp, ws.pst, ws.flies, ws.skip, j.sat_status,
+        if (int rc = ws.f.fly(ctx, S, K, j.flags, c.prop_max_step, st)) return rc;
+        hipLaunchKernelGGL(ar_select_kernel, dim3((unsigned)S), dim3(64), 0, st, S, K, j.Ks, j.Y, ws.f.Yp, ws.f.pst, ws.flies, ws.skip, j.sat_status,
                            c.Y_out, c.hist_term + (size_t)t * S);
         MPCX_HIP(ctx, hipGetLastError());
         if (int rc = c.track ? mpcx_conjunction_track_traj_dev(ctx, n, j.pairs, S, K, j.Ks, c.Y_out, j.units, j.span, D, D ? j.cat_K : 0,
@@ -863,7 +864,7 @@ static int ar_enqueue(mpcx_ctx *ctx, const ArCall &c, void *workspace, hipStream
                                                                D ? ws.cat_st : nullptr, ws.scr, st))
             return rc;
         AjCall q = j;
-        q.pairs = c.pairs_out; q.Y = c.Y_out; q.U = ws.Ut;
+        q.pairs = c.pairs_out; q.Y = c.Y_out; q.U = ws.f.Ut;
         q.du = ws.du_try; q.sat_out = ws.sat_try; q.row_out = ws.row_try; q.sat_status = ws.sat_st_try; q.row_status = ws.row_st_try;
         if (!solve) { q.rows = nullptr; q.tsens = nullptr; }
         AjPass x;

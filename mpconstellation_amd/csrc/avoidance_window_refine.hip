@@ -46,8 +46,9 @@ __global__ __launch_bounds__(256) void awr_first_kernel(int n, int rounds, const
 }
 
 struct AwrVirtual {
-    int32_t *obj, *Ks;                // [V]: the object a virtual trajectory copies, its node count
-    double *units, *span, *consts, *radius, *q, *P0, *y0, *tf, *end_tau;
+    FlightSet f;                      // the V virtual trajectories as they fly
+    int32_t *obj;                     // [V]: the object a virtual trajectory copies
+    double *units, *span, *radius, *q, *P0;
     double *pairs, *pairs_trk;        // [n][4]: the list on the virtual constellation; the same for the tracker (a row whose two
 };                                    //   objects are one is no pair to it, as on the given indices)
 
@@ -61,18 +62,18 @@ __global__ __launch_bounds__(64) void awr_gather_kernel(int n, int NS, int S, in
     const bool ok = ok0[r] != 0;
     const double *row = pairs + (size_t)r * 4;
     const int o = ok ? (int)row[sl] : 0;                            // (a row that passed pass 0: cp_state tested the index)
-    if (lane < 7) w.y0[(size_t)v * 7 + lane] = Y[((size_t)o * 7 + lane) * K];
+    if (lane < 7) w.f.y0[(size_t)v * 7 + lane] = Y[((size_t)o * 7 + lane) * K];
     if (lane < 36) w.P0[(size_t)v * 36 + lane] = P[(size_t)o * K * 36 + lane];
-    if (lane < MPCX_NCONST) w.consts[(size_t)v * MPCX_NCONST + lane] = consts[(size_t)o * MPCX_NCONST + lane];
+    if (lane < MPCX_NCONST) w.f.consts[(size_t)v * MPCX_NCONST + lane] = consts[(size_t)o * MPCX_NCONST + lane];
     if (lane < 2) { w.units[2 * (size_t)v + lane] = units[2 * (size_t)o + lane]; w.span[2 * (size_t)v + lane] = span[2 * (size_t)o + lane]; }
     if (lane == 0) {
         w.obj[v] = o;
-        w.Ks[v] = Ks ? Ks[o] : K;
+        w.f.Ks[v] = Ks ? Ks[o] : K;
         w.radius[v] = radius[o];
         w.q[v] = q ? q[o] : 0.0;
-        const double tfv = (span[2 * (size_t)o + 1] - span[2 * (size_t)o]) / units[2 * (size_t)o + 1];        // (enc_tf_kernel's rule)
-        w.tf[v] = tfv > 0.0 && cp_finite(tfv) ? tfv : 1.0;
-        w.end_tau[v] = 1.0;
+        double tfv;
+        w.f.tf[v] = tr_tf(span[2 * (size_t)o], span[2 * (size_t)o + 1], units[2 * (size_t)o + 1], tfv) ? tfv : 1.0;
+        w.f.end_tau[v] = 1.0;
         if (sl == 0) {
             double *pv = w.pairs + (size_t)r * 4, *pt = w.pairs_trk + (size_t)r * 4;
             const double vi = ok ? (double)v : cp_nan();
@@ -310,9 +311,9 @@ static int awr_check(mpcx_ctx *ctx, const AwrCall &c)
 struct AwrWorkspace {
     void *aw, *scr;
     AwrVirtual v;
-    double *Ut, *Yp, *Pc, *Pt, *trk, *pairs_t, *fig, *wout, *g, *e, *dx;
+    double *Pc, *Pt, *trk, *pairs_t, *fig, *wout, *g, *e, *dx;
     CwsWorkspace lin;
-    int32_t *pst, *nsteps, *cst, *eph_st, *cat_st, *trk_st, *fst, *wstat, *flies, *frozen, *ok0;
+    int32_t *cst, *eph_st, *cat_st, *trk_st, *fst, *wstat, *flies, *frozen, *ok0;
     size_t bytes;
     AwrWorkspace(void *base, int n, int S, int K, int D, int M, int panels, int NS)
     {
@@ -320,19 +321,18 @@ struct AwrWorkspace {
         Carver c(base);
         aw = c.take<char>(mpcx_avoidance_window_workspace_bytes(n, S, K, panels));
         scr = c.take<char>(M >= 2 ? mpcx_conjunction_track_workspace_bytes((int)V, D, M) : 0);
-        v.obj = c.take<int32_t>(V); v.Ks = c.take<int32_t>(V);
-        v.units = c.take<double>(V * 2); v.span = c.take<double>(V * 2); v.consts = c.take<double>(V * MPCX_NCONST);
-        v.radius = c.take<double>(V); v.q = c.take<double>(V); v.P0 = c.take<double>(V * 36); v.y0 = c.take<double>(V * 7);
-        v.tf = c.take<double>(V); v.end_tau = c.take<double>(V);
+        v.f.carve(c, V, (size_t)K);
+        v.obj = c.take<int32_t>(V);
+        v.units = c.take<double>(V * 2); v.span = c.take<double>(V * 2);
+        v.radius = c.take<double>(V); v.q = c.take<double>(V); v.P0 = c.take<double>(V * 36);
         v.pairs = c.take<double>((size_t)n * 4); v.pairs_trk = c.take<double>((size_t)n * 4);
-        Ut = c.take<double>(V * 3 * K); Yp = c.take<double>(V * 7 * K);
         Pc = c.take<double>(V * K * 36); Pt = c.take<double>(V * K * 36);
         trk = c.take<double>((size_t)n * 4); pairs_t = c.take<double>((size_t)n * 4);
         lin.carve_cws(c, n, (int)V, K);
         fig = c.take<double>((size_t)n * MPCX_NPW); wout = c.take<double>((size_t)n * MPCX_NPW);
         g = c.take<double>((size_t)n * 2 * 3 * K); e = c.take<double>((size_t)n * 2 * 3 * K);
         dx = c.take<double>((size_t)n * 4 * K * 6);
-        for (int32_t **p : {&pst, &nsteps, &cst, &eph_st}) *p = c.take<int32_t>(V);
+        for (int32_t **p : {&cst, &eph_st}) *p = c.take<int32_t>(V);
         cat_st = c.take<int32_t>((size_t)(D > 0 ? D : 1));
         for (int32_t **p : {&trk_st, &fst, &wstat, &flies, &frozen, &ok0}) *p = c.take<int32_t>((size_t)n);
         bytes = c.bytes();
@@ -359,16 +359,14 @@ static int awr_enqueue(mpcx_ctx *ctx, const AwrCall &c, void *workspace, hipStre
     for (int t = 1; t <= c.rounds + 1; ++t) {
         const bool solve = t <= c.rounds;
         const size_t total = (size_t)V * 3 * K;
-        hipLaunchKernelGGL(awr_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, V, NS, K, w.U, w.du, ws.v.obj, ws.flies, ws.Ut);
+        hipLaunchKernelGGL(awr_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, V, NS, K, w.U, w.du, ws.v.obj, ws.flies, ws.v.f.Ut);
         MPCX_HIP(ctx, hipGetLastError());
-        if (int rc = mpcx_propagate_batch_ragged_dev(ctx, V, K, ws.v.Ks, ws.v.y0, ws.v.tf, ws.v.consts, w.flags, MPCX_CTRL_SEQUENCE, ws.Ut, K, ws.v.Ks,
-                                                     ws.v.end_tau, c.prop_max_step, ws.Yp, ws.pst, ws.nsteps, st))
-            return rc;
-        hipLaunchKernelGGL(awr_select_kernel, dim3((unsigned)n), dim3(64), 0, st, NS, K, w.who, w.Y, ws.Yp, ws.pst, ws.v.obj, ws.v.Ks, ws.flies,
+        if (int rc = ws.v.f.fly(ctx, V, K, w.flags, c.prop_max_step, st)) return rc;
+        hipLaunchKernelGGL(awr_select_kernel, dim3((unsigned)n), dim3(64), 0, st, NS, K, w.who, w.Y, ws.v.f.Yp, ws.v.f.pst, ws.v.obj, ws.v.f.Ks, ws.flies,
                            ws.frozen, w.status, c.Y_out);
         MPCX_HIP(ctx, hipGetLastError());
         if (c.M >= 2)
-            if (int rc = mpcx_conjunction_track_traj_dev(ctx, n, ws.v.pairs_trk, V, K, ws.v.Ks, c.Y_out, ws.v.units, ws.v.span, D, D ? w.cat_K : 0,
+            if (int rc = mpcx_conjunction_track_traj_dev(ctx, n, ws.v.pairs_trk, V, K, ws.v.f.Ks, c.Y_out, ws.v.units, ws.v.span, D, D ? w.cat_K : 0,
                                                          D ? w.cat_Ks : nullptr, D ? w.cat_Y : nullptr, D ? w.cat_units : nullptr,
                                                          D ? w.cat_span : nullptr, c.M, c.T0, c.T1, c.max_shift, ws.trk, nullptr, ws.trk_st,
                                                          ws.eph_st, D ? ws.cat_st : nullptr, ws.scr, st))
@@ -378,12 +376,12 @@ static int awr_enqueue(mpcx_ctx *ctx, const AwrCall &c, void *workspace, hipStre
         MPCX_HIP(ctx, hipGetLastError());
         // the pass's problem: the virtual constellation as flown
         CwsCall q = w;
-        q.pairs = ws.pairs_t; q.S = V; q.Ks = ws.v.Ks; q.Y = c.Y_out; q.U = ws.Ut; q.units = ws.v.units; q.span = ws.v.span;
-        q.consts = ws.v.consts; q.radius = ws.v.radius;
+        q.pairs = ws.pairs_t; q.S = V; q.Ks = ws.v.f.Ks; q.Y = c.Y_out; q.U = ws.v.f.Ut; q.units = ws.v.units; q.span = ws.v.span;
+        q.consts = ws.v.f.consts; q.radius = ws.v.radius;
         if (solve || c.recov)
             if (int rc = enc_linearise(ctx, q, ws.lin, st)) return rc;
         if (c.recov) {
-            if (int rc = cov_enqueue(ctx, V, K, ws.v.Ks, ws.lin.stage, ws.lin.dstat, ws.v.units, ws.v.span, ws.v.P0, ws.v.q, ws.Pc, ws.cst, st))
+            if (int rc = cov_enqueue(ctx, V, K, ws.v.f.Ks, ws.lin.stage, ws.lin.dstat, ws.v.units, ws.v.span, ws.v.P0, ws.v.q, ws.Pc, ws.cst, st))
                 return rc;
             hipLaunchKernelGGL(awr_pselect_kernel, dim3((unsigned)n), dim3(64), 0, st, NS, K, w.who, 1, w.P, ws.Pc, ws.cst, ws.v.obj, ws.flies, ws.frozen,
                                w.status, Pt);

@@ -9,6 +9,7 @@
 // The encounter frame, the encounter-plane covariance and the butterfly are collision_device.hpp's, shared with avoidance.hip and
 // avoidance_joint.hip; the linearisation step enc_linearise (encounter_host.hpp) is defined here, for them and for the covariance.
 #include "collision_device.hpp"
+#include "covariance_device.hpp"
 #include "encounter_host.hpp"
 
 #include <math.h>
@@ -17,15 +18,15 @@ namespace mpcx {
 
 // ---------------------------------------------------------------- covariance along trajectories
 
-// tf [S] of the linearisation: the span in the satellite's own time unit.  A satellite whose span and time unit give no positive
-// finite tf -- an empty span, a time unit that is zero, negative or not finite -- is linearised with tf = 1 (enc_linearise);
-// covariance_kernel and cp_mover make the same test and give that satellite MPCX_ST_BADK and NaN whatever the discretiser returns.
+// tf [S] of the linearisation: tr_tf, the span in the satellite's own time unit.  A satellite without one is linearised with tf = 1
+// (enc_linearise); cov_status and cp_mover make the same test and give that satellite MPCX_ST_BADK and NaN whatever the discretiser
+// returns.
 __global__ __launch_bounds__(256) void enc_tf_kernel(int S, const double *units, const double *span, double *tf)
 {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= S) return;
-    const double v = (span[2 * s + 1] - span[2 * s]) / units[2 * s + 1];
-    tf[s] = v > 0.0 && cp_finite(v) ? v : 1.0;
+    double v;
+    tf[s] = tr_tf(span[2 * s], span[2 * s + 1], units[2 * s + 1], v) ? v : 1.0;
 }
 
 int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream)
@@ -59,31 +60,21 @@ __global__ __launch_bounds__(64) void covariance_kernel(CovArgs a)
     const double ta = a.span[2 * s], tb = a.span[2 * s + 1], Tu = a.units[2 * s + 1];
     const double qs = a.q ? a.q[s] : 0.0;
     double pij = a.P0[(size_t)s * 36 + lo * 6 + hi];                 // the upper triangle alone is read
-    int st = MPCX_ST_OK;
-    const double tfv = (tb - ta) / Tu;                               // (enc_tf_kernel's test: no positive finite tf, no linearisation)
-    if (nn < 2 || nn > a.K || !(tb > ta) || !(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
-    else if (a.dstat[s] != MPCX_ST_OK) st = a.dstat[s];
-    else if (__any(own && !cp_finite(pij))) st = MPCX_ST_NUMERIC;
+    const int st = cov_status(nn, a.K, ta, tb, Tu, a.dstat + s, own && !cp_finite(pij));
     double *Ps = a.P + (size_t)s * a.K * 36;
     if (lane == 0) a.status[s] = st;
     if (st != MPCX_ST_OK) {
-        for (int e = lane; e < a.K * 36; e += 64) Ps[e] = cp_nan();
+        cov_fill(Ps, lane, 0, a.K * 36, cp_nan());
         return;
     }
-    for (int e = nn * 36 + lane; e < a.K * 36; e += 64) Ps[e] = 0.0;  // columns past the satellite's count
+    cov_fill(Ps, lane, nn * 36, a.K * 36, 0.0);                      // columns past the satellite's count
     const double h = (tb - ta) / (double)(nn - 1);
-    // q Q(h), entry (lo, hi): [[h^3/3 I, h^2/2 I], [h^2/2 I, h I]]
-    double Qe = 0.0;
-    if (hi < 3) Qe = lo == hi ? h * h * h / 3.0 : 0.0;
-    else if (lo < 3) Qe = hi - 3 == lo ? h * h / 2.0 : 0.0;
-    else Qe = lo == hi ? h : 0.0;
-    const double qQ = qs * Qe;
+    const double qQ = qs * cov_noise_entry(lo, hi, h);
     if (own) { Pm[lane] = pij; Ps[lane] = pij; }
     for (int k = 0; k + 1 < nn; ++k) {
         const double *A = a.stage + ((size_t)s * (a.K - 1) + k) * MPCX_STAGE_DOUBLES;      // 7 x 7, row-major: its upper-left 6 x 6
         if (own) {
-            const double f = A[i * 7 + j];
-            phi[lane] = i < 3 && j >= 3 ? f * Tu : (i >= 3 && j < 3 ? f / Tu : f);
+            phi[lane] = cov_scale6(A[i * 7 + j], i, j, Tu);
         }
         __syncthreads();
         if (own) {
@@ -126,15 +117,6 @@ struct CovWorkspace : LinWorkspace {
         bytes = c.bytes();
     }
 };
-
-static int cov_check(mpcx_ctx *ctx, int S, int K, int flags, double max_step)
-{
-    if (S < 1 || K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "covariance: need S>=1, K>=2");
-    if (!(max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "covariance: max_step must be > 0");
-    if (flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
-        return ctx_fail(ctx, MPCX_E_BADARG, "covariance: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
-    return ctx_check_atmosphere(ctx, flags, "covariance");
-}
 
 // ---------------------------------------------------------------- collision probability of listed pairs
 
@@ -252,7 +234,7 @@ extern "C" int mpcx_covariance_batch_dev(mpcx_ctx *ctx, int S, int K, const int3
                                          const double *q, double *P, int32_t *status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (int rc = cov_check(ctx, S, K, flags, max_step)) return rc;
+    if (int rc = cov_check(ctx, "covariance", S, K, flags, max_step)) return rc;
     if (!X || !units || !span || !consts || !P0 || !P || !status || !workspace)
         return ctx_fail(ctx, MPCX_E_BADARG, "covariance: X, units, span, consts, P0, P, status and workspace are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
@@ -271,7 +253,7 @@ extern "C" int mpcx_covariance_batch(mpcx_ctx *ctx, int S, int K, const int32_t 
                                      double *P, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (int rc = cov_check(ctx, S, K, flags, max_step)) return rc;
+    if (int rc = cov_check(ctx, "covariance", S, K, flags, max_step)) return rc;
     if (!X || !units || !span || !consts || !P0 || !P || !status)
         return ctx_fail(ctx, MPCX_E_BADARG, "covariance: X, units, span, consts, P0, P and status are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));

@@ -1,6 +1,7 @@
 // collision_device.hpp -- the encounter core: the device functions that collision_probability_kernel (collision.hip), avoidance_kernel
 // (avoidance.hip) and aj_rows_kernel / aj_solve_kernel / ar_trhs_kernel (avoidance_joint.hip) share, each written once.
-//   an object at the pair's time   cp_state (the cubic Hermite on its own nodes), cp_covariance (the nearest node's covariance carried
+//   (trajectory_device.hpp)        cp_nan, cp_inf, cp_finite, cp_dot, tr_tf and the cubic Hermite of a trajectory, below everything here
+//   an object at the pair's time   cp_state (tr_state on its own nodes, behind the object's tests), cp_covariance (the nearest node's covariance carried
 //                                  over), cp_object (both, in the order collision_probability_kernel has always run them)
 //   the encounter                  cp_frame (e_1, e_2, e_w, the miss and the speed), cp_plane_covariance (C_2 = E^T Cs E, its eigenvalues)
 //   the thrust sensitivities       cp_mover (what a manoeuvring object brings to the sweep), cp_sweep_seed, cp_sweep_node (one node of
@@ -12,13 +13,11 @@
 // (tests/collision_reference.py and tests/avoidance_reference.py restate them).
 #pragma once
 #include "mpcx_host.hpp"
+#include "trajectory_device.hpp"
 
 #include <math.h>
 
 namespace mpcx {
-
-__device__ __forceinline__ double cp_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ bool cp_finite(double x) { return fabs(x) < __longlong_as_double(0x7ff0000000000000LL); }
 
 // one side of the list: the objects a pair's row or column index selects
 struct CpSide {
@@ -35,7 +34,7 @@ struct CpNode {
 };
 
 // Object `fidx` (an index as the pairs list holds it: a double) of one side at time t: position p, velocity v from the cubic Hermite
-// on its own nodes (ephemeris_kernel's formulas).  Returns MPCX_ST_OK or MPCX_ST_BADK (no such object, a node count outside 2..K,
+// on its own nodes (tr_state, as ephemeris_kernel).  Returns MPCX_ST_OK or MPCX_ST_BADK (no such object, a node count outside 2..K,
 // an empty span, t outside the span); on BADK nothing is written and no memory of the object is read.
 __device__ __forceinline__ int cp_state(const CpSide &sd, double fidx, double t, double (&p)[3], double (&v)[3], CpNode &nd)
 {
@@ -44,24 +43,12 @@ __device__ __forceinline__ int cp_state(const CpSide &sd, double fidx, double t,
     const int nn = sd.Ks ? sd.Ks[o] : sd.K;
     const double ta = sd.span[2 * o], tb = sd.span[2 * o + 1];
     if (nn < 2 || nn > sd.K || !(tb > ta) || !(t >= ta && t <= tb)) return MPCX_ST_BADK;
-    const double hn = (tb - ta) / (double)(nn - 1);
-    const double u = (t - ta) / hn;
-    int k = (int)u;
-    if (k > nn - 2) k = nn - 2;
-    if (k < 0) k = 0;
-    const double sg = u - (double)k, s2 = sg * sg, s3 = s2 * sg;
-    const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + sg, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
-    const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
+    const TrNode at = tr_locate(nn, ta, tb, t);
+    double h00, h10, h01, h11;
+    tr_value_basis(at.sg, h00, h10, h01, h11);
     const double L = sd.units[2 * o], V = L / sd.units[2 * o + 1];
-    const double *y = sd.Y + (size_t)o * 7 * sd.K;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double p0 = y[(size_t)c * sd.K + k] * L, p1 = y[(size_t)c * sd.K + k + 1] * L;
-        const double m0 = hn * (y[(size_t)(3 + c) * sd.K + k] * V), m1 = hn * (y[(size_t)(3 + c) * sd.K + k + 1] * V);
-        p[c] = h00 * p0 + h10 * m0 + h01 * p1 + h11 * m1;
-        v[c] = (g00 * p0 + g10 * m0 + g01 * p1 + g11 * m1) / hn;
-    }
-    nd = CpNode{o, k, nn, sg, hn, h00, h10, h01, h11};
+    tr_state(sd.Y + (size_t)o * 7 * sd.K, (size_t)sd.K, at, h00, h10, h01, h11, L, V, p, v);
+    nd = CpNode{o, at.k, nn, at.sg, at.hn, h00, h10, h01, h11};
     return MPCX_ST_OK;
 }
 
@@ -287,8 +274,8 @@ __device__ __forceinline__ int cp_mover(const CpSide &row, const int32_t *dstat,
 {
     int st = MPCX_ST_OK;
     const double L = row.units[2 * nd.o], Tu = row.units[2 * nd.o + 1];
-    const double tfv = (row.span[2 * nd.o + 1] - row.span[2 * nd.o]) / Tu;
-    if (!(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
+    double tfv;
+    if (!tr_tf(row.span[2 * nd.o], row.span[2 * nd.o + 1], Tu, tfv)) st = MPCX_ST_BADK;
     else if (dstat[nd.o] != MPCX_ST_OK) st = dstat[nd.o];
     mv = CpMover{nd.o, nd.k, nd.nn, nd.hn, tfv / (double)(nd.nn - 1), L, L / (Tu * Tu), row.Y + ((size_t)nd.o * 7 + 6) * K};
     return st;

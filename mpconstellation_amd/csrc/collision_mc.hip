@@ -7,9 +7,9 @@
 //   mc_sample_kernel      one wave per virtual trajectory (row, slot, sample): lanes 0..3 run the Philox blocks of the state and the
 //                         mass, every lane the 6 x 6 factor (wave-uniform), lane k the Gates draw of thrust node k -> y0, the thrust
 //                         table and what the flight needs of the object.  The catalogue side of a catalogue call is a second launch.
-//   propagate             mpcx_propagate_batch_ragged_dev on the virtual constellation, as mpcx_avoidance_window_refine flies
+//   propagate             FlightSet::fly on the virtual constellation, as mpcx_avoidance_window_refine flies
 //   mc_scan_kernel        one wave per (row, sample), lane l scan interval l (l + 64, ...): both flown objects at the interval's ends
-//                         by cp_state's Hermite, cj_interval's rule restated on the relative cubic (mc_interval), integer butterflies
+//                         by tr_state's Hermite, cj_interval's rule on the relative cubic (mc_interval), integer butterflies
 //                         -> the sample's record (three int32 in the workspace; the optional `samples` row)
 //   mc_accumulate_kernel  the chunk's records summed into counts [n][MPCX_NMCC]: per block a stride over the samples, the integer
 //                         butterfly, four waves through LDS, one 64-bit atomicAdd per column -- integers, so any order gives the same
@@ -19,6 +19,7 @@
 // the launch.  All launches go onto one stream; their number is fixed by the arguments; nothing is read back.
 // tests/collision_mc_reference.py restates the generator, the draws and the scan.
 #include "collision_window_device.hpp"
+#include "covariance_device.hpp"
 #include "encounter_host.hpp"
 
 #include <math.h>
@@ -113,18 +114,11 @@ struct McSide {
     const double *Y, *U, *units, *span, *consts, *P0, *exec, *mvar;
 };
 
-// the virtual constellation of one sampler launch (V = n slots C trajectories, v = (r slots + slot) C + c, rows of length K)
-struct McGroup {
-    int32_t *Ks, *pst, *nsteps;
-    double *y0, *Ut, *tf, *end_tau, *consts, *Yp;
-};
+// The virtual constellation of one sampler launch is a FlightSet (encounter_host.hpp): V = n slots C trajectories,
+// v = (r slots + slot) C + c, rows of length K.
 
-// the flight's tf of an object (enc_tf_kernel's rule) and whether it is one
-__device__ __forceinline__ bool mc_tf(const McSide &sd, int o, double &tf)
-{
-    tf = (sd.span[2 * o + 1] - sd.span[2 * o]) / sd.units[2 * o + 1];
-    return tf > 0.0 && cp_finite(tf);
-}
+// the flight's tf of an object and whether it is one
+__device__ __forceinline__ bool mc_tf(const McSide &sd, int o, double &tf) { return tr_tf(sd.span[2 * o], sd.span[2 * o + 1], sd.units[2 * o + 1], tf); }
 
 // what is drawn about object o can be drawn: the factor, a mass variance and an exec row that are finite and not negative
 __device__ __forceinline__ bool mc_drawable(const McSide &sd, int o)
@@ -132,8 +126,7 @@ __device__ __forceinline__ bool mc_drawable(const McSide &sd, int o)
     double L[21];
     bool ok = mc_factor(sd.P0 + (size_t)o * 36, L);
     if (sd.mvar) { const double m = sd.mvar[o]; ok = ok && m >= 0.0 && cp_finite(m); }
-    if (sd.exec)
-        for (int e = 0; e < MPCX_NEXEC; ++e) { const double x = sd.exec[(size_t)o * MPCX_NEXEC + e]; ok = ok && x >= 0.0 && cp_finite(x); }
+    if (sd.exec) ok = ok && gates_valid(gates_load(sd.exec + (size_t)o * MPCX_NEXEC));
     return ok;
 }
 
@@ -170,7 +163,7 @@ struct McSampleArgs {
     uint32_t side, k0, k1, s0;        // 0 constellation, 1 catalogue; the key; the chunk's first sample
     int n, slots, col0, C;            // slots of this launch per row, the pairs column of its slot 0, samples in the chunk
     const double *pairs;
-    McGroup g;
+    FlightSet g;
 };
 
 __global__ __launch_bounds__(64) void mc_sample_kernel(McSampleArgs a)
@@ -213,11 +206,8 @@ __global__ __launch_bounds__(64) void mc_sample_kernel(McSampleArgs a)
         a.g.end_tau[v] = 1.0;
     }
     // ---- the thrust table: lane k node k; blocks 4 + 2k and 5 + 2k its three normals
-    double fm = 0.0, pm = 0.0, fp = 0.0, pp = 0.0, off = 0.0;
-    if (sd.exec) {
-        const double *ex = sd.exec + (size_t)o * MPCX_NEXEC;
-        fm = ex[0]; pm = ex[1]; fp = ex[2]; pp = ex[3]; off = ex[4];
-    }
+    GatesRow ex{};
+    if (sd.exec) ex = gates_load(sd.exec + (size_t)o * MPCX_NEXEC);
     double *ut = a.g.Ut + (size_t)v * 3 * K;
     for (int k = lane; k < sd.K; k += 64) {
         double ux = 0.0, uy = 0.0, uz = 0.0;
@@ -225,13 +215,14 @@ __global__ __launch_bounds__(64) void mc_sample_kernel(McSampleArgs a)
             const double *u = sd.U + (size_t)o * 3 * K;
             ux = u[k]; uy = u[K + k]; uz = u[2 * K + k];
             const double un = sqrt(ux * ux + uy * uy + uz * uz);
-            if (sd.exec && un > off) {
+            if (sd.exec && gates_on(ex, un)) {
                 double z1, z2, z3, zu;
                 mc_normals(smp, (uint32_t)o, 4u + 2u * (uint32_t)k, a.side, a.k0, a.k1, z1, z2);
                 mc_normals(smp, (uint32_t)o, 5u + 2u * (uint32_t)k, a.side, a.k0, a.k1, z3, zu);
                 const double hx = ux / un, hy = uy / un, hz = uz / un;
-                const double am = pm * un, ap = pp * un;
-                const double spar = sqrt(fm * fm + am * am), sperp = sqrt(fp * fp + ap * ap);
+                double vpar, vperp;
+                gates_variances(ex, un, vpar, vperp);
+                const double spar = sqrt(vpar), sperp = sqrt(vperp);
                 // e_1: the coordinate axis on which |u^| is smallest (the first of equal ones), made orthogonal to u^ (cp_frame's rule)
                 int ax = 0;
                 double ea = hx;
@@ -253,59 +244,41 @@ __global__ __launch_bounds__(64) void mc_sample_kernel(McSampleArgs a)
 
 // ---------------------------------------------------------------- the scan
 
-// position p (m) and velocity v (m/s) at time t of a flown trajectory y [7][ld] with nn nodes over [ta, tb]: cp_state's
-// expressions (mpcx_ephemeris_batch's Hermite) without its tests -- the caller's t lies in the span
+// position p (m) and velocity v (m/s) at time t of a flown trajectory y [7][ld] with nn nodes over [ta, tb]: tr_state, as cp_state
+// without its tests -- the caller's t lies in the span
 __device__ __forceinline__ void mc_state(const double *y, size_t ld, int nn, double ta, double tb, double L, double Tu, double t,
                                          double (&p)[3], double (&v)[3])
 {
-    const double hn = (tb - ta) / (double)(nn - 1);
-    const double u = (t - ta) / hn;
-    int k = (int)u;
-    if (k > nn - 2) k = nn - 2;
-    if (k < 0) k = 0;
-    const double sg = u - (double)k, s2 = sg * sg, s3 = s2 * sg;
-    const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + sg, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
-    const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
-    const double V = L / Tu;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double p0 = y[(size_t)c * ld + k] * L, p1 = y[(size_t)c * ld + k + 1] * L;
-        const double m0 = hn * (y[(size_t)(3 + c) * ld + k] * V), m1 = hn * (y[(size_t)(3 + c) * ld + k + 1] * V);
-        p[c] = h00 * p0 + h10 * m0 + h01 * p1 + h11 * m1;
-        v[c] = (g00 * p0 + g10 * m0 + g01 * p1 + g11 * m1) / hn;
-    }
+    const TrNode at = tr_locate(nn, ta, tb, t);
+    double h00, h10, h01, h11;
+    tr_value_basis(at.sg, h00, h10, h01, h11);
+    tr_state(y, ld, at, h00, h10, h01, h11, L, L / Tu, p, v);
 }
-
-__device__ __forceinline__ double mc_dot(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // One scan interval of length h from t0: the relative position is the cubic Hermite of the end differences d0, d1 and the end
 // relative velocities w0, w1.  q0, q1: the squared distances at the ends; (qm, tm): the smallest squared distance found and its time
-// by conjunction.hip's cj_interval rule, restated -- the ends (the later one only if strictly smaller), the clamped minimum of the
-// chord as the start of three Newton steps on the cubic, each clamped to [0, 1], the interior point only if strictly smaller.
+// by conjunction.hip's cj_interval rule -- the ends (the later one only if strictly smaller), then the interior point of tr_chord_start
+// and tr_newton, only if strictly smaller.  (Its time is formed in two statements, t0 + (s h) rounded twice, where cj_interval's one
+// expression is contracted: each keeps its own.)
 __device__ __forceinline__ void mc_interval(const double (&d0)[3], const double (&d1)[3], const double (&w0)[3], const double (&w1)[3], double h,
                                             double t0, double t1, double &q0, double &q1, double &qm, double &tm)
 {
-    q0 = mc_dot(d0, d0); q1 = mc_dot(d1, d1);
+    q0 = cp_dot(d0, d0); q1 = cp_dot(d1, d1);
     qm = q0; tm = t0;
     if (q1 < qm) { qm = q1; tm = t1; }
-    const double D[3] = {d1[0] - d0[0], d1[1] - d0[1], d1[2] - d0[2]};
-    const double DD = mc_dot(D, D), b = mc_dot(d0, D);
-    double s = 0.0;
-    if (DD > 0.0 && cp_finite(DD)) {
-        s = -b / DD;
-        s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-    }
+    double s = tr_chord_start(d0, d1);
     if (s > 0.0 && s < 1.0) {
         double a0[3], a1[3], x[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { a0[c] = h * w0[c]; a1[c] = h * w1[c]; }
-        for (int it = 0; it < 4; ++it) {                             // three Newton steps, then the distance at the result
-            const double s2 = s * s, s3 = s2 * s;
-            const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + s, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
+        for (int it = 0; it < 4; ++it) {                             // tr_newton's loop, kept as text: through the call mc_scan_kernel's
+            double h00, h10, h01, h11;                               // register count moves (194 -> 192)
+            tr_value_basis(s, h00, h10, h01, h11);
 #pragma unroll
             for (int c = 0; c < 3; ++c) x[c] = h00 * d0[c] + h10 * a0[c] + h01 * d1[c] + h11 * a1[c];
             if (it == 3) break;
-            const double g00 = 6.0 * s2 - 6.0 * s, g10 = 3.0 * s2 - 4.0 * s + 1.0, g01 = -6.0 * s2 + 6.0 * s, g11 = 3.0 * s2 - 2.0 * s;
+            double g00, g10, g01, g11;
+            tr_slope_basis(s, g00, g10, g01, g11);
             const double k00 = 12.0 * s - 6.0, k10 = 6.0 * s - 4.0, k01 = -12.0 * s + 6.0, k11 = 6.0 * s - 2.0;
             double x1[3], x2[3];
 #pragma unroll
@@ -313,13 +286,13 @@ __device__ __forceinline__ void mc_interval(const double (&d0)[3], const double 
                 x1[c] = g00 * d0[c] + g10 * a0[c] + g01 * d1[c] + g11 * a1[c];
                 x2[c] = k00 * d0[c] + k10 * a0[c] + k01 * d1[c] + k11 * a1[c];
             }
-            const double g = mc_dot(x, x1), gp = mc_dot(x1, x1) + mc_dot(x, x2);
+            const double g = cp_dot(x, x1), gp = cp_dot(x1, x1) + cp_dot(x, x2);
             if (gp > 0.0) {
                 s = s - g / gp;
                 s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
             }
         }
-        const double qs = mc_dot(x, x);
+        const double qs = cp_dot(x, x);
         const double ts = s * h;
         if (qs < qm) { qm = qs; tm = t0 + ts; }
     }
@@ -340,7 +313,7 @@ struct McScanArgs {
     const double *pairs, *info;
     const int32_t *rowst;
     McSide rs, cs;
-    McGroup a, b;
+    FlightSet a, b;
     int32_t *rec;                     // [n][C][3]: flight status (or MC_SKIP), inside_start, entries
     double *samples;                  // [n][N][MPCX_NMS] or NULL
 };
@@ -367,7 +340,7 @@ __global__ __launch_bounds__(64) void mc_scan_kernel(McScanArgs a)
     const double *row = a.pairs + (size_t)r * 4;
     const int oi = (int)row[0], oj = (int)row[1];                    // (tested by cw_row)
     const size_t vi = ((size_t)r * a.slots) * a.C + c, vj = a.slots == 2 ? ((size_t)r * 2 + 1) * a.C + c : (size_t)r * a.C + c;
-    const McGroup &gj = a.slots == 2 ? a.a : a.b;
+    const FlightSet &gj = a.slots == 2 ? a.a : a.b;
     int fst = a.a.pst[vi];
     if (fst == MPCX_ST_OK) fst = gj.pst[vj];
     const double inf = __longlong_as_double(0x7ff0000000000000LL);
@@ -564,23 +537,17 @@ static int mc_check(mpcx_ctx *ctx, const McCall &c)
 struct McWorkspace {
     double *info;
     int32_t *rowst, *rec;
-    McGroup a, b;
+    FlightSet a, b;
     size_t bytes;
-    static void carve(Carver &c, McGroup &g, size_t V, size_t K)
-    {
-        g.Ks = c.take<int32_t>(V); g.pst = c.take<int32_t>(V); g.nsteps = c.take<int32_t>(V);
-        g.y0 = c.take<double>(V * 7); g.Ut = c.take<double>(V * 3 * K); g.tf = c.take<double>(V); g.end_tau = c.take<double>(V);
-        g.consts = c.take<double>(V * MPCX_NCONST); g.Yp = c.take<double>(V * 7 * K);
-    }
     McWorkspace(void *base, int n, int K, bool cat, int cat_K, int Cs)
     {
         Carver c(base);
         info = c.take<double>((size_t)n * 3);
         rowst = c.take<int32_t>((size_t)n);
         rec = c.take<int32_t>((size_t)n * Cs * 3);
-        carve(c, a, (size_t)n * (cat ? 1 : 2) * Cs, (size_t)K);
-        b = McGroup{};
-        if (cat) carve(c, b, (size_t)n * Cs, (size_t)cat_K);
+        a.carve(c, (size_t)n * (cat ? 1 : 2) * Cs, (size_t)K);
+        b = FlightSet{};
+        if (cat) b.carve(c, (size_t)n * Cs, (size_t)cat_K);
         bytes = c.bytes();
     }
 };
@@ -606,17 +573,12 @@ static int mc_enqueue(mpcx_ctx *ctx, const McCall &c, void *workspace, hipStream
         hipLaunchKernelGGL(mc_sample_kernel, dim3((unsigned)Va), dim3(64), 0, st,
                            McSampleArgs{rs, 0u, k0, k1, (uint32_t)s0, n, NS, 0, C, c.pairs, ws.a});
         MPCX_HIP(ctx, hipGetLastError());
-        if (int rc = mpcx_propagate_batch_ragged_dev(ctx, Va, K, ws.a.Ks, ws.a.y0, ws.a.tf, ws.a.consts, c.flags, MPCX_CTRL_SEQUENCE, ws.a.Ut, K,
-                                                     ws.a.Ks, ws.a.end_tau, c.prop_max_step, ws.a.Yp, ws.a.pst, ws.a.nsteps, st))
-            return rc;
+        if (int rc = ws.a.fly(ctx, Va, K, c.flags, c.prop_max_step, st)) return rc;
         if (cat) {
             hipLaunchKernelGGL(mc_sample_kernel, dim3((unsigned)Vb), dim3(64), 0, st,
                                McSampleArgs{cs, 1u, k0, k1, (uint32_t)s0, n, 1, 1, C, c.pairs, ws.b});
             MPCX_HIP(ctx, hipGetLastError());
-            if (int rc = mpcx_propagate_batch_ragged_dev(ctx, Vb, c.cat_K, ws.b.Ks, ws.b.y0, ws.b.tf, ws.b.consts, c.flags, MPCX_CTRL_SEQUENCE,
-                                                         ws.b.Ut, c.cat_K, ws.b.Ks, ws.b.end_tau, c.prop_max_step, ws.b.Yp, ws.b.pst,
-                                                         ws.b.nsteps, st))
-                return rc;
+            if (int rc = ws.b.fly(ctx, Vb, c.cat_K, c.flags, c.prop_max_step, st)) return rc;
         }
         hipLaunchKernelGGL(mc_scan_kernel, dim3((unsigned)(n * C)), dim3(64), 0, st,
                            McScanArgs{n, C, N, c.scan, NS, (uint32_t)s0, c.pairs, ws.info, ws.rowst, rs, cs, ws.a, ws.b, ws.rec, c.samples});

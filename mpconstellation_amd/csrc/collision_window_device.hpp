@@ -450,8 +450,8 @@ struct CwBasis {
 };
 __device__ __forceinline__ void cw_basis(const CpNode &nd, double L, double Tu, double htau, CwBasis &b)
 {
-    const double sg = nd.sg, s2 = sg * sg;
-    const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
+    double g00, g10, g01, g11;
+    tr_slope_basis(nd.sg, g00, g10, g01, g11);
     const double V = L / Tu;
     b.p[0] = L * nd.h00; b.p[1] = L * (htau * nd.h10); b.p[2] = L * nd.h01; b.p[3] = L * (htau * nd.h11);
     b.v[0] = (L * g00) / nd.hn; b.v[1] = V * g10; b.v[2] = (L * g01) / nd.hn; b.v[3] = V * g11;

@@ -3,7 +3,8 @@
 // (SatelliteScale: length = its start radius, time = its own period), so node k of two satellites is two different instants in
 // two different lengths.  Here
 //   ephemeris_kernel   resamples every trajectory at M common instants in metres and m/s: cubic Hermite in physical time on the
-//                      node positions and velocities (the state carries the velocity: C1, error h_n^4 / 384 max |p''''|);
+//                      node positions and velocities (the state carries the velocity: C1, error h_n^4 / 384 max |p''''|), by
+//                      trajectory_device.hpp's tr_state, as every later kernel of the chain places an object;
 //   screen_kernel      for every (row, column) pair and every grid interval the closest approach of the two Hermite arcs -- chord
 //                      minimum, then three Newton steps on d . d' -- reduced to one (distance, partner, time) per row and, with a
 //                      threshold, to a list of the pairs that come closer than it;
@@ -23,6 +24,7 @@
 // a total order (squared distance, then column index, then interval), so nothing depends on tiles, grid dimensions, row blocks
 // or device count.
 #include "mpcx_host.hpp"
+#include "trajectory_device.hpp"
 
 #include <math.h>
 
@@ -32,9 +34,6 @@ constexpr int CJ_TC = 16;             // columns of a tile: a lane keeps the pai
 constexpr int CJ_MAXGROUPS = 64;      // all pairs: column groups (gridDim.y) at the most
 constexpr int CJX_WAVES = 2048;       // cross: waves the launch aims at, two on each of the 256 x 4 SIMDs, what the kernel's registers admit
 constexpr int CJX_WIDE_FROM = 512;    // cross: rows from which a workgroup takes 256 of them (four waves share the staged columns) instead of 64
-
-__device__ __forceinline__ double cj_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ double cj_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
 
 // np.linspace(T0, T1, M)[m]: m * step, the last instant exactly T1 (a satellite whose span ends at T1 is still inside)
 __device__ __forceinline__ double cj_time(int m, int M, double T0, double T1, double h)
@@ -62,25 +61,15 @@ __global__ __launch_bounds__(256) void ephemeris_kernel(EphArgs a)
     const bool bad = nn < 2 || nn > a.n || !(tb > ta);
     if (m == 0) a.status[s] = bad ? MPCX_ST_BADK : MPCX_ST_OK;
     double o[6];
-    for (int c = 0; c < 6; ++c) o[c] = cj_nan();
+    for (int c = 0; c < 6; ++c) o[c] = cp_nan();
     const double t = cj_time(m, a.M, a.T0, a.T1, a.h);
     if (!bad && t >= ta && t <= tb) {
-        const double hn = (tb - ta) / (double)(nn - 1);
-        const double u = (t - ta) / hn;
-        int k = (int)u;
-        if (k > nn - 2) k = nn - 2;
-        if (k < 0) k = 0;
-        const double sg = u - (double)k, s2 = sg * sg, s3 = s2 * sg;
-        const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + sg, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
-        const double g00 = 6.0 * s2 - 6.0 * sg, g10 = 3.0 * s2 - 4.0 * sg + 1.0, g01 = -6.0 * s2 + 6.0 * sg, g11 = 3.0 * s2 - 2.0 * sg;
+        const TrNode nd = tr_locate(nn, ta, tb, t);
+        double h00, h10, h01, h11, p[3], v[3];
+        tr_value_basis(nd.sg, h00, h10, h01, h11);
         const double L = a.units[2 * s], V = L / a.units[2 * s + 1];
-        const double *y = a.Y + (size_t)s * 7 * a.n;
-        for (int c = 0; c < 3; ++c) {
-            const double p0 = y[(size_t)c * a.n + k] * L, p1 = y[(size_t)c * a.n + k + 1] * L;
-            const double m0 = hn * (y[(size_t)(3 + c) * a.n + k] * V), m1 = hn * (y[(size_t)(3 + c) * a.n + k + 1] * V);
-            o[c] = h00 * p0 + h10 * m0 + h01 * p1 + h11 * m1;
-            o[3 + c] = (g00 * p0 + g10 * m0 + g01 * p1 + g11 * m1) / hn;
-        }
+        tr_state(a.Y + (size_t)s * 7 * a.n, (size_t)a.n, nd, h00, h10, h01, h11, L, V, p, v);
+        for (int c = 0; c < 3; ++c) { o[c] = p[c]; o[3 + c] = v[c]; }
     }
     for (int c = 0; c < 6; ++c) a.eph[((size_t)s * 6 + c) * a.M + m] = o[c];
 }
@@ -96,56 +85,31 @@ __global__ __launch_bounds__(256) void conjunction_transpose_kernel(int S, int M
     double v[6];
     bool nan = false;
     for (int c = 0; c < 6; ++c) { v[c] = eph[((size_t)s * 6 + c) * M + m]; nan = nan || !(v[c] == v[c]); }
-    for (int c = 0; c < 6; ++c) ephT[((size_t)m * 6 + c) * S + s] = nan ? cj_nan() : v[c];
+    for (int c = 0; c < 6; ++c) ephT[((size_t)m * 6 + c) * S + s] = nan ? cp_nan() : v[c];
 }
-
-__device__ __forceinline__ double cj_dot(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // The closest approach of one pair inside one grid interval.  d0, d1: hi - lo position differences at the interval's ends;
 // cv0, cv1 / v0, v1: the column's and the row's velocities there (their difference, hi - lo, is formed only where the Newton
 // steps need it; up: the column is the higher index).  Distances are compared squared (the root is taken once, on the way out).  Updates
-// (best, tbest) when the interval comes closer: ends first, the interior point last, each only if strictly smaller.
+// (best, tbest) when the interval comes closer: ends first, the interior point (tr_chord_start, tr_newton) last, each only if
+// strictly smaller.
 __device__ __forceinline__ void cj_interval(const double (&d0)[3], const double (&d1)[3], const double *cv0, const double *cv1,
                                             const double (&v0)[3], const double (&v1)[3], bool up, double h, double t0, double t1,
                                             double &best, double &tbest)
 {
-    const double q0 = cj_dot(d0, d0), q1 = cj_dot(d1, d1);
+    const double q0 = cp_dot(d0, d0), q1 = cp_dot(d1, d1);
     if (!(q0 == q0) || !(q1 == q1)) return;                       // an end outside a satellite's span
     double q = q0, tq = t0;
     if (q1 < q) { q = q1; tq = t1; }
-    const double D[3] = {d1[0] - d0[0], d1[1] - d0[1], d1[2] - d0[2]};
-    const double DD = cj_dot(D, D), b = cj_dot(d0, D);
-    double s = 0.0;
-    if (DD > 0.0 && DD < cj_inf()) {
-        s = -b / DD;
-        s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-    }
+    double s = tr_chord_start(d0, d1);
     if (s > 0.0 && s < 1.0) {
         double a0[3], a1[3];                                      // h w0, h w1
         for (int c = 0; c < 3; ++c) {
             a0[c] = h * (up ? cv0[c] - v0[c] : v0[c] - cv0[c]);
             a1[c] = h * (up ? cv1[c] - v1[c] : v1[c] - cv1[c]);
         }
-        double x[3];
-        for (int it = 0; it < 4; ++it) {                          // three Newton steps, then the distance at the result
-            const double s2 = s * s, s3 = s2 * s;
-            const double h00 = 2.0 * s3 - 3.0 * s2 + 1.0, h10 = s3 - 2.0 * s2 + s, h01 = -2.0 * s3 + 3.0 * s2, h11 = s3 - s2;
-            for (int c = 0; c < 3; ++c) x[c] = h00 * d0[c] + h10 * a0[c] + h01 * d1[c] + h11 * a1[c];
-            if (it == 3) break;
-            const double g00 = 6.0 * s2 - 6.0 * s, g10 = 3.0 * s2 - 4.0 * s + 1.0, g01 = -6.0 * s2 + 6.0 * s, g11 = 3.0 * s2 - 2.0 * s;
-            const double k00 = 12.0 * s - 6.0, k10 = 6.0 * s - 4.0, k01 = -12.0 * s + 6.0, k11 = 6.0 * s - 2.0;
-            double x1[3], x2[3];
-            for (int c = 0; c < 3; ++c) {
-                x1[c] = g00 * d0[c] + g10 * a0[c] + g01 * d1[c] + g11 * a1[c];
-                x2[c] = k00 * d0[c] + k10 * a0[c] + k01 * d1[c] + k11 * a1[c];
-            }
-            const double g = cj_dot(x, x1), gp = cj_dot(x1, x1) + cj_dot(x, x2);
-            if (gp > 0.0) {
-                s = s - g / gp;
-                s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-            }
-        }
-        const double qs = cj_dot(x, x);
+        double qs;
+        s = tr_newton(d0, d1, a0, a1, s, qs);
         if (qs < q) { q = qs; tq = t0 + s * h; }
     }
     if (q < best) { best = q; tbest = tq; }
@@ -181,21 +145,21 @@ template <int ROWS, int TM, bool SELF> __global__ __launch_bounds__(ROWS) void s
     const size_t ir = row_ok ? r : 0;                            // (lanes past the last row load the first row's ends and record nothing)
     const int i = a.row0 + (int)ir;                              // SELF: the row's index among the columns
     const size_t R = a.rstride, C = (size_t)a.C;
-    double bd2 = cj_inf(), bt = cj_nan();
+    double bd2 = cp_inf(), bt = cp_nan();
     int bj = -1;
     const int ntile = (a.C + CJ_TC - 1) / CJ_TC;
     for (int jt = blockIdx.y; jt < ntile; jt += gridDim.y) {
         const int j0 = jt * CJ_TC;
         double pd2[CJ_TC], pt[CJ_TC];
 #pragma unroll
-        for (int jj = 0; jj < CJ_TC; ++jj) { pd2[jj] = cj_inf(); pt[jj] = cj_nan(); }
+        for (int jj = 0; jj < CJ_TC; ++jj) { pd2[jj] = cp_inf(); pt[jj] = cp_nan(); }
         for (int m0 = 0; m0 < a.M - 1; m0 += TM) {
             const int nm = a.M - 1 - m0 < TM ? a.M - 1 - m0 : TM;                // intervals of this chunk
             __syncthreads();
             for (int e = lane; e < (nm + 1) * CJ_TC * 6; e += ROWS) {
                 const int mm = e / (CJ_TC * 6), q = e - mm * (CJ_TC * 6), c = q / CJ_TC, jj = q - c * CJ_TC;
                 const int j = j0 + jj;
-                col[(mm * CJ_TC + jj) * 6 + c] = j < a.C ? a.colT[((size_t)(m0 + mm) * 6 + c) * C + j] : cj_nan();
+                col[(mm * CJ_TC + jj) * 6 + c] = j < a.C ? a.colT[((size_t)(m0 + mm) * 6 + c) * C + j] : cp_nan();
             }
             __syncthreads();
             double p0[3], v0[3], p1[3], v1[3];
@@ -229,7 +193,7 @@ template <int ROWS, int TM, bool SELF> __global__ __launch_bounds__(ROWS) void s
 #pragma unroll
         for (int jj = 0; jj < CJ_TC; ++jj) {
             const int j = j0 + jj;
-            if (!(pd2[jj] < cj_inf())) continue;                                 // no valid interval for this pair (or j == i, j >= C)
+            if (!(pd2[jj] < cp_inf())) continue;                                 // no valid interval for this pair (or j == i, j >= C)
             if (pd2[jj] < bd2 || (pd2[jj] == bd2 && j < bj)) { bd2 = pd2[jj]; bt = pt[jj]; bj = j; }
             if (a.thr > 0.0 && (!SELF || j > i)) {
                 const double d = sqrt(pd2[jj]);
@@ -255,7 +219,7 @@ __global__ __launch_bounds__(256) void conjunction_reduce_kernel(int nrows, int 
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= nrows) return;
-    double bd2 = cj_inf(), bt = cj_nan();
+    double bd2 = cp_inf(), bt = cp_nan();
     int bj = -1;
     for (int g = 0; g < ngroups; ++g) {
         const size_t at = (size_t)g * nrows + r;
@@ -264,7 +228,7 @@ __global__ __launch_bounds__(256) void conjunction_reduce_kernel(int nrows, int 
         const double d2 = pd2[at];
         if (bj < 0 || d2 < bd2 || (d2 == bd2 && j < bj)) { bd2 = d2; bt = pt[at]; bj = j; }
     }
-    dmin[r] = bj < 0 ? cj_inf() : sqrt(bd2);
+    dmin[r] = bj < 0 ? cp_inf() : sqrt(bd2);
     partner[r] = bj;
     tca[r] = bt;
 }
@@ -290,7 +254,7 @@ __device__ __forceinline__ void cj_end(const double *e, int M, int m, double (&p
         p[c] = e[(size_t)c * M + m]; v[c] = e[(size_t)(3 + c) * M + m];
         nan = nan || !(p[c] == p[c]) || !(v[c] == v[c]);
     }
-    for (int c = 0; c < 3; ++c) { p[c] = nan ? cj_nan() : p[c]; v[c] = nan ? cj_nan() : v[c]; }
+    for (int c = 0; c < 3; ++c) { p[c] = nan ? cp_nan() : p[c]; v[c] = nan ? cp_nan() : v[c]; }
 }
 
 // Grid interval m of a listed pair through cj_interval into (best, tbest).  er, ec: the rows of the ephemerides of object i (the
@@ -331,12 +295,12 @@ __global__ __launch_bounds__(64) void pairs_kernel(PairsArgs a)
     const int i = cj_index(xi, a.S), j = cj_index(xj, cross ? a.D : a.S);
     double *o = a.out + (size_t)r * 4;
     if (i < 0 || j < 0 || (!cross && i == j)) {                      // (the whole wave: it reads nothing of the ephemerides)
-        if (lane == 0) { o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan(); a.status[r] = MPCX_ST_BADK; }
+        if (lane == 0) { o[0] = xi; o[1] = xj; o[2] = cp_nan(); o[3] = cp_nan(); a.status[r] = MPCX_ST_BADK; }
         return;
     }
     const bool up = cross || j > i;                                  // the column is the higher index: column - row
     const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
-    double best = cj_inf(), tbest = cj_nan();
+    double best = cp_inf(), tbest = cp_nan();
     int mbest = 0x7fffffff;
     for (int m = lane; m < a.M - 1; m += 64) {
         const double before = best;
@@ -350,8 +314,8 @@ __global__ __launch_bounds__(64) void pairs_kernel(PairsArgs a)
     }
     if (lane == 0) {
         o[0] = xi; o[1] = xj;
-        o[2] = best < cj_inf() ? sqrt(best) : cj_inf();              // no valid interval: +inf, NaN, as the screens' rows have it
-        o[3] = best < cj_inf() ? tbest : cj_nan();
+        o[2] = best < cp_inf() ? sqrt(best) : cp_inf();              // no valid interval: +inf, NaN, as the screens' rows have it
+        o[3] = best < cp_inf() ? tbest : cp_nan();
         a.status[r] = MPCX_ST_OK;
     }
 }
@@ -394,11 +358,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
         const bool up = cross || j > i;                              // the column is the higher index: column - row
         const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
         const int nchunk = (a.M - 1 + 63) / 64;
-        double qp = cj_inf(), tp = cj_nan();                         // the pending chunk's interval of this lane
-        double carry = cj_inf();                                     // q of the interval before the pending chunk's first
+        double qp = cp_inf(), tp = cp_nan();                         // the pending chunk's interval of this lane
+        double carry = cp_inf();                                     // q of the interval before the pending chunk's first
         for (int c = 0; c <= nchunk; ++c) {
             const int m = 64 * c + lane;
-            double q = cj_inf(), t = cj_nan();
+            double q = cp_inf(), t = cp_nan();
             if (m < a.M - 1) cj_pair_interval(a, er, ec, up, m, q, t);
             const int mp = m - 64;
             double left = __shfl_up(qp, 1), right = __shfl_down(qp, 1);
@@ -406,13 +370,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
             if (lane == 0) left = carry;
             if (lane == 63) right = next;
             const double d = sqrt(qp);
-            const bool event = qp < cj_inf() && qp < left && qp <= right && (!(e.thr > 0.0) || d <= e.thr);
+            const bool event = qp < cp_inf() && qp < left && qp <= right && (!(e.thr > 0.0) || d <= e.thr);
             const unsigned long long lanes = __ballot(event);
             const int slot = found + __popcll(lanes & ((1ULL << lane) - 1ULL));
             if (event && slot < e.E) {
                 // still closing where the pair's common span ends: the time is an assigned end of the interval, so == is exact
-                const bool edge = (!(left < cj_inf()) && tp == cj_time(mp, a.M, a.T0, a.T1, a.h)) ||
-                                  (!(right < cj_inf()) && tp == cj_time(mp + 1, a.M, a.T0, a.T1, a.h));
+                const bool edge = (!(left < cp_inf()) && tp == cj_time(mp, a.M, a.T0, a.T1, a.h)) ||
+                                  (!(right < cp_inf()) && tp == cj_time(mp + 1, a.M, a.T0, a.T1, a.h));
                 double *o = ev + (size_t)slot * 4;
                 o[0] = xi; o[1] = xj; o[2] = d; o[3] = tp;
                 inf[2 * slot] = mp; inf[2 * slot + 1] = edge ? 1 : 0;
@@ -424,7 +388,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     }
     for (int s = (found < e.E ? found : e.E) + lane; s < e.E; s += 64) {
         double *o = ev + (size_t)s * 4;
-        o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan();
+        o[0] = xi; o[1] = xj; o[2] = cp_nan(); o[3] = cp_nan();
         inf[2 * s] = -1; inf[2 * s + 1] = 0;
     }
     if (lane == 0) { e.count[r] = found; a.status[r] = bad ? MPCX_ST_BADK : MPCX_ST_OK; }
@@ -461,7 +425,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     // (the whole wave: it reads nothing of the ephemerides; trow - trow is 0 for a finite time and NaN otherwise)
     if (i < 0 || j < 0 || (!cross && i == j) || !(trow - trow == 0.0)) {
         if (lane == 0) {
-            o[0] = xi; o[1] = xj; o[2] = cj_nan(); o[3] = cj_nan();
+            o[0] = xi; o[1] = xj; o[2] = cp_nan(); o[3] = cp_nan();
             if (e.info) { e.info[2 * (size_t)r] = -1; e.info[2 * (size_t)r + 1] = 0; }
             a.status[r] = MPCX_ST_BADK;
         }
@@ -470,20 +434,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     const bool up = cross || j > i;                                  // the column is the higher index: column - row
     const double *er = a.eph + (size_t)i * 6 * a.M, *ec = (cross ? a.cat : a.eph) + (size_t)j * 6 * a.M;
     const int nchunk = (a.M - 1 + 63) / 64;
-    double qp = cj_inf(), tp = cj_nan();                             // the pending chunk's interval of this lane
-    double carry = cj_inf();                                         // q of the interval before the pending chunk's first
-    double bdt = cj_inf();                                           // this lane's best candidate: |dt| and the interval
+    double qp = cp_inf(), tp = cp_nan();                             // the pending chunk's interval of this lane
+    double carry = cp_inf();                                         // q of the interval before the pending chunk's first
+    double bdt = cp_inf();                                           // this lane's best candidate: |dt| and the interval
     int bm = 0x7fffffff;                                             //   (INT_MAX: none)
     for (int c = 0; c <= nchunk; ++c) {
         const int m = 64 * c + lane;
-        double q = cj_inf(), t = cj_nan();
+        double q = cp_inf(), t = cp_nan();
         if (m < a.M - 1) cj_pair_interval(a, er, ec, up, m, q, t);
         const int mp = m - 64;
         double left = __shfl_up(qp, 1), right = __shfl_down(qp, 1);
         const double next = __shfl(q, 0);
         if (lane == 0) left = carry;
         if (lane == 63) right = next;
-        const bool event = qp < cj_inf() && qp < left && qp <= right;
+        const bool event = qp < cp_inf() && qp < left && qp <= right;
         const double dt = fabs(tp - trow);
         // (a lane's intervals ascend, so its own ties keep the earlier; the comparison is the butterfly's all the same)
         if (event && (!(e.max_shift > 0.0) || dt <= e.max_shift) && (dt < bdt || (dt == bdt && mp < bm))) { bdt = dt; bm = mp; }
@@ -499,16 +463,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     // neighbours' q, from which lane 1 restates events_kernel's edge rule on the same operands.
     const bool have = bm != 0x7fffffff;
     const int mw = bm - 1 + lane;
-    double q = cj_inf(), t = cj_nan();
+    double q = cp_inf(), t = cp_nan();
     if (have && lane < 3 && mw >= 0 && mw < a.M - 1) cj_pair_interval(a, er, ec, up, mw, q, t);
     const double left = __shfl_up(q, 1), right = __shfl_down(q, 1);
     if (lane == 1) {
         // still closing where the pair's common span ends: the time is an assigned end of the interval, so == is exact
-        const bool edge = have && ((!(left < cj_inf()) && t == cj_time(bm, a.M, a.T0, a.T1, a.h)) ||
-                                   (!(right < cj_inf()) && t == cj_time(bm + 1, a.M, a.T0, a.T1, a.h)));
+        const bool edge = have && ((!(left < cp_inf()) && t == cj_time(bm, a.M, a.T0, a.T1, a.h)) ||
+                                   (!(right < cp_inf()) && t == cj_time(bm + 1, a.M, a.T0, a.T1, a.h)));
         o[0] = xi; o[1] = xj;
-        o[2] = have ? sqrt(q) : cj_inf();                            // no event (within max_shift): +inf, NaN, as pairs_kernel's
-        o[3] = have ? t : cj_nan();                                  // row without a valid interval
+        o[2] = have ? sqrt(q) : cp_inf();                            // no event (within max_shift): +inf, NaN, as pairs_kernel's
+        o[3] = have ? t : cp_nan();                                  // row without a valid interval
         if (e.info) { e.info[2 * (size_t)r] = have ? bm : -1; e.info[2 * (size_t)r + 1] = edge ? 1 : 0; }
         a.status[r] = MPCX_ST_OK;
     }

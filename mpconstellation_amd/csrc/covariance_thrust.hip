@@ -10,8 +10,10 @@
 // The operation order is fixed (tests/covariance_thrust_reference.py restates it); LDS is ten small matrices whatever K.  The 6-term
 // prefix of every sum over the state is written as covariance_kernel (collision.hip) writes it: with an all-zero exec row and no
 // mass variance every further term is an exact zero and P has mpcx_covariance_batch's bits, satellite by satellite in a mixed batch.
+// The status, the fills, q Q(h), the 6 x 6 block's scaling and the exec row are covariance_device.hpp's, shared with that kernel.
 // No atomics, nothing crosses a workgroup.  The linearisation is enc_linearise (encounter_host.hpp), as everywhere.
 #include "collision_device.hpp"
+#include "covariance_device.hpp"
 #include "encounter_host.hpp"
 
 #include <math.h>
@@ -29,20 +31,17 @@ struct CtArgs {
 
 enum { CT_N = 7, CT_NN = 49, CT_NB = 21, CT_BN = 49, CT_BP = 70 };     // CT_BN, CT_BP: where B_kn and B_kp start in a record
 
-// a satellite's exec row
-struct CtExec { double fm, pm, fp, pp, off; };
-
 // Column c of Sigma of node k of the thrust table u (rows K apart).  Zero when the engine is off (|u| <= u_off; a |u| that is not a
 // number counts as off).  Wave-uniform but for the choice of the column.
-__device__ __forceinline__ void ct_sigma_column(const double *u, size_t K, int k, const CtExec &ex, int c, double &c0, double &c1, double &c2)
+__device__ __forceinline__ void ct_sigma_column(const double *u, size_t K, int k, const GatesRow &ex, int c, double &c0, double &c1, double &c2)
 {
     const double ux = u[k], uy = u[K + k], uz = u[2 * K + k];
     const double un = sqrt(ux * ux + uy * uy + uz * uz);
     c0 = 0.0; c1 = 0.0; c2 = 0.0;
-    if (!(un > ex.off)) return;
+    if (!gates_on(ex, un)) return;
     const double hx = ux / un, hy = uy / un, hz = uz / un;
-    const double a = ex.pm * un, b = ex.pp * un;
-    const double sp = ex.fm * ex.fm + a * a, sq = ex.fp * ex.fp + b * b;
+    double sp, sq;
+    gates_variances(ex, un, sp, sq);
     const double xx = hx * hx, xy = hx * hy, xz = hx * hz, yy = hy * hy, yz = hy * hz, zz = hz * hz;
     const double sxx = sp * xx + sq * (1.0 - xx), sxy = sp * xy - sq * xy, sxz = sp * xz - sq * xz;
     const double syy = sp * yy + sq * (1.0 - yy), syz = sp * yz - sq * yz;
@@ -66,35 +65,21 @@ __global__ __launch_bounds__(64) void covariance_thrust_kernel(CtArgs a)
     const int nn = a.Ks ? a.Ks[s] : a.K;
     const double ta = a.span[2 * s], tb = a.span[2 * s + 1], L = a.units[2 * s], Tu = a.units[2 * s + 1];
     const double qs = a.q ? a.q[s] : 0.0, mv = a.mvar ? a.mvar[s] : 0.0;
-    const double *er = a.exec + (size_t)s * MPCX_NEXEC;
-    const CtExec ex{er[0], er[1], er[2], er[3], er[4]};
+    const GatesRow ex = gates_load(a.exec + (size_t)s * MPCX_NEXEC);
     double pij = pv ? a.P0[(size_t)s * 36 + lo * 6 + hi] : (lane == CT_NN - 1 ? mv : 0.0);     // the upper triangle alone is read
-    int st = MPCX_ST_OK;
-    const double tfv = (tb - ta) / Tu;                               // (enc_tf_kernel's test: no positive finite tf, no linearisation)
-    const bool exec_ok = mv >= 0.0 && cp_finite(mv) && ex.fm >= 0.0 && cp_finite(ex.fm) && ex.pm >= 0.0 && cp_finite(ex.pm) && ex.fp >= 0.0 &&
-                         cp_finite(ex.fp) && ex.pp >= 0.0 && cp_finite(ex.pp) && ex.off >= 0.0 && cp_finite(ex.off);
-    if (nn < 2 || nn > a.K || !(tb > ta) || !(tfv > 0.0) || !cp_finite(tfv)) st = MPCX_ST_BADK;
-    else if (a.dstat[s] != MPCX_ST_OK) st = a.dstat[s];
-    else if (__any(pv && !cp_finite(pij))) st = MPCX_ST_NUMERIC;
-    else if (!exec_ok) st = MPCX_ST_NUMERIC;
+    int st = cov_status(nn, a.K, ta, tb, Tu, a.dstat + s, pv && !cp_finite(pij));
+    if (st == MPCX_ST_OK && !(mv >= 0.0 && cp_finite(mv) && gates_valid(ex))) st = MPCX_ST_NUMERIC;
     double *Ps = a.P + (size_t)s * K * 36, *Ms = a.Pm ? a.Pm + (size_t)s * K * 7 : nullptr;
     if (lane == 0) a.status[s] = st;
     if (st != MPCX_ST_OK) {
-        for (int e = lane; e < a.K * 36; e += 64) Ps[e] = cp_nan();
-        if (Ms)
-            for (int e = lane; e < a.K * 7; e += 64) Ms[e] = cp_nan();
+        cov_fill(Ps, lane, 0, a.K * 36, cp_nan());
+        if (Ms) cov_fill(Ms, lane, 0, a.K * 7, cp_nan());
         return;
     }
-    for (int e = nn * 36 + lane; e < a.K * 36; e += 64) Ps[e] = 0.0;  // columns past the satellite's count
-    if (Ms)
-        for (int e = nn * 7 + lane; e < a.K * 7; e += 64) Ms[e] = 0.0;
+    cov_fill(Ps, lane, nn * 36, a.K * 36, 0.0);                      // columns past the satellite's count
+    if (Ms) cov_fill(Ms, lane, nn * 7, a.K * 7, 0.0);
     const double h = (tb - ta) / (double)(nn - 1);
-    // q Q(h), entry (lo, hi): [[h^3/3 I, h^2/2 I], [h^2/2 I, h I]] on the position / velocity block, nothing on the mass
-    double Qe = 0.0;
-    if (hi < 3) Qe = lo == hi ? h * h * h / 3.0 : 0.0;
-    else if (lo < 3) Qe = hi - 3 == lo ? h * h / 2.0 : 0.0;
-    else if (hi < 6) Qe = lo == hi ? h : 0.0;
-    const double qQ = qs * Qe;
+    const double qQ = qs * cov_noise_entry(lo, hi, h);
     const double V = L / Tu;
     const double Di = bi < 3 ? L : (bi < 6 ? V : 1.0);               // D of the row of this lane's 7 x 3 entry
     const double *srec = a.stage + (size_t)s * (K - 1) * MPCX_STAGE_DOUBLES, *us = a.U + (size_t)s * 3 * K;
@@ -117,7 +102,7 @@ __global__ __launch_bounds__(64) void covariance_thrust_kernel(CtArgs a)
         ct_sigma_column(us, K, k + 1, ex, bc, t0, t1, t2);
         if (own) {                                                   // Phi~ = D A D^-1, D = diag(L, L, L, V, V, V, 1)
             const double f = rec[lane];
-            double v = i < 3 && j >= 3 ? f * Tu : (i >= 3 && j < 3 ? f / Tu : f);      // (the 6 x 6 block as covariance_kernel forms it)
+            double v = cov_scale6(f, i, j, Tu);
             if (j == 6 && i < 6) v = i < 3 ? f * L : f * V;
             if (i == 6 && j < 6) v = j < 3 ? f / L : f / V;
             phi[lane] = v;
@@ -174,26 +159,6 @@ __global__ __launch_bounds__(64) void covariance_thrust_kernel(CtArgs a)
     }
 }
 
-// workspace of the _dev call: the linearisation's, nothing else
-struct CtWorkspace : LinWorkspace {
-    size_t bytes;
-    CtWorkspace(void *base, int S, int K)
-    {
-        Carver c(base);
-        carve(c, S, K);
-        bytes = c.bytes();
-    }
-};
-
-static int ct_check(mpcx_ctx *ctx, int S, int K, int flags, double max_step)
-{
-    if (S < 1 || K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "covariance_thrust: need S>=1, K>=2");
-    if (!(max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "covariance_thrust: max_step must be > 0");
-    if (flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
-        return ctx_fail(ctx, MPCX_E_BADARG, "covariance_thrust: flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
-    return ctx_check_atmosphere(ctx, flags, "covariance_thrust");
-}
-
 }  // namespace mpcx
 
 using namespace mpcx;
@@ -201,7 +166,7 @@ using namespace mpcx;
 extern "C" size_t mpcx_covariance_thrust_workspace_bytes(int S, int K)
 {
     if (S < 1 || K < 2) return 0;
-    return CtWorkspace(nullptr, S, K).bytes;
+    return LinOnlyWorkspace(nullptr, S, K).bytes;               // the linearisation's, nothing else
 }
 
 extern "C" int mpcx_covariance_thrust_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U,
@@ -210,12 +175,12 @@ extern "C" int mpcx_covariance_thrust_batch_dev(mpcx_ctx *ctx, int S, int K, con
                                                 double *Pm, int32_t *status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (int rc = ct_check(ctx, S, K, flags, max_step)) return rc;
+    if (int rc = cov_check(ctx, "covariance_thrust", S, K, flags, max_step)) return rc;
     if (!X || !U || !units || !span || !consts || !P0 || !exec || !P || !status || !workspace)
         return ctx_fail(ctx, MPCX_E_BADARG, "covariance_thrust: X, U, units, span, consts, P0, exec, P, status and workspace are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
-    const CtWorkspace ws(workspace, S, K);
+    const LinOnlyWorkspace ws(workspace, S, K);
     EncProblem lin{};
     lin.S = S; lin.K = K; lin.Ks = Ks; lin.Y = X; lin.U = U; lin.units = units; lin.span = span; lin.consts = consts;
     lin.flags = flags; lin.max_step = max_step;
@@ -232,7 +197,7 @@ extern "C" int mpcx_covariance_thrust_batch(mpcx_ctx *ctx, int S, int K, const i
                                             int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    if (int rc = ct_check(ctx, S, K, flags, max_step)) return rc;
+    if (int rc = cov_check(ctx, "covariance_thrust", S, K, flags, max_step)) return rc;
     if (!X || !U || !units || !span || !consts || !P0 || !exec || !P || !status)
         return ctx_fail(ctx, MPCX_E_BADARG, "covariance_thrust: X, U, units, span, consts, P0, exec, P and status are required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));

@@ -1,6 +1,7 @@
 // encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint*, mpcx_avoidance_refine*,
 // mpcx_collision_window_sensitivity*, mpcx_avoidance_window* and mpcx_avoidance_window_refine* share, and the linearisation step they share with
-// mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver.
+// mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver, and the set of
+// trajectories that mpcx_avoidance_refine*, mpcx_avoidance_window_refine* and mpcx_collision_probability_mc* fly again (FlightSet).
 #pragma once
 #include "collision_device.hpp"                                     // CpSide
 #include "mpcx_host.hpp"
@@ -94,6 +95,27 @@ struct Carver {
     size_t bytes() const { return (size_t)(p - base); }
 };
 
+// A set of V trajectories (rows of K nodes) flown again from their first node under a thrust table, as the refine loops and the Monte
+// Carlo fly them: what the flight reads -- node counts, first nodes, tf, end_tau = 1, constants, the table Ut [V][3][K] -- and what it
+// writes: Yp [V][7][K], status and step count.  A plain set of pointers: kernels take it by value.
+struct FlightSet {
+    int32_t *Ks, *pst, *nsteps;
+    double *y0, *Ut, *tf, *end_tau, *consts, *Yp;
+    // all nine regions, for a caller that owns them all
+    void carve(Carver &c, size_t V, size_t K)
+    {
+        Ks = c.take<int32_t>(V); pst = c.take<int32_t>(V); nsteps = c.take<int32_t>(V);
+        y0 = c.take<double>(V * 7); Ut = c.take<double>(V * 3 * K); tf = c.take<double>(V); end_tau = c.take<double>(V);
+        consts = c.take<double>(V * MPCX_NCONST); Yp = c.take<double>(V * 7 * K);
+    }
+    // the flight: every trajectory over its whole table under the model `flags` with the step limit max_step
+    int fly(mpcx_ctx *ctx, int V, int K, int flags, double max_step, hipStream_t stream) const
+    {
+        return mpcx_propagate_batch_ragged_dev(ctx, V, K, Ks, y0, tf, consts, flags, MPCX_CTRL_SEQUENCE, Ut, K, Ks, end_tau, max_step, Yp, pst, nsteps,
+                                               stream);
+    }
+};
+
 // the regions every linearising call's workspace starts with: [stage S (K-1) records][tf S][discretiser status S]
 struct LinWorkspace {
     double *stage, *tf;
@@ -105,6 +127,26 @@ struct LinWorkspace {
         dstat = c.take<int32_t>((size_t)S);
     }
 };
+
+// a workspace that is the linearisation's regions and nothing else, with its size (mpcx_covariance_thrust_batch_dev's)
+struct LinOnlyWorkspace : LinWorkspace {
+    size_t bytes;
+    LinOnlyWorkspace(void *base, int S, int K)
+    {
+        Carver c(base);
+        carve(c, S, K);
+        bytes = c.bytes();
+    }
+};
+
+// the argument tests of both covariance chains (`name`: covariance or covariance_thrust)
+inline int cov_check(mpcx_ctx *ctx, const char *name, int S, int K, int flags, double max_step)
+{
+    if (S < 1 || K < 2) return enc_fail(ctx, name, "need S>=1, K>=2");
+    if (!(max_step > 0.0)) return enc_fail(ctx, name, "max_step must be > 0");
+    if (flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO)) return enc_fail(ctx, name, "flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
+    return ctx_check_atmosphere(ctx, flags, name);
+}
 
 // The linearisation about (p.Y, p.U) under p.flags, p.max_step: tf [S], the span in each satellite's own time unit (1 where that is
 // not positive and finite: the discretiser's step-size control never sees a value it was not written for, and the kernels that read
