@@ -382,7 +382,7 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
                 const int passes = 1 + ((delta_w == 0.0 && gr[GR_SUM] > kRefineTw) ? o.n_refine : 0);
                 if (passes > 1 && !ns_kept) newton_blocks<true>(s, sd, (double *)&w, mu, delta_w, lane);
                 refined_prev = passes > 1;
-                bool okl = riccati_factor(s, sd, w, lane, true, passes > 1);     // (a local breakdown is reported through the border's reduction)
+                bool okl = riccati_factor(s, sd, w, lane, passes > 1);     // (a local breakdown is reported through the border's reduction)
                 bool ok = true;
                 for (int pass = 0; pass < passes && ok; ++pass) {
                     if (okl && pass > 0) { reduced_residual(s, sd, (double *)&w, lane); sweep_backward(s, sd, w, 0, 1, lane); }
@@ -431,7 +431,7 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
             bool ok = tp_cmd_factor(s, sd, g_tp, lane, passes > 1);       // every segment's factorisation + fused backward sweeps, side by side
             if (g_tp.dead) break;                                         // (a workgroup of the satellite did not answer: MPCX_ST_NUMERIC)
 #else
-            bool ok = riccati_factor(s, sd, w, lane, true, passes > 1);   // factorisation + backward sweep of all 8 channels
+            bool ok = riccati_factor(s, sd, w, lane, passes > 1);   // factorisation + backward sweep of all 8 channels
 #endif
             PT_END(2)
 #ifdef MPCX_ITER_LOG

@@ -119,6 +119,234 @@ __device__ __forceinline__ void load_m_lower(const double *Pn, const double *D, 
     }
 }
 
+// ---- the pieces of one factorisation node that the one-wave form (riccati_factor) and the two roles of the two-wave form
+// ---- (riccati_factor2) share: each expression of a node stands here once, which is what keeps the builds' bits the same
+template <bool B> struct BoolC {         // a compile-time flag passed to a generic lambda, or where a run-time bool is taken too
+    static constexpr bool value = B;
+    __device__ constexpr operator bool() const { return B; }
+};
+
+// Elimination step pp of the LDL^T of a symmetric 7 x 7 matrix in registers (m: its lower triangle, row by row) with the
+// reciprocal rdp of the pivot: column pp becomes the unit lower factor's, the trailing triangle is updated.
+__device__ __forceinline__ void ldl7_eliminate(double (&m)[28], int pp, double rdp)
+{
+    double col[7];
+#pragma unroll
+    for (int i = pp + 1; i < 7; ++i) col[i] = m[i * (i + 1) / 2 + pp];
+#pragma unroll
+    for (int i = pp + 1; i < 7; ++i) {
+        const double lip = col[i] * rdp;
+#pragma unroll
+        for (int j = pp + 1; j <= i; ++j) m[i * (i + 1) / 2 + j] -= lip * col[j];
+        m[i * (i + 1) / 2 + pp] = lip;
+    }
+}
+// ... of M = D + Pn: rd[pp] = 1 / pivot; returns the pivot (not positive: breakdown).  Same arithmetic as the oracle's ldl_solve7.
+__device__ __forceinline__ double ldl7_pivot(double (&m)[28], double (&rd)[7], int pp)
+{
+    const double d = m[pp * (pp + 1) / 2 + pp];
+    rd[pp] = rcp_pos(d);
+    ldl7_eliminate(m, pp, rd[pp]);
+    return d;
+}
+
+// P3: x = Lt^-1 c (unit lower, the strict part of m) for the lane's column c of [Pn | I]: lanes 0..6 a column of Pn (xc: the
+// lane, clamped), with IDENT lanes 7..13 a column of the identity, by select.
+template <bool IDENT>
+__device__ __forceinline__ void fwd_subst7(const double *Pn, const double (&m)[28], int lane, int xc, double (&x)[7])
+{
+#pragma unroll
+    for (int pp = 0; pp < 7; ++pp) {
+        const double pv = Pn[pp * PS + xc];
+        if constexpr (IDENT) x[pp] = (lane < 7) ? pv : (lane - 7 == pp ? 1.0 : 0.0);
+        else x[pp] = pv;
+    }
+#pragma unroll
+    for (int pp = 1; pp < 7; ++pp)
+#pragma unroll
+        for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
+}
+
+// P4: an entry a^T R b of X^T R X with R = diag(rd), a and b columns of [X1 | X2]
+__device__ __forceinline__ double xrx7(const double (&a)[7], const double (&rd)[7], const double (&b)[7])
+{
+    double acc = 0.0;
+#pragma unroll
+    for (int l = 0; l < 7; ++l) acc += a[l] * (rd[l] * b[l]);
+    return acc;
+}
+
+// Operand prefetch: node k's (A, Bn | Bpm | Wx, Wu, D, SX) -> registers -> LDS buffer.  Three branch-free loads per lane,
+// elements lane, lane + 64 and lane + 128 of the fetch order [A 49 | Bn 21 | Bpm 21 | Wx 49 | Wu 9 | D 7 | SX 8]: A, Bn are the
+// head of stage record k, Bpm = B_kp of record k-1 (same offset), Wx (expanded from its compact form) | Wu | D | SX from the
+// Newton-block record; what node k does not have (no dynamics at K-1, no Bpm at 0) is zeroed when stashed.
+struct OpsPrefetch {
+    double pre[3] = {0.0, 0.0, 0.0};
+    int e1, e2, wx1, src2;               // the lane's second and third element, their sources in the Newton record
+    int slot0, slot1, slot2;             // byte offsets of the lane's three elements inside StageOps
+    // element q of the 7 x 7 stage Hessian in the compact Newton record: its 3x3 block entry, the common diagonal value, or
+    // the record's zero
+    static __device__ __forceinline__ int wx_src(int q)
+    {
+        const int i = q / 7, j = q - 7 * i;
+        return (i < 3 && j < 3) ? N_W3 + i * 3 + j : (i == j ? N_DIAG : N_ZERO);
+    }
+    static __device__ __forceinline__ int ops_slot(int e)
+    {
+        if (e < 49) return (int)offsetof(StageOps, F) + 8 * ((e / 7) * FS + e % 7);
+        if (e < 70) return (int)offsetof(StageOps, Bn) + 8 * (e - 49);
+        if (e < 91) return (int)offsetof(StageOps, Bpm) + 8 * (e - 70);
+        if (e < 140) return (int)offsetof(StageOps, G2) + 8 * (((e - 91) / 7) * FS + (e - 91) % 7);
+        if (e < 149) return (int)offsetof(StageOps, Wu) + 8 * (e - 140);
+        if (e < 156) return (int)offsetof(StageOps, D) + 8 * (e - 149);
+        return (int)offsetof(StageOps, SX) + 8 * ((e < OPS_IN) ? e - 156 : 0);
+    }
+    __device__ __forceinline__ explicit OpsPrefetch(int lane) : e1(lane + 64), e2(lane + 128)
+    {
+        wx1 = (e1 >= 91) ? wx_src(e1 - 91) : 0;
+        src2 = (e2 < 140) ? wx_src(e2 - 91) : (e2 < OPS_IN ? N_WU + (e2 - 140) : 0);
+        slot0 = ops_slot(lane); slot1 = ops_slot(e1); slot2 = ops_slot(e2);
+    }
+    __device__ __forceinline__ void fetch(const Sat &s, int lane, int k)
+    {
+        const int K = s.K;
+        cgf64 *stk = s.stage + (size_t)(k <= K - 2 ? k : K - 2) * MPCX_STAGE_DOUBLES;
+        cgf64 *stm = s.stage + (size_t)(k >= 1 ? k - 1 : 0) * MPCX_STAGE_DOUBLES;
+        cwf64 *nb = s.nb + (size_t)k * NB_N;
+#ifdef MPCX_WS_LDS
+        // (stage records in global memory, the Newton record in LDS: the lane's second element comes from one or the other)
+        cgf64 *pg = (e1 < 70) ? stk + e1 : stm + (e1 < 91 ? e1 : 70);
+        const double g1 = *pg, l1 = nb[wx1];
+        pre[0] = stk[lane]; pre[1] = (e1 < 91) ? g1 : l1; pre[2] = nb[src2];
+#else
+        cgf64 *p1 = (e1 < 70) ? stk + e1 : (e1 < 91) ? stm + e1 : nb + wx1;
+        cgf64 *p2 = nb + src2;
+        pre[0] = stk[lane]; pre[1] = xld(p1); pre[2] = xld(p2);
+#endif
+    }
+    // dynk: node k has dynamics (k <= K - 2), a BoolC where the caller knows it at compile time
+    template <typename DYN>
+    __device__ __forceinline__ void stash(StageOps &o, int k, DYN dyn) const
+    {
+        const bool dynk = dyn;
+        char *base = (char *)&o;
+        *(double *)(base + slot0) = dynk ? pre[0] : 0.0;
+        *(double *)(base + slot1) = ((e1 < 70) ? dynk : (e1 < 91) ? (k >= 1) : true) ? pre[1] : 0.0;
+        if (e2 < OPS_IN) *(double *)(base + slot2) = (e2 < 149 || e2 >= 156 || dynk) ? pre[2] : 0.0;
+    }
+};
+
+// What a lane does in the phases of a node (one lane per matrix element)
+struct FactorLanes {
+    int mi, mj;                          // (row, column) of a 7 x 7 matrix, lanes 0..48
+    int xc;                              // column of [Pn | I] this lane substitutes (lanes 0..13)
+    // P1: lanes 0..20 element e of Bh = A Bpm + Bn (into F), lanes 32..52 element e of Wx Bpm (into G2), one body
+    bool p1_bh, p1_wx;
+    int p1_e, p1_i, p1_j;
+    // P5: first round task lane of the 70 of T = Pt F; second round lanes 0..5 the other 6 (row 6, columns 4..9),
+    // lanes 6..35 element (r, j) of Bpm^T G2 (j < 7: Quy0, j >= 7: Quu0)
+    int p5_i, p5_j;
+    bool p5b_t, p5b_wu, p5b_qy;
+    int p5b_r, p5b_j, p5b_sa;
+    // P6: lane t < 55 is entry (i, j), i <= j, of the 10 x 10 matrix S = F^T T
+    int p6_i, p6_j;
+    bool p6_qyy, p6_quy, p6_quu;
+    __device__ __forceinline__ explicit FactorLanes(int lane)
+    {
+        mi = lane / 7; mj = lane - 7 * mi;
+        xc = (lane < 7) ? lane : 6;
+        p1_bh = lane < 21; p1_wx = lane >= 32 && lane < 53;
+        p1_e = p1_wx ? lane - 32 : (p1_bh ? lane : 0); p1_i = p1_e / 3; p1_j = p1_e - 3 * p1_i;
+        p5_i = lane / FS; p5_j = lane - FS * p5_i;
+        p5b_t = lane < 6;
+        const bool p5b_g = lane >= 6 && lane < 36;
+        const int p5b_q = p5b_g ? lane - 6 : 0;
+        p5b_r = p5b_q / FS;
+        p5b_j = p5b_t ? 4 + lane : p5b_q - FS * p5b_r;
+        p5b_sa = p5b_t ? 1 : 3;
+        p5b_wu = p5b_g && p5b_j >= 7; p5b_qy = p5b_g && p5b_j < 7;
+        p6_i = 0; p6_j = 0;
+        { int tt = lane; for (int i = 0; i < FS; ++i) { const int n = FS - i; if (tt < n) { p6_i = i; p6_j = i + tt; break; } tt -= n; } }
+        const bool p6_on = lane < 55;
+        p6_qyy = p6_on && p6_j < 7; p6_quy = p6_on && p6_i < 7 && p6_j >= 7; p6_quu = p6_on && p6_i >= 7;
+    }
+};
+
+// P1: Bh = A Bpm + Bn ; WxBp = Wx Bpm  (dyn: the node has dynamics; without, Bh = 0)
+template <typename DYN>
+__device__ __forceinline__ void factor_p1(StageOps &o, Scratch &w, const FactorLanes &r, int lane, DYN dyn)
+{
+    const double dot = dotN<7>((r.p1_wx ? o.G2 : o.F) + r.p1_i * FS, 1, o.Bpm + r.p1_j, 3);
+    const double val = r.p1_wx ? dot : (dyn ? o.Bn[r.p1_e] + dot : 0.0);
+    double *dst = r.p1_wx ? &o.G2[r.p1_i * FS + 7 + r.p1_j] : (r.p1_bh ? &o.F[r.p1_i * FS + 7 + r.p1_j] : &w.sink[lane]);
+    *dst = val;
+}
+
+// P5: T = Pt F (70 dot products of one pattern: 64 in the first round, 6 in the second) and
+//     [Quy0 | Quu0 - Wu] = Bpm^T G2 (30, second round, lanes 6..35)
+__device__ __forceinline__ void factor_p5(StageOps &o, Scratch &w, const FactorLanes &r, int lane)
+{
+    w.T[r.p5_i * FS + r.p5_j] = dotN<7>(o.Pt + r.p5_i * 7, 1, o.F + r.p5_j, FS);
+    const double *a = r.p5b_t ? o.Pt + 42 : o.Bpm + r.p5b_r;
+    const double *b = (r.p5b_t ? o.F : o.G2) + r.p5b_j;
+    double acc = 0.0;
+#pragma unroll
+    for (int l = 0; l < 7; ++l) acc += a[l * r.p5b_sa] * b[l * FS];
+    const double *add = r.p5b_wu ? &o.Wu[r.p5b_r * 3 + r.p5b_j - 7] : &w.zero;
+    double *dst = r.p5b_t ? &w.T[6 * FS + r.p5b_j] : (r.p5b_wu ? &w.Quu[r.p5b_r * 3 + r.p5b_j - 7] : (r.p5b_qy ? &w.Quy[r.p5b_r * 7 + r.p5b_j] : &w.sink[lane]));
+    *dst = *add + acc;
+}
+
+// P6: the upper triangle of S = F^T T (55 dot products of one pattern): Qyy = Wx + A^T Pt A (upper part only, read
+//     back through (min, max)), Quy += Bh^T Pt A, Quu += Bh^T Pt Bh (upper part: all the 3x3 inverse reads)
+__device__ __forceinline__ void factor_p6(StageOps &o, Scratch &w, const FactorLanes &r, int lane)
+{
+    const double sdot = dotN<7>(o.F + r.p6_i, FS, w.T + r.p6_j, FS);
+    double *dst = r.p6_qyy ? &w.Qyy[r.p6_i * 7 + r.p6_j] : (r.p6_quy ? &w.Quy[(r.p6_j - 7) * 7 + r.p6_i] : (r.p6_quu ? &w.Quu[(r.p6_i - 7) * 3 + r.p6_j - 7] : &w.sink[lane]));
+    const double *add = r.p6_qyy ? &o.G2[r.p6_i * FS + r.p6_j] : dst;
+    *dst = *add + sdot;
+}
+
+// P7-P9: every lane inverts the 3x3 itself (false: a pivot of Q_uu is not positive); P_k = sym(Qyy - Quy^T Qi Quy) into Pk
+// (row stride PS) straight from the lane's own two columns of Quy (no exchange of the gain on the way); the gain Kg = Qi Quy
+// (lanes 0..20) goes to the node's operand buffer.  kg and qv = element lane < 9 of Q_uu^-1 are handed back: where they are
+// stored for the sweeps is the caller's business.
+__device__ __forceinline__ bool factor_p79(StageOps &o, Scratch &w, const FactorLanes &r, int lane, double *Pk, double &kg, double &qv)
+{
+    double Qi[9];
+    const bool ok = inv3_spd(w.Quu, Qi);
+    if (lane < 49) {
+        const int lo = (r.mi < r.mj) ? r.mi : r.mj, hi = (r.mi < r.mj) ? r.mj : r.mi;
+        double qi[3], qj[3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) { qi[l] = w.Quy[l * 7 + lo]; qj[l] = w.Quy[l * 7 + hi]; }
+        // (qi, qj) = columns (min, max) of Quy: lanes (i,j) and (j,i) evaluate the same expression, P_k is
+        // symmetric by construction; Qyy is symmetrised through the same (min, max) read (rounding-level asymmetry
+        // of A^T (Pt A) otherwise)
+        double a1 = w.Qyy[lo * 7 + hi];
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            const double kj = Qi[l * 3] * qj[0] + Qi[l * 3 + 1] * qj[1] + Qi[l * 3 + 2] * qj[2];     // Kg(l, hi)
+            a1 -= qi[l] * kj;
+        }
+        Pk[r.mi * PS + r.mj] = a1;
+    }
+    // (Qi is indexed with constants only and picked by selects: a register array indexed by a lane-dependent value
+    //  is placed in scratch memory, and its store / load pair would sit behind an s_waitcnt vmcnt(0) in every node)
+    const bool on21 = lane < 21;
+    const int l21 = on21 ? lane : 0;
+    const int rr = l21 / 7, c = l21 - 7 * rr;
+    const double q0 = w.Quy[c], q1 = w.Quy[7 + c], q2 = w.Quy[14 + c];
+    const double k0 = Qi[0] * q0 + Qi[1] * q1 + Qi[2] * q2, k1 = Qi[3] * q0 + Qi[4] * q1 + Qi[5] * q2,
+                 k2 = Qi[6] * q0 + Qi[7] * q1 + Qi[8] * q2;
+    kg = (rr == 0) ? k0 : (rr == 1 ? k1 : k2);
+    *(on21 ? &o.Kg[lane] : &w.sink[lane]) = kg;
+    qv = Qi[0];
+#pragma unroll
+    for (int e = 1; e < 9; ++e) qv = (lane == e) ? Qi[e] : qv;
+    return ok;
+}
+
 #ifdef MPCX_PHASE_TIMING
 #define FT_DECL unsigned long long ft0_ = __builtin_amdgcn_s_memtime(), ft1_;
 #define FT_MARK(i) { ft1_ = __builtin_amdgcn_s_memtime(); if (lane == 0) sd.fpt[i] += ft1_ - ft0_; ft0_ = ft1_; }
@@ -174,6 +402,45 @@ __device__ __forceinline__ ChanIn chan_mask(const ChanRaw &cr, int c, int r, boo
     ci.gx = c0 ? cr.gx : 0.0; ci.gu = (c0 && r < 3) ? cr.gu : 0.0; ci.rho = c0 ? cr.rho : 0.0;
     ci.aff = (act && c <= 1) ? cr.aff : 0.0;
     return ci;
+}
+
+// ---- one node of the backward linear-term sweep, lane group = channel, lane r = component ----
+//   t = p+ - G (rho + p+) + Pt aff ;  qu = gu + Bpm^T gx + Bh^T t ;  p = gx + A^T t - Kg^T qu
+// in sweep_backward and in the sweep fused into both factorisations.  Shared: t's accumulation and, for the fused sweeps, the
+// reads of the lane's rows and columns out of an operand buffer.  The tail (t -> qu, p) stands in each of the four places: as
+// a function of its own it compiles to other LDS instructions in riccati_factor2 and a peeled loop in the LDS-resident
+// sweep_backward (profiles/factor_shared.txt), so "same arithmetic as sweep_backward" is still a promise there.
+struct SweepCols { double A[7], Bpm[7], Bh[7], Kg[3]; };
+
+// t's accumulation over the columns q0 .. q1-1 (in pieces where the caller spreads it over other work), v = rho + p+
+__device__ __forceinline__ void sweep_t_accum(double &t, const double (&Grow)[7], const double (&Ptrow)[7], double v, double aff, int q0, int q1)
+{
+#pragma unroll
+    for (int q = q0; q < q1; ++q) t += -Grow[q] * gshfl8(v, q) + Ptrow[q] * gshfl8(aff, q);
+}
+
+// The fused sweep's operands of a node whose matrices sit complete in an operand buffer: rows rr of G and Pt ...
+__device__ __forceinline__ void sweep_rows_of(const StageOps &o, int rr, double (&Grow)[7], double (&Ptrow)[7])
+{
+#pragma unroll
+    for (int q = 0; q < 7; ++q) { Grow[q] = o.G[rr * 7 + q]; Ptrow[q] = o.Pt[rr * 7 + q]; }
+}
+// ... and columns rr of A and Kg, r3 of Bpm and Bh
+__device__ __forceinline__ void sweep_cols_of(const StageOps &o, int rr, int r3, SweepCols &m)
+{
+#pragma unroll
+    for (int q = 0; q < 7; ++q) { m.A[q] = o.F[q * FS + rr]; m.Bpm[q] = o.Bpm[q * 3 + r3]; m.Bh[q] = o.F[q * FS + 7 + r3]; }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) m.Kg[q] = o.Kg[q * 7 + rr];
+}
+
+// The terminal node's inputs of the fused sweep (masked from the branch-free fetch): no dynamics terms, and the unit channels
+// 2.. carry their terminal gradients
+__device__ __forceinline__ void terminal_chan_inputs(ChanIn &cur, const SatData &sd, int c, int rr, bool act)
+{
+    const double tg = (c == 2) ? sd.avt[rr] : sd.ta[c >= 3 ? c - 3 : 0][rr];
+    cur.gx = (act && c >= 2) ? tg : cur.gx;
+    cur.rho = 0.0; cur.aff = 0.0;
 }
 
 // Stiff stage terms (excess weight ex above kStageCap of the position term, direction a, and of the thrust ball, direction
@@ -264,20 +531,19 @@ struct TpRange { int lo, hi; bool last; double *Wout; };
 #define RF_HI rg.hi
 #define RF_LO rg.lo
 #define RF_LAST rg.last
-#define RF_GOOD w.good_flag
 #else
 #define RF_ARGS
 #define RF_HI K
 #define RF_LO 0
 #define RF_LAST true
-#define RF_GOOD w.good_flag
 #endif
 // The same factorisation shared by the two waves of a small-batch workgroup (role 0 / role 1), one hardware barrier per node.
 // Role 0 keeps what the next node waits for -- the critical chain P_{k+1} -> LDL^T -> X1 -> Pt -> T = Pt F -> S = F^T T ->
 // Q_uu^-1 -> P_k -- and the operand prefetch; role 1 takes everything else off that chain: its own (redundant) LDL^T for
 // X2, the blocks G and Minv the sweeps need, the fused backward sweep of the node before (k+1, whose matrices sit complete
-// in another operand buffer) and all stores to the factor record.  Every element is computed by the same expressions as in
-// the one-wave form (bit-identical results: the library is built with -ffp-contract=on).  ~7 750 -> ~4 800 cycles per node for a wave that is alone on its
+// in another operand buffer) and all stores to the factor record.  Both roles call the node's pieces that the one-wave form
+// calls (above; the sweep's tail apart), so every element comes from the same expressions: bit-identical results (the library
+// is built with -ffp-contract=on).  ~7 750 -> ~4 800 cycles per node for a wave that is alone on its
 // SIMD (64 satellites on a 1024-SIMD chip: the small-batch regime of BASELINE configs[1]).
 __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scratch &w, int lane, int role, bool keep_pt RF_ARGS)
 {
@@ -288,73 +554,19 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
     const bool sact = sr < 7;
     const int srr = (sr < 7) ? sr : 6, sr3 = (sr < 3) ? sr : 2;
     const int sink_e = s.o_sink + lane;
-    const int mi = lane / 7, mj = lane - 7 * mi;
-    const int xc = (lane < 7) ? lane : 6;
-    // ---- role 0: operand prefetch (as in the one-wave form, three buffers) ----
-    double pre[3] = {0.0, 0.0, 0.0};
-    const int e1 = lane + 64, e2 = lane + 128;
-    auto wx_src = [](int q) -> int {
-        const int i = q / 7, j = q - 7 * i;
-        return (i < 3 && j < 3) ? N_W3 + i * 3 + j : (i == j ? N_DIAG : N_ZERO);
-    };
-    const int wx1 = (e1 >= 91) ? wx_src(e1 - 91) : 0;
-    const int src2 = (e2 < 140) ? wx_src(e2 - 91) : (e2 < OPS_IN ? N_WU + (e2 - 140) : 0);
-    auto fetch = [&](int k) {
-        cgf64 *stk = s.stage + (size_t)(k <= K - 2 ? k : K - 2) * MPCX_STAGE_DOUBLES;
-        cgf64 *stm = s.stage + (size_t)(k >= 1 ? k - 1 : 0) * MPCX_STAGE_DOUBLES;
-        cwf64 *nb = s.nb + (size_t)k * NB_N;
-#ifdef MPCX_WS_LDS
-        // (stage records in global memory, the Newton record in LDS: the lane's second element comes from one or the other)
-        cgf64 *pg = (e1 < 70) ? stk + e1 : stm + (e1 < 91 ? e1 : 70);
-        const double g1 = *pg, l1 = nb[wx1];
-        pre[0] = stk[lane]; pre[1] = (e1 < 91) ? g1 : l1; pre[2] = nb[src2];
-#else
-        cgf64 *p1 = (e1 < 70) ? stk + e1 : (e1 < 91) ? stm + e1 : nb + wx1;
-        cgf64 *p2 = nb + src2;
-        pre[0] = stk[lane]; pre[1] = xld(p1); pre[2] = xld(p2);
-#endif
-    };
-    auto ops_slot = [](int e) -> int {
-        if (e < 49) return (int)offsetof(StageOps, F) + 8 * ((e / 7) * FS + e % 7);
-        if (e < 70) return (int)offsetof(StageOps, Bn) + 8 * (e - 49);
-        if (e < 91) return (int)offsetof(StageOps, Bpm) + 8 * (e - 70);
-        if (e < 140) return (int)offsetof(StageOps, G2) + 8 * (((e - 91) / 7) * FS + (e - 91) % 7);
-        if (e < 149) return (int)offsetof(StageOps, Wu) + 8 * (e - 140);
-        if (e < 156) return (int)offsetof(StageOps, D) + 8 * (e - 149);
-        return (int)offsetof(StageOps, SX) + 8 * ((e < OPS_IN) ? e - 156 : 0);
-    };
-    const int slot0 = ops_slot(lane), slot1 = ops_slot(e1), slot2 = ops_slot(e2);
-    auto stash = [&](StageOps &o, int k) {
-        const bool dynk = (k <= K - 2);
-        char *base = (char *)&o;
-        *(double *)(base + slot0) = dynk ? pre[0] : 0.0;
-        *(double *)(base + slot1) = ((e1 < 70) ? dynk : (e1 < 91) ? (k >= 1) : true) ? pre[1] : 0.0;
-        if (e2 < OPS_IN) *(double *)(base + slot2) = (e2 < 149 || e2 >= 156 || dynk) ? pre[2] : 0.0;
-    };
-    if (role == 1) {                     // (the operand prefetch is the second wave's: it has the slack)
-        fetch(RF_HI - 1);
-        stash(w.ops[(RF_HI - 1) % 3], RF_HI - 1);
+    const FactorLanes ln(lane);
+    const int mi = ln.mi, mj = ln.mj;
+    OpsPrefetch pf(lane);
+    if (role == 1) {                     // (the operand prefetch is the second wave's: it has the slack; three buffers)
+        pf.fetch(s, lane, RF_HI - 1);
+        pf.stash(w.ops[(RF_HI - 1) % 3], RF_HI - 1, RF_HI - 1 <= K - 2);
         if (RF_LAST && lane < 49) w.ops[(RF_HI - 1) % 3].G2[(lane / 7) * FS + lane % 7] = sd.WxK[lane];
     } else {
         if (lane < PN_N) w.Pn2[RF_HI & 1][lane] = 0.0;                       // P_K = 0 (read as "P of node k+1" by node K-1)
         if (lane == 0) { w.zero = 0.0; w.good_flag = 1; }
     }
     WG_BARRIER();
-    // ---- role 0 lane roles (P1, P5, P6: as in the one-wave form) ----
-    const bool p1_bh = lane < 21, p1_wx = lane >= 32 && lane < 53;
-    const int p1_e = p1_wx ? lane - 32 : (p1_bh ? lane : 0), p1_i = p1_e / 3, p1_j = p1_e - 3 * p1_i;
-    const int p5_i = lane / FS, p5_j = lane - FS * p5_i;
-    const bool p5b_t = lane < 6, p5b_g = lane >= 6 && lane < 36;
-    const int p5b_q = p5b_g ? lane - 6 : 0;
-    const int p5b_r = p5b_q / FS;
-    const int p5b_j = p5b_t ? 4 + lane : p5b_q - FS * p5b_r;
-    const int p5b_sa = p5b_t ? 1 : 3;
-    const bool p5b_wu = p5b_g && p5b_j >= 7, p5b_qy = p5b_g && p5b_j < 7;
-    int p6_i = 0, p6_j = 0;
-    { int tt = lane; for (int i = 0; i < FS; ++i) { const int n = FS - i; if (tt < n) { p6_i = i; p6_j = i + tt; break; } tt -= n; } }
-    const bool p6_on = lane < 55;
-    const bool p6_qyy = p6_on && p6_j < 7, p6_quy = p6_on && p6_i < 7 && p6_j >= 7, p6_quu = p6_on && p6_i >= 7;
-    // ---- role 1: the fused backward sweep, one node behind (same arithmetic as sweep_backward) ----
+    // ---- role 1: the fused backward sweep, one node behind ----
     ChanIn cur{0.0, 0.0, 0.0, 0.0};
     ChanRaw nraw{0.0, 0.0, 0.0, 0.0};
     const int scl = RF_LAST ? sc : (sc == 0 ? 1 : 2);        // the group's channel as chan_fetch / chan_mask know it (2: no stage data)
@@ -370,46 +582,39 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
     auto sweep_node = [&](const StageOps &o, int j) {        // node j's p, qu from its complete operand buffer
         const bool dynj = (j <= K - 2);
         double sw_G[7], sw_Pt[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { sw_G[q] = o.G[srr * 7 + q]; sw_Pt[q] = o.Pt[srr * 7 + q]; }
-        const double sw_v = cur.rho + pnext;
-        double tt = pnext;
-#pragma unroll
-        for (int q = 0; q < 7; ++q) tt += -sw_G[q] * gshfl8(sw_v, q) + sw_Pt[q] * gshfl8(cur.aff, q);
-        double Acol[7], Bpmcol[7], Bhcol[7], Kgcol[3];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { Acol[q] = o.F[q * FS + srr]; Bpmcol[q] = o.Bpm[q * 3 + sr3]; Bhcol[q] = o.F[q * FS + 7 + sr3]; }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) Kgcol[q] = o.Kg[q * 7 + srr];
+        SweepCols m;
+        sweep_rows_of(o, srr, sw_G, sw_Pt);
+        double tt = pnext, qu, pp;
+        sweep_t_accum(tt, sw_G, sw_Pt, cur.rho + pnext, cur.aff, 0, 7);
+        sweep_cols_of(o, srr, sr3, m);
+        // (the tail: same arithmetic as sweep_backward)
         if (!dynj || !sact) tt = 0.0;
-        double qu = cur.gu;
+        qu = cur.gu;
 #pragma unroll
-        for (int q = 0; q < 7; ++q) qu += Bpmcol[q] * gshfl8(cur.gx, q) + Bhcol[q] * gshfl8(tt, q);
+        for (int q = 0; q < 7; ++q) qu += m.Bpm[q] * gshfl8(cur.gx, q) + m.Bh[q] * gshfl8(tt, q);
         if (sr >= 3 || !sact) qu = 0.0;
-        double pp = cur.gx;
+        pp = cur.gx;
 #pragma unroll
-        for (int q = 0; q < 7; ++q) pp += Acol[q] * gshfl8(tt, q);
+        for (int q = 0; q < 7; ++q) pp += m.A[q] * gshfl8(tt, q);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) pp -= Kgcol[q] * gshfl8(qu, q);
+        for (int q = 0; q < 3; ++q) pp -= m.Kg[q] * gshfl8(qu, q);
         ustore(s.ws, sact ? s.o_ch + j * CH_N + C_P + sc * 7 + sr : sink_e, pp);
         ustore(s.ws, (sact && sr < 3) ? s.o_ch + j * CH_N + C_QU + sc * 3 + sr3 : sink_e, qu);
         pnext = sact ? pp : pnext;
 #ifdef MPCX_TP
         if (!RF_LAST) {
-            const double v0 = cur0.rho + pnext0;
-            double t0 = pnext0;
-#pragma unroll
-            for (int q = 0; q < 7; ++q) t0 += -sw_G[q] * gshfl8(v0, q) + sw_Pt[q] * gshfl8(cur0.aff, q);
+            double t0 = pnext0, qu0, pp0;
+            sweep_t_accum(t0, sw_G, sw_Pt, cur0.rho + pnext0, cur0.aff, 0, 7);
             if (!dynj || !act0) t0 = 0.0;
-            double qu0 = cur0.gu;
+            qu0 = cur0.gu;
 #pragma unroll
-            for (int q = 0; q < 7; ++q) qu0 += Bpmcol[q] * gshfl8(cur0.gx, q) + Bhcol[q] * gshfl8(t0, q);
+            for (int q = 0; q < 7; ++q) qu0 += m.Bpm[q] * gshfl8(cur0.gx, q) + m.Bh[q] * gshfl8(t0, q);
             if (sr >= 3 || !act0) qu0 = 0.0;
-            double pp0 = cur0.gx;
+            pp0 = cur0.gx;
 #pragma unroll
-            for (int q = 0; q < 7; ++q) pp0 += Acol[q] * gshfl8(t0, q);
+            for (int q = 0; q < 7; ++q) pp0 += m.A[q] * gshfl8(t0, q);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) pp0 -= Kgcol[q] * gshfl8(qu0, q);
+            for (int q = 0; q < 3; ++q) pp0 -= m.Kg[q] * gshfl8(qu0, q);
             ustore(s.ws, act0 ? s.o_chx + j * CHX_N + sr : sink_e, pp0);
             ustore(s.ws, (act0 && sr < 3) ? s.o_chx + j * CHX_N + 7 + sr3 : sink_e, qu0);
             pnext0 = act0 ? pp0 : pnext0;
@@ -428,41 +633,17 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
         const double *Pn = w.Pn2[(k + 1) & 1];
         const bool dyn = (k <= K - 2);
         if (role == 0) {
-            // P1: Bh = A Bpm + Bn ; WxBp = Wx Bpm
-            {
-                const double dot = dotN<7>((p1_wx ? o.G2 : o.F) + p1_i * FS, 1, o.Bpm + p1_j, 3);
-                const double val = p1_wx ? dot : (dyn ? o.Bn[p1_e] + dot : 0.0);
-                double *dst = p1_wx ? &o.G2[p1_i * FS + 7 + p1_j] : (p1_bh ? &o.F[p1_i * FS + 7 + p1_j] : &w.sink[lane]);
-                *dst = val;
-            }
+            factor_p1(o, w, ln, lane, dyn);
             double rd[7] = {0, 0, 0, 0, 0, 0, 0};
             if (dyn) {
                 // P2: LDL^T of M = D + Pn in registers; P3 (this wave's half): X1 = Lt^-1 Pn, lane c < 7 owns column c
                 double m[28];
                 load_m_lower(Pn, o.D, m);
 #pragma unroll
-                for (int pp = 0; pp < 7; ++pp) {
-                    const double d = m[pp * (pp + 1) / 2 + pp];
-                    if (!(d > 0.0)) good = false;
-                    rd[pp] = rcp_pos(d);
-                    double col[7];
-#pragma unroll
-                    for (int i = pp + 1; i < 7; ++i) col[i] = m[i * (i + 1) / 2 + pp];
-#pragma unroll
-                    for (int i = pp + 1; i < 7; ++i) {
-                        const double lip = col[i] * rd[pp];
-#pragma unroll
-                        for (int j = pp + 1; j <= i; ++j) m[i * (i + 1) / 2 + j] -= lip * col[j];
-                        m[i * (i + 1) / 2 + pp] = lip;
-                    }
-                }
+                for (int pp = 0; pp < 7; ++pp)
+                    if (!(ldl7_pivot(m, rd, pp) > 0.0)) good = false;
                 double x[7];
-#pragma unroll
-                for (int pp = 0; pp < 7; ++pp) x[pp] = Pn[pp * PS + xc];
-#pragma unroll
-                for (int pp = 1; pp < 7; ++pp)
-#pragma unroll
-                    for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
+                fwd_subst7<false>(Pn, m, lane, ln.xc, x);
                 lds_st7((lane < 7) ? &w.WlLi[lane * PS] : &w.sink[0], x);
             }
             wsync();
@@ -471,76 +652,31 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                 const bool on = lane < 49;
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
                 const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
-                double a1 = 0.0, x1lo[7], x1hi[7];
+                double x1lo[7], x1hi[7];
                 lds_ld7(&w.WlLi[lo * PS], x1lo); lds_ld7(&w.WlLi[hi * PS], x1hi);
-#pragma unroll
-                for (int l = 0; l < 7; ++l) a1 += x1lo[l] * (rd[l] * x1hi[l]);
-                const double pt = dyn ? Pn[lo * PS + hi] - a1 : 0.0;
+                const double pt = dyn ? Pn[lo * PS + hi] - xrx7(x1lo, rd, x1hi) : 0.0;
                 *(on ? &o.Pt[lane] : &w.sink[lane]) = pt;
                 if (keep_pt) ustore(s.ws, on ? s.o_fac + k * FAC_N + F_PT + lane : sink_e, pt);
                 wsync();
             }
-            // P5
-            w.T[p5_i * FS + p5_j] = dotN<7>(o.Pt + p5_i * 7, 1, o.F + p5_j, FS);
-            {
-                const double *a = p5b_t ? o.Pt + 42 : o.Bpm + p5b_r;
-                const double *b = (p5b_t ? o.F : o.G2) + p5b_j;
-                double acc = 0.0;
-#pragma unroll
-                for (int l = 0; l < 7; ++l) acc += a[l * p5b_sa] * b[l * FS];
-                const double *add = p5b_wu ? &o.Wu[p5b_r * 3 + p5b_j - 7] : &w.zero;
-                double *dst = p5b_t ? &w.T[6 * FS + p5b_j] : (p5b_wu ? &w.Quu[p5b_r * 3 + p5b_j - 7] : (p5b_qy ? &w.Quy[p5b_r * 7 + p5b_j] : &w.sink[lane]));
-                *dst = *add + acc;
-            }
+            factor_p5(o, w, ln, lane);
             wsync();
-            // P6
-            {
-                const double sdot = dotN<7>(o.F + p6_i, FS, w.T + p6_j, FS);
-                double *dst = p6_qyy ? &w.Qyy[p6_i * 7 + p6_j] : (p6_quy ? &w.Quy[(p6_j - 7) * 7 + p6_i] : (p6_quu ? &w.Quu[(p6_i - 7) * 3 + p6_j - 7] : &w.sink[lane]));
-                const double *add = p6_qyy ? &o.G2[p6_i * FS + p6_j] : dst;
-                *dst = *add + sdot;
-            }
+            factor_p6(o, w, ln, lane);
             wsync();
-            // P7-P9: Q_uu^-1, P_k (into the other P buffer), the gain and Q_uu^-1 into the node's operand buffer
-            double Qi[9];
-            if (!inv3_spd(w.Quu, Qi)) good = false;
-            if (lane < 49) {
-                const int lo = (mi < mj) ? mi : mj, hi = (mi < mj) ? mj : mi;
-                double qi[3], qj[3];
-#pragma unroll
-                for (int l = 0; l < 3; ++l) { qi[l] = w.Quy[l * 7 + lo]; qj[l] = w.Quy[l * 7 + hi]; }
-                double a1 = w.Qyy[lo * 7 + hi];
-#pragma unroll
-                for (int l = 0; l < 3; ++l) {
-                    const double kj = Qi[l * 3] * qj[0] + Qi[l * 3 + 1] * qj[1] + Qi[l * 3 + 2] * qj[2];
-                    a1 -= qi[l] * kj;
-                }
-                w.Pn2[k & 1][mi * PS + mj] = a1;
-            }
-            {
-                const bool on21 = lane < 21;
-                const int l21 = on21 ? lane : 0;
-                const int r = l21 / 7, c = l21 - 7 * r;
-                const double q0 = w.Quy[c], q1 = w.Quy[7 + c], q2 = w.Quy[14 + c];
-                const double k0 = Qi[0] * q0 + Qi[1] * q1 + Qi[2] * q2, k1 = Qi[3] * q0 + Qi[4] * q1 + Qi[5] * q2,
-                             k2 = Qi[6] * q0 + Qi[7] * q1 + Qi[8] * q2;
-                const double kg = (r == 0) ? k0 : (r == 1 ? k1 : k2);
-                *(on21 ? &o.Kg[lane] : &w.sink[lane]) = kg;
-                double qv = Qi[0];
-#pragma unroll
-                for (int e = 1; e < 9; ++e) qv = (lane == e) ? Qi[e] : qv;
-                *(lane < 9 ? &o.Qi[lane] : &w.sink[lane]) = qv;
-            }
+            // P7-P9: P_k into the other P buffer, the gain and Q_uu^-1 into the node's operand buffer
+            double kg, qv;
+            if (!factor_p79(o, w, ln, lane, w.Pn2[k & 1], kg, qv)) good = false;
+            *(lane < 9 ? &o.Qi[lane] : &w.sink[lane]) = qv;
             // stiff stage terms (rare): rank-1 update of P_k, the gain and Q_uu^-1 -- on this node's LDS copies, which the
             // second wave writes to the record afterwards
             if (o.SX[SX_EX] > 0.0 || o.SX[SX_EU] > 0.0) {
                 wsync();
                 stiff_stage_update<false>(o, w, w.Pn2[k & 1], nullptr, lane);
             }
-            if (!__all(good) && lane == 0) RF_GOOD = 0;
+            if (!__all(good) && lane == 0) w.good_flag = 0;
         } else {
             // ---- role 1 ----
-            if (k > RF_LO) fetch(k - 1);
+            if (k > RF_LO) pf.fetch(s, lane, k - 1);
             nraw = chan_fetch(s, k, scl, srr, sr3);
 #ifdef MPCX_TP
             if (!RF_LAST) nraw0 = chan_fetch(s, k, 0, srr, sr3);
@@ -549,41 +685,17 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
                 double m[28], rd[7];
                 load_m_lower(Pn, o.D, m);
 #pragma unroll
-                for (int pp = 0; pp < 7; ++pp) {
-                    const double d = m[pp * (pp + 1) / 2 + pp];
-                    rd[pp] = rcp_pos(d);
-                    double col[7];
-#pragma unroll
-                    for (int i = pp + 1; i < 7; ++i) col[i] = m[i * (i + 1) / 2 + pp];
-#pragma unroll
-                    for (int i = pp + 1; i < 7; ++i) {
-                        const double lip = col[i] * rd[pp];
-#pragma unroll
-                        for (int j = pp + 1; j <= i; ++j) m[i * (i + 1) / 2 + j] -= lip * col[j];
-                        m[i * (i + 1) / 2 + pp] = lip;
-                    }
-                }
+                for (int pp = 0; pp < 7; ++pp) (void)ldl7_pivot(m, rd, pp);      // (the pivots' signs are role 0's to test)
                 double x[7];
-#pragma unroll
-                for (int pp = 0; pp < 7; ++pp) {
-                    const double pv = Pn[pp * PS + xc];
-                    x[pp] = (lane < 7) ? pv : (lane - 7 == pp ? 1.0 : 0.0);
-                }
-#pragma unroll
-                for (int pp = 1; pp < 7; ++pp)
-#pragma unroll
-                    for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
+                fwd_subst7<true>(Pn, m, lane, ln.xc, x);
                 lds_st7((lane < 14) ? &w.WlLi1[lane * PS] : &w.sink[8], x);
                 wsync();
                 // G = X1^T R X2, Minv = X2^T R X2 into the node's operand buffer and the factor record
                 const bool on = lane < 49;
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
-                double a2 = 0.0, a3 = 0.0, x1i[7], x2i[7], x2j[7];
+                double x1i[7], x2i[7], x2j[7];
                 lds_ld7(&w.WlLi1[ci * PS], x1i); lds_ld7(&w.WlLi1[(7 + ci) * PS], x2i); lds_ld7(&w.WlLi1[(7 + cj) * PS], x2j);
-#pragma unroll
-                for (int l = 0; l < 7; ++l) {
-                    a2 += x1i[l] * (rd[l] * x2j[l]); a3 += x2i[l] * (rd[l] * x2j[l]);
-                }
+                const double a2 = xrx7(x1i, rd, x2j), a3 = xrx7(x2i, rd, x2j);
                 *(on ? &o.G[lane] : &w.sink[lane]) = a2;
                 *(on ? &o.Minv[lane] : &w.sink[lane]) = a3;
                 const int fb = s.o_fac + k * FAC_N;
@@ -604,15 +716,11 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
 #ifdef MPCX_TP
             if (!RF_LAST) cur0 = chan_mask(nraw0, 0, sr, act0);
 #endif
-            if (!dyn) {
-                const double tg = (sc == 2) ? sd.avt[srr] : sd.ta[sc >= 3 ? sc - 3 : 0][srr];
-                cur.gx = (sact && sc >= 2) ? tg : cur.gx;
-                cur.rho = 0.0; cur.aff = 0.0;
-            }
-            if (k > RF_LO) stash(w.ops[(k - 1) % 3], k - 1);
+            if (!dyn) terminal_chan_inputs(cur, sd, sc, srr, sact);
+            if (k > RF_LO) pf.stash(w.ops[(k - 1) % 3], k - 1, k - 1 <= K - 2);
         }
         WG_BARRIER();
-        if (RF_GOOD == 0) { good = false; break; }
+        if (w.good_flag == 0) { good = false; break; }
     }
 #ifdef MPCX_TP
     if (role == 0 && good && lane < 49) rg.Wout[lane] = w.Pn2[RF_LO & 1][mi * PS + mj];     // the segment's cost-to-go Hessian at its first node
@@ -625,27 +733,24 @@ __device__ __noinline__ bool riccati_factor2(const Sat &s_in, SatData &sd, Scrat
 // What the first wave's driver calls: tell the second wave (parked in solve_kernel2w's command loop) to join, take role 0.
 enum { CMD_FACTOR = 1, CMD_EXIT = 2, CMD_SWEEP = 3, CMD_COMBINE = 4 };
 #ifndef MPCX_TP
-__device__ __forceinline__ bool riccati_factor(const Sat &s, SatData &sd, Scratch &w, int lane, bool fuse_sweep, bool keep_pt)
+__device__ __forceinline__ bool riccati_factor(const Sat &s, SatData &sd, Scratch &w, int lane, bool keep_pt)
 {
-    (void)fuse_sweep;                              // (the backward sweep always rides along: it is the second wave's)
     if (lane == 0) { w.cmd = CMD_FACTOR; w.cmd_arg = keep_pt ? 1 : 0; }
     WG_BARRIER();
     return riccati_factor2(s, sd, w, lane, 0, keep_pt);
 }
 #endif
 #else
-template <bool B> struct BoolC { static constexpr bool value = B; };     // a compile-time flag passed to a generic lambda
 // A value the compiler may not look through (an empty asm that "changes" the register): a lane-dependent choice of a store's
 // address stays a select.  Without it the compiler splits the fused sweep's two stores (channel slot or sink) into exec-mask
 // regions of their own -- saveexec / restore pairs and branches in every node of the factorisation loop.
 template <typename T> __device__ __forceinline__ T opaque(T v) { asm("" : "+v"(v)); return v; }
 
 // Backward Riccati sweep: factorisation (DESIGN.md "Solver algorithm").  Returns false on breakdown.
-// The backward linear-term sweep of all 8 channels always rides along (fuse_sweep: every caller asks for it): node k's
-// p_k, qu_k are formed right after its matrices, while they are still in LDS (same arithmetic as sweep_backward).
-__device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratch &w, int lane, bool fuse_sweep, bool keep_pt)
+// The backward linear-term sweep of all 8 channels always rides along: node k's p_k, qu_k are formed right after its
+// matrices, while they are still in LDS.
+__device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratch &w, int lane, bool keep_pt)
 {
-    (void)fuse_sweep;
     if (MPCX_PRIO_RIC) __builtin_amdgcn_s_setprio(MPCX_PRIO_RIC);
     const Sat s = uniform_view(s_in);   // private copy: scalar registers, not re-read after every LDS fence
     const int K = s.K;
@@ -658,33 +763,28 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
     ChanIn cur{0.0, 0.0, 0.0, 0.0};           // inputs of the node swept in this iteration (k+1)
     ChanRaw nraw{0.0, 0.0, 0.0, 0.0};         // raw inputs of node k, in flight during iteration k
     double pnext = 0.0;
-    // one node of the sweep: t = p+ - G(rho + p+) + Pt aff ; qu = gu + Bpm^T gx + Bh^T t ; p = gx + A^T t - Kg^T qu
-    // (written in three pieces so that the first matrix-vector product can be spread over the pivots of the LDL^T)
+    // one node of the sweep, in three pieces so that the first matrix-vector product can be spread over the pivots of the LDL^T
     double sw_G[7], sw_Pt[7], sw_v = 0.0, sw_t = 0.0;
     auto sweep_begin = [&](const StageOps &o) {
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { sw_G[q] = o.G[srr * 7 + q]; sw_Pt[q] = o.Pt[srr * 7 + q]; }
+        sweep_rows_of(o, srr, sw_G, sw_Pt);
         sw_v = cur.rho + pnext; sw_t = pnext;
     };
-    auto sweep_col = [&](int q) { sw_t += -sw_G[q] * gshfl8(sw_v, q) + sw_Pt[q] * gshfl8(cur.aff, q); };
+    auto sweep_col = [&](int q) { sweep_t_accum(sw_t, sw_G, sw_Pt, sw_v, cur.aff, q, q + 1); };
     auto sweep_finish = [&](const StageOps &o, int j, double &pp, double &qu) {
+        SweepCols m;
+        sweep_cols_of(o, srr, sr3, m);
         const bool dynj = (j <= K - 2);
-        double Acol[7], Bpmcol[7], Bhcol[7], Kgcol[3];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) { Acol[q] = o.F[q * FS + srr]; Bpmcol[q] = o.Bpm[q * 3 + sr3]; Bhcol[q] = o.F[q * FS + 7 + sr3]; }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) Kgcol[q] = o.Kg[q * 7 + srr];
-        double tt = sw_t;
+        double tt = sw_t;                                     // (the tail: same arithmetic as sweep_backward)
         if (!dynj || !sact) tt = 0.0;
         qu = cur.gu;
 #pragma unroll
-        for (int q = 0; q < 7; ++q) qu += Bpmcol[q] * gshfl8(cur.gx, q) + Bhcol[q] * gshfl8(tt, q);
+        for (int q = 0; q < 7; ++q) qu += m.Bpm[q] * gshfl8(cur.gx, q) + m.Bh[q] * gshfl8(tt, q);
         if (sr >= 3 || !sact) qu = 0.0;
         pp = cur.gx;
 #pragma unroll
-        for (int q = 0; q < 7; ++q) pp += Acol[q] * gshfl8(tt, q);
+        for (int q = 0; q < 7; ++q) pp += m.A[q] * gshfl8(tt, q);
 #pragma unroll
-        for (int q = 0; q < 3; ++q) pp -= Kgcol[q] * gshfl8(qu, q);
+        for (int q = 0; q < 3; ++q) pp -= m.Kg[q] * gshfl8(qu, q);
     };
     const int sink_e = s.o_sink + lane;                       // this lane's sink slot (element offset in the workspace)
     auto sweep_store = [&](int j, double pp, double qu) {
@@ -692,79 +792,16 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
         ustore(s.ws, opaque((sact && sr < 3) ? s.o_ch + j * CH_N + C_QU + sc * 3 + sr3 : sink_e), qu);
         pnext = sact ? pp : pnext;
     };
-    // operand prefetch: node k's (A, Bn | Bpm | Wx, Wu, D) -> registers -> LDS buffer.  Three branch-free loads per
-    // lane: A, Bn are the head of stage record k, Bpm = B_kp of record k-1 (same offset), Wx (expanded from its compact
-    // form) | Wu | D | SX from the Newton-block record; what node k does not have (no dynamics at K-1, no Bpm at 0) is
-    // zeroed when stashed.
-    double pre[3];
-    const int e1 = lane + 64, e2 = lane + 128;
-    // element q of the 7 x 7 stage Hessian in the compact Newton record: its 3x3 block entry, the common diagonal value, or
-    // the record's zero
-    auto wx_src = [](int q) -> int {
-        const int i = q / 7, j = q - 7 * i;
-        return (i < 3 && j < 3) ? N_W3 + i * 3 + j : (i == j ? N_DIAG : N_ZERO);
-    };
-    const int wx1 = (e1 >= 91) ? wx_src(e1 - 91) : 0;
-    const int src2 = (e2 < 140) ? wx_src(e2 - 91) : (e2 < OPS_IN ? N_WU + (e2 - 140) : 0);
-    auto fetch = [&](int k) {
-        cgf64 *stk = s.stage + (size_t)(k <= K - 2 ? k : K - 2) * MPCX_STAGE_DOUBLES;
-        cgf64 *stm = s.stage + (size_t)(k >= 1 ? k - 1 : 0) * MPCX_STAGE_DOUBLES;
-        cwf64 *nb = s.nb + (size_t)k * NB_N;
-#ifdef MPCX_WS_LDS
-        // (stage records in global memory, the Newton record in LDS: the lane's second element comes from one or the other)
-        cgf64 *pg = (e1 < 70) ? stk + e1 : stm + (e1 < 91 ? e1 : 70);
-        const double g1 = *pg, l1 = nb[wx1];
-        pre[0] = stk[lane]; pre[1] = (e1 < 91) ? g1 : l1; pre[2] = nb[src2];
-#else
-        cgf64 *p1 = (e1 < 70) ? stk + e1 : (e1 < 91) ? stm + e1 : nb + wx1;
-        cgf64 *p2 = nb + src2;
-        pre[0] = stk[lane]; pre[1] = xld(p1); pre[2] = xld(p2);
-#endif
-    };
-    // LDS slot (byte offset inside StageOps) of element e of the fetch order [A 49 | Bn 21 | Bpm 21 | Wx 49 | Wu 9 | D 7 | SX 8]
-    auto ops_slot = [](int e) -> int {
-        if (e < 49) return (int)offsetof(StageOps, F) + 8 * ((e / 7) * FS + e % 7);
-        if (e < 70) return (int)offsetof(StageOps, Bn) + 8 * (e - 49);
-        if (e < 91) return (int)offsetof(StageOps, Bpm) + 8 * (e - 70);
-        if (e < 140) return (int)offsetof(StageOps, G2) + 8 * (((e - 91) / 7) * FS + (e - 91) % 7);
-        if (e < 149) return (int)offsetof(StageOps, Wu) + 8 * (e - 140);
-        if (e < 156) return (int)offsetof(StageOps, D) + 8 * (e - 149);
-        return (int)offsetof(StageOps, SX) + 8 * ((e < OPS_IN) ? e - 156 : 0);
-    };
-    const int slot0 = ops_slot(lane), slot1 = ops_slot(e1), slot2 = ops_slot(e2);
-    auto stash = [&](auto dyn_c, StageOps &o, int k) {
-        constexpr bool dynk = decltype(dyn_c)::value;             // (k <= K - 2)
-        char *base = (char *)&o;
-        *(double *)(base + slot0) = dynk ? pre[0] : 0.0;
-        *(double *)(base + slot1) = ((e1 < 70) ? dynk : (e1 < 91) ? (k >= 1) : true) ? pre[1] : 0.0;
-        if (e2 < OPS_IN) *(double *)(base + slot2) = (e2 < 149 || e2 >= 156 || dynk) ? pre[2] : 0.0;
-    };
-    fetch(K - 1);
-    stash(BoolC<false>{}, w.ops[(K - 1) & 1], K - 1);
+    OpsPrefetch pf(lane);
+    pf.fetch(s, lane, K - 1);
+    pf.stash(w.ops[(K - 1) & 1], K - 1, BoolC<false>{});
     // (the terminal node's Hessian -- soft part, capped rank-1 terms, AL term -- is a full matrix: from SatData)
     if (lane < 49) w.ops[(K - 1) & 1].G2[(lane / 7) * FS + lane % 7] = sd.WxK[lane];
     if (lane < PN_N) w.Pn[lane] = 0.0;
     if (lane == 0) w.zero = 0.0;
     WG_SYNC();
-    const int mi = lane / 7, mj = lane - 7 * mi;
-    const int xc = (lane < 7) ? lane : 6;                 // column of [Pn | I] this lane substitutes (lanes 0..13)
-    // P1 roles: lanes 0..20 element e of Bh = A Bpm + Bn (into F), lanes 32..52 element e of Wx Bpm (into G2), one body
-    const bool p1_bh = lane < 21, p1_wx = lane >= 32 && lane < 53;
-    const int p1_e = p1_wx ? lane - 32 : (p1_bh ? lane : 0), p1_i = p1_e / 3, p1_j = p1_e - 3 * p1_i;
-    // P5 roles: first round task lane of the 70 of T = Pt F; second round lanes 0..5 the other 6 (row 6, columns 4..9),
-    // lanes 6..35 element (r, j) of Bpm^T G2 (j < 7: Quy0, j >= 7: Quu0)
-    const int p5_i = lane / FS, p5_j = lane - FS * p5_i;
-    const bool p5b_t = lane < 6, p5b_g = lane >= 6 && lane < 36;
-    const int p5b_q = p5b_g ? lane - 6 : 0;
-    const int p5b_r = p5b_q / FS;
-    const int p5b_j = p5b_t ? 4 + lane : p5b_q - FS * p5b_r;
-    const int p5b_sa = p5b_t ? 1 : 3;
-    const bool p5b_wu = p5b_g && p5b_j >= 7, p5b_qy = p5b_g && p5b_j < 7;
-    // P6 roles: lane t < 55 is entry (i, j), i <= j, of the 10 x 10 matrix S = F^T T
-    int p6_i = 0, p6_j = 0;
-    { int tt = lane; for (int i = 0; i < FS; ++i) { const int n = FS - i; if (tt < n) { p6_i = i; p6_j = i + tt; break; } tt -= n; } }
-    const bool p6_on = lane < 55;
-    const bool p6_qyy = p6_on && p6_j < 7, p6_quy = p6_on && p6_i < 7 && p6_j >= 7, p6_quu = p6_on && p6_i >= 7;
+    const FactorLanes ln(lane);
+    const int mi = ln.mi, mj = ln.mj;
     // One node of the recursion, specialised at compile time: DYN -- a node with dynamics (k <= K-2; not the terminal node),
     // LAST -- node 0, the last one visited (nothing to prefetch or stash behind it).  The terminal node K-1 and node 0 are
     // peeled off the loop (K >= 3: the loop runs at least once), so its body tests neither.  Returns false on a breakdown.
@@ -773,16 +810,10 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
         StageOps &o = w.ops[k & 1];
         wf64 *fac = s.fac + (size_t)k * FAC_N;
         FT_DECL
-        if constexpr (!last) fetch(k - 1);
+        if constexpr (!last) pf.fetch(s, lane, k - 1);
         nraw = chan_fetch(s, k, sc, srr, sr3);
         FT_MARK(0)
-        // P1: Bh = A Bpm + Bn ; WxBp = Wx Bpm
-        {
-            const double dot = dotN<7>((p1_wx ? o.G2 : o.F) + p1_i * FS, 1, o.Bpm + p1_j, 3);
-            const double val = p1_wx ? dot : (dyn ? o.Bn[p1_e] + dot : 0.0);
-            double *dst = p1_wx ? &o.G2[p1_i * FS + 7 + p1_j] : (p1_bh ? &o.F[p1_i * FS + 7 + p1_j] : &w.sink[lane]);
-            *dst = val;
-        }
+        factor_p1(o, w, ln, lane, dyn_c);
         double rd[7] = {0, 0, 0, 0, 0, 0, 0};
         if constexpr (dyn) {
             double sw_p = 0.0, sw_qu = 0.0;
@@ -797,31 +828,11 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
 #pragma unroll
             for (int pp = 0; pp < 7; ++pp) {
                 sweep_col(pp);
-                const double d = m[pp * (pp + 1) / 2 + pp];
-                if (!(d > 0.0)) good = false;
-                rd[pp] = rcp_pos(d);
-                double col[7];
-#pragma unroll
-                for (int i = pp + 1; i < 7; ++i) col[i] = m[i * (i + 1) / 2 + pp];
-#pragma unroll
-                for (int i = pp + 1; i < 7; ++i) {
-                    const double lip = col[i] * rd[pp];
-#pragma unroll
-                    for (int j = pp + 1; j <= i; ++j) m[i * (i + 1) / 2 + j] -= lip * col[j];
-                    m[i * (i + 1) / 2 + pp] = lip;
-                }
+                if (!(ldl7_pivot(m, rd, pp) > 0.0)) good = false;
             }
             // P3: [X1 | X2] = Lt^-1 [Pn | I] (unit lower), lane c < 14 owns column c
             double x[7];
-#pragma unroll
-            for (int pp = 0; pp < 7; ++pp) {
-                const double pv = w.Pn[pp * PS + xc];
-                x[pp] = (lane < 7) ? pv : (lane - 7 == pp ? 1.0 : 0.0);
-            }
-#pragma unroll
-            for (int pp = 1; pp < 7; ++pp)
-#pragma unroll
-                for (int q = 0; q < pp; ++q) x[pp] -= m[pp * (pp + 1) / 2 + q] * x[q];
+            fwd_subst7<true>(w.Pn, m, lane, ln.xc, x);
             // (column lane of WlLi, contiguous: four stores; the lanes that own none write theirs to the head of the sink)
             lds_st7((lane < 14) ? &w.WlLi[lane * PS] : &w.sink[0], x);
             sweep_finish(on, k + 1, sw_p, sw_qu);
@@ -840,15 +851,11 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             if constexpr (dyn) {
                 const int ci = on ? mi : 0, cj = on ? mj : 0;
                 const int lo = (ci < cj) ? ci : cj, hi = (ci < cj) ? cj : ci;
-                double a1 = 0.0, x1i[7], x1lo[7], x1hi[7], x2i[7], x2j[7];
+                double x1i[7], x1lo[7], x1hi[7], x2i[7], x2j[7];
                 lds_ld7(&w.WlLi[ci * PS], x1i); lds_ld7(&w.WlLi[lo * PS], x1lo); lds_ld7(&w.WlLi[hi * PS], x1hi);
                 lds_ld7(&w.WlLi[(7 + ci) * PS], x2i); lds_ld7(&w.WlLi[(7 + cj) * PS], x2j);
-#pragma unroll
-                for (int l = 0; l < 7; ++l) {
-                    a1 += x1lo[l] * (rd[l] * x1hi[l]);
-                    a2 += x1i[l] * (rd[l] * x2j[l]); a3 += x2i[l] * (rd[l] * x2j[l]);
-                }
-                pt = w.Pn[lo * PS + hi] - a1;
+                a2 = xrx7(x1i, rd, x2j); a3 = xrx7(x2i, rd, x2j);
+                pt = w.Pn[lo * PS + hi] - xrx7(x1lo, rd, x1hi);
             }
             *(on ? &o.Pt[lane] : &w.sink[lane]) = pt;
             *(on ? &o.G[lane] : &w.sink[lane]) = a2;
@@ -860,69 +867,21 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
             wsync();
         }
         FT_MARK(3)
-        // P5: T = Pt F (70 dot products of one pattern: 64 in the first round, 6 in the second) and
-        //     [Quy0 | Quu0 - Wu] = Bpm^T G2 (30, second round, lanes 6..35)
-        w.T[p5_i * FS + p5_j] = dotN<7>(o.Pt + p5_i * 7, 1, o.F + p5_j, FS);
-        {
-            const double *a = p5b_t ? o.Pt + 42 : o.Bpm + p5b_r;
-            const double *b = (p5b_t ? o.F : o.G2) + p5b_j;
-            double acc = 0.0;
-#pragma unroll
-            for (int l = 0; l < 7; ++l) acc += a[l * p5b_sa] * b[l * FS];
-            const double *add = p5b_wu ? &o.Wu[p5b_r * 3 + p5b_j - 7] : &w.zero;
-            double *dst = p5b_t ? &w.T[6 * FS + p5b_j] : (p5b_wu ? &w.Quu[p5b_r * 3 + p5b_j - 7] : (p5b_qy ? &w.Quy[p5b_r * 7 + p5b_j] : &w.sink[lane]));
-            *dst = *add + acc;
-        }
+        factor_p5(o, w, ln, lane);
         wsync();
         FT_MARK(4)
-        // P6: the upper triangle of S = F^T T (55 dot products of one pattern): Qyy = Wx + A^T Pt A (upper part only, read
-        //     back through (min, max)), Quy += Bh^T Pt A, Quu += Bh^T Pt Bh (upper part: all the 3x3 inverse reads)
-        {
-            const double sdot = dotN<7>(o.F + p6_i, FS, w.T + p6_j, FS);
-            double *dst = p6_qyy ? &w.Qyy[p6_i * 7 + p6_j] : (p6_quy ? &w.Quy[(p6_j - 7) * 7 + p6_i] : (p6_quu ? &w.Quu[(p6_i - 7) * 3 + p6_j - 7] : &w.sink[lane]));
-            const double *add = p6_qyy ? &o.G2[p6_i * FS + p6_j] : dst;
-            *dst = *add + sdot;
-        }
+        factor_p6(o, w, ln, lane);
         wsync();
         FT_MARK(5)
-        // P7-P9: every lane inverts the 3x3 itself; P_k = sym(Qyy - Quy^T Qi Quy) straight from its own two columns of
-        // Quy (no exchange of the gain on the way); the gain Kg = Qi Quy goes to LDS / the factor record for the sweeps
-        double Qi[9];
-        if (!inv3_spd(w.Quu, Qi)) good = false;
-        if (lane < 49) {
-            const int lo = (mi < mj) ? mi : mj, hi = (mi < mj) ? mj : mi;
-            double qi[3], qj[3];
-#pragma unroll
-            for (int l = 0; l < 3; ++l) { qi[l] = w.Quy[l * 7 + lo]; qj[l] = w.Quy[l * 7 + hi]; }
-            // (qi, qj) = columns (min, max) of Quy: lanes (i,j) and (j,i) evaluate the same expression, P_k is
-            // symmetric by construction; Qyy is symmetrised through the same (min, max) read (rounding-level asymmetry
-            // of A^T (Pt A) otherwise)
-            double a1 = w.Qyy[lo * 7 + hi];
-#pragma unroll
-            for (int l = 0; l < 3; ++l) {
-                const double kj = Qi[l * 3] * qj[0] + Qi[l * 3 + 1] * qj[1] + Qi[l * 3 + 2] * qj[2];     // Kg(l, hi)
-                a1 -= qi[l] * kj;
-            }
-            w.Pn[mi * PS + mj] = a1;
-        }
-        // (Qi is indexed with constants only and picked by selects: a register array indexed by a lane-dependent value
-        //  is placed in scratch memory, and its store / load pair would sit behind an s_waitcnt vmcnt(0) in every node)
+        // P7-P9; the node's record entries Kg, Bh, Qi: branch-free (see ustore)
         {
-            // gain Kg = Qi Quy (lanes 0..20) and the node's record entries Kg, Bh, Qi: branch-free (see ustore)
+            double kg, qv;
+            if (!factor_p79(o, w, ln, lane, w.Pn, kg, qv)) good = false;
             const bool on21 = lane < 21;
             const int l21 = on21 ? lane : 0;
-            const int r = l21 / 7, c = l21 - 7 * r;
-            const double q0 = w.Quy[c], q1 = w.Quy[7 + c], q2 = w.Quy[14 + c];
-            const double k0 = Qi[0] * q0 + Qi[1] * q1 + Qi[2] * q2, k1 = Qi[3] * q0 + Qi[4] * q1 + Qi[5] * q2,
-                         k2 = Qi[6] * q0 + Qi[7] * q1 + Qi[8] * q2;
-            const double kg = (r == 0) ? k0 : (r == 1 ? k1 : k2);
-            *(on21 ? &o.Kg[lane] : &w.sink[lane]) = kg;
             const int fb = s.o_fac + k * FAC_N;
             ustore(s.ws, on21 ? fb + F_KG + lane : sink_e, kg);
             ustore(s.ws, on21 ? fb + F_BH + lane : sink_e, o.F[(l21 / 3) * FS + 7 + l21 % 3]);
-            double qv = Qi[0];
-#pragma unroll
-            for (int e = 1; e < 9; ++e) qv = (lane == e) ? Qi[e] : qv;
             ustore(s.ws, lane < 9 ? fb + F_QI + lane : sink_e, qv);
         }
         // stiff stage terms (rare: an active r_min plane / radius or thrust ball late in the iteration): rank-1 update of
@@ -934,15 +893,11 @@ __device__ __noinline__ bool riccati_factor(const Sat &s_in, SatData &sd, Scratc
         // (the terminal node's inputs come through the same branch-free fetch: a conditional load here would make
         //  the first use of `cur` in the next node wait with vmcnt(0), i.e. for that node's whole prefetch)
         cur = chan_mask(nraw, sc, sr, sact);
-        if constexpr (!dyn) {
-            const double tg = (sc == 2) ? sd.avt[srr] : sd.ta[sc >= 3 ? sc - 3 : 0][srr];
-            cur.gx = (sact && sc >= 2) ? tg : cur.gx;
-            cur.rho = 0.0; cur.aff = 0.0;
-        }
+        if constexpr (!dyn) terminal_chan_inputs(cur, sd, sc, srr, sact);
         FT_MARK(8)
         // a breakdown (every lane sees the same pivots) ends the sweep here: the caller retries with a larger delta_w
         if (!__all(good)) return false;
-        if constexpr (!last) stash(BoolC<true>{}, w.ops[(k - 1) & 1], k - 1);
+        if constexpr (!last) pf.stash(w.ops[(k - 1) & 1], k - 1, BoolC<true>{});
         wsync();
         FT_MARK(9)
         return true;
@@ -1068,10 +1023,8 @@ __device__ __noinline__ void sweep_backward(const Sat &s_in, SatData &sd, Scratc
         }
 #pragma unroll
         for (int q = 0; q < 3; ++q) Kgcol[q] = fr[F_KG + q * 7 + rr];
-        const double v = cur.rho + pnext;
         double t = pnext;
-#pragma unroll
-        for (int q = 0; q < 7; ++q) t += -Grow[q] * gshfl8(v, q) + Ptrow[q] * gshfl8(cur.aff, q);
+        sweep_t_accum(t, Grow, Ptrow, cur.rho + pnext, cur.aff, 0, 7);
         if (!dyn || !act) t = 0.0;
         double qu = cur.gu;
 #pragma unroll

@@ -246,17 +246,7 @@ __device__ __forceinline__ bool tp_ldl7(const double *M, double (&m)[28])
     for (int pp = 0; pp < 7; ++pp) {
         const double d = m[pp * (pp + 1) / 2 + pp];
         if (!(d > 0.0)) ok = false;
-        const double rd = rcp_pos(d > 0.0 ? d : 1.0);
-        double col[7];
-#pragma unroll
-        for (int i = pp + 1; i < 7; ++i) col[i] = m[i * (i + 1) / 2 + pp];
-#pragma unroll
-        for (int i = pp + 1; i < 7; ++i) {
-            const double lip = col[i] * rd;
-#pragma unroll
-            for (int jj = pp + 1; jj <= i; ++jj) m[i * (i + 1) / 2 + jj] -= lip * col[jj];
-            m[i * (i + 1) / 2 + pp] = lip;
-        }
+        ldl7_eliminate(m, pp, rcp_pos(d > 0.0 ? d : 1.0));
     }
     return ok;
 }

@@ -6,6 +6,12 @@ prints its instruction count by kind, then solve_kernel's VGPR / spill / scratch
 metadata.
 
     python profiles/tools/isa_loop_mix.py [--src mpconstellation_amd/csrc/solve.hip] [--asm FILE] [--keep FILE.s]
+
+With --func NAME / --kernel NAME (both repeatable, any translation unit of the solver) it prints instead one line per function
+-- instructions of the whole body: total, fp64, LDS, scratch, s_waitcnt -- and one per kernel -- VGPRs, AGPRs, VGPR and SGPR
+spills, scratch bytes, static LDS from the code object metadata:
+
+    python profiles/tools/isa_loop_mix.py --src mpconstellation_amd/csrc/solve2w.hip --func riccati_factor2 --kernel solve_kernel2w
 """
 import argparse
 import collections
@@ -97,8 +103,25 @@ def classify(ins):
     return "other"
 
 
-def kernel_meta(text):
-    m = re.search(r"\.name:\s+" + re.escape(KERNEL) + r"\s*$", text, re.M)
+def function_figures(lines, name):
+    """(mangled name, counts) of the function `name` of the solver's namespace (mpcx, mpcx2w, mpcxl, mpcxtp), lambdas apart"""
+    rx = re.compile(r"^(_ZN\d+mpcx\w*?%d%sE\S*):" % (len(name), re.escape(name)))
+    for ln in lines:
+        m = rx.match(ln)
+        if m:
+            break
+    else:
+        sys.exit(f"function {name} not found")
+    ins = [l.strip().split(";")[0].strip() for l in function_lines(lines, m.group(1))[1:]]
+    ins = [i for i in ins if i and not i.startswith(".") and not i.endswith(":")]
+    mix = collections.Counter(classify(i) for i in ins)
+    return {"total": len(ins), "fp64": mix["fp64"], "LDS": mix["LDS"], "scratch": mix["scratch"],
+            "s_waitcnt": sum(1 for i in ins if i.startswith("s_waitcnt"))}
+
+
+def kernel_meta(text, kernel=KERNEL):
+    """code object metadata of a kernel, by its mangled name or by its plain name in the solver's namespace"""
+    m = re.search(r"\.name:\s+(" + re.escape(kernel) + r"|_ZN\d+mpcx\w*?%d%sE\S*)\s*$" % (len(kernel), re.escape(kernel)), text, re.M)
     if not m:
         return {}
     # the metadata map of one kernel: from its "  - ." line to the next kernel's
@@ -119,6 +142,8 @@ def main():
     ap.add_argument("--src", default=os.path.join(ROOT, "mpconstellation_amd", "csrc", "solve.hip"))
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
     ap.add_argument("--keep", help="keep the compiled assembly here")
+    ap.add_argument("--func", action="append", default=[], help="whole-function instruction counts of this function")
+    ap.add_argument("--kernel", action="append", default=[], help="register / spill / scratch / LDS figures of this kernel")
     args = ap.parse_args()
     if args.asm:
         path = args.asm
@@ -127,6 +152,18 @@ def main():
         compile_asm(args.src, path)
     text = open(path).read()
     lines = text.splitlines()
+    if args.func or args.kernel:
+        for name in args.func:
+            f = function_figures(lines, name)
+            print(f"{name}: " + ", ".join(f"{k} {v}" for k, v in f.items()))
+        for name in args.kernel:
+            meta = kernel_meta(text, name)
+            if not meta:
+                sys.exit(f"kernel {name} not found")
+            print(f"{name}: VGPRs {meta.get('vgpr_count')}, AGPRs {meta.get('agpr_count', 0)}, VGPR spills {meta.get('vgpr_spill_count')}, "
+                  f"SGPR spills {meta.get('sgpr_spill_count')}, scratch {meta.get('private_segment_fixed_size')} B, "
+                  f"LDS {meta.get('group_segment_fixed_size')} B")
+        return
     body = function_lines(lines, FUNC)
     lp = loops(body)
     if not lp:
