@@ -49,28 +49,11 @@ struct RhsCtx {
     double atm[MPCX_NATMO];      // ATMO forms: the atmosphere's coefficients (launch constants)
 };
 
-// 1/d and 1/sqrt(d) for d > 0 well inside the normal range: hardware seed + two Newton steps (half an ulp, measured:
-// profiles/tools/rcp_accuracy.hip) instead of the IEEE division / square-root sequences (~3x the instructions)
-__device__ __forceinline__ double rcp_nr(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) { const double e = fma(-d, r, 1.0); r = fma(r, e, r); }
-    return r;
-}
-__device__ __forceinline__ double rsq_nr(double d)
-{
-    double r = __builtin_amdgcn_rsq(d);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) { const double e = fma(-d * r, r, 1.0); r = fma(0.5 * r, e, r); }
-    return r;
-}
-
-// The linearisation at one point (x, u): tf * G = tf * d a / d r, tf * gm = tf * d a / d m (jacobian_blocks), the acceleration and the
-// mass flow of Simulator.satellite_dynamics (dynamics_unscaled, tf = 1).  The ~48 right-hand sides and ~9 quadrature nodes per
-// interval are nearly all of the kernel's instructions, and a third of theirs were IEEE division / square-root sequences:
-// here everything is arranged around one reciprocal each of |r|, m and |u| (round 3).  Results move by rounding only (a few
-// ulp per evaluation, 1e-13 on A_k, B_k against the reference's arrays; the accepted RK45 nodes are the same).
+// The linearisation at one point (x, u): tf * G = tf * d a / d r, tf * gm = tf * d a / d m (Dxf, linearize_discretize.py:144-179), the
+// acceleration and the mass flow of Simulator.satellite_dynamics (tf = 1; the plain form: oracle/dynamics.c).  The ~48 right-hand
+// sides and ~9 quadrature nodes per interval are nearly all of the kernel's instructions, and a third of theirs were IEEE division /
+// square-root sequences: here everything is arranged around one reciprocal each of |r|, m and |u| (rcp_pos, rsq_pos).  Results move by
+// rounding only (a few ulp per evaluation, 1e-13 on A_k, B_k against the reference's arrays; the accepted RK45 nodes are the same).
 struct Lin {
     double Gt[3][3], gmt[3], acc[3], im, irn;
 };
@@ -82,8 +65,8 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
 {
     const double rx = r[0], ry = r[1], rz = r[2];
     const double r2 = rx * rx + ry * ry + rz * rz;
-    const double irn = rsq_nr(r2), irn2 = irn * irn, ir3 = irn2 * irn, ir5 = ir3 * irn2;
-    const double im = rcp_nr(m > 0.0 ? m : 1.0);
+    const double irn = rsq_pos(r2), irn2 = irn * irn, ir3 = irn2 * irn, ir5 = ir3 * irn2;
+    const double im = rcp_pos(m > 0.0 ? m : 1.0);
     const double c1 = -c.mu * ir3, c1t = tf * c1, c2t = tf * (3.0 * c.mu * ir5);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -91,9 +74,9 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
         for (int j = 0; j < 3; ++j) L.Gt[i][j] = (i == j ? c1t : 0.0) + c2t * (r[i] * r[j]);
     double j2a[3] = {0.0, 0.0, 0.0};
     if (flags & MPCX_FLAG_J2) {
-        const double kJ2 = 1.5 * c.j2 * c.mu * (c.re * c.re);
+        const double kJ2 = j2_factor(c);
         const double q2 = (rz * rz) * irn2;
-        const double g[3] = {5.0 * q2 - 1.0, 5.0 * q2 - 1.0, 5.0 * q2 - 3.0};
+        const double g[3] = {j2_bracket(q2, 0), j2_bracket(q2, 1), j2_bracket(q2, 2)};
         const double ir4 = irn2 * irn2, ir7 = ir5 * irn2;
         double ddr[3];
 #pragma unroll
@@ -116,8 +99,8 @@ __device__ __forceinline__ void lin_eval(const double (&r)[3], const double (&v)
     if (flags & MPCX_FLAG_DRAG) {                            // simulator.py:150-153
         const double vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
         double dens;
-        if constexpr (ATMO) dens = dens_atmo; else dens = kRho500 / c.rho;
-        const double coef = -0.5 * kCd * c.s * im * dens * vn;
+        if constexpr (ATMO) dens = dens_atmo; else dens = fixed_density(c);
+        const double coef = drag_k(c, im) * dens * vn;
 #pragma unroll
         for (int i = 0; i < 3; ++i) L.acc[i] += coef * v[i];
     }
@@ -139,13 +122,13 @@ template <bool ATMO>
 __device__ __forceinline__ DragLin drag_lin(const double (&v)[3], const SatConst &c, double tf, double dens_atmo, double drho, Lin &L)
 {
     const double vv = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    const double ivn = rsq_nr(vv), vn = vv * ivn;
+    const double ivn = rsq_pos(vv), vn = vv * ivn;
     double kdt, krt = 0.0;
     if constexpr (ATMO) {
-        const double k0 = tf * (-0.5 * kCd * c.s * L.im);
+        const double k0 = tf * drag_k(c, L.im);
         kdt = k0 * dens_atmo;
         krt = ((k0 * vn) * drho) * L.irn;
-    } else kdt = tf * (-0.5 * kCd * c.s * L.im * (kRho500 / c.rho));
+    } else kdt = tf * (drag_k(c, L.im) * fixed_density(c));
     const double gm = -(kdt * vn) * L.im;
 #pragma unroll
     for (int i = 0; i < 3; ++i) L.gmt[i] += gm * v[i];
@@ -182,7 +165,7 @@ __device__ __forceinline__ void time_eval(RhsCtx &p, double ts, TimePart &T, int
     if (e) err = e;
     T.stable = (p.foh.k == k0);
     const double uu = T.u[0] * T.u[0] + T.u[1] * T.u[1] + T.u[2] * T.u[2];
-    T.iun = rsq_nr(fmax(uu, 1e-300));
+    T.iun = rsq_pos(fmax(uu, 1e-300));
     T.un = uu * T.iun;
     T.mdot = -T.un * p.inv_ve;
 }
@@ -199,17 +182,26 @@ __device__ __forceinline__ void state_eval(const RhsCtx &p, const double (&r)[3]
     if constexpr (DRAG) D = drag_lin<ATMO>(v, p.cst, p.tf, dens, drho, L);
 }
 
+// (r, v, m) of the x column, lane 7's, in every lane of the group.  Drag acts in the x column only, so a right-hand side without
+// the drag partials reads lane 7's own velocity (BCAST_V false); the DRAG forms' Phi columns and every node need it broadcast.
+template <bool BCAST_V>
+__device__ __forceinline__ void x_column(const double (&y)[7], double (&r)[3], double (&v)[3], double &m)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) r[i] = bcast8<7>(y[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[i] = BCAST_V ? bcast8<7>(y[3 + i]) : y[3 + i];
+    m = bcast8<7>(y[6]);
+}
+
 // One evaluation of dPhi (linearize_discretize.py:262-290) for this lane's column, at the time part T; L, D: the state part
 // it was formed with (the node after an accepted step takes the last stage's).
 template <bool DRAG, bool ATMO>
 __device__ __forceinline__ void rhs_state(RhsCtx &p, const double (&ys)[7], const TimePart &T,
                                           double (&out)[7], int &err, Lin &L, DragLin &D)
 {
-    const double r[3] = {bcast8<7>(ys[0]), bcast8<7>(ys[1]), bcast8<7>(ys[2])};
-    // drag acts in the x column only: lane 7's own velocity -- except in the DRAG forms, whose Phi columns need the reference
-    // velocity for the drag partials: broadcast from lane 7 like r and m
-    const double v[3] = {DRAG ? bcast8<7>(ys[3]) : ys[3], DRAG ? bcast8<7>(ys[4]) : ys[4], DRAG ? bcast8<7>(ys[5]) : ys[5]};
-    const double m = bcast8<7>(ys[6]);
+    double r[3], v[3], m;
+    x_column<DRAG>(ys, r, v, m);
     const double tf = p.tf;
     state_eval<DRAG, ATMO>(p, r, v, m, T, L, D);
     double dv[3] = {0.0, 0.0, 0.0};
@@ -272,7 +264,7 @@ __device__ __forceinline__ bool lu_solve_cols(double (&col)[6], double (&b)[6])
             const double ra = b[p], rb = b[i];                                                        \
             b[p] = sw ? rb : ra; b[i] = sw ? ra : rb;                                                 \
         }                                                                                             \
-        invd[p] = bcast8<p>(rcp_nr(col[p]));                                                          \
+        invd[p] = bcast8<p>(rcp_pos(col[p]));                                                          \
         _Pragma("unroll") for (int i = p + 1; i < 6; ++i) {                                           \
             const double mlt = bcast8<p>(col[i]) * invd[p];                                           \
             col[i] -= mlt * col[p];                                                                   \
@@ -363,11 +355,27 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
 {
     TimePart T;
     time_eval(p, t, T, err);
-    const double r[3] = {bcast8<7>(y[0]), bcast8<7>(y[1]), bcast8<7>(y[2])}, v[3] = {bcast8<7>(y[3]), bcast8<7>(y[4]), bcast8<7>(y[5])};
+    double r[3], v[3], m;
+    x_column<true>(y, r, v, m);
     Lin L;
     DragLin D;
-    state_eval<DRAG, ATMO>(p, r, v, bcast8<7>(y[6]), T, L, D);
+    state_eval<DRAG, ATMO>(p, r, v, m, T, L, D);
     node_columns<DRAG, ATMO>(p, y, T, L, D, t, tau_k, tau_kp1, g, err);
+}
+
+// One component's quotient of scipy's error norm (rk.py:97-99, 139-141): e h / (atol + max(|y|, |y_new|) rtol), e the
+// tableau's error combination of the stages -- by the reciprocal, where the rollout divides.
+__device__ __forceinline__ double err_quotient(double e, double h, double y, double yn, double atol, double rtol)
+{
+    const double sc = atol + fmax(fabs(y), fabs(yn)) * rtol;
+    return (e * h) * rcp_pos(sc);
+}
+
+// np.trapz's slice of one node (linearize_discretize.py:77-80) for one component: acc += d (g + g_prev) / 2, and g is the next g_prev
+__device__ __forceinline__ void trapz_commit(double d, double g, double &gprev, double &acc)
+{
+    acc += d * (g + gprev) / 2.0;
+    gprev = g;
 }
 
 // UNIFORM: Discretizer.use_uniform_steps (linearize_discretize.py:27-30, 50-53): the quadrature nodes are integrator_steps
@@ -429,7 +437,6 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
     const double tau_kp1 = (k + 1 == Km1s) ? 1.0 : (double)(k + 1) * step + 0.0;
     const double t_bound = tau_kp1;
     const double rtol = 1e-3, atol = 1e-6;
-    constexpr double kErrExp = (METHOD == 23) ? -1.0 / 3.0 : -0.2;      // rk.py:93: -1 / (error_estimator_order + 1)
     int err = (badk || badku) ? MPCX_ST_BADK : 0;
 
     double y[7], f[7];
@@ -451,8 +458,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         }
         const double inv_sqrt_n = 1.0 / sqrt(56.0);
         const double d0 = sqrt(group_sum(s0)) * inv_sqrt_n, d1 = sqrt(group_sum(s1)) * inv_sqrt_n;
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, interval);
+        const double h0 = rk_initial_h0(d0, d1, interval);
         double y1[7], f1[7];
 #pragma unroll
         for (int i = 0; i < 7; ++i) y1[i] = y[i] + h0 * f[i];
@@ -461,11 +467,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
 #pragma unroll
         for (int i = 0; i < 7; ++i) { const double d = (f1[i] - f[i]) / scale[i]; s2 += d * d; }
         const double d2 = sqrt(group_sum(s2)) * inv_sqrt_n / h0;
-        double h1;
-        if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
-        else h1 = pow(0.01 / fmax(d1, d2), METHOD == 23 ? 1.0 / 3.0 : 1.0 / 5.0);       // 1 / (error_estimator_order + 1)
-        h_abs = fmin(fmin(100.0 * h0, h1), fmin(interval, a.max_step));
-        if (interval == 0.0) h_abs = 0.0;
+        h_abs = rk_initial_h_abs<METHOD>(h0, d1, d2, interval, a.max_step);
     }
 
     // ---- quadrature state: trapezoid accumulators for this lane's column ----
@@ -491,16 +493,9 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             break;
         }
         const double min_step = 10.0 * fabs(nextafter(t, INFINITY) - t);
-        if (!rejected) {
-            if (h_abs > a.max_step) h_abs = a.max_step;
-            else if (h_abs < min_step) h_abs = min_step;
-        }
-        bool fail = active && !(h_abs >= min_step);   // also catches a non-finite step
-        double h = h_abs;
-        double t_new = t + h;
-        if (t_new - t_bound > 0.0) t_new = t_bound;
-        h = t_new - t;
-        const double h_try = fabs(h);
+        const RkAttempt at = rk_attempt(t, t_bound, a.max_step, rejected, h_abs, min_step);
+        const bool fail = active && at.too_small;     // also catches a non-finite step
+        const double h = at.h, t_new = at.t_new, h_try = at.h_try;
 
         double K1[7], K2[7], K3[7], K4[7], K5[7], K6[7], yt[7], yn[7];
         double se = 0.0;
@@ -524,8 +519,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             for (int i = 0; i < 7; ++i) {
                 K3[i] = 0.0; K4[i] = 0.0; K5[i] = 0.0;
                 const double e = f[i] * RK23_E[0] + K1[i] * RK23_E[1] + K2[i] * RK23_E[2] + K6[i] * RK23_E[3];
-                const double sc = atol + fmax(fabs(y[i]), fabs(yn[i])) * rtol;
-                const double q = (e * h) * rcp_nr(sc);
+                const double q = err_quotient(e, h, y[i], yn[i], atol, rtol);
                 se += q * q;
             }
         } else {
@@ -564,8 +558,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
         for (int i = 0; i < 7; ++i) {
             const double e = f[i] * RK_E[0] + K1[i] * RK_E[1] + K2[i] * RK_E[2] + K3[i] * RK_E[3] +
                              K4[i] * RK_E[4] + K5[i] * RK_E[5] + K6[i] * RK_E[6];
-            const double sc = atol + fmax(fabs(y[i]), fabs(yn[i])) * rtol;
-            const double q = (e * h) * rcp_nr(sc);
+            const double q = err_quotient(e, h, y[i], yn[i], atol, rtol);
             se += q * q;
         }
         }
@@ -575,7 +568,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
             if (active && !fail) { h_abs = rk_accepted_h_abs<METHOD>(h_abs, error_norm, h_try, a.max_step, rejected, t_new == t_bound); accept = true; }
         } else if (active && !fail) {
             // NaN error norms land here as in scipy (comparison false) and shrink the step
-            h_abs = h_try * fmax(RK_MIN_FACTOR, RK_SAFETY * pow(error_norm, kErrExp));
+            h_abs = rk_rejected_h_abs<METHOD>(h_try, error_norm);
             rejected = true;
         }
         if (fail) {            // scipy: TOO_SMALL_STEP -> solver fails; freeze this group
@@ -599,7 +592,8 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
 #pragma unroll
                 for (int i = 0; i < 7; ++i) {
                     if constexpr (METHOD == 23) {
-                        const double kk[4] = {f[i], K1[i], K2[i], K6[i]};       // (K of rk.py: f, the two inner stages, f(y_new))
+                        // (K of rk.py: f, the two inner stages, f(y_new); this tableau's rk_dense_q stays here, see there)
+                        const double kk[4] = {f[i], K1[i], K2[i], K6[i]};
 #pragma unroll
                         for (int cc = 0; cc < 3; ++cc) {
                             double q = 0.0;
@@ -609,14 +603,8 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                         }
                         Q[i][3] = 0.0;
                     } else {
-                    const double kk[7] = {f[i], K1[i], K2[i], K3[i], K4[i], K5[i], K6[i]};
-#pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        double q = 0.0;
-#pragma unroll
-                        for (int jj = 0; jj < 7; ++jj) q += kk[jj] * RK_P[jj][cc];
-                        Q[i][cc] = q;
-                    }
+                        const double kk[7] = {f[i], K1[i], K2[i], K3[i], K4[i], K5[i], K6[i]};
+                        rk_dense_q(kk, Q[i]);
                     }
                 }
                 for (;;) {
@@ -624,19 +612,17 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                     const bool has = accept && ei < n_uni && !(te > t);
                     if (!__any(has)) break;
                     const double xx = (te - t_old) / h;
-                    const double p1 = xx, p2 = p1 * xx, p3 = p2 * xx, p4 = p3 * xx;
                     double yd[7], g[7];
 #pragma unroll
                     for (int i = 0; i < 7; ++i) {
-                        const double accq = (METHOD == 23) ? Q[i][0] * p1 + Q[i][1] * p2 + Q[i][2] * p3
-                                                            : Q[i][0] * p1 + Q[i][1] * p2 + Q[i][2] * p3 + Q[i][3] * p4;
+                        const double accq = rk_dense_at<METHOD>(Q[i], xx);
                         yd[i] = has ? h * accq + yold[i] : y[i];
                     }
                     node_integrand<DRAG, ATMO>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
                     if (has) {
                         const double d = te - te_prev;
 #pragma unroll
-                        for (int i = 0; i < 7; ++i) { acc[i] += d * (g[i] + gprev[i]) / 2.0; gprev[i] = g[i]; ylast[i] = yd[i]; }
+                        for (int i = 0; i < 7; ++i) { trapz_commit(d, g[i], gprev[i], acc[i]); ylast[i] = yd[i]; }
                         te_prev = te; ++ei;
                     }
                 }
@@ -658,17 +644,14 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                 if (T6.ferr) err = MPCX_ST_FOH;      // (what the hold's second call at this time would have flagged)
             } else {
                 time_eval(p, t, T6, err);
-                const double r[3] = {bcast8<7>(y[0]), bcast8<7>(y[1]), bcast8<7>(y[2])}, v[3] = {bcast8<7>(y[3]), bcast8<7>(y[4]), bcast8<7>(y[5])};
-                state_eval<DRAG, ATMO>(p, r, v, bcast8<7>(y[6]), T6, L6, D6);
+                double r[3], v[3], m;
+                x_column<true>(y, r, v, m);
+                state_eval<DRAG, ATMO>(p, r, v, m, T6, L6, D6);
             }
             node_columns<DRAG, ATMO>(p, y, T6, L6, D6, t, tau_k, tau_kp1, g, err);
             if (accept) {
-                const double d = h;          // ts[i+1] - ts[i]
 #pragma unroll
-                for (int i = 0; i < 7; ++i) {
-                    acc[i] += d * (g[i] + gprev[i]) / 2.0;
-                    gprev[i] = g[i];
-                }
+                for (int i = 0; i < 7; ++i) trapz_commit(h, g[i], gprev[i], acc[i]);      // ts[i+1] - ts[i] = h
             }
         }
     }

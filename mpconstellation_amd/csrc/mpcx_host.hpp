@@ -420,3 +420,32 @@ class DeviceArena {
     bool dirty_;              // transfers queued and not yet waited for
     std::vector<Out> out_;
 };
+
+// A thrust law's parameters (include/mpcx.h: ctrl_vec is [S][3] under CONSTANT, [S] magnitudes under TANGENTIAL, the tables
+// [S][3][Ku] under SEQUENCE, which also has end_tau [S]; nothing under ZERO): how many doubles ctrl_vec holds, and both arrays
+// on their way to the device -- nullptr for what the law does not have or the caller did not give (the launcher refuses that).
+inline size_t ctrl_vec_doubles(int ctrl_kind, int S, int Ku)
+{
+    if (ctrl_kind == MPCX_CTRL_CONSTANT) return (size_t)S * 3;
+    if (ctrl_kind == MPCX_CTRL_TANGENTIAL) return (size_t)S;
+    if (ctrl_kind == MPCX_CTRL_SEQUENCE) return (size_t)S * 3 * Ku;
+    return 0;
+}
+struct DeviceLaw { double *ctrl_vec, *end_tau; };
+inline DeviceLaw upload_law(DeviceArena &ar, int ctrl_kind, int S, int Ku, const double *ctrl_vec, const double *end_tau)
+{
+    const size_t nv = ctrl_vec_doubles(ctrl_kind, S, Ku);
+    DeviceLaw d;
+    d.ctrl_vec = (nv && ctrl_vec) ? ar.upload(ctrl_vec, nv) : nullptr;
+    d.end_tau = (ctrl_kind == MPCX_CTRL_SEQUENCE && end_tau) ? ar.upload(end_tau, S) : nullptr;
+    return d;
+}
+
+// Ragged rows: a rollout writes each satellite's own columns of y [S][7][K] and u [S][3][K] (u may be nullptr) and nothing behind
+// them; the unused columns are zeroed on the stream ahead of it.
+inline hipError_t zero_ragged_rows(double *y, double *u, size_t S, size_t K, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(y, 0, S * 7 * K * sizeof(double), st);
+    if (e == hipSuccess && u) e = hipMemsetAsync(u, 0, S * 3 * K * sizeof(double), st);
+    return e;
+}

@@ -42,25 +42,6 @@ struct Ctrl {
     double uk, uk1, tau_k, tau_kp1, id;
 };
 
-// 1/d and 1/sqrt(d) for d > 0 well inside the normal range: hardware seed + two Newton steps (half an ulp, measured:
-// profiles/tools/rcp_accuracy.hip) instead of the IEEE division / square-root sequences (scaling, fix-up: ~3x the
-// instructions).  The rollout is ~1000 sequential RK45 steps x 6 right-hand sides: its time is the number of
-// instructions of the right-hand side.
-__device__ __forceinline__ double rcp_fast(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) { const double e = fma(-d, r, 1.0); r = fma(r, e, r); }
-    return r;
-}
-__device__ __forceinline__ double rsq_fast(double d)
-{
-    double r = __builtin_amdgcn_rsq(d);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) { const double e = fma(-d * r, r, 1.0); r = fma(0.5 * r, e, r); }
-    return r;
-}
-
 // quad exchange: sum over the four lanes (bitwise identical on all of them: both steps add the same two operands), the two
 // rotations of the (0,1,2) triple (lane 3 keeps its own value), and the value of lane 2
 __device__ __forceinline__ double quad_sum(double v) { v += dpp64<0xB1>(v); v += dpp64<0x4E>(v); return v; }
@@ -68,10 +49,8 @@ __device__ __forceinline__ double rot1(double v) { return dpp64<0xC9>(v); }     
 __device__ __forceinline__ double rot2(double v) { return dpp64<0xD2>(v); }     // quad_perm [2,0,1,3]: lane c <- lane (c+2) mod 3
 __device__ __forceinline__ double lane2(double v) { return dpp64<0xAA>(v); }    // quad_perm [2,2,2,2]
 
-// First-order hold of this lane's row of a (3,Ku) table at tau in [0,1] (control.py:104-126), same node index as foh3:
-// k = int(tau // dtau) is the floor of the exact quotient (Python's float floor division goes through an exact fmod);
-// floor(tau * (Ku-1)) is that number unless the product sits within rounding of an integer, and only then the exact routine
-// is needed.
+// First-order hold of this lane's row of a (3,Ku) table at tau in [0,1] (control.py:104-126), foh3's node (foh_node, by its
+// quick route).
 __device__ __forceinline__ double foh_cached(double tau, Ctrl &c, int &err)
 {
     const int Ku = c.Ku;
@@ -81,15 +60,10 @@ __device__ __forceinline__ double foh_cached(double tau, Ctrl &c, int &err)
     // side is evaluated six times per step and every branch in it costs the in-order wave ~40 cycles.
     if (!(tau > c.tau_k + 1e-12 && tau < c.tau_kp1 - 1e-12)) {
     if (tau == 1.0) return u[Ku - 1];
-    const double km1 = (double)(Ku - 1);
-    const double q = tau * km1;
-    int k = (fabs(q - rint(q)) > 1e-9 * fmax(1.0, q)) ? (int)floor(q) : (int)py_floordiv(tau, 1.0 / km1);
-    if (k < 0 || k + 1 >= Ku) {          // the reference raises IndexError here
-        err = MPCX_ST_FOH;
-        k = k < 0 ? 0 : Ku - 2;
-        if (Ku < 2) return 0.0;
-    }
+    int k;
+    if (!foh_node<true>(tau, Ku, k, err)) return 0.0;
     if (k != c.kc) {
+        const double km1 = (double)(Ku - 1);
         c.kc = k;
         c.tau_k = (double)k / km1; c.tau_kp1 = (double)(k + 1) / km1;
         c.id = 1.0 / (c.tau_kp1 - c.tau_k);
@@ -101,20 +75,20 @@ __device__ __forceinline__ double foh_cached(double tau, Ctrl &c, int &err)
 }
 
 // Simulator.satellite_dynamics (simulator.py:116-161) under the controller's thrust law (control.py), times tf, for the
-// component this lane owns (r, v: its position / velocity component, m: the mass; on: lane < 3) -- the same quantities as
-// dynamics_unscaled / ctrl_eval (which the discretizer keeps using, division for division as numpy evaluates them),
-// arranged around one reciprocal each of |r|, |h|, m instead of a division per component: results differ from those forms
-// by rounding only (rollouts agree with the reference's to 1e-12, the accepted step sequence is the same -- max_step
-// clips every step).  inv_gi = 1 / (g0 Isp).
+// component this lane owns (r, v: its position / velocity component, m: the mass; on: lane < 3) -- the quantities of the plain
+// form (oracle/dynamics.c, division for division as numpy evaluates them), arranged around one reciprocal each of |r|, |h|, m
+// instead of a division per component: results differ from that form by rounding only (rollouts agree with the reference's to
+// 1e-12, the accepted step sequence is the same -- max_step clips every step).  The rollout is ~1000 sequential RK45 steps x 6
+// right-hand sides: its time is the number of instructions of this function.  inv_gi = 1 / (g0 Isp).
 template <int KIND, int FLAGS>
 __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, const double (&atm)[MPCX_NATMO], double inv_gi, double tf, double tau, int comp, bool on,
                                          double r, double v, double m, double &dr, double &dv, double &dm, int &err)
 {
     constexpr int flags = FLAGS;
     const double r2 = quad_sum(r * r);            // (lane 3 of the quad carries r = v = 0: nothing to mask in the sums)
-    const double irn = rsq_fast(r2), irn2 = irn * irn;
+    const double irn = rsq_pos(r2), irn2 = irn * irn;
     if (m <= 0.0) err = MPCX_ST_MASS;
-    const double im = rcp_fast(m > 0.0 ? m : 1.0);
+    const double im = rcp_pos(m > 0.0 ? m : 1.0);
     double u, un;
     if (KIND == MPCX_CTRL_CONSTANT) {
         u = c.vc; un = c.vn;
@@ -124,7 +98,7 @@ __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, const dou
         // norm, no rotations of the triple
         const double rv = quad_sum(r * v);
         const double w = v * r2 - r * rv;
-        const double iwn = rsq_fast(quad_sum(w * w));
+        const double iwn = rsq_pos(quad_sum(w * w));
         u = c.vc * (w * iwn);
         un = fabs(c.vc);
     } else if (KIND == MPCX_CTRL_SEQUENCE) {                  // control.py:132-142
@@ -137,7 +111,7 @@ __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, const dou
         tn = live ? tn : ((c.kc >= 0) ? 0.5 * (c.tau_k + c.tau_kp1) : 0.5);
         const double uf = foh_cached(tn, c, err);
         const double uu = quad_sum(on ? uf * uf : 0.0);
-        un = live ? uu * rsq_fast(fmax(uu, 1e-300)) : 0.0;    // |u| (0 for u = 0)
+        un = live ? uu * rsq_pos(fmax(uu, 1e-300)) : 0.0;    // |u| (0 for u = 0)
         u = (live && on) ? uf : 0.0;
     } else { u = 0.0; un = 0.0; }
     const double kg = -cst.mu * (irn2 * irn);
@@ -147,15 +121,15 @@ __device__ __forceinline__ void prop_rhs(Ctrl &c, const SatConst &cst, const dou
         const double vn = sqrt(quad_sum(v * v));
         double dens;                                         // rho / cst.rho: the fixed density, or the atmosphere's at this altitude
         if constexpr ((flags & MPCX_FLAG_ATMO) != 0) { const double p = r * cst.r0; dens = atmo_density(quad_sum(p * p), cst, atm); }
-        else dens = kRho500 / cst.rho;
-        const double coef = -0.5 * kCd * cst.s * im * dens * vn;
+        else dens = fixed_density(cst);
+        const double coef = drag_k(cst, im) * dens * vn;
         dv += coef * v;
     }
     if (flags & MPCX_FLAG_J2) {                              // simulator.py:154-158
         const double rz = lane2(r);
         const double q2 = (rz * rz) * irn2;
-        const double coef = 1.5 * cst.j2 * cst.mu * (cst.re * cst.re) * (irn2 * irn2 * irn);
-        dv += coef * ((5.0 * q2 - (comp == 2 ? 3.0 : 1.0)) * r);
+        const double coef = j2_factor(cst) * (irn2 * irn2 * irn);
+        dv += coef * (j2_bracket(q2, comp) * r);
     }
     dm = -un * inv_gi;
     dr = tf * dr; dv = tf * dv; dm = tf * dm;
@@ -205,13 +179,11 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
     {
         const double scr = atol + fabs(yr) * rtol, scv = atol + fabs(yv) * rtol, scm = atol + fabs(ym) * rtol;
         const double d0 = rms7(yr / scr, yv / scv, ym / scm), d1 = rms7(fr / scr, fv / scv, fm / scm);
-        double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-        h0 = fmin(h0, 1.0);
+        const double h0 = rk_initial_h0(d0, d1, 1.0);
         double f1r, f1v, f1m;
         prop_rhs<KIND, FLAGS>(c, cst, a.atmo, inv_gi, tf, t + h0, comp, on, yr + h0 * fr, yv + h0 * fv, ym + h0 * fm, f1r, f1v, f1m, err);
         const double d2 = rms7((f1r - fr) / scr, (f1v - fv) / scv, (f1m - fm) / scm) / h0;
-        const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? fmax(1e-6, h0 * 1e-3) : pow(0.01 / fmax(d1, d2), 0.2);
-        h_abs = fmin(fmin(100.0 * h0, h1), fmin(1.0, a.max_step));
+        h_abs = rk_initial_h_abs<45>(h0, d1, d2, 1.0, a.max_step);
     }
     const double estep = (n_eval > 1) ? 1.0 / (double)(n_eval - 1) : 0.0;
     int ei = 0, nsteps = 0;
@@ -222,15 +194,9 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
         // scipy: min_step = 10 |nextafter(t, inf) - t| <= 10 ulp(1) = 2.3e-15 for t in [0, 1]; it only guards against
         // vanishing steps, so it is evaluated only when h_abs could be anywhere near it
         const double min_step = (h_abs > 1e-12) ? 0.0 : 10.0 * fabs(nextafter(t, INFINITY) - t);
-        if (!rejected) {
-            if (h_abs > a.max_step) h_abs = a.max_step;
-            else if (h_abs < min_step) h_abs = min_step;
-        }
-        if (!(h_abs >= min_step)) { err = MPCX_ST_STEP; break; }
-        double h = h_abs, t_new = t + h;
-        if (t_new - t_bound > 0.0) t_new = t_bound;
-        h = t_new - t;
-        const double h_try = fabs(h);
+        const RkAttempt at = rk_attempt(t, t_bound, a.max_step, rejected, h_abs, min_step);
+        if (at.too_small) { err = MPCX_ST_STEP; break; }
+        const double h = at.h, t_new = at.t_new, h_try = at.h_try;
         // the six stages, each of this lane's three components with the arithmetic of the one-lane form
         double Kr[6], Kv[6], Km[6];
 #define MPCX_STAGE(S, EXPR_R, EXPR_V, EXPR_M)                                                                            \
@@ -281,16 +247,14 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
                 if (te > t_new) break;
                 const double x = (te - t) / h;
                 const double pw[4] = {x, x * x, (x * x) * x, ((x * x) * x) * x};
+                // Q's row by rk_dense_q; the polynomial is summed from 0.0 here and from its first term in rk_dense_at, which
+                // differ in the sign of a zero sum (x = 0 at the first output point): this text stays
                 auto dense = [&](double f0, const double (&K)[6], double y0) {
                     const double kk[7] = {f0, K[0], K[1], K[2], K[3], K[4], K[5]};
-                    double acc = 0.0;
+                    double q[4], acc = 0.0;
+                    rk_dense_q(kk, q);
 #pragma unroll
-                    for (int cc = 0; cc < 4; ++cc) {
-                        double q = 0.0;
-#pragma unroll
-                        for (int j = 0; j < 7; ++j) q += kk[j] * RK_P[j][cc];
-                        acc += q * pw[cc];
-                    }
+                    for (int cc = 0; cc < 4; ++cc) acc += q[cc] * pw[cc];
                     return h * acc + y0;
                 };
                 const double orr = dense(fr, Kr, yr), ov = dense(fv, Kv, yv), om = dense(fm, Km, ym);
@@ -304,7 +268,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
                     else if (KIND == MPCX_CTRL_TANGENTIAL) {
                         const double q2 = quad_sum(on ? orr * orr : 0.0), qv = quad_sum(on ? orr * ov : 0.0);
                         const double wv = ov * q2 - orr * qv;
-                        uo = c.vc * (wv * rsq_fast(quad_sum(on ? wv * wv : 0.0)));
+                        uo = c.vc * (wv * rsq_pos(quad_sum(on ? wv * wv : 0.0)));
                     } else if (KIND == MPCX_CTRL_SEQUENCE) {
                         if (te <= c.end_tau) {                       // control.py:132-142, the hold as foh3 evaluates it (divisions)
                             double o3[3];
@@ -320,7 +284,7 @@ __global__ __launch_bounds__(64) void propagate_kernel(PropArgs a)
             yr = ynr; yv = ynv; ym = ynm; fr = Kr[5]; fv = Kv[5]; fm = Km[5];
             ++nsteps;
         } else {
-            h_abs = h_try * fmax(RK_MIN_FACTOR, RK_SAFETY * pow(en, -0.2));
+            h_abs = rk_rejected_h_abs<45>(h_try, en);
             rejected = true;
         }
     }
@@ -435,23 +399,15 @@ extern "C" int mpcx_propagate_thrust_batch_ragged(mpcx_ctx *ctx, int S, int n_ev
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     double *dy0 = ar.upload(y0, (size_t)S * 7), *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST);
-    size_t nv = 0;
-    if (ctrl_kind == MPCX_CTRL_CONSTANT) nv = (size_t)S * 3;
-    else if (ctrl_kind == MPCX_CTRL_TANGENTIAL) nv = S;
-    else if (ctrl_kind == MPCX_CTRL_SEQUENCE) nv = (size_t)S * 3 * Ku;
-    double *dv = (nv && ctrl_vec) ? ar.upload(ctrl_vec, nv) : nullptr;
-    double *de = (ctrl_kind == MPCX_CTRL_SEQUENCE && end_tau) ? ar.upload(end_tau, S) : nullptr;
+    const DeviceLaw law = upload_law(ar, ctrl_kind, S, Ku, ctrl_vec, end_tau);
     int32_t *dne = n_evals ? ar.upload(n_evals, S) : nullptr, *dku = Kus ? ar.upload(Kus, S) : nullptr;
     double *dy = ar.alloc<double>((size_t)S * 7 * n_eval);
     double *du = u_out ? ar.alloc<double>((size_t)S * 3 * n_eval) : nullptr;
     int32_t *dst = ar.alloc<int32_t>(S), *dns = ar.alloc<int32_t>(S);
     if (ar.failed()) return ar.code();
-    if (n_evals) {                                                                                             // the unused columns
-        MPCX_HIP(ctx, hipMemsetAsync(dy, 0, (size_t)S * 7 * n_eval * sizeof(double), ctx->stream));
-        if (du) MPCX_HIP(ctx, hipMemsetAsync(du, 0, (size_t)S * 3 * n_eval * sizeof(double), ctx->stream));
-    }
-    int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, n_eval, dne, dy0, dtf, dc, flags, ctrl_kind, dv, Ku, dku, de, max_step, dy,
-                                                    du, dst, dns, ctx->stream);
+    if (n_evals) MPCX_HIP(ctx, zero_ragged_rows(dy, du, S, n_eval, ctx->stream));
+    int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, n_eval, dne, dy0, dtf, dc, flags, ctrl_kind, law.ctrl_vec, Ku, dku, law.end_tau,
+                                                    max_step, dy, du, dst, dns, ctx->stream);
     if (rc) return rc;
     ar.download(y_out, dy, (size_t)S * 7 * n_eval);
     if (du) ar.download(u_out, du, (size_t)S * 3 * n_eval);

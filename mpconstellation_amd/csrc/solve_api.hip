@@ -444,23 +444,15 @@ extern "C" int mpcx_scp_iteration_batch_ragged_sat(mpcx_ctx *ctx, int S, int K, 
     if (!ws) return MPCX_E_NOMEM;
     DeviceArena ar(ctx);
     double *dy0 = ar.upload(y0, (size_t)S * 7), *dtf = ar.upload(tf, S), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST), *drd = ar.upload(r_des, S);
-    size_t nv = 0;
-    if (ctrl_kind == MPCX_CTRL_CONSTANT) nv = (size_t)S * 3;
-    else if (ctrl_kind == MPCX_CTRL_TANGENTIAL) nv = S;
-    else if (ctrl_kind == MPCX_CTRL_SEQUENCE) nv = (size_t)S * 3 * Ku;
-    double *dv = (nv && ctrl_vec) ? ar.upload(ctrl_vec, nv) : nullptr;
-    double *de = (ctrl_kind == MPCX_CTRL_SEQUENCE && end_tau) ? ar.upload(end_tau, S) : nullptr;
+    const DeviceLaw law = upload_law(ar, ctrl_kind, S, Ku, ctrl_vec, end_tau);
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr, *dKus = Kus ? ar.upload(Kus, S) : nullptr;
     double *dpo = popts ? ar.upload(popts, (size_t)S * MPCX_NPOPT) : nullptr;
     double *dx = ar.alloc<double>((size_t)S * 7 * K), *du = ar.alloc<double>((size_t)S * 3 * K);
     SolveResults r(ar, S, K, nullptr);
     int32_t *dps = ar.alloc<int32_t>(S), *dpn = ar.alloc<int32_t>(S);
     if (ar.failed()) return ar.code();
-    if (Ks) {                                                                                        // the unused columns
-        MPCX_HIP(ctx, hipMemsetAsync(dx, 0, (size_t)S * 7 * K * sizeof(double), ctx->stream));
-        MPCX_HIP(ctx, hipMemsetAsync(du, 0, (size_t)S * 3 * K * sizeof(double), ctx->stream));
-    }
-    int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, K, dKs, dy0, dtf, dc, prop_flags, ctrl_kind, dv, Ku, dKus, de, prop_max_step,
+    if (Ks) MPCX_HIP(ctx, zero_ragged_rows(dx, du, S, K, ctx->stream));
+    int rc = mpcx_propagate_thrust_batch_ragged_dev(ctx, S, K, dKs, dy0, dtf, dc, prop_flags, ctrl_kind, law.ctrl_vec, Ku, dKus, law.end_tau, prop_max_step,
                                                     dx, du, dps, dpn, ctx->stream);
     if (rc) return rc;
     rc = mpcx_mpc_step_batch_ragged_sat_dev(ctx, S, K, dKs, dx, du, dtf, dc, drd, disc_flags, disc_max_step, opts, dpo, r.X, r.U, r.NU,
@@ -572,10 +564,7 @@ extern "C" int mpcx_mpc_update_batch_sat(mpcx_ctx *ctx, int S, int K, int n_scp,
         const SolvePlace at = {&ctx->ord[lane], f, split ? S : n};
         for (int it = 0; it < n_scp && rc == MPCX_OK; ++it) {
             double *Uw = dU[it & 1] + o3, *tfw = dtfu[it & 1] + o1;
-            if (Ks) {                                                                         // ragged rows: the unused columns
-                MPCX_HIP(ctx, hipMemsetAsync(dx + o7, 0, (size_t)n * 7 * K * sizeof(double), st));
-                MPCX_HIP(ctx, hipMemsetAsync(du + o3, 0, (size_t)n * 3 * K * sizeof(double), st));
-            }
+            if (Ks) MPCX_HIP(ctx, zero_ragged_rows(dx + o7, du + o3, n, K, st));
             // control.py:178-180 / :217-227: rollout under the tangential reference law, then under the sequence just optimised,
             // played over its own horizon (end_tau = 1) and sampled at int(base_res * tf_u) nodes; u_bar = extract_uk (:188)
             if (it == 0)

@@ -121,17 +121,6 @@ __device__ __forceinline__ double uni(double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// 1/d for d > 0 well inside the normal range: hardware seed + two Newton steps (the full IEEE division sequence
-// with its scaling / fix-up is not needed for pivots, slacks and determinants).  Measured on gfx950 over 1e-40..1e40
-// (profiles/tools/rcp_accuracy.hip): seed 4.5e-8 relative, one step 2.1e-15, two steps 1.1e-16 = half an ulp.
-__device__ __forceinline__ double rcp_pos(double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) { const double e = fma(-d, r, 1.0); r = fma(r, e, r); }
-    return r;
-}
-
 // c~ = |v|^2 - (r.v)^2/|r|^2 - vt_des^2 (same zero set as the quartic of optimizer.py:492-517)
 __device__ void vt_reduced(const double *x, double vt_des, double &c, double *g6, double *H36)
 {

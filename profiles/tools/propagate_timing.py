@@ -5,6 +5,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 from mpconstellation_amd import _ffi
+if os.environ.get("MPCX_LIB"): _ffi.LIB_PATH = os.path.abspath(os.environ["MPCX_LIB"])       # A/B against another build
 from mpconstellation_amd.constellation import constellation_states, normalize_batch
 lib = _ffi.load(); ctx = _ffi.context(0)
 dev = torch.device("cuda", 0)

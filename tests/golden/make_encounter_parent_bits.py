@@ -65,10 +65,10 @@ def arrays_of(res, prefix=""):
     return out
 
 
-def stored(key, a):
+def stored(key, a, big=BIG):
     """what the file keeps of result `a` under `key`"""
     a = np.ascontiguousarray(a)
-    if a.nbytes <= BIG:
+    if a.nbytes <= big:
         return {key: a}
     return {key + ".sha256": np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8), key + ".shape": np.array(a.shape, dtype=np.int64)}
 
