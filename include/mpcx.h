@@ -943,6 +943,64 @@ int mpcx_collision_probability_window_dev(mpcx_ctx *ctx, int n, const double *pa
                                           const double *half_window, int panels, double *out, int32_t *status, void *stream);
 
 /*
+ * mpcx_encounter_window: the time window of every listed row, chosen on the device -- the half_window that
+ * mpcx_collision_probability_window, mpcx_collision_window_sensitivity, mpcx_avoidance_window, mpcx_avoidance_window_refine and
+ * mpcx_collision_probability_mc take per row.  One rule whether the pair closes at km/s (a fraction of a second) or does not move at
+ * all (minutes, or the whole span): outside the window the pair's MEAN separation is more than nsigma combined sigmas, plus the summed
+ * radii, away from a collision.
+ * Arguments: those of mpcx_collision_probability_window up to mu, then max_half [n] in seconds (how far from t the search may go, per
+ * row), nsigma (positive and finite) and levels (1 .. MPCX_EW_MAX_LEVELS).
+ * The rule.  At a time tau the node of mpcx_collision_probability_window (the same device function) gives the mean relative position d
+ * and L^-1 of A = L L^T, the position block of the summed, carried 6 x 6 covariances.  With R = radius_i + radius_j,
+ *   g(tau) = |L^-1 d| - max(R, 0) |L^-1|_F - nsigma,
+ * |.|_F the Frobenius norm of the six stored entries of L^-1 summed row by row.  Since |L^-1|_F >= |L^-1|_2, g > 0 means that every
+ * point of the sphere |rho| <= R -- every relative position that is a collision -- lies more than nsigma whitened units from the
+ * mean d: |L^-1 (x - d)| >= |L^-1 d| - |L^-1|_2 |x|.  The rule is CONSERVATIVE on purpose: the Frobenius norm overstates the sphere by up to sqrt(3), so the window errs wide.
+ * tau is LIVE when g(tau) <= 0.  A scan time outside either object's span is not live.  A scan time at which the node fails
+ * numerically (a pivot of A not positive and finite, a relative speed that is not finite) cannot be ruled out: it counts as live and
+ * sets MPCX_EW_BAD_SCAN in the row's flags, whether or not it ends up inside the window.
+ * The search, for the side before t (sign -1), then for the side after it (sign +1), with H = max_half of the row: the bracket
+ * [a, b] = [0, H] of offsets from t; `levels` times: wd = (b - a) / 64, cell end l = 0 .. 63 at the offset a + (l + 1) wd (one fused
+ * multiply-add) is tested at t + sign offset, l* is the first that is not live, and [a, b] <- [a + l* wd, a + (l* + 1) wd].  No such
+ * end at the first level: the side is OPEN, its reach is H and its search stops (MPCX_EW_OPEN_BEFORE / MPCX_EW_OPEN_AFTER: the live
+ * stretch runs past max_half).  No such end at a later level: b stays and the search stops.  The side's reach is the final b, the
+ * first offset known not to be live: the window errs wide by at most one final cell, H / 64^levels.  Only the connected live stretch
+ * about t counts; a second approach of the same pair inside H is another row's (mpcx_conjunction_events lists it, and the caller
+ * bounds max_half by the spacing to the neighbouring event).  g(t) > 0 -- t itself is not live --: the row is CLEAR
+ * (MPCX_EW_CLEAR), nothing is searched and both reaches are H / 64^levels, so that every consumer still receives a positive window.
+ * out [n][MPCX_NEW] (MPCX_EW_*), flags [n] (MPCX_EW_CLEAR | MPCX_EW_OPEN_BEFORE | MPCX_EW_OPEN_AFTER | MPCX_EW_BAD_SCAN), status [n]:
+ * index, node count, span and t are tested on both objects at t as in mpcx_collision_probability_window (MPCX_ST_BADK); max_half not
+ * positive and finite: MPCX_ST_BADK; R not finite, the node failing numerically at t itself, or a g(t) that is not finite:
+ * MPCX_ST_NUMERIC.  A row whose status is not MPCX_ST_OK is NaN in every column with flags 0; the other rows are untouched by it.
+ * One wave per row, 1 + 2 levels node evaluations per lane, no atomics: a row's result depends on its own arguments alone -- not on
+ * the list's order or length, the launch or the device count.  n < 1, S < 1, K < 2, mu <= 0, a catalogue with D < 1 or cat_K < 2,
+ * nsigma not positive and finite, levels outside 1 .. MPCX_EW_MAX_LEVELS, a required array NULL: MPCX_E_BADARG, nothing enqueued.
+ * The _dev variant takes device pointers throughout and needs no workspace.
+ */
+enum { MPCX_EW_HALF = 0,        /* max(REACH_BEFORE, REACH_AFTER): what every half_window argument takes, s */
+       MPCX_EW_TA,              /* t - REACH_BEFORE and t + REACH_AFTER, cut to both objects' spans, s */
+       MPCX_EW_TB,
+       MPCX_EW_REACH_BEFORE,    /* the first offset before t known not to be live (max_half: open), s */
+       MPCX_EW_REACH_AFTER,     /* the same after t */
+       MPCX_EW_G0,              /* g(t) */
+       MPCX_NEW };
+enum { MPCX_EW_CLEAR = 1,       /* flags: g(t) > 0, nothing searched */
+       MPCX_EW_OPEN_BEFORE = 2, /* live all the way to t - max_half */
+       MPCX_EW_OPEN_AFTER = 4,  /* live all the way to t + max_half */
+       MPCX_EW_BAD_SCAN = 8 };  /* a scan time was numerically bad and counted as live */
+enum { MPCX_EW_MAX_LEVELS = 4 };
+int mpcx_encounter_window(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                          const double *units, const double *span, const double *P, const double *radius, int D, int cat_K,
+                          const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                          const double *cat_P, const double *cat_radius, double mu, const double *max_half, double nsigma, int levels,
+                          double *out, int32_t *flags, int32_t *status);
+int mpcx_encounter_window_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
+                              const double *units, const double *span, const double *P, const double *radius, int D, int cat_K,
+                              const int32_t *cat_Ks, const double *cat_Y, const double *cat_units, const double *cat_span,
+                              const double *cat_P, const double *cat_radius, double mu, const double *max_half, double nsigma,
+                              int levels, double *out, int32_t *flags, int32_t *status, void *stream);
+
+/*
  * Avoidance manoeuvres for screened pairs from thrust sensitivities.  The screens say who comes close and when, the probability how
  * much that matters; this says what to change in the plan.  For every row (i, j, distance, time t in s) of a pairs list: the
  * derivative of the encounter-plane miss with respect to every thrust node of the plan (the B-plane sensitivity), by a backward

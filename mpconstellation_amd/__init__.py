@@ -19,7 +19,7 @@ from .conjunction import (common_clock, screen, screen_against, screen_pairs, sc
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult,
                           collision_window_sensitivity, WindowSensitivityResult, avoidance_window, AvoidanceWindowResult,
                           avoidance_window_refine, AvoidanceWindowRefineResult, collision_probability_mc,
-                          MonteCarloCollisionResult)
+                          MonteCarloCollisionResult, encounter_window, EncounterWindowResult)
 
 __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer", "mpc_step_batch", "solve_batch", "solve_shared_tf", "scp_iteration_batch", "mpc_update_batch",
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
@@ -30,4 +30,5 @@ __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer
            "WindowCollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult",
            "collision_window_sensitivity", "WindowSensitivityResult", "avoidance_window", "AvoidanceWindowResult",
-           "avoidance_window_refine", "AvoidanceWindowRefineResult", "collision_probability_mc", "MonteCarloCollisionResult"]
+           "avoidance_window_refine", "AvoidanceWindowRefineResult", "collision_probability_mc", "MonteCarloCollisionResult",
+           "encounter_window", "EncounterWindowResult"]

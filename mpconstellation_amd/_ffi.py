@@ -171,6 +171,11 @@ _SIGS = {
                                           + [C.c_double, _dp, C.c_int, _dp, _ip]),
     "mpcx_collision_probability_window_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
                                               + [C.c_double, _vp, C.c_int, _vp, _vp, _vp]),
+    # the time window of every listed row, chosen on the device (after mu: max_half, nsigma, levels; out, flags, status)
+    "mpcx_encounter_window": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2
+                              + [C.c_double, _dp, C.c_double, C.c_int, _dp, _ip, _ip]),
+    "mpcx_encounter_window_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
+                                  + [C.c_double, _vp, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
     # avoidance manoeuvres for screened pairs: thrust sensitivities of the encounter-plane miss, least-effort thrust change
     "mpcx_avoidance_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "mpcx_avoidance": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp,
@@ -251,6 +256,9 @@ NPC = 6                                                                     # MP
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)
 NPW, PW_MAX_PANELS = 7, 64                                                  # MPCX_NPW: columns of mpcx_collision_probability_window's out
 PW_P, PW_START, PW_ENTRIES, PW_RATE_MAX, PW_T_RATE_MAX, PW_TA, PW_TB = range(NPW)
+NEW, EW_MAX_LEVELS = 6, 4                                                   # MPCX_NEW: columns of mpcx_encounter_window's out
+EW_HALF, EW_TA, EW_TB, EW_REACH_BEFORE, EW_REACH_AFTER, EW_G0 = range(NEW)
+EW_CLEAR, EW_OPEN_BEFORE, EW_OPEN_AFTER, EW_BAD_SCAN = 1, 2, 4, 8           # MPCX_EW_*: bits of its flags
 NAV = 10                                                                    # MPCX_NAV: columns of mpcx_avoidance's out
 AV_D0, AV_D1, AV_DM1, AV_DM2, AV_MISS1, AV_DT, AV_DV_I, AV_DV_J, AV_UMAX_I, AV_UMAX_J = range(NAV)
 NAW = 9                                                                     # MPCX_NAW: columns of mpcx_avoidance_window's out

@@ -21,6 +21,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   collision_probability_window   for encounters too slow for that model (neighbours in one shell, satellites deployed together):
                  the probability over a time window from the time-varying relative state and the full 6 x 6 covariances;
                  encounter_half_window is the window inside which the two models must agree;
+  encounter_window   that window chosen on the device for every listed row, fast or without any relative speed: the stretch of time
+                 about the row's time within nsigma combined sigmas of a collision;
   collision_probability_mc   the same rows by sampled flights through the nonlinear dynamics: initial states, masses and thrust
                  execution errors drawn, flown and counted -- what the linearised figures above are held against;
   catalogue_covariance    catalogue_trajectories followed by covariance;
@@ -783,6 +785,72 @@ def _collision_window_call(pairs, half, *, device, slot, out, rows, cols, mu, pa
     pairs, half = _ffi.as_f64(pairs), _ffi.as_f64(half)
     _ffi.call("mpcx_collision_probability_window", _context(device, slot), len(pairs), _ffi.dptr(pairs), *_side_args(rows, 2), *_side_args(cols, 2),
               mu, _ffi.dptr(half), panels, _ffi.dptr(out["out"]), _ffi.iptr(out["status"]))
+
+
+# ---- the window of every listed row, chosen on the device (include/mpcx.h: mpcx_encounter_window; csrc/encounter_window.hip)
+DEFAULT_NSIGMA, DEFAULT_LEVELS = 8, 3
+
+
+class EncounterWindowResult:
+    """For the n rows of `pairs` (i, j, distance, time), row for row: half (n,) seconds, what every half_window argument takes (the
+    larger of the two reaches); window (n, 2) = (t - reach before, t + reach after) cut to both objects' spans; reach (n, 2) the
+    first offsets before and after t known not to be live; g0 (n,) = g(t); flags (n,) int32 (1 clear, 2 open before, 4 open after, 8 a
+    scan time was numerically bad and counted as live) with clear (n,) bool and open (n, 2) bool read from them; status (n,) int32
+    MPCX_ST_* (a row whose status is not 0 is NaN in every column with flags 0)."""
+
+    def __init__(self, pairs, out, flags, status):
+        self.pairs, self.flags, self.status = pairs, flags, status
+        self.half, self.window, self.g0 = out[:, _ffi.EW_HALF], out[:, _ffi.EW_TA:_ffi.EW_TB + 1], out[:, _ffi.EW_G0]
+        self.reach = out[:, _ffi.EW_REACH_BEFORE:_ffi.EW_REACH_AFTER + 1]
+        self.clear = (flags & _ffi.EW_CLEAR) != 0
+        self.open = np.column_stack([(flags & _ffi.EW_OPEN_BEFORE) != 0, (flags & _ffi.EW_OPEN_AFTER) != 0])
+
+    def __repr__(self):
+        return f"EncounterWindowResult(pairs={len(self.pairs)}, clear={int(self.clear.sum())}, open={int(self.open.any(axis=1).sum())})"
+
+
+def _check_search(max_half, nsigma, levels, n):
+    """the search of every row of a list of n -> (max_half (n,), nsigma, levels)"""
+    max_half = _per_row(max_half, n, "max_half", "seconds")
+    if np.ndim(nsigma) != 0 or isinstance(nsigma, str) or not (nsigma > 0.0 and np.isfinite(nsigma)):
+        raise ValueError(f"nsigma: need a positive finite number, got {nsigma}")
+    if np.ndim(levels) != 0 or isinstance(levels, str) or int(levels) != levels or not 1 <= levels <= _ffi.EW_MAX_LEVELS:
+        raise ValueError(f"levels: need an integer in 1 .. {_ffi.EW_MAX_LEVELS}, got {levels}")
+    return max_half, float(nsigma), int(levels)
+
+
+def encounter_window(pairs, radius, Y, units, span, P, max_half, nsigma=DEFAULT_NSIGMA, levels=DEFAULT_LEVELS, ns=None, cat=None, mu=None,
+                     device=0, devices=None):
+    """The time window about every listed row's own time outside which the pair's mean separation is more than nsigma combined
+    sigmas, plus the summed radii, away from a collision -> EncounterWindowResult, whose .half is what collision_probability_window,
+    collision_window_sensitivity, avoidance_window, avoidance_window_refine and collision_probability_mc take as half_window.  One
+    rule for a crossing at km/s (a fraction of a second) and for a pair without relative motion (minutes, or all of max_half), where
+    encounter_half_window has no answer.  pairs: (n, 4) rows (i, j, distance, time in s), a ConjunctionResult or an EncounterEvents;
+    radius, Y, units, span, P [, ns], cat and mu exactly as collision_probability_window takes them; max_half a scalar or (n,) of
+    seconds: how far from the row's time the search may go -- for the events of one pair, at most the spacing to the neighbouring
+    event, since only the connected stretch about the row's time counts.  A time tau is live when |L^-1 d| - max(R, 0) |L^-1|_F -
+    nsigma <= 0, with the mean relative position d and the Cholesky factor L of the combined position covariance at tau as
+    collision_probability_window forms them; the Frobenius norm makes the rule conservative (include/mpcx.h).  Each side of the row's
+    time is searched by `levels` (1 .. 4) refinements of 64 cells: a reach errs wide by at most max_half / 64^levels.  A side that
+    is live all the way to max_half is open (its reach is max_half); a row whose own time is not live is clear and gets the smallest
+    window, max_half / 64^levels.  A max_half that is not positive and finite is status 9 for that row.  An empty list returns empty
+    arrays without a library call.  devices=[d0, d1, ...]: contiguous blocks of the list's rows on several devices (every device
+    holds all trajectories), written in place, the bits of one device."""
+    pairs = _as_pairs(pairs)
+    how = dict(rows=_check_side(Y, units, span, P, radius, ns), cols=_check_cat_radii(cat), mu=_check_mu(mu))
+    n = pairs.shape[0]
+    max_half, how["nsigma"], how["levels"] = _check_search(max_half, nsigma, levels, n)
+    out = dict(out=np.empty((n, _ffi.NEW)), flags=np.zeros(n, dtype=np.int32), status=np.zeros(n, dtype=np.int32))
+    if n:
+        dispatch(_encounter_window_call, [pairs, max_half], out, device, devices, **how)
+    return EncounterWindowResult(pairs, out["out"], out["flags"], out["status"])
+
+
+def _encounter_window_call(pairs, max_half, *, device, slot, out, rows, cols, mu, nsigma, levels):
+    """one block of the list's rows on context (device, slot), into `out` (the block's views)"""
+    pairs, max_half = _ffi.as_f64(pairs), _ffi.as_f64(max_half)
+    _ffi.call("mpcx_encounter_window", _context(device, slot), len(pairs), _ffi.dptr(pairs), *_side_args(rows, 2), *_side_args(cols, 2), mu,
+              _ffi.dptr(max_half), nsigma, levels, _ffi.dptr(out["out"]), _ffi.iptr(out["flags"]), _ffi.iptr(out["status"]))
 
 
 # ---- the same list by sampled flights through the truth model (include/mpcx.h: mpcx_collision_probability_mc; csrc/collision_mc.hip)

@@ -399,6 +399,37 @@ class ConstellationMPC:
         w, screened, where = self._screen_plan(threshold_m, samples_per_node, max_pairs, trajectories)
         return w, screened, self._plan_covariance(w, P0, q, execution, mass_var0), dict(ns=w["ns"], cat=cat, **where)
 
+    @staticmethod
+    def _window_choice(half_window, max_half, nsigma):
+        """half_window of the window methods, tested before anything is screened: a number or one per listed pair (False; max_half
+        belongs to 'auto' and is refused), or the string 'auto' (True) with max_half None, a positive finite scalar or an array of
+        them, and a positive finite nsigma"""
+        if not isinstance(half_window, str):
+            if max_half is not None:
+                raise ValueError("max_half: goes with half_window='auto'; a given half_window is used as it is")
+            return False
+        if half_window != "auto":
+            raise ValueError(f"half_window: expected seconds (a scalar or one per listed pair) or 'auto', got {half_window!r}")
+        if max_half is not None:
+            mh = np.asarray(max_half)
+            if mh.ndim > 1 or mh.dtype.kind not in "iuf" or not (np.isfinite(mh).all() and (mh > 0.0).all()):
+                raise ValueError(f"max_half: need positive finite seconds (a scalar or one per listed pair) or None, got {max_half!r}")
+        if np.ndim(nsigma) != 0 or isinstance(nsigma, str) or not (nsigma > 0.0 and np.isfinite(nsigma)):
+            raise ValueError(f"nsigma: need a positive finite number, got {nsigma!r}")
+        return True
+
+    def _chosen_window(self, auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan):
+        """-> (the half_window the window calls receive, what the method's tuple gains): the given one and nothing; with 'auto' the
+        .half of conjunction.encounter_window on the screened rows, the plan and its covariance -- max_half None: half the plan's
+        common span -- and that EncounterWindowResult"""
+        if not auto:
+            return half_window, ()
+        from . import conjunction as cj
+        if max_half is None:
+            max_half = 0.5 * (w["T1"] - w["T0"])
+        chosen = cj.encounter_window(screened, radius_m, w["Y"], w["units"], w["span"], P, max_half, nsigma=nsigma, **plan)
+        return chosen.half, (chosen,)
+
     def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None, execution=None,
                               mass_var0=None):
         """Collision probabilities of the last plan's close approaches -> (ConjunctionResult, CollisionResult).  The plan is screened
@@ -415,55 +446,67 @@ class ConstellationMPC:
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan)
 
     def collision_probability_window(self, threshold_m, P0, radius_m, half_window, panels=4, q=None, samples_per_node=4, max_pairs=None,
-                                     catalogue=None, execution=None, mass_var0=None):
+                                     catalogue=None, execution=None, mass_var0=None, *, max_half=None, nsigma=8):
         """collision_probability and the window probability of the same rows -> (ConjunctionResult, CollisionResult,
         WindowCollisionResult).  The screening arguments, P0, radius_m, q and catalogue are collision_probability's, and the first two
         results are what it returns; every listed pair also gets its probability over [t - half_window, t + half_window]
         (conjunction.collision_probability_window on the same plan, covariances and radii; half_window a scalar or one per listed
         pair, in seconds; panels as there).  For the pairs of a constellation that pass each other slowly the short-encounter figure
-        is outside its model, and without relative speed it fails: the window figure is the one to read there.  The plan only."""
+        is outside its model, and without relative speed it fails: the window figure is the one to read there.  half_window='auto':
+        every listed pair's window is chosen on the device (conjunction.encounter_window on the same rows, plan, covariances and radii,
+        searching max_half seconds to either side -- a scalar or one per listed pair; None: half the plan's common span -- for the
+        stretch within nsigma combined sigmas of a collision), its .half is what the window call receives, and the
+        EncounterWindowResult is returned as a fourth element.  The plan only."""
         from . import conjunction as cj
+        auto = self._window_choice(half_window, max_half, nsigma)
         w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0)
+        half_window, chosen = self._chosen_window(auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan)
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
-                cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan))
+                cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan)) + chosen
 
     def collision_probability_mc(self, threshold_m, P0, radius_m, half_window, samples, seed=0, execution=None, mass_var0=None, scan=64,
                                  panels=4, model="plan", samples_per_node=4, max_pairs=None, prop_max_step=1e-3, max_flights=0,
-                                 return_samples=False, return_trajectories=False):
+                                 return_samples=False, return_trajectories=False, *, max_half=None, nsigma=8):
         """The window probability of the last plan's close approaches and its Monte Carlo counterpart side by side ->
         (ConjunctionResult, WindowCollisionResult, MonteCarloCollisionResult).  The plan is screened at threshold_m inside the
         constellation; the window figure is conjunction.collision_probability_window on plan_covariance(P0, execution=execution,
         mass_var0=mass_var0) -- no acceleration noise: the samples have none --; the sampled figure is
         conjunction.collision_probability_mc on the same rows, plan, P0, execution errors and radii: `samples` worlds drawn with
         `seed` and flown under model = 'plan' (plan_drag, plan_J2, what the covariance was linearised under) or 'truth' (the model the
-        segments are flown with).  The plan only."""
+        segments are flown with).  half_window='auto' with max_half and nsigma as in collision_probability_window: both figures run
+        over the chosen windows and the EncounterWindowResult is a fourth element.  The plan only."""
         from . import conjunction as cj
+        auto = self._window_choice(half_window, max_half, nsigma)
         w, screened, P, plan = self._plan_probabilities(threshold_m, P0, None, samples_per_node, max_pairs, None, execution, mass_var0)
         plan.pop("cat")
+        half_window, chosen = self._chosen_window(auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan)
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.collision_probability_mc(screened, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P0, half_window, samples,
                                             seed=seed, scan=scan, execution=execution, mass_var0=mass_var0, prop_max_step=prop_max_step,
                                             max_flights=max_flights, return_samples=return_samples, return_trajectories=return_trajectories,
-                                            **self._conjunction_model(model), **plan))
+                                            **self._conjunction_model(model), **plan)) + chosen
 
     def avoidance_window(self, threshold_m, P0, radius_m, half_window, target_p, panels=4, q=None, samples_per_node=4, max_pairs=None,
-                         catalogue=None, who="i", tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL):
+                         catalogue=None, who="i", tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, *, max_half=None, nsigma=8):
         """Avoidance for the last plan's slow close approaches -> (ConjunctionResult, WindowCollisionResult, AvoidanceWindowResult).
         The plan is screened and its covariance propagated exactly as collision_probability_window does (the same arguments);
         every listed pair gets its window probability and the thrust change of conjunction.avoidance_window on (plan X, plan U,
         plan_tf, plan_K) under the planning model's flags and atmosphere that brings that probability down to target_p; who = 'i',
         'j' or 'both' (inside the constellation) says which satellite of a pair moves.  AvoidanceWindowResult.apply(plan U, row) is
         the changed thrust table.  The covariances are not propagated again under the manoeuvre and nothing is flown
-        (avoidance_window_refine does both).  The plan only."""
+        (avoidance_window_refine does both).  half_window='auto' with max_half and nsigma as in collision_probability_window: the
+        probability and the manoeuvre run over the chosen windows and the EncounterWindowResult is a fourth element.  The plan only."""
         from . import conjunction as cj
+        auto = self._window_choice(half_window, max_half, nsigma)
         w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue)
+        half_window, chosen = self._chosen_window(auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan)
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.avoidance_window(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
-                                    panels=panels, who=who, tol=tol, max_eval=max_eval, **self._conjunction_model(), **plan))
+                                    panels=panels, who=who, tol=tol, max_eval=max_eval, **self._conjunction_model(), **plan)) + chosen
 
     def avoidance_window_refine(self, threshold_m, P0, radius_m, half_window, target_p, rounds=2, model="plan", recov=True, panels=4, q=None,
                                 samples_per_node=4, max_pairs=None, catalogue=None, who="i", track=True, max_shift=None,
-                                tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, prop_max_step=1e-3):
+                                tol=_ffi.AW_DEFAULT_TOL, max_eval=_ffi.AW_DEFAULT_MAX_EVAL, prop_max_step=1e-3, *, max_half=None, nsigma=8):
         """avoidance_window's manoeuvres flown again, re-evaluated and corrected `rounds` times on the device -> (ConjunctionResult,
         WindowCollisionResult, AvoidanceWindowRefineResult).  The plan is screened and its covariance propagated exactly as
         avoidance_window does (the same arguments); every listed pair then goes through conjunction.avoidance_window_refine on (plan X,
@@ -471,15 +514,19 @@ class ConstellationMPC:
         time), with recov the covariances of the satellites that move are propagated again along every flight with the same q.  model
         = 'plan' flies and linearises under the planning model (plan_drag, plan_J2), 'truth' under the model the segments are flown
         with (include_drag, include_J2, the atmosphere).  Nothing is installed: the manoeuvres are row-private, and two rows that move
-        one satellite can conflict (AvoidanceWindowRefineResult.apply(plan U, row) is one row's changed thrust table).  The plan
+        one satellite can conflict (AvoidanceWindowRefineResult.apply(plan U, row) is one row's changed thrust table).
+        half_window='auto' with max_half and nsigma as in collision_probability_window: the windows are chosen once, on the plan as it
+        stands (they do not follow the manoeuvre from pass to pass), and the EncounterWindowResult is a fourth element.  The plan
         only."""
         from . import conjunction as cj
+        auto = self._window_choice(half_window, max_half, nsigma)
         flight = self._conjunction_model(model)
         w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue)
+        half_window, chosen = self._chosen_window(auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan)
         return (screened, cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan),
                 cj.avoidance_window_refine(screened, target_p, radius_m, w["Y"], self._plan[1], w["units"], w["span"], self.consts, P, half_window,
                                            rounds=rounds, track=(w["M"], w["T0"], w["T1"]) if track else None, max_shift=max_shift, recov=recov,
-                                           q=q, prop_max_step=prop_max_step, panels=panels, who=who, tol=tol, max_eval=max_eval, **flight, **plan))
+                                           q=q, prop_max_step=prop_max_step, panels=panels, who=who, tol=tol, max_eval=max_eval, **flight, **plan)) + chosen
 
     def _screened_plan(self, threshold_m, samples_per_node, max_pairs, catalogue, P0, q):
         """what `avoidance` and `avoidance_joint` start from: the plan's screen window, its pairs list at threshold_m (inside the

@@ -2,7 +2,8 @@
 // (collision_device.hpp), whose cp_state, CP_GL and butterflies they use.
 //   an object at a time node       cw_covariance_add (the nearest node's 6 x 6 covariance carried over, added to the pair's sum)
 //   the relative state at a node   cw_node: mean (d, w), the sphere rule's frame (cw_pole), the Cholesky factor of the position block
-//                                  and what the conditional velocity needs of the other blocks (cw_factor)
+//                                  and what the conditional velocity needs of the other blocks (cw_factor); encounter_window.hip
+//                                  calls cw_node as it stands for its d and L^-1
 //   a row of the list              cw_row (its own tests: the window, the radius), cw_out, cw_out_empty, cw_store (its row of `out`)
 //   the sphere                     cw_point (point (j, k) of the 512), cw_whiten, cw_rate (the entry rate), cw_ball_share (a lane's
 //                                  64 points of the ball term)
