@@ -237,6 +237,9 @@ struct AvCall : EncProblem {
     int32_t *status;
 };
 
+// the arguments of both entry points as an AvCall
+#define MPCX_AV_CALL AvCall{MPCX_ENC_PROBLEM(nullptr, nullptr, target), who, out, du, sens, status}
+
 static int av_check(mpcx_ctx *ctx, const AvCall &c)
 {
     if (int rc = enc_check(ctx, c, "avoidance", c.out && c.du && c.status, "out, du and status")) return rc;
@@ -249,8 +252,8 @@ static int av_enqueue(mpcx_ctx *ctx, const AvCall &c, void *workspace, hipStream
 {
     const AvWorkspace ws(workspace, c.n, c.S, c.K);
     if (int rc = enc_linearise(ctx, c, ws, st)) return rc;
-    const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, nullptr};
-    const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, nullptr} : row;
+    CpSide row, col;
+    enc_sides(c, row, col);
     const AvArgs a{c.n, c.K, c.cat_Y ? 1 : 2, c.who, c.pairs, row, col, c.P != nullptr, ws.stage, ws.dstat, c.mu, c.target,
                    c.out, c.du, c.sens ? c.sens : ws.g, c.sens != nullptr, c.status};
     hipLaunchKernelGGL(avoidance_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
@@ -275,8 +278,7 @@ extern "C" int mpcx_avoidance_dev(mpcx_ctx *ctx, int n, const double *pairs, int
                                   double *sens, int32_t *status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AvCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                    mu, target}, who, out, du, sens, status};
+    const AvCall c = MPCX_AV_CALL;
     if (int rc = av_check(ctx, c)) return rc;
     if (!workspace) return ctx_fail(ctx, MPCX_E_BADARG, "avoidance: a workspace of mpcx_avoidance_workspace_bytes(n, S, K) bytes is required");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
@@ -290,25 +292,17 @@ extern "C" int mpcx_avoidance(mpcx_ctx *ctx, int n, const double *pairs, int S, 
                               int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AvCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                    mu, target}, who, out, du, sens, status};
+    const AvCall c = MPCX_AV_CALL;
     if (int rc = av_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     AvCall d = c;
     const size_t NS = cat_Y ? 1 : 2;
     enc_upload(ar, d);
-    d.out = ar.alloc<double>((size_t)n * MPCX_NAV);
-    d.du = ar.alloc<double>((size_t)n * NS * 3 * K);
-    d.sens = sens ? ar.alloc<double>((size_t)n * NS * 9 * K) : nullptr;
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, mpcx_avoidance_workspace_bytes(n, S, K));
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = av_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NAV);
-    ar.download(du, d.du, (size_t)n * NS * 3 * K);
-    if (sens) ar.download(sens, d.sens, (size_t)n * NS * 9 * K);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    d.out = ar.result(out, (size_t)n * MPCX_NAV);
+    d.du = ar.result(du, (size_t)n * NS * 3 * K);
+    d.sens = ar.result(sens, (size_t)n * NS * 9 * K);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, mpcx_avoidance_workspace_bytes(n, S, K), [&](void *ws, hipStream_t st) { return av_enqueue(ctx, d, ws, st); });
 }
+#undef MPCX_AV_CALL

@@ -526,6 +526,11 @@ struct AjCall : EncProblem {
     int32_t *sat_status, *row_status;
 };
 
+// the arguments of an entry point as an AjCall; SAT0, NSAT: the block of satellites it computes
+#define MPCX_AJ_CALL(SAT0, NSAT)                                                                                                   \
+    AjCall{MPCX_ENC_PROBLEM(nullptr, nullptr, target), mover, u_max, hold_terminal, tol, max_iter, SAT0, NSAT, du, sat_out, row_out, \
+           rows, tsens, sat_status, row_status}
+
 static int aj_check(mpcx_ctx *ctx, const AjCall &c)
 {
     if (int rc = enc_check(ctx, c, "avoidance_joint", c.du && c.sat_out && c.row_out && c.sat_status && c.row_status,
@@ -538,21 +543,27 @@ static int aj_check(mpcx_ctx *ctx, const AjCall &c)
     return MPCX_OK;
 }
 
+// the device array of a result of the joint call: on its way back whole, or (a block of satellites) for the caller to download in parts
+template <typename T> static T *aj_out(DeviceArena &ar, bool whole, T *host, size_t len)
+{
+    return whole ? ar.result(host, len) : host ? ar.alloc<T>(len) : nullptr;
+}
+
 // the problem's and the joint call's own host arrays replaced by copies on the device, and the device arrays of its results: they
 // have the caller's shapes, whatever block of satellites the call computes
-static void aj_stage(DeviceArena &ar, AjCall &d)
+static void aj_stage(DeviceArena &ar, AjCall &d, bool whole)
 {
     const size_t n = (size_t)d.n, S = (size_t)d.S, K = (size_t)d.K;
     enc_upload(ar, d);
     d.mover = d.mover ? ar.upload(d.mover, n) : nullptr;
     d.u_max = d.u_max ? ar.upload(d.u_max, S) : nullptr;
-    d.du = ar.alloc<double>(S * 3 * K);
-    d.sat_out = ar.alloc<double>(S * MPCX_NAJ);
-    d.row_out = ar.alloc<double>(n * MPCX_NAR);
-    d.rows = d.rows ? ar.alloc<double>(n * 3 * K) : nullptr;
-    d.tsens = d.tsens ? ar.alloc<double>(S * 18 * K) : nullptr;
-    d.sat_status = ar.alloc<int32_t>(S);
-    d.row_status = ar.alloc<int32_t>(n);
+    d.du = aj_out(ar, whole, d.du, S * 3 * K);
+    d.sat_out = aj_out(ar, whole, d.sat_out, S * MPCX_NAJ);
+    d.row_out = aj_out(ar, whole, d.row_out, n * MPCX_NAR);
+    d.rows = aj_out(ar, whole, d.rows, n * 3 * K);
+    d.tsens = aj_out(ar, whole, d.tsens, S * 18 * K);
+    d.sat_status = aj_out(ar, whole, d.sat_status, S);
+    d.row_status = aj_out(ar, whole, d.row_status, n);
 }
 
 // what a pass of the refinement adds to the joint call (all NULL / 0 with solve = 1: the joint call)
@@ -574,8 +585,7 @@ static int aj_enqueue(mpcx_ctx *ctx, const AjCall &c, void *workspace, hipStream
     a.n = c.n; a.S = c.S; a.K = c.K; a.sat0 = c.sat0; a.nsat = c.nsat; a.have_cat = c.cat_Y != nullptr; a.have_P = c.P != nullptr;
     a.hold = c.hold_terminal != 0; a.max_iter = c.max_iter;
     a.pairs = c.pairs; a.mover = c.mover;
-    a.row = CpSide{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, nullptr};
-    a.col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, nullptr} : a.row;
+    enc_sides(c, a.row, a.col);
     a.U = c.U; a.stage = ws.stage; a.dstat = ws.dstat; a.u_max = c.u_max;
     a.mu = c.mu; a.target = c.target; a.tol = c.tol;
     a.g = ws.g; a.a = c.rows ? c.rows : ws.a; a.info = ws.info; a.owner = ws.owner;
@@ -614,8 +624,7 @@ extern "C" int mpcx_avoidance_joint_dev(mpcx_ctx *ctx, int n, const double *pair
                                         int32_t *row_status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AjCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                    mu, target}, mover, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    const AjCall c = MPCX_AJ_CALL(sat0, nsat);
     if (int rc = aj_check(ctx, c)) return rc;
     if (!workspace)
         return ctx_fail(ctx, MPCX_E_BADARG, "avoidance_joint: a workspace of mpcx_avoidance_joint_workspace_bytes(n, S, K) bytes is required");
@@ -631,14 +640,13 @@ extern "C" int mpcx_avoidance_joint(mpcx_ctx *ctx, int n, const double *pairs, c
                                     double *sat_out, double *row_out, double *rows, double *tsens, int32_t *sat_status, int32_t *row_status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const AjCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                    mu, target}, mover, u_max, hold_terminal, tol, max_iter, sat0, nsat, du, sat_out, row_out, rows, tsens, sat_status, row_status};
+    const AjCall c = MPCX_AJ_CALL(sat0, nsat);
     if (int rc = aj_check(ctx, c)) return rc;
     if (int rc = check_mover(ctx, c, mover, "avoidance_joint")) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     AjCall d = c;
-    aj_stage(ar, d);
+    aj_stage(ar, d, false);
     if (ar.failed()) return ar.code();
     void *ws = ctx_workspace(ctx, mpcx_avoidance_joint_workspace_bytes(n, S, K));
     if (!ws) return MPCX_E_NOMEM;
@@ -894,10 +902,9 @@ extern "C" size_t mpcx_avoidance_refine_workspace_bytes(int n, int S, int K, int
 }
 
 // the arguments of the four entry points below as an ArCall; TRACK, SHIFT: the re-screen's mode
-#define MPCX_AR_CALL(TRACK, SHIFT)                                                                                                          \
-    ArCall{AjCall{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,   \
-                   mu, target}, mover, u_max, hold_terminal, tol, max_iter, 0, S, du, sat_out, row_out, rows, tsens, sat_status, row_status}, \
-           M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, rhs_term, TRACK, SHIFT}
+#define MPCX_AR_CALL(TRACK, SHIFT)                                                                                                   \
+    ArCall{MPCX_AJ_CALL(0, S), M, T0, T1, prop_max_step, rounds, Y_out, pairs_out, hist_d0, hist_tca, hist_term, rounds_done, rhs_rows, \
+           rhs_term, TRACK, SHIFT}
 
 namespace mpcx {
 
@@ -920,33 +927,16 @@ static int ar_host(mpcx_ctx *ctx, const ArCall &c)
     DeviceArena ar(ctx);
     ArCall d = c;
     AjCall &j = d.j;
-    aj_stage(ar, j);
+    aj_stage(ar, j, true);
     const int n = c.j.n, S = c.j.S, K = c.j.K;
     const size_t np = (size_t)c.rounds + 2;
-    d.Y_out = ar.alloc<double>((size_t)S * 7 * K); d.pairs_out = ar.alloc<double>((size_t)n * 4);
-    d.hist_d0 = ar.alloc<double>(np * n); d.hist_tca = ar.alloc<double>(np * n); d.hist_term = ar.alloc<double>(np * S);
-    d.rounds_done = ar.alloc<int32_t>(S);
-    d.rhs_rows = c.rhs_rows ? ar.alloc<double>((size_t)n) : nullptr;
-    d.rhs_term = c.rhs_term ? ar.alloc<double>((size_t)S * 6) : nullptr;
-    const size_t wbytes = mpcx_avoidance_refine_workspace_bytes(n, S, K, c.j.cat_Y ? c.j.D : 0, c.M);
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, wbytes);
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = ar_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(c.j.du, j.du, (size_t)S * 3 * K);
-    ar.download(c.j.sat_out, j.sat_out, (size_t)S * MPCX_NAJ);
-    ar.download(c.j.row_out, j.row_out, (size_t)n * MPCX_NAR);
-    if (c.j.rows) ar.download(c.j.rows, j.rows, (size_t)n * 3 * K);
-    if (c.j.tsens) ar.download(c.j.tsens, j.tsens, (size_t)S * 18 * K);
-    ar.download(c.j.sat_status, j.sat_status, (size_t)S);
-    ar.download(c.j.row_status, j.row_status, (size_t)n);
-    ar.download(c.Y_out, d.Y_out, (size_t)S * 7 * K);
-    ar.download(c.pairs_out, d.pairs_out, (size_t)n * 4);
-    ar.download(c.hist_d0, d.hist_d0, np * n); ar.download(c.hist_tca, d.hist_tca, np * n); ar.download(c.hist_term, d.hist_term, np * S);
-    ar.download(c.rounds_done, d.rounds_done, (size_t)S);
-    if (c.rhs_rows) ar.download(c.rhs_rows, d.rhs_rows, (size_t)n);
-    if (c.rhs_term) ar.download(c.rhs_term, d.rhs_term, (size_t)S * 6);
-    return ar.finish();
+    d.Y_out = ar.result(c.Y_out, (size_t)S * 7 * K); d.pairs_out = ar.result(c.pairs_out, (size_t)n * 4);
+    d.hist_d0 = ar.result(c.hist_d0, np * n); d.hist_tca = ar.result(c.hist_tca, np * n); d.hist_term = ar.result(c.hist_term, np * S);
+    d.rounds_done = ar.result(c.rounds_done, (size_t)S);
+    d.rhs_rows = ar.result(c.rhs_rows, (size_t)n);
+    d.rhs_term = ar.result(c.rhs_term, (size_t)S * 6);
+    return host_run(ctx, ar, mpcx_avoidance_refine_workspace_bytes(n, S, K, c.j.cat_Y ? c.j.D : 0, c.M),
+                    [&](void *ws, hipStream_t st) { return ar_enqueue(ctx, d, ws, st); });
 }
 
 }  // namespace mpcx
@@ -1005,3 +995,4 @@ extern "C" int mpcx_avoidance_refine_tracked(mpcx_ctx *ctx, int n, const double 
     return ar_host(ctx, MPCX_AR_CALL(true, max_shift));
 }
 #undef MPCX_AR_CALL
+#undef MPCX_AJ_CALL

@@ -173,18 +173,11 @@ extern "C" int mpcx_avoidance_window(mpcx_ctx *ctx, int n, const double *pairs, 
     DeviceArena ar(ctx);
     AwCall d = c;
     const size_t NS = cat_Y ? 1 : 2;
-    cws_upload(ar, d);
-    d.out = ar.alloc<double>((size_t)n * MPCX_NAW);
-    d.du = ar.alloc<double>((size_t)n * NS * 3 * K);
-    d.sens = sens ? ar.alloc<double>((size_t)n * NS * 3 * K) : nullptr;
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, mpcx_avoidance_window_workspace_bytes(n, S, K, panels));
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = aw_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NAW);
-    ar.download(du, d.du, (size_t)n * NS * 3 * K);
-    if (sens) ar.download(sens, d.sens, (size_t)n * NS * 3 * K);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    enc_upload(ar, d); d.half = ar.upload(half_window, (size_t)n);
+    d.out = ar.result(out, (size_t)n * MPCX_NAW);
+    d.du = ar.result(du, (size_t)n * NS * 3 * K);
+    d.sens = ar.result(sens, (size_t)n * NS * 3 * K);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, mpcx_avoidance_window_workspace_bytes(n, S, K, panels),
+                    [&](void *ws, hipStream_t st) { return aw_enqueue(ctx, d, ws, st); });
 }

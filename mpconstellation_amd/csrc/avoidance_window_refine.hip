@@ -466,28 +466,17 @@ extern "C" int mpcx_avoidance_window_refine(mpcx_ctx *ctx, int n, const double *
     DeviceArena ar(ctx);
     AwrCall d = c;
     const size_t NS = cat_Y ? 1 : 2, V = (size_t)n * NS, np = (size_t)rounds + 2;
-    cws_upload(ar, d.w);
+    enc_upload(ar, d.w); d.w.half = ar.upload(half_window, (size_t)n);
     d.q = recov && q ? ar.upload(q, (size_t)S) : nullptr;
-    d.w.out = ar.alloc<double>((size_t)n * MPCX_NAW);
-    d.w.du = ar.alloc<double>(V * 3 * K);
-    d.w.sens = sens ? ar.alloc<double>(V * 3 * K) : nullptr;
-    d.w.status = ar.alloc<int32_t>(n);
-    d.rounds_done = ar.alloc<int32_t>(n);
-    d.Y_out = ar.alloc<double>(V * 7 * K);
-    d.P_out = recov && P_out ? ar.alloc<double>(V * K * 36) : nullptr;
-    d.hist_p = ar.alloc<double>(np * n); d.hist_t = ar.alloc<double>(np * n); d.hist_pred = ar.alloc<double>((np - 1) * n);
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, mpcx_avoidance_window_refine_workspace_bytes(n, S, K, cat_Y ? D : 0, M, panels));
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = awr_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(out, d.w.out, (size_t)n * MPCX_NAW);
-    ar.download(du, d.w.du, V * 3 * K);
-    if (sens) ar.download(sens, d.w.sens, V * 3 * K);
-    ar.download(status, d.w.status, n);
-    ar.download(rounds_done, d.rounds_done, n);
-    ar.download(Y_out, d.Y_out, V * 7 * K);
-    if (d.P_out) ar.download(P_out, d.P_out, V * K * 36);
-    ar.download(hist_p, d.hist_p, np * n); ar.download(hist_t, d.hist_t, np * n); ar.download(hist_pred, d.hist_pred, (np - 1) * n);
-    return ar.finish();
+    d.w.out = ar.result(out, (size_t)n * MPCX_NAW);
+    d.w.du = ar.result(du, V * 3 * K);
+    d.w.sens = ar.result(sens, V * 3 * K);
+    d.w.status = ar.result(status, (size_t)n);
+    d.rounds_done = ar.result(rounds_done, (size_t)n);
+    d.Y_out = ar.result(Y_out, V * 7 * K);
+    d.P_out = ar.result(recov ? P_out : nullptr, V * K * 36);
+    d.hist_p = ar.result(hist_p, np * n); d.hist_t = ar.result(hist_t, np * n); d.hist_pred = ar.result(hist_pred, (np - 1) * n);
+    return host_run(ctx, ar, mpcx_avoidance_window_refine_workspace_bytes(n, S, K, cat_Y ? D : 0, M, panels),
+                    [&](void *ws, hipStream_t st) { return awr_enqueue(ctx, d, ws, st); });
 }
 #undef MPCX_AWR_CALL

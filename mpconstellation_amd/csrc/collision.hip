@@ -192,31 +192,17 @@ __global__ __launch_bounds__(64) void collision_probability_kernel(CpArgs a)
     }
 }
 
-struct CpCall {
-    int n;
-    const double *pairs;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *units, *span, *P, *radius;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P, *cat_radius;
-    double mu;
+struct CpCall : EncGeometry {
     double *out;
     int32_t *status;
 };
+// the arguments of both entry points as a CpCall
+#define MPCX_CP_CALL CpCall{MPCX_GEOMETRY(radius, cat_radius), out, status}
 
 static int cp_check(mpcx_ctx *ctx, const CpCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: need n>=1, S>=1, K>=2, mu>0");
-    if (!c.pairs || !c.Y || !c.units || !c.span || !c.P || !c.radius || !c.out || !c.status)
-        return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: pairs, Y, units, span, P, radius, out and status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span || !c.cat_P || !c.cat_radius)
-            return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability: cat_units, cat_span, cat_P and cat_radius are required with cat_Y");
-    }
-    return MPCX_OK;
+    if (int rc = geom_check_sizes(ctx, c, "collision_probability")) return rc;
+    return geom_check_arrays(ctx, c, "collision_probability", true, c.out && c.status, "pairs, Y, units, span, P, radius, out and status");
 }
 
 }  // namespace mpcx
@@ -262,20 +248,18 @@ extern "C" int mpcx_covariance_batch(mpcx_ctx *ctx, int S, int K, const int32_t 
     double *du = ar.upload(units, (size_t)S * 2), *dsp = ar.upload(span, (size_t)S * 2), *dc = ar.upload(consts, (size_t)S * MPCX_NCONST);
     double *dP0 = ar.upload(P0, (size_t)S * 36), *dq = q ? ar.upload(q, S) : nullptr;
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr;
-    double *dP = ar.alloc<double>((size_t)S * K * 36);
-    int32_t *dst = ar.alloc<int32_t>(S);
+    double *dP = ar.result(P, (size_t)S * K * 36);
+    int32_t *dst = ar.result(status, (size_t)S);
     char *dws = ar.alloc<char>(mpcx_covariance_workspace_bytes(S, K));
-    if (ar.failed()) return ar.code();
-    if (int rc = mpcx_covariance_batch_dev(ctx, S, K, dKs, dX, dU, du, dsp, dc, flags, max_step, dP0, dq, dP, dst, dws, ctx->stream)) return rc;
-    ar.download(P, dP, (size_t)S * K * 36);
-    ar.download(status, dst, S);
-    return ar.finish();
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) {
+        return mpcx_covariance_batch_dev(ctx, S, K, dKs, dX, dU, du, dsp, dc, flags, max_step, dP0, dq, dP, dst, dws, st);
+    });
 }
 
 static int cp_enqueue(mpcx_ctx *ctx, const CpCall &c, hipStream_t st)
 {
-    const CpSide row{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
-    const CpSide col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
+    CpSide row, col;
+    enc_sides(c, row, col);
     const CpArgs a{c.n, c.pairs, row, col, c.mu, c.out, c.status};
     hipLaunchKernelGGL(collision_probability_kernel, dim3((unsigned)c.n), dim3(64), 0, st, a);
     MPCX_HIP(ctx, hipGetLastError());
@@ -289,7 +273,7 @@ extern "C" int mpcx_collision_probability_dev(mpcx_ctx *ctx, int n, const double
                                               int32_t *status, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CpCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu, out, status};
+    const CpCall c = MPCX_CP_CALL;
     if (int rc = cp_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     return cp_enqueue(ctx, c, (hipStream_t)stream);
@@ -301,26 +285,14 @@ extern "C" int mpcx_collision_probability(mpcx_ctx *ctx, int n, const double *pa
                                           const double *cat_P, const double *cat_radius, double mu, double *out, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CpCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu, out, status};
+    const CpCall c = MPCX_CP_CALL;
     if (int rc = cp_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     CpCall d = c;
-    d.pairs = ar.upload(pairs, (size_t)n * 4);
-    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2);
-    d.P = ar.upload(P, (size_t)S * K * 36); d.radius = ar.upload(radius, S);
-    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        d.cat_span = ar.upload(cat_span, (size_t)D * 2); d.cat_P = ar.upload(cat_P, (size_t)D * cat_K * 36);
-        d.cat_radius = ar.upload(cat_radius, D);
-        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
-    d.out = ar.alloc<double>((size_t)n * MPCX_NPC);
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    if (int rc = cp_enqueue(ctx, d, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NPC);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    geom_upload(ar, d);
+    d.out = ar.result(out, (size_t)n * MPCX_NPC);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) { return cp_enqueue(ctx, d, st); });
 }
+#undef MPCX_CP_CALL

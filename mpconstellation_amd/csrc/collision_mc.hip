@@ -478,18 +478,12 @@ __global__ __launch_bounds__(256) void mc_copy_kernel(size_t total, int rows, in
 
 // ---------------------------------------------------------------- the host side
 
-struct McCall {
-    int n;
-    const double *pairs;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *U, *units, *span, *consts;
+// the geometry (no P, cat_P or mu: the covariances are sampled from P0) plus the truth model, the sampling and the outputs
+struct McCall : EncGeometry {
+    const double *U, *consts;
     int flags;
     double prop_max_step;
-    const double *P0, *exec, *m_var0, *radius;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_consts, *cat_P0, *cat_radius;
+    const double *P0, *exec, *m_var0, *cat_consts, *cat_P0;
     const double *half;
     int scan, n_samples;
     uint64_t seed;
@@ -522,11 +516,9 @@ static int mc_check(mpcx_ctx *ctx, const McCall &c)
     if (c.max_flights < 0) return enc_fail(ctx, MC_NAME, "max_flights is 0 (the default) or > 0");
     if (!c.pairs || !c.Y || !c.units || !c.span || !c.consts || !c.P0 || !c.radius || !c.half || !c.counts || !c.out || !c.status)
         return enc_fail(ctx, MC_NAME, "pairs, Y, units, span, consts, P0, radius, half_window, counts, out and status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return enc_fail(ctx, MC_NAME, "a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span || !c.cat_consts || !c.cat_P0 || !c.cat_radius)
-            return enc_fail(ctx, MC_NAME, "cat_units, cat_span, cat_consts, cat_P0 and cat_radius are required with cat_Y");
-    }
+    if (int rc = geom_check_catalogue(ctx, c, MC_NAME, c.cat_consts && c.cat_P0 && c.cat_radius,
+                                      "cat_units, cat_span, cat_consts, cat_P0 and cat_radius"))
+        return rc;
     const int NS = c.cat_Y ? 1 : 2;
     if ((long long)c.n * 2 * mc_chunk(c.n, NS, c.n_samples, c.max_flights) > 0x7fffffffLL)
         return enc_fail(ctx, MC_NAME, "too many virtual trajectories in one chunk: lower max_flights or split the list");
@@ -560,8 +552,8 @@ static int mc_enqueue(mpcx_ctx *ctx, const McCall &c, void *workspace, hipStream
     const McWorkspace ws(workspace, n, K, cat, c.cat_K, Cs);
     const McSide rs{c.S, K, c.Ks, c.Y, c.U, c.units, c.span, c.consts, c.P0, c.exec, c.m_var0};
     const McSide cs = cat ? McSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, nullptr, c.cat_units, c.cat_span, c.cat_consts, c.cat_P0, nullptr, nullptr} : rs;
-    const CpSide row{c.S, K, c.Ks, c.Y, c.units, c.span, nullptr, c.radius};
-    const CpSide col = cat ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, nullptr, c.cat_radius} : row;
+    CpSide row, col;
+    enc_sides(c, row, col);
     const uint32_t k0 = (uint32_t)(c.seed & 0xffffffffu), k1 = (uint32_t)(c.seed >> 32);
     const unsigned gn = (unsigned)((n + 255) / 256);
     long long *counts = (long long *)c.counts;
@@ -614,9 +606,9 @@ extern "C" size_t mpcx_collision_probability_mc_workspace_bytes(int n, int S, in
 
 // the arguments of the two entry points below as a McCall
 #define MPCX_MC_CALL                                                                                                                        \
-    McCall{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, prop_max_step, P0, exec, m_var0, radius, D, cat_K, cat_Ks, cat_Y, cat_units, \
-           cat_span, cat_consts, cat_P0, cat_radius, half_window, scan, n_samples, seed, max_flights, counts, out, status, samples, Y_samples, \
-           U_samples}
+    McCall{{n, pairs, S, K, Ks, Y, units, span, nullptr, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, nullptr, cat_radius, 0.0}, \
+           U, consts, flags, prop_max_step, P0, exec, m_var0, cat_consts, cat_P0, half_window, scan, n_samples, seed, max_flights, counts,  \
+           out, status, samples, Y_samples, U_samples}
 
 extern "C" int mpcx_collision_probability_mc_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks, const double *Y,
                                                  const double *U, const double *units, const double *span, const double *consts, int flags,
@@ -653,35 +645,19 @@ extern "C" int mpcx_collision_probability_mc(mpcx_ctx *ctx, int n, const double 
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     McCall d = c;
-    const size_t Sz = (size_t)S, Kz = (size_t)K, Dz = (size_t)D, cK = (size_t)cat_K, nz = (size_t)n, N = (size_t)n_samples;
-    const size_t NS = cat_Y ? 1 : 2;
-    d.pairs = ar.upload(pairs, nz * 4); d.half = ar.upload(half_window, nz);
-    d.Y = ar.upload(Y, Sz * 7 * Kz); d.U = U ? ar.upload(U, Sz * 3 * Kz) : nullptr;
-    d.units = ar.upload(units, Sz * 2); d.span = ar.upload(span, Sz * 2); d.consts = ar.upload(consts, Sz * MPCX_NCONST);
-    d.Ks = Ks ? ar.upload(Ks, Sz) : nullptr;
+    const size_t Sz = (size_t)S, Kz = (size_t)K, Dz = (size_t)D, nz = (size_t)n, N = (size_t)n_samples, NS = cat_Y ? 1 : 2;
+    geom_upload(ar, d);
+    d.half = ar.upload(half_window, nz); d.U = U ? ar.upload(U, Sz * 3 * Kz) : nullptr; d.consts = ar.upload(consts, Sz * MPCX_NCONST);
     d.P0 = ar.upload(P0, Sz * 36); d.exec = exec ? ar.upload(exec, Sz * MPCX_NEXEC) : nullptr;
-    d.m_var0 = m_var0 ? ar.upload(m_var0, Sz) : nullptr; d.radius = ar.upload(radius, Sz);
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, Dz * 7 * cK); d.cat_units = ar.upload(cat_units, Dz * 2); d.cat_span = ar.upload(cat_span, Dz * 2);
-        d.cat_consts = ar.upload(cat_consts, Dz * MPCX_NCONST); d.cat_P0 = ar.upload(cat_P0, Dz * 36);
-        d.cat_radius = ar.upload(cat_radius, Dz); d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, Dz) : nullptr;
-    }
-    d.counts = ar.alloc<int64_t>(nz * MPCX_NMCC);
-    d.out = ar.alloc<double>(nz * MPCX_NMC);
-    d.status = ar.alloc<int32_t>(nz);
-    d.samples = samples ? ar.alloc<double>(nz * N * MPCX_NMS) : nullptr;
-    d.Y_samples = Y_samples ? ar.alloc<double>(nz * NS * N * 7 * Kz) : nullptr;
-    d.U_samples = U_samples ? ar.alloc<double>(nz * NS * N * 3 * Kz) : nullptr;
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, mpcx_collision_probability_mc_workspace_bytes(n, S, K, cat_Y ? D : 0, cat_K, n_samples, max_flights));
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = mc_enqueue(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(counts, d.counts, nz * MPCX_NMCC);
-    ar.download(out, d.out, nz * MPCX_NMC);
-    ar.download(status, d.status, nz);
-    if (samples) ar.download(samples, d.samples, nz * N * MPCX_NMS);
-    if (Y_samples) ar.download(Y_samples, d.Y_samples, nz * NS * N * 7 * Kz);
-    if (U_samples) ar.download(U_samples, d.U_samples, nz * NS * N * 3 * Kz);
-    return ar.finish();
+    d.m_var0 = m_var0 ? ar.upload(m_var0, Sz) : nullptr;
+    if (cat_Y) { d.cat_consts = ar.upload(cat_consts, Dz * MPCX_NCONST); d.cat_P0 = ar.upload(cat_P0, Dz * 36); }
+    d.counts = ar.result(counts, nz * MPCX_NMCC);
+    d.out = ar.result(out, nz * MPCX_NMC);
+    d.status = ar.result(status, nz);
+    d.samples = ar.result(samples, nz * N * MPCX_NMS);
+    d.Y_samples = ar.result(Y_samples, nz * NS * N * 7 * Kz);
+    d.U_samples = ar.result(U_samples, nz * NS * N * 3 * Kz);
+    return host_run(ctx, ar, mpcx_collision_probability_mc_workspace_bytes(n, S, K, cat_Y ? D : 0, cat_K, n_samples, max_flights),
+                    [&](void *ws, hipStream_t st) { return mc_enqueue(ctx, d, ws, st); });
 }
 #undef MPCX_MC_CALL

@@ -21,7 +21,7 @@
 //                             node of the objects that move (include/mpcx.h: mpcx_collision_window_sensitivity*): the gradient with
 //                             respect to the mean relative state at every time node, carried onto the bracketing node states and
 //                             swept backwards over the stage records (tests/avoidance_window_reference.py restates it).  Its host
-//                             side (cws_check, cws_enqueue, cws_upload: encounter_host.hpp) also serves avoidance_window.hip.
+//                             side (cws_check, cws_enqueue: encounter_host.hpp) also serves avoidance_window.hip.
 #include "collision_window_device.hpp"
 #include "encounter_host.hpp"
 
@@ -84,38 +84,20 @@ __global__ __launch_bounds__(64) void collision_window_kernel(CwArgs a)
 }
 
 // the call as both entry points take it
-struct CwCall {
-    int n;
-    const double *pairs;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *units, *span, *P, *radius;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P, *cat_radius;
-    double mu;
+struct CwCall : EncGeometry {
     const double *half;
     int panels;
     double *out;
     int32_t *status;
 };
+#define MPCX_CW_CALL CwCall{MPCX_GEOMETRY(radius, cat_radius), half_window, panels, out, status}
 
 static int cw_check(mpcx_ctx *ctx, const CwCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0))
-        return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability_window: need n>=1, S>=1, K>=2, mu>0");
-    if (c.panels < 1 || c.panels > MPCX_PW_MAX_PANELS)
-        return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability_window: panels must be 1..MPCX_PW_MAX_PANELS");
-    if (!c.pairs || !c.Y || !c.units || !c.span || !c.P || !c.radius || !c.half || !c.out || !c.status)
-        return ctx_fail(ctx, MPCX_E_BADARG,
-                        "collision_probability_window: pairs, Y, units, span, P, radius, half_window, out and status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "collision_probability_window: a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span || !c.cat_P || !c.cat_radius)
-            return ctx_fail(ctx, MPCX_E_BADARG,
-                            "collision_probability_window: cat_units, cat_span, cat_P and cat_radius are required with cat_Y");
-    }
-    return MPCX_OK;
+    static const char *const name = "collision_probability_window";
+    if (int rc = geom_check_sizes(ctx, c, name)) return rc;
+    if (c.panels < 1 || c.panels > MPCX_PW_MAX_PANELS) return enc_fail(ctx, name, "panels must be 1..MPCX_PW_MAX_PANELS");
+    return geom_check_arrays(ctx, c, name, true, c.half && c.out && c.status, "pairs, Y, units, span, P, radius, half_window, out and status");
 }
 
 static int cw_enqueue(mpcx_ctx *ctx, const CwCall &c, hipStream_t st)
@@ -371,14 +353,6 @@ int cws_enqueue(mpcx_ctx *ctx, const CwsCall &c, const CwsWorkspace &ws, hipStre
     return MPCX_OK;
 }
 
-void cws_upload(DeviceArena &ar, CwsCall &c)
-{
-    c.radius = ar.upload(c.radius, (size_t)c.S);
-    c.half = ar.upload(c.half, (size_t)c.n);
-    if (c.cat_Y) c.cat_radius = ar.upload(c.cat_radius, (size_t)c.D);
-    enc_upload(ar, c);
-}
-
 // workspace of the _dev call
 struct CwsOwnWorkspace : CwsWorkspace {
     size_t bytes;
@@ -396,6 +370,9 @@ static int cws_run(mpcx_ctx *ctx, const CwsCall &c, void *workspace, hipStream_t
     if (int rc = enc_linearise(ctx, c, ws, st)) return rc;
     return cws_enqueue(ctx, c, ws, st);
 }
+
+// the arguments of both entry points as a CwsCall (the target is not an argument of theirs)
+#define MPCX_CWS_CALL CwsCall{MPCX_ENC_PROBLEM(radius, cat_radius, 1.0), half_window, panels, who, out, sens, state_grad, status}
 
 static const char *const CWS_NAME = "collision_window_sensitivity";
 static const char *const CWS_REQUIRED = "P, radius, half_window, out, sens and status";
@@ -419,8 +396,7 @@ extern "C" int mpcx_collision_window_sensitivity_dev(mpcx_ctx *ctx, int n, const
                                                      double *state_grad, int32_t *status, void *workspace, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CwsCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                     mu, 1.0}, radius, cat_radius, half_window, panels, who, out, sens, state_grad, status};
+    const CwsCall c = MPCX_CWS_CALL;
     if (int rc = cws_check(ctx, c, CWS_NAME, out && sens && status, CWS_REQUIRED)) return rc;
     if (!workspace)
         return enc_fail(ctx, CWS_NAME, "a workspace of mpcx_collision_window_sensitivity_workspace_bytes(n, S, K, panels) bytes is required");
@@ -436,28 +412,21 @@ extern "C" int mpcx_collision_window_sensitivity(mpcx_ctx *ctx, int n, const dou
                                                  int panels, int who, double *out, double *sens, double *state_grad, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CwsCall c{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P,
-                     mu, 1.0}, radius, cat_radius, half_window, panels, who, out, sens, state_grad, status};
+    const CwsCall c = MPCX_CWS_CALL;
     if (int rc = cws_check(ctx, c, CWS_NAME, out && sens && status, CWS_REQUIRED)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     CwsCall d = c;
     const size_t NS = cat_Y ? 1 : 2, NQ = (size_t)64 * panels + 1;
-    cws_upload(ar, d);
-    d.out = ar.alloc<double>((size_t)n * MPCX_NPW);
-    d.sens = ar.alloc<double>((size_t)n * NS * 3 * K);
-    d.state_grad = state_grad ? ar.alloc<double>((size_t)n * NQ * 6) : nullptr;
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    void *ws = ctx_workspace(ctx, mpcx_collision_window_sensitivity_workspace_bytes(n, S, K, panels));
-    if (!ws) return MPCX_E_NOMEM;
-    if (int rc = cws_run(ctx, d, ws, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NPW);
-    ar.download(sens, d.sens, (size_t)n * NS * 3 * K);
-    if (state_grad) ar.download(state_grad, d.state_grad, (size_t)n * NQ * 6);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    enc_upload(ar, d); d.half = ar.upload(half_window, (size_t)n);
+    d.out = ar.result(out, (size_t)n * MPCX_NPW);
+    d.sens = ar.result(sens, (size_t)n * NS * 3 * K);
+    d.state_grad = ar.result(state_grad, (size_t)n * NQ * 6);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, mpcx_collision_window_sensitivity_workspace_bytes(n, S, K, panels),
+                    [&](void *ws, hipStream_t st) { return cws_run(ctx, d, ws, st); });
 }
+#undef MPCX_CWS_CALL
 
 extern "C" int mpcx_collision_probability_window_dev(mpcx_ctx *ctx, int n, const double *pairs, int S, int K, const int32_t *Ks,
                                                      const double *Y, const double *units, const double *span, const double *P,
@@ -467,8 +436,7 @@ extern "C" int mpcx_collision_probability_window_dev(mpcx_ctx *ctx, int n, const
                                                      double *out, int32_t *status, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CwCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu,
-                   half_window, panels, out, status};
+    const CwCall c = MPCX_CW_CALL;
     if (int rc = cw_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     return cw_enqueue(ctx, c, (hipStream_t)stream);
@@ -481,28 +449,14 @@ extern "C" int mpcx_collision_probability_window(mpcx_ctx *ctx, int n, const dou
                                                  const double *half_window, int panels, double *out, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const CwCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu,
-                   half_window, panels, out, status};
+    const CwCall c = MPCX_CW_CALL;
     if (int rc = cw_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     CwCall d = c;
-    d.pairs = ar.upload(pairs, (size_t)n * 4);
-    d.half = ar.upload(half_window, (size_t)n);
-    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2);
-    d.P = ar.upload(P, (size_t)S * K * 36); d.radius = ar.upload(radius, S);
-    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        d.cat_span = ar.upload(cat_span, (size_t)D * 2); d.cat_P = ar.upload(cat_P, (size_t)D * cat_K * 36);
-        d.cat_radius = ar.upload(cat_radius, D);
-        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
-    d.out = ar.alloc<double>((size_t)n * MPCX_NPW);
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    if (int rc = cw_enqueue(ctx, d, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NPW);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    geom_upload(ar, d); d.half = ar.upload(half_window, (size_t)n);
+    d.out = ar.result(out, (size_t)n * MPCX_NPW);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) { return cw_enqueue(ctx, d, st); });
 }
+#undef MPCX_CW_CALL

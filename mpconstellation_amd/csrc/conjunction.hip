@@ -859,21 +859,13 @@ static int pairs_enqueue(mpcx_ctx *ctx, const PairsCall &c, const double *pairs,
     return MPCX_OK;
 }
 
-// device arrays for the outputs `o` of a host-pointer call, and their way back (a track call's info only where it is asked for)
-static PairsOut pairs_out_alloc(DeviceArena &ar, const PairsCall &c, const PairsOut &o)
+// device arrays for the outputs `o` of a host-pointer call, on their way back (a track call's info only where it is asked for)
+static PairsOut pairs_results(DeviceArena &ar, const PairsCall &c, const PairsOut &o)
 {
-    PairsOut d{ar.alloc<double>(c.rows() * 4), ar.alloc<int32_t>(c.n), nullptr, nullptr};
-    if (c.events) { d.info = ar.alloc<int32_t>(c.rows() * 2); d.count = ar.alloc<int32_t>(c.n); }
-    if (c.track && o.info) d.info = ar.alloc<int32_t>(c.rows() * 2);
+    PairsOut d{ar.result(o.rows, c.rows() * 4), ar.result(o.status, (size_t)c.n), nullptr, nullptr};
+    if (c.events || c.track) d.info = ar.result(o.info, c.rows() * 2);
+    if (c.events) d.count = ar.result(o.count, (size_t)c.n);
     return d;
-}
-
-static void pairs_out_download(DeviceArena &ar, const PairsCall &c, const PairsOut &o, const PairsOut &d)
-{
-    ar.download(o.rows, d.rows, c.rows() * 4);
-    ar.download(o.status, d.status, c.n);
-    if (c.events) { ar.download(o.info, d.info, c.rows() * 2); ar.download(o.count, d.count, c.n); }
-    if (c.track && o.info) ar.download(o.info, d.info, c.rows() * 2);
 }
 
 // the four forms of a list call behind their extern "C" names (n = 0 passes pairs_check for the events and track calls only: nothing to do)
@@ -898,11 +890,8 @@ static int pairs_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall &c, c
     DeviceArena ar(ctx);
     double *dp = ar.upload(pairs, (size_t)c.n * 4), *de = ar.upload(eph, (size_t)c.S * 6 * c.M);
     double *dc = c.D > 0 ? ar.upload(cat, (size_t)c.D * 6 * c.M) : nullptr;
-    const PairsOut d = pairs_out_alloc(ar, c, o);
-    if (ar.failed()) return ar.code();
-    if (int rc = pairs_enqueue(ctx, c, dp, de, dc, d, ctx->stream)) return rc;
-    pairs_out_download(ar, c, o, d);
-    return ar.finish();
+    const PairsOut d = pairs_results(ar, c, o);
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) { return pairs_enqueue(ctx, c, dp, de, dc, d, st); });
 }
 
 // one side's trajectories as mpcx_ephemeris_batch takes them
@@ -954,11 +943,11 @@ static int pairs_traj_host(mpcx_ctx *ctx, const PairsNames &nm, const PairsCall 
         cst = ar.alloc<int32_t>(D);
     }
     int32_t *est = ar.alloc<int32_t>(S);
-    const PairsOut d = pairs_out_alloc(ar, c, o);
+    const PairsOut d = pairs_results(ar, c, o);
     char *dws = ar.alloc<char>(PairsWorkspace(nullptr, S, D, c.M).bytes);                // neither ephemeris leaves HBM
     if (ar.failed()) return ar.code();
     if (int rc = pairs_traj_dev(ctx, nm, c, dp, ds, dc, d, est, cst, dws, ctx->stream)) return rc;
-    pairs_out_download(ar, c, o, d);
+    ar.fetch();
     if (eph_status) ar.download(eph_status, est, S);
     if (D > 0 && cat_status) ar.download(cat_status, cst, D);
     return ar.finish();

@@ -207,15 +207,10 @@ extern "C" int mpcx_covariance_thrust_batch(mpcx_ctx *ctx, int S, int K, const i
     double *dP0 = ar.upload(P0, (size_t)S * 36), *dq = q ? ar.upload(q, S) : nullptr;
     double *dex = ar.upload(exec, (size_t)S * MPCX_NEXEC), *dmv = m_var0 ? ar.upload(m_var0, S) : nullptr;
     int32_t *dKs = Ks ? ar.upload(Ks, S) : nullptr;
-    double *dP = ar.alloc<double>((size_t)S * K * 36), *dPm = Pm ? ar.alloc<double>((size_t)S * K * 7) : nullptr;
-    int32_t *dst = ar.alloc<int32_t>(S);
+    double *dP = ar.result(P, (size_t)S * K * 36), *dPm = ar.result(Pm, (size_t)S * K * 7);
+    int32_t *dst = ar.result(status, (size_t)S);
     char *dws = ar.alloc<char>(mpcx_covariance_thrust_workspace_bytes(S, K));
-    if (ar.failed()) return ar.code();
-    if (int rc = mpcx_covariance_thrust_batch_dev(ctx, S, K, dKs, dX, dU, du, dsp, dc, flags, max_step, dP0, dq, dex, dmv, dP, dPm, dst, dws,
-                                                  ctx->stream))
-        return rc;
-    ar.download(P, dP, (size_t)S * K * 36);
-    if (Pm) ar.download(Pm, dPm, (size_t)S * K * 7);
-    ar.download(status, dst, S);
-    return ar.finish();
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) {
+        return mpcx_covariance_thrust_batch_dev(ctx, S, K, dKs, dX, dU, du, dsp, dc, flags, max_step, dP0, dq, dex, dmv, dP, dPm, dst, dws, st);
+    });
 }

@@ -1,29 +1,35 @@
-// encounter_host.hpp -- the host side that mpcx_avoidance*, mpcx_avoidance_joint*, mpcx_avoidance_refine*,
-// mpcx_collision_window_sensitivity*, mpcx_avoidance_window* and mpcx_avoidance_window_refine* share, and the linearisation step they share with
-// mpcx_covariance_batch*: the description of the problem, its argument tests and uploads, the workspace carver, and the set of
-// trajectories that mpcx_avoidance_refine*, mpcx_avoidance_window_refine* and mpcx_collision_probability_mc* fly again (FlightSet).
+// encounter_host.hpp -- the host side of the listed-pair calls.  What is shared:
+//   EncGeometry     the list and its two sides, with its argument tests (geom_check_*), its uploads (geom_upload) and the CpSide pair
+//                   its kernels take (enc_sides); every call of the family is "that, plus my own few members"
+//   EncProblem      the geometry plus the model of its linearisation and the target, with enc_check / enc_upload / enc_linearise:
+//                   mpcx_avoidance*, mpcx_avoidance_joint*, mpcx_avoidance_refine*, mpcx_collision_window_sensitivity*,
+//                   mpcx_avoidance_window*, mpcx_avoidance_window_refine*; mpcx_covariance_batch* share the linearisation
+//   MPCX_GEOMETRY / MPCX_ENC_PROBLEM   an entry point's arguments, under their names in include/mpcx.h, as either
+//   Carver, LinWorkspace, FlightSet    the workspace carver, the linearisation's regions, the trajectories flown again
+// Results and the tail of a host form (DeviceArena::result, host_run) are mpcx_host.hpp's.  A call owns its kernel arguments, its
+// own members with their tests and uploads, its workspace layout and its enqueue.
 #pragma once
 #include "collision_device.hpp"                                     // CpSide
 #include "mpcx_host.hpp"
 
 namespace mpcx {
 
-// a listed-pairs problem as every avoidance entry point takes it: the list, the plan that was screened, the model of its linearisation,
-// the covariances and the catalogue (both optional), the target
-struct EncProblem {
+// The list and its two sides as every listed-pair call takes them: the rows, the constellation with its covariances and radii, the
+// catalogue (optional, with its own), mu.  A call that has no P or no radii leaves them NULL.
+struct EncGeometry {
     int n;
     const double *pairs;
     int S, K;
     const int32_t *Ks;
-    const double *Y, *U, *units, *span, *consts;
-    int flags;
-    double max_step;
-    const double *P;
+    const double *Y, *units, *span, *P, *radius;
     int D, cat_K;
     const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P;
-    double mu, target;
+    const double *cat_Y, *cat_units, *cat_span, *cat_P, *cat_radius;
+    double mu;
 };
+// the arguments of an entry point, under their names in include/mpcx.h, as an EncGeometry (RADIUS, CAT_RADIUS: nullptr where it has none)
+#define MPCX_GEOMETRY(RADIUS, CAT_RADIUS) \
+    {n, pairs, S, K, Ks, Y, units, span, P, RADIUS, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, CAT_RADIUS, mu}
 
 inline int enc_fail(mpcx_ctx *ctx, const char *name, const char *what)
 {
@@ -32,26 +38,88 @@ inline int enc_fail(mpcx_ctx *ctx, const char *name, const char *what)
     return ctx_fail(ctx, MPCX_E_BADARG, msg);
 }
 
+// The argument tests of the geometry for the call `name`, in the two steps between which a call tests its own scalars: the sizes,
+// then the arrays.
+inline int geom_check_sizes(mpcx_ctx *ctx, const EncGeometry &g, const char *name)
+{
+    if (g.n < 1 || g.S < 1 || g.K < 2 || !(g.mu > 0.0)) return enc_fail(ctx, name, "need n>=1, S>=1, K>=2, mu>0");
+    return MPCX_OK;
+}
+// a catalogue's own: own_given / names as below, for what is required with cat_Y
+inline int geom_check_catalogue(mpcx_ctx *ctx, const EncGeometry &g, const char *name, bool own_given, const char *names)
+{
+    if (!g.cat_Y) return MPCX_OK;
+    if (g.D < 1 || g.cat_K < 2) return enc_fail(ctx, name, "a catalogue needs D>=1, cat_K>=2");
+    if (!g.cat_units || !g.cat_span || !own_given) {
+        char what[160];
+        snprintf(what, sizeof what, "%s are required with cat_Y", names);
+        return enc_fail(ctx, name, what);
+    }
+    return MPCX_OK;
+}
+// full: the call requires P, radius and, with a catalogue, cat_P, cat_radius (the probability family); else all four are optional
+// here (the avoidance family has no radii and takes P or not).  own_given / names: whether the call's own required arrays are all
+// there, and the whole list of required arrays as the message names it.
+inline int geom_check_arrays(mpcx_ctx *ctx, const EncGeometry &g, const char *name, bool full, bool own_given, const char *names)
+{
+    if (!g.pairs || !g.Y || !g.units || !g.span || (full && (!g.P || !g.radius)) || !own_given) {
+        char what[224];
+        snprintf(what, sizeof what, "%s are required", names);
+        return enc_fail(ctx, name, what);
+    }
+    return geom_check_catalogue(ctx, g, name, !full || (g.cat_P && g.cat_radius),
+                                full ? "cat_units, cat_span, cat_P and cat_radius" : "cat_units and cat_span");
+}
+
+// the geometry's host arrays replaced by copies on the device
+inline void geom_upload(DeviceArena &ar, EncGeometry &g)
+{
+    const size_t S = (size_t)g.S, K = (size_t)g.K, D = (size_t)g.D, cK = (size_t)g.cat_K;
+    g.pairs = ar.upload(g.pairs, (size_t)g.n * 4);
+    g.Y = ar.upload(g.Y, S * 7 * K); g.units = ar.upload(g.units, S * 2); g.span = ar.upload(g.span, S * 2);
+    g.Ks = g.Ks ? ar.upload(g.Ks, S) : nullptr;
+    g.P = g.P ? ar.upload(g.P, S * K * 36) : nullptr;
+    g.radius = g.radius ? ar.upload(g.radius, S) : nullptr;
+    if (g.cat_Y) {
+        g.cat_Y = ar.upload(g.cat_Y, D * 7 * cK); g.cat_units = ar.upload(g.cat_units, D * 2);
+        g.cat_span = ar.upload(g.cat_span, D * 2);
+        g.cat_P = g.cat_P ? ar.upload(g.cat_P, D * cK * 36) : nullptr;
+        g.cat_radius = g.cat_radius ? ar.upload(g.cat_radius, D) : nullptr;
+        g.cat_Ks = g.cat_Ks ? ar.upload(g.cat_Ks, D) : nullptr;
+    }
+}
+
+// The two sides of the list as the kernels take them: the constellation, and the catalogue where there is one, else the
+// constellation again.
+inline void enc_sides(const EncGeometry &g, CpSide &row, CpSide &col)
+{
+    row = CpSide{g.S, g.K, g.Ks, g.Y, g.units, g.span, g.P, g.radius};
+    col = g.cat_Y ? CpSide{g.D, g.cat_K, g.cat_Ks, g.cat_Y, g.cat_units, g.cat_span, g.cat_P, g.cat_radius} : row;
+}
+
+// a listed-pairs problem as every avoidance entry point takes it: the geometry, the plan that was screened and the model of its
+// linearisation, the target
+struct EncProblem : EncGeometry {
+    const double *U, *consts;
+    int flags;
+    double max_step, target;
+};
+#define MPCX_ENC_PROBLEM(RADIUS, CAT_RADIUS, TARGET) {MPCX_GEOMETRY(RADIUS, CAT_RADIUS), U, consts, flags, max_step, TARGET}
+
 // The argument tests of the call `name` that every avoidance entry point makes.  outputs_given / outputs: whether the call's own
 // required output arrays are all there, and their names as the message lists them behind the inputs.
 inline int enc_check(mpcx_ctx *ctx, const EncProblem &p, const char *name, bool outputs_given, const char *outputs)
 {
-    if (p.n < 1 || p.S < 1 || p.K < 2 || !(p.mu > 0.0)) return enc_fail(ctx, name, "need n>=1, S>=1, K>=2, mu>0");
+    if (int rc = geom_check_sizes(ctx, p, name)) return rc;
     if (!(p.target > 0.0) || !(p.target < __builtin_inf())) return enc_fail(ctx, name, "target must be a positive finite number");
     if (!(p.max_step > 0.0)) return enc_fail(ctx, name, "max_step must be > 0");
     if (p.flags & ~(MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO))
         return enc_fail(ctx, name, "flags are MPCX_FLAG_DRAG | MPCX_FLAG_J2 | MPCX_FLAG_ATMO");
-    if (!p.pairs || !p.Y || !p.U || !p.units || !p.span || !p.consts || !outputs_given) {
-        char what[192];
-        snprintf(what, sizeof what, "pairs, Y, U, units, span, consts, %s are required", outputs);
-        return enc_fail(ctx, name, what);
-    }
-    if (p.cat_Y) {
-        if (p.D < 1 || p.cat_K < 2) return enc_fail(ctx, name, "a catalogue needs D>=1, cat_K>=2");
-        if (!p.cat_units || !p.cat_span) return enc_fail(ctx, name, "cat_units and cat_span are required with cat_Y");
-        if ((p.P != nullptr) != (p.cat_P != nullptr))
-            return enc_fail(ctx, name, "P and cat_P come together (a Mahalanobis target) or not at all (metres)");
-    }
+    char names[192];
+    snprintf(names, sizeof names, "pairs, Y, U, units, span, consts, %s", outputs);
+    if (int rc = geom_check_arrays(ctx, p, name, false, p.U && p.consts && outputs_given, names)) return rc;
+    if (p.cat_Y && (p.P != nullptr) != (p.cat_P != nullptr))
+        return enc_fail(ctx, name, "P and cat_P come together (a Mahalanobis target) or not at all (metres)");
     return ctx_check_atmosphere(ctx, p.flags, name);
 }
 
@@ -68,18 +136,8 @@ inline int check_mover(mpcx_ctx *ctx, const EncProblem &p, const int32_t *mover,
 // the problem's host arrays replaced by copies on the device
 inline void enc_upload(DeviceArena &ar, EncProblem &p)
 {
-    const size_t S = (size_t)p.S, K = (size_t)p.K, D = (size_t)p.D, cK = (size_t)p.cat_K;
-    p.pairs = ar.upload(p.pairs, (size_t)p.n * 4);
-    p.Y = ar.upload(p.Y, S * 7 * K); p.U = ar.upload(p.U, S * 3 * K);
-    p.units = ar.upload(p.units, S * 2); p.span = ar.upload(p.span, S * 2); p.consts = ar.upload(p.consts, S * MPCX_NCONST);
-    p.Ks = p.Ks ? ar.upload(p.Ks, S) : nullptr;
-    p.P = p.P ? ar.upload(p.P, S * K * 36) : nullptr;
-    if (p.cat_Y) {
-        p.cat_Y = ar.upload(p.cat_Y, D * 7 * cK); p.cat_units = ar.upload(p.cat_units, D * 2);
-        p.cat_span = ar.upload(p.cat_span, D * 2);
-        p.cat_P = p.cat_P ? ar.upload(p.cat_P, D * cK * 36) : nullptr;
-        p.cat_Ks = p.cat_Ks ? ar.upload(p.cat_Ks, D) : nullptr;
-    }
+    geom_upload(ar, p);
+    p.U = ar.upload(p.U, (size_t)p.S * 3 * p.K); p.consts = ar.upload(p.consts, (size_t)p.S * MPCX_NCONST);
 }
 
 // a workspace cut into regions, each rounded up to 256 bytes
@@ -157,19 +215,11 @@ int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hi
 // mpcx_collision_window_sensitivity* as its entry points take it, and as mpcx_avoidance_window* (avoidance_window.hip) runs it
 // first: the problem (its `target` is not read), the window call's own arguments, who moves, the outputs
 struct CwsCall : EncProblem {
-    const double *radius, *cat_radius, *half;
+    const double *half;
     int panels, who;
     double *out, *sens, *state_grad;
     int32_t *status;
 };
-
-// The two sides of the list of a window call (CwsCall, or collision_window.hip's CwCall: the same names) as its kernels take them:
-// the constellation, and the catalogue where there is one, else the constellation again.
-template <typename Call> inline void enc_sides(const Call &c, CpSide &row, CpSide &col)
-{
-    row = CpSide{c.S, c.K, c.Ks, c.Y, c.units, c.span, c.P, c.radius};
-    col = c.cat_Y ? CpSide{c.D, c.cat_K, c.cat_Ks, c.cat_Y, c.cat_units, c.cat_span, c.cat_P, c.cat_radius} : row;
-}
 
 // workspace of the sensitivity: [the linearisation's][node sources n 2 K 6]
 struct CwsWorkspace : LinWorkspace {
@@ -184,8 +234,6 @@ struct CwsWorkspace : LinWorkspace {
 // The argument tests of both calls (`name` in the messages) and the sensitivity kernel on linearised stage records.  (collision_window.hip)
 int cws_check(mpcx_ctx *ctx, const CwsCall &c, const char *name, bool outputs_given, const char *outputs);
 int cws_enqueue(mpcx_ctx *ctx, const CwsCall &c, const CwsWorkspace &ws, hipStream_t stream);
-// the call's host arrays replaced by copies on the device
-void cws_upload(DeviceArena &ar, CwsCall &c);
 
 // mpcx_avoidance_window* as its entry points take it, and as mpcx_avoidance_window_refine* (avoidance_window_refine.hip) runs it
 // as its pass 0
@@ -195,9 +243,8 @@ struct AwCall : CwsCall {
     double *du;
 };
 // the arguments of an entry point of either, under their names in include/mpcx.h, as an AwCall
-#define MPCX_AW_CALL                                                                                                                  \
-    AwCall{{{n, pairs, S, K, Ks, Y, U, units, span, consts, flags, max_step, P, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, \
-             mu, target_p}, radius, cat_radius, half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du}
+#define MPCX_AW_CALL \
+    AwCall{{MPCX_ENC_PROBLEM(radius, cat_radius, target_p), half_window, panels, who, out, sens, nullptr, status}, tol, max_eval, du}
 
 // The argument tests of mpcx_avoidance_window* and the call itself on a workspace of mpcx_avoidance_window_workspace_bytes(n, S, K,
 // panels) bytes.  (avoidance_window.hip)

@@ -127,37 +127,23 @@ __global__ __launch_bounds__(64) void encounter_window_kernel(EwArgs a)
 }
 
 // the call as both entry points take it (the names enc_sides reads)
-struct EwCall {
-    int n;
-    const double *pairs;
-    int S, K;
-    const int32_t *Ks;
-    const double *Y, *units, *span, *P, *radius;
-    int D, cat_K;
-    const int32_t *cat_Ks;
-    const double *cat_Y, *cat_units, *cat_span, *cat_P, *cat_radius;
-    double mu;
+struct EwCall : EncGeometry {
     const double *max_half;
     double nsigma;
     int levels;
     double *out;
     int32_t *flags, *status;
 };
+#define MPCX_EW_CALL EwCall{MPCX_GEOMETRY(radius, cat_radius), max_half, nsigma, levels, out, flags, status}
 
 static int ew_check(mpcx_ctx *ctx, const EwCall &c)
 {
-    if (c.n < 1 || c.S < 1 || c.K < 2 || !(c.mu > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: need n>=1, S>=1, K>=2, mu>0");
-    if (!(c.nsigma > 0.0) || !(fabs(c.nsigma) < INFINITY)) return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: nsigma must be positive and finite");
-    if (c.levels < 1 || c.levels > MPCX_EW_MAX_LEVELS)
-        return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: levels must be 1..MPCX_EW_MAX_LEVELS");
-    if (!c.pairs || !c.Y || !c.units || !c.span || !c.P || !c.radius || !c.max_half || !c.out || !c.flags || !c.status)
-        return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: pairs, Y, units, span, P, radius, max_half, out, flags and status are required");
-    if (c.cat_Y) {
-        if (c.D < 1 || c.cat_K < 2) return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: a catalogue needs D>=1, cat_K>=2");
-        if (!c.cat_units || !c.cat_span || !c.cat_P || !c.cat_radius)
-            return ctx_fail(ctx, MPCX_E_BADARG, "encounter_window: cat_units, cat_span, cat_P and cat_radius are required with cat_Y");
-    }
-    return MPCX_OK;
+    static const char *const name = "encounter_window";
+    if (int rc = geom_check_sizes(ctx, c, name)) return rc;
+    if (!(c.nsigma > 0.0) || !(fabs(c.nsigma) < INFINITY)) return enc_fail(ctx, name, "nsigma must be positive and finite");
+    if (c.levels < 1 || c.levels > MPCX_EW_MAX_LEVELS) return enc_fail(ctx, name, "levels must be 1..MPCX_EW_MAX_LEVELS");
+    return geom_check_arrays(ctx, c, name, true, c.max_half && c.out && c.flags && c.status,
+                             "pairs, Y, units, span, P, radius, max_half, out, flags and status");
 }
 
 static int ew_enqueue(mpcx_ctx *ctx, const EwCall &c, hipStream_t st)
@@ -181,8 +167,7 @@ extern "C" int mpcx_encounter_window_dev(mpcx_ctx *ctx, int n, const double *pai
                                          int levels, double *out, int32_t *flags, int32_t *status, void *stream)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const EwCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu,
-                   max_half, nsigma, levels, out, flags, status};
+    const EwCall c = MPCX_EW_CALL;
     if (int rc = ew_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     return ew_enqueue(ctx, c, (hipStream_t)stream);
@@ -195,30 +180,15 @@ extern "C" int mpcx_encounter_window(mpcx_ctx *ctx, int n, const double *pairs, 
                                      int levels, double *out, int32_t *flags, int32_t *status)
 {
     if (!ctx) return MPCX_E_BADARG;
-    const EwCall c{n, pairs, S, K, Ks, Y, units, span, P, radius, D, cat_K, cat_Ks, cat_Y, cat_units, cat_span, cat_P, cat_radius, mu,
-                   max_half, nsigma, levels, out, flags, status};
+    const EwCall c = MPCX_EW_CALL;
     if (int rc = ew_check(ctx, c)) return rc;
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     DeviceArena ar(ctx);
     EwCall d = c;
-    d.pairs = ar.upload(pairs, (size_t)n * 4);
-    d.max_half = ar.upload(max_half, (size_t)n);
-    d.Y = ar.upload(Y, (size_t)S * 7 * K); d.units = ar.upload(units, (size_t)S * 2); d.span = ar.upload(span, (size_t)S * 2);
-    d.P = ar.upload(P, (size_t)S * K * 36); d.radius = ar.upload(radius, S);
-    d.Ks = Ks ? ar.upload(Ks, S) : nullptr;
-    if (cat_Y) {
-        d.cat_Y = ar.upload(cat_Y, (size_t)D * 7 * cat_K); d.cat_units = ar.upload(cat_units, (size_t)D * 2);
-        d.cat_span = ar.upload(cat_span, (size_t)D * 2); d.cat_P = ar.upload(cat_P, (size_t)D * cat_K * 36);
-        d.cat_radius = ar.upload(cat_radius, D);
-        d.cat_Ks = cat_Ks ? ar.upload(cat_Ks, D) : nullptr;
-    }
-    d.out = ar.alloc<double>((size_t)n * MPCX_NEW);
-    d.flags = ar.alloc<int32_t>(n);
-    d.status = ar.alloc<int32_t>(n);
-    if (ar.failed()) return ar.code();
-    if (int rc = ew_enqueue(ctx, d, ctx->stream)) return rc;
-    ar.download(out, d.out, (size_t)n * MPCX_NEW);
-    ar.download(flags, d.flags, n);
-    ar.download(status, d.status, n);
-    return ar.finish();
+    geom_upload(ar, d); d.max_half = ar.upload(max_half, (size_t)n);
+    d.out = ar.result(out, (size_t)n * MPCX_NEW);
+    d.flags = ar.result(flags, (size_t)n);
+    d.status = ar.result(status, (size_t)n);
+    return host_run(ctx, ar, 0, [&](void *, hipStream_t st) { return ew_enqueue(ctx, d, st); });
 }
+#undef MPCX_EW_CALL

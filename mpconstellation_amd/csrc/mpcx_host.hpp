@@ -368,6 +368,20 @@ class DeviceArena {
         out_.push_back({h, pin, n * sizeof(T), ev});
         trace.mark("down:enq");
     }
+    // A result of the call, stated once: the device array behind the caller's `host` [n], on its way back with fetch().  A NULL
+    // host (an optional output that was not asked for) gives nullptr and brings nothing back.
+    template <typename T> T *result(T *host, size_t n)
+    {
+        if (!host) return nullptr;
+        T *d = alloc<T>(n);
+        results_.push_back({(char *)host, (const char *)d, n * sizeof(T)});
+        return d;
+    }
+    // the downloads of the registered results, in the order of their registration (after the kernels are enqueued)
+    void fetch()
+    {
+        for (const auto &r : results_) download(r.host, r.dev, r.bytes);
+    }
     // wait for the stream, then hand the downloads to the caller's buffers
     int finish()
     {
@@ -419,7 +433,22 @@ class DeviceArena {
     int code_;
     bool dirty_;              // transfers queued and not yet waited for
     std::vector<Out> out_;
+    struct Result { char *host; const char *dev; size_t bytes; };
+    std::vector<Result> results_;
 };
+
+// The tail of a host-pointer call whose arrays are staged and whose results are registered (DeviceArena::result): the arena's own
+// failure, the context's workspace of ws_bytes (0: the call has none, the context's is not touched), the call's
+// enqueue(workspace, stream) on the context's stream, the results on their way back, the wait.
+template <typename Enqueue> inline int host_run(mpcx_ctx *ctx, DeviceArena &ar, size_t ws_bytes, Enqueue enqueue)
+{
+    if (ar.failed()) return ar.code();
+    void *ws = ws_bytes ? ctx_workspace(ctx, ws_bytes) : nullptr;
+    if (ws_bytes && !ws) return MPCX_E_NOMEM;
+    if (int rc = enqueue(ws, ctx->stream)) return rc;
+    ar.fetch();
+    return ar.finish();
+}
 
 // A thrust law's parameters (include/mpcx.h: ctrl_vec is [S][3] under CONSTANT, [S] magnitudes under TANGENTIAL, the tables
 // [S][3][Ku] under SEQUENCE, which also has end_tau [S]; nothing under ZERO): how many doubles ctrl_vec holds, and both arrays
