@@ -12,7 +12,11 @@ namespace MPCX_NS {
     const unsigned long long rt0_ = __builtin_amdgcn_s_memrealtime(), mt0_ = __builtin_amdgcn_s_memtime();
 #define PT_BEGIN pt0_ = __builtin_amdgcn_s_memtime();
 #define PT_END(i) { pt_[i] += __builtin_amdgcn_s_memtime() - pt0_; pc_[i]++; }
+#define PT_PARAMS , unsigned long long (&pt_)[12], unsigned (&pc_)[12], unsigned long long &pt0_
+#define PT_ARGS , pt_, pc_, pt0_
 #else
+#define PT_PARAMS
+#define PT_ARGS
 #define PT_DECL
 #define PT_BEGIN
 #define PT_END(i)
@@ -33,6 +37,7 @@ __shared__ Scratch g_w;
 // the driver's pointer swaps went to scratch.  In LDS, at one address in every kernel, the phase functions address it with
 // compile-time offsets like the other two objects.
 __shared__ Sat g_s;
+__device__ __forceinline__ double *stage_area() { return (double *)&g_w; }
 #endif
 
 // View of satellite `sat`'s problem and of workspace slot `slot` (K: its node count, Kmax: the row length of the arrays)
@@ -129,6 +134,344 @@ __device__ __forceinline__ void shared_fold(GridSync &g, ResAcc &r, double tf, c
     }
 }
 
+// The interior-point iteration of one satellite, from the start point solve_satellite has left in the workspace to the last
+// accepted iterate; what it hands back is in sd.dv (status, it_count, E0, n_reg, first_reg) and sd.racc[0].  A function of its
+// own, not inlined: every value the loops keep in vector registers across a phase call is a scratch slot reloaded behind the
+// call, and inlined into solve_satellite the loops shared such slots with the start-up and the result section -- the zero
+// register (LDS base of every access to sd) went to scratch as the upper half of their zero-extended 64-bit indices, the
+// literals and the kernel arguments with it (profiles/solve_spill_traffic.txt).  (MPCX_NO_TAIL: see solve_common.hpp.)
+// The time-parallel build keeps it inlined: its kernel runs one wave per SIMD on more than 256 registers and its driver has no
+// such reloads (5 scratch loads in its loops); out of line the function is held to 256 and spills 34 registers there.
+#ifdef MPCX_TP
+#define MPCX_ITERATE_FN __device__ __forceinline__
+#else
+#define MPCX_ITERATE_FN __device__ __noinline__ MPCX_NO_TAIL
+#endif
+template <bool SHARED>
+MPCX_ITERATE_FN void ipm_iterate(const SolveArgs &a, const int sat, SatData &sd, Scratch &w, const double mu0, const int lane,
+                                                      GridSync *gsync PT_PARAMS)
+{
+    Sat &s = g_s;
+    const int K = uni(s.K), Kmax = a.K;
+    // (the options the loops read, copied to the loop state once: through `a` they were loads behind a pointer that every
+    //  block of the loops reloaded from scratch first)
+    sd.dv.tol = a.o.tol; sd.dv.acc_tol = a.o.acc_tol; sd.dv.acc_iter = a.o.acc_iter; sd.dv.max_iter = a.o.max_iter; sd.dv.n_refine = a.o.n_refine;
+    const double &tol = sd.dv.tol, &acc_tol = sd.dv.acc_tol;
+    const int &acc_iter = sd.dv.acc_iter, &max_iter = sd.dv.max_iter, &n_refine = sd.dv.n_refine;
+    int &clean = sd.dv.clean;
+    (void)sat; (void)Kmax;          // (the diagnostic builds' logs)
+    double gr[GR_N];                // (shared tf: operands / results of the launch-wide reductions)
+    // (the loop state lives in LDS, SatData::dv: see there)
+    double &mu = sd.dv.mu, &dw_last = sd.dv.dw_last;            // mu: this iteration's complementarity target
+    // (the start values of the loop state go out one field per lane -- DRV_D0 doubles from mu on, DRV_I0 counters from n_acc on:
+    //  written as constants by every lane they are 16-byte stores of register tuples with zero parts, and the register that
+    //  holds 0 -- the LDS base of every access to sd in this function -- is rematerialised only while no tuple has taken it in.
+    //  Counted with plain assignments here: 51 scratch loads and 37 vmcnt(0) waits in this function's loops, against 24 and 10.
+    //  The fields are addressed by their byte offsets inside sd.dv; the static_assert behind SatData pins their order)
+    {
+        char *const dvb = (char *)&sd.dv;
+        if (lane < SatData::DRV_D0)                                                               // mu | dw_last, E0
+            *(double *)(dvb + offsetof(SatData::Drv, mu) + lane * sizeof(double)) = (lane == 0) ? mu0 : 0.0;
+        if (lane < SatData::DRV_I0)                                                               // status, first_reg; the others 0
+            *(int *)(dvb + offsetof(SatData::Drv, n_acc) + lane * sizeof(int)) = (lane == 1) ? MPCX_ST_MAXITER : (lane == 4) ? -1 : 0;
+    }
+    // (shared tf: the counts of the whole launch -- S satellites without their own tf rows plus tf's two range inequalities)
+    const int nzc = uni(SHARED ? a.S * n_ineq(K, sd.nT, 1) + 2 : n_ineq(K, sd.nT, sd.fixed_tf));
+    const int nlc = uni((SHARED ? a.S : 1) * (7 * (K - 1) + (sd.nT == 6 ? 1 : 0)));
+    // (as doubles, with the loop state in LDS: converted once here they were two register pairs the loops reloaded from scratch)
+    double &nz = sd.dv.nz, &nzl = sd.dv.nzl;
+    nz = (double)nzc; nzl = (double)(nzc + nlc);
+    // shared tf: slacks / multipliers of 0 <= tf <= tf_max, their trial values, and the launch's part of the tf row
+    double gs[2] = {0.0, 0.0}, gz[2] = {0.0, 0.0}, gst[2] = {0.0, 0.0}, gzt[2] = {0.0, 0.0}, gds[2] = {0.0, 0.0}, gdz[2] = {0.0, 0.0};
+    if (SHARED) {
+        const double tf = sd.tfbar;
+        gs[0] = fmax(-(-tf - sd.b_tf[0]), kBoundPush * fmax(1.0, fabs(sd.b_tf[0]))); gz[0] = kMuInit / gs[0];
+        gs[1] = fmax(-(tf - sd.b_tf[1]), kBoundPush * fmax(1.0, fabs(sd.b_tf[1]))); gz[1] = kMuInit / gs[1];
+    }
+    const double b_tf2[2] = {sd.b_tf[0], sd.b_tf[1]};
+    int &n_acc = sd.dv.n_acc, &status = sd.dv.status, &it_count = sd.dv.it_count, &n_reg = sd.dv.n_reg, &first_reg = sd.dv.first_reg;
+    // second safeguard of the adaptive barrier rule (the first is the kMuErr bound below): after kFbN consecutive accepted
+    // steps shorter than kFbAlpha -- the iterate is jammed against its bounds -- mu is lifted to kFbBoost * mean(s z) and
+    // follows ipopt's monotone Fiacco-McCormick rule from then on.  kFbN = 8: benchmark problems at K = 100 take up to seven
+    // short regularised steps in a row and recover by themselves in 16 / 25 iterations (the monotone rule: 32 / 41).
+    int &mono = sd.dv.mono, &refined_prev = sd.dv.refined_prev, &n_small = sd.dv.n_small;      // refined_prev: the last iteration's unregularised solve ran refinement passes
+    double &E0 = sd.dv.E0;
+    // residual of the start point; afterwards the accepted trial of the line search is the next iteration's evaluation
+    // (sq in its mu = 0 form: it serves E_0 and, for any mu, the line search's ||F_mu||)
+    ResAcc &r0 = sd.racc[0], &rt = sd.racc[1];       // (in LDS: eval_residual<false> writes the first, <true> the second)
+    PT_END(6)
+    PT_BEGIN
+    eval_residual<false>(s, sd, 0.0, 0.0, 0.0, lane);
+    PT_END(0)
+    if (SHARED) shared_fold(*gsync, r0, sd.tfbar, b_tf2, gs, gz, 0.0, lane);
+    int &iter = sd.dv.iter;
+    for (iter = 0;; ++iter) {
+        it_count = iter;
+        E0 = uni(scaled_error_n(r0, nz, nzl, 0.0));
+        if (SHARED && gsync->aborted) { status = MPCX_ST_NUMERIC; break; }
+        if (!(E0 == E0) || !(E0 < 1e300)) { status = MPCX_ST_NUMERIC; break; }
+        if (E0 <= tol) { status = MPCX_ST_OK; break; }
+        n_acc = (E0 <= acc_tol) ? n_acc + 1 : 0;
+        if (n_acc >= acc_iter) { status = MPCX_ST_ACCEPTABLE; break; }
+        if (iter >= max_iter) { status = (E0 <= acc_tol) ? MPCX_ST_ACCEPTABLE : MPCX_ST_MAXITER; break; }
+        // adaptive barrier parameter: a fixed fraction of the iterate's mean complementarity (DESIGN.md, "Solver algorithm")
+        double &mu_cur = sd.dv.mu_cur;
+        mu_cur = uni(r0.prod_sum / nz);
+        if (!mono && n_small >= kFbN) {
+            mono = 1;
+            mu = uni(fmax(tol / 10.0, fmin(kMuInit, kFbBoost * mu_cur)));
+        }
+        // (never below kMuErr * E_0: the mean complementarity may collapse while the iterate is still infeasible)
+        if (!mono) mu = uni(fmax(fmax(clean ? fmin(kSigma * mu_cur, mu_cur * sqrt(mu_cur)) : kSigma * mu_cur, tol / 10.0), kMuErr * E0));
+        else {
+            // mu moves on only when the barrier problem is solved to E_mu <= 10 mu: mu <- max(tol/10, min(0.2 mu, mu^1.5))
+            for (int lv = 0; lv < 64 && mu > tol / 10.0 && scaled_error_n(r0, nz, nzl, mu) <= 10.0 * mu; ++lv)
+                mu = uni(fmax(tol / 10.0, fmin(0.2 * mu, mu * sqrt(mu))));
+        }
+        // Newton direction, with Hessian regularisation retries on breakdown
+        int &have_dir = sd.dv.have_dir;
+        double &delta_w = sd.dv.delta_w, &alpha = sd.dv.alpha;
+        have_dir = 0; delta_w = 0.0; alpha = 1.0;
+#ifdef MPCX_ITER_LOG
+        int fail_mask = 0;     // decimal digits: factor, border, finite-check failures of this iteration
+#endif
+        double &tau = sd.dv.tau;
+        tau = uni(fmax(0.99, 1.0 - mu));
+        // Hessian regularisation on breakdown follows ipopt's inertia-correction schedule: 0 first, then a third of
+        // the last value that worked (1e-4 the first time), growing by 8 (by 100 until some value has worked), up to 1e40
+        while (!have_dir && delta_w <= kDwMax) {
+            PT_BEGIN
+            // (an iteration that follows a refining one almost always refines too -- the barrier weights grow as mu falls -- and then
+            //  needs the Newton scalars kept: newton_blocks<true> at once, instead of <false> now and <true> again below.  Same
+            //  records either way: <true> is <false> plus the stores of the scalars)
+            const bool ns_kept = refined_prev && delta_w == 0.0;
+            if (ns_kept) newton_blocks<true>(s, sd, mu, delta_w, lane);
+            else newton_blocks<false>(s, sd, mu, delta_w, lane);
+            PT_END(1)
+            first_rhs_scalars(sd);    // (sd.rs_*; the node records of the first right-hand side: newton_blocks)
+#ifndef MPCX_TP                 // (the shared-tf launch has its own kernel, solve.hip)
+            if (SHARED) {
+                // ---- the same direction computation in lock step with the other satellites of the launch ----
+                GridSync &g = *gsync;
+                if (g.aborted) break;
+                // the launch's own part of the tf row: the 1 of the objective, the barrier terms of 0 <= tf <= tf_max, delta_w
+                double W_glob = delta_w, g_glob = 1.0, sig_tf = 0.0;
+                const double tfc = s.itg[G_TF];
+                const double gvv[2] = {-tfc - sd.b_tf[0], tfc - sd.b_tf[1]};
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const double sig = gz[j] / gs[j], zh = mu / gs[j] + sig * (gvv[j] + gs[j]);
+                    W_glob += sig; g_glob += (j == 0 ? -zh : zh); sig_tf = fmax(sig_tf, sig);
+                }
+                double twmax = fmax(sd.sigmax, sig_tf);
+                for (int t = 0; t < NTERM; ++t) twmax = fmax(twmax, sd.tw[t]);
+                gr_clear(gr); gr[GR_SUM] = twmax;
+                grid_reduce(g, gr, lane);                         // every satellite refines, or none
+                const int passes = 1 + ((delta_w == 0.0 && gr[GR_SUM] > kRefineTw) ? n_refine : 0);
+                if (passes > 1 && !ns_kept) newton_blocks<true>(s, sd, mu, delta_w, lane);
+                refined_prev = passes > 1;
+                bool okl = riccati_factor(s, sd, w, lane, passes > 1);     // (a local breakdown is reported through the border's reduction)
+                bool ok = true;
+                for (int pass = 0; pass < passes && ok; ++pass) {
+                    if (okl && pass > 0) { reduced_residual(s, sd, lane); sweep_backward(s, sd, w, 0, 1, lane); }
+                    if (okl) {
+                        sweep_forward(s, sd, w, 0, (pass == 0) ? NCH : 1, lane);
+                        if (pass == 0) okl = border_factor_shared(sd, lane);
+                    }
+                    const double dtf_cur = (pass == 0) ? 0.0 : s.drg[G_TF];
+                    ok = border_solve_shared(sd, g, W_glob, -(g_glob + W_glob * dtf_cur), !okl, lane);
+                    if (!ok) break;
+                    combine_channels(s, sd, lane, pass == 0);
+                }
+                if (ok) {
+                    alpha = uni(finish_direction(s, sd, mu, tau, lane));
+                    const bool fin = sd.dir_finite != 0;
+                    const double dtf = s.drg[G_TF];
+                    const double dgv[2] = {-dtf, dtf};
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {       // the range constraint's pairs: direction and fraction to the boundary
+                        const PairDir q = pair_dir(gs[j], gz[j], gvv[j], dgv[j], mu);
+                        gds[j] = q.ds; gdz[j] = q.dz;
+                        if (q.ds < 0.0) alpha = fmin(alpha, -tau * gs[j] / q.ds);
+                        if (q.dz < 0.0) alpha = fmin(alpha, -tau * gz[j] / q.dz);
+                    }
+                    gr_clear(gr); gr[0] = fin ? 0.0 : 1.0; gr[GR_SUM + GR_MAX] = alpha;
+                    grid_reduce(g, gr, lane);                     // one step length for the whole launch
+                    alpha = gr[GR_SUM + GR_MAX];
+                    ok = (gr[0] == 0.0) && !g.aborted;
+                }
+                if (ok) have_dir = 1;
+                else if (g.aborted) break;
+                else if (delta_w == 0.0) delta_w = (dw_last == 0.0) ? kDwFirst : fmax(kDwMin, dw_last / 3.0);
+                else delta_w *= (dw_last == 0.0) ? 100.0 : 8.0;
+                continue;
+            }
+#endif
+            // iterative refinement only once a barrier weight (terminal rank-1 terms, stage balls and planes, the tf
+            // bounds) is stiff enough to cost digits
+            double twmax = sd.sigmax;
+            for (int t = 0; t < NTERM; ++t) twmax = fmax(twmax, sd.tw[t]);
+            const int passes = 1 + ((delta_w == 0.0 && twmax > kRefineTw) ? n_refine : 0);
+            if (passes > 1 && !ns_kept) newton_blocks<true>(s, sd, mu, delta_w, lane);      // (the scalars reduced_residual reads)
+            if (delta_w == 0.0) refined_prev = passes > 1;
+            PT_BEGIN
+#ifdef MPCX_TP
+            bool ok = tp_cmd_factor(s, sd, g_tp, lane, passes > 1);       // every segment's factorisation + fused backward sweeps, side by side
+            if (g_tp.dead) break;                                         // (a workgroup of the satellite did not answer: MPCX_ST_NUMERIC)
+#else
+            bool ok = riccati_factor(s, sd, w, lane, passes > 1);   // factorisation + backward sweep of all 8 channels
+#endif
+            PT_END(2)
+#ifdef MPCX_ITER_LOG
+            if (!ok) fail_mask += 1;
+#endif
+            if (ok) {
+                // the direction starts from (0, ..., -lam, -lam_vt) so that the first right-hand side carries no
+                // multipliers; combine_channels writes it with that starting value (no separate reset pass)
+                for (int pass = 0; pass < passes && ok; ++pass) {
+                    if (pass > 0) {
+                        PT_BEGIN
+                        reduced_residual(s, sd, lane);
+                        PT_END(5)
+                    }
+                    // pass 0: all 8 channels (right-hand side + the 7 border columns); refinement: channel 0 only
+                    const int c1 = (pass == 0) ? NCH : 1;
+#ifdef MPCX_TP
+                    // the segments' sweeps side by side (all waves), then the coarse problem over the cuts: x_K and Sigma . lam of
+                    // every channel for the border
+                    PT_BEGIN
+                    (void)c1;
+                    if (pass > 0) tp_cmd_sweeps(s, sd, g_tp, lane, false);      // (the first pass's sweeps ran behind the factorisation)
+                    PT_END(3)
+                    if (g_tp.dead) { ok = false; break; }
+                    PT_BEGIN
+                    ok = tp_coarse(s, sd, g_tp, lane, pass == 0);
+                    if (ok && pass == 0) ok = border_factor(sd, lane);
+                    PT_END(4)
+#else
+                    if (pass > 0) {
+                        PT_BEGIN
+                        sweep_backward(s, sd, w, 0, c1, lane);
+                        PT_END(3)
+                    }
+                    PT_BEGIN
+                    sweep_forward(s, sd, w, 0, c1, lane);
+                    if (pass == 0) ok = border_factor(sd, lane);
+                    PT_END(4)
+#endif
+#ifdef MPCX_ITER_LOG
+                    if (!ok) fail_mask += 100;
+#endif
+                    if (!ok) break;
+                    PT_BEGIN
+                    border_solve(sd, lane);
+#if defined(MPCX_ITER_LOG) && defined(MPCX_LOG_IT)
+                    // diagnostic build only: the border system of one chosen iteration into this satellite's NU block
+                    if (iter == MPCX_LOG_IT && pass == 0 && lane == 0) {
+                        double *lg = a.NU + (size_t)sat * 7 * Kmax; int n = 0;
+                        for (int j = 0; j < NBD; ++j) lg[n++] = sd.sol[j];
+                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.tw[j];
+                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.twin[j];
+                        for (int j = 0; j < NCH; ++j) lg[n++] = sd.siglam[j];
+                        for (int c = 0; c < NCH; ++c) for (int j = 0; j < 7; ++j) lg[n++] = sd.xK[c][j];
+                        lg[n++] = sd.rs_gtf; lg[n++] = sd.rs_rvt;
+                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.rs_gex[j];
+                        lg[n++] = sd.Wtf; lg[n++] = sd.gam; lg[n++] = delta_w;
+                    }
+#endif
+#ifdef MPCX_TP
+                    tp_cmd_combine(s, sd, g_tp, lane, pass == 0);
+#else
+                    combine_channels(s, sd, lane, pass == 0);
+#endif
+                    PT_END(7)
+                }
+            }
+            if (ok) {
+                // dt, ds, dz, the fraction-to-the-boundary step and the finite check on the direction
+                PT_BEGIN
+                alpha = uni(finish_direction(s, sd, mu, tau, lane));
+                ok = sd.dir_finite != 0;
+                PT_END(8)
+#ifdef MPCX_ITER_LOG
+                if (!ok) fail_mask += 10000;
+#endif
+            }
+            if (ok) have_dir = 1;
+            else if (delta_w == 0.0) delta_w = (dw_last == 0.0) ? kDwFirst : fmax(kDwMin, dw_last / 3.0);
+            else delta_w *= (dw_last == 0.0) ? 100.0 : 8.0;
+        }
+        if (have_dir && delta_w > 0.0) { dw_last = delta_w; if (n_reg++ == 0) first_reg = iter; }
+        if (!have_dir) {
+#ifdef MPCX_ITER_LOG
+            if (lane == 0 && 5 * iter + 4 < 7 * K) { double *lg = a.X + (size_t)sat * 7 * Kmax + 5 * iter; lg[0] = mu; lg[1] = E0; lg[2] = -1.0; lg[3] = delta_w; lg[4] = (double)fail_mask; }
+#endif
+            status = MPCX_ST_NUMERIC; break;
+        }
+        // backtracking on ||F_mu||_2 with the N_-inf(gamma) neighbourhood
+        // ||F_mu||^2 of the iterate from the mu = 0 evaluation: sum (s z - mu)^2 = sum (s z)^2 - 2 mu sum s z + n mu^2
+        double &rn0 = sd.dv.rn0;
+        rn0 = uni(sqrt(fmax(0.0, r0.sq - 2.0 * mu * r0.prod_sum + nz * mu * mu)));
+        // every trial is evaluated as the iterate it would become (slack reset and multiplier safeguard applied) and
+        // left in the second iterate buffer
+        double &mu_clip = sd.dv.mu_clip;
+        mu_clip = uni(fmax(mu, mu_cur));
+        // shared tf: the trial values of the range constraint's pairs (slack reset and multiplier safeguard like every
+        // other pair), then the launch's residual from the satellites' (a reduction: every workgroup decides alike)
+        auto shared_trial = [&]() {
+            const double tft = s.itg[G_TF] + alpha * s.drg[G_TF];
+            const double gvt[2] = {-tft - sd.b_tf[0], tft - sd.b_tf[1]};
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                gst[j] = fmax(gs[j] + alpha * gds[j], -gvt[j]);
+                gzt[j] = fmin(gz[j] + alpha * gdz[j], kKappaSigma * (mu_clip * rcp_pos(gst[j])));
+            }
+            shared_fold(*gsync, rt, tft, b_tf2, gst, gzt, mu, lane);
+        };
+        int &have_trial = sd.dv.have_trial, &ls = sd.dv.ls;
+        have_trial = 0;
+        for (ls = 0; ls < 30; ++ls) {
+            if (0.5 * alpha < kAlphaFloor) break;      // a rejection could not shorten the step any more: take it
+            PT_BEGIN
+            eval_residual<true>(s, sd, alpha, mu, mu_clip, lane);
+            PT_END(10)
+            if (SHARED) shared_trial();
+            const bool dec = sqrt(rt.sq) <= (1.0 - 1e-4 * alpha) * rn0;
+            const bool cen = rt.prod_min >= kGammaNbhd * fmin(mu, rt.prod_sum / nz);
+#ifdef MPCX_ITER_LOG
+            // diagnostic build only: the first trial's margins into this satellite's U block
+            if (ls == 0 && lane == 0 && 3 * iter + 2 < 3 * K) { double *lg = a.U + (size_t)sat * 3 * Kmax + 3 * iter; lg[0] = alpha; lg[1] = sqrt(rt.sq) / rn0; lg[2] = rt.prod_min / (kGammaNbhd * fmin(mu, rt.prod_sum / nz)); }
+#endif
+            if (dec && cen) { have_trial = 1; break; }
+            alpha = uni(alpha * 0.5);
+        }
+        if (!have_trial) {                              // the step taken untested
+            PT_BEGIN
+            eval_residual<true>(s, sd, alpha, mu, mu_clip, lane);
+            PT_END(10)
+            if (SHARED) shared_trial();
+        }
+#ifdef MPCX_ITER_LOG
+        // diagnostic build only: iteration log (mu, E0, accepted step, regularisation) into this satellite's X block
+        if (lane == 0 && 5 * iter + 4 < 7 * K) { double *lg = a.X + (size_t)sat * 7 * Kmax + 5 * iter; lg[0] = mu; lg[1] = E0; lg[2] = alpha; lg[3] = delta_w; lg[4] = (double)fail_mask; }
+#endif
+        n_small = (alpha < kFbAlpha) ? n_small + 1 : 0;
+        // accept: the candidate becomes the iterate, its residual (sq back in the mu = 0 form) the next iteration's
+        if (lane == 0) { wf64 *q = s.it; s.it = s.itB; s.itB = q; lf64 *g = s.itg; s.itg = s.itgB; s.itgB = g; }
+        WG_SYNC();
+        if (SHARED) { gs[0] = gst[0]; gs[1] = gst[1]; gz[0] = gzt[0]; gz[1] = gzt[1]; }
+        {   // (both records are in LDS: the next iteration's evaluation is a copy of the accepted trial's, by the wave's first lanes)
+            const double sq0 = rt.sq + 2.0 * mu * rt.prod_sum - nz * mu * mu;
+            // (one field per lane: as a struct copy through a local it was 72 bytes of the function's stack, written and read back)
+            constexpr int RA_N = sizeof(ResAcc) / sizeof(double), RA_SQ = offsetof(ResAcc, sq) / sizeof(double);
+            const double t = (lane == RA_SQ) ? sq0 : ((const double *)&rt)[lane < RA_N ? lane : 0];
+            WG_SYNC();
+            if (lane < RA_N) ((double *)&r0)[lane] = t;
+            WG_SYNC();
+        }
+    }
+}
+
 // One satellite from the problem constants to its results; `slot` selects the workspace (see solve_kernel).
 // SHARED (solve_shared_kernel): the satellites of the launch share ONE final time (several satellites in one reference
 // Optimizer, optimizer.py:287,311,322,336).  Every workgroup runs this same iteration in lock step: barrier parameter, step
@@ -203,7 +546,7 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
     // (round 5: the next block's loads issued before a block's stores and wave-level fences in place of the barriers -- one memory
     //  round trip instead of four -- changes nothing under load, 4.85 / 4.87 ms at S4096_K30: profiles/r05/streaming_phases_ab.txt)
     {
-        double *stg = (double *)&w;
+        double *stg = stage_area();
         static_assert(sizeof(Scratch) >= 16 * MPCX_STAGE_DOUBLES * sizeof(double), "stage transposition buffer");
         for (int k0 = 0; k0 < K - 1; k0 += 16) {
             const int nk = (K - 1 - k0 < 16) ? K - 1 - k0 : 16;
@@ -285,301 +628,11 @@ __device__ __forceinline__ void solve_satellite(const SolveArgs &a, const int sa
     }
     WG_SYNC();
 
-    // (the loop state lives in LDS, SatData::dv: see there)
-    double &mu = sd.dv.mu, &dw_last = sd.dv.dw_last;            // mu: this iteration's complementarity target
-    mu = mu0; dw_last = 0.0;
-    // (shared tf: the counts of the whole launch -- S satellites without their own tf rows plus tf's two range inequalities)
-    const int nzc = uni(SHARED ? a.S * n_ineq(K, sd.nT, 1) + 2 : n_ineq(K, sd.nT, sd.fixed_tf));
-    const int nlc = uni((SHARED ? a.S : 1) * (7 * (K - 1) + (sd.nT == 6 ? 1 : 0)));
-    // shared tf: slacks / multipliers of 0 <= tf <= tf_max, their trial values, and the launch's part of the tf row
-    double gs[2] = {0.0, 0.0}, gz[2] = {0.0, 0.0}, gst[2] = {0.0, 0.0}, gzt[2] = {0.0, 0.0}, gds[2] = {0.0, 0.0}, gdz[2] = {0.0, 0.0};
-    if (SHARED) {
-        const double tf = sd.tfbar;
-        gs[0] = fmax(-(-tf - sd.b_tf[0]), kBoundPush * fmax(1.0, fabs(sd.b_tf[0]))); gz[0] = kMuInit / gs[0];
-        gs[1] = fmax(-(tf - sd.b_tf[1]), kBoundPush * fmax(1.0, fabs(sd.b_tf[1]))); gz[1] = kMuInit / gs[1];
-    }
-    const double b_tf2[2] = {sd.b_tf[0], sd.b_tf[1]};
-    int &n_acc = sd.dv.n_acc, &status = sd.dv.status, &it_count = sd.dv.it_count, &n_reg = sd.dv.n_reg, &first_reg = sd.dv.first_reg;
-    n_acc = 0; status = MPCX_ST_MAXITER; it_count = 0; n_reg = 0; first_reg = -1;
-    // second safeguard of the adaptive barrier rule (the first is the kMuErr bound below): after kFbN consecutive accepted
-    // steps shorter than kFbAlpha -- the iterate is jammed against its bounds -- mu is lifted to kFbBoost * mean(s z) and
-    // follows ipopt's monotone Fiacco-McCormick rule from then on.  kFbN = 8: benchmark problems at K = 100 take up to seven
-    // short regularised steps in a row and recover by themselves in 16 / 25 iterations (the monotone rule: 32 / 41).
-    int &mono = sd.dv.mono, &refined_prev = sd.dv.refined_prev, &n_small = sd.dv.n_small;      // refined_prev: the last iteration's unregularised solve ran refinement passes
-    double &E0 = sd.dv.E0;
-    mono = 0; refined_prev = 0; n_small = 0; E0 = 0.0;
-    // residual of the start point; afterwards the accepted trial of the line search is the next iteration's evaluation
-    // (sq in its mu = 0 form: it serves E_0 and, for any mu, the line search's ||F_mu||)
-    ResAcc &r0 = sd.racc[0], &rt = sd.racc[1];       // (in LDS: eval_residual<false> writes the first, <true> the second)
-    PT_END(6)
-    PT_BEGIN
-    eval_residual<false>(s, sd, 0.0, 0.0, 0.0, lane);
-    PT_END(0)
-    if (SHARED) shared_fold(*gsync, r0, sd.tfbar, b_tf2, gs, gz, 0.0, lane);
-    int &iter = sd.dv.iter;
-    for (iter = 0;; ++iter) {
-        it_count = iter;
-        E0 = uni(scaled_error_n(r0, nzc, nlc, 0.0));
-        if (SHARED && gsync->aborted) { status = MPCX_ST_NUMERIC; break; }
-        if (!(E0 == E0) || !(E0 < 1e300)) { status = MPCX_ST_NUMERIC; break; }
-        if (E0 <= o.tol) { status = MPCX_ST_OK; break; }
-        n_acc = (E0 <= o.acc_tol) ? n_acc + 1 : 0;
-        if (n_acc >= o.acc_iter) { status = MPCX_ST_ACCEPTABLE; break; }
-        if (iter >= o.max_iter) { status = (E0 <= o.acc_tol) ? MPCX_ST_ACCEPTABLE : MPCX_ST_MAXITER; break; }
-        // adaptive barrier parameter: a fixed fraction of the iterate's mean complementarity (DESIGN.md, "Solver algorithm")
-        double &mu_cur = sd.dv.mu_cur;
-        mu_cur = uni(r0.prod_sum / (double)nzc);
-        if (!mono && n_small >= kFbN) {
-            mono = 1;
-            mu = uni(fmax(o.tol / 10.0, fmin(kMuInit, kFbBoost * mu_cur)));
-        }
-        // (never below kMuErr * E_0: the mean complementarity may collapse while the iterate is still infeasible)
-        if (!mono) mu = uni(fmax(fmax(clean ? fmin(kSigma * mu_cur, mu_cur * sqrt(mu_cur)) : kSigma * mu_cur, o.tol / 10.0), kMuErr * E0));
-        else {
-            // mu moves on only when the barrier problem is solved to E_mu <= 10 mu: mu <- max(tol/10, min(0.2 mu, mu^1.5))
-            for (int lv = 0; lv < 64 && mu > o.tol / 10.0 && scaled_error_n(r0, nzc, nlc, mu) <= 10.0 * mu; ++lv)
-                mu = uni(fmax(o.tol / 10.0, fmin(0.2 * mu, mu * sqrt(mu))));
-        }
-        // Newton direction, with Hessian regularisation retries on breakdown
-        int &have_dir = sd.dv.have_dir;
-        double &delta_w = sd.dv.delta_w, &alpha = sd.dv.alpha;
-        have_dir = 0; delta_w = 0.0; alpha = 1.0;
-#ifdef MPCX_ITER_LOG
-        int fail_mask = 0;     // decimal digits: factor, border, finite-check failures of this iteration
-#endif
-        double &tau = sd.dv.tau;
-        tau = uni(fmax(0.99, 1.0 - mu));
-        // Hessian regularisation on breakdown follows ipopt's inertia-correction schedule: 0 first, then a third of
-        // the last value that worked (1e-4 the first time), growing by 8 (by 100 until some value has worked), up to 1e40
-        while (!have_dir && delta_w <= kDwMax) {
-            PT_BEGIN
-            // (an iteration that follows a refining one almost always refines too -- the barrier weights grow as mu falls -- and then
-            //  needs the Newton scalars kept: newton_blocks<true> at once, instead of <false> now and <true> again below.  Same
-            //  records either way: <true> is <false> plus the stores of the scalars)
-            const bool ns_kept = refined_prev && delta_w == 0.0;
-            if (ns_kept) newton_blocks<true>(s, sd, (double *)&w, mu, delta_w, lane);
-            else newton_blocks<false>(s, sd, (double *)&w, mu, delta_w, lane);
-            PT_END(1)
-            first_rhs_scalars(sd);    // (sd.rs_*; the node records of the first right-hand side: newton_blocks)
-#ifndef MPCX_TP                 // (the shared-tf launch has its own kernel, solve.hip)
-            if (SHARED) {
-                // ---- the same direction computation in lock step with the other satellites of the launch ----
-                GridSync &g = *gsync;
-                if (g.aborted) break;
-                // the launch's own part of the tf row: the 1 of the objective, the barrier terms of 0 <= tf <= tf_max, delta_w
-                double W_glob = delta_w, g_glob = 1.0, sig_tf = 0.0;
-                const double tfc = s.itg[G_TF];
-                const double gvv[2] = {-tfc - sd.b_tf[0], tfc - sd.b_tf[1]};
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double sig = gz[j] / gs[j], zh = mu / gs[j] + sig * (gvv[j] + gs[j]);
-                    W_glob += sig; g_glob += (j == 0 ? -zh : zh); sig_tf = fmax(sig_tf, sig);
-                }
-                double twmax = fmax(sd.sigmax, sig_tf);
-                for (int t = 0; t < NTERM; ++t) twmax = fmax(twmax, sd.tw[t]);
-                gr_clear(gr); gr[GR_SUM] = twmax;
-                grid_reduce(g, gr, lane);                         // every satellite refines, or none
-                const int passes = 1 + ((delta_w == 0.0 && gr[GR_SUM] > kRefineTw) ? o.n_refine : 0);
-                if (passes > 1 && !ns_kept) newton_blocks<true>(s, sd, (double *)&w, mu, delta_w, lane);
-                refined_prev = passes > 1;
-                bool okl = riccati_factor(s, sd, w, lane, passes > 1);     // (a local breakdown is reported through the border's reduction)
-                bool ok = true;
-                for (int pass = 0; pass < passes && ok; ++pass) {
-                    if (okl && pass > 0) { reduced_residual(s, sd, (double *)&w, lane); sweep_backward(s, sd, w, 0, 1, lane); }
-                    if (okl) {
-                        sweep_forward(s, sd, w, 0, (pass == 0) ? NCH : 1, lane);
-                        if (pass == 0) okl = border_factor_shared(sd, lane);
-                    }
-                    const double dtf_cur = (pass == 0) ? 0.0 : s.drg[G_TF];
-                    ok = border_solve_shared(sd, g, W_glob, -(g_glob + W_glob * dtf_cur), !okl, lane);
-                    if (!ok) break;
-                    combine_channels(s, sd, (double *)&w, lane, pass == 0);
-                }
-                if (ok) {
-                    alpha = uni(finish_direction(s, sd, mu, tau, lane));
-                    const bool fin = sd.dir_finite != 0;
-                    const double dtf = s.drg[G_TF];
-                    const double dgv[2] = {-dtf, dtf};
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {       // the range constraint's pairs: direction and fraction to the boundary
-                        const PairDir q = pair_dir(gs[j], gz[j], gvv[j], dgv[j], mu);
-                        gds[j] = q.ds; gdz[j] = q.dz;
-                        if (q.ds < 0.0) alpha = fmin(alpha, -tau * gs[j] / q.ds);
-                        if (q.dz < 0.0) alpha = fmin(alpha, -tau * gz[j] / q.dz);
-                    }
-                    gr_clear(gr); gr[0] = fin ? 0.0 : 1.0; gr[GR_SUM + GR_MAX] = alpha;
-                    grid_reduce(g, gr, lane);                     // one step length for the whole launch
-                    alpha = gr[GR_SUM + GR_MAX];
-                    ok = (gr[0] == 0.0) && !g.aborted;
-                }
-                if (ok) have_dir = 1;
-                else if (g.aborted) break;
-                else if (delta_w == 0.0) delta_w = (dw_last == 0.0) ? kDwFirst : fmax(kDwMin, dw_last / 3.0);
-                else delta_w *= (dw_last == 0.0) ? 100.0 : 8.0;
-                continue;
-            }
-#endif
-            // iterative refinement only once a barrier weight (terminal rank-1 terms, stage balls and planes, the tf
-            // bounds) is stiff enough to cost digits
-            double twmax = sd.sigmax;
-            for (int t = 0; t < NTERM; ++t) twmax = fmax(twmax, sd.tw[t]);
-            const int passes = 1 + ((delta_w == 0.0 && twmax > kRefineTw) ? o.n_refine : 0);
-            if (passes > 1 && !ns_kept) newton_blocks<true>(s, sd, (double *)&w, mu, delta_w, lane);      // (the scalars reduced_residual reads)
-            if (delta_w == 0.0) refined_prev = passes > 1;
-            PT_BEGIN
-#ifdef MPCX_TP
-            bool ok = tp_cmd_factor(s, sd, g_tp, lane, passes > 1);       // every segment's factorisation + fused backward sweeps, side by side
-            if (g_tp.dead) break;                                         // (a workgroup of the satellite did not answer: MPCX_ST_NUMERIC)
-#else
-            bool ok = riccati_factor(s, sd, w, lane, passes > 1);   // factorisation + backward sweep of all 8 channels
-#endif
-            PT_END(2)
-#ifdef MPCX_ITER_LOG
-            if (!ok) fail_mask += 1;
-#endif
-            if (ok) {
-                // the direction starts from (0, ..., -lam, -lam_vt) so that the first right-hand side carries no
-                // multipliers; combine_channels writes it with that starting value (no separate reset pass)
-                for (int pass = 0; pass < passes && ok; ++pass) {
-                    if (pass > 0) {
-                        PT_BEGIN
-                        reduced_residual(s, sd, (double *)&w, lane);
-                        PT_END(5)
-                    }
-                    // pass 0: all 8 channels (right-hand side + the 7 border columns); refinement: channel 0 only
-                    const int c1 = (pass == 0) ? NCH : 1;
-#ifdef MPCX_TP
-                    // the segments' sweeps side by side (all waves), then the coarse problem over the cuts: x_K and Sigma . lam of
-                    // every channel for the border
-                    PT_BEGIN
-                    (void)c1;
-                    if (pass > 0) tp_cmd_sweeps(s, sd, g_tp, lane, false);      // (the first pass's sweeps ran behind the factorisation)
-                    PT_END(3)
-                    if (g_tp.dead) { ok = false; break; }
-                    PT_BEGIN
-                    ok = tp_coarse(s, sd, g_tp, lane, pass == 0);
-                    if (ok && pass == 0) ok = border_factor(sd, lane);
-                    PT_END(4)
-#else
-                    if (pass > 0) {
-                        PT_BEGIN
-                        sweep_backward(s, sd, w, 0, c1, lane);
-                        PT_END(3)
-                    }
-                    PT_BEGIN
-                    sweep_forward(s, sd, w, 0, c1, lane);
-                    if (pass == 0) ok = border_factor(sd, lane);
-                    PT_END(4)
-#endif
-#ifdef MPCX_ITER_LOG
-                    if (!ok) fail_mask += 100;
-#endif
-                    if (!ok) break;
-                    PT_BEGIN
-                    border_solve(sd, lane);
-#if defined(MPCX_ITER_LOG) && defined(MPCX_LOG_IT)
-                    // diagnostic build only: the border system of one chosen iteration into this satellite's NU block
-                    if (iter == MPCX_LOG_IT && pass == 0 && lane == 0) {
-                        double *lg = a.NU + (size_t)sat * 7 * Kmax; int n = 0;
-                        for (int j = 0; j < NBD; ++j) lg[n++] = sd.sol[j];
-                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.tw[j];
-                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.twin[j];
-                        for (int j = 0; j < NCH; ++j) lg[n++] = sd.siglam[j];
-                        for (int c = 0; c < NCH; ++c) for (int j = 0; j < 7; ++j) lg[n++] = sd.xK[c][j];
-                        lg[n++] = sd.rs_gtf; lg[n++] = sd.rs_rvt;
-                        for (int j = 0; j < NTERM; ++j) lg[n++] = sd.rs_gex[j];
-                        lg[n++] = sd.Wtf; lg[n++] = sd.gam; lg[n++] = delta_w;
-                    }
-#endif
-#ifdef MPCX_TP
-                    tp_cmd_combine(s, sd, g_tp, (double *)&w, lane, pass == 0);
-#else
-                    combine_channels(s, sd, (double *)&w, lane, pass == 0);
-#endif
-                    PT_END(7)
-                }
-            }
-            if (ok) {
-                // dt, ds, dz, the fraction-to-the-boundary step and the finite check on the direction
-                PT_BEGIN
-                alpha = uni(finish_direction(s, sd, mu, tau, lane));
-                ok = sd.dir_finite != 0;
-                PT_END(8)
-#ifdef MPCX_ITER_LOG
-                if (!ok) fail_mask += 10000;
-#endif
-            }
-            if (ok) have_dir = 1;
-            else if (delta_w == 0.0) delta_w = (dw_last == 0.0) ? kDwFirst : fmax(kDwMin, dw_last / 3.0);
-            else delta_w *= (dw_last == 0.0) ? 100.0 : 8.0;
-        }
-        if (have_dir && delta_w > 0.0) { dw_last = delta_w; if (n_reg++ == 0) first_reg = iter; }
-        if (!have_dir) {
-#ifdef MPCX_ITER_LOG
-            if (lane == 0 && 5 * iter + 4 < 7 * K) { double *lg = a.X + (size_t)sat * 7 * Kmax + 5 * iter; lg[0] = mu; lg[1] = E0; lg[2] = -1.0; lg[3] = delta_w; lg[4] = (double)fail_mask; }
-#endif
-            status = MPCX_ST_NUMERIC; break;
-        }
-        // backtracking on ||F_mu||_2 with the N_-inf(gamma) neighbourhood
-        // ||F_mu||^2 of the iterate from the mu = 0 evaluation: sum (s z - mu)^2 = sum (s z)^2 - 2 mu sum s z + n mu^2
-        double &rn0 = sd.dv.rn0;
-        rn0 = uni(sqrt(fmax(0.0, r0.sq - 2.0 * mu * r0.prod_sum + (double)nzc * mu * mu)));
-        // every trial is evaluated as the iterate it would become (slack reset and multiplier safeguard applied) and
-        // left in the second iterate buffer
-        double &mu_clip = sd.dv.mu_clip;
-        mu_clip = uni(fmax(mu, mu_cur));
-        // shared tf: the trial values of the range constraint's pairs (slack reset and multiplier safeguard like every
-        // other pair), then the launch's residual from the satellites' (a reduction: every workgroup decides alike)
-        auto shared_trial = [&]() {
-            const double tft = s.itg[G_TF] + alpha * s.drg[G_TF];
-            const double gvt[2] = {-tft - sd.b_tf[0], tft - sd.b_tf[1]};
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                gst[j] = fmax(gs[j] + alpha * gds[j], -gvt[j]);
-                gzt[j] = fmin(gz[j] + alpha * gdz[j], kKappaSigma * (mu_clip * rcp_pos(gst[j])));
-            }
-            shared_fold(*gsync, rt, tft, b_tf2, gst, gzt, mu, lane);
-        };
-        int &have_trial = sd.dv.have_trial, &ls = sd.dv.ls;
-        have_trial = 0;
-        for (ls = 0; ls < 30; ++ls) {
-            if (0.5 * alpha < kAlphaFloor) break;      // a rejection could not shorten the step any more: take it
-            PT_BEGIN
-            eval_residual<true>(s, sd, alpha, mu, mu_clip, lane);
-            PT_END(10)
-            if (SHARED) shared_trial();
-            const bool dec = sqrt(rt.sq) <= (1.0 - 1e-4 * alpha) * rn0;
-            const bool cen = rt.prod_min >= kGammaNbhd * fmin(mu, rt.prod_sum / (double)nzc);
-#ifdef MPCX_ITER_LOG
-            // diagnostic build only: the first trial's margins into this satellite's U block
-            if (ls == 0 && lane == 0 && 3 * iter + 2 < 3 * K) { double *lg = a.U + (size_t)sat * 3 * Kmax + 3 * iter; lg[0] = alpha; lg[1] = sqrt(rt.sq) / rn0; lg[2] = rt.prod_min / (kGammaNbhd * fmin(mu, rt.prod_sum / (double)nzc)); }
-#endif
-            if (dec && cen) { have_trial = 1; break; }
-            alpha = uni(alpha * 0.5);
-        }
-        if (!have_trial) {                              // the step taken untested
-            PT_BEGIN
-            eval_residual<true>(s, sd, alpha, mu, mu_clip, lane);
-            PT_END(10)
-            if (SHARED) shared_trial();
-        }
-#ifdef MPCX_ITER_LOG
-        // diagnostic build only: iteration log (mu, E0, accepted step, regularisation) into this satellite's X block
-        if (lane == 0 && 5 * iter + 4 < 7 * K) { double *lg = a.X + (size_t)sat * 7 * Kmax + 5 * iter; lg[0] = mu; lg[1] = E0; lg[2] = alpha; lg[3] = delta_w; lg[4] = (double)fail_mask; }
-#endif
-        n_small = (alpha < kFbAlpha) ? n_small + 1 : 0;
-        // accept: the candidate becomes the iterate, its residual (sq back in the mu = 0 form) the next iteration's
-        if (lane == 0) { wf64 *q = s.it; s.it = s.itB; s.itB = q; lf64 *g = s.itg; s.itg = s.itgB; s.itgB = g; }
-        WG_SYNC();
-        if (SHARED) { gs[0] = gst[0]; gs[1] = gst[1]; gz[0] = gzt[0]; gz[1] = gzt[1]; }
-        {   // (both records are in LDS: the next iteration's evaluation is a copy of the accepted trial's, by the wave's first lanes)
-            const double sq0 = rt.sq + 2.0 * mu * rt.prod_sum - (double)nzc * mu * mu;
-            const ResAcc t = rt;
-            WG_SYNC();
-            r0 = t; r0.sq = sq0;
-            WG_SYNC();
-        }
-    }
+    // the iteration (out of line: see ipm_iterate); its outcome is in the loop state and the iterate's residual record
+    ipm_iterate<SHARED>(a, sat, sd, w, mu0, lane, gsync PT_ARGS);
+    const ResAcc &r0 = sd.racc[0];
+    const int status = sd.dv.status, it_count = sd.dv.it_count, n_reg = sd.dv.n_reg, first_reg = sd.dv.first_reg;
+    const double E0 = sd.dv.E0;
 
     // ---- results in the reference's shapes: X (7,K), U (3,K), NU (7,K) ----
     for (int k = lane; k < K; k += 64) {

@@ -52,8 +52,13 @@ struct SatData {
     // Here a call costs them nothing and a use is an LDS read.
     struct Drv {
         double mu, dw_last, E0, delta_w, alpha, tau, mu_cur, rn0, mu_clip;
+        double nz, nzl;      // the counts of inequality pairs, and of pairs plus equality rows, as the doubles the error scaling divides by
         int n_acc, status, it_count, n_reg, first_reg, mono, refined_prev, n_small, iter, have_dir, have_trial, clean, ls;
+        double tol, acc_tol;                     // the solve's options that the loops read (SolveOpts)
+        int acc_iter, max_iter, n_refine;
     } dv;
+    // (ipm_iterate writes the start values of mu, dw_last, E0 and of n_acc .. n_small one field per lane: they lead their types)
+    static constexpr int DRV_D0 = 3, DRV_I0 = 8;
     double infeas;           // > 0: the constraint set is empty whatever the dynamics (structural_violation)
     double eps_r;            // the satellite's own eps_r (build_terminal_sat): the clean-start test reads it
     int flag;
@@ -61,6 +66,11 @@ struct SatData {
     unsigned long long fpt[16];   // diagnostic build only: cycle sums of the recursion's inner phases
 #endif
 };
+
+static_assert(offsetof(SatData::Drv, mu) == 0 && offsetof(SatData::Drv, E0) == (SatData::DRV_D0 - 1) * sizeof(double) &&
+              offsetof(SatData::Drv, n_small) - offsetof(SatData::Drv, n_acc) == (SatData::DRV_I0 - 1) * sizeof(int) &&
+              offsetof(SatData::Drv, status) - offsetof(SatData::Drv, n_acc) == sizeof(int) &&
+              offsetof(SatData::Drv, first_reg) - offsetof(SatData::Drv, n_acc) == 4 * sizeof(int), "field order of the loop state's start values");
 
 __device__ __forceinline__ double relax(double b) { return b + kBoundRelax * fmax(1.0, fabs(b)); }
 
@@ -725,11 +735,12 @@ __device__ __noinline__ void eval_residual(const Sat &s, SatData &sd, double a, 
 __device__ __forceinline__ int n_ineq(int K, int nT, int fixed_tf) { return K + (K - 1) + (K - 2) + nT + 1 + 14 * (K - 1) + (fixed_tf ? 0 : 2); }
 
 // ipopt's scaled optimality error E_mu from one residual evaluation: max_i |s_i z_i - mu| = max(pmax - mu, mu - pmin)
-__device__ double scaled_error_n(const ResAcc &r, int nz, int nl, double mu)
+// (nz, nzl: the number of inequality pairs and that number plus the equality rows, as doubles -- SatData::Drv)
+__device__ double scaled_error_n(const ResAcc &r, double nz, double nzl, double mu)
 {
     const double smax = 100.0;
-    const double sdl = fmax(smax, (r.zsum + r.lsum) / (double)(nz + nl)) / smax;
-    const double sc = fmax(smax, r.zsum / (double)nz) / smax;
+    const double sdl = fmax(smax, (r.zsum + r.lsum) / nzl) / smax;
+    const double sc = fmax(smax, r.zsum / nz) / smax;
     const double comp = fmax(r.prod_max - mu, mu - r.prod_min);
     return fmax(fmax(r.dual_max / sdl, r.prim_max), comp / sc);
 }
@@ -743,6 +754,11 @@ __device__ double scaled_error(const ResAcc &r, int K, int nT, int fixed_tf, dou
     return fmax(fmax(r.dual_max / sdl, r.prim_max), comp / sc);
 }
 
+// The LDS staging area of the node-parallel phases: the recursion's scratch (g_w, idle while they run), defined with the kernels'
+// LDS objects behind these headers (solve_driver.hpp; solve_tp.hpp).  The phases address it here, at its compile-time address,
+// instead of taking it as a pointer argument from the driver.
+__device__ __forceinline__ double *stage_area();
+
 // ---- Newton blocks (stage-parallel) ------------------------------------------------------------
 // stg: LDS staging area of 32 * (NB_N + RHS_N) doubles (the recursion's scratch, idle during this phase).  A node's Newton and
 // right-hand-side records are assembled there and the 32 records of a round go out as contiguous, coalesced blocks: written straight from the node
@@ -752,8 +768,9 @@ __device__ double scaled_error(const ResAcc &r, int K, int nT, int fixed_tf, dou
 // refinement passes of a stiff iteration) reads them: the driver runs newton_blocks<true> once more when it finds that the
 // iteration refines (rare), the plain iteration does not write them.
 template <bool KEEP_NS>
-__device__ __noinline__ void newton_blocks(const Sat &s, SatData &sd, double *stg, double mu, double delta_w, int lane)
+__device__ __noinline__ void newton_blocks(const Sat &s, SatData &sd, double mu, double delta_w, int lane)
 {
+    double *const stg = stage_area();
     const int K = s.K;
     const double w_tr = sd.w_tr, w_nu = sd.w_nu, b_u = sd.b_u, b_rmax = sd.b_rmax, b_rmin = sd.b_rmin;
     const int half = HALF_OF(lane);
@@ -1018,8 +1035,9 @@ __device__ __noinline__ void newton_blocks(const Sat &s, SatData &sd, double *st
 // four components per lane and round so that their loads are in flight together.  `first` (the plain solve of an
 // iteration): the direction is written, with -lam as the starting value of the multiplier part (the first
 // right-hand side carries no multipliers); otherwise (refinement) the correction is added.
-__device__ __noinline__ void combine_channels(const Sat &s_in, SatData &sd, double *stg, int lane, bool first)
+__device__ __noinline__ void combine_channels(const Sat &s_in, SatData &sd, int lane, bool first)
 {
+    double *const stg = stage_area();
     const Sat s = uniform_view(s_in);
     const int K = s.K, KP = s.KP;
     double sol[NBD];
@@ -1113,8 +1131,9 @@ __device__ __noinline__ void combine_channels(const Sat &s_in, SatData &sd, doub
 // stg: LDS staging area (the recursion's scratch, idle here) of 64 right-hand-side records: they leave as coalesced blocks
 // (straight from the node lanes they were 24 eight-byte stores per node, each to its own cache line: this phase was as long
 // as a factorisation on problems that refine in most iterations -- the stiff terminal windows of OptimalController's options).
-__device__ __noinline__ void reduced_residual(const Sat &s, SatData &sd, double *stg, int lane)
+__device__ __noinline__ void reduced_residual(const Sat &s, SatData &sd, int lane)
 {
+    double *const stg = stage_area();
     double rvt_rhs, gex[NTERM];      // (-> sd.rs_rvt, sd.rs_gex at the end; sd.rs_gtf)
     const int K = s.K;
     double gtf_part = 0.0;

@@ -58,6 +58,7 @@ __shared__ SatData g_sd;
 __shared__ Scratch g_w;
 __shared__ Sat g_s;                      // (the view of the satellite's problem and workspace: solve_driver.hpp)
 __shared__ TpData g_tp;
+__device__ __forceinline__ double *stage_area() { return (double *)&g_w; }
 
 // mailbox of a satellite's workgroups (ints in global memory, zeroed by the host before the launch)
 enum { TPM_SEQ = 0, TPM_CMD = 1, TPM_ARG = 2, TPM_DONE = 3, TPM_OK = 4, TPM_DEAD = 5, TPM_PROG = 8, TPM_XCC = 12 };
@@ -526,8 +527,9 @@ __device__ __forceinline__ void tp_combine_coefs(SatData &sd, TpData &tp, int la
     }
     wsync();
 }
-__device__ __noinline__ void tp_combine(const Sat &s_in, SatData &sd, TpData &tp, double *stg, int lane, bool first, int wave)
+__device__ __noinline__ void tp_combine(const Sat &s_in, SatData &sd, TpData &tp, int lane, bool first, int wave)
 {
+    double *const stg = stage_area();
     const Sat s = uniform_view(s_in);
     const int K = s.K, KP = s.KP;
     const int nseg = tp.nseg;
@@ -707,12 +709,12 @@ __device__ __forceinline__ void tp_cmd_sweeps(const Sat &s, SatData &sd, TpData 
     TP_DBG("[drv b%d] workers' sweeps done dead %d\n", (int)blockIdx.x, tp.dead);
 }
 
-__device__ __forceinline__ void tp_cmd_combine(const Sat &s, SatData &sd, TpData &tp, double *stg, int lane, bool first)
+__device__ __forceinline__ void tp_cmd_combine(const Sat &s, SatData &sd, TpData &tp, int lane, bool first)
 {
     tp_combine_coefs(sd, tp, lane);
     if (lane == 0) { tp.it_cur = s.it; g_w.cmd = CMD_COMBINE; g_w.cmd_arg = first ? 1 : 0; }
     WG_BARRIER();
-    tp_combine(s, sd, tp, stg, lane, first, 0);
+    tp_combine(s, sd, tp, lane, first, 0);
 }
 
 // a workgroup that owns another segment: wait for the first workgroup's commands (its first wave polls the mailbox, the second

@@ -12,6 +12,14 @@ With --func NAME / --kernel NAME (both repeatable, any translation unit of the s
 spills, scratch bytes, static LDS from the code object metadata:
 
     python profiles/tools/isa_loop_mix.py --src mpconstellation_amd/csrc/solve2w.hip --func riccati_factor2 --kernel solve_kernel2w
+
+With --driver FUNCTION (a kernel or a device function; every instantiation of a template) it prints the spill traffic of the
+function's own body: per loop depth the instructions, the scratch loads and stores by stack offset, the full vmcnt(0) waits, the
+lane moves of the SGPR spills and the calls; then the whole-body spill figures of every function of the translation unit that has
+any (scratch instructions, lane moves, spilled VGPR dwords, SGPR spill lanes).  The code object metadata that --kernel prints
+counts a kernel's own body only, not the functions it calls (profiles/solve_spill_traffic.txt):
+
+    python profiles/tools/isa_loop_mix.py --driver solve_kernel --driver ipm_iterate --kernel solve_kernel
 """
 import argparse
 import collections
@@ -137,6 +145,102 @@ def kernel_meta(text, kernel=KERNEL):
     return meta
 
 
+def blocks_by_depth(body):
+    """[(loop depth, [instruction, ...]), ...] of a function's basic blocks, from the compiler's block annotations
+    (`=>This Loop Header: Depth=n`, which may stand on a comment line of its own behind the label, and `in Loop: Header=... Depth=n`)"""
+    out = []
+    fresh = False       # the last line was a block label or one of its comment lines
+    for ln in body:
+        m = re.match(r"^(\.LBB\w+|; %bb\.\d+):\s*(;.*)?$", ln)
+        if m:
+            out.append([0, []])
+            fresh = True
+        elif not (fresh and re.match(r"^\s+;", ln)):
+            fresh = False
+        if fresh and out:
+            d = re.search(r"Loop Header: Depth=(\d+)|in Loop: Header=\w+ Depth=(\d+)", ln)
+            if d:
+                out[-1][0] = int(d.group(1) or d.group(2))
+            continue
+        s = ln.strip()
+        if not out or not s or s.startswith((";", ".")) or s.endswith(":"):
+            continue
+        out[-1][1].append(s.split(";")[0].strip())
+    return out
+
+
+def scratch_offset(ins):
+    m = re.search(r"offset:(\d+)", ins)
+    return int(m.group(1)) if m else 0
+
+
+def short_name(mangled):
+    ns = re.match(r"^_ZN(\d+)", mangled)                    # _ZN <length> namespace <length> name ...
+    dm = re.compile(r"(\d+)").match(mangled, ns.end() + int(ns.group(1)))
+    n = int(dm.group(1))
+    return mangled[dm.end():dm.end() + n] + ("<1>" if "ILb1E" in mangled else "<0>" if "ILb0E" in mangled else "")
+
+
+def spill_figures(raw):
+    """whole body of one function from its assembly lines: scratch instructions, lane moves, and the spill slots they serve --
+    dwords of the distinct stack offsets the compiler marks `Folded Spill`, distinct (register, lane) targets of v_writelane"""
+    ins = [l.strip() for l in raw]
+    slots, lanes = {}, set()
+    for i in ins:
+        m = re.match(r"scratch_store_dword(x(\d))?\b.*Folded Spill", i)
+        if m:
+            slots[scratch_offset(i)] = int(m.group(2) or 1)
+        m = re.match(r"v_writelane_b32 (v\d+), \S+ (\d+)", i)
+        if m:
+            lanes.add(m.groups())
+    return {"scratch": sum(1 for i in ins if i.startswith("scratch_")),
+            "lane moves": sum(1 for i in ins if re.match(r"v_(readlane|writelane)", i)),
+            "VGPR spill dwords": sum(slots.values()), "SGPR spill lanes": len(lanes)}
+
+
+def driver_census(lines, func):
+    """Spill traffic of a function's own body per loop depth -- a kernel (its driver, inlined) or a device function, every
+    instantiation if it is a template -- then its whole-body spill figures and those of every out-of-line function of the
+    translation unit.  A kernel's code object metadata (--kernel) counts the spills of the kernel's own body only: the functions
+    it calls are in this table."""
+    rx = re.compile(r"^(_ZN\d+mpcx\w*?%d%s[EI]\S*):" % (len(func), re.escape(func)))
+    names = [rx.match(l).group(1) for l in lines if rx.match(l)]
+    if not names:
+        sys.exit(f"function {func} not found")
+    for name in names:
+        raw = function_lines(lines, name)[1:]
+        blocks = blocks_by_depth(raw)
+        print(f"{short_name(name)}: the function's own body by loop depth")
+        loops_ld = loops_wait = 0
+        for depth in sorted({d for d, _ in blocks}):
+            ins = [i for d, b in blocks if d == depth for i in b]
+            ld = collections.Counter(scratch_offset(i) for i in ins if i.startswith("scratch_load"))
+            st = collections.Counter(scratch_offset(i) for i in ins if i.startswith("scratch_store"))
+            waits = sum(1 for i in ins if re.match(r"s_waitcnt .*vmcnt[(]0[)]", i))
+            print(f"  depth {depth}: {len(ins)} instructions, scratch loads {sum(ld.values())}, scratch stores {sum(st.values())}, "
+                  f"vmcnt(0) waits {waits}, "
+                  f"v_readlane {sum(1 for i in ins if i.startswith('v_readlane'))}, v_writelane {sum(1 for i in ins if i.startswith('v_writelane'))}, "
+                  f"calls {sum(1 for i in ins if i.startswith('s_swappc'))}")
+            for what, c in (("loads", ld), ("stores", st)):
+                if c:
+                    print(f"    {what} by stack offset: " + ", ".join(f"{o}: {n}" for o, n in sorted(c.items())))
+            if depth >= 1:
+                loops_ld += sum(ld.values()); loops_wait += waits
+        print(f"  in loops (depth >= 1): {loops_ld} scratch loads, {loops_wait} vmcnt(0) waits")
+        print("  whole body: " + ", ".join(f"{k} {v}" for k, v in spill_figures(raw).items()))
+
+
+def function_table(lines):
+    print("functions of the translation unit: " + " / ".join(spill_figures([]).keys()))
+    for ln in lines:
+        m = re.match(r"^(_ZN\d+mpcx\w*?\d+\w+?E\S*):", ln)
+        if not m:
+            continue
+        f = spill_figures(function_lines(lines, m.group(1))[1:])
+        if any(f.values()):
+            print(f"  {short_name(m.group(1))}: " + " / ".join(str(v) for v in f.values()))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--src", default=os.path.join(ROOT, "mpconstellation_amd", "csrc", "solve.hip"))
@@ -144,6 +248,7 @@ def main():
     ap.add_argument("--keep", help="keep the compiled assembly here")
     ap.add_argument("--func", action="append", default=[], help="whole-function instruction counts of this function")
     ap.add_argument("--kernel", action="append", default=[], help="register / spill / scratch / LDS figures of this kernel")
+    ap.add_argument("--driver", action="append", default=[], help="spill traffic of this function's body (kernel or device function) per loop depth, and spill figures of every function")
     args = ap.parse_args()
     if args.asm:
         path = args.asm
@@ -152,7 +257,11 @@ def main():
         compile_asm(args.src, path)
     text = open(path).read()
     lines = text.splitlines()
-    if args.func or args.kernel:
+    if args.func or args.kernel or args.driver:
+        for name in args.driver:
+            driver_census(lines, name)
+        if args.driver:
+            function_table(lines)
         for name in args.func:
             f = function_figures(lines, name)
             print(f"{name}: " + ", ".join(f"{k} {v}" for k, v in f.items()))
