@@ -87,6 +87,17 @@ extern "C" {
  * without MPCX_FLAG_DRAG, or on a context with no atmosphere set, is MPCX_E_BADARG before anything is enqueued.  Without the
  * bit every call takes the kernels it takes on a context that never had an atmosphere. */
 #define MPCX_FLAG_ATMO 32
+/* mpcx_discretize_stages_dev and mpcx_discretize_stages_ragged_dev only, with MPCX_FLAG_DRAG and the adaptive RK45 steps: the
+ * record's Sigma slot (doubles 91..97) holds the drag column G_k in Sigma_k's place,
+ *   G_k = d x_k+1 / d beta = A_k int Phi(tau)^-1 tf [0; a_D(x(tau)); 0] dtau,
+ * the sensitivity of the interval's end state to a scale (1 + beta) on the drag acceleration a_D -- the fixed density's, or the
+ * context's atmosphere's under MPCX_FLAG_ATMO -- over the same accepted nodes, by the same trapezoid and the same A_k as the other
+ * columns; its mass row is 0.  A, B_kn, B_kp and xi of such a record are, to the bit, what the call without the bit writes, and the
+ * steps are the same.  The solver cannot read such a record (it needs Sigma): mpcx_covariance_drag_batch does.  The bit without
+ * MPCX_FLAG_DRAG, with MPCX_FLAG_UNIFORM_STEPS or with MPCX_FLAG_RK23: MPCX_E_BADARG with "discretize" in the message, nothing
+ * enqueued.  The reference-layout discretize calls and the fused step ignore the bit; every other entry point treats it as the
+ * unknown flag it is there. */
+#define MPCX_FLAG_DRAG_COLUMN 64
 
 /* normalised constants per satellite: reference constants.py:11-20 field order */
 enum { MPCX_C_MU = 0, MPCX_C_R_E, MPCX_C_J2, MPCX_C_G0, MPCX_C_ISP, MPCX_C_S, MPCX_C_R0,
@@ -829,6 +840,54 @@ int mpcx_covariance_thrust_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t 
                                      const double *units, const double *span, const double *consts, int flags, double max_step,
                                      const double *P0, const double *q, const double *exec, const double *m_var0, double *P, double *Pm,
                                      int32_t *status, void *workspace, void *stream);
+
+/*
+ * mpcx_covariance_drag_batch: mpcx_covariance_thrust_batch with a fourth source of uncertainty, the drag.  The other chains treat
+ * the drag as known exactly; over several revolutions the error of the atmospheric density together with the ballistic coefficient
+ * (typically 10-30 %) is the largest uncertainty of a low orbit, it grows along-track roughly quadratically with time, and white
+ * acceleration noise q cannot imitate it.  Arguments as mpcx_covariance_thrust_batch, with
+ *   flags containing MPCX_FLAG_DRAG (the drag is always in the model), exec optional (NULL: all-zero rows, no execution error),
+ *   dens [S][MPCX_NDENS] = (sigma_b, tau_b) per satellite  ->  P [S][K][6][6], Pm [S][K][7] (optional), Pb [S][K][8] (optional,
+ *   NULL: not returned), status [S].
+ * The model.  The drag acceleration of satellite s is (1 + beta) a_D; beta, the fractional error of rho C_D S / m, is a zero-mean
+ * scalar, independent of the initial state, of the thrust errors and of q: a first-order Gauss-Markov process with stationary
+ * variance sigma_b^2 and correlation time tau_b in seconds, held constant over each node interval:
+ *   beta_k+1 = phi beta_k + w_k,  phi = exp(-h / tau_b),  Var w_k = (1 - phi^2) sigma_b^2,  h the node spacing in seconds.
+ * tau_b = +inf is a constant bias (the classical consider parameter): phi = 1 exactly.
+ * The chain runs over z = (position, velocity, mass, beta).  The library linearises once, with MPCX_FLAG_DRAG_COLUMN, so that every
+ * record carries G_k = d x_k+1 / d beta; with D, Phi~, Bn~, Bp~, Sigma_k, C_k of mpcx_covariance_thrust_batch and G~ = D G_k:
+ *   Phi8  = [[Phi~_k, G~], [0, phi]],   P8_0 = diag(P0, m_var0, sigma_b^2),
+ *   P8_k+1 = (((((Phi8 P8_k) Phi8^T + (Y + Y^T)) + (Bn~ Sigma_k) Bn~^T) + (Bp~ Sigma_k+1) Bp~^T) + q Q(h)) + (1 - phi^2) sigma_b^2 e_7 e_7^T,
+ * the thrust terms on the 7 x 7 block (the beta row of C_k is zero and is not carried), q Q(h) on the 6 x 6 block.  Sums run their
+ * index in ascending order -- the seven terms of mpcx_covariance_thrust_batch's sums first, written as its kernel writes them, the
+ * beta term last; entry (i, j) is computed as entry (min, max) and mirrored, so P is symmetric to the bit.
+ * P is the position / velocity block (m, m/s), unchanged in meaning: every consumer takes it as is.  Pm is row 6 of the 8 x 8 (its
+ * first 7 entries), as in mpcx_covariance_thrust_batch.  Pb is row 7: Cov(beta_k, position) in m, Cov(beta_k, velocity) in m/s,
+ * Cov(beta_k, mass) and Var beta_k.
+ * The zero case is mpcx_covariance_thrust_batch, to the bit: for a satellite with sigma_b = 0 row and column 7 of P8 stay exact
+ * zeros, every beta term is x * 0, and P and Pm have that call's bits under the same flags (a zero may differ in sign), per
+ * satellite inside a mixed batch; with an all-zero exec row and m_var0 = 0 as well they are mpcx_covariance_batch's.
+ * Not modelled: a density error common to both objects of a pair.  Two satellites of one shell see nearly the same density error,
+ * which largely cancels in their relative position; consumers that add P_i + P_j as independent overstate the relative covariance
+ * of such a pair.  Pb is returned so that a caller can form the cross term.
+ * status: mpcx_covariance_thrust_batch's, in its order; then a negative or non-finite sigma_b, or a tau_b that is <= 0 or NaN
+ * (+inf is valid): MPCX_ST_NUMERIC.  A failed satellite is NaN in P, Pm and Pb at all K nodes and the other satellites are
+ * untouched; otherwise the nodes past Ks[s] come back zero.  S < 1, K < 2, max_step <= 0, an unknown flag (MPCX_FLAG_DRAG_COLUMN is
+ * one here), a missing MPCX_FLAG_DRAG, MPCX_FLAG_ATMO without an atmosphere on the context, or a NULL X, U, units, span, consts, P0,
+ * dens, P or status: MPCX_E_BADARG with "covariance_drag" in the message, nothing enqueued.
+ * The _dev variant takes device pointers throughout and a workspace of mpcx_covariance_drag_workspace_bytes(S, K) bytes (the stage
+ * records, tf, the discretiser's status; 0 for S < 1 or K < 2; contents unspecified on entry and exit).
+ */
+#define MPCX_NDENS 2
+size_t mpcx_covariance_drag_workspace_bytes(int S, int K);
+int mpcx_covariance_drag_batch(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U, const double *units,
+                               const double *span, const double *consts, int flags, double max_step, const double *P0, const double *q,
+                               const double *exec, const double *m_var0, const double *dens, double *P, double *Pm, double *Pb,
+                               int32_t *status);
+int mpcx_covariance_drag_batch_dev(mpcx_ctx *ctx, int S, int K, const int32_t *Ks, const double *X, const double *U,
+                                   const double *units, const double *span, const double *consts, int flags, double max_step,
+                                   const double *P0, const double *q, const double *exec, const double *m_var0, const double *dens,
+                                   double *P, double *Pm, double *Pb, int32_t *status, void *workspace, void *stream);
 
 /*
  * mpcx_collision_probability: pairs [n][4] rows exactly as the screens write them, (i, j, distance, time in s); the distance is

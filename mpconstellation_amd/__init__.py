@@ -13,7 +13,7 @@ from .constellation_mpc import ConstellationMPC
 from .atmosphere import Atmosphere
 from . import conjunction
 from .conjunction import (common_clock, screen, screen_against, screen_pairs, screen_events, screen_track, EncounterEvents, cumulative_probability,
-                          catalogue_trajectories, ConjunctionResult, covariance, covariance_thrust, gates_execution,
+                          catalogue_trajectories, ConjunctionResult, covariance, covariance_thrust, covariance_drag, gates_execution,
                           collision_probability, catalogue_covariance, CollisionResult, collision_probability_window,
                           encounter_half_window, WindowCollisionResult, avoidance, AvoidanceResult,
                           avoidance_joint, AvoidanceJointResult, avoidance_refine, AvoidanceRefineResult,
@@ -25,7 +25,7 @@ __all__ = ["Constants", "Satellite", "SatelliteScale", "Discretizer", "Optimizer
            "Controller", "ConstantThrustController", "ConstantTangentialThrustController", "SequenceController",
            "OptimalController", "Simulator", "propagate_batch", "ConstellationMPC", "Atmosphere",
            "conjunction", "common_clock", "screen", "screen_against", "screen_pairs", "screen_events", "screen_track", "EncounterEvents",
-           "cumulative_probability", "catalogue_trajectories", "ConjunctionResult", "covariance", "covariance_thrust", "gates_execution",
+           "cumulative_probability", "catalogue_trajectories", "ConjunctionResult", "covariance", "covariance_thrust", "covariance_drag", "gates_execution",
            "collision_probability", "catalogue_covariance", "CollisionResult", "collision_probability_window", "encounter_half_window",
            "WindowCollisionResult", "avoidance", "AvoidanceResult",
            "avoidance_joint", "AvoidanceJointResult", "avoidance_refine", "AvoidanceRefineResult",

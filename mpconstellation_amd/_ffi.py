@@ -18,6 +18,7 @@ STATUS_TEXT = {
     10: "time-parallel solve: a workgroup of the satellite did not answer within the wait limit (device shared with another long kernel?)",
 }
 FLAG_DRAG, FLAG_J2, FLAG_UNIFORM_STEPS, FLAG_RK23, FLAG_PLAN_ROLLOUTS, FLAG_ATMO = 1, 2, 4, 8, 16, 32
+FLAG_DRAG_COLUMN = 64      # mpcx_discretize_stages*_dev with FLAG_DRAG: the drag column G_k in the record's Sigma slot
 NATMO = 4
 CTRL_ZERO, CTRL_CONSTANT, CTRL_TANGENTIAL, CTRL_SEQUENCE = 0, 1, 2, 3
 NCONST = 8
@@ -163,6 +164,12 @@ _SIGS = {
                                                _dp, _dp, _ip]),
     "mpcx_covariance_thrust_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the chain over eight states with an uncertain drag (after m_var0: dens; after Pm: Pb)
+    "mpcx_covariance_drag_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "mpcx_covariance_drag_batch": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp,
+                                             _dp, _dp, _dp, _dp, _ip]),
+    "mpcx_covariance_drag_batch_dev": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_double, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpcx_collision_probability": (C.c_int, [_vp, C.c_int, _dp] + [C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp] * 2 + [C.c_double, _dp, _ip]),
     "mpcx_collision_probability_dev": (C.c_int, [_vp, C.c_int, _vp] + [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp] * 2
                                        + [C.c_double, _vp, _vp, _vp]),
@@ -251,6 +258,7 @@ NMCC, NMC, NMS = 6, 9, 5                                                    # MP
 MCC_FLOWN, MCC_FAILED, MCC_START, MCC_ENTRIES, MCC_SQUARES, MCC_HIT = range(NMCC)
 MC_P_HIT, MC_SE_HIT, MC_START, MC_ENTRIES, MC_SE_BOUND, MC_EXCESS, MC_TA, MC_TB, MC_N_OK = range(NMC)
 MS_DMIN, MS_T_MIN, MS_INSIDE_START, MS_ENTRIES, MS_STATUS = range(NMS)
+NDENS = 2                                                                  # MPCX_NDENS: (sigma_b, tau_b) of mpcx_covariance_drag_batch's dens
 NEXEC = 5                                                                  # MPCX_NEXEC: (s_fm, s_pm, s_fp, s_pp, u_off) of mpcx_covariance_thrust_batch's exec
 NPC = 6                                                                     # MPCX_NPC: columns of mpcx_collision_probability's out
 PC_P, PC_MISS, PC_SPEED, PC_SIGMA1, PC_SIGMA2, PC_MAHAL = range(NPC)

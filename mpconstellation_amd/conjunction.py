@@ -17,6 +17,8 @@ satellites at once.  Here (include/mpcx.h, csrc/conjunction.hip: one screen kern
   covariance     a position / velocity covariance propagated along trajectories by the state-transition matrices of the linearisation;
   covariance_thrust   the same with the execution errors of the thrust (the Gates model; gates_execution turns newtons into its
                  figures): all seven states and both input blocks of the linearisation, for the covariance after a burn;
+  covariance_drag     covariance_thrust with an uncertain drag: a Gauss-Markov scale error on density times ballistic coefficient as
+                 an eighth state, driven by the drag column of the linearisation, for predictions over several revolutions;
   collision_probability   for every pair a screen lists, the short-encounter collision probability in the encounter plane;
   collision_probability_window   for encounters too slow for that model (neighbours in one shell, satellites deployed together):
                  the probability over a time window from the time-varying relative state and the full 6 x 6 covariances;
@@ -657,6 +659,56 @@ def _covariance_thrust_call(Y, units, span, consts, P0, U, ns, q, execution, mas
     _ffi.call("mpcx_covariance_thrust_batch", _context(device, slot, flags, atmosphere), S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
               _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr(execution),
               _ffi.dptr_opt(mass_var0), _ffi.dptr(out["P"]), _ffi.dptr_opt(out.get("Pm")), _ffi.iptr(out["status"]))
+
+
+def _check_density(density, S):
+    density = _ffi.as_f64(density)
+    if density.shape == (_ffi.NDENS,):
+        density = np.broadcast_to(density, (S, _ffi.NDENS))
+    if density.shape != (S, _ffi.NDENS):
+        raise ValueError(f"density: expected ({_ffi.NDENS},) or ({S}, {_ffi.NDENS}) rows (sigma, tau in seconds; np.inf: a bias), got {density.shape}")
+    return _ffi.as_f64(density)
+
+
+def covariance_drag(Y, units, span, consts, P0, density, U=None, execution=None, mass_var0=None, ns=None, q=None, include_J2=False,
+                    atmosphere=None, max_step=DEFAULT_MAX_STEP, device=0, devices=None, return_status=False, return_mass=False,
+                    return_density=False):
+    """covariance_thrust with an uncertain drag -> P (S, n, 6, 6), what every consumer of covariance's P takes.  The drag is always
+    in the model (include_J2 and atmosphere as in covariance).  density (2,) or (S, 2) = (sigma, tau): the drag acceleration of a
+    satellite is (1 + beta) a_D, beta -- the fractional error of density times ballistic coefficient -- a zero-mean first-order
+    Gauss-Markov process with stationary deviation sigma and correlation time tau in seconds (np.inf: a constant bias), held over
+    each node interval, independent of P0, of the thrust errors and of q.  U (S, 3, n) the thrust at the nodes (None: zero thrust),
+    execution and mass_var0 as in covariance_thrust (None: no execution error, no mass variance).  The device chains the eight
+    states (position, velocity, mass, beta) with the drag column of one linearisation (include/mpcx.h, mpcx_covariance_drag_batch).
+    A satellite with sigma = 0 gets covariance_thrust's bits, and with a zero execution row and no mass variance covariance's.
+    A failed satellite -- covariance_thrust's failures, or a negative or non-finite sigma, or a tau that is <= 0 or NaN -- is NaN
+    throughout (return_status=True appends status).  return_mass=True appends Pm (S, n, 7); return_density=True appends Pb (S, n, 8):
+    beta's covariances with position (m), velocity (m/s) and mass, and its variance.  The results come as P[, Pm][, Pb][, status].
+    Density errors common to two objects of a pair are not modelled: adding two such P as independent overstates the pair's
+    relative covariance (Pb is what a cross term would be formed from).  devices=[d0, d1, ...]: contiguous blocks of satellites on
+    several devices (sharding.sharded_call), the bits of one device."""
+    batched, out = _covariance_problem(Y, units, span, consts, P0, U, ns, q)
+    S, _, n = batched[0].shape
+    if batched[5] is None:
+        batched[5] = np.zeros((S, 3, n))
+    batched += [None if execution is None else _check_execution(execution, S),
+                None if mass_var0 is None else _per_row(mass_var0, S, "mass_var0", "values"), _check_density(density, S)]
+    if return_mass:
+        out["Pm"] = np.empty((S, n, 7))
+    if return_density:
+        out["Pb"] = np.empty((S, n, 8))
+    dispatch(_covariance_drag_call, batched, out, device, devices, **_model(True, include_J2, atmosphere, max_step))
+    res = (out["P"],) + ((out["Pm"],) if return_mass else ()) + ((out["Pb"],) if return_density else ()) + ((out["status"],) if return_status else ())
+    return res[0] if len(res) == 1 else res
+
+
+def _covariance_drag_call(Y, units, span, consts, P0, U, ns, q, execution, mass_var0, density, *, device, slot, out, flags, max_step, atmosphere):
+    """one block of satellites on context (device, slot), P, Pm, Pb and status into `out` (the block's views)"""
+    S, _, n = Y.shape
+    _ffi.call("mpcx_covariance_drag_batch", _context(device, slot, flags, atmosphere), S, n, _ffi.iptr_opt(ns), _ffi.dptr(Y), _ffi.dptr(U),
+              _ffi.dptr(units), _ffi.dptr(span), _ffi.dptr(consts), flags, max_step, _ffi.dptr(P0), _ffi.dptr_opt(q), _ffi.dptr_opt(execution),
+              _ffi.dptr_opt(mass_var0), _ffi.dptr(density), _ffi.dptr(out["P"]), _ffi.dptr_opt(out.get("Pm")), _ffi.dptr_opt(out.get("Pb")),
+              _ffi.iptr(out["status"]))
 
 
 def _check_side(Y, units, span, P, radius, ns, pre=""):

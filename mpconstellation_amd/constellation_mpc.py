@@ -325,17 +325,25 @@ class ConstellationMPC:
                for w in self._screen_windows(what, samples_per_node, T0, T1)]
         return res[0] if len(res) == 1 else cj.combine(res)
 
-    def plan_covariance(self, P0, q=None, execution=None, mass_var0=None):
+    def plan_covariance(self, P0, q=None, execution=None, mass_var0=None, density=None):
         """The covariance (S, plan_K, 6, 6) of the last plan at its nodes under the planning model's flags and atmosphere (plan_drag,
         plan_J2): conjunction.covariance along (plan X, plan U, plan_tf, plan_K) from P0 with the acceleration noise q when execution
         is None, otherwise conjunction.covariance_thrust with the thrust execution errors execution ((5,) or (S, 5):
-        conjunction.gates_execution) and the mass variance mass_var0 at the first node."""
+        conjunction.gates_execution) and the mass variance mass_var0 at the first node.  density ((2,) or (S, 2) = (sigma, tau in
+        seconds; np.inf: a bias)): conjunction.covariance_drag, the same with an uncertain drag (execution and mass_var0 optional);
+        it needs plan_drag=True -- without drag the planning model has no density to be uncertain about."""
         (w,) = self._screen_windows("plan", 1)                            # (the plan's nodes, units and span: the grid is not used)
-        return self._plan_covariance(w, P0, q, execution, mass_var0)
+        return self._plan_covariance(w, P0, q, execution, mass_var0, density)
 
-    def _plan_covariance(self, w, P0, q, execution, mass_var0):
+    def _plan_covariance(self, w, P0, q, execution, mass_var0, density=None):
         from . import conjunction as cj
         where = dict(device=self.device, devices=self.devices)
+        if density is not None:
+            if not self.plan_drag:
+                raise ValueError("density: the planning model has no drag (plan_drag=False), so there is no density to be uncertain about")
+            model = self._conjunction_model()
+            return cj.covariance_drag(w["Y"], w["units"], w["span"], self.consts, P0, density, U=self._plan[1], execution=execution,
+                                      mass_var0=mass_var0, ns=w["ns"], q=q, include_J2=model["include_J2"], atmosphere=model["atmosphere"], **where)
         if execution is None:
             if mass_var0 is not None:
                 raise ValueError("mass_var0: a mass variance needs execution (covariance carries no mass)")
@@ -392,12 +400,14 @@ class ConstellationMPC:
         screen = cj.screen if trajectories is None else cj.screen_against
         return w, screen(threshold=threshold_m, **_catalogue_keywords(trajectories), **where, **w, **kw), where
 
-    def _plan_probabilities(self, threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution=None, mass_var0=None):
+    def _plan_probabilities(self, threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution=None, mass_var0=None, density=None):
         """what the probabilities and the window manoeuvres start from: the plan screened at threshold_m (against catalogue = (Y, units,
         span, P, radius[, ns]) if given) and its covariance -> (w, screened, P, the keywords ns, cat, device and devices)"""
+        if density is not None and not self.plan_drag:                   # (refused before anything is screened)
+            raise ValueError("density: the planning model has no drag (plan_drag=False), so there is no density to be uncertain about")
         cat, trajectories = self._catalogue_with_radii(catalogue)
         w, screened, where = self._screen_plan(threshold_m, samples_per_node, max_pairs, trajectories)
-        return w, screened, self._plan_covariance(w, P0, q, execution, mass_var0), dict(ns=w["ns"], cat=cat, **where)
+        return w, screened, self._plan_covariance(w, P0, q, execution, mass_var0, density), dict(ns=w["ns"], cat=cat, **where)
 
     @staticmethod
     def _window_choice(half_window, max_half, nsigma):
@@ -431,27 +441,28 @@ class ConstellationMPC:
         return chosen.half, (chosen,)
 
     def collision_probability(self, threshold_m, P0, radius_m, q=None, samples_per_node=4, max_pairs=None, catalogue=None, execution=None,
-                              mass_var0=None):
+                              mass_var0=None, density=None):
         """Collision probabilities of the last plan's close approaches -> (ConjunctionResult, CollisionResult).  The plan is screened
         at threshold_m (screen(what='plan'); screen_against when catalogue = (Y, units, span, P, radius) or (Y, units, span, P,
         radius, ns) is given: the objects' trajectories, their covariances -- conjunction.catalogue_covariance -- and hard-body
         radii); P0 ((6, 6) or (S, 6, 6); m, m/s), the covariance of every satellite at the plan's first node, is propagated along
         (plan X, plan U, plan_tf, plan_K) under the planning model's flags and atmosphere (plan_drag, plan_J2) with the acceleration
         noise q (plan_covariance: conjunction.covariance, or with execution / mass_var0 conjunction.covariance_thrust, the covariance
-        with thrust execution errors), and every listed pair gets its probability (conjunction.collision_probability; radius_m a
-        scalar or (S,)).  The plan only: a linearisation needs the thrust a trajectory was flown with, and ConstellationMPC does not
-        keep the thrust of its flown segments."""
+        with thrust execution errors, or with density conjunction.covariance_drag, the covariance with an uncertain drag), and
+        every listed pair gets its probability (conjunction.collision_probability; radius_m a scalar or (S,)).  The plan only: a
+        linearisation needs the thrust a trajectory was flown with, and ConstellationMPC does not keep the thrust of its flown
+        segments."""
         from . import conjunction as cj
-        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0, density)
         return screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan)
 
     def collision_probability_window(self, threshold_m, P0, radius_m, half_window, panels=4, q=None, samples_per_node=4, max_pairs=None,
-                                     catalogue=None, execution=None, mass_var0=None, *, max_half=None, nsigma=8):
+                                     catalogue=None, execution=None, mass_var0=None, *, max_half=None, nsigma=8, density=None):
         """collision_probability and the window probability of the same rows -> (ConjunctionResult, CollisionResult,
-        WindowCollisionResult).  The screening arguments, P0, radius_m, q and catalogue are collision_probability's, and the first two
-        results are what it returns; every listed pair also gets its probability over [t - half_window, t + half_window]
-        (conjunction.collision_probability_window on the same plan, covariances and radii; half_window a scalar or one per listed
-        pair, in seconds; panels as there).  For the pairs of a constellation that pass each other slowly the short-encounter figure
+        WindowCollisionResult).  The screening arguments, P0, radius_m, q, catalogue, execution, mass_var0 and density are
+        collision_probability's, and the first two results are what it returns; every listed pair also gets its probability over
+        [t - half_window, t + half_window] (conjunction.collision_probability_window on the same plan, covariances and radii;
+        half_window a scalar or one per listed pair, in seconds; panels as there).  For the pairs of a constellation that pass each other slowly the short-encounter figure
         is outside its model, and without relative speed it fails: the window figure is the one to read there.  half_window='auto':
         every listed pair's window is chosen on the device (conjunction.encounter_window on the same rows, plan, covariances and radii,
         searching max_half seconds to either side -- a scalar or one per listed pair; None: half the plan's common span -- for the
@@ -459,7 +470,7 @@ class ConstellationMPC:
         EncounterWindowResult is returned as a fourth element.  The plan only."""
         from . import conjunction as cj
         auto = self._window_choice(half_window, max_half, nsigma)
-        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0)
+        w, screened, P, plan = self._plan_probabilities(threshold_m, P0, q, samples_per_node, max_pairs, catalogue, execution, mass_var0, density)
         half_window, chosen = self._chosen_window(auto, half_window, max_half, nsigma, w, screened, radius_m, P, plan)
         return (screened, cj.collision_probability(screened, radius_m, w["Y"], w["units"], w["span"], P, **plan),
                 cj.collision_probability_window(screened, radius_m, w["Y"], w["units"], w["span"], P, half_window, panels=panels, **plan)) + chosen

@@ -29,11 +29,12 @@ __global__ __launch_bounds__(256) void enc_tf_kernel(int S, const double *units,
     tf[s] = tr_tf(span[2 * s], span[2 * s + 1], units[2 * s + 1], v) ? v : 1.0;
 }
 
-int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream)
+int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream, bool drag_column)
 {
+    const int flags = p.flags | (drag_column ? MPCX_FLAG_DRAG_COLUMN : 0);
     hipLaunchKernelGGL(enc_tf_kernel, dim3((unsigned)((p.S + 255) / 256)), dim3(256), 0, stream, p.S, p.units, p.span, ws.tf);
     MPCX_HIP(ctx, hipGetLastError());
-    return mpcx_discretize_stages_ragged_dev(ctx, p.S, p.K, p.Ks, p.K, p.Ks, p.Y, p.U, ws.tf, p.consts, p.flags, p.max_step, ws.stage, ws.dstat,
+    return mpcx_discretize_stages_ragged_dev(ctx, p.S, p.K, p.Ks, p.K, p.Ks, p.Y, p.U, ws.tf, p.consts, flags, p.max_step, ws.stage, ws.dstat,
                                              stream);
 }
 

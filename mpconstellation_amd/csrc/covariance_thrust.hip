@@ -10,7 +10,8 @@
 // The operation order is fixed (tests/covariance_thrust_reference.py restates it); LDS is ten small matrices whatever K.  The 6-term
 // prefix of every sum over the state is written as covariance_kernel (collision.hip) writes it: with an all-zero exec row and no
 // mass variance every further term is an exact zero and P has mpcx_covariance_batch's bits, satellite by satellite in a mixed batch.
-// The status, the fills, q Q(h), the 6 x 6 block's scaling and the exec row are covariance_device.hpp's, shared with that kernel.
+// The status, the fills, q Q(h), the 6 x 6 block's scaling and the exec row are covariance_device.hpp's, shared with that kernel;
+// Sigma's column (ct_sigma_column) is there too, shared with covariance_drag_kernel.
 // No atomics, nothing crosses a workgroup.  The linearisation is enc_linearise (encounter_host.hpp), as everywhere.
 #include "collision_device.hpp"
 #include "covariance_device.hpp"
@@ -30,26 +31,6 @@ struct CtArgs {
 };
 
 enum { CT_N = 7, CT_NN = 49, CT_NB = 21, CT_BN = 49, CT_BP = 70 };     // CT_BN, CT_BP: where B_kn and B_kp start in a record
-
-// Column c of Sigma of node k of the thrust table u (rows K apart).  Zero when the engine is off (|u| <= u_off; a |u| that is not a
-// number counts as off).  Wave-uniform but for the choice of the column.
-__device__ __forceinline__ void ct_sigma_column(const double *u, size_t K, int k, const GatesRow &ex, int c, double &c0, double &c1, double &c2)
-{
-    const double ux = u[k], uy = u[K + k], uz = u[2 * K + k];
-    const double un = sqrt(ux * ux + uy * uy + uz * uz);
-    c0 = 0.0; c1 = 0.0; c2 = 0.0;
-    if (!gates_on(ex, un)) return;
-    const double hx = ux / un, hy = uy / un, hz = uz / un;
-    double sp, sq;
-    gates_variances(ex, un, sp, sq);
-    const double xx = hx * hx, xy = hx * hy, xz = hx * hz, yy = hy * hy, yz = hy * hz, zz = hz * hz;
-    const double sxx = sp * xx + sq * (1.0 - xx), sxy = sp * xy - sq * xy, sxz = sp * xz - sq * xz;
-    const double syy = sp * yy + sq * (1.0 - yy), syz = sp * yz - sq * yz;
-    const double szz = sp * zz + sq * (1.0 - zz);
-    c0 = c == 0 ? sxx : (c == 1 ? sxy : sxz);
-    c1 = c == 0 ? sxy : (c == 1 ? syy : syz);
-    c2 = c == 0 ? sxz : (c == 1 ? syz : szz);
-}
 
 __global__ __launch_bounds__(64) void covariance_thrust_kernel(CtArgs a)
 {

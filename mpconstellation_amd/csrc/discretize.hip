@@ -287,7 +287,10 @@ __device__ __forceinline__ bool lu_solve_cols(double (&col)[6], double (&b)[6])
 // Quadrature integrand column of this lane at an accepted node (linearize_discretize.py:60-75):
 // g = Phi(t)^-1 [B lam-, B lam+, Sigma, xi][:, c]
 // (T, L, D: the time and state parts at (t, y) -- evaluated by node_integrand, or the last stage's where it was this very point)
-template <bool DRAG, bool ATMO>
+// DCOL (MPCX_FLAG_DRAG_COLUMN): the Sigma lane integrates the drag column tf [0; a_D; 0] in Sigma's place -- a_D the drag that lin_eval
+// adds to L.acc, as tf a_D = D.kvt v: drag_lin's |v| is vv rsq(vv) where lin_eval's is sqrt(vv), the same to rounding, not to the bit --
+// so that the record's Sigma slot holds G_k = d x_k+1 / d beta for a scale (1 + beta) on the drag.
+template <bool DRAG, bool ATMO, bool DCOL = false>
 __device__ __forceinline__ void node_columns(RhsCtx &p, const double (&y)[7], const TimePart &T, const Lin &L, const DragLin &D,
                                              double t, double tau_k, double tau_kp1,
                                              double (&g)[7], int &err)
@@ -327,7 +330,13 @@ __device__ __forceinline__ void node_columns(RhsCtx &p, const double (&y)[7], co
         bu6 += nou ? 0.0 : (b6s * u[i]) * u[i];
     }
     xi[6] = -(0.0 + bu6);
-    const double sg[7] = {x[3], x[4], x[5], L.acc[0], L.acc[1], L.acc[2], T.mdot};      // Sigma = f(.; tf = 1)
+    double sg[7] = {x[3], x[4], x[5], L.acc[0], L.acc[1], L.acc[2], T.mdot};            // Sigma = f(.; tf = 1)
+    if constexpr (DCOL) {
+        static_assert(DRAG, "the drag column is the drag's");
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { sg[i] = 0.0; sg[3 + i] = D.kvt * v[i]; }
+        sg[6] = 0.0;
+    }
 
     double R[7];
 #pragma unroll
@@ -348,7 +357,7 @@ __device__ __forceinline__ void node_columns(RhsCtx &p, const double (&y)[7], co
     for (int i = 0; i < 6; ++i) g[i] = b[i];
     g[6] = R[6];
 }
-template <bool DRAG, bool ATMO>
+template <bool DRAG, bool ATMO, bool DCOL = false>
 __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
                                                double t, double tau_k, double tau_kp1,
                                                double (&g)[7], int &err)
@@ -360,7 +369,7 @@ __device__ __forceinline__ void node_integrand(RhsCtx &p, const double (&y)[7],
     Lin L;
     DragLin D;
     state_eval<DRAG, ATMO>(p, r, v, m, T, L, D);
-    node_columns<DRAG, ATMO>(p, y, T, L, D, t, tau_k, tau_kp1, g, err);
+    node_columns<DRAG, ATMO, DCOL>(p, y, T, L, D, t, tau_k, tau_kp1, g, err);
 }
 
 // One component's quotient of scipy's error norm (rk.py:97-99, 139-141): e h / (atol + max(|y|, |y_new|) rtol), e the
@@ -387,13 +396,17 @@ __device__ __forceinline__ void trapz_commit(double d, double g, double &gprev, 
 // in Phi's Jacobian and in xi (drag_lin / drag_dv); separate instantiations, the drag-free ones are untouched.
 // ATMO: MPCX_FLAG_ATMO on top of DRAG -- the altitude-dependent density (atmo_density) in every right-hand side, Sigma and xi, and
 // the position block Dr a_D in the Jacobian; a third set of instantiations, the other two are untouched.
-template <int LAYOUT, bool UNIFORM, int METHOD = 45, bool DRAG = false, bool ATMO = false>
+// DCOL: MPCX_FLAG_DRAG_COLUMN on top of DRAG, stage layout and adaptive RK45 only -- the drag column G_k in the record's Sigma slot
+// (node_columns); the same steps (the error norm runs over the 56 ODE components), the same A, B_kn, B_kp and xi to the bit; two
+// more instantiations (fixed density, ATMO), the others are untouched.
+template <int LAYOUT, bool UNIFORM, int METHOD = 45, bool DRAG = false, bool ATMO = false, bool DCOL = false>
 #ifndef MPCX_DISC_WAVES
 #define MPCX_DISC_WAVES 1      // waves per SIMD the register allocation is bounded for (360 registers at 1)
 #endif
 __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArgs a)
 {
     static_assert(DRAG || !ATMO, "the atmosphere is a property of the drag");
+    static_assert(!DCOL || (DRAG && LAYOUT == LAYOUT_STAGE && !UNIFORM && METHOD == 45), "the drag column: stage records of the adaptive RK45 drag forms");
     __shared__ double lds[8 * kRec];
     const int lane = threadIdx.x;
     const int grp = lane >> 3, c = lane & 7;
@@ -474,7 +487,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
     double acc[7], gprev[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) acc[i] = 0.0;
-    node_integrand<DRAG, ATMO>(p, y, t, tau_k, tau_kp1, gprev, err);
+    node_integrand<DRAG, ATMO, DCOL>(p, y, t, tau_k, tau_kp1, gprev, err);
 
     // uniform mode: index of the next evaluation point, time of the previous one, the interpolated state at it
     const double ustep = UNIFORM ? (tau_kp1 - tau_k) / (double)(n_uni - 1) : 0.0;   // np.linspace(tau_k, tau_kp1, n)
@@ -618,7 +631,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                         const double accq = rk_dense_at<METHOD>(Q[i], xx);
                         yd[i] = has ? h * accq + yold[i] : y[i];
                     }
-                    node_integrand<DRAG, ATMO>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
+                    node_integrand<DRAG, ATMO, DCOL>(p, yd, has ? te : t, tau_k, tau_kp1, g, err);
                     if (has) {
                         const double d = te - te_prev;
 #pragma unroll
@@ -648,7 +661,7 @@ __global__ __launch_bounds__(64, MPCX_DISC_WAVES) void discretize_kernel(DiscArg
                 x_column<true>(y, r, v, m);
                 state_eval<DRAG, ATMO>(p, r, v, m, T6, L6, D6);
             }
-            node_columns<DRAG, ATMO>(p, y, T6, L6, D6, t, tau_k, tau_kp1, g, err);
+            node_columns<DRAG, ATMO, DCOL>(p, y, T6, L6, D6, t, tau_k, tau_kp1, g, err);
             if (accept) {
 #pragma unroll
                 for (int i = 0; i < 7; ++i) trapz_commit(h, g[i], gprev[i], acc[i]);      // ts[i+1] - ts[i] = h
@@ -725,6 +738,10 @@ static int launch_discretize(mpcx_ctx *ctx, int layout, DiscArgs a, hipStream_t 
     if (a.S < 1 || a.K < 2 || a.Ku < 2) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: need S>=1, K>=2, Ku>=2");
     if (!(a.max_step > 0.0)) return ctx_fail(ctx, MPCX_E_BADARG, "discretize: max_step must be > 0");
     if (int rc = ctx_atmosphere(ctx, a.flags, a.atmo, "discretize")) return rc;
+    // the drag column: honoured by the stage records alone (the reference layout has no use for it and masks the bit as ever)
+    const bool dcol = layout == LAYOUT_STAGE && (a.flags & MPCX_FLAG_DRAG_COLUMN) != 0;
+    if (dcol && (!(a.flags & MPCX_FLAG_DRAG) || (a.flags & (MPCX_FLAG_UNIFORM_STEPS | MPCX_FLAG_RK23))))
+        return ctx_fail(ctx, MPCX_E_BADARG, "discretize: MPCX_FLAG_DRAG_COLUMN needs MPCX_FLAG_DRAG and the adaptive RK45 steps (no MPCX_FLAG_UNIFORM_STEPS, no MPCX_FLAG_RK23)");
     MPCX_HIP(ctx, hipSetDevice(ctx->device));
     MPCX_HIP(ctx, hipMemsetAsync(a.status, 0, sizeof(int32_t) * a.S, st));
     const long total = (long)a.S * (a.K - 1);
@@ -743,7 +760,10 @@ static int launch_discretize(mpcx_ctx *ctx, int layout, DiscArgs a, hipStream_t 
     if (layout == LAYOUT_STAGE) {
         if (rk23) { if (uni) MPCX_DISC_LAUNCH(LAYOUT_STAGE, true, 23); else MPCX_DISC_LAUNCH(LAYOUT_STAGE, false, 23); }
         else if (uni) MPCX_DISC_LAUNCH(LAYOUT_STAGE, true, 45);
-        else MPCX_DISC_LAUNCH(LAYOUT_STAGE, false, 45);
+        else if (dcol) {
+            if (atmo) hipLaunchKernelGGL((discretize_kernel<LAYOUT_STAGE, false, 45, true, true, true>), dim3(blocks), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL((discretize_kernel<LAYOUT_STAGE, false, 45, true, false, true>), dim3(blocks), dim3(64), 0, st, a);
+        } else MPCX_DISC_LAUNCH(LAYOUT_STAGE, false, 45);
     } else {
         if (rk23) { if (uni) MPCX_DISC_LAUNCH(LAYOUT_REF, true, 23); else MPCX_DISC_LAUNCH(LAYOUT_REF, false, 23); }
         else if (uni) MPCX_DISC_LAUNCH(LAYOUT_REF, true, 45);

@@ -197,7 +197,7 @@ struct LinOnlyWorkspace : LinWorkspace {
     }
 };
 
-// the argument tests of both covariance chains (`name`: covariance or covariance_thrust)
+// the argument tests of the covariance chains (`name`: covariance, covariance_thrust or covariance_drag)
 inline int cov_check(mpcx_ctx *ctx, const char *name, int S, int K, int flags, double max_step)
 {
     if (S < 1 || K < 2) return enc_fail(ctx, name, "need S>=1, K>=2");
@@ -209,8 +209,10 @@ inline int cov_check(mpcx_ctx *ctx, const char *name, int S, int K, int flags, d
 // The linearisation about (p.Y, p.U) under p.flags, p.max_step: tf [S], the span in each satellite's own time unit (1 where that is
 // not positive and finite: the discretiser's step-size control never sees a value it was not written for, and the kernels that read
 // the records make the same test and give that satellite MPCX_ST_BADK), then the stage records and the discretiser's status.
-// Reads S, K, Ks, Y, U, units, span, consts, flags, max_step of p.  (collision.hip)
-int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream);
+// Reads S, K, Ks, Y, U, units, span, consts, flags, max_step of p.  drag_column: the records carry the drag column G_k in their
+// Sigma slot (MPCX_FLAG_DRAG_COLUMN; p.flags must contain MPCX_FLAG_DRAG) -- asked for here, not in p.flags, whose validation
+// stays what it is.  (collision.hip)
+int enc_linearise(mpcx_ctx *ctx, const EncProblem &p, const LinWorkspace &ws, hipStream_t stream, bool drag_column = false);
 
 // mpcx_collision_window_sensitivity* as its entry points take it, and as mpcx_avoidance_window* (avoidance_window.hip) runs it
 // first: the problem (its `target` is not read), the window call's own arguments, who moves, the outputs

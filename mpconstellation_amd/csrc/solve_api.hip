@@ -311,7 +311,8 @@ static int mpc_step_ragged(mpcx_ctx *ctx, const SolvePlace &at, int S, int K, co
     double *stage = (double *)workspace, *sws = stage + lay.solver_at;
     int32_t *dstat = (int32_t *)(stage + lay.status_at);
     // (a ragged batch's thrust tables have as many columns as the satellite has nodes)
-    int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, xbar, ubar, tf, consts, flags, max_step, stage, dstat, st);
+    // (the solver reads Sigma: the stage calls' drag-column bit is masked here, as the discretiser always masked it)
+    int rc = mpcx_discretize_stages_ragged_dev(ctx, S, K, Ks, K, Ks, xbar, ubar, tf, consts, flags & ~MPCX_FLAG_DRAG_COLUMN, max_step, stage, dstat, st);
     if (rc) return rc;
     rc = solve_ragged(ctx, at, S, K, Ks, stage, xbar, ubar, tf, consts, r_des, opts, popts, X, U, NU, tf_out, status, iters, kkt, sws, st);
     if (rc) return rc;
