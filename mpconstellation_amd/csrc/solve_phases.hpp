@@ -131,6 +131,14 @@ __device__ __forceinline__ double uni(double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// Lane l's value of v (l a constant after unrolling, all 64 lanes active), in scalar registers: two v_readlane for a double.
+__device__ __forceinline__ double lane_value(double v, int l)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // c~ = |v|^2 - (r.v)^2/|r|^2 - vt_des^2 (same zero set as the quartic of optimizer.py:492-517)
 __device__ void vt_reduced(const double *x, double vt_des, double &c, double *g6, double *H36)
 {
@@ -161,7 +169,7 @@ __device__ void vt_reduced(const double *x, double vt_des, double &c, double *g6
 
 // Optimizer.get_constraint_terms (optimizer.py:80-170) for the terminal node, incl. the
 // operator-precedence form of Dv_h_hat (:122); builds the six terminal linear inequalities.
-__device__ __noinline__ void build_terminal(const double *xK, double mu_grav, double r_des, const SolveOpts &o, SatData &sd)
+__device__ __forceinline__ void build_terminal(const double *xK, double mu_grav, double r_des, const SolveOpts &o, SatData &sd)
 {
     double r[3] = {xK[0], xK[1], xK[2]}, v[3] = {xK[3], xK[4], xK[5]}, h[3], rh[3], hh[3];
     const double rn = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
@@ -248,8 +256,8 @@ __device__ __noinline__ void build_terminal(const double *xK, double mu_grav, do
 // build_terminal for satellite `sat` of a launch with per-satellite problem options: a local copy of the launch's options --
 // solver controls and flags as they are -- takes the eleven problem options from the satellite's row of the table (SolveArgs::popts,
 // [S][MPCX_NPOPT] in the order of mpcx_solve_opts' first eleven doubles, indexed by SATELLITE), and build_terminal gets the copy.
-// popts == nullptr: the launch's options for everybody.  Out of line, like build_terminal: the copy lives in this function's frame,
-// not in the driver's.
+// popts == nullptr: the launch's options for everybody.  Out of line, with build_terminal inlined into it: the copy is then a set
+// of registers (as the argument of a second out-of-line function it was a stack object of this one, 16 scratch stores per call).
 __device__ __noinline__ void build_terminal_sat(const double *xK, double mu_grav, double r_des, const SolveOpts &o, const double *popts, int sat, SatData &sd)
 {
     SolveOpts os = o;
@@ -1136,7 +1144,6 @@ __device__ __noinline__ void reduced_residual(const Sat &s, SatData &sd, int lan
     double *const stg = stage_area();
     double rvt_rhs, gex[NTERM];      // (-> sd.rs_rvt, sd.rs_gex at the end; sd.rs_gtf)
     const int K = s.K;
-    double gtf_part = 0.0;
     const double dtf = s.drg[G_TF];
     // terminal-node completion terms (the rank-1 terms and the AL shift): from the direction at node K-1, known up front
     double gin[NTERM], rvt_x;
@@ -1168,205 +1175,240 @@ __device__ __noinline__ void reduced_residual(const Sat &s, SatData &sd, int lan
             gex[t] = on ? (adx - sd.zeta[t] / wex + sd.tgh[t] / sd.tw[t]) * wex : 0.0;
         }
     }
-    for (int k0 = 0; k0 < K; k0 += 64) {
-      const int k = k0 + lane;
-      double *rec = stg + lane * RHS_LD;
+    // Two lanes per node, passes of 32 nodes (NODE_OF / HALF_OF).  The record's rows are split so that no sum is shared: half 0
+    // forms the gradient rows R_GX, R_GU, half 1 the rows R_RHO, R_AFF and the node's Sigma . lt.  One lane per node held the
+    // ~230 loaded values of a node and spilled 112 registers; a half holds about half of them.  Both halves run ONE product with
+    // A -- half 0 the column sums A^T lt, half 1 the row sums A (-dx) on top of its row's start value: the same loads and
+    // multiply-adds, half 1 reading A transposed (a field offset per lane; fma(a, -b, c) is fma(-a, b, c) bit for bit, so
+    // `acc -= A[i][j] * dx[j]` keeps its value) -- and what only one half needs sits in branches on the half.
+    // Loads in batches as before (round 5): a batch's loads go out together, from clamped (always valid) addresses, and are
+    // selected afterwards; every sum in its old order.
+    const int half = HALF_OF(lane), kl = NODE_OF(lane);
+    const bool h0 = (half == 0);
+    double gtf_even = 0.0, gtf_odd = 0.0;      // half 1: the Sigma . lt sums of this lane's nodes of the even and of the odd passes
+    for (int k0 = 0; k0 < K; k0 += 32) {
+      const int k = k0 + kl;
+      double *rec = stg + kl * RHS_LD;
       if (k < K) {
-        // Four batches of loads per node (round 5): the node's ~230 loads were issued one at a time, each waited for before the
-        // next (the function holds its 248 registers' worth of live values and the scheduler sank every load to its use): ~150
-        // dependent memory round trips per call -- the refinement passes of the stiff-window solves waited here longer than a
-        // factorisation takes.  Loads from clamped (always valid) addresses, selected afterwards; every sum in its old order.
-        cwf64 *nb = s.nb + (size_t)k * NB_N;
-        const auto ns = s.nsn(k);
         const auto p = s.itn(k), d = s.drn(k);
         const bool hp = (k >= 1), dyn = (k <= K - 2), term = (k == K - 1);
         const auto pm = p.node(hp ? -1 : 0), dm = d.node(hp ? -1 : 0), dn = d.node(dyn ? 1 : 0);
-        // ---- batch 1: multipliers of rows k and k-1 ----
-        double lt[7], ltm[7];
+        // ---- batch 1: multipliers of row k; half 0: those of row k-1; half 1: the next node's dx, the node's dnu ----
+        double lt[7];
+        double q0[7], q1[7];      // half 0: ltm (q0); half 1: dnx (q0), dnu (q1)
+        {
+            double a0[7], a1[7], b0[7], b1[7];
 #pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const double a0 = p[I_LAM + i], a1 = d[I_LAM + i], b0 = pm[I_LAM + i], b1 = dm[I_LAM + i];
-            lt[i] = dyn ? a0 + a1 : 0.0;        // total multipliers lam + dlam of rows k and k-1
-            ltm[i] = hp ? b0 + b1 : 0.0;
+            for (int i = 0; i < 7; ++i) { a0[i] = p[I_LAM + i]; a1[i] = d[I_LAM + i]; }
+            if (h0) {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) { b0[i] = pm[I_LAM + i]; b1[i] = dm[I_LAM + i]; }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) { b0[i] = dn[I_X + i]; b1[i] = d[I_NU + i]; }
+            }
+            CHUNK_END
+#pragma unroll
+            for (int i = 0; i < 7; ++i) {
+                lt[i] = dyn ? a0[i] + a1[i] : 0.0;        // total multipliers lam + dlam of rows k and k-1
+                const double ltm = hp ? b0[i] + b1[i] : 0.0;
+                q0[i] = h0 ? ltm : b0[i]; q1[i] = b1[i];
+            }
         }
-        CHUNK_END
-        // ---- batch 2: the node's direction, Newton scalars and record ----
-        double dx[7], du[3], dnu[7], nsgx[7], nsgu[3], w3[9], wu[9], sx[SX_N];
+        // ---- batch 2: the node's direction; half 0: Newton scalars and record; half 1: Sigma, the next node's du, rho, D ----
+        double dx[7], du[3];
+        double gx[7], gu[3];      // half 0
+        double out[7], vec[7];    // the product with A: half 0 atl = A^T lt; half 1 aff = dn_x - Sigma dtf - dnu - A dx (- Bn du - Bp dn_u below)
+        double dnuu[3];           // half 1
 #pragma unroll
-        for (int i = 0; i < 7; ++i) { dx[i] = d[I_X + i]; dnu[i] = d[I_NU + i]; nsgx[i] = ns[NS_GX + i]; }
+        for (int i = 0; i < 7; ++i) dx[i] = d[I_X + i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { du[i] = d[I_U + i]; nsgu[i] = ns[NS_GU + i]; }
+        for (int i = 0; i < 3; ++i) du[i] = d[I_U + i];
+        if (h0) {
+            cwf64 *nb = s.nb + (size_t)k * NB_N;
+            const auto ns = s.nsn(k);
+            double nsgx[7], nsgu[3], w3[9], wu[9], sx[SX_N];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) { w3[i] = nb[N_W3 + i]; wu[i] = nb[N_WU + i]; }
+            for (int i = 0; i < 7; ++i) nsgx[i] = ns[NS_GX + i];
 #pragma unroll
-        for (int i = 0; i < SX_N; ++i) sx[i] = nb[N_SX + i];
-        const double dg = nb[N_DIAG];
-        CHUNK_END
-        double gx[7], gu[3];
-        if (hp) {
-            if (term) {
+            for (int i = 0; i < 3; ++i) nsgu[i] = ns[NS_GU + i];
 #pragma unroll
-                for (int i = 0; i < 7; ++i) {
-                    double acc = sd.gxKsoft[i] + ltm[i];
+            for (int i = 0; i < 9; ++i) { w3[i] = nb[N_W3 + i]; wu[i] = nb[N_WU + i]; }
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) acc += sd.WxKsoft[i * 7 + j] * dx[j];
-                    gx[i] = acc;
+            for (int i = 0; i < SX_N; ++i) sx[i] = nb[N_SX + i];
+            const double dg = nb[N_DIAG];
+            CHUNK_END
+            const double *ltm = q0;
+            if (hp) {
+                if (term) {
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) {
+                        double acc = sd.gxKsoft[i] + ltm[i];
+#pragma unroll
+                        for (int j = 0; j < 7; ++j) acc += sd.WxKsoft[i * 7 + j] * dx[j];
+                        gx[i] = acc;
+                    }
+                } else {
+                    // stage Hessian in its compact form: the 3x3 position block, the common diagonal value elsewhere (the
+                    // entries left out are exact zeros: same sums as with the full matrix)
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) {
+                        double acc = nsgx[i] + ltm[i];
+                        if (i < 3) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) acc += w3[i * 3 + j] * dx[j];
+                        } else acc += dg * dx[i];
+                        gx[i] = acc;
+                    }
+                }
+                if (term) {
+                    const double lvt = s.itg[G_LVT] + s.drg[G_LVT];
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) gx[i] += sd.avt[i] * lvt;
                 }
             } else {
-                // stage Hessian in its compact form: the 3x3 position block, the common diagonal value elsewhere (the
-                // entries left out are exact zeros: same sums as with the full matrix)
 #pragma unroll
-                for (int i = 0; i < 7; ++i) {
-                    double acc = nsgx[i] + ltm[i];
-                    if (i < 3) {
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) acc += w3[i * 3 + j] * dx[j];
-                    } else acc += dg * dx[i];
-                    gx[i] = acc;
-                }
+                for (int i = 0; i < 7; ++i) gx[i] = 0.0;
             }
-            if (term) {
-                const double lvt = s.itg[G_LVT] + s.drg[G_LVT];
 #pragma unroll
-                for (int i = 0; i < 7; ++i) gx[i] += sd.avt[i] * lvt;
+            for (int i = 0; i < 3; ++i) {
+                double acc = nsgu[i];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) acc += wu[i * 3 + j] * du[j];
+                gu[i] = acc;
             }
+            {
+                // the stiff stage terms' excess weight, which the blocks N_W3 / N_WU do not carry (newton_blocks)
+                const double ex_x = sx[SX_EX], ex_u = sx[SX_EU];
+                const double a0 = sx[SX_A], a1 = sx[SX_A + 1], a2 = sx[SX_A + 2];
+                const double c0 = sx[SX_CU], c1 = sx[SX_CU + 1], c2 = sx[SX_CU + 2];
+                const double px = ex_x * (a0 * dx[0] + a1 * dx[1] + a2 * dx[2]);
+                const double pu = ex_u * (c0 * du[0] + c1 * du[1] + c2 * du[2]);
+                if (hp && dyn) { gx[0] += px * a0; gx[1] += px * a1; gx[2] += px * a2; }
+                gu[0] += pu * c0; gu[1] += pu * c1; gu[2] += pu * c2;
+            }
+#pragma unroll
+            for (int i = 0; i < 7; ++i) { out[i] = 0.0; vec[i] = lt[i]; }
         } else {
+            const auto ns = s.nsn(k);
+            const auto Sg = s.Sigt(dyn ? k : 0);
+            double sg[7], rho[7], dd[7];
 #pragma unroll
-            for (int i = 0; i < 7; ++i) gx[i] = 0.0;
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            double acc = nsgu[i];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc += wu[i * 3 + j] * du[j];
-            gu[i] = acc;
-        }
-        {
-            // the stiff stage terms' excess weight, which the blocks N_W3 / N_WU do not carry (newton_blocks)
-            const double ex_x = sx[SX_EX], ex_u = sx[SX_EU];
-            const double a0 = sx[SX_A], a1 = sx[SX_A + 1], a2 = sx[SX_A + 2];
-            const double c0 = sx[SX_CU], c1 = sx[SX_CU + 1], c2 = sx[SX_CU + 2];
-            const double px = ex_x * (a0 * dx[0] + a1 * dx[1] + a2 * dx[2]);
-            const double pu = ex_u * (c0 * du[0] + c1 * du[1] + c2 * du[2]);
-            if (hp && dyn) { gx[0] += px * a0; gx[1] += px * a1; gx[2] += px * a2; }
-            gu[0] += pu * c0; gu[1] += pu * c1; gu[2] += pu * c2;
-        }
-        // ---- batch 3: B_kp of the interval before, Sigma, the next node's direction ----
-        double sg[7], dnx[7], dnuu[3];
-        {
-            double bm[21];
-            const auto Bm = s.Bpt(hp ? k - 1 : 0), Sg = s.Sigt(dyn ? k : 0);
-#pragma unroll
-            for (int e = 0; e < 21; ++e) bm[e] = Bm[e];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) { sg[i] = Sg[i]; dnx[i] = dn[I_X + i]; }
+            for (int i = 0; i < 7; ++i) { sg[i] = Sg[i]; rho[i] = ns[NS_RHO + i]; dd[i] = ns[NS_D + i]; }
 #pragma unroll
             for (int i = 0; i < 3; ++i) dnuu[i] = dn[I_U + i];
             CHUNK_END
-            if (hp) {
+            const double *dnx = q0, *dnu = q1;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) acc += bm[i * 3 + j] * ltm[i];
-                    gu[j] -= acc;
-                }
-            }
-        }
-        // ---- batches 4, 5: A in two halves of rows (the column sums A^T lt run over the rows in order, across the halves) ----
-        double aff[7], atl[7];      // aff: dn_x - Sigma dtf - dnu - A dx (- Bn du - Bp dn_u below); atl: A^T lt
-#pragma unroll
-        for (int j = 0; j < 7; ++j) atl[j] = 0.0;
-        {
-            const auto A = s.At(dyn ? k : 0);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int r0 = h ? 4 : 0, r1 = h ? 7 : 4;
-                double am[28];
-#pragma unroll
-                for (int i = r0; i < r1; ++i)
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) am[(i - r0) * 7 + j] = A[i * 7 + j];
-                CHUNK_END
-#pragma unroll
-                for (int i = r0; i < r1; ++i) {
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) atl[j] += am[(i - r0) * 7 + j] * lt[i];
-                    double acc = dnx[i] - sg[i] * dtf - dnu[i];
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) acc -= am[(i - r0) * 7 + j] * dx[j];
-                    aff[i] = acc;
-                }
-            }
-        }
-        if (dyn && hp) {
-#pragma unroll
-            for (int j = 0; j < 7; ++j) gx[j] -= atl[j];
-        }
-        // ---- batch 6: B_kn, B_kp of this interval ----
-        {
-            double bn[21], bp[21];
-            const auto Bn = s.Bnt(dyn ? k : 0), Bp = s.Bpt(dyn ? k : 0);
-#pragma unroll
-            for (int e = 0; e < 21; ++e) { bn[e] = Bn[e]; bp[e] = Bp[e]; }
-            CHUNK_END
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double acc = 0.0;
-#pragma unroll
-                for (int i = 0; i < 7; ++i) acc += bn[i * 3 + j] * lt[i];
-                if (dyn) gu[j] -= acc;
-            }
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                double acc = aff[i];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) acc -= bn[i * 3 + j] * du[j] + bp[i * 3 + j] * dnuu[j];
-                aff[i] = acc;
-            }
-        }
-        // ---- batch 7: the node's rho, D, e ----
-        {
-            double rho[7], dd[7], ee[7];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) { rho[i] = ns[NS_RHO + i]; dd[i] = ns[NS_D + i]; ee[i] = ns[NS_E + i]; }
-            CHUNK_END
+            for (int i = 0; i < 7; ++i) { out[i] = dnx[i] - sg[i] * dtf - dnu[i]; vec[i] = -dx[i]; }
             if (dyn) {
                 double sl = 0.0;
 #pragma unroll
                 for (int i = 0; i < 7; ++i) {
                     rec[R_RHO + i] = rho[i] + dd[i] * dnu[i] - lt[i];
-                    rec[R_AFF + i] = -ee[i] - aff[i];
                     sl += sg[i] * lt[i];
                 }
-                gtf_part -= sl;
+                // (node k's sum goes where it went with one lane per node: into partial sum k mod 64, pass after pass)
+                if (k0 & 32) gtf_odd -= sl; else gtf_even -= sl;
             }
         }
-        if (term) {
-            // terminal-node completion: the rank-1 terms and the AL shift; its rho / aff slots are zero as in the first record
-            for (int t = 0; t < NTERM; ++t) {
+        // ---- batches 3, 4: A in two halves of rows (half 1: of columns); the sums run over them in order, across the halves ----
+        {
+            const auto A = s.At(dyn ? k : 0);
+            const int ra = h0 ? 7 : 1, rb = h0 ? 1 : 7;      // field of the product's entry (a, b): A[a][b] / A[b][a]
 #pragma unroll
-                for (int i = 0; i < 7; ++i) gx[i] += gin[t] * sd.ta[t][i];
+            for (int h = 0; h < 2; ++h) {
+                const int r0 = h ? 4 : 0, r1 = h ? 7 : 4;
+                double am[28];
+#pragma unroll
+                for (int a = r0; a < r1; ++a)
+#pragma unroll
+                    for (int b = 0; b < 7; ++b) am[(a - r0) * 7 + b] = A[a * ra + b * rb];
+                CHUNK_END
+#pragma unroll
+                for (int a = r0; a < r1; ++a)
+#pragma unroll
+                    for (int b = 0; b < 7; ++b) out[b] += am[(a - r0) * 7 + b] * vec[a];
+            }
+        }
+        if (h0) {
+            if (dyn && hp) {
+#pragma unroll
+                for (int j = 0; j < 7; ++j) gx[j] -= out[j];
+            }
+            if (term) {
+                // terminal-node completion: the rank-1 terms and the AL shift
+                for (int t = 0; t < NTERM; ++t) {
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) gx[i] += gin[t] * sd.ta[t][i];
+                }
+#pragma unroll
+                for (int i = 0; i < 7; ++i) gx[i] -= sd.gam * rvt_x * sd.avt[i];
             }
 #pragma unroll
-            for (int i = 0; i < 7; ++i) gx[i] -= sd.gam * rvt_x * sd.avt[i];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) { rec[R_RHO + i] = 0.0; rec[R_AFF + i] = 0.0; }
+            for (int i = 0; i < 7; ++i) rec[R_GX + i] = gx[i];
         }
+        // ---- batch 5: B_kn; B_kp of the interval before (half 0) / of this interval (half 1); half 1: the node's e ----
+        {
+            double bn[21], bp[21], ee[7];
+            const auto Bn = s.Bnt(dyn ? k : 0), Bp = s.Bpt(h0 ? (hp ? k - 1 : 0) : (dyn ? k : 0));
 #pragma unroll
-        for (int i = 0; i < 7; ++i) rec[R_GX + i] = gx[i];
+            for (int e = 0; e < 21; ++e) { bn[e] = Bn[e]; bp[e] = Bp[e]; }
+            if (!h0) {
+                const auto ns = s.nsn(k);
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rec[R_GU + i] = gu[i];
+                for (int i = 0; i < 7; ++i) ee[i] = ns[NS_E + i];
+            }
+            CHUNK_END
+            if (h0) {
+                const double *ltm = q0;
+                if (hp) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        double acc = 0.0;
+#pragma unroll
+                        for (int i = 0; i < 7; ++i) acc += bp[i * 3 + j] * ltm[i];
+                        gu[j] -= acc;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) acc += bn[i * 3 + j] * lt[i];
+                    if (dyn) gu[j] -= acc;
+                }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) rec[R_GU + i] = gu[i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 7; ++i) {
+                    double acc = out[i];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) acc -= bn[i * 3 + j] * du[j] + bp[i * 3 + j] * dnuu[j];
+                    if (dyn) rec[R_AFF + i] = -ee[i] - acc;
+                }
+                if (term) {
+                    // the terminal node's rho / aff slots are zero as in the first record
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) { rec[R_RHO + i] = 0.0; rec[R_AFF + i] = 0.0; }
+                }
+            }
+        }
       }
       WG_SYNC();
       {
-          const int nr = ((K - k0 < 64) ? K - k0 : 64) * RHS_N;
+          const int nr = ((K - k0 < 32) ? K - k0 : 32) * RHS_N;
           wf64 *ch = s.ch + (size_t)k0 * CH_N + C_RHS;
-          for (int e = lane; e < nr; e += 64) { const int kl = e / RHS_N, i = e - kl * RHS_N; ch[(size_t)kl * CH_N + i] = stg[kl * RHS_LD + i]; }
+          for (int e = lane; e < nr; e += 64) { const int kr = e / RHS_N, i = e - kr * RHS_N; ch[(size_t)kr * CH_N + i] = stg[kr * RHS_LD + i]; }
       }
       WG_SYNC();
     }
-    sd.rs_gtf = sd.gtf + sd.Wtf * dtf + wave_sum(gtf_part);
+    // the 64 partial sums one lane per node kept, lane l that of the nodes k = l mod 64: the even passes' of half 1 belong to the
+    // lanes of half 0; the fold over the 64 lanes is the same
+    const double gtf_below = __shfl_xor(gtf_even, 32, 64);
+    const double gtf_lane = h0 ? gtf_below : gtf_odd;
+    sd.rs_gtf = sd.gtf + sd.Wtf * dtf + wave_sum(gtf_lane);
     sd.rs_rvt = rvt_rhs;
 #pragma unroll
     for (int t = 0; t < NTERM; ++t) sd.rs_gex[t] = gex[t];

@@ -1232,13 +1232,18 @@ __device__ __noinline__ void border_solve(SatData &sd, int lane)
     const double gtf_rhs = sd.rs_gtf, rvt_rhs = sd.rs_rvt;
     const double *gex = sd.rs_gex;
     double rb[NBD], x[NBD], r[NBD];
-#pragma unroll
-    for (int p = 0; p < NBD - 1; ++p) {
-        const double *a = (p == 0) ? sd.avt : sd.ta[p - 1];
+    {
+        // Row p's a . x_K on lane p, read off that lane by all (scalar registers).  Formed in every lane the six rows were 42 LDS
+        // operands at the head of a function that also holds the factors and the matrix, 170 doubles for 256 registers: eleven
+        // 16-byte spills and their reloads, each behind a full wait, in every call (profiles/refine_two_lane.txt).
+        const int pl = (lane < NBD - 1) ? lane : 0;
+        const double *a = (pl == 0) ? sd.avt : sd.ta[pl - 1];
         double acc = 0.0;
 #pragma unroll
         for (int l = 0; l < 7; ++l) acc += a[l] * sd.xK[0][l];
-        rb[p] = -acc;
+        const double nacc = -acc;
+#pragma unroll
+        for (int p = 0; p < NBD - 1; ++p) rb[p] = lane_value(nacc, p);
     }
     rb[0] += rvt_rhs;
     double iw[NBD - 1];
